@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the alignment -> structure hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cpu-baseline full|sample|none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--cpu-baseline full|sample|none]]
 
 A "step" is one batch of complete predictions (features, sequence trunk, 11 pair-trunk passes with
 recycling, MDS, coordinate GRU, 2 x 100 minimiser steps, backbone) of synthetic targets of
@@ -13,8 +13,15 @@ collective, only the timing barrier.  `--gpus N` with N > 1 starts the N ranks i
 (torch.distributed.run on 127.0.0.1) unless the process already runs under a launcher
 (RANK / WORLD_SIZE in the environment, as the driver's command line does).
 
-Three arithmetic settings of the same workload and scheduler are measured, each with its own warm-up and its own
-HIP-event intervals around every convolution launch (recorded on the launching streams):
+A plain run measures the headline leg only: set-up, `--warmup` untimed steps, exactly `--steps` timed steps, the result
+line (`value`, `ms_per_step` = milliseconds of one timed step, `roofline` from the HIP events of those steps).
+`--dump-outputs DIR` writes what the timed path returned for the targets of its last timed step (rank 0):
+DIR/coords.npy (targets, L, 5, 3) and DIR/confs.npy (targets, L), float32.  The inputs depend on the arguments only
+(synthetic seeds), so two builds can be compared output for output.  `--full` adds everything below - the two
+secondary legs, the verification, the single-target latency, the files leg and the CPU baseline.
+
+Three arithmetic settings of the same workload and scheduler are measured (`--full`), each with its own warm-up and its
+own HIP-event intervals around every convolution launch (recorded on the launching streams):
   * `value` / `roofline` / `dtype` - THE HEADLINE: option "precision" 2, full-width operands at the 16-bit matrix cores'
     rate.  Every float32 operand of the convolutions is split EXACTLY into three bf16 pieces (3 x 8 = the 24 significand
     bits of a float32), the six piece products above 2^-24 are accumulated in float32 (conv5x5_bf16x6_kernel), and the
@@ -30,6 +37,7 @@ HIP-event intervals around every convolution launch (recorded on the launching s
   headline, not instead of it.
 Rank 0 prints ONE JSON line with all three, a verification of the outputs against the reference's golden vectors for
 this configuration in every setting (`verify`), and (N = 1 only) the CPU oracle timed on this host (`cpu_baseline`).
+Without `--full`, `verify` holds only the finiteness of the outputs.
 """
 import argparse
 import ctypes as C
@@ -259,6 +267,41 @@ def interval_union(iv):
     return tot
 
 
+def make_targets(seeds, L, N):
+    """encode_aln(synth_msa(L, N, seed)) per seed, on a pool of host threads (the Philox draws and the encoding release
+    the GIL; one target alone takes ~25 ms, and a plain run builds (warmup + steps) x batch of them before the clock)"""
+    from concurrent.futures import ThreadPoolExecutor
+    from dmpfold2_amd import synth
+    from dmpfold2_amd.predict import encode_aln
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except AttributeError:
+        ncpu = os.cpu_count() or 1
+    with ThreadPoolExecutor(max(1, min(16, ncpu))) as ex:
+        return list(ex.map(lambda s: encode_aln(synth.synth_msa(L, N, seed=s)), seeds))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outs, first_index):
+    """--dump-outputs: the (coords, confs) the timed path returned for its last step's targets as float32 .npy files,
+    plus target_index.npy (float64: each dumped target's number in the run's target sequence).  Past 64 MB a fixed
+    sample of the targets (Philox key 0) is written instead."""
+    import numpy as np
+    coords = np.stack([c.detach().cpu().numpy() for c, _ in outs]).astype(np.float32)
+    confs = np.stack([f.detach().cpu().numpy() for _, f in outs]).astype(np.float32)
+    idx = np.arange(len(outs))
+    per_target = coords[0].nbytes + confs[0].nbytes + 8 if len(outs) else 0
+    if per_target * len(outs) > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // per_target
+        idx = np.sort(np.random.Generator(np.random.Philox(key=0)).choice(len(outs), size=k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "coords.npy"), coords[idx])
+    np.save(os.path.join(out_dir, "confs.npy"), confs[idx])
+    np.save(os.path.join(out_dir, "target_index.npy"), (first_index + idx).astype(np.float64))
+
+
 def thread_cpu_snapshot():
     """CPU seconds of every thread of this process: {tid: (name, utime + stime)} from /proc (who burns the host CPU the
     process reports: the scheduler thread inside the library, or the HIP runtime's own)."""
@@ -346,11 +389,18 @@ def main(argv=None):
                     help="targets in flight per GPU (one context + HIP stream each)")
     ap.add_argument("--batch", type=int, default=0,
                     help="targets per step and GPU (default 2 x streams)")
-    ap.add_argument("--cpu-baseline", choices=("full", "sample", "none"), default="full")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the two secondary arithmetic legs, the verification against the stored "
+                         "digests and reference goldens, single-target latency, host work per target, the files leg and "
+                         "the CPU baseline (a plain run does the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the coordinates and confidences of the last timed step's targets to DIR/*.npy")
+    ap.add_argument("--cpu-baseline", choices=("full", "sample", "none"), default="full", help="(--full)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     ap.add_argument("--no-exact-f32", "--headline-only", dest="headline_only", action="store_true",
-                    help="skip the two secondary arithmetic legs (precision 1 and 0)")
-    ap.add_argument("--no-files-leg", action="store_true", help="skip the alignment files -> PDB files measurement (N = 1)")
+                    help="(--full) skip the two secondary arithmetic legs (precision 1 and 0)")
+    ap.add_argument("--no-files-leg", action="store_true",
+                    help="(--full) skip the alignment files -> PDB files measurement (N = 1)")
     ap.add_argument("--legs", choices=("all",) + tuple(LEGS), default="all",
                     help="profiling: run ONE arithmetic leg only, with the full --steps (no verification or latency extras, "
                          "so that a kernel-stats table of the run holds that leg's launches only)")
@@ -410,10 +460,7 @@ def main(argv=None):
     # B synthetic targets per step and rank, all resident in HBM before the clock starts
     B = args.batch if args.batch > 0 else 2 * S
     total = (args.warmup + args.steps) * B
-    targets = []
-    for i in range(total):
-        rows = synth.synth_msa(L_NS, N_NS, seed=100000 * rank + i)
-        targets.append(torch.from_numpy(encode_aln(rows)).to(device))
+    targets = [torch.from_numpy(a).to(device) for a in make_targets([100000 * rank + i for i in range(total)], L_NS, N_NS)]
 
     def sync_all():
         torch.cuda.synchronize(device)
@@ -521,6 +568,8 @@ def main(argv=None):
     # ---- a single leg alone (profiling): its numbers under the leg's own keys, nothing else is measured
     if args.legs != "all":
         r = timed_leg(args.legs, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0 and args.steps > 0:
+            dump_outputs(args.dump_outputs, r["timed"][-B:], (args.warmup + args.steps - 1) * B)
         if distributed:
             t = torch.tensor([r["elapsed"]], dtype=torch.float64, device=red_device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -538,11 +587,13 @@ def main(argv=None):
             dist.destroy_process_group()
         return 0
 
-    # ---- the headline leg, then the two secondary ones at a quarter of the steps
+    # ---- the headline leg, then (--full) the two secondary ones at a quarter of the steps
     res = {HEADLINE: timed_leg(HEADLINE, args.steps, args.warmup)}
     ok = res[HEADLINE]["finite"]
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, res[HEADLINE]["timed"][-B:], (args.warmup + args.steps - 1) * B)
     k2, w2 = max(2, args.steps // 4), min(1, args.warmup)
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         for name in LEGS:
             if name != HEADLINE:
                 res[name] = timed_leg(name, min(k2, args.steps), w2)
@@ -551,134 +602,135 @@ def main(argv=None):
 
     # ---- verification of the outputs (untimed) ---------------------------------------------------
     verify = {"finite_outputs": ok}
-    first = args.warmup * B                                   # first target of the headline leg's timed region
-    es = Engine(device, L_NS, N_NS)                           # an engine of its own, with the pipeline's packed weights
-    es.share_weights(pipe.engines[0])
-    if per_row:
-        es.set_option("vgru_persistent", 0)
     single, t0_out = {}, {}
-    try:
-        for name, r in res.items():
-            prec, sfx = LEGS[name]["precision"], LEGS[name]["sfx"]
-            es.set_option("precision", prec)
-            # (1) the scheduler's result of the leg's first timed target == the same target alone on one engine, bit for
-            #     bit.  The bits are compared with the scheduler's kernels selected (its engines tridiagonalise with one
-            #     launch per Householder step; the cluster launch of a lone engine is the same algorithm with its float64
-            #     sums associated differently - the same bits on almost every matrix, not on all)
-            es.set_option("tridiag_cluster", 0)
-            lo = (r["warmup"]) * B
-            c1, f1 = es.predict_device(targets[lo], None, ITERS, MINSTEPS)
-            es.sync_check()
-            same = bool(torch.equal(c1, r["timed"][0][0]) and torch.equal(f1, r["timed"][0][1]))
-            verify["timed_target_bitwise_equals_single_engine" + sfx] = same
-            ok = ok and same
-            if rank != 0:
-                continue
-            # (2) digest of bench target 0 (seed 0, the full 10 + 100 prediction, alone on one engine - the same bits the
-            #     scheduler delivers, by (1)) against the stored one (profiles/bench_digest.json, written by
-            #     DMP_WRITE_DIGEST=1); the results are bit-reproducible, so a change means the arithmetic changed.
-            c0, f0 = es.predict_device(targets[0], None, ITERS, MINSTEPS)
-            es.sync_check()
-            t0_out[name] = (c0.clone(), f0.clone())
-            digest = hashlib.sha256(c0.cpu().numpy().tobytes() + f0.cpu().numpy().tobytes()).hexdigest()
-            dpath = os.path.join(ROOT, "profiles", "bench_digest.json")
-            key = f"L{L_NS}_N{N_NS}_n{ITERS}_m{MINSTEPS}_seed0" + ("" if prec == 0 else f"_precision{prec}")
-            if not es.get_option("vgru_persistent"):         # the launch-per-row chain sums K in another order: its own bits
-                key += "_vgru_per_row"
-            stored = {}
-            if os.path.exists(dpath):
-                try:
-                    stored = json.load(open(dpath))
-                except Exception:
-                    stored = {}
-            if os.environ.get("DMP_WRITE_DIGEST") == "1":
-                stored[key] = digest
-                json.dump(stored, open(dpath, "w"), indent=1, sort_keys=True)
-            match = (stored.get(key) == digest) if key in stored else None
-            verify["digest" + sfx] = {"sha256": digest, "expected": stored.get(key), "match": match}
-            if match is False:                               # the arithmetic changed: not a valid run
-                ok = False
-            # (3) bench target 0 (seed 0) at iterations=1, minsteps=0 against the vector captured from the reference
-            #     itself at this size (tests/golden/synth_L300_N2000_n1_m0.npz; data only)
-            gpath = os.path.join(ROOT, "tests", "golden", "synth_L300_N2000_n1_m0.npz")
-            if os.path.exists(gpath):
-                g = np.load(gpath)
-                sha = hashlib.sha256(targets[0].cpu().numpy().tobytes()).hexdigest()
-                gc, gf = es.predict_device(targets[0], None, 1, 0)
+    if args.full:
+        first = args.warmup * B                                   # first target of the headline leg's timed region
+        es = Engine(device, L_NS, N_NS)                           # an engine of its own, with the pipeline's packed weights
+        es.share_weights(pipe.engines[0])
+        if per_row:
+            es.set_option("vgru_persistent", 0)
+        try:
+            for name, r in res.items():
+                prec, sfx = LEGS[name]["precision"], LEGS[name]["sfx"]
+                es.set_option("precision", prec)
+                # (1) the scheduler's result of the leg's first timed target == the same target alone on one engine, bit for
+                #     bit.  The bits are compared with the scheduler's kernels selected (its engines tridiagonalise with one
+                #     launch per Householder step; the cluster launch of a lone engine is the same algorithm with its float64
+                #     sums associated differently - the same bits on almost every matrix, not on all)
+                es.set_option("tridiag_cluster", 0)
+                lo = (r["warmup"]) * B
+                c1, f1 = es.predict_device(targets[lo], None, ITERS, MINSTEPS)
                 es.sync_check()
-                d = gc.cpu().numpy()[:, 1].astype(np.float64) - g["coords"][:, 1].astype(np.float64)
-                rmsd = float(np.sqrt((d ** 2).sum(-1).mean()))
-                dconf = float(np.abs(gf.cpu().numpy() - g["confs"]).max())
-                same_input = sha == bytes(g["alnmat_sha256"]).decode()
-                verify["reference_golden_L300_N2000_n1_m0" + sfx] = {
-                    "ca_rmsd_A": rmsd, "max_dconf": dconf, "same_input": same_input,
-                    "ok": bool(same_input and rmsd <= 1e-3 and dconf < 1e-4)}
-                ok = ok and verify["reference_golden_L300_N2000_n1_m0" + sfx]["ok"]
-            # ---- latency of ONE prediction of the same configuration (the reference's use case: one CLI call; the
-            #      scheduler above is the throughput mode), with the lone engine's cluster tridiagonalisation.
-            es.set_option("tridiag_cluster", 1)
-            ts = []
-            for _ in range(4):
-                torch.cuda.synchronize(device)
-                t = time.perf_counter()
-                es.predict_device(targets[lo], None, ITERS, MINSTEPS)
+                same = bool(torch.equal(c1, r["timed"][0][0]) and torch.equal(f1, r["timed"][0][1]))
+                verify["timed_target_bitwise_equals_single_engine" + sfx] = same
+                ok = ok and same
+                if rank != 0:
+                    continue
+                # (2) digest of bench target 0 (seed 0, the full 10 + 100 prediction, alone on one engine - the same bits the
+                #     scheduler delivers, by (1)) against the stored one (profiles/bench_digest.json, written by
+                #     DMP_WRITE_DIGEST=1); the results are bit-reproducible, so a change means the arithmetic changed.
+                c0, f0 = es.predict_device(targets[0], None, ITERS, MINSTEPS)
                 es.sync_check()
-                ts.append((time.perf_counter() - t) * 1e3)
-            single[name] = {"ms": min(ts[1:]), "runs_ms": ts}
-    finally:
-        es.close()
-    if rank == 0:
-        # (4) THE METRIC'S CONFIGURATION ITSELF against the reference, in every arithmetic setting: 10 + 100 on the weight
-        #     sets on which the reference is stable there (coord_fc fitted to a protein-like trace, MDS feedback
-        #     attenuated): tests/golden/fitns_*.npz and (round 6: other alignment, weight and trace seeds) fitns2_*.npz hold
-        #     the reference's output, its thread-count floor and the fitted matrix; data only.  Own engine: the
-        #     pipeline's weights stay untouched.
-        for gname in ("fitns_L300_N2000_n10_m100", "fitns2_L300_N2000_n10_m100"):
-            gpath = os.path.join(ROOT, "tests", "golden", gname + ".npz")
-            if not os.path.exists(gpath):
-                continue
-            g = np.load(gpath)
-            wseed = int(g["weights_seed"]) if "weights_seed" in g else 0
-            mseed = int(g["msa_seed"])
-            sdh = synth.headline_fixture_weights(g["coord_fc"], float(g["coord_gru_mds_scale"]), seed=wseed)
-            msa_h = targets[0] if mseed == 0 else torch.from_numpy(encode_aln(synth.synth_msa(L_NS, N_NS, mseed))).to(device)
-            eh = Engine(device, L_NS, N_NS)
-            if per_row:
-                eh.set_option("vgru_persistent", 0)        # (two processes on this GPU: see above)
-            try:
-                eh.set_weights({k: torch.from_numpy(np.array(v)) for k, v in sdh.items()})
-                same = (hashlib.sha256(msa_h.cpu().numpy().tobytes()).hexdigest() == bytes(g["alnmat_sha256"]).decode()
-                        and synth.weights_checksum(sdh) == bytes(g["weights_sha256"]).decode())
-                floor = float(g["noise_ca_rmsd"])
-                for name in res:
-                    eh.set_option("precision", LEGS[name]["precision"])
-                    gc, gf = eh.predict_device(msa_h, None, ITERS, MINSTEPS)
-                    eh.sync_check()
+                t0_out[name] = (c0.clone(), f0.clone())
+                digest = hashlib.sha256(c0.cpu().numpy().tobytes() + f0.cpu().numpy().tobytes()).hexdigest()
+                dpath = os.path.join(ROOT, "profiles", "bench_digest.json")
+                key = f"L{L_NS}_N{N_NS}_n{ITERS}_m{MINSTEPS}_seed0" + ("" if prec == 0 else f"_precision{prec}")
+                if not es.get_option("vgru_persistent"):         # the launch-per-row chain sums K in another order: its own bits
+                    key += "_vgru_per_row"
+                stored = {}
+                if os.path.exists(dpath):
+                    try:
+                        stored = json.load(open(dpath))
+                    except Exception:
+                        stored = {}
+                if os.environ.get("DMP_WRITE_DIGEST") == "1":
+                    stored[key] = digest
+                    json.dump(stored, open(dpath, "w"), indent=1, sort_keys=True)
+                match = (stored.get(key) == digest) if key in stored else None
+                verify["digest" + sfx] = {"sha256": digest, "expected": stored.get(key), "match": match}
+                if match is False:                               # the arithmetic changed: not a valid run
+                    ok = False
+                # (3) bench target 0 (seed 0) at iterations=1, minsteps=0 against the vector captured from the reference
+                #     itself at this size (tests/golden/synth_L300_N2000_n1_m0.npz; data only)
+                gpath = os.path.join(ROOT, "tests", "golden", "synth_L300_N2000_n1_m0.npz")
+                if os.path.exists(gpath):
+                    g = np.load(gpath)
+                    sha = hashlib.sha256(targets[0].cpu().numpy().tobytes()).hexdigest()
+                    gc, gf = es.predict_device(targets[0], None, 1, 0)
+                    es.sync_check()
                     d = gc.cpu().numpy()[:, 1].astype(np.float64) - g["coords"][:, 1].astype(np.float64)
                     rmsd = float(np.sqrt((d ** 2).sum(-1).mean()))
                     dconf = float(np.abs(gf.cpu().numpy() - g["confs"]).max())
-                    v = {"ca_rmsd_A": rmsd, "max_dconf": dconf, "reference_thread_noise_A": floor, "same_input": bool(same),
-                         "ok": bool(same and rmsd <= max(1e-3, 3.0 * floor) and dconf < 1e-4)}
-                    verify["reference_golden_" + gname[:gname.index("_")] + "_L300_N2000_n10_m100" + LEGS[name]["sfx"]] = v
-                    ok = ok and v["ok"]
-            finally:
-                eh.close()
-        for name in t0_out:
-            if name == HEADLINE:
-                continue
-            a, b = t0_out[HEADLINE], t0_out[name]
-            d = (a[0][:, 1].double() - b[0][:, 1].double())
-            verify["headline_vs%s_bench_target_0" % LEGS[name]["sfx"]] = {
-                "ca_rmsd_A": float((d ** 2).sum(-1).mean().sqrt()),
-                "max_dconf": float((a[1] - b[1]).abs().max()),
-                "note": "two arithmetic settings on the same target (10 + 100 on random weights: the minimiser on a "
-                        "collapsed trace amplifies rounding differences, as the reference's own runs do; informational)"}
+                    same_input = sha == bytes(g["alnmat_sha256"]).decode()
+                    verify["reference_golden_L300_N2000_n1_m0" + sfx] = {
+                        "ca_rmsd_A": rmsd, "max_dconf": dconf, "same_input": same_input,
+                        "ok": bool(same_input and rmsd <= 1e-3 and dconf < 1e-4)}
+                    ok = ok and verify["reference_golden_L300_N2000_n1_m0" + sfx]["ok"]
+                # ---- latency of ONE prediction of the same configuration (the reference's use case: one CLI call; the
+                #      scheduler above is the throughput mode), with the lone engine's cluster tridiagonalisation.
+                es.set_option("tridiag_cluster", 1)
+                ts = []
+                for _ in range(4):
+                    torch.cuda.synchronize(device)
+                    t = time.perf_counter()
+                    es.predict_device(targets[lo], None, ITERS, MINSTEPS)
+                    es.sync_check()
+                    ts.append((time.perf_counter() - t) * 1e3)
+                single[name] = {"ms": min(ts[1:]), "runs_ms": ts}
+        finally:
+            es.close()
+        if rank == 0:
+            # (4) THE METRIC'S CONFIGURATION ITSELF against the reference, in every arithmetic setting: 10 + 100 on the weight
+            #     sets on which the reference is stable there (coord_fc fitted to a protein-like trace, MDS feedback
+            #     attenuated): tests/golden/fitns_*.npz and (round 6: other alignment, weight and trace seeds) fitns2_*.npz hold
+            #     the reference's output, its thread-count floor and the fitted matrix; data only.  Own engine: the
+            #     pipeline's weights stay untouched.
+            for gname in ("fitns_L300_N2000_n10_m100", "fitns2_L300_N2000_n10_m100"):
+                gpath = os.path.join(ROOT, "tests", "golden", gname + ".npz")
+                if not os.path.exists(gpath):
+                    continue
+                g = np.load(gpath)
+                wseed = int(g["weights_seed"]) if "weights_seed" in g else 0
+                mseed = int(g["msa_seed"])
+                sdh = synth.headline_fixture_weights(g["coord_fc"], float(g["coord_gru_mds_scale"]), seed=wseed)
+                msa_h = targets[0] if mseed == 0 else torch.from_numpy(encode_aln(synth.synth_msa(L_NS, N_NS, mseed))).to(device)
+                eh = Engine(device, L_NS, N_NS)
+                if per_row:
+                    eh.set_option("vgru_persistent", 0)        # (two processes on this GPU: see above)
+                try:
+                    eh.set_weights({k: torch.from_numpy(np.array(v)) for k, v in sdh.items()})
+                    same = (hashlib.sha256(msa_h.cpu().numpy().tobytes()).hexdigest() == bytes(g["alnmat_sha256"]).decode()
+                            and synth.weights_checksum(sdh) == bytes(g["weights_sha256"]).decode())
+                    floor = float(g["noise_ca_rmsd"])
+                    for name in res:
+                        eh.set_option("precision", LEGS[name]["precision"])
+                        gc, gf = eh.predict_device(msa_h, None, ITERS, MINSTEPS)
+                        eh.sync_check()
+                        d = gc.cpu().numpy()[:, 1].astype(np.float64) - g["coords"][:, 1].astype(np.float64)
+                        rmsd = float(np.sqrt((d ** 2).sum(-1).mean()))
+                        dconf = float(np.abs(gf.cpu().numpy() - g["confs"]).max())
+                        v = {"ca_rmsd_A": rmsd, "max_dconf": dconf, "reference_thread_noise_A": floor, "same_input": bool(same),
+                             "ok": bool(same and rmsd <= max(1e-3, 3.0 * floor) and dconf < 1e-4)}
+                        verify["reference_golden_" + gname[:gname.index("_")] + "_L300_N2000_n10_m100" + LEGS[name]["sfx"]] = v
+                        ok = ok and v["ok"]
+                finally:
+                    eh.close()
+            for name in t0_out:
+                if name == HEADLINE:
+                    continue
+                a, b = t0_out[HEADLINE], t0_out[name]
+                d = (a[0][:, 1].double() - b[0][:, 1].double())
+                verify["headline_vs%s_bench_target_0" % LEGS[name]["sfx"]] = {
+                    "ca_rmsd_A": float((d ** 2).sum(-1).mean().sqrt()),
+                    "max_dconf": float((a[1] - b[1]).abs().max()),
+                    "note": "two arithmetic settings on the same target (10 + 100 on random weights: the minimiser on a "
+                            "collapsed trace amplifies rounding differences, as the reference's own runs do; informational)"}
 
     # ---- host side of one aln_to_coords call (SURVEY 8d's unit of work; outside the timed region, whose
     #      inputs are resident in HBM): alignment file -> rows -> residue codes -> device, and the PDB text
     #      of a result brought back to the host.  Reported, never part of `value`.
     host = None
-    if rank == 0 and timed_outs:
+    if args.full and rank == 0 and timed_outs:
         import tempfile
         from dmpfold2_amd.predict import read_aln, pdb_text
         rows0 = synth.synth_msa(L_NS, N_NS, seed=0)
@@ -722,6 +774,7 @@ def main(argv=None):
             "ranks": ranks_seen,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": r["elapsed"] / r["steps"] * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -776,7 +829,7 @@ def main(argv=None):
         #      dmpfold2_amd.batch), same configuration and arithmetic as the headline, on a pipeline of its own that takes
         #      over the timed pipeline's streams.  Reported beside `value` (whose inputs are resident in HBM), never
         #      instead of it.
-        if world == 1 and not args.no_files_leg:
+        if args.full and world == 1 and not args.no_files_leg:
             import shutil
             import tempfile
             from dmpfold2_amd import batch
@@ -809,7 +862,7 @@ def main(argv=None):
                 else:
                     os.environ["DMPFOLD_PRECISION"] = keep
         mode = "none" if args.no_cpu_baseline else args.cpu_baseline
-        if world == 1 and mode != "none":
+        if args.full and world == 1 and mode != "none":
             line["cpu_baseline"] = cpu_baseline(mode)
             try:
                 line["cpu_baseline"]["all_host_threads"] = all_threads_probe(line["cpu_baseline"]["cores"])

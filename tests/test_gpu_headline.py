@@ -981,7 +981,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--streams", "2", "--cpu-baseline", "none", "--no-exact-f32"],
+                        "--streams", "2", "--full", "--cpu-baseline", "none", "--no-exact-f32"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1007,7 +1007,7 @@ def test_bench_under_the_drivers_launcher_over_rccl():
     env = dict(os.environ, DMP_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DMP_BENCH_SHARE_GPU"):
         env.pop(k, None)
-    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "1", "--warmup", "1", "--streams", "2",
+    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "1", "--warmup", "1", "--streams", "2", "--full",
                                    "--cpu-baseline", "none"], bench.free_port())
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -1017,3 +1017,46 @@ def test_bench_under_the_drivers_launcher_over_rccl():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["ranks"] == 1 and d["verify"]["ok"]
     assert d["value"] > 0 and d["value_f32"] > 0 and 0 < d["roofline_f32"]["frac"] < 1 and 0 < d["roofline"]["frac"] < 1
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path, synth_sd):
+    """`python bench.py --steps 2 --warmup 1 --dump-outputs DIR` without --full: the headline leg alone (no secondary legs,
+    verification, latency, files leg or CPU baseline), exactly two timed steps, and DIR holds the coordinates and
+    confidences of the last timed step's targets - the same bits one engine gives for the last of them in the headline
+    arithmetic with the scheduler's kernels."""
+    import json
+    import subprocess
+    import sys
+    from dmpfold2_amd import synth
+    from dmpfold2_amd.predict import encode_aln
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DMP_BENCH_SHARE_GPU", "DMP_FORCE_DIST"):
+        env.pop(k, None)
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--streams", "2", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False and d["verify"]["ok"]
+    assert d["unit"] == "structures/s" and d["higher_is_better"] is True and "precision = 2" in d["dtype"]
+    assert d["value"] > 0 and abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("value_f32", "value_split_f16", "single_target", "files_to_pdb", "cpu_baseline", "host_ms_per_target"):
+        assert k not in d, k
+    coords, confs = np.load(out / "coords.npy"), np.load(out / "confs.npy")
+    index = np.load(out / "target_index.npy")
+    assert coords.dtype == np.float32 and coords.shape == (4, 300, 5, 3) and np.isfinite(coords).all()
+    assert confs.dtype == np.float32 and confs.shape == (4, 300) and np.isfinite(confs).all()
+    assert index.dtype == np.float64 and index.tolist() == [8, 9, 10, 11]     # step 3 of 3 (warm-up 1 + 2 timed), 4 targets
+    eng = _engine(synth_sd, 300, 2000)
+    try:
+        eng.set_option("precision", 2)
+        eng.set_option("tridiag_cluster", 0)
+        msa = torch.from_numpy(encode_aln(synth.synth_msa(300, 2000, seed=11))).to("cuda:0")
+        c, f = eng.predict_device(msa, None, 10, 100)
+        eng.sync_check()
+        assert np.array_equal(c.cpu().numpy(), coords[-1]) and np.array_equal(f.cpu().numpy(), confs[-1])
+    finally:
+        eng.close()

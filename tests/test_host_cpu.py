@@ -302,6 +302,33 @@ def test_bench_launches_its_own_ranks_over_gloo():
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "4", "--steps", "1"]
 
 
+def test_bench_inputs_and_output_dump(tmp_path, monkeypatch):
+    """bench.py's targets built on a pool of host threads are the codes of synth_msa of their seeds, in seed order, and
+    --dump-outputs writes float32 coordinates / confidences of the targets it is given with their numbers (float64);
+    past the size limit a fixed sample of them, the same from run to run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    seeds = [0, 1, 100000, 100001, 7, 3]
+    for s, a in zip(seeds, bench.make_targets(seeds, 40, 64)):
+        assert np.array_equal(a, predict.encode_aln(synth.synth_msa(40, 64, seed=s))), s
+    outs = [(torch.full((12, 5, 3), float(i)), torch.full((12,), 0.5 * i)) for i in range(6)]
+    bench.dump_outputs(str(tmp_path / "all"), outs, 18)
+    c, f = np.load(tmp_path / "all" / "coords.npy"), np.load(tmp_path / "all" / "confs.npy")
+    ix = np.load(tmp_path / "all" / "target_index.npy")
+    assert c.dtype == np.float32 and c.shape == (6, 12, 5, 3) and (c[:, 3, 2, 1] == np.arange(6)).all()
+    assert f.dtype == np.float32 and f.shape == (6, 12) and (f[:, 0] == 0.5 * np.arange(6)).all()
+    assert ix.dtype == np.float64 and ix.tolist() == list(range(18, 24))
+    per_target = 12 * 5 * 3 * 4 + 12 * 4 + 8
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * per_target + 1)
+    picks = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs, 18)
+        c, ix = np.load(tmp_path / run / "coords.npy"), np.load(tmp_path / run / "target_index.npy")
+        assert c.shape == (3, 12, 5, 3) and (np.diff(ix) > 0).all() and (c[:, 0, 0, 0] + 18 == ix).all()
+        picks.append(ix.tolist())
+    assert picks[0] == picks[1]
+
+
 def test_north_star_golden_input_is_reproducible():
     """The L=300, N=2000 golden stores only a checksum of its alignment: the generator must give the
     same bytes here and on the GPU box."""

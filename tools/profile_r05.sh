@@ -27,7 +27,7 @@ f=$(find /tmp/single_prof -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && timeout 120 python $R/tools/single_trace.py analyse "$f" > $O/single_timeline.txt 2>&1
 timeout 300 python $R/tools/single_trace.py run 300 2000 10 100 6 > $O/single_run_noprof.txt 2>&1
 cd $R; timeout 600 python tools/lane_trace.py > $O/lane_trace.txt 2>&1
-timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 1500 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 timeout 600 python tools/time_vgru_persist.py 8 300 2000 > $O/vgru_persist.txt 2>&1
 VGRU_F32=1 timeout 600 python tools/time_vgru_persist.py 8 300 2000 > $O/vgru_f32.txt 2>&1
 timeout 600 python tools/time_inverse.py 300 500 1000 > $O/inverse.txt 2>&1

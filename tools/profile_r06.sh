@@ -22,7 +22,7 @@ for p in 2 0; do
 done
 cd $R
 DMPFOLD_PRECISION=2 timeout 600 python tools/lane_trace.py > $O/lane_trace_p2.txt 2>&1
-timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 1500 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 timeout 1500 python tools/bench_configs.py --skip-c5-f32 > $O/configs.jsonl 2> $O/configs.err
 VGRU_F32=1 timeout 600 python tools/time_vgru_persist.py 8 300 2000 > $O/vgru_f32.txt 2>&1
 VGRU_F32=2 timeout 600 python tools/time_vgru_persist.py 8 300 2000 > $O/vgru_x3.txt 2>&1
