@@ -1,4 +1,10 @@
-"""Thin helper for the GPU tests: call C-ABI stage functions with torch tensors."""
+"""Thin helper for the GPU tests: call C-ABI stage functions with torch tensors.
+
+Every output buffer is a view into an allocation filled with NaN and followed by a NaN guard tail of GUARD elements:
+an element the kernel does not write stays NaN and fails any `max |got - ref| <= tol` assertion, and a write past the
+end of the output spoils the guard, which `Stages.check_guards()` reports.  The header describes every output of these
+entry points as overwritten, not accumulated (e.g. include/dmpfold_hip.h: the backward outputs), so none is zero-filled.
+"""
 import ctypes as C
 
 import numpy as np
@@ -14,12 +20,38 @@ class Stages:
         self.eng.set_weights({k: torch.from_numpy(np.array(v)) for k, v in state_dict.items()})
         self.lib = self.eng.lib
         self.dev = self.eng.device
+        self._guards = []              # (allocation, elements of the output) since the last check_guards()
+        self._guard_bytes = 0
 
     def _s(self):
         return self.eng.stream()
 
+    GUARD = 4096                       # elements of NaN after every output
+    GUARD_PENDING_BYTES = 1 << 30      # outputs held for the guard check before one is made on the spot
+
+    def poisoned(self, shape, dtype=torch.float32):
+        """An output of `shape`: NaN, followed by a NaN guard tail of GUARD elements (checked by check_guards)."""
+        n = 1
+        for d in shape:
+            n *= int(d)
+        if self._guard_bytes > self.GUARD_PENDING_BYTES:
+            self.check_guards()        # bound the memory held by tests that never check
+        buf = torch.full((n + self.GUARD,), float("nan"), dtype=dtype, device=self.dev)
+        self._guards.append((buf, n))
+        self._guard_bytes += buf.numel() * buf.element_size()
+        return buf[:n].view(shape)
+
     def f32(self, *shape):
-        return torch.empty(shape, dtype=torch.float32, device=self.dev)
+        return self.poisoned(shape)
+
+    def check_guards(self):
+        """Wait for the queued work; every guard tail since the last check must still be NaN.  Forgets those guards."""
+        torch.cuda.synchronize(self.dev)
+        guards, self._guards, self._guard_bytes = self._guards, [], 0
+        for buf, n in guards:
+            tail = buf[n:]
+            bad = int((~torch.isnan(tail)).sum())
+            assert bad == 0, f"{bad} of the {tail.numel()} guard elements after an output of {n} elements were written"
 
     def to(self, a, dtype=torch.float32):
         return torch.as_tensor(np.ascontiguousarray(a)).to(dtype).to(self.dev).contiguous()
@@ -96,7 +128,7 @@ class Stages:
     def conv(self, block, x):
         L = x.shape[-1]
         u = self.f32(128, L, L)
-        st = torch.empty((128, 2), dtype=torch.float64, device=self.dev)
+        st = self.poisoned((128, 2), torch.float64)
         self.call("dmp_block_conv5x5_maxout", block, x, L, u, st)
         return u, st
 

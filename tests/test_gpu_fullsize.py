@@ -77,13 +77,12 @@ def test_ns_covariance_inverse_identity(ns, ns_msa):
     assert float((inv - inv.t()).abs().max()) <= 1e-4 * float(inv.abs().max())
 
 
-def test_ns_gru_vertical_vs_torch_gru(ns, ns_msa, synth_sd):
-    """2000 recurrent steps x 300 columns against the GRU recurrence (network.py:189; ATen
-    gru_cell: h' = (h - n) z + n) written out with float64 matmuls on the GPU."""
-    out = ns.gru_vertical(ns_msa)
-    W = {k: torch.from_numpy(np.array(v)).cuda().double() for k, v in synth_sd.items() if k.startswith(("vgru.", "embed."))}
+def _gru_recurrence(ns_msa, synth_sd, dtype):
+    """The vertical GRU (network.py:189; ATen gru_cell: h' = (h - n) z + n) written out with torch matmuls in `dtype` on
+    the GPU: the last row's hidden state of the second layer, (300, 512)."""
+    W = {k: torch.from_numpy(np.array(v)).cuda().to(dtype) for k, v in synth_sd.items() if k.startswith(("vgru.", "embed."))}
     codes = torch.from_numpy(ns_msa.astype(np.int64)).cuda()
-    h = [torch.zeros(300, 512, dtype=torch.float64, device="cuda") for _ in range(2)]
+    h = [torch.zeros(ns_msa.shape[1], 512, dtype=dtype, device="cuda") for _ in range(2)]
     for t in range(ns_msa.shape[0]):
         x = W["embed.weight"][codes[t]]
         for l in range(2):
@@ -94,7 +93,42 @@ def test_ns_gru_vertical_vs_torch_gru(ns, ns_msa, synth_sd):
             n = torch.tanh(gi[:, 1024:] + r * gh[:, 1024:])
             h[l] = (h[l] - n) * z + n
             x = h[l]
-    assert float((out.double() - h[1]).abs().max()) < 2e-5
+    return h[1].double()
+
+
+@pytest.fixture(scope="module")
+def ns_gru_refs(ns_msa, synth_sd):
+    """(float64 recurrence, distance of the same recurrence in float32 matmuls from it), once per module."""
+    h64 = _gru_recurrence(ns_msa, synth_sd, torch.float64)
+    tf32 = torch.backends.cuda.matmul.allow_tf32
+    torch.backends.cuda.matmul.allow_tf32 = False
+    try:
+        h32 = _gru_recurrence(ns_msa, synth_sd, torch.float32)
+    finally:
+        torch.backends.cuda.matmul.allow_tf32 = tf32
+    return h64, float((h32 - h64).abs().max())
+
+
+@pytest.mark.parametrize("form", [0, 1, 2])
+def test_ns_gru_vertical_vs_torch_gru(ns, ns_msa, ns_gru_refs, form):
+    """2000 recurrent steps x 300 columns - the headline's depth - against the GRU recurrence in float64 on the GPU, in
+    each form of the vertical GRU (option vgru_f32): 0 the split-f16 products, 1 float32 MFMAs (vgru_f32.hip), 2
+    full-width operands on the bf16 matrix cores (vgru_x3.hip, the headline).  The float32 forms are held to the
+    distance of a float32 evaluation of the same recurrence (torch matmuls, no TF32) from float64."""
+    h64, err_f32 = ns_gru_refs
+    ns.eng.set_option("vgru_f32", form)
+    try:
+        assert ns.eng.get_option("vgru_f32") == form
+        out = ns.gru_vertical(ns_msa)
+        ns.eng.sync_check()
+        err = float((out.double() - h64).abs().max())
+    finally:
+        ns.eng.set_option("vgru_f32", 0)
+    print(f"vertical GRU form {form}: max |dev| from float64 {err:.3e} (torch float32 {err_f32:.3e})")
+    if form == 0:
+        assert err < 2e-5
+    else:
+        assert err <= 2.0 * err_f32 + 1e-7, (err, err_f32)
 
 
 @pytest.mark.parametrize("mode", [0, 2])

@@ -34,12 +34,14 @@ CONV_MODES = {"f16x3": 0, "f32": 1, "bf16x6": 2}
 
 @pytest.fixture(params=list(CONV_MODES))
 def st(request, st_engine):
-    """Every test runs with each convolution path at the SAME tolerances: the default (float32
-    products from 2-way f16 splits, 3 MFMA products), the exact-f32 MFMA path, and the 3-way bf16
-    split (6 products)."""
-    st_engine.eng.set_option("conv_mode", CONV_MODES[request.param])
+    """Every test runs in each precision at the SAME tolerances, so with each convolution path: the fast mode (float32
+    products from 2-way f16 splits, 3 MFMA products; split-f16 vertical GRU), the exact-f32 MFMA path (float32 vertical
+    GRU, vgru_f32.hip), and the headline mode (3-way bf16 split, 6 products; vertical GRU on full-width bf16 operands,
+    vgru_x3.hip).  "conv_mode" alone would leave the vertical GRU in its split-f16 form (common.h: vgru_runs_f32)."""
+    st_engine.eng.set_option("precision", CONV_MODES[request.param])
     yield st_engine
-    st_engine.eng.set_option("conv_mode", 0)
+    st_engine.eng.set_option("precision", 0)
+    st_engine.check_guards()
     st_engine.eng.sync_check()
 
 
