@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import shard
-from .predict import (MAX_SEQS, Pipeline, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
+from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
                       pdb_text, read_a3m, read_aln, read_template_ca)
 
 
@@ -196,8 +196,11 @@ def cost_order(targets, iterations):
 
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
-              weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None):
+              weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
+              converge=None, stats_out=None):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
+    `converge` (Angstrom, None = off): targets stop recycling once converged (Pipeline.set_converge); `stats_out`, a
+    dict, then receives this rank's "passes_run" and "passes_saved".
 
     Which targets those are: with `store` (a torch.distributed key-value store shared by the ranks of the job) every
     rank takes the next most expensive target from ONE shared queue whenever it has room; without it the static
@@ -235,6 +238,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
             sd = state_dict if state_dict is not None else load_state_dict(weights_file)
             pipe = Pipeline(dev, max_L, max_N, sd, streams=streams, precision=drop_in_precision())
+            if converge is not None:
+                pipe.set_converge(converge)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -363,13 +368,16 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 outputs.append(write_result(out_dir, aln_path, res[t][0], res[t][1], alnmat, fmt))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
+        if stats_out is not None and converge is not None:
+            st = pipe.stats()
+            stats_out["passes_run"], stats_out["passes_saved"] = st["passes_run"], st["passes_saved"]
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
     return n_taken, elapsed, outputs
 
 
-def main(argv=None):
+def batch_parser():
     ap = argparse.ArgumentParser(description="DMPfold2 batch prediction on AMD MI355X (one process per GPU)")
     ap.add_argument("-l", "--list", default=None, help="text file: one alignment path (+ optional template) per line")
     ap.add_argument("-i", "--input", nargs="*", default=[],
@@ -383,6 +391,14 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=4, help="targets in flight per GPU")
     ap.add_argument("--static-shards", action="store_true",
                     help="several ranks: fixed partition by estimated cost instead of the shared work queue")
+    ap.add_argument("--converge", type=_tolerance_arg, default=None, metavar="TOL",
+                    help="stop a target's recycling once a pass changes its seed distance map by no more than TOL Angstrom "
+                         "(RMS); the summary then counts the passes run and saved")
+    return ap
+
+
+def main(argv=None):
+    ap = batch_parser()
     args = ap.parse_args(argv)
     if not args.list and not args.input:
         ap.error("give -l targets.txt and / or -i alignments ...")
@@ -403,10 +419,12 @@ def main(argv=None):
     targets = (read_target_list(args.list) if args.list else []) + expand_inputs(args.input)
     status, n_failed, broke = 0, 0, 0
     store = job_store if (world > 1 and not args.static_shards) else None
+    passes = {}
     try:
         n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                   weights_file=args.model_weights, streams=args.streams,
-                                  device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store)
+                                  device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
+                                  converge=args.converge, stats_out=passes)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -417,12 +435,16 @@ def main(argv=None):
         print(f"dmpfold-batch: rank {rank}: {type(exc).__name__}: {exc}", file=sys.stderr)
         n, elapsed, status, broke = 0, 0.0, 2, 1
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
+    if args.converge is not None:
+        passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
     if rank == 0:
         summary = {"targets": total, "seconds": tmax, "structures_per_s": total / tmax if tmax > 0 else 0.0,
                    "n_gpus": world, "failed_targets": failed_all, "failed_ranks": broke_all}
         if broke_all:
             summary["note"] = ("%d rank(s) broke down: the targets they had taken are missing from the output directory - "
                                "compare it with the target list" % broke_all)
+        if args.converge is not None:
+            summary["converge"], summary["passes_run"], summary["passes_saved"] = args.converge, passes_all[0], passes_all[1]
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

@@ -509,9 +509,17 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(best_mean, 1);
   A_(conf_means, c->max_passes);
   A_(ca_pass, (int64_t)c->max_passes * L * 3);
+  A_(delta_keep, 2 * L * 3);
+  A_(pass_delta, c->max_passes);
+  A_(delta_partial, 64);
+  A_(delta_counter, 1);
 #undef A_
   if (rc) { dmp_ctx_destroy(c); return rc; }
   if (hipMemset(c->seq_abort, 0, 2 * sizeof(int)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  if (hipMemset(c->delta_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  // the word recycle_delta tells the host its stop decision through (read only after the pass tail's event)
+  if (hipHostMalloc((void**)&c->delta_host, sizeof(int), hipHostMallocMapped) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  *c->delta_host = 0;
   if ((rc = trunk_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
   if ((rc = mds_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
   if ((rc = gj_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
@@ -568,6 +576,12 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->conv_mode = value;
     return DMP_OK;
   }
+  if (k == "recycle_tol_mA") {       // takes effect with the next prediction begun
+    DMP_ARG(value >= 0, "recycle_tol_mA must be >= 0 (milli-Angstrom; 0 = fixed depth), got %d", value);
+    ctx->recycle_tol_mA = value;
+    return DMP_OK;
+  }
+  DMP_ARG(k != "passes_run", "passes_run is read only");
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
 }
@@ -607,6 +621,8 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "gj_lookahead") { *h_value = ctx->gj_lookahead; return DMP_OK; }
   if (k == "gj_pairs") { *h_value = ctx->gj_pairs; return DMP_OK; }
   if (k == "gj_diag_blocked") { *h_value = ctx->gj_diag_blocked; return DMP_OK; }
+  if (k == "recycle_tol_mA") { *h_value = ctx->recycle_tol_mA; return DMP_OK; }
+  if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
 }
@@ -627,6 +643,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (!c) return;
   coresident_forget(c);
   if (c->bwd_ws) (void)hipFree(c->bwd_ws);
+  if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -971,6 +988,8 @@ int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d
   // begin_units + every front-end unit (the features on the context's side stream) + every unit of every pass + end
   int rc = predict_begin(ctx, d_msa, N, L, d_template_ca, Lt, nloops, refine_steps, stream);
   if (rc) return rc;
+  // (with "recycle_tol_mA" the issue call waits at every pass boundary from the second on for the pass tail's stop
+  // decision, and a stop shortens run_nloops: one host synchronisation per pass; with the option off, none)
   while (ctx->passes_done <= ctx->run_nloops)
     if ((rc = dmp_predict_issue_unit(ctx, stream))) return rc;
   return dmp_predict_end(ctx, d_coords, d_conf, stream);
@@ -983,6 +1002,32 @@ int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d
 // MDS, coordinate GRU, best-of update.
 static constexpr int FE_INV_BLOCKS = 6;    // Gauss-Jordan block steps per front-end unit
 static constexpr int FE_VGRU_STEPS = VGRU_CHUNK;  // vertical-GRU time steps per front-end unit (one graph replay)
+
+// Convergence stop (option "recycle_tol_mA"): the tail unit of pass p >= 1 left its decision in c->delta_host; it is read
+// at the boundary in front of unit 0 of pass p + 1, once that tail unit has completed.  Nothing has been issued since the
+// tail unit there, so its event is the newest of the unit ring.  Returns 1 = go on (decided, or nothing to decide),
+// 0 = the tail unit is still running (only with block = false), negative = error.  A stop ends the prediction as if
+// `iterations` had been p: run_nloops becomes p, dmp_predict_end's precondition holds.
+static int recycle_gate(dmp_ctx* c, bool block) {
+  if (c->run_tol_mA <= 0 || c->fe_next < c->fe_total || c->unit_next != 0) return 1;
+  const int pass = c->passes_done;
+  if (pass < 2 || pass > c->run_nloops || c->gate_pass == pass) return 1;
+  hipEvent_t tail = (hipEvent_t)c->unit_ev[(c->unit_seq - 1) & 1];
+  if (block) DMP_HIP(hipEventSynchronize(tail));
+  else {
+    const hipError_t e = hipEventQuery(tail);
+    if (e == hipErrorNotReady) return 0;
+    if (e != hipSuccess) return hip_fail(e, "hipEventQuery", __FILE__, __LINE__);
+  }
+  const int word = __atomic_load_n(c->delta_host, __ATOMIC_ACQUIRE);
+  if ((word >> 1) != pass) {
+    set_error("recycle_delta of pass %d left no record (word %d)", pass - 1, word);
+    return DMP_ERR_FAULT;
+  }
+  c->gate_pass = pass;
+  if (word & 1) c->run_nloops = pass - 1;
+  return 1;
+}
 
 static int record_unit(dmp_ctx* c, hipStream_t s) {
   DMP_HIP(hipEventRecord((hipEvent_t)c->unit_ev[c->unit_seq & 1], s));
@@ -1140,6 +1185,8 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   c->passes_done = 0;
   c->unit_next = 0;
   c->end_refined = false;
+  c->run_tol_mA = c->recycle_tol_mA;
+  c->gate_pass = 0;
   c->run_nloops = nloops < 0 ? 0 : nloops;
   c->run_refine = refine_steps < 0 ? 0 : refine_steps;
   c->run_msa = d_msa;
@@ -1251,6 +1298,8 @@ int dmp_predict_next_unit(const dmp_ctx* ctx) {
   if (ctx->fe_next == ctx->fe_total - 1 && ctx->vg_leader && ctx->vg_leader != ctx && !vg_done(ctx->vg_leader))
     return DMP_UNIT_WAIT;      // the group's chain has not been issued to its end yet
   if (ctx->fe_next < ctx->fe_total) return DMP_UNIT_LIGHT;
+  // a pass boundary with the convergence stop on: undecided until the pass tail has completed (event query, never blocks)
+  if (recycle_gate(const_cast<dmp_ctx*>(ctx), false) == 0) return DMP_UNIT_WAIT;
   if (ctx->passes_done > ctx->run_nloops) return DMP_UNIT_NONE;
   return (ctx->unit_next >= 1 && ctx->unit_next <= NBLOCK) ? DMP_UNIT_CONV : DMP_UNIT_LIGHT;
 }
@@ -1261,6 +1310,12 @@ int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream) {
   hipStream_t s = STREAM;
   if (c->fe_next < c->fe_total) return issue_front_end_unit(c, s);
   DMP_ARG(c->passes_done <= c->run_nloops, "all passes of this prediction were already issued");
+  {
+    // a caller that did not wait for dmp_predict_next_unit's answer (dmp_predict) waits here; on a stop nothing is issued
+    const int go = recycle_gate(c, true);
+    if (go < 0) return go;
+    if (c->passes_done > c->run_nloops) return DMP_OK;
+  }
   const int L = c->last_L, pass = c->passes_done, u = c->unit_next;
   int rc = DMP_OK;
   if (u == 0) {
@@ -1274,6 +1329,7 @@ int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream) {
     if (!rc) rc = coords_from_mds(c, c->mat1d, c->mds, L, c->ca, s);
     if (!rc && pass == 0 && c->run_refine > 0) rc = refine_coords(c, c->ca, L, c->run_refine, s);
     if (!rc) rc = select_best(c, c->conf, c->ca, L, pass, c->max_passes, s);
+    if (!rc && c->run_tol_mA > 0) rc = recycle_delta(c, c->ca, L, pass, c->max_passes, s);
   }
   if (rc) { c->xsplit_current = false; return rc; }
   if (u == NBLOCK + 1) { c->unit_next = 0; c->passes_done = pass + 1; }
@@ -1372,6 +1428,7 @@ int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t ca
   else if (k == "mat1d") { src = ctx->mat1d; n = WIDTH * L; }
   else if (k == "conf_means") { src = ctx->conf_means; n = P; }
   else if (k == "ca_pass") { src = ctx->ca_pass; n = P * L * 3; }
+  else if (k == "pass_delta") { src = ctx->pass_delta; n = ctx->run_tol_mA > 0 ? P : 0; }
   else if (k == "best_ca") { src = ctx->best_ca_snapshot; n = L * 3; }
   else if (k == "best_ca_refined") { src = ctx->best_ca; n = L * 3; }
   else if (k == "inv_cov") { src = ctx->cov; n = (int64_t)NS * L * NS * L; }

@@ -235,6 +235,15 @@ struct dmp_ctx {
   float* ca_pass = nullptr;    // [P][L][3]
   float* best_ca_snapshot = nullptr;
   int passes_done = 0;
+  // option "recycle_tol_mA": stop recycling once a pass moves the seed distance map by no more than this (RMS, mA; 0 = off)
+  int recycle_tol_mA = 0;
+  int run_tol_mA = 0;              // ... as the prediction in flight began with it
+  int gate_pass = 0;               // the boundary in front of this pass has been decided (recycle_gate, api.hip)
+  float* delta_keep = nullptr;     // [2][max_L][3] the trace each pass is compared with (coords.hip: recycle_delta)
+  float* pass_delta = nullptr;     // [P] d_p of every pass (+inf for pass 0)
+  double* delta_partial = nullptr; // [64] per-workgroup sums
+  unsigned* delta_counter = nullptr;
+  int* delta_host = nullptr;       // pinned host word the kernel writes: ((pass + 1) << 1) | stop
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -464,6 +473,7 @@ int pair_distances(const float* d_ca, int L, int clamp, float* d_dmap, hipStream
 int fill_f32(float* d, int64_t n, float v, hipStream_t s);
 int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int pass, int rec_cap,
                 hipStream_t s);
+int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, hipStream_t s);
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);

@@ -134,6 +134,110 @@ int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int p
 }
 
 // ---------------------------------------------------------------------------------------
+// recycle_delta (option "recycle_tol_mA"): how far did this pass move the trace?
+// ---------------------------------------------------------------------------------------
+// d_p = sqrt(mean over i < j of (D(ca_p)_ij - D(seed_p)_ij)^2), D(x)_ij = sqrt(max(|x_i - x_j|^2, 1e-8)): the RMS change
+// of the distance map the NEXT pass would be seeded with against the one THIS pass was seeded with (network.py:272 forms
+// that map from the trace; here both maps are formed on the fly from the two traces in LDS, 2 x 3L floats, no L^2
+// traffic).  Float64 throughout: at d = 1e-3 A the float32 rounding of two 30 A distances is a tenth of the value.
+// Rows i are dealt round robin to the workgroups, a row's partners j to the threads; every thread sums its pairs in a
+// fixed order, the workgroup's tree and the last arriver's loop over the partial sums are fixed too, so the value - and
+// with it the stop decision - has the same bits however the workgroups are scheduled.  Workgroup 0 keeps the trace for
+// the next pass's comparison (the two keep buffers alternate: nobody reads the one being written).  The last arriver
+// records d_p and tells the host: {pass + 1, stop} in one word of pinned host memory, an ordinary store - the route of
+// the pipeline's per-ticket fault words.
+constexpr int RD_THREADS = 256;
+constexpr int RD_MAX_WG = 64;
+
+__host__ __device__ inline int recycle_delta_groups(int L) {
+  const int g = L / 32;
+  return g < 1 ? 1 : (g > RD_MAX_WG ? RD_MAX_WG : g);
+}
+
+struct RecycleDeltaArgs {
+  const float* ca;       // [L][3] this pass's trace
+  const float* seed;     // [L][3] the trace whose distance map seeded this pass (null: pass 0, no delta)
+  float* keep;           // [L][3] <- ca
+  int L, pass, rec_cap;
+  float tol;             // A
+  float* pass_delta;     // [rec_cap]
+  double* partial;       // [RD_MAX_WG]
+  unsigned* counter;     // zero between launches
+  int* host_word;        // pinned: ((pass + 1) << 1) | stop
+};
+
+__global__ __launch_bounds__(RD_THREADS) void recycle_delta_kernel(RecycleDeltaArgs a) {
+  extern __shared__ float sm[];          // 2 x 3L coordinates
+  __shared__ double red[RD_THREADS];
+  const int L = a.L, tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+  if (g == 0)
+    for (int i = tid; i < 3 * L; i += RD_THREADS) a.keep[i] = a.ca[i];
+  if (!a.seed) {                         // pass 0 (one workgroup): nothing to compare with
+    if (tid == 0) {
+      if (a.pass < a.rec_cap) a.pass_delta[a.pass] = __builtin_inff();
+      *a.host_word = (a.pass + 1) << 1;
+    }
+    return;
+  }
+  float* xa = sm;
+  float* xb = sm + 3 * L;
+  for (int i = tid; i < 3 * L; i += RD_THREADS) { xa[i] = a.ca[i]; xb[i] = a.seed[i]; }
+  __syncthreads();
+  double acc = 0.0;
+  for (int i = g; i < L - 1; i += G) {
+    const double ax = xa[3 * i], ay = xa[3 * i + 1], az = xa[3 * i + 2];
+    const double bx = xb[3 * i], by = xb[3 * i + 1], bz = xb[3 * i + 2];
+    for (int j = i + 1 + tid; j < L; j += RD_THREADS) {
+      const double ux = (double)xa[3 * j] - ax, uy = (double)xa[3 * j + 1] - ay, uz = (double)xa[3 * j + 2] - az;
+      const double vx = (double)xb[3 * j] - bx, vy = (double)xb[3 * j + 1] - by, vz = (double)xb[3 * j + 2] - bz;
+      const double da = sqrt(fmax((ux * ux + uy * uy) + uz * uz, 1e-8));
+      const double db = sqrt(fmax((vx * vx + vy * vy) + vz * vz, 1e-8));
+      const double e = da - db;
+      acc += e * e;
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = RD_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.partial[g]), (unsigned long long)__double_as_longlong(red[0]),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned before = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (before == (unsigned)G - 1u) {          // the last arriver: every partial sum is behind its owner's release
+      double sum = 0.0;
+      for (int k = 0; k < G; ++k)
+        sum += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(&a.partial[k]),
+                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      const float d = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
+      if (a.pass < a.rec_cap) a.pass_delta[a.pass] = d;
+      const int stop = d <= a.tol ? 1 : 0;           // false for NaN
+      __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *a.host_word = ((a.pass + 1) << 1) | stop;
+    }
+  }
+}
+
+int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, hipStream_t s) {
+  RecycleDeltaArgs a{};
+  a.ca = d_ca;
+  a.seed = pass > 0 ? c->delta_keep + (int64_t)((pass - 1) & 1) * 3 * c->max_L : nullptr;
+  a.keep = c->delta_keep + (int64_t)(pass & 1) * 3 * c->max_L;
+  a.L = L; a.pass = pass; a.rec_cap = rec_cap;
+  a.tol = (float)c->run_tol_mA * 1e-3f;
+  a.pass_delta = c->pass_delta;
+  a.partial = c->delta_partial;
+  a.counter = c->delta_counter;
+  a.host_word = c->delta_host;
+  const int G = pass > 0 ? recycle_delta_groups(L) : 1;
+  hipLaunchKernelGGL(recycle_delta_kernel, dim3(G), dim3(RD_THREADS), pass > 0 ? sizeof(float) * 6 * L : 0, s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // refine_coords: all steps in one launch, coordinates double-buffered in LDS
 // ---------------------------------------------------------------------------------------
 // T threads share a residue j, each summing the steric term over a contiguous slice of the

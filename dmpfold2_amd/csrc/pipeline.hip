@@ -121,6 +121,7 @@ struct dmp_pipeline {
   std::vector<bool> fault_slot_used;
   std::atomic<long long> stat_rider_chains{0}, stat_max_riders{0}, stat_max_group{0}, stat_groups{0}, stat_idle_rounds{0};
   std::atomic<long long> stat_thread_cpu_us{0}, stat_rounds{0};
+  std::atomic<long long> stat_passes{0}, stat_early{0}, stat_saved{0};     // option "recycle_tol_mA": passes issued, stops, passes saved
 };
 
 namespace {
@@ -311,10 +312,19 @@ bool pump(dmp_pipeline* p) {
     hipStream_t st = p->stream[s];
     while (true) {
       const int kind = dmp_predict_next_unit(c);
-      if (kind == 3) break;                                 // waits for its group leader's vertical-GRU chain
+      // waits for its group leader's vertical-GRU chain - or, with "recycle_tol_mA", for its own pass tail's stop decision
+      if (kind == 3) break;
       int rc = DMP_OK;
       if (kind == 0) {
         // final refinement + backbone; neither needs the lane
+        {
+          // a prediction that converged ("recycle_tol_mA") ends here before its planned sl.total blocks; nothing else
+          // hangs on that count: the group-patience and stagger tests look at BUSY slots, and this one is free from here on
+          int passes = sl.job.nloops + 1;
+          dmp_ctx_get_option(c, "passes_run", &passes);
+          p->stat_passes += passes;
+          if (passes < sl.job.nloops + 1) { p->stat_early++; p->stat_saved += sl.job.nloops + 1 - passes; }
+        }
         int fslot = -1;
         hipEvent_t ev;
         {
@@ -664,9 +674,9 @@ int dmp_pipeline_stats(dmp_pipeline* p, long long* h_stats, int capacity) {
     std::lock_guard<std::mutex> g(p->mu);
     ahead_left = (long long)p->ahead.size() + (long long)p->riding.size();
   }
-  const long long v[8] = {p->stat_groups, p->stat_max_group, p->stat_rider_chains, p->stat_max_riders, ahead_left, p->stat_idle_rounds,
-                          p->stat_rounds, p->stat_thread_cpu_us};
-  for (int i = 0; i < capacity && i < 8; ++i) h_stats[i] = v[i];
+  const long long v[11] = {p->stat_groups, p->stat_max_group, p->stat_rider_chains, p->stat_max_riders, ahead_left, p->stat_idle_rounds,
+                           p->stat_rounds, p->stat_thread_cpu_us, p->stat_passes, p->stat_early, p->stat_saved};
+  for (int i = 0; i < capacity && i < 11; ++i) h_stats[i] = v[i];
   return DMP_OK;
 }
 

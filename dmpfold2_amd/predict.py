@@ -14,7 +14,9 @@ Differences from the reference, all additive or forced by the environment:
   * packed weights are cached per (device, weights file) instead of being rebuilt on
     every call (the reference constructs and loads a fresh network each time);
   * eigenvector signs of the MDS step follow a fixed rule (see include/dmpfold_hip.h);
-  * missing trained weights raise FileNotFoundError (no download: predict.py:64-71).
+  * missing trained weights raise FileNotFoundError (no download: predict.py:64-71);
+  * `converge` (Angstrom, None / 0 = off, the default): recycling stops after the first pass that moves the seed
+    distance map by no more than that (RMS); the result is then the one `iterations` = that pass would have given.
 """
 from __future__ import annotations
 
@@ -129,6 +131,27 @@ def load_state_dict(weights_file=None):
         # weights_only: a user-supplied -w file is data (a tensor dict), never unpickled code
         sd = torch.load(weights_file, map_location="cpu", weights_only=True)
     return sd
+
+
+def converge_to_mA(converge):
+    """The convergence tolerance of the Python / CLI boundary (Angstrom, float, None = off) as the C option's integer
+    number of milli-Angstrom ("recycle_tol_mA", include/dmpfold_hip.h).  Negative or non-finite values raise ValueError."""
+    if converge is None:
+        return 0
+    tol = float(converge)
+    if not (tol >= 0.0) or tol == float("inf"):
+        raise ValueError(f"converge must be a finite tolerance >= 0 (Angstrom), got {converge!r}")
+    return int(round(tol * 1000.0))
+
+
+def _tolerance_arg(text):
+    """argparse type of -c / --converge: a float >= 0."""
+    try:
+        tol = float(text)
+        converge_to_mA(tol)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a tolerance >= 0 (Angstrom)")
+    return tol
 
 
 # device-side fault bits (include/dmpfold_hip.h, DMP_FAULT_*)
@@ -251,16 +274,33 @@ class Engine:
         self.weights_tag = other.weights_tag
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
-                minsteps=default_minsteps):
-        """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU."""
+                minsteps=default_minsteps, converge=None):
+        """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `converge` (Angstrom; None = the engine's "recycle_tol_mA" option as it stands, 0 by default): stop recycling
+        after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
+        are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
+        call synchronises with the GPU once per pass."""
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps)
+        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge)
+
+    @property
+    def passes_run(self):
+        """Trunk passes of the last prediction (iterations + 1 unless it converged earlier)."""
+        return self.get_option("passes_run")
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
-                       minsteps=default_minsteps):
+                       minsteps=default_minsteps, converge=None):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
+        if converge is not None:
+            # the option is read when the prediction begins: set for this call, then as it was
+            before = self.get_option("recycle_tol_mA")
+            self.set_option("recycle_tol_mA", converge_to_mA(converge))
+            try:
+                return self.predict_device(d_msa, template_ca, iterations, minsteps)
+            finally:
+                self.set_option("recycle_tol_mA", before)
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
@@ -316,7 +356,7 @@ class Engine:
         raise_for_faults(self.sync_faults())
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
-                        minsteps=default_minsteps):
+                        minsteps=default_minsteps, converge=None):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
@@ -324,11 +364,18 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps)
+        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
-                               minsteps=default_minsteps):
+                               minsteps=default_minsteps, converge=None):
         """`predict_checked` for residue codes already resident on the GPU."""
+        if converge is not None:
+            before = self.get_option("recycle_tol_mA")
+            self.set_option("recycle_tol_mA", converge_to_mA(converge))
+            try:
+                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps)
+            finally:
+                self.set_option("recycle_tol_mA", before)
         coords, confs = self.predict_device(d_msa, template_ca, iterations, minsteps)
         bits = self.sync_faults()
         self.last_fallback = False
@@ -395,9 +442,11 @@ class Pipeline:
     of rounds 1-5 had - submit / pump / drain / result, step / poll / peek for the streaming batch front end, collect for
     the repeat of faulted targets."""
 
-    def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False):
+    def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
-        the library's own - for a host that wants every stream to be one its allocator knows."""
+        the library's own - for a host that wants every stream to be one its allocator knows.
+        `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
+        (`set_converge`; `stats()` counts the passes run and saved)."""
         self.lib = _lib.load()
         self.device = _resolve_device(device)
         S = max(1, int(streams))
@@ -418,6 +467,8 @@ class Pipeline:
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
+        if converge is not None:
+            self.set_converge(converge)
         self._jobs = {}               # ticket -> (d_msa, iterations, minsteps, d_tpl, coords, confs, ready event): kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -425,6 +476,10 @@ class Pipeline:
         """An engine option on EVERY engine of the (idle) pipeline: a group's vertical-GRU chain runs in its leader's
         arithmetic and serves all members, so the engines must agree on "precision" / "vgru_f32" / "vgru_persistent"."""
         _lib.check(self.lib.dmp_pipeline_set_option(self._p, name.encode(), int(value)))
+
+    def set_converge(self, converge):
+        """Convergence tolerance (Angstrom; None or 0 = fixed depth) of every target submitted from now on; idle pipeline only."""
+        self.set_option("recycle_tol_mA", converge_to_mA(converge))
 
     def close(self):
         if self._p:
@@ -556,10 +611,11 @@ class Pipeline:
         return job[4], job[5]
 
     def stats(self):
-        v = (C.c_longlong * 8)()
-        _lib.check(self.lib.dmp_pipeline_stats(self._p, v, 8))
+        v = (C.c_longlong * 11)()
+        _lib.check(self.lib.dmp_pipeline_stats(self._p, v, 11))
         return {"groups": v[0], "max_group": v[1], "rider_chains": v[2], "max_riders": v[3], "riders_left": v[4],
-                "idle_rounds": v[5], "rounds": v[6], "scheduler_thread_cpu_s": v[7] * 1e-6}
+                "idle_rounds": v[5], "rounds": v[6], "scheduler_thread_cpu_s": v[7] * 1e-6,
+                "passes_run": v[8], "early_stops": v[9], "passes_saved": v[10]}
 
     def submit_many(self, d_msas, iterations=default_iterations, minsteps=default_minsteps):
         """Submit a batch with the scheduler paused, so that the first vertical-GRU group is formed from the whole batch
@@ -706,9 +762,12 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 # the reference's public functions
 # ---------------------------------------------------------------------------
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
-                  minsteps=default_minsteps, weights_file=None, return_alnmat=False):
+                  minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
-    plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158)."""
+    plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
+    `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
+    than this (RMS) - the answer `iterations` = that pass would have given (Engine.predict)."""
+    tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
     template_ca = read_template_ca(template) if template is not None else None
@@ -716,7 +775,7 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     nseqs, length = alnmat.shape
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
         eng = get_engine(dev, length, nseqs, weights_file=weights_file)
-        coords, confs = eng.predict_checked(alnmat, template_ca, iterations, minsteps)
+        coords, confs = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol)
     if return_alnmat:
         return coords, confs, alnmat
     return coords, confs
@@ -742,8 +801,8 @@ def pdb_text(coords, confs, alnmat):
     return "\n".join(lines) + "\n"
 
 
-def run_dmpfold(argv=None):
-    """Command-line entry point with the reference's flags (predict.py:160-208)."""
+def dmpfold_parser():
+    """The reference's flags (predict.py:160-208) and -c / --converge."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -759,9 +818,17 @@ def run_dmpfold(argv=None):
                         help="number of minimization steps")
     parser.add_argument("-w", "--model_weights", type=str, required=False,
                         help="use a custom set of model weights")
-    args = parser.parse_args(argv)
+    parser.add_argument("-c", "--converge", type=_tolerance_arg, default=None, required=False, metavar="TOL",
+                        help="stop recycling once a pass changes the seed distance map by no more than TOL Angstrom (RMS); "
+                             "default: always run all iteration cycles")
+    return parser
+
+
+def run_dmpfold(argv=None):
+    """Command-line entry point with the reference's flags (predict.py:160-208)."""
+    args = dmpfold_parser().parse_args(argv)
     coords, confs, alnmat = aln_to_coords(args.input_file, device=args.device,
                                           template=args.template, iterations=args.iterations,
                                           minsteps=args.minsteps, weights_file=args.model_weights,
-                                          return_alnmat=True)
+                                          return_alnmat=True, converge=args.converge)
     sys.stdout.write(pdb_text(coords, confs, alnmat))

@@ -50,6 +50,18 @@ def job_summary(n_done: int, elapsed: float, group=None, failures=None):
     return int(round(cnt[0].item())), float(tmax.item()), int(round(cnt[1].item())), int(round(cnt[2].item()))
 
 
+def sum_over_ranks(counts, group=None):
+    """Integer counters summed over the ranks of the job (a single rank: themselves)."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return [int(v) for v in counts]
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    t = torch.tensor([float(v) for v in counts], dtype=torch.float64, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return [int(round(v)) for v in t.tolist()]
+
+
 def job_store(rank: int, world: int, timeout_s: float = 1800.0):
     """The key-value store of a multi-rank job, made with torch.distributed's PUBLIC constructor (the address of the
     launcher's environment: MASTER_ADDR / MASTER_PORT) so that it can be handed to init_process_group(store=...) AND

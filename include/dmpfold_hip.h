@@ -154,7 +154,23 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * raise DMP_FAULT_VGRU_HANDOFF and leave its row loop; the Python layer then repeats with one launch per row.
  * "refine_single" = 1 runs the minimiser (dmp_refine_coords, dmp_predict*) in one workgroup instead
  * of a cluster of 16 that hands the coordinates over every step; same iteration, different
- * partial-sum slices (results agree to float32 rounding). */
+ * partial-sum slices (results agree to float32 rounding).
+ * "recycle_tol_mA" (default 0 = off; negative: DMP_ERR_ARG): stop recycling once the C-alpha trace has converged.  The
+ * value is a tolerance in milli-Angstrom, read when a prediction begins.  With it > 0 the tail unit of every pass p
+ * launches one more kernel (recycle_delta, csrc/coords.hip) that computes
+ *   d_p = sqrt(mean over i < j of (D(ca_p)_ij - D(seed_p)_ij)^2),  D(x)_ij = sqrt(max(|x_i - x_j|^2, 1e-8)),
+ * the RMS change, in Angstrom, between the distance map that seeded pass p (seed_p: the refined pass-0 trace for p = 1,
+ * ca_(p-1) after that) and the one pass p's own trace would seed (the traces "ca_pass" records; float64, fixed summation
+ * order: the same bits on every run).  Pass 0 has no delta (+inf is recorded).  If (float)d_p <= tol_mA * 1e-3f (false for
+ * NaN) for a p >= 1, pass p is the last one: best-of, final refinement and backbone run exactly as if nloops had been p,
+ * so A CONVERGED PREDICTION THAT STOPPED AFTER PASS k IS BIT-IDENTICAL TO A PLAIN ONE WITH nloops = k, and one that
+ * never meets the tolerance to the plain one with the nloops given.  The decision is the host's, between passes: the
+ * kernel leaves {pass, stop} in a word of pinned host memory, and it is read in front of unit 0 of every pass >= 2 once
+ * the tail unit before it has completed - see dmp_predict and dmp_predict_next_unit below.  With the option 0 no extra
+ * kernel is launched and nothing ever waits.
+ * "passes_run" (read only): the trunk passes of this context's last prediction, valid after dmp_predict_end (nloops + 1
+ * unless "recycle_tol_mA" stopped it earlier).  The tickets of a pipeline do not carry their own count - that would take
+ * a new entry point (an ABI 6); dmp_pipeline_stats has the sums. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
@@ -323,7 +339,9 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
 /* GRUResNet.forward + the feature glue of aln_to_coords (predict.py:134-153,
  * network.py:218-314).  d_msa: N x L codes (N already capped).  d_template_ca: Lt x 3 or NULL
  * (seed distance channel = -1).  nloops = recycling iterations, refine_steps = minimiser
- * steps.  Outputs d_coords (L x 5 x 3) and d_conf (L).  No host synchronisation. */
+ * steps.  Outputs d_coords (L x 5 x 3) and d_conf (L).  No host synchronisation - unless option "recycle_tol_mA" is
+ * set: the call then waits for the tail of every pass p >= 1 that has a successor (one event synchronisation per pass)
+ * to learn whether to go on, and returns with the remaining work enqueued as always. */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
                 int Lt, int nloops, int refine_steps, float* d_coords, float* d_conf,
                 void* stream);
@@ -342,7 +360,12 @@ int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d
 #define DMP_UNIT_NONE 0   /* every pass of this prediction was issued: call dmp_predict_end */
 #define DMP_UNIT_LIGHT 1  /* no convolution in the unit */
 #define DMP_UNIT_CONV 2   /* residual block: one lane turn */
-#define DMP_UNIT_WAIT 3   /* nothing to issue now: the unit waits for another context's units (dmp_predict_group_vgru) */
+#define DMP_UNIT_WAIT 3   /* nothing to issue now: the unit waits for another context's units (dmp_predict_group_vgru), or -
+                             with option "recycle_tol_mA" - for this prediction's own pass tail: at the boundary in front of
+                             every pass >= 2 dmp_predict_next_unit queries that unit's event (it never blocks) and answers
+                             WAIT until it has completed, then DMP_UNIT_NONE (converged) or the next unit.  A caller that
+                             issues without asking (dmp_predict_issue_unit at such a boundary) is made to wait there, and
+                             on a stop the call enqueues nothing and returns DMP_OK. */
 int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L,
                             const float* d_template_ca, int Lt, int nloops, int refine_steps);
 int dmp_predict_next_unit(const dmp_ctx* ctx);
@@ -442,7 +465,9 @@ int dmp_pipeline_backlog(dmp_pipeline* p, int* h_queued, int* h_running);
 int dmp_pipeline_pause(dmp_pipeline* p, int on);
 /* counters since creation: [0] vertical-GRU groups formed, [1] largest group, [2] chains that carried riders, [3] most
  * riders in one chain, [4] rider results not yet consumed (0 on an idle pipeline), [5] scheduling rounds that found nothing
- * to issue, [6] scheduling rounds, [7] CPU microseconds of the scheduler thread */
+ * to issue, [6] scheduling rounds, [7] CPU microseconds of the scheduler thread; with option "recycle_tol_mA" in mind:
+ * [8] trunk passes issued (of the predictions issued to their end), [9] predictions that stopped before their nloops,
+ * [10] passes saved that way.  Entries beyond `capacity` are not written (a caller built for 8 counters keeps working). */
 int dmp_pipeline_stats(dmp_pipeline* p, long long* h_stats, int capacity);
 
 /* Synchronise `stream` and report the device-side faults recorded since the last report
@@ -453,7 +478,8 @@ int dmp_sync_faults(dmp_ctx* ctx, void* stream, int* h_bits);
 /* ---- introspection for tests and the benchmark ------------------------------------------- */
 /* After dmp_predict: copy an internal tensor to d_dst (device).  Names: "w", "contacts",
  * "mat1d", "conf_means" (P floats), "ca_pass" (P x L x 3), "best_ca" (L x 3, before the final
- * refinement), "inv_cov" (21L x 21L), "mds" (L x 8) and "gram" (L x L) of the last pass.  Returns the number of floats written or a negative status. */
+ * refinement), "inv_cov" (21L x 21L), "mds" (L x 8) and "gram" (L x L) of the last pass, "pass_delta" (P floats: d_p of
+ * option "recycle_tol_mA", +inf for pass 0; nothing - 0 floats - if the prediction ran with the option off).  Returns the number of floats written or a negative status. */
 int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t capacity,
                         void* stream);
 /* Optional HIP-event timing of every conv5x5 launch inside dmp_predict / dmp_trunk_pass / the unit calls (events
