@@ -33,7 +33,7 @@ import torch
 
 from . import shard
 from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
-                      pdb_text, read_a3m, read_aln, read_template_ca)
+                      pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy)
 
 
 class BatchFailures(RuntimeError):
@@ -142,13 +142,23 @@ def ca_only_text(coords, confs, alnmat):
     return "\n".join(out)
 
 
-def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb"):
+def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None):
+    """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
+    (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
+    the structure (float32, as `dmpfold --distmap` writes it)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
+        extra = {}
+        if distmap is not None:
+            h_info = info.detach().cpu().numpy()
+            extra = {"distmap": distmap.detach().cpu().numpy(), "best_pass": np.int32(h_info[0]),
+                     "passes_run": np.int32(h_info[1]), "map_rms": np.float32(h_info[2])}
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
-                            alnmat=alnmat)
+                            alnmat=alnmat, **extra)
         return path
+    if distmap is not None:
+        save_distmap_npy(stem + ".distmap.npy", distmap)
     path = stem + ".pdb"
     with open(path, "w") as fh:
         fh.write(pdb_text(coords, confs, alnmat) if fmt == "pdb" else ca_only_text(coords, confs, alnmat))
@@ -197,8 +207,9 @@ def cost_order(targets, iterations):
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
-              converge=None, stats_out=None):
+              converge=None, stats_out=None, distmap=False):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
+    `distmap`: every target's chosen-pass distance map is brought back and written too (write_result).
     `converge` (Angstrom, None = off): targets stop recycling once converged (Pipeline.set_converge); `stats_out`, a
     dict, then receives this rank's "passes_run" and "passes_saved".
 
@@ -240,6 +251,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             pipe = Pipeline(dev, max_L, max_N, sd, streams=streams, precision=drop_in_precision())
             if converge is not None:
                 pipe.set_converge(converge)
+            if distmap:
+                pipe.set_distmap(True)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -247,7 +260,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         return pipe
 
     done = []                                           # completed on the GPU AND copied to the host, not yet written
-    copying = []                                        # (ticket, host coords, host confs, event): D2H in flight
+    copying = []                                        # (ticket, (host coords, host confs[, map, info]), event): D2H in flight
 
     # The scheduler's thread never blocks on the GPU: a synchronous copy on the default stream can queue behind an
     # engine's kernels (streams share hardware queues) and would stall the thread - and with it every engine.
@@ -255,32 +268,31 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     # end's own stream; completion is polled.  (Measured at the north-star size: files -> PDB files 6.2 structures/s
     # including the pipeline's set-up against 6.7 for the same targets resident in HBM, tools/batch_throughput.py.)
     def start_copy_back(t):
-        coords, confs = pipe.peek(t)
-        if coords.is_cuda:
-            hc = torch.empty(coords.shape, dtype=coords.dtype, pin_memory=True)
-            hf = torch.empty(confs.shape, dtype=confs.dtype, pin_memory=True)
+        outs = pipe.peek(t)                           # (coords, confs), with `distmap` also (map, info)
+        if outs[0].is_cuda:
+            host = tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in outs)
             with (torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext()):
-                hc.copy_(coords, non_blocking=True)   # the prediction has completed (polled): no ordering needed
-                hf.copy_(confs, non_blocking=True)
+                for h, x in zip(host, outs):
+                    h.copy_(x, non_blocking=True)     # the prediction has completed (polled): no ordering needed
                 ev = torch.cuda.Event()
                 ev.record()
         else:
-            hc, hf, ev = coords, confs, None
-        copying.append((t, hc, hf, ev))
+            host, ev = tuple(outs), None
+        copying.append((t, host, ev))
 
     def reap_copies():
-        while copying and (copying[0][3] is None or copying[0][3].query()):
-            done.append(copying.pop(0)[:3])
+        while copying and (copying[0][2] is None or copying[0][2].query()):
+            done.append(copying.pop(0)[:2])
 
     def finish(item):
-        t, coords, confs = item
+        t, (coords, confs, *dm) = item
         aln_path, alnmat, _ = parsed.pop(t)
         if bool(torch.isnan(confs[:1]).any()):          # a device-side fault poisoned it: repeated alone at the end
             parsed[t] = (aln_path, alnmat, None)
             faulted.append(t)
             return
         pipe.result(t)
-        outputs.append(write_result(out_dir, aln_path, coords, confs, alnmat, fmt))
+        outputs.append(write_result(out_dir, aln_path, coords, confs, alnmat, fmt, *dm))
 
     exhausted = False
     cap = 2 * max(1, int(streams))                      # started + queued per rank
@@ -353,8 +365,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             elif done:
                 finish(done.pop(0))
     if copying:
-        if copying[-1][3] is not None:
-            copying[-1][3].synchronize()
+        if copying[-1][2] is not None:
+            copying[-1][2].synchronize()
         reap_copies()
     for item in done:
         finish(item)
@@ -365,7 +377,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             if isinstance(res[t], Exception):
                 failed.append((aln_path, res[t]))
             else:
-                outputs.append(write_result(out_dir, aln_path, res[t][0], res[t][1], alnmat, fmt))
+                outputs.append(write_result(out_dir, aln_path, res[t][0], res[t][1], alnmat, fmt, *res[t][2:]))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:
@@ -394,6 +406,9 @@ def batch_parser():
     ap.add_argument("--converge", type=_tolerance_arg, default=None, metavar="TOL",
                     help="stop a target's recycling once a pass changes its seed distance map by no more than TOL Angstrom "
                          "(RMS); the summary then counts the passes run and saved")
+    ap.add_argument("--distmap", action="store_true",
+                    help="also write every target's predicted C-alpha distance map (the pass the best-of rule chose): npz "
+                         "gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca write <stem>.distmap.npy")
     return ap
 
 
@@ -424,7 +439,7 @@ def main(argv=None):
         n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                   weights_file=args.model_weights, streams=args.streams,
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
-                                  converge=args.converge, stats_out=passes)
+                                  converge=args.converge, stats_out=passes, distmap=args.distmap)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)

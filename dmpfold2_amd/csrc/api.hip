@@ -405,14 +405,15 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // End of a prediction: if a device-side fault was recorded while it ran, its outputs become NaN (an
 // invalid structure can never be mistaken for a result, and a batch can tell WHICH target failed) and
 // the fault bits are latched into the word dmp_sync_faults reports.
+// `nconf`: the floats behind `conf` - L, or L + L*L + 3 with option "emit_distmap" (the whole extension becomes NaN too).
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
-                                   float* __restrict__ conf, int L, int* __restrict__ report) {
+                                   float* __restrict__ conf, int L, int64_t nconf, int* __restrict__ report) {
   const int f = words[0];
   if (!f) return;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const float nan = __builtin_nanf("");
   if (i < 15 * L) coords[i] = nan;
-  if (i < L) conf[i] = nan;
+  if (i < nconf) conf[i] = nan;
   if (i == 0) {
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
@@ -513,10 +514,15 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(pass_delta, c->max_passes);
   A_(delta_partial, 64);
   A_(delta_counter, 1);
+  A_(best_pass, 1);
+  A_(best_dm, LL);
+  A_(rms_partial, 64);
+  A_(rms_counter, 1);
 #undef A_
   if (rc) { dmp_ctx_destroy(c); return rc; }
   if (hipMemset(c->seq_abort, 0, 2 * sizeof(int)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->delta_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  if (hipMemset(c->rms_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   // the word recycle_delta tells the host its stop decision through (read only after the pass tail's event)
   if (hipHostMalloc((void**)&c->delta_host, sizeof(int), hipHostMallocMapped) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   *c->delta_host = 0;
@@ -581,6 +587,11 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->recycle_tol_mA = value;
     return DMP_OK;
   }
+  if (k == "emit_distmap") {         // takes effect with the next prediction begun
+    DMP_ARG(value == 0 || value == 1, "emit_distmap must be 0 or 1, got %d", value);
+    ctx->emit_distmap = value;
+    return DMP_OK;
+  }
   DMP_ARG(k != "passes_run", "passes_run is read only");
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -622,6 +633,7 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "gj_pairs") { *h_value = ctx->gj_pairs; return DMP_OK; }
   if (k == "gj_diag_blocked") { *h_value = ctx->gj_diag_blocked; return DMP_OK; }
   if (k == "recycle_tol_mA") { *h_value = ctx->recycle_tol_mA; return DMP_OK; }
+  if (k == "emit_distmap") { *h_value = ctx->emit_distmap; return DMP_OK; }
   if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -1186,6 +1198,7 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   c->unit_next = 0;
   c->end_refined = false;
   c->run_tol_mA = c->recycle_tol_mA;
+  c->run_emit = c->emit_distmap;
   c->gate_pass = 0;
   c->run_nloops = nloops < 0 ? 0 : nloops;
   c->run_refine = refine_steps < 0 ? 0 : refine_steps;
@@ -1329,6 +1342,7 @@ int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream) {
     if (!rc) rc = coords_from_mds(c, c->mat1d, c->mds, L, c->ca, s);
     if (!rc && pass == 0 && c->run_refine > 0) rc = refine_coords(c, c->ca, L, c->run_refine, s);
     if (!rc) rc = select_best(c, c->conf, c->ca, L, pass, c->max_passes, s);
+    if (!rc && c->run_emit) rc = keep_best_dm(c, L, pass, s);     // head0 is still this pass's plane here
     if (!rc && c->run_tol_mA > 0) rc = recycle_delta(c, c->ca, L, pass, c->max_passes, s);
   }
   if (rc) { c->xsplit_current = false; return rc; }
@@ -1382,8 +1396,11 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // (tools/isa_lint.py).
   rc = ca_to_backbone(c->best_ca, c->best_conf, L, d_coords, d_conf, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(fault_latch_kernel, dim3(cdiv(15 * L, 256)), dim3(256), 0, s, c->seq_abort, d_coords,
-                     d_conf, L, c->end_fault_out);
+  // option "emit_distmap": d_conf holds L + L*L + 3 floats; the map, {best_pass, passes_run, map_rms} behind the confidences
+  const int64_t nconf = c->run_emit ? (int64_t)L + (int64_t)L * L + 3 : L;
+  if (c->run_emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + L, s))) return rc;
+  hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, nconf), 256)), dim3(256), 0, s,
+                     c->seq_abort, d_coords, d_conf, L, nconf, c->end_fault_out);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }
@@ -1429,6 +1446,8 @@ int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t ca
   else if (k == "conf_means") { src = ctx->conf_means; n = P; }
   else if (k == "ca_pass") { src = ctx->ca_pass; n = P * L * 3; }
   else if (k == "pass_delta") { src = ctx->pass_delta; n = ctx->run_tol_mA > 0 ? P : 0; }
+  else if (k == "best_dm") { src = ctx->best_dm; n = ctx->run_emit ? L * L : 0; }
+  else if (k == "best_pass") { src = ctx->best_pass; n = 1; }
   else if (k == "best_ca") { src = ctx->best_ca_snapshot; n = L * 3; }
   else if (k == "best_ca_refined") { src = ctx->best_ca; n = L * 3; }
   else if (k == "inv_cov") { src = ctx->cov; n = (int64_t)NS * L * NS * L; }

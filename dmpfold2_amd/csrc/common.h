@@ -48,6 +48,12 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return cdiv(a, b) * b; }
 
+// One entry of a pass's predicted distance map from the head's channel 0 and its transpose: dm_ij = |(h0_ij + h0_ji) / 2|
+// (network.py:237-243).  The one definition both gram_kernel (trunk.hip) and keep_best_dm_kernel (coords.hip) evaluate, so
+// the map handed out with option "emit_distmap" is, bit for bit, the one the Gram matrix was formed from.  One add, one
+// multiply by a power of two: nothing to contract, the same value in either translation unit, and dm_ij == dm_ji.
+__host__ __device__ inline float distmap_entry(float h_ij, float h_ji) { return fabsf((h_ij + h_ji) * 0.5f); }
+
 // padded activation geometry: interior [2, 2+L) in both axes, zero elsewhere
 inline int act_tiles(int L) { return cdiv(L, CONV_TILE); }
 inline int act_pitch(int L) { return act_tiles(L) * CONV_TILE + 4; }
@@ -244,6 +250,13 @@ struct dmp_ctx {
   double* delta_partial = nullptr; // [64] per-workgroup sums
   unsigned* delta_counter = nullptr;
   int* delta_host = nullptr;       // pinned host word the kernel writes: ((pass + 1) << 1) | stop
+  // option "emit_distmap": the chosen pass's predicted distance map behind the confidences (include/dmpfold_hip.h)
+  int emit_distmap = 0;
+  int run_emit = 0;                // ... as the prediction in flight began with it
+  float* best_pass = nullptr;      // [1] the pass select_best took last, as a float (always written)
+  float* best_dm = nullptr;        // [max_L][max_L] dm of that pass (coords.hip: keep_best_dm; only with the option on)
+  double* rms_partial = nullptr;   // [64] per-workgroup sums of emit_distmap
+  unsigned* rms_counter = nullptr;
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -474,6 +487,8 @@ int fill_f32(float* d, int64_t n, float v, hipStream_t s);
 int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int pass, int rec_cap,
                 hipStream_t s);
 int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, hipStream_t s);
+int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
+int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_ext, hipStream_t s);
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);

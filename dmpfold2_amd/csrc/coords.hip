@@ -99,7 +99,8 @@ __global__ __launch_bounds__(256) void select_best_kernel(const float* __restric
                                                           float* __restrict__ best_conf,
                                                           float* __restrict__ best_ca,
                                                           float* __restrict__ conf_means,
-                                                          float* __restrict__ ca_pass) {
+                                                          float* __restrict__ ca_pass,
+                                                          float* __restrict__ best_pass) {
   __shared__ double red[256];
   __shared__ int take;
   double acc = 0.0;
@@ -114,7 +115,10 @@ __global__ __launch_bounds__(256) void select_best_kernel(const float* __restric
     const float mean = (float)(red[0] / (double)L);
     if (pass < rec_cap) conf_means[pass] = mean;
     take = (pass == 0) || (mean > best_mean[0]);
-    if (take) best_mean[0] = mean;
+    if (take) {
+      best_mean[0] = mean;
+      best_pass[0] = (float)pass;        // the word keep_best_dm and emit_distmap read (exact below 2^24)
+    }
   }
   __syncthreads();
   if (pass < rec_cap)
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void select_best_kernel(const float* __restric
 int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int pass, int rec_cap,
                 hipStream_t s) {
   hipLaunchKernelGGL(select_best_kernel, dim3(1), dim3(256), 0, s, d_conf, d_ca, L, pass, rec_cap,
-                     c->best_mean, c->best_conf, c->best_ca, c->conf_means, c->ca_pass);
+                     c->best_mean, c->best_conf, c->best_ca, c->conf_means, c->ca_pass, c->best_pass);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }
@@ -233,6 +237,135 @@ int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, h
   a.host_word = c->delta_host;
   const int G = pass > 0 ? recycle_delta_groups(L) : 1;
   hipLaunchKernelGGL(recycle_delta_kernel, dim3(G), dim3(RD_THREADS), pass > 0 ? sizeof(float) * 6 * L : 0, s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// option "emit_distmap": the chosen pass's predicted distance map (include/dmpfold_hip.h)
+// ---------------------------------------------------------------------------------------
+// keep_best_dm runs in the pass tail behind select_best.  Every workgroup reads the pass select_best took last and
+// leaves at once unless it is this one; otherwise head0 - the plane the last block's norm kernel left, which nothing
+// has overwritten in the tail unit - becomes best_dm, dm_ij = distmap_entry(h0_ij, h0_ji).  A workgroup owns the tile
+// pair (bi <= bj): tiles (bi, bj) and (bj, bi) of h0 go to LDS with row-contiguous (coalesced) reads, and both mirrored
+// tiles of dm are written row-contiguously, the transposed operand coming from LDS.  64 x 64 floats per tile: a wave
+// reads or writes one 256-byte row segment per instruction.  The LDS rows are padded to 65 words: ds_read_b32 and
+// ds_write_b32 resolve banks as (word address) % 32 within each 32-lane half, the row access r * 65 + lane is
+// conflict-free at any pitch, and the column access lane * 65 + r lands on bank (lane + r) % 32 - 32 different banks
+// per half - where pitch 64 would put a whole half on one bank.  2 x 64 x 65 x 4 B = 33 KB per workgroup.
+constexpr int KD_TILE = 64;
+constexpr int KD_PITCH = KD_TILE + 1;
+constexpr int KD_THREADS = 256;
+
+__global__ __launch_bounds__(KD_THREADS) void keep_best_dm_kernel(const float* __restrict__ h0,
+                                                                  const float* __restrict__ best_pass, int L,
+                                                                  int pass, float* __restrict__ best_dm) {
+  __shared__ float ta[KD_TILE * KD_PITCH];     // h0 tile (bi, bj)
+  __shared__ float tb[KD_TILE * KD_PITCH];     // h0 tile (bj, bi)
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  if (bi > bj) return;
+  if (best_pass[0] != (float)pass) return;
+  const int i0 = bi * KD_TILE, j0 = bj * KD_TILE;
+  const int tx = threadIdx.x & (KD_TILE - 1), ty = threadIdx.x / KD_TILE;
+  constexpr int ROWS = KD_THREADS / KD_TILE;
+  for (int r = ty; r < KD_TILE; r += ROWS) {
+    float a = 0.f, b = 0.f;
+    if (i0 + r < L && j0 + tx < L) a = h0[(int64_t)(i0 + r) * L + j0 + tx];
+    if (j0 + r < L && i0 + tx < L) b = h0[(int64_t)(j0 + r) * L + i0 + tx];
+    ta[r * KD_PITCH + tx] = a;
+    tb[r * KD_PITCH + tx] = b;
+  }
+  __syncthreads();
+  for (int r = ty; r < KD_TILE; r += ROWS) {
+    // dm[i0 + r][j0 + tx] from h0[i0 + r][j0 + tx] and h0[j0 + tx][i0 + r]
+    if (i0 + r < L && j0 + tx < L)
+      best_dm[(int64_t)(i0 + r) * L + j0 + tx] = distmap_entry(ta[r * KD_PITCH + tx], tb[tx * KD_PITCH + r]);
+    // the mirrored tile: dm[j0 + r][i0 + tx] from h0[j0 + r][i0 + tx] and h0[i0 + tx][j0 + r]
+    if (bi != bj && j0 + r < L && i0 + tx < L)
+      best_dm[(int64_t)(j0 + r) * L + i0 + tx] = distmap_entry(tb[r * KD_PITCH + tx], ta[tx * KD_PITCH + r]);
+  }
+}
+
+int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s) {
+  const int T = cdiv(L, KD_TILE);
+  hipLaunchKernelGGL(keep_best_dm_kernel, dim3(T, T), dim3(KD_THREADS), 0, s, c->head0, c->best_pass, L, pass,
+                     c->best_dm);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// emit_distmap runs in dmp_predict_end behind ca_to_backbone: best_dm goes to the caller's buffer behind the
+// confidences, followed by {best_pass, passes_run, map_rms},
+//   map_rms = sqrt(mean over i < j of (dm_ij - |ca_i - ca_j|)^2)     [Angstrom],
+// ca the final, refined trace the backbone was built from: distances in float64 from the float32 coordinates, no clamp.
+// The sum is formed the way recycle_delta forms its own: the trace in LDS, rows dealt round robin to the workgroups, a
+// row's partners to the threads, per-thread sums in a fixed order, a fixed tree, and the last arriver adds the partial
+// sums in index order and resets the counter - the same bits on every run.  The workgroup that owns a row copies it.
+struct EmitDistmapArgs {
+  const float* best_dm;    // [L][L]
+  const float* ca;         // [L][3]
+  const float* best_pass;  // [1]
+  int L, passes_run;
+  float* out;              // [L*L + 3]
+  double* partial;         // [RD_MAX_WG]
+  unsigned* counter;       // zero between launches
+};
+
+__global__ __launch_bounds__(RD_THREADS) void emit_distmap_kernel(EmitDistmapArgs a) {
+  extern __shared__ float sm[];          // 3L coordinates
+  __shared__ double red[RD_THREADS];
+  const int L = a.L, tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+  for (int i = tid; i < 3 * L; i += RD_THREADS) sm[i] = a.ca[i];
+  __syncthreads();
+  double acc = 0.0;
+  for (int i = g; i < L; i += G) {
+    const double ax = sm[3 * i], ay = sm[3 * i + 1], az = sm[3 * i + 2];
+    const float* src = a.best_dm + (int64_t)i * L;
+    float* dst = a.out + (int64_t)i * L;
+    for (int j = tid; j < L; j += RD_THREADS) {
+      const float dm = src[j];
+      dst[j] = dm;
+      if (j > i) {
+        const double ux = (double)sm[3 * j] - ax, uy = (double)sm[3 * j + 1] - ay, uz = (double)sm[3 * j + 2] - az;
+        const double e = (double)dm - sqrt((ux * ux + uy * uy) + uz * uz);
+        acc += e * e;
+      }
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = RD_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.partial[g]), (unsigned long long)__double_as_longlong(red[0]),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned before = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (before == (unsigned)G - 1u) {          // the last arriver: every partial sum is behind its owner's release
+      double sum = 0.0;
+      for (int k = 0; k < G; ++k)
+        sum += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(&a.partial[k]),
+                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      float* tail = a.out + (int64_t)L * L;
+      tail[0] = a.best_pass[0];
+      tail[1] = (float)a.passes_run;
+      tail[2] = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
+      __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_ext, hipStream_t s) {
+  EmitDistmapArgs a{};
+  a.best_dm = c->best_dm;
+  a.ca = d_ca;
+  a.best_pass = c->best_pass;
+  a.L = L; a.passes_run = passes_run;
+  a.out = d_ext;
+  a.partial = c->rms_partial;
+  a.counter = c->rms_counter;
+  hipLaunchKernelGGL(emit_distmap_kernel, dim3(recycle_delta_groups(L)), dim3(RD_THREADS), sizeof(float) * 3 * L, s, a);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

@@ -906,7 +906,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ h0,
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= L) return;
   auto dm = [&](int a, int b) {
-    return fabsf((h0[(int64_t)a * L + b] + h0[(int64_t)b * L + a]) * 0.5f);
+    return distmap_entry(h0[(int64_t)a * L + b], h0[(int64_t)b * L + a]);
   };
   const float d0j = dm(0, j), di0 = dm(i, 0), dij = dm(i, j);
   const float t = d0j * d0j + di0 * di0;

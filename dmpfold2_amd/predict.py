@@ -16,7 +16,9 @@ Differences from the reference, all additive or forced by the environment:
   * eigenvector signs of the MDS step follow a fixed rule (see include/dmpfold_hip.h);
   * missing trained weights raise FileNotFoundError (no download: predict.py:64-71);
   * `converge` (Angstrom, None / 0 = off, the default): recycling stops after the first pass that moves the seed
-    distance map by no more than that (RMS); the result is then the one `iterations` = that pass would have given.
+    distance map by no more than that (RMS); the result is then the one `iterations` = that pass would have given;
+  * `distmap` / `return_distmap` / `dmpfold --distmap FILE`: the predicted C-alpha distance map of the pass the best-of
+    rule chose (option "emit_distmap" of include/dmpfold_hip.h) comes back with the structure.
 """
 from __future__ import annotations
 
@@ -142,6 +144,28 @@ def converge_to_mA(converge):
     if not (tol >= 0.0) or tol == float("inf"):
         raise ValueError(f"converge must be a finite tolerance >= 0 (Angstrom), got {converge!r}")
     return int(round(tol * 1000.0))
+
+
+def distmap_floats(L, on=True):
+    """Floats the `d_conf` buffer of a prediction of length L must hold: L, or L + L*L + 3 with option "emit_distmap"."""
+    L = int(L)
+    return L + L * L + 3 if on else L
+
+
+def split_distmap_buffer(buf, L):
+    """The three parts of an "emit_distmap" output buffer (a 1-D tensor or array of distmap_floats(L) floats), as views:
+    confs (L,), distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms] (include/dmpfold_hip.h)."""
+    L = int(L)
+    if buf.ndim != 1 or buf.shape[0] != distmap_floats(L):
+        raise ValueError(f"an emit_distmap buffer of length {L} has {distmap_floats(L)} floats, got shape {tuple(buf.shape)}")
+    return buf[:L], buf[L:L + L * L].reshape(L, L), buf[L + L * L:]
+
+
+def save_distmap_npy(path, distmap):
+    """The (L, L) map as a float32 .npy file (what `dmpfold --distmap` and `dmpfold-batch --distmap` write)."""
+    arr = distmap.detach().cpu().numpy() if isinstance(distmap, torch.Tensor) else np.asarray(distmap)
+    with open(path, "wb") as fh:           # an open file: np.save would append ".npy" to a name without it
+        np.save(fh, np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def _tolerance_arg(text):
@@ -274,8 +298,14 @@ class Engine:
         self.weights_tag = other.weights_tag
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
-                minsteps=default_minsteps, converge=None):
+                minsteps=default_minsteps, converge=None, distmap=False):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `distmap=True` returns (coords, confs, distmap (L, L), info (3,)): the chosen pass's predicted distance map and
+        [best_pass, passes_run, map_rms] (option "emit_distmap", include/dmpfold_hip.h; the map's diagonal is what the
+        network predicts, not zero).  confs, distmap and info are views of the one allocation handed to the library.
+        The option is set for this call only; no host synchronisation is added.  (On an engine whose "emit_distmap" option
+        was set to 1 by hand the library writes the long buffer in every call; without `distmap=True` the call still
+        returns the two tensors, confs being the first L floats of it.)
         `converge` (Angstrom; None = the engine's "recycle_tol_mA" option as it stands, 0 by default): stop recycling
         after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
@@ -283,7 +313,7 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge)
+        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap)
 
     @property
     def passes_run(self):
@@ -291,16 +321,24 @@ class Engine:
         return self.get_option("passes_run")
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
-                       minsteps=default_minsteps, converge=None):
+                       minsteps=default_minsteps, converge=None, distmap=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
         if converge is not None:
             # the option is read when the prediction begins: set for this call, then as it was
             before = self.get_option("recycle_tol_mA")
             self.set_option("recycle_tol_mA", converge_to_mA(converge))
             try:
-                return self.predict_device(d_msa, template_ca, iterations, minsteps)
+                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)
             finally:
                 self.set_option("recycle_tol_mA", before)
+        if distmap and not self.get_option("emit_distmap"):
+            self.set_option("emit_distmap", 1)
+            try:
+                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, True)
+            finally:
+                self.set_option("emit_distmap", 0)
+        # the buffer is sized by the option as the context holds it: the library writes L + L*L + 3 floats when it is on
+        emit = bool(self.get_option("emit_distmap"))
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
@@ -308,7 +346,7 @@ class Engine:
                                "(MDS embedding width, reference network.py:250-253)")
         with torch.cuda.device(self.device):
             coords = torch.empty((L, 5, 3), dtype=torch.float32, device=self.device)
-            confs = torch.empty((L,), dtype=torch.float32, device=self.device)
+            confs = torch.empty((distmap_floats(L, emit),), dtype=torch.float32, device=self.device)
             d_tpl, lt = None, 0
             if template_ca is not None:
                 d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(self.device)
@@ -330,7 +368,9 @@ class Engine:
                 coords.data_ptr(), confs.data_ptr(), self.stream()))
             # d_msa / d_tpl are stream-ordered temporaries: keep them alive until the work is queued
             self._keep = (d_msa, d_tpl)
-        return coords, confs
+        if emit and distmap:
+            return (coords,) + split_distmap_buffer(confs, L)
+        return coords, confs[:L]
 
     def set_option(self, name, value):
         """Additive engine options, e.g. ("conv_f32_exact", 1); see include/dmpfold_hip.h."""
@@ -356,7 +396,7 @@ class Engine:
         raise_for_faults(self.sync_faults())
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
-                        minsteps=default_minsteps, converge=None):
+                        minsteps=default_minsteps, converge=None, distmap=False):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
@@ -364,19 +404,26 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge)
+        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
-                               minsteps=default_minsteps, converge=None):
-        """`predict_checked` for residue codes already resident on the GPU."""
+                               minsteps=default_minsteps, converge=None, distmap=False):
+        """`predict_checked` for residue codes already resident on the GPU (`distmap`: see `predict`; a repeat of the
+        prediction returns the repeat's map)."""
         if converge is not None:
             before = self.get_option("recycle_tol_mA")
             self.set_option("recycle_tol_mA", converge_to_mA(converge))
             try:
-                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps)
+                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, distmap)
             finally:
                 self.set_option("recycle_tol_mA", before)
-        coords, confs = self.predict_device(d_msa, template_ca, iterations, minsteps)
+        if distmap and not self.get_option("emit_distmap"):
+            self.set_option("emit_distmap", 1)
+            try:
+                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, True)
+            finally:
+                self.set_option("emit_distmap", 0)
+        out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)     # 2 tensors, or 4 with `distmap`
         bits = self.sync_faults()
         self.last_fallback = False
         if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
@@ -385,7 +432,7 @@ class Engine:
             print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
                   "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
             self.set_option("vgru_persistent", 0)
-            coords, confs = self.predict_device(d_msa, template_ca, iterations, minsteps)
+            out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)
             bits = self.sync_faults()
         if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
             print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
@@ -394,12 +441,12 @@ class Engine:
             self.last_fallback = True
             self.set_option("conv_mode", 2)
             try:
-                coords, confs = self.predict_device(d_msa, template_ca, iterations, minsteps)
+                out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)
                 bits = self.sync_faults()
             finally:
                 self.set_option("conv_mode", 0)
         raise_for_faults(bits)
-        return coords, confs
+        return out
 
     def fetch(self, name, numel):
         out = torch.empty((int(numel),), dtype=torch.float32, device=self.device)
@@ -442,11 +489,14 @@ class Pipeline:
     of rounds 1-5 had - submit / pump / drain / result, step / poll / peek for the streaming batch front end, collect for
     the repeat of faulted targets."""
 
-    def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None):
+    def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
+                 distmap=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
-        (`set_converge`; `stats()` counts the passes run and saved)."""
+        (`set_converge`; `stats()` counts the passes run and saved).
+        `distmap`: every target also returns its chosen pass's distance map and [best_pass, passes_run, map_rms]
+        (`set_distmap`): `result`, `peek`, `collect` and `run` then give (coords, confs, distmap, info) per target."""
         self.lib = _lib.load()
         self.device = _resolve_device(device)
         S = max(1, int(streams))
@@ -469,7 +519,9 @@ class Pipeline:
             self.set_option("precision", prec)
         if converge is not None:
             self.set_converge(converge)
-        self._jobs = {}               # ticket -> (d_msa, iterations, minsteps, d_tpl, coords, confs, ready event): kept alive
+        if distmap:
+            self.set_distmap(True)
+        self._jobs = {}               # ticket -> (d_msa, iterations, minsteps, d_tpl, coords, confs, ready event, long buffer?): kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
     def set_option(self, name, value):
@@ -480,6 +532,18 @@ class Pipeline:
     def set_converge(self, converge):
         """Convergence tolerance (Angstrom; None or 0 = fixed depth) of every target submitted from now on; idle pipeline only."""
         self.set_option("recycle_tol_mA", converge_to_mA(converge))
+
+    def set_distmap(self, on):
+        """Option "emit_distmap" on every engine: targets submitted from now on return their distance map; idle pipeline only."""
+        self.set_option("emit_distmap", 1 if on else 0)
+
+    @staticmethod
+    def _outputs(job):
+        coords, confs, emit = job[4], job[5], job[7]
+        L = coords.shape[0]
+        if emit:                                           # an "emit_distmap" buffer: confs | map | info
+            return (coords,) + split_distmap_buffer(confs, L)
+        return coords, confs[:L]
 
     def close(self):
         if self._p:
@@ -515,7 +579,11 @@ class Pipeline:
                     raise RuntimeError(f"Sizes of tensors must match: template has {d_tpl.shape[0]} CA atoms, "
                                        f"alignment has {L} columns")
             coords = torch.empty((L, 5, 3), dtype=torch.float32, device=self.device)
-            confs = torch.empty((L,), dtype=torch.float32, device=self.device)
+            # the library cannot check the buffer: it is sized by the option as the engines hold it, whichever way it was
+            # set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
+            flags = [bool(e.get_option("emit_distmap")) for e in self.engines]
+            emit = all(flags)                             # the extension is handed out only if whichever engine runs it writes it
+            confs = torch.empty((distmap_floats(L, any(flags)),), dtype=torch.float32, device=self.device)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -530,7 +598,7 @@ class Pipeline:
             self._p, d_msa.data_ptr(), n, L, d_tpl.data_ptr() if d_tpl is not None else None,
             int(max(iterations, 0)), int(max(minsteps, 0)), coords.data_ptr(), confs.data_ptr(),
             C.c_void_p(ready.cuda_event)))
-        self._jobs[t] = (d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, coords, confs, ready)
+        self._jobs[t] = (d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, coords, confs, ready, emit)
         self._reap()
         return t
 
@@ -575,7 +643,7 @@ class Pipeline:
         job = self._jobs.pop(ticket)
         self._handed.append(ticket)
         self._reap()
-        return job[4], job[5]
+        return self._outputs(job)
 
     # ---- streaming use (dmpfold2_amd.batch): submit / step / poll, no barrier between targets ----------------
     def step(self, rounds=32):
@@ -607,8 +675,7 @@ class Pipeline:
                 return out
 
     def peek(self, ticket):
-        job = self._jobs[ticket]
-        return job[4], job[5]
+        return self._outputs(self._jobs[ticket])
 
     def stats(self):
         v = (C.c_longlong * 11)()
@@ -627,7 +694,8 @@ class Pipeline:
             _lib.check(self.lib.dmp_pipeline_pause(self._p, 0))
 
     def collect(self, tickets):
-        """drain + synchronise + verify.  Returns {ticket: (coords, confs) or Exception}: a target
+        """drain + synchronise + verify.  Returns {ticket: (coords, confs) - with `distmap` on (coords, confs, distmap,
+        info) - or Exception}: a target
         whose prediction recorded a device-side fault (its outputs are NaN) is repeated alone through
         `Engine.predict_device_checked` - which falls back to the range-free convolution where that
         is the cure - and only if that fails too its entry is the exception.  One bad target never
@@ -647,14 +715,14 @@ class Pipeline:
             for t in tickets:
                 st, bits, rc = self._status(t)
                 job = self._jobs.get(t)
-                coords, confs = self.result(t)
+                res = self.result(t)
                 if st == _T_FAILED:
                     out[t] = _lib.DmpError(_lib.load().dmp_last_error().decode("utf-8", "replace") or f"error {rc}")
                     continue
                 if bits:
                     d_msa, nloops, minsteps, d_tpl = job[:4]
                     try:
-                        coords, confs = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps)
+                        res = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps, distmap=job[7])
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
                         if not eng.get_option("vgru_persistent"):
@@ -665,13 +733,14 @@ class Pipeline:
                     except (IndexError, _lib.DmpError) as exc:
                         out[t] = exc
                         continue
-                out[t] = (coords, confs)
+                out[t] = res
         finally:
             eng.set_option("conv_mode", mode0)
         return out
 
     def run(self, d_msas, iterations=default_iterations, minsteps=default_minsteps):
-        """Predict every target (uint8 (N, L) tensors on the GPU).  Returns [(coords, confs)] in
+        """Predict every target (uint8 (N, L) tensors on the GPU).  Returns [(coords, confs)] ([(coords, confs, distmap,
+        info)] with `distmap` on) in
         input order, ordered on the current stream; the host is not synchronised with the tail."""
         tickets = self.submit_many(d_msas, iterations, minsteps)
         self.drain()
@@ -762,11 +831,14 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 # the reference's public functions
 # ---------------------------------------------------------------------------
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
-                  minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None):
+                  minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
+                  return_distmap=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
-    than this (RMS) - the answer `iterations` = that pass would have given (Engine.predict)."""
+    than this (RMS) - the answer `iterations` = that pass would have given (Engine.predict).
+    `return_distmap` (addition): the (L, L) predicted C-alpha distance map of the pass the best-of rule chose is appended
+    as the last element of the returned tuple (after `alnmat` when that is requested too)."""
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -775,10 +847,10 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     nseqs, length = alnmat.shape
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
         eng = get_engine(dev, length, nseqs, weights_file=weights_file)
-        coords, confs = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol)
-    if return_alnmat:
-        return coords, confs, alnmat
-    return coords, confs
+        out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap))
+    coords, confs = out[0], out[1]
+    ret = (coords, confs) + ((alnmat,) if return_alnmat else ()) + ((out[2],) if return_distmap else ())
+    return ret
 
 
 def pdb_text(coords, confs, alnmat):
@@ -802,7 +874,7 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208) and -c / --converge."""
+    """The reference's flags (predict.py:160-208), -c / --converge and --distmap."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -821,14 +893,19 @@ def dmpfold_parser():
     parser.add_argument("-c", "--converge", type=_tolerance_arg, default=None, required=False, metavar="TOL",
                         help="stop recycling once a pass changes the seed distance map by no more than TOL Angstrom (RMS); "
                              "default: always run all iteration cycles")
+    parser.add_argument("--distmap", type=str, default=None, required=False, metavar="FILE",
+                        help="also write the predicted C-alpha distance map of the chosen pass to FILE (float32 .npy, L x L)")
     return parser
 
 
 def run_dmpfold(argv=None):
     """Command-line entry point with the reference's flags (predict.py:160-208)."""
     args = dmpfold_parser().parse_args(argv)
-    coords, confs, alnmat = aln_to_coords(args.input_file, device=args.device,
-                                          template=args.template, iterations=args.iterations,
-                                          minsteps=args.minsteps, weights_file=args.model_weights,
-                                          return_alnmat=True, converge=args.converge)
+    out = aln_to_coords(args.input_file, device=args.device,
+                        template=args.template, iterations=args.iterations,
+                        minsteps=args.minsteps, weights_file=args.model_weights,
+                        return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None)
+    coords, confs, alnmat = out[:3]
+    if args.distmap is not None:
+        save_distmap_npy(args.distmap, out[3])
     sys.stdout.write(pdb_text(coords, confs, alnmat))

@@ -170,7 +170,29 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * kernel is launched and nothing ever waits.
  * "passes_run" (read only): the trunk passes of this context's last prediction, valid after dmp_predict_end (nloops + 1
  * unless "recycle_tol_mA" stopped it earlier).  The tickets of a pipeline do not carry their own count - that would take
- * a new entry point (an ABI 6); dmp_pipeline_stats has the sums. */
+ * a new entry point (an ABI 6); dmp_pipeline_stats has the sums (and "emit_distmap" hands every prediction, a
+ * pipeline's tickets included, its own count).
+ * "emit_distmap" (0 or 1, default 0; any other value: DMP_ERR_ARG): return the predicted C-alpha distance map of the pass
+ * the best-of rule chose.  Read when a prediction begins (dmp_predict, dmp_predict_begin_units) and held for it.  With it
+ * 0 no extra kernel is launched, nothing extra is written, and every output is bit for bit what it is without the
+ * option.  With it 1 THE d_conf ARGUMENT OF dmp_predict, dmp_predict_end AND dmp_pipeline_submit MUST HOLD
+ * L + L*L + 3 FLOATS (the library cannot check the size):
+ *   [0, L)          the confidences, unchanged
+ *   [L, L + L*L)    dm, row-major: dm[i][j] = |(h0[i][j] + h0[j][i]) * 0.5f| of the chosen pass, h0 the head's channel 0
+ *                   (network.py:237-243) - bit for bit the values that pass's Gram matrix, and through it the MDS
+ *                   embedding and the trace, were formed from.  dm is exactly symmetric.  Its DIAGONAL IS WHAT THE
+ *                   NETWORK PREDICTS, NOT ZERO.
+ *   L + L*L         best_pass: the 0-based pass the strict '>' rule on the mean confidence logit (network.py:302) kept,
+ *                   as a float
+ *   L + L*L + 1     passes_run: trunk passes run, as a float (nloops + 1, or fewer with "recycle_tol_mA"; exact below 2^24)
+ *   L + L*L + 2     map_rms = sqrt(mean over i < j of (dm[i][j] - |ca_i - ca_j|)^2) in Angstrom, ca the final, refined
+ *                   C-alpha trace the backbone is built from: how well the model realises the map it was derived from.
+ *                   The distances are formed in float64 from the float32 coordinates, sqrt((dx*dx + dy*dy) + dz*dz)
+ *                   with no clamp, the squares summed in float64 in a fixed order (the same bits on every run), and
+ *                   the result is rounded once to float32.  The reference has no such quantity.
+ * A prediction that latched a device-side fault returns NaN in all L + L*L + 3 floats.  Cost: one store in the best-of
+ * kernel always; with the option on one kernel per pass tail (keep_best_dm: workgroups of a pass that was not taken leave
+ * at once) and one in dmp_predict_end (emit_distmap), csrc/coords.hip.  A context holds max_L^2 floats for the map. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
@@ -341,7 +363,8 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
  * (seed distance channel = -1).  nloops = recycling iterations, refine_steps = minimiser
  * steps.  Outputs d_coords (L x 5 x 3) and d_conf (L).  No host synchronisation - unless option "recycle_tol_mA" is
  * set: the call then waits for the tail of every pass p >= 1 that has a successor (one event synchronisation per pass)
- * to learn whether to go on, and returns with the remaining work enqueued as always. */
+ * to learn whether to go on, and returns with the remaining work enqueued as always.
+ * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option). */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
                 int Lt, int nloops, int refine_steps, float* d_coords, float* d_conf,
                 void* stream);
@@ -395,7 +418,8 @@ int dmp_predict_group_riders(dmp_ctx* lead, int n, const uint8_t* const* d_msas,
  * chain touches none of the buffers the trunk uses).  d_vout must stay valid until that unit has run. */
 int dmp_predict_set_vgru_result(dmp_ctx* ctx, const float* d_vout, void* event);
 /* After the last unit: final refinement of the best trace + backbone + confidences into d_coords (L x 5 x 3) and
- * d_conf (L); a prediction during which a device-side fault was recorded returns NaN. */
+ * d_conf (L); a prediction during which a device-side fault was recorded returns NaN.
+ * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option). */
 int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream);
 int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream);
 int dmp_ctx_pending(dmp_ctx* ctx);
@@ -452,6 +476,8 @@ dmp_ctx* dmp_pipeline_ctx(dmp_pipeline* p, int i);
 void* dmp_pipeline_stream(dmp_pipeline* p, int i);
 int dmp_pipeline_weights_ready(dmp_pipeline* p);
 int dmp_pipeline_set_option(dmp_pipeline* p, const char* name, int value);
+/* d_coords: L x 5 x 3 floats, d_conf: L floats.  WITH OPTION "emit_distmap" = 1 ON THE PIPELINE d_conf MUST HOLD
+ * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run. */
 int64_t dmp_pipeline_submit(dmp_pipeline* p, const uint8_t* d_msa, int N, int L, const float* d_template_ca, int nloops,
                             int refine_steps, float* d_coords, float* d_conf, void* ready_event);
 int dmp_pipeline_wait(dmp_pipeline* p, int what);
@@ -479,7 +505,9 @@ int dmp_sync_faults(dmp_ctx* ctx, void* stream, int* h_bits);
 /* After dmp_predict: copy an internal tensor to d_dst (device).  Names: "w", "contacts",
  * "mat1d", "conf_means" (P floats), "ca_pass" (P x L x 3), "best_ca" (L x 3, before the final
  * refinement), "inv_cov" (21L x 21L), "mds" (L x 8) and "gram" (L x L) of the last pass, "pass_delta" (P floats: d_p of
- * option "recycle_tol_mA", +inf for pass 0; nothing - 0 floats - if the prediction ran with the option off).  Returns the number of floats written or a negative status. */
+ * option "recycle_tol_mA", +inf for pass 0; nothing - 0 floats - if the prediction ran with the option off), "best_dm" (L x L: the
+ * chosen pass's distance map of option "emit_distmap"; 0 floats if the prediction ran with the option off) and "best_pass"
+ * (1 float: the pass the best-of rule kept; always available).  Returns the number of floats written or a negative status. */
 int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t capacity,
                         void* stream);
 /* Optional HIP-event timing of every conv5x5 launch inside dmp_predict / dmp_trunk_pass / the unit calls (events
