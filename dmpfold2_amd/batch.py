@@ -31,6 +31,7 @@ import time
 import numpy as np
 import torch
 
+from . import score as _score
 from . import shard
 from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
                       pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy)
@@ -142,10 +143,20 @@ def ca_only_text(coords, confs, alnmat):
     return "\n".join(out)
 
 
-def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None):
+def split_extras(extra):
+    """What a Pipeline hands out behind (coords, confs) -> (distmap, info, score block), None for what is not there: two
+    tensors with "emit_distmap", then one with "score_native"."""
+    extra = tuple(extra)
+    dm, info = extra[:2] if len(extra) >= 2 else (None, None)
+    return dm, info, (extra[-1] if len(extra) % 2 else None)
+
+
+def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
-    the structure (float32, as `dmpfold --distmap` writes it)."""
+    the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
+    npz gains n_pairs, lnorm, rmsd, tm, gdt_ts, gdt_ha, lddt, counts, R, t, lddt_res and deviation; pdb / ca get
+    <stem>.scores.json (the line `dmpfold --native` prints)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -154,11 +165,19 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             h_info = info.detach().cpu().numpy()
             extra = {"distmap": distmap.detach().cpu().numpy(), "best_pass": np.int32(h_info[0]),
                      "passes_run": np.int32(h_info[1]), "map_rms": np.float32(h_info[2])}
+        if scores is not None:
+            extra.update({"n_pairs": np.int32(scores["n_pairs"]), "lnorm": np.float32(scores["lnorm"]),
+                          "counts": np.asarray(scores["counts"], dtype=np.int32)})
+            extra.update({k: np.float32(scores[k]) for k in _score.SCORE_NAMES[1:]})
+            extra.update({k: np.asarray(scores[k], dtype=np.float32) for k in ("R", "t", "lddt_res", "deviation")})
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
     if distmap is not None:
         save_distmap_npy(stem + ".distmap.npy", distmap)
+    if scores is not None:
+        with open(stem + ".scores.json", "w") as fh:
+            fh.write(json.dumps(_score.scores_json(scores)) + "\n")
     path = stem + ".pdb"
     with open(path, "w") as fh:
         fh.write(pdb_text(coords, confs, alnmat) if fmt == "pdb" else ca_only_text(coords, confs, alnmat))
@@ -207,8 +226,11 @@ def cost_order(targets, iterations):
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
-              converge=None, stats_out=None, distmap=False):
+              converge=None, stats_out=None, distmap=False, natives=None):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
+    `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
+    the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
+    unscored.  `stats_out` then receives "scores": {stem: the dict of score.scores_json}.
     `distmap`: every target's chosen-pass distance map is brought back and written too (write_result).
     `converge` (Angstrom, None = off): targets stop recycling once converged (Pipeline.set_converge); `stats_out`, a
     dict, then receives this rank's "passes_run" and "passes_saved".
@@ -253,6 +275,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_converge(converge)
             if distmap:
                 pipe.set_distmap(True)
+            if natives:
+                pipe.set_score(True)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -284,15 +308,28 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         while copying and (copying[0][2] is None or copying[0][2].query()):
             done.append(copying.pop(0)[:2])
 
+    scored, all_scores = set(), {}
+
+    def unpack(aln_path, t, extra):
+        """(distmap, info, scores) of a target's extras; the scores only if it had a native"""
+        dm, info, block = split_extras(extra)
+        sc = None
+        if block is not None and t in scored:
+            sc = _score.unpack_scores(block, alnmat_len[t])
+            all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = _score.scores_json(sc)
+        return dm, info, sc
+
+    alnmat_len = {}
+
     def finish(item):
-        t, (coords, confs, *dm) = item
+        t, (coords, confs, *extra) = item
         aln_path, alnmat, _ = parsed.pop(t)
         if bool(torch.isnan(confs[:1]).any()):          # a device-side fault poisoned it: repeated alone at the end
             parsed[t] = (aln_path, alnmat, None)
             faulted.append(t)
             return
         pipe.result(t)
-        outputs.append(write_result(out_dir, aln_path, coords, confs, alnmat, fmt, *dm))
+        outputs.append(write_result(out_dir, aln_path, coords, confs, alnmat, fmt, *unpack(aln_path, t, extra)))
 
     exhausted = False
     cap = 2 * max(1, int(streams))                      # started + queued per rank
@@ -311,6 +348,11 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             rows = read_a3m(aln_path) if aln_path.endswith(".a3m") else read_aln(aln_path)
             tpl = read_template_ca(tpl_path) if tpl_path else None
             alnmat = encode_aln(rows)
+            nat = None
+            if natives:
+                nat_path = os.path.join(natives, os.path.splitext(os.path.basename(aln_path))[0] + ".pdb")
+                if os.path.exists(nat_path):
+                    nat = _score.native_from_pdb(rows[0], nat_path)
             p = ensure_pipe()
             h_msa = torch.from_numpy(np.ascontiguousarray(alnmat))
             with (torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext()):
@@ -321,7 +363,11 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                     d_msa = h_msa
                 # the pinned source stays alive in `parsed` until the target is written; the engine that takes the
                 # target orders its stream behind the stream that is current at submission (the copy stream)
-                parsed[p.submit(d_msa, iterations, minsteps, template_ca=tpl)] = (aln_path, alnmat, h_msa)
+                t = p.submit(d_msa, iterations, minsteps, template_ca=tpl, **({"native": nat} if nat is not None else {}))
+                parsed[t] = (aln_path, alnmat, h_msa)
+                alnmat_len[t] = alnmat.shape[1]
+                if nat is not None:
+                    scored.add(t)
         except (IndexError, ValueError, OSError, UnicodeDecodeError, RuntimeError) as exc:
             # unknown residue letter / ragged rows / unreadable file / larger than the scan said: this target only
             failed.append((aln_path, exc))
@@ -377,12 +423,15 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             if isinstance(res[t], Exception):
                 failed.append((aln_path, res[t]))
             else:
-                outputs.append(write_result(out_dir, aln_path, res[t][0], res[t][1], alnmat, fmt, *res[t][2:]))
+                outputs.append(write_result(out_dir, aln_path, res[t][0], res[t][1], alnmat, fmt,
+                                            *unpack(aln_path, t, res[t][2:])))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:
             st = pipe.stats()
             stats_out["passes_run"], stats_out["passes_saved"] = st["passes_run"], st["passes_saved"]
+        if stats_out is not None and natives:
+            stats_out["scores"] = all_scores
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
@@ -409,7 +458,22 @@ def batch_parser():
     ap.add_argument("--distmap", action="store_true",
                     help="also write every target's predicted C-alpha distance map (the pass the best-of rule chose): npz "
                          "gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca write <stem>.distmap.npy")
+    ap.add_argument("--natives", default=None, metavar="DIR",
+                    help="directory of native structures, <stem>.pdb per target: such targets are scored on the GPU (TM-score, "
+                         "GDT, RMSD, lDDT-CA); the summary gains the per-target scores, their means and medians; npz gains the "
+                         "arrays, pdb / ca write <stem>.scores.json; a target without a file is predicted unscored")
     return ap
+
+
+def score_summary(scores):
+    """{stem: scores} -> the summary's part: the per-target scores, and mean and median of each score over the targets
+    that have it."""
+    out = {"scored_targets": len(scores), "scores": scores}
+    for name in ("tm", "gdt_ts", "gdt_ha", "rmsd", "lddt"):
+        vals = [s[name] for s in scores.values() if s.get(name) is not None]
+        out["mean_" + name] = float(np.mean(vals)) if vals else None
+        out["median_" + name] = float(np.median(vals)) if vals else None
+    return out
 
 
 def main(argv=None):
@@ -439,7 +503,7 @@ def main(argv=None):
         n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                   weights_file=args.model_weights, streams=args.streams,
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
-                                  converge=args.converge, stats_out=passes, distmap=args.distmap)
+                                  converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -449,6 +513,8 @@ def main(argv=None):
         # this rank had already taken from the shared queue is lost with it: the summary says so
         print(f"dmpfold-batch: rank {rank}: {type(exc).__name__}: {exc}", file=sys.stderr)
         n, elapsed, status, broke = 0, 0.0, 2, 1
+    if args.natives and world > 1:                   # host side, through the job's key-value store: read behind the reduction
+        job_store.set(f"dmpfold_batch_scores/{rank}", json.dumps(passes.get("scores", {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
         passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
@@ -460,6 +526,11 @@ def main(argv=None):
                                "compare it with the target list" % broke_all)
         if args.converge is not None:
             summary["converge"], summary["passes_run"], summary["passes_saved"] = args.converge, passes_all[0], passes_all[1]
+        if args.natives:
+            scores = dict(passes.get("scores", {}))
+            for r in range(1, world):
+                scores.update(json.loads(job_store.get(f"dmpfold_batch_scores/{r}").decode()))
+            summary.update(score_summary(dict(sorted(scores.items()))))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

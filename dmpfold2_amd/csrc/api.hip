@@ -406,14 +406,17 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // invalid structure can never be mistaken for a result, and a batch can tell WHICH target failed) and
 // the fault bits are latched into the word dmp_sync_faults reports.
 // `nconf`: the floats behind `conf` - L, or L + L*L + 3 with option "emit_distmap" (the whole extension becomes NaN too).
+// `nscore`: 0, or 5L + 24 with option "score_native": the score block behind those; its outputs [3L + 1, 5L + 24) become NaN,
+// its inputs (the native trace and lnorm) are the caller's and stay.
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
-                                   float* __restrict__ conf, int L, int64_t nconf, int* __restrict__ report) {
+                                   float* __restrict__ conf, int L, int64_t nconf, int64_t nscore, int* __restrict__ report) {
   const int f = words[0];
   if (!f) return;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const float nan = __builtin_nanf("");
   if (i < 15 * L) coords[i] = nan;
   if (i < nconf) conf[i] = nan;
+  else if (i >= nconf + 3 * L + 1 && i < nconf + nscore) conf[i] = nan;
   if (i == 0) {
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
@@ -518,11 +521,19 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(best_dm, LL);
   A_(rms_partial, 64);
   A_(rms_counter, 1);
+  A_(score_pm, 3 * L);
+  A_(score_qn, 3 * L);
+  A_(score_idx, L);
+  A_(score_hdr, 8);
+  A_(score_rec, 6 * L * SCORE_REC);
+  A_(score_tot, 2);
+  A_(score_ticket, 1);
 #undef A_
   if (rc) { dmp_ctx_destroy(c); return rc; }
   if (hipMemset(c->seq_abort, 0, 2 * sizeof(int)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->delta_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->rms_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  if (hipMemset(c->score_ticket, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   // the word recycle_delta tells the host its stop decision through (read only after the pass tail's event)
   if (hipHostMalloc((void**)&c->delta_host, sizeof(int), hipHostMallocMapped) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   *c->delta_host = 0;
@@ -592,6 +603,11 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->emit_distmap = value;
     return DMP_OK;
   }
+  if (k == "score_native") {         // takes effect with the next prediction begun
+    DMP_ARG(value == 0 || value == 1, "score_native must be 0 or 1, got %d", value);
+    ctx->score_native = value;
+    return DMP_OK;
+  }
   DMP_ARG(k != "passes_run", "passes_run is read only");
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -634,6 +650,7 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "gj_diag_blocked") { *h_value = ctx->gj_diag_blocked; return DMP_OK; }
   if (k == "recycle_tol_mA") { *h_value = ctx->recycle_tol_mA; return DMP_OK; }
   if (k == "emit_distmap") { *h_value = ctx->emit_distmap; return DMP_OK; }
+  if (k == "score_native") { *h_value = ctx->score_native; return DMP_OK; }
   if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -1199,6 +1216,7 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   c->end_refined = false;
   c->run_tol_mA = c->recycle_tol_mA;
   c->run_emit = c->emit_distmap;
+  c->run_score = c->score_native;
   c->gate_pass = 0;
   c->run_nloops = nloops < 0 ? 0 : nloops;
   c->run_refine = refine_steps < 0 ? 0 : refine_steps;
@@ -1399,8 +1417,11 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // option "emit_distmap": d_conf holds L + L*L + 3 floats; the map, {best_pass, passes_run, map_rms} behind the confidences
   const int64_t nconf = c->run_emit ? (int64_t)L + (int64_t)L * L + 3 : L;
   if (c->run_emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + L, s))) return rc;
-  hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, nconf), 256)), dim3(256), 0, s,
-                     c->seq_abort, d_coords, d_conf, L, nconf, c->end_fault_out);
+  // option "score_native": the score block of 5L + 24 floats behind that, the native trace and lnorm in it (score.hip)
+  const int64_t nscore = c->run_score ? 5 * (int64_t)L + 24 : 0;
+  if (c->run_score && (rc = score_native(c, d_coords, L, d_conf + nconf, s))) return rc;
+  hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, nconf + nscore), 256)), dim3(256), 0, s,
+                     c->seq_abort, d_coords, d_conf, L, nconf, nscore, c->end_fault_out);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

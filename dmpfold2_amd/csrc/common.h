@@ -257,6 +257,16 @@ struct dmp_ctx {
   float* best_dm = nullptr;        // [max_L][max_L] dm of that pass (coords.hip: keep_best_dm; only with the option on)
   double* rms_partial = nullptr;   // [64] per-workgroup sums of emit_distmap
   unsigned* rms_counter = nullptr;
+  // option "score_native": the model scored against a native C-alpha trace in the d_conf buffer (include/dmpfold_hip.h)
+  int score_native = 0;
+  int run_score = 0;               // ... as the prediction in flight began with it
+  float* score_pm = nullptr;       // [max_L][3] model trace, rows with a native residue only (score.hip: score_prep)
+  float* score_qn = nullptr;       // [max_L][3] native trace, the same rows
+  int* score_idx = nullptr;        // [max_L] alignment column of each such row
+  double* score_hdr = nullptr;     // [8] n, lnorm, d0, d_cut
+  double* score_rec = nullptr;     // [6 max_L][SCORE_REC] one record per seed of the superposition search
+  unsigned long long* score_tot = nullptr;   // [2] lDDT: preserved, pairs
+  unsigned* score_ticket = nullptr;          // zero between launches
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -489,6 +499,8 @@ int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int p
 int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, hipStream_t s);
 int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
 int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_ext, hipStream_t s);
+constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
+int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);

@@ -1,0 +1,456 @@
+// option "score_native": the prediction scored against a native C-alpha trace (include/dmpfold_hip.h has the layout of
+// the score block and the definition of every number).  Three launches in dmp_predict_end behind ca_to_backbone:
+//   score_prep    one workgroup: the rows that have a native residue, packed in sequence order (model trace from
+//                 d_coords[:, 1], native from the block), n, lnorm, d0, d_cut; NaN into every out slot but n_pairs.
+//   score_lddt    rows dealt to the workgroups: integer counts, so lDDT is exact and order-free.
+//   score_search  one workgroup per seed of the superposition search; the last arriver (agent-scope ticket, as in
+//                 recycle_delta_kernel) reduces the seeds' records in seed order and writes the header and the deviations.
+// Float64 from the float32 coordinates throughout; every sum has a fixed per-thread order, a fixed butterfly inside a
+// wave (both partners of an exchange form a + b, so all 64 lanes hold the same bits) and a fixed order over the four
+// waves' partial sums in LDS: the same bits on every run, and every thread of a workgroup takes the same branch.
+// Nothing here is a reference computation, so contraction is switched off only to keep the bits independent of the
+// compiler's choices.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace dmp {
+
+constexpr int SC_THREADS = 256;
+constexpr int SC_WAVES = SC_THREADS / 64;
+constexpr int SC_ITERS = 20;
+constexpr int SC_LDDT_MAX_WG = 64;
+// a seed's record (SCORE_REC doubles): tm, the five counts, R (9), t (3), rmsd (seed 0 only), spare
+constexpr int REC_TM = 0, REC_CNT = 1, REC_R = 6, REC_T = 15, REC_RMSD = 18;
+// header of the scratch: n, lnorm, d0, d_cut
+constexpr int HDR_N = 0, HDR_LNORM = 1, HDR_D0 = 2, HDR_DCUT = 3;
+
+// The distinct fragment lengths f_0 = n, f_k = max(n >> k, min(4, n)), k = 1..5, in level order (they never increase, so
+// a repeat is a repeat of the one before); returns how many.
+__host__ __device__ inline int score_levels(int n, int f[6]) {
+  const int lo = n < 4 ? n : 4;
+  int m = 0;
+  for (int k = 0; k <= 5; ++k) {
+    const int v = k == 0 ? n : ((n >> k) > lo ? (n >> k) : lo);
+    if (m == 0 || f[m - 1] != v) f[m++] = v;
+  }
+  return m;
+}
+
+// Seeds of n rows: every start of every distinct fragment length.  Never decreases with n (n - f_k + 1 does not, and a
+// longer chain has no fewer distinct levels), so a grid sized for L covers every n <= L; at most 1 + 5n.
+__host__ __device__ inline int score_seeds(int n) {
+  int f[6];
+  const int m = score_levels(n, f);
+  int total = 0;
+  for (int q = 0; q < m; ++q) total += n - f[q] + 1;
+  return total;
+}
+
+// Rotation R (row-major) maximising sum_k q_k . R p_k from the covariance M[a][b] = sum_k p_a q_b of the centred sets:
+// the eigenvector of the largest eigenvalue of Horn's symmetric 4 x 4 matrix (J. Opt. Soc. Am. A 4, 629, 1987), by cyclic
+// Jacobi rotations in float64.  Unlike the Newton iteration on the characteristic polynomial (QCP) it loses nothing when
+// M is singular - three points, a planar set - where two eigenvalues of the polynomial approach each other.  A bounded
+// number of sweeps whatever the input holds (NaN included).
+__host__ __device__ inline void horn_rotation(const double M[9], double R[9]) {
+  const double Sxx = M[0], Sxy = M[1], Sxz = M[2], Syx = M[3], Syy = M[4], Syz = M[5], Szx = M[6], Szy = M[7], Szz = M[8];
+  double A[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                    {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                    {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
+                    {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
+  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    double off = 0.0, diag = 0.0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      diag += A[p][p] * A[p][p];
+#pragma unroll
+      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
+    }
+    if (off <= 1e-36 * diag || off == 0.0) break;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < 4; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {          // A <- A J
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = cs * akp - sn * akq;
+          A[k][q] = sn * akp + cs * akq;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {          // A <- J^T A
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = cs * apk - sn * aqk;
+          A[q][k] = sn * apk + cs * aqk;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {          // V <- V J: the columns of V stay the eigenvectors
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = cs * vkp - sn * vkq;
+          V[k][q] = sn * vkp + cs * vkq;
+        }
+      }
+    }
+  }
+  double w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0], top = A[0][0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j)
+    if (A[j][j] > top) { top = A[j][j]; w = V[0][j]; x = V[1][j]; y = V[2][j]; z = V[3][j]; }
+  const double nrm = sqrt((w * w + x * x) + (y * y + z * z));
+  w /= nrm; x /= nrm; y /= nrm; z /= nrm;
+  R[0] = w * w + x * x - y * y - z * z; R[1] = 2.0 * (x * y - w * z);         R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z);         R[4] = w * w - x * x + y * y - z * z; R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y);         R[7] = 2.0 * (y * z + w * x);         R[8] = w * w - x * x - y * y + z * z;
+}
+
+// |R p + t - q|
+__device__ inline double score_dev(const double* R, const double* t, const float* p, const float* q) {
+  const double px = p[0], py = p[1], pz = p[2];
+  const double ex = (((R[0] * px + R[1] * py) + R[2] * pz) + t[0]) - (double)q[0];
+  const double ey = (((R[3] * px + R[4] * py) + R[5] * pz) + t[1]) - (double)q[1];
+  const double ez = (((R[6] * px + R[7] * py) + R[8] * pz) + t[2]) - (double)q[2];
+  return sqrt((ex * ex + ey * ey) + ez * ez);
+}
+
+__device__ inline double score_dist(const float* a, const float* b) {
+  const double ux = (double)a[0] - (double)b[0], uy = (double)a[1] - (double)b[1], uz = (double)a[2] - (double)b[2];
+  return sqrt((ux * ux + uy * uy) + uz * uz);
+}
+
+// Sum of K values per thread over the workgroup, left in v[] of EVERY thread.  `wred` is reused by the next call: the
+// leading barrier keeps its writers behind the previous call's readers.
+template <int K>
+__device__ inline void score_block_sum(double (&v)[K], double (*wred)[16]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) wred[wv][k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = ((wred[0][k] + wred[1][k]) + wred[2][k]) + wred[3][k];
+}
+
+__device__ inline void score_store(double* p, double v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ inline double score_load(double* p) {
+  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(p), __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT));
+}
+
+struct ScoreArgs {
+  const float* coords;   // [L][5][3] the backbone; the model trace is atom 1
+  float* blk;            // the score block: [0, 3L) native (in), 3L lnorm (in), the rest out
+  int L;
+  float* pm;             // [n][3] packed model trace
+  float* qn;             // [n][3] packed native trace
+  int* idx;              // [n] alignment column of a packed row
+  double* hdr;           // [8]
+  double* rec;           // [seeds][SCORE_REC]
+  unsigned long long* tot;   // [2] lDDT: preserved, pairs
+  unsigned* ticket;      // zero between launches
+};
+
+// ---------------------------------------------------------------------------------------
+// score_prep: pack the present rows, the constants, NaN into the out slots
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SC_THREADS) void score_prep_kernel(ScoreArgs a) {
+  __shared__ int cnt[SC_THREADS];
+  const int L = a.L, tid = threadIdx.x;
+  const int chunk = (L + SC_THREADS - 1) / SC_THREADS;
+  const int r0 = tid * chunk < L ? tid * chunk : L, r1 = r0 + chunk < L ? r0 + chunk : L;
+  int mine = 0;
+  for (int i = r0; i < r1; ++i) {
+    const float x = a.blk[3 * i];
+    mine += x == x ? 1 : 0;
+  }
+  cnt[tid] = mine;
+  __syncthreads();
+  int at = 0, n = 0;
+  for (int k = 0; k < SC_THREADS; ++k) {
+    if (k < tid) at += cnt[k];
+    n += cnt[k];
+  }
+  for (int i = r0; i < r1; ++i) {
+    const float x = a.blk[3 * i];
+    if (x == x) {
+      for (int c = 0; c < 3; ++c) {
+        a.pm[3 * at + c] = a.coords[15 * (int64_t)i + 3 + c];
+        a.qn[3 * at + c] = a.blk[3 * i + c];
+      }
+      a.idx[at] = i;
+      ++at;
+    }
+  }
+  const float nan = __builtin_nanf("");
+  float* out = a.blk + 3 * L + 1;
+  for (int i = tid; i < 2 * L + 23; i += SC_THREADS) out[i] = i == 0 ? (float)n : nan;
+  if (tid == 0) {
+    const double given = (double)a.blk[3 * L];
+    const double lnorm = given == 0.0 ? (double)n : given;
+    const double d0 = lnorm > 15.0 ? fmax(1.24 * cbrt(lnorm - 15.0) - 1.8, 0.5) : 0.5;
+    a.hdr[HDR_N] = (double)n;
+    a.hdr[HDR_LNORM] = lnorm;
+    a.hdr[HDR_D0] = d0;
+    a.hdr[HDR_DCUT] = fmin(fmax(d0, 4.5), 8.0);
+    a.tot[0] = 0ull;
+    a.tot[1] = 0ull;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// score_lddt: superposition-free, integer counts
+// ---------------------------------------------------------------------------------------
+__host__ __device__ inline int score_lddt_groups(int L) {
+  const int g = L / 16;
+  return g < 1 ? 1 : (g > SC_LDDT_MAX_WG ? SC_LDDT_MAX_WG : g);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void score_lddt_kernel(ScoreArgs a) {
+  extern __shared__ float sm[];          // 2 x 3n coordinates
+  __shared__ int ired[SC_WAVES][2];
+  const int n = (int)a.hdr[HDR_N], L = a.L, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (n < 3) return;                     // every out slot but n_pairs stays NaN
+  float* pm = sm;
+  float* qn = sm + 3 * n;
+  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = a.pm[i]; qn[i] = a.qn[i]; }
+  __syncthreads();
+  float* out = a.blk + 3 * L + 24;
+  unsigned long long tot_pres = 0ull, tot_part = 0ull;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    int pres = 0, part = 0;
+    for (int j = tid; j < n; j += SC_THREADS) {
+      if (j == i) continue;
+      const double dn = score_dist(qn + 3 * i, qn + 3 * j);
+      if (dn < 15.0) {
+        const double e = fabs(score_dist(pm + 3 * i, pm + 3 * j) - dn);
+        part += 1;
+        pres += (e < 0.5 ? 1 : 0) + (e < 1.0 ? 1 : 0) + (e < 2.0 ? 1 : 0) + (e < 4.0 ? 1 : 0);
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      pres += __shfl_xor(pres, off, 64);
+      part += __shfl_xor(part, off, 64);
+    }
+    __syncthreads();
+    if (lane == 0) { ired[wv][0] = pres; ired[wv][1] = part; }
+    __syncthreads();
+    if (tid == 0) {
+      pres = part = 0;
+      for (int k = 0; k < SC_WAVES; ++k) { pres += ired[k][0]; part += ired[k][1]; }
+      out[a.idx[i]] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
+      tot_pres += (unsigned long long)pres;
+      tot_part += (unsigned long long)part;
+    }
+  }
+  if (tid == 0) {
+    __hip_atomic_fetch_add(&a.tot[0], tot_pres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&a.tot[1], tot_part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// score_search: one workgroup per seed
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
+  extern __shared__ float sm[];          // 2 x 3n coordinates, then n flags: the set S
+  __shared__ double wred[SC_WAVES][16];
+  __shared__ double bc[12];              // R, t of this iteration (at the end: of the best seed)
+  __shared__ int sh_last, sh_seed[SC_WAVES];
+  const int n = (int)a.hdr[HDR_N], L = a.L, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (n < 3) return;
+  int nseeds = score_seeds(n);
+  if (nseeds > (int)gridDim.x) nseeds = (int)gridDim.x;     // never: score_seeds does not decrease with n, the grid is score_seeds(L)
+  if ((int)blockIdx.x >= nseeds) return;
+  const double lnorm = a.hdr[HDR_LNORM], d0 = a.hdr[HDR_D0], d_cut = a.hdr[HDR_DCUT];
+  // (level, start) of this seed
+  int frag, start = (int)blockIdx.x;
+  {
+    int f[6];
+    const int m = score_levels(n, f);
+    int q = 0;
+    while (q < m - 1 && start >= n - f[q] + 1) { start -= n - f[q] + 1; ++q; }
+    frag = f[q];
+  }
+  float* pm = sm;
+  float* qn = sm + 3 * n;
+  unsigned char* fl = reinterpret_cast<unsigned char*>(sm + 6 * n);
+  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = a.pm[i]; qn[i] = a.qn[i]; }
+  for (int k = tid; k < n; k += SC_THREADS) fl[k] = (k >= start && k < start + frag) ? 1 : 0;
+  __syncthreads();
+
+  // thread 0 keeps the seed's best
+  double best_tm = -1.0, best_R[9], best_t[3], best_cnt[5] = {0, 0, 0, 0, 0}, rmsd = 0.0;
+  for (int c = 0; c < 9; ++c) best_R[c] = 0.0;
+  for (int c = 0; c < 3; ++c) best_t[c] = 0.0;
+
+  for (int it = 0; it < SC_ITERS; ++it) {
+    // a thread owns the rows k = tid, tid + 256, ...: it alone reads and writes their flags
+    double s7[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int k = tid; k < n; k += SC_THREADS)
+      if (fl[k]) {
+        s7[0] += 1.0;
+        for (int c = 0; c < 3; ++c) { s7[1 + c] += (double)pm[3 * k + c]; s7[4 + c] += (double)qn[3 * k + c]; }
+      }
+    score_block_sum<7>(s7, wred);
+    const double pc[3] = {s7[1] / s7[0], s7[2] / s7[0], s7[3] / s7[0]};
+    const double qc[3] = {s7[4] / s7[0], s7[5] / s7[0], s7[6] / s7[0]};
+    double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = tid; k < n; k += SC_THREADS)
+      if (fl[k]) {
+        const double px = (double)pm[3 * k] - pc[0], py = (double)pm[3 * k + 1] - pc[1], pz = (double)pm[3 * k + 2] - pc[2];
+        const double qx = (double)qn[3 * k] - qc[0], qy = (double)qn[3 * k + 1] - qc[1], qz = (double)qn[3 * k + 2] - qc[2];
+        M[0] += px * qx; M[1] += px * qy; M[2] += px * qz;
+        M[3] += py * qx; M[4] += py * qy; M[5] += py * qz;
+        M[6] += pz * qx; M[7] += pz * qy; M[8] += pz * qz;
+      }
+    score_block_sum<9>(M, wred);
+    if (tid == 0) {
+      double R[9];
+      horn_rotation(M, R);
+      for (int c = 0; c < 9; ++c) bc[c] = R[c];
+      for (int c = 0; c < 3; ++c) bc[9 + c] = qc[c] - ((R[3 * c] * pc[0] + R[3 * c + 1] * pc[1]) + R[3 * c + 2] * pc[2]);
+    }
+    __syncthreads();
+    double R[9], t[3];
+    for (int c = 0; c < 9; ++c) R[c] = bc[c];
+    for (int c = 0; c < 3; ++c) t[c] = bc[9 + c];
+    // tm sum, the five counts, |S'|, rows whose flag changed, sum of squares
+    double s9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = tid; k < n; k += SC_THREADS) {
+      const double d = score_dev(R, t, pm + 3 * k, qn + 3 * k);
+      const double r = d / d0;
+      s9[0] += 1.0 / (1.0 + r * r);
+      s9[1] += d < 0.5 ? 1.0 : 0.0;
+      s9[2] += d < 1.0 ? 1.0 : 0.0;
+      s9[3] += d < 2.0 ? 1.0 : 0.0;
+      s9[4] += d < 4.0 ? 1.0 : 0.0;
+      s9[5] += d < 8.0 ? 1.0 : 0.0;
+      const unsigned char in = d < d_cut ? 1 : 0;
+      s9[6] += (double)in;
+      s9[7] += in != fl[k] ? 1.0 : 0.0;
+      s9[8] += d * d;
+      fl[k] = in;
+    }
+    score_block_sum<9>(s9, wred);
+    if (tid == 0) {
+      const double tm = s9[0] / lnorm;
+      if (tm > best_tm) {
+        best_tm = tm;
+        for (int c = 0; c < 9; ++c) best_R[c] = R[c];
+        for (int c = 0; c < 3; ++c) best_t[c] = t[c];
+      }
+      for (int c = 0; c < 5; ++c) best_cnt[c] = fmax(best_cnt[c], s9[1 + c]);
+      if (it == 0) rmsd = sqrt(s9[8] / (double)n);       // meaningful for seed 0: S is the whole chain there
+    }
+    // the same bits in every thread: a uniform branch.  (A NaN keeps the loop going to its bound.)
+    if (s9[6] < 3.0 || s9[7] == 0.0) break;
+  }
+
+  if (tid == 0) {
+    double* rec = a.rec + (int64_t)blockIdx.x * SCORE_REC;
+    score_store(rec + REC_TM, best_tm);
+    for (int c = 0; c < 5; ++c) score_store(rec + REC_CNT + c, best_cnt[c]);
+    for (int c = 0; c < 9; ++c) score_store(rec + REC_R + c, best_R[c]);
+    for (int c = 0; c < 3; ++c) score_store(rec + REC_T + c, best_t[c]);
+    score_store(rec + REC_RMSD, rmsd);
+    const unsigned before = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    sh_last = before == (unsigned)nseeds - 1u ? 1 : 0;     // the last arriver: every record is behind its owner's release
+    if (sh_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  }
+  __syncthreads();
+  if (!sh_last) return;
+
+  // the last arriver: the best seed (ties: the lowest number) and the maximum of each count, every thread over its share of
+  // the records (agent-scope loads), then a butterfly and the four waves in order - a maximum does not depend on the order
+  double top = -__builtin_inf();
+  int top_seed = 0x7fffffff;
+  double cmax[5] = {0, 0, 0, 0, 0};
+  for (int s = tid; s < nseeds; s += SC_THREADS) {
+    double* rec = a.rec + (int64_t)s * SCORE_REC;
+    const double tm = score_load(rec + REC_TM);
+    if (tm > top) { top = tm; top_seed = s; }          // s rises: the first of equals stays
+    for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], score_load(rec + REC_CNT + c));
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o_top = __shfl_xor(top, off, 64);
+    const int o_seed = __shfl_xor(top_seed, off, 64);
+    if (o_top > top || (o_top == top && o_seed < top_seed)) { top = o_top; top_seed = o_seed; }
+    for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], __shfl_xor(cmax[c], off, 64));
+  }
+  __syncthreads();
+  if (lane == 0) {
+    wred[wv][0] = top;
+    sh_seed[wv] = top_seed;
+    for (int c = 0; c < 5; ++c) wred[wv][1 + c] = cmax[c];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < SC_WAVES; ++k) {
+      if (wred[k][0] > top || (wred[k][0] == top && sh_seed[k] < top_seed)) { top = wred[k][0]; top_seed = sh_seed[k]; }
+      for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], wred[k][1 + c]);
+    }
+    float* out = a.blk + 3 * L;
+    const float nan = __builtin_nanf("");
+    const bool found = top_seed != 0x7fffffff;         // false only if every seed's tm is NaN
+    double* rec = a.rec + (int64_t)(found ? top_seed : 0) * SCORE_REC;
+    out[2] = (float)score_load(a.rec + REC_RMSD);
+    out[3] = found ? (float)top : nan;
+    out[4] = (float)((((cmax[1] + cmax[2]) + cmax[3]) + cmax[4]) / 4.0 / lnorm);
+    out[5] = (float)((((cmax[0] + cmax[1]) + cmax[2]) + cmax[3]) / 4.0 / lnorm);
+    const unsigned long long pres = a.tot[0], part = a.tot[1];     // score_lddt ran before this launch
+    out[6] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
+    for (int c = 0; c < 5; ++c) out[7 + c] = (float)cmax[c];
+    for (int c = 0; c < 12; ++c) {
+      const double v = score_load(rec + REC_R + c);
+      bc[c] = v;
+      out[12 + c] = found ? (float)v : nan;
+    }
+    sh_last = found ? 1 : 0;
+    __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (!sh_last) return;                                // the deviations stay NaN
+  double R[9], t[3];
+  for (int c = 0; c < 9; ++c) R[c] = bc[c];
+  for (int c = 0; c < 3; ++c) t[c] = bc[9 + c];
+  float* dev = a.blk + 4 * L + 24;
+  for (int k = tid; k < n; k += SC_THREADS) dev[a.idx[k]] = (float)score_dev(R, t, pm + 3 * k, qn + 3 * k);
+}
+
+int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
+  ScoreArgs a{};
+  a.coords = d_coords;
+  a.blk = d_block;
+  a.L = L;
+  a.pm = c->score_pm;
+  a.qn = c->score_qn;
+  a.idx = c->score_idx;
+  a.hdr = c->score_hdr;
+  a.rec = c->score_rec;
+  a.tot = c->score_tot;
+  a.ticket = c->score_ticket;
+  hipLaunchKernelGGL(score_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a);
+  DMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(score_lddt_kernel, dim3(score_lddt_groups(L)), dim3(SC_THREADS), sizeof(float) * 6 * L, s, a);
+  DMP_LAUNCH_CHECK();
+  // the records hold 6 max_L seeds >= 1 + 5L; 6L floats + L flags of LDS: 50 KB at L = 2048
+  hipLaunchKernelGGL(score_search_kernel, dim3(score_seeds(L)), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+}  // namespace dmp

@@ -18,12 +18,15 @@ Differences from the reference, all additive or forced by the environment:
   * `converge` (Angstrom, None / 0 = off, the default): recycling stops after the first pass that moves the seed
     distance map by no more than that (RMS); the result is then the one `iterations` = that pass would have given;
   * `distmap` / `return_distmap` / `dmpfold --distmap FILE`: the predicted C-alpha distance map of the pass the best-of
-    rule chose (option "emit_distmap" of include/dmpfold_hip.h) comes back with the structure.
+    rule chose (option "emit_distmap" of include/dmpfold_hip.h) comes back with the structure;
+  * `native` / `return_scores` / `dmpfold --native PDB`: the model is scored against a native structure on the GPU
+    (option "score_native": TM-score, GDT, RMSD, lDDT-C-alpha; dmpfold2_amd/score.py has the host side).
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
+import json
 import os
 import sys
 import threading
@@ -33,6 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import score as _score
 
 default_device = "cuda"
 default_iterations = 10
@@ -298,8 +302,11 @@ class Engine:
         self.weights_tag = other.weights_tag
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
-                minsteps=default_minsteps, converge=None, distmap=False):
+                minsteps=default_minsteps, converge=None, distmap=False, native=None):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `native` (an (L, 3) array, one native C-alpha per alignment column, NaN rows where there is none, or a tuple
+        (array, lnorm); score.native_rows makes one from a structure): the model is scored against it on the GPU (option
+        "score_native", set for this call only); what the call returns does not change, the scores are in `scores`.
         `distmap=True` returns (coords, confs, distmap (L, L), info (3,)): the chosen pass's predicted distance map and
         [best_pass, passes_run, map_rms] (option "emit_distmap", include/dmpfold_hip.h; the map's diagonal is what the
         network predicts, not zero).  confs, distmap and info are views of the one allocation handed to the library.
@@ -313,7 +320,22 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap)
+        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native)
+
+    @property
+    def scores(self):
+        """The scores of the last prediction as score.unpack_scores gives them, None if it ran without option
+        "score_native".  Synchronises with the GPU."""
+        if getattr(self, "_score", None) is None:
+            return None
+        block, L = self._score
+        torch.cuda.synchronize(self.device)
+        return _score.unpack_scores(block, L)
+
+    @property
+    def score_block(self):
+        """The last prediction's score block on the GPU (5L + 24 floats, a view of the buffer handed to the library), or None."""
+        return None if getattr(self, "_score", None) is None else self._score[0]
 
     @property
     def passes_run(self):
@@ -321,24 +343,32 @@ class Engine:
         return self.get_option("passes_run")
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
-                       minsteps=default_minsteps, converge=None, distmap=False):
+                       minsteps=default_minsteps, converge=None, distmap=False, native=None):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
         if converge is not None:
             # the option is read when the prediction begins: set for this call, then as it was
             before = self.get_option("recycle_tol_mA")
             self.set_option("recycle_tol_mA", converge_to_mA(converge))
             try:
-                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)
+                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
             finally:
                 self.set_option("recycle_tol_mA", before)
         if distmap and not self.get_option("emit_distmap"):
             self.set_option("emit_distmap", 1)
             try:
-                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, True)
+                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, True, native)
             finally:
                 self.set_option("emit_distmap", 0)
-        # the buffer is sized by the option as the context holds it: the library writes L + L*L + 3 floats when it is on
+        if native is not None and not self.get_option("score_native"):
+            self.set_option("score_native", 1)
+            try:
+                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
+            finally:
+                self.set_option("score_native", 0)
+        # the buffer is sized by the options as the context holds them: the library writes L + L*L + 3 floats with
+        # "emit_distmap" on, and reads and writes 5L + 24 more behind them with "score_native" on
         emit = bool(self.get_option("emit_distmap"))
+        score = bool(self.get_option("score_native"))
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
@@ -346,7 +376,14 @@ class Engine:
                                "(MDS embedding width, reference network.py:250-253)")
         with torch.cuda.device(self.device):
             coords = torch.empty((L, 5, 3), dtype=torch.float32, device=self.device)
-            confs = torch.empty((distmap_floats(L, emit),), dtype=torch.float32, device=self.device)
+            confs = torch.empty((_score.conf_floats(L, emit, score),), dtype=torch.float32, device=self.device)
+            self._score = None
+            if score:
+                # the library reads the native trace from the block: no native = no row present (n_pairs 0, NaN scores)
+                block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
+                view = confs[_score.score_offset(L, emit):]
+                view.copy_(torch.from_numpy(block))
+                self._score = (view, L)
             d_tpl, lt = None, 0
             if template_ca is not None:
                 d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(self.device)
@@ -369,7 +406,7 @@ class Engine:
             # d_msa / d_tpl are stream-ordered temporaries: keep them alive until the work is queued
             self._keep = (d_msa, d_tpl)
         if emit and distmap:
-            return (coords,) + split_distmap_buffer(confs, L)
+            return (coords,) + split_distmap_buffer(confs[:distmap_floats(L)], L)
         return coords, confs[:L]
 
     def set_option(self, name, value):
@@ -396,7 +433,7 @@ class Engine:
         raise_for_faults(self.sync_faults())
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
-                        minsteps=default_minsteps, converge=None, distmap=False):
+                        minsteps=default_minsteps, converge=None, distmap=False, native=None):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
@@ -404,26 +441,32 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap)
+        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
-                               minsteps=default_minsteps, converge=None, distmap=False):
-        """`predict_checked` for residue codes already resident on the GPU (`distmap`: see `predict`; a repeat of the
-        prediction returns the repeat's map)."""
+                               minsteps=default_minsteps, converge=None, distmap=False, native=None):
+        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`: see `predict`; a repeat of
+        the prediction returns the repeat's map and scores)."""
         if converge is not None:
             before = self.get_option("recycle_tol_mA")
             self.set_option("recycle_tol_mA", converge_to_mA(converge))
             try:
-                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, distmap)
+                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, distmap, native)
             finally:
                 self.set_option("recycle_tol_mA", before)
         if distmap and not self.get_option("emit_distmap"):
             self.set_option("emit_distmap", 1)
             try:
-                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, True)
+                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, True, native)
             finally:
                 self.set_option("emit_distmap", 0)
-        out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)     # 2 tensors, or 4 with `distmap`
+        if native is not None and not self.get_option("score_native"):
+            self.set_option("score_native", 1)
+            try:
+                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, distmap, native)
+            finally:
+                self.set_option("score_native", 0)
+        out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)     # 2 tensors, or 4 with `distmap`
         bits = self.sync_faults()
         self.last_fallback = False
         if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
@@ -432,7 +475,7 @@ class Engine:
             print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
                   "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
             self.set_option("vgru_persistent", 0)
-            out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)
+            out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
             bits = self.sync_faults()
         if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
             print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
@@ -441,7 +484,7 @@ class Engine:
             self.last_fallback = True
             self.set_option("conv_mode", 2)
             try:
-                out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap)
+                out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
                 bits = self.sync_faults()
             finally:
                 self.set_option("conv_mode", 0)
@@ -490,13 +533,15 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False):
+                 distmap=False, score=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
         (`set_converge`; `stats()` counts the passes run and saved).
         `distmap`: every target also returns its chosen pass's distance map and [best_pass, passes_run, map_rms]
-        (`set_distmap`): `result`, `peek`, `collect` and `run` then give (coords, confs, distmap, info) per target."""
+        (`set_distmap`): `result`, `peek`, `collect` and `run` then give (coords, confs, distmap, info) per target.
+        `score`: every target is scored against the native trace given to `submit` (`set_score`); its score block (5L + 24
+        floats, score.unpack_scores) is then the last element of what those calls give per target."""
         self.lib = _lib.load()
         self.device = _resolve_device(device)
         S = max(1, int(streams))
@@ -521,6 +566,8 @@ class Pipeline:
             self.set_converge(converge)
         if distmap:
             self.set_distmap(True)
+        if score:
+            self.set_score(True)
         self._jobs = {}               # ticket -> (d_msa, iterations, minsteps, d_tpl, coords, confs, ready event, long buffer?): kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -537,13 +584,19 @@ class Pipeline:
         """Option "emit_distmap" on every engine: targets submitted from now on return their distance map; idle pipeline only."""
         self.set_option("emit_distmap", 1 if on else 0)
 
+    def set_score(self, on):
+        """Option "score_native" on every engine: targets submitted from now on are scored against the `native` given to
+        `submit` (none given: no row present, n_pairs 0); idle pipeline only."""
+        self.set_option("score_native", 1 if on else 0)
+
     @staticmethod
     def _outputs(job):
-        coords, confs, emit = job[4], job[5], job[7]
+        coords, confs, emit, score = job[4], job[5], job[7], job[8]
         L = coords.shape[0]
+        tail = (confs[_score.score_offset(L, emit):],) if score else ()      # the "score_native" block, the last element
         if emit:                                           # an "emit_distmap" buffer: confs | map | info
-            return (coords,) + split_distmap_buffer(confs, L)
-        return coords, confs[:L]
+            return (coords,) + split_distmap_buffer(confs[:distmap_floats(L)], L) + tail
+        return (coords, confs[:L]) + tail
 
     def close(self):
         if self._p:
@@ -561,9 +614,9 @@ class Pipeline:
             pass
 
     # ---- submission --------------------------------------------------------------------------
-    def submit(self, d_msa, iterations=default_iterations, minsteps=default_minsteps, template_ca=None):
+    def submit(self, d_msa, iterations=default_iterations, minsteps=default_minsteps, template_ca=None, native=None):
         """Queue one target (uint8 (N, L) tensor on the GPU, optional template CA trace (L, 3));
-        returns a ticket for `result`."""
+        returns a ticket for `result`.  `native`: the trace to score against (Engine.predict), read only with `set_score` on."""
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
@@ -583,7 +636,15 @@ class Pipeline:
             # set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
             flags = [bool(e.get_option("emit_distmap")) for e in self.engines]
             emit = all(flags)                             # the extension is handed out only if whichever engine runs it writes it
-            confs = torch.empty((distmap_floats(L, any(flags)),), dtype=torch.float32, device=self.device)
+            sflags = [bool(e.get_option("score_native")) for e in self.engines]
+            score = all(sflags)
+            if any(sflags) and not (score and emit == any(flags)):
+                raise RuntimeError("score_native: the engines of a pipeline must agree on \"score_native\" and \"emit_distmap\" "
+                                   "(the score block's place in the buffer depends on both); use set_score / set_distmap")
+            confs = torch.empty((_score.conf_floats(L, any(flags), score),), dtype=torch.float32, device=self.device)
+            if score:                                     # written on the current stream: `ready` below is behind it
+                block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
+                confs[_score.score_offset(L, emit):].copy_(torch.from_numpy(block))
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -598,7 +659,8 @@ class Pipeline:
             self._p, d_msa.data_ptr(), n, L, d_tpl.data_ptr() if d_tpl is not None else None,
             int(max(iterations, 0)), int(max(minsteps, 0)), coords.data_ptr(), confs.data_ptr(),
             C.c_void_p(ready.cuda_event)))
-        self._jobs[t] = (d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, coords, confs, ready, emit)
+        self._jobs[t] = (d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, coords, confs, ready, emit, score,
+                         native if score else None)
         self._reap()
         return t
 
@@ -722,7 +784,12 @@ class Pipeline:
                 if bits:
                     d_msa, nloops, minsteps, d_tpl = job[:4]
                     try:
-                        res = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps, distmap=job[7])
+                        if job[8]:
+                            nat = job[9] if job[9] is not None else np.full((d_msa.shape[1], 3), np.nan, dtype=np.float32)
+                            res = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps, distmap=job[7], native=nat)
+                            res = tuple(res) + (eng.score_block,)
+                        else:
+                            res = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps, distmap=job[7])
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
                         if not eng.get_option("vgru_persistent"):
@@ -832,25 +899,34 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 # ---------------------------------------------------------------------------
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
-                  return_distmap=False):
+                  return_distmap=False, native=None, return_scores=False, native_chain=None):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
     than this (RMS) - the answer `iterations` = that pass would have given (Engine.predict).
     `return_distmap` (addition): the (L, L) predicted C-alpha distance map of the pass the best-of rule chose is appended
-    as the last element of the returned tuple (after `alnmat` when that is requested too)."""
+    as the last element of the returned tuple (after `alnmat` when that is requested too).
+    `native` (addition): a PDB file (its chain `native_chain`, default the first, is aligned with the query sequence:
+    score.native_from_pdb) or an array as Engine.predict takes it; the model is scored against it on the GPU.  With
+    `return_scores` the dict of score.unpack_scores is appended behind everything else (None without a `native`)."""
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
     template_ca = read_template_ca(template) if template is not None else None
     alnmat = encode_aln(aln)
     nseqs, length = alnmat.shape
+    if isinstance(native, (str, os.PathLike)):
+        native = _score.native_from_pdb(aln[0], native, native_chain)
+    scores = None
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
         eng = get_engine(dev, length, nseqs, weights_file=weights_file)
-        out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap))
+        out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap),
+                                  native=native)
+        if native is not None and return_scores:
+            scores = eng.scores
     coords, confs = out[0], out[1]
     ret = (coords, confs) + ((alnmat,) if return_alnmat else ()) + ((out[2],) if return_distmap else ())
-    return ret
+    return ret + ((scores,) if return_scores else ())
 
 
 def pdb_text(coords, confs, alnmat):
@@ -874,7 +950,7 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208), -c / --converge and --distmap."""
+    """The reference's flags (predict.py:160-208), -c / --converge, --distmap and --native."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -895,6 +971,13 @@ def dmpfold_parser():
                              "default: always run all iteration cycles")
     parser.add_argument("--distmap", type=str, default=None, required=False, metavar="FILE",
                         help="also write the predicted C-alpha distance map of the chosen pass to FILE (float32 .npy, L x L)")
+    parser.add_argument("--native", type=str, default=None, required=False, metavar="PDB",
+                        help="score the model against this native structure on the GPU (TM-score, GDT, RMSD, lDDT-CA); the scores "
+                             "go to standard error as one JSON line, the model on standard output is unchanged")
+    parser.add_argument("--native-chain", type=str, default=None, required=False, metavar="C",
+                        help="chain of --native (default: its first)")
+    parser.add_argument("--scores", type=str, default=None, required=False, metavar="FILE",
+                        help="write the JSON line of --native to FILE instead of standard error")
     return parser
 
 
@@ -904,8 +987,16 @@ def run_dmpfold(argv=None):
     out = aln_to_coords(args.input_file, device=args.device,
                         template=args.template, iterations=args.iterations,
                         minsteps=args.minsteps, weights_file=args.model_weights,
-                        return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None)
+                        return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None,
+                        native=args.native, return_scores=args.native is not None, native_chain=args.native_chain)
     coords, confs, alnmat = out[:3]
     if args.distmap is not None:
         save_distmap_npy(args.distmap, out[3])
+    if args.native is not None:
+        line = json.dumps(_score.scores_json(out[-1])) + "\n"
+        if args.scores is not None:
+            with open(args.scores, "w") as fh:
+                fh.write(line)
+        else:
+            sys.stderr.write(line)
     sys.stdout.write(pdb_text(coords, confs, alnmat))

@@ -1,0 +1,177 @@
+"""Host side of option "score_native" (include/dmpfold_hip.h): a prediction scored against a native structure on the GPU.
+
+The library compares the model's C-alpha trace with a native trace that the caller places, one row per alignment column,
+in the score block behind the confidences.  This module makes that block from a PDB file - parsing, a global sequence
+alignment of the query against the native chain - and takes it apart again.  Nothing here touches the GPU.
+
+The scores are TM-score, GDT_TS / GDT_HA, Kabsch RMSD and lDDT-C-alpha as include/dmpfold_hip.h defines them: the
+TM-score program's KIND of search over superpositions, not its bits - any superposition gives a lower bound of the true
+maximum, and nobody has compared the values with that program's.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+AA3 = "ALA ARG ASN ASP CYS GLN GLU GLY HIS ILE LEU LYS MET PHE PRO SER THR TRP TYR VAL".split()
+AA1 = "ARNDCQEGHILKMFPSTWYV"
+_THREE_TO_ONE = dict(zip(AA3, AA1))
+_THREE_TO_ONE["MSE"] = "M"           # selenomethionine, as structure files of expressed proteins carry it
+
+SCORE_HEADER = 24                    # floats between the native trace and the per-residue arrays
+SCORE_NAMES = ("n_pairs", "rmsd", "tm", "gdt_ts", "gdt_ha", "lddt")
+COUNT_CUTOFFS = (0.5, 1.0, 2.0, 4.0, 8.0)
+
+
+def score_floats(L):
+    """Floats of the score block of a prediction of length L."""
+    return 5 * int(L) + SCORE_HEADER
+
+
+def conf_floats(L, distmap=False, score=False):
+    """Floats the `d_conf` buffer of a prediction of length L must hold: the confidences, the L*L + 3 floats of option
+    "emit_distmap" and the 5L + 24 floats of option "score_native", in this order."""
+    L = int(L)
+    return L + (L * L + 3 if distmap else 0) + (score_floats(L) if score else 0)
+
+
+def score_offset(L, distmap=False):
+    """Where the score block begins in the `d_conf` buffer (S0 of include/dmpfold_hip.h)."""
+    return conf_floats(L, distmap, False)
+
+
+def read_native_ca(pdb, chain=None):
+    """(ca float32 (n, 3), one-letter sequence) of a chain of a PDB file: ATOM records (and HETATM MSE) with atom name CA,
+    fixed columns; the first model only; of alternate locations the first one met per residue.  `chain` None = the chain of
+    the first such atom.  A residue name outside the twenty (and MSE) reads as 'X'."""
+    xyz, seq, seen = [], [], set()
+    with open(pdb, "r") as fh:
+        for line in fh:
+            rec = line[:6]
+            if rec.startswith("ENDMDL"):
+                break
+            if not (rec == "ATOM  " or (rec == "HETATM" and line[17:20] == "MSE")) or line[12:16] != " CA ":
+                continue
+            if chain is None:
+                chain = line[21]
+            if line[21] != chain:
+                continue
+            key = line[22:27]                               # residue number + insertion code
+            if key in seen:
+                continue                                    # a further alternate location of the same residue
+            seen.add(key)
+            xyz.append((float(line[30:38]), float(line[38:46]), float(line[46:54])))
+            seq.append(_THREE_TO_ONE.get(line[17:20], "X"))
+    return np.asarray(xyz, dtype=np.float32).reshape(-1, 3), "".join(seq)
+
+
+def align_pairs(a, b, match=2, mismatch=-1, gap=-2):
+    """Global (Needleman-Wunsch) alignment of two strings with a linear gap penalty; returns [(i, j)] of the aligned
+    positions.  Scores and tie-breaking (diagonal, then a gap in `b`, then a gap in `a`) are those of
+    tools/accuracy_3fgx.py:needleman_wunsch, so the pair list is the same; the table is filled a row at a time.
+
+    Row i is max(diag, up) followed by the recurrence S[j] = max(T[j], S[j-1] + gap) along the row.  With
+    U[j] = S[j] - gap*j that is a running maximum, U[j] = max(T[j] - gap*j, U[j-1]): one np.maximum.accumulate."""
+    n, m = len(a), len(b)
+    A = np.frombuffer(a.encode("latin-1"), dtype=np.uint8)
+    B = np.frombuffer(b.encode("latin-1"), dtype=np.uint8)
+    ramp = gap * np.arange(m + 1, dtype=np.int64)
+    S = np.empty((n + 1, m + 1), dtype=np.int64)
+    S[0] = ramp
+    for i in range(1, n + 1):
+        prev = S[i - 1]
+        T = np.empty(m + 1, dtype=np.int64)
+        T[0] = gap * i
+        sub = np.where(B == A[i - 1], match, mismatch)
+        T[1:] = np.maximum(prev[:-1] + sub, prev[1:] + gap)
+        S[i] = np.maximum.accumulate(T - ramp) + ramp
+    pairs, i, j = [], n, m
+    while i > 0 and j > 0:
+        if S[i, j] == S[i - 1, j - 1] + (match if a[i - 1] == b[j - 1] else mismatch):
+            pairs.append((i - 1, j - 1))
+            i, j = i - 1, j - 1
+        elif S[i, j] == S[i - 1, j] + gap:
+            i -= 1
+        else:
+            j -= 1
+    return pairs[::-1]
+
+
+def native_rows(query, native_seq, native_ca):
+    """The native trace as the library wants it: (rows float32 (L, 3), lnorm) - row i holds the native C-alpha the
+    alignment pairs with query position i, NaN where there is none; lnorm = the native chain's length."""
+    native_ca = np.asarray(native_ca, dtype=np.float32).reshape(-1, 3)
+    if len(native_seq) != native_ca.shape[0]:
+        raise ValueError(f"native sequence has {len(native_seq)} residues, its trace {native_ca.shape[0]}")
+    rows = np.full((len(query), 3), np.nan, dtype=np.float32)
+    for i, j in align_pairs(query, native_seq):
+        rows[i] = native_ca[j]
+    return rows, float(len(native_seq))
+
+
+def native_from_pdb(query, pdb, chain=None):
+    """`native_rows` of a PDB file's chain."""
+    ca, seq = read_native_ca(pdb, chain)
+    if ca.shape[0] == 0:
+        raise ValueError(f"{pdb}: no C-alpha atoms" + (f" in chain {chain}" if chain else ""))
+    return native_rows(query, seq, ca)
+
+
+def as_native(native, L):
+    """What the front ends accept as `native` -> (rows float32 (L, 3), lnorm float): an (L, 3) array (NaN rows allowed;
+    lnorm 0 = the rows present) or a tuple (array, lnorm)."""
+    lnorm = 0.0
+    if isinstance(native, tuple):
+        native, lnorm = native
+    rows = np.ascontiguousarray(np.asarray(native, dtype=np.float32))
+    if rows.shape != (int(L), 3):
+        raise ValueError(f"native must be one row per alignment column, ({int(L)}, 3); got {rows.shape}")
+    return rows, float(lnorm)
+
+
+def pack_native(rows, lnorm, L):
+    """The score block (float32 (5L + 24,)) with its two inputs filled in and NaN elsewhere."""
+    rows, lnorm = as_native((rows, lnorm), L)
+    block = np.full(score_floats(L), np.nan, dtype=np.float32)
+    block[:3 * L] = rows.reshape(-1)
+    block[3 * L] = lnorm
+    return block
+
+
+def empty_native(L):
+    """A score block without any native residue (the library then reports n_pairs = 0 and NaN)."""
+    return pack_native(np.full((int(L), 3), np.nan, dtype=np.float32), 0.0, L)
+
+
+def unpack_scores(block, L):
+    """A score block (5L + 24 floats, array or tensor) -> dict: n_pairs (int), rmsd, tm, gdt_ts, gdt_ha, lddt (float),
+    counts (5 ints: rows within 0.5, 1, 2, 4, 8 A), R (3, 3) and t (3,) with native ~ R model + t, lddt_res (L,),
+    deviation (L,), and the inputs back: lnorm, native (L, 3)."""
+    L = int(L)
+    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    if b.ndim != 1 or b.shape[0] != score_floats(L):
+        raise ValueError(f"a score block of length {L} has {score_floats(L)} floats, got shape {tuple(b.shape)}")
+    h = b[3 * L:]
+    out = {"n_pairs": int(h[1]) if h[1] == h[1] else 0}
+    for k, name in enumerate(SCORE_NAMES[1:]):
+        out[name] = float(h[2 + k])
+    out["counts"] = [int(v) if v == v else 0 for v in h[7:12]]
+    out["R"] = h[12:21].reshape(3, 3).copy()
+    out["t"] = h[21:24].copy()
+    out["lddt_res"] = b[3 * L + 24:4 * L + 24].copy()
+    out["deviation"] = b[4 * L + 24:].copy()
+    out["lnorm"] = float(h[0])
+    out["native"] = b[:3 * L].reshape(L, 3).copy()
+    return out
+
+
+def scores_json(scores):
+    """The scalar part of `unpack_scores` as a JSON-ready dict (what `dmpfold --native` prints and `dmpfold-batch --natives`
+    writes); NaN becomes None."""
+    def num(v):
+        v = float(v)
+        return v if v == v else None
+    out = {"n_pairs": int(scores["n_pairs"]), "lnorm": num(scores["lnorm"])}
+    for name in SCORE_NAMES[1:]:
+        out[name] = num(scores[name])
+    out["counts"] = [int(c) for c in scores["counts"]]
+    return out

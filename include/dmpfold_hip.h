@@ -192,7 +192,50 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  *                   the result is rounded once to float32.  The reference has no such quantity.
  * A prediction that latched a device-side fault returns NaN in all L + L*L + 3 floats.  Cost: one store in the best-of
  * kernel always; with the option on one kernel per pass tail (keep_best_dm: workgroups of a pass that was not taken leave
- * at once) and one in dmp_predict_end (emit_distmap), csrc/coords.hip.  A context holds max_L^2 floats for the map. */
+ * at once) and one in dmp_predict_end (emit_distmap), csrc/coords.hip.  A context holds max_L^2 floats for the map.
+ * "score_native" (0 or 1, default 0; any other value: DMP_ERR_ARG): score the model against a native C-alpha trace on the
+ * device.  Read when a prediction begins and held for it.  With it 0 nothing is launched, nothing extra is read or written,
+ * and every output is bit for bit what it is without the option.  With it 1 THE d_conf ARGUMENT OF dmp_predict,
+ * dmp_predict_end AND dmp_pipeline_submit MUST HOLD S0 + 5L + 24 FLOATS, S0 = L, OR L + L*L + 3 WITH "emit_distmap" ON AS
+ * WELL (the library cannot check the size): behind the confidences (and the distance-map extension) sits the SCORE BLOCK.
+ * THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL (on a pipeline: the submission's ready_event is behind those writes);
+ * dmp_predict_end reads them from d_conf itself.  Offsets relative to S0:
+ *   [0, 3L)         in   native C-alpha trace, one row (x, y, z) per alignment column; a row whose x is NaN: no native
+ *                        residue here
+ *   3L              in   lnorm, the length TM-score and GDT are normalised by; 0: the number of rows present
+ *   3L + 1          out  n_pairs: rows present
+ *   3L + 2          out  rmsd: Kabsch RMSD over all present rows [Angstrom]
+ *   3L + 3          out  tm
+ *   3L + 4          out  gdt_ts = (c1 + c2 + c4 + c8) / 4 / lnorm, c the counts below
+ *   3L + 5          out  gdt_ha = (c0.5 + c1 + c2 + c4) / 4 / lnorm
+ *   3L + 6          out  lddt: global lDDT-C-alpha
+ *   3L + 7 .. 11    out  the five counts of rows deviating by less than 0.5, 1, 2, 4, 8 Angstrom, each its own maximum over
+ *                        every superposition the search visited
+ *   3L + 12 .. 23   out  R (row-major 3 x 3) and t of the superposition that gave tm: native ~ R model + t
+ *   [3L+24, 4L+24)  out  per-residue lDDT-C-alpha; NaN where the native row is absent, 0 where the residue has no partner
+ *                        inside the radius
+ *   [4L+24, 5L+24)  out  per-residue deviation [Angstrom] under that superposition; NaN where the native row is absent
+ * The model trace is the final, refined C-alpha trace the backbone is built from (d_coords[:, 1]).  n_pairs < 3: NaN in
+ * every out slot except n_pairs, no fault.  A prediction that latched a device-side fault returns NaN in every out slot;
+ * the inputs are left alone.
+ * The scores (the reference has none of them; float64 from the float32 coordinates, each output rounded once to float32).
+ * The n present rows in sequence order are k = 0 .. n-1; d0 = max(1.24 (lnorm - 15)^(1/3) - 1.8, 0.5) for lnorm > 15, else
+ * 0.5; d_cut = min(max(d0, 4.5), 8).  Seeds: the fragment lengths are the distinct values of f_0 = n and
+ * f_k = max(n >> k, min(4, n)), k = 1..5; every start s = 0 .. n - f of every length is a seed, numbered by (level,
+ * start): at most 1 + 5 max_L, a context holds records for 6 max_L.  One seed starts with S = its fragment and repeats at
+ * most 20 times: Kabsch superposition of the model on the native over S; deviations d_k of all n rows;
+ * TM = sum_k 1 / (1 + (d_k / d0)^2) / lnorm and the five counts #{d_k < c}; the seed's best TM (with its R, t) and each of
+ * its five best counts are updated; S' = {k : d_k < d_cut}; stop if |S'| < 3 or S' = S, else S = S'.  Seed 0 (the whole
+ * chain), iteration 0, also yields rmsd.  tm is the maximum over the seeds, ties to the lowest seed number (R, t are
+ * reproducible); each count is its own maximum over all seeds.  lDDT-C-alpha is superposition-free: over the ordered pairs
+ * i != j of present rows with native distance below 15 Angstrom, a pair is preserved at threshold 0.5, 1, 2, 4 if
+ * |d_model - d_native| is below it; per residue preserved / (4 x partners), globally total preserved / (4 x total pairs)
+ * (0 without any pair), from integer counts: exact and order-free.
+ * THIS IS THE TM-SCORE PROGRAM'S KIND OF SEARCH, NOT ITS BITS: any superposition gives a lower bound of the true maximum,
+ * and nobody has compared the values with that program's.  MaxSub and sequence-independent alignment are not offered.
+ * Cost with the option on: three launches in dmp_predict_end (csrc/score.hip: score_prep, score_lddt, score_search - one
+ * workgroup per seed, both traces and the set S in LDS, 6L floats + L flags; sums in a fixed order, the same bits on
+ * every run).  A context holds 6 max_L records of 20 doubles. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
@@ -364,7 +407,9 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
  * steps.  Outputs d_coords (L x 5 x 3) and d_conf (L).  No host synchronisation - unless option "recycle_tol_mA" is
  * set: the call then waits for the tail of every pass p >= 1 that has a successor (one event synchronisation per pass)
  * to learn whether to go on, and returns with the remaining work enqueued as always.
- * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option). */
+ * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
+ * WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN INTO THEM
+ * (layout: dmp_ctx_set_option). */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
                 int Lt, int nloops, int refine_steps, float* d_coords, float* d_conf,
                 void* stream);
@@ -419,7 +464,9 @@ int dmp_predict_group_riders(dmp_ctx* lead, int n, const uint8_t* const* d_msas,
 int dmp_predict_set_vgru_result(dmp_ctx* ctx, const float* d_vout, void* event);
 /* After the last unit: final refinement of the best trace + backbone + confidences into d_coords (L x 5 x 3) and
  * d_conf (L); a prediction during which a device-side fault was recorded returns NaN.
- * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option). */
+ * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
+ * IF IT BEGAN WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE; the native trace and lnorm are read
+ * from them here. */
 int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream);
 int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream);
 int dmp_ctx_pending(dmp_ctx* ctx);
@@ -477,7 +524,9 @@ void* dmp_pipeline_stream(dmp_pipeline* p, int i);
 int dmp_pipeline_weights_ready(dmp_pipeline* p);
 int dmp_pipeline_set_option(dmp_pipeline* p, const char* name, int value);
 /* d_coords: L x 5 x 3 floats, d_conf: L floats.  WITH OPTION "emit_distmap" = 1 ON THE PIPELINE d_conf MUST HOLD
- * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run. */
+ * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run.
+ * WITH OPTION "score_native" = 1 ON THE PIPELINE d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN
+ * INTO THEM BEFORE ready_event. */
 int64_t dmp_pipeline_submit(dmp_pipeline* p, const uint8_t* d_msa, int N, int L, const float* d_template_ca, int nloops,
                             int refine_steps, float* d_coords, float* d_conf, void* ready_event);
 int dmp_pipeline_wait(dmp_pipeline* p, int what);

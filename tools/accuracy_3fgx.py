@@ -5,6 +5,9 @@ trace with chain A of example/3FGX.pdb (TM-score, RMSD after superposition).
 
     python tools/accuracy_3fgx.py [-w weights.pt] [-n 10] [-m 100]
 
+Beside the host-side numbers of this script the result carries "library": what the GPU computed for the same prediction
+(option "score_native", dmpfold2_amd/score.py).
+
 Needs the two FINAL_fullmap_e2e_model_part*.pt files (absent from the reference tree, see
 .MISSING_LARGE_BLOBS) in dmpfold2_amd/trained_model/ or a -w file.  The native CA trace and sequence
 come from tests/golden/kat_refine_backbone.npz (data captured from the example PDB file).
@@ -78,13 +81,16 @@ def tm_score(P, Q, l_norm):
 def evaluate(aln_path, native_npz, weights_file=None, iterations=10, minsteps=100, device="cuda:0"):
     from dmpfold2_amd import aln_to_coords
     from dmpfold2_amd.predict import read_aln
-    coords, confs = aln_to_coords(aln_path, device=device, iterations=iterations, minsteps=minsteps,
-                                  weights_file=weights_file)
-    ca = coords[:, 1].cpu().numpy().astype(np.float64)
+    from dmpfold2_amd import score as S
     nat = np.load(native_npz)
     native = nat["ca_in"].astype(np.float64)
     native_seq = bytes(nat["seq1"]).decode()
     query = read_aln(aln_path)[0]
+    # the library's own scores of the same prediction (option "score_native": every start of six fragment lengths)
+    coords, confs, lib_scores = aln_to_coords(aln_path, device=device, iterations=iterations, minsteps=minsteps,
+                                              weights_file=weights_file, return_scores=True,
+                                              native=S.native_rows(query, native_seq, nat["ca_in"]))
+    ca = coords[:, 1].cpu().numpy().astype(np.float64)
     pairs = needleman_wunsch(query, native_seq)
     qi = np.array([i for i, _ in pairs])
     nj = np.array([j for _, j in pairs])
@@ -94,7 +100,8 @@ def evaluate(aln_path, native_npz, weights_file=None, iterations=10, minsteps=10
     ident = float(np.mean([query[i] == native_seq[j] for i, j in pairs]))
     return {"aligned_pairs": len(pairs), "sequence_identity": ident, "ca_rmsd_A": rmsd,
             "tm_score": tm_score(P, Q, len(native)), "tm_score_by_query_length": tm_score(P, Q, len(query)),
-            "mean_conf": float(confs.mean()), "query_length": len(query), "native_length": len(native)}
+            "mean_conf": float(confs.mean()), "query_length": len(query), "native_length": len(native),
+            "library": S.scores_json(lib_scores)}
 
 
 def main():
