@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import score as _score
+from .score import Outputs
 from . import shard
 from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
                       pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy)
@@ -141,14 +142,6 @@ def ca_only_text(coords, confs, alnmat):
             ln = "ATOM   %4d" % k + ln[11:]
         out.append(ln)
     return "\n".join(out)
-
-
-def split_extras(extra):
-    """What a Pipeline hands out behind (coords, confs) -> (distmap, info, score block), None for what is not there: two
-    tensors with "emit_distmap", then one with "score_native"."""
-    extra = tuple(extra)
-    dm, info = extra[:2] if len(extra) >= 2 else (None, None)
-    return dm, info, (extra[-1] if len(extra) % 2 else None)
 
 
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None):
@@ -284,7 +277,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         return pipe
 
     done = []                                           # completed on the GPU AND copied to the host, not yet written
-    copying = []                                        # (ticket, (host coords, host confs[, map, info]), event): D2H in flight
+    copying = []                                        # (ticket, (host coords, host confs[, map, info][, block]), event): D2H in flight
 
     # The scheduler's thread never blocks on the GPU: a synchronous copy on the default stream can queue behind an
     # engine's kernels (streams share hardware queues) and would stall the thread - and with it every engine.
@@ -310,26 +303,24 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     scored, all_scores = set(), {}
 
-    def unpack(aln_path, t, extra):
-        """(distmap, info, scores) of a target's extras; the scores only if it had a native"""
-        dm, info, block = split_extras(extra)
+    def write(t, public):
+        """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
+        out = Outputs.of(public, distmap, bool(natives))
+        aln_path, alnmat, _ = parsed.pop(t)
         sc = None
-        if block is not None and t in scored:
-            sc = _score.unpack_scores(block, alnmat_len[t])
+        if out.score_block is not None and t in scored:
+            sc = _score.unpack_scores(out.score_block, alnmat.shape[1])
             all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = _score.scores_json(sc)
-        return dm, info, sc
-
-    alnmat_len = {}
+        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap, out.info, sc))
 
     def finish(item):
-        t, (coords, confs, *extra) = item
-        aln_path, alnmat, _ = parsed.pop(t)
-        if bool(torch.isnan(confs[:1]).any()):          # a device-side fault poisoned it: repeated alone at the end
-            parsed[t] = (aln_path, alnmat, None)
+        t, public = item
+        if bool(torch.isnan(public[1][:1]).any()):      # a device-side fault poisoned it: repeated alone at the end
+            parsed[t] = parsed[t][:2] + (None,)
             faulted.append(t)
             return
         pipe.result(t)
-        outputs.append(write_result(out_dir, aln_path, coords, confs, alnmat, fmt, *unpack(aln_path, t, extra)))
+        write(t, public)
 
     exhausted = False
     cap = 2 * max(1, int(streams))                      # started + queued per rank
@@ -365,7 +356,6 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 # target orders its stream behind the stream that is current at submission (the copy stream)
                 t = p.submit(d_msa, iterations, minsteps, template_ca=tpl, **({"native": nat} if nat is not None else {}))
                 parsed[t] = (aln_path, alnmat, h_msa)
-                alnmat_len[t] = alnmat.shape[1]
                 if nat is not None:
                     scored.add(t)
         except (IndexError, ValueError, OSError, UnicodeDecodeError, RuntimeError) as exc:
@@ -419,12 +409,10 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     if faulted:
         res = pipe.collect(faulted)
         for t in faulted:
-            aln_path, alnmat, _ = parsed.pop(t)
             if isinstance(res[t], Exception):
-                failed.append((aln_path, res[t]))
+                failed.append((parsed.pop(t)[0], res[t]))
             else:
-                outputs.append(write_result(out_dir, aln_path, res[t][0], res[t][1], alnmat, fmt,
-                                            *unpack(aln_path, t, res[t][2:])))
+                write(t, res[t])
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:

@@ -405,18 +405,17 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // End of a prediction: if a device-side fault was recorded while it ran, its outputs become NaN (an
 // invalid structure can never be mistaken for a result, and a batch can tell WHICH target failed) and
 // the fault bits are latched into the word dmp_sync_faults reports.
-// `nconf`: the floats behind `conf` - L, or L + L*L + 3 with option "emit_distmap" (the whole extension becomes NaN too).
-// `nscore`: 0, or 5L + 24 with option "score_native": the score block behind those; its outputs [3L + 1, 5L + 24) become NaN,
-// its inputs (the native trace and lnorm) are the caller's and stay.
+// `lay`: the d_conf buffer of this prediction (common.h) - the confidences and, with option "emit_distmap", the whole extension
+// become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
+// caller's and stay.
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
-                                   float* __restrict__ conf, int L, int64_t nconf, int64_t nscore, int* __restrict__ report) {
+                                   float* __restrict__ conf, int L, ConfLayout lay, int* __restrict__ report) {
   const int f = words[0];
   if (!f) return;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const float nan = __builtin_nanf("");
   if (i < 15 * L) coords[i] = nan;
-  if (i < nconf) conf[i] = nan;
-  else if (i >= nconf + 3 * L + 1 && i < nconf + nscore) conf[i] = nan;
+  if (i < lay.score_off || (i >= lay.score_out && i < lay.total)) conf[i] = nan;
   if (i == 0) {
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
@@ -595,17 +594,17 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
   }
   if (k == "recycle_tol_mA") {       // takes effect with the next prediction begun
     DMP_ARG(value >= 0, "recycle_tol_mA must be >= 0 (milli-Angstrom; 0 = fixed depth), got %d", value);
-    ctx->recycle_tol_mA = value;
+    ctx->opt.tol_mA = value;
     return DMP_OK;
   }
   if (k == "emit_distmap") {         // takes effect with the next prediction begun
     DMP_ARG(value == 0 || value == 1, "emit_distmap must be 0 or 1, got %d", value);
-    ctx->emit_distmap = value;
+    ctx->opt.emit = value;
     return DMP_OK;
   }
   if (k == "score_native") {         // takes effect with the next prediction begun
     DMP_ARG(value == 0 || value == 1, "score_native must be 0 or 1, got %d", value);
-    ctx->score_native = value;
+    ctx->opt.score = value;
     return DMP_OK;
   }
   DMP_ARG(k != "passes_run", "passes_run is read only");
@@ -648,9 +647,9 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "gj_lookahead") { *h_value = ctx->gj_lookahead; return DMP_OK; }
   if (k == "gj_pairs") { *h_value = ctx->gj_pairs; return DMP_OK; }
   if (k == "gj_diag_blocked") { *h_value = ctx->gj_diag_blocked; return DMP_OK; }
-  if (k == "recycle_tol_mA") { *h_value = ctx->recycle_tol_mA; return DMP_OK; }
-  if (k == "emit_distmap") { *h_value = ctx->emit_distmap; return DMP_OK; }
-  if (k == "score_native") { *h_value = ctx->score_native; return DMP_OK; }
+  if (k == "recycle_tol_mA") { *h_value = ctx->opt.tol_mA; return DMP_OK; }
+  if (k == "emit_distmap") { *h_value = ctx->opt.emit; return DMP_OK; }
+  if (k == "score_native") { *h_value = ctx->opt.score; return DMP_OK; }
   if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -1038,7 +1037,7 @@ static constexpr int FE_VGRU_STEPS = VGRU_CHUNK;  // vertical-GRU time steps per
 // 0 = the tail unit is still running (only with block = false), negative = error.  A stop ends the prediction as if
 // `iterations` had been p: run_nloops becomes p, dmp_predict_end's precondition holds.
 static int recycle_gate(dmp_ctx* c, bool block) {
-  if (c->run_tol_mA <= 0 || c->fe_next < c->fe_total || c->unit_next != 0) return 1;
+  if (c->run.tol_mA <= 0 || c->fe_next < c->fe_total || c->unit_next != 0) return 1;
   const int pass = c->passes_done;
   if (pass < 2 || pass > c->run_nloops || c->gate_pass == pass) return 1;
   hipEvent_t tail = (hipEvent_t)c->unit_ev[(c->unit_seq - 1) & 1];
@@ -1214,9 +1213,7 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   c->passes_done = 0;
   c->unit_next = 0;
   c->end_refined = false;
-  c->run_tol_mA = c->recycle_tol_mA;
-  c->run_emit = c->emit_distmap;
-  c->run_score = c->score_native;
+  c->run = c->opt;
   c->gate_pass = 0;
   c->run_nloops = nloops < 0 ? 0 : nloops;
   c->run_refine = refine_steps < 0 ? 0 : refine_steps;
@@ -1360,8 +1357,8 @@ int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream) {
     if (!rc) rc = coords_from_mds(c, c->mat1d, c->mds, L, c->ca, s);
     if (!rc && pass == 0 && c->run_refine > 0) rc = refine_coords(c, c->ca, L, c->run_refine, s);
     if (!rc) rc = select_best(c, c->conf, c->ca, L, pass, c->max_passes, s);
-    if (!rc && c->run_emit) rc = keep_best_dm(c, L, pass, s);     // head0 is still this pass's plane here
-    if (!rc && c->run_tol_mA > 0) rc = recycle_delta(c, c->ca, L, pass, c->max_passes, s);
+    if (!rc && c->run.emit) rc = keep_best_dm(c, L, pass, s);     // head0 is still this pass's plane here
+    if (!rc && c->run.tol_mA > 0) rc = recycle_delta(c, c->ca, L, pass, c->max_passes, s);
   }
   if (rc) { c->xsplit_current = false; return rc; }
   if (u == NBLOCK + 1) { c->unit_next = 0; c->passes_done = pass + 1; }
@@ -1414,14 +1411,13 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // (tools/isa_lint.py).
   rc = ca_to_backbone(c->best_ca, c->best_conf, L, d_coords, d_conf, s);
   if (rc) return rc;
-  // option "emit_distmap": d_conf holds L + L*L + 3 floats; the map, {best_pass, passes_run, map_rms} behind the confidences
-  const int64_t nconf = c->run_emit ? (int64_t)L + (int64_t)L * L + 3 : L;
-  if (c->run_emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + L, s))) return rc;
-  // option "score_native": the score block of 5L + 24 floats behind that, the native trace and lnorm in it (score.hip)
-  const int64_t nscore = c->run_score ? 5 * (int64_t)L + 24 : 0;
-  if (c->run_score && (rc = score_native(c, d_coords, L, d_conf + nconf, s))) return rc;
-  hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, nconf + nscore), 256)), dim3(256), 0, s,
-                     c->seq_abort, d_coords, d_conf, L, nconf, nscore, c->end_fault_out);
+  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score);
+  // option "emit_distmap": the map and {best_pass, passes_run, map_rms} behind the confidences
+  if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map_off, d_conf + lay.info_off, s))) return rc;
+  // option "score_native": the score block behind that, the native trace and lnorm in it (score.hip)
+  if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score_off, s))) return rc;
+  hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, lay.total), 256)), dim3(256), 0, s,
+                     c->seq_abort, d_coords, d_conf, L, lay, c->end_fault_out);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }
@@ -1466,8 +1462,8 @@ int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t ca
   else if (k == "mat1d") { src = ctx->mat1d; n = WIDTH * L; }
   else if (k == "conf_means") { src = ctx->conf_means; n = P; }
   else if (k == "ca_pass") { src = ctx->ca_pass; n = P * L * 3; }
-  else if (k == "pass_delta") { src = ctx->pass_delta; n = ctx->run_tol_mA > 0 ? P : 0; }
-  else if (k == "best_dm") { src = ctx->best_dm; n = ctx->run_emit ? L * L : 0; }
+  else if (k == "pass_delta") { src = ctx->pass_delta; n = ctx->run.tol_mA > 0 ? P : 0; }
+  else if (k == "best_dm") { src = ctx->best_dm; n = ctx->run.emit ? L * L : 0; }
   else if (k == "best_pass") { src = ctx->best_pass; n = 1; }
   else if (k == "best_ca") { src = ctx->best_ca_snapshot; n = L * 3; }
   else if (k == "best_ca_refined") { src = ctx->best_ca; n = L * 3; }

@@ -54,6 +54,21 @@ inline int round_up(int a, int b) { return cdiv(a, b) * b; }
 // multiply by a power of two: nothing to contract, the same value in either translation unit, and dm_ij == dm_ji.
 __host__ __device__ inline float distmap_entry(float h_ij, float h_ji) { return fabsf((h_ij + h_ji) * 0.5f); }
 
+// The caller's d_conf buffer in floats, the library's one restatement of include/dmpfold_hip.h (it cannot check the buffer):
+//   [0, L) confidences | with "emit_distmap": L*L map, 3 info floats | with "score_native": the score block =
+//   [0, 3L) native trace (in) | SCORE_HEADER floats, the first of them lnorm (in) | lddt_res [L] | deviation [L].
+constexpr int SCORE_HEADER = 24;
+struct ScoreLayout { int lnorm, out, lddt_res, deviation, total; };     // lnorm: also where the header begins; out: the first float written
+__host__ __device__ inline ScoreLayout score_layout(int L) {
+  const int hdr = 3 * L, res = hdr + SCORE_HEADER;
+  return {hdr, hdr + 1, res, res + L, res + 2 * L};
+}
+struct ConfLayout { int64_t map_off, info_off, score_off, score_out, total; };   // score_off: the end of what "emit_distmap" gives
+__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score) {
+  const int64_t info_off = L + (emit ? (int64_t)L * L : 0), score_off = info_off + (emit ? 3 : 0);
+  return {L, info_off, score_off, score_off + score_layout(L).out, score_off + (score ? score_layout(L).total : 0)};
+}
+
 // padded activation geometry: interior [2, 2+L) in both axes, zero elsewhere
 inline int act_tiles(int L) { return cdiv(L, CONV_TILE); }
 inline int act_pitch(int L) { return act_tiles(L) * CONV_TILE + 4; }
@@ -126,6 +141,8 @@ struct dmp_lane {
   void* last = nullptr;    // event recorded after the most recent conv launch
   long long count = 0;     // conv launches recorded so far (event of launch i: ev[i % RING])
 };
+
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0; };   // options "recycle_tol_mA", "emit_distmap", "score_native"
 
 struct dmp_ctx {
   int device = 0;
@@ -241,9 +258,9 @@ struct dmp_ctx {
   float* ca_pass = nullptr;    // [P][L][3]
   float* best_ca_snapshot = nullptr;
   int passes_done = 0;
+  TailOpts opt;                    // as set through dmp_ctx_set_option (they take effect with the next prediction begun)
+  TailOpts run;                    // ... as the prediction in flight began with them
   // option "recycle_tol_mA": stop recycling once a pass moves the seed distance map by no more than this (RMS, mA; 0 = off)
-  int recycle_tol_mA = 0;
-  int run_tol_mA = 0;              // ... as the prediction in flight began with it
   int gate_pass = 0;               // the boundary in front of this pass has been decided (recycle_gate, api.hip)
   float* delta_keep = nullptr;     // [2][max_L][3] the trace each pass is compared with (coords.hip: recycle_delta)
   float* pass_delta = nullptr;     // [P] d_p of every pass (+inf for pass 0)
@@ -251,15 +268,11 @@ struct dmp_ctx {
   unsigned* delta_counter = nullptr;
   int* delta_host = nullptr;       // pinned host word the kernel writes: ((pass + 1) << 1) | stop
   // option "emit_distmap": the chosen pass's predicted distance map behind the confidences (include/dmpfold_hip.h)
-  int emit_distmap = 0;
-  int run_emit = 0;                // ... as the prediction in flight began with it
   float* best_pass = nullptr;      // [1] the pass select_best took last, as a float (always written)
   float* best_dm = nullptr;        // [max_L][max_L] dm of that pass (coords.hip: keep_best_dm; only with the option on)
   double* rms_partial = nullptr;   // [64] per-workgroup sums of emit_distmap
   unsigned* rms_counter = nullptr;
   // option "score_native": the model scored against a native C-alpha trace in the d_conf buffer (include/dmpfold_hip.h)
-  int score_native = 0;
-  int run_score = 0;               // ... as the prediction in flight began with it
   float* score_pm = nullptr;       // [max_L][3] model trace, rows with a native residue only (score.hip: score_prep)
   float* score_qn = nullptr;       // [max_L][3] native trace, the same rows
   int* score_idx = nullptr;        // [max_L] alignment column of each such row
@@ -452,6 +465,48 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// ---- a float64 sum over the workgroups of a launch, the same bits however they are scheduled ----------------------
+// The workgroup's tree (this pairing, so these bits).  EVERY thread of the workgroup calls it; `red`: THREADS doubles of LDS.
+template <int THREADS>
+__device__ __forceinline__ double block_tree_sum_f64(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+// relaxed agent-scope accesses: served past the L1 and the XCD's L2, where every workgroup of the device finds the value
+__device__ __forceinline__ void agent_store_f64(double* p, double v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double agent_load_f64(double* p) {
+  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(p), __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT));
+}
+// A ticket (zero between launches) counts n workgroups in.  True for the last arriver: what the others stored before they
+// took theirs is behind their release.  Nobody waits; the last arriver resets the ticket for the next launch.
+__device__ __forceinline__ bool ticket_take_last(unsigned* ticket, unsigned n) {
+  return __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == n - 1u;
+}
+__device__ __forceinline__ void ticket_reset(unsigned* ticket) { __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The whole protocol (1-D grid, every thread calls it): the tree, thread 0 publishes its workgroup's sum in partial[block] and
+// takes the ticket, the last arriver adds the partial sums in index order.  True in that one thread of the launch, *total set.
+template <int THREADS>
+__device__ __forceinline__ bool grid_sum_f64(double v, double* red, double* partial, unsigned* ticket, double* total) {
+  const double mine = block_tree_sum_f64<THREADS>(v, red);
+  if (threadIdx.x != 0) return false;
+  agent_store_f64(&partial[blockIdx.x], mine);
+  if (!ticket_take_last(ticket, gridDim.x)) return false;
+  *total = 0.0;
+  for (unsigned k = 0; k < gridDim.x; ++k) *total += agent_load_f64(&partial[k]);
+  ticket_reset(ticket);
+  return true;
+}
+
 // ---- hand-off between the workgroups of a cluster kernel (seq_gru_kernel, refine_cluster_kernel) -------------------
 // Granules {epoch, value} are published with a store and gathered with sc1 loads (agent scope: past the L1, served by
 // the L2).  An agent-scope STORE is written through to the memory side so that every XCD can see it: measured
@@ -498,7 +553,7 @@ int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int p
                 hipStream_t s);
 int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, hipStream_t s);
 int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
-int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_ext, hipStream_t s);
+int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_map, float* d_info, hipStream_t s);
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);

@@ -105,14 +105,9 @@ __global__ __launch_bounds__(256) void select_best_kernel(const float* __restric
   __shared__ int take;
   double acc = 0.0;
   for (int i = threadIdx.x; i < L; i += 256) acc += (double)conf[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  const double sum = block_tree_sum_f64<256>(acc, red);
   if (threadIdx.x == 0) {
-    const float mean = (float)(red[0] / (double)L);
+    const float mean = (float)(sum / (double)L);
     if (pass < rec_cap) conf_means[pass] = mean;
     take = (pass == 0) || (mean > best_mean[0]);
     if (take) {
@@ -145,7 +140,7 @@ int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int p
 // that map from the trace; here both maps are formed on the fly from the two traces in LDS, 2 x 3L floats, no L^2
 // traffic).  Float64 throughout: at d = 1e-3 A the float32 rounding of two 30 A distances is a tenth of the value.
 // Rows i are dealt round robin to the workgroups, a row's partners j to the threads; every thread sums its pairs in a
-// fixed order, the workgroup's tree and the last arriver's loop over the partial sums are fixed too, so the value - and
+// fixed order, the workgroup's tree and the last arriver's loop over the partial sums (grid_sum_f64) are fixed too, so the value - and
 // with it the stop decision - has the same bits however the workgroups are scheduled.  Workgroup 0 keeps the trace for
 // the next pass's comparison (the two keep buffers alternate: nobody reads the one being written).  The last arriver
 // records d_p and tells the host: {pass + 1, stop} in one word of pinned host memory, an ordinary store - the route of
@@ -200,27 +195,12 @@ __global__ __launch_bounds__(RD_THREADS) void recycle_delta_kernel(RecycleDeltaA
       acc += e * e;
     }
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = RD_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.partial[g]), (unsigned long long)__double_as_longlong(red[0]),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned before = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (before == (unsigned)G - 1u) {          // the last arriver: every partial sum is behind its owner's release
-      double sum = 0.0;
-      for (int k = 0; k < G; ++k)
-        sum += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(&a.partial[k]),
-                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      const float d = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
-      if (a.pass < a.rec_cap) a.pass_delta[a.pass] = d;
-      const int stop = d <= a.tol ? 1 : 0;           // false for NaN
-      __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *a.host_word = ((a.pass + 1) << 1) | stop;
-    }
+  double sum;
+  if (grid_sum_f64<RD_THREADS>(acc, red, a.partial, a.counter, &sum)) {
+    const float d = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
+    if (a.pass < a.rec_cap) a.pass_delta[a.pass] = d;
+    const int stop = d <= a.tol ? 1 : 0;           // false for NaN
+    *a.host_word = ((a.pass + 1) << 1) | stop;
   }
 }
 
@@ -230,7 +210,7 @@ int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, h
   a.seed = pass > 0 ? c->delta_keep + (int64_t)((pass - 1) & 1) * 3 * c->max_L : nullptr;
   a.keep = c->delta_keep + (int64_t)(pass & 1) * 3 * c->max_L;
   a.L = L; a.pass = pass; a.rec_cap = rec_cap;
-  a.tol = (float)c->run_tol_mA * 1e-3f;
+  a.tol = (float)c->run.tol_mA * 1e-3f;
   a.pass_delta = c->pass_delta;
   a.partial = c->delta_partial;
   a.counter = c->delta_counter;
@@ -306,7 +286,8 @@ struct EmitDistmapArgs {
   const float* ca;         // [L][3]
   const float* best_pass;  // [1]
   int L, passes_run;
-  float* out;              // [L*L + 3]
+  float* out;              // [L][L]
+  float* info;             // [3] best_pass, passes_run, map_rms
   double* partial;         // [RD_MAX_WG]
   unsigned* counter;       // zero between launches
 };
@@ -332,37 +313,21 @@ __global__ __launch_bounds__(RD_THREADS) void emit_distmap_kernel(EmitDistmapArg
       }
     }
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = RD_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.partial[g]), (unsigned long long)__double_as_longlong(red[0]),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned before = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (before == (unsigned)G - 1u) {          // the last arriver: every partial sum is behind its owner's release
-      double sum = 0.0;
-      for (int k = 0; k < G; ++k)
-        sum += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(&a.partial[k]),
-                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      float* tail = a.out + (int64_t)L * L;
-      tail[0] = a.best_pass[0];
-      tail[1] = (float)a.passes_run;
-      tail[2] = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
-      __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  double sum;
+  if (grid_sum_f64<RD_THREADS>(acc, red, a.partial, a.counter, &sum)) {
+    a.info[0] = a.best_pass[0];
+    a.info[1] = (float)a.passes_run;
+    a.info[2] = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
   }
 }
 
-int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_ext, hipStream_t s) {
+int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_map, float* d_info, hipStream_t s) {
   EmitDistmapArgs a{};
   a.best_dm = c->best_dm;
   a.ca = d_ca;
   a.best_pass = c->best_pass;
   a.L = L; a.passes_run = passes_run;
-  a.out = d_ext;
+  a.out = d_map; a.info = d_info;
   a.partial = c->rms_partial;
   a.counter = c->rms_counter;
   hipLaunchKernelGGL(emit_distmap_kernel, dim3(recycle_delta_groups(L)), dim3(RD_THREADS), sizeof(float) * 3 * L, s, a);

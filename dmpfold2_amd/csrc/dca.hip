@@ -13,14 +13,9 @@ __global__ __launch_bounds__(256) void wsum_kernel(const float* __restrict__ w, 
   __shared__ double red[256];
   double acc = 0.0;
   for (int n = threadIdx.x; n < N; n += 256) acc += (double)w[n];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  const double total = block_tree_sum_f64<256>(acc, red);
   if (threadIdx.x == 0) {
-    const float S = (float)red[0];
+    const float S = (float)total;
     const float mean = S / (float)N;
     sc[0] = S;
     sc[1] = S - sqrtf(mean);
@@ -789,13 +784,8 @@ __global__ __launch_bounds__(256) void apc_total_kernel(int L, double* __restric
   __shared__ double red[256];
   double a = 0.0;
   for (int k = threadIdx.x; k < L; k += 256) a += sums[L + k];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sums[2 * L] = red[0];
+  const double total = block_tree_sum_f64<256>(a, red);
+  if (threadIdx.x == 0) sums[2 * L] = total;
 }
 
 __global__ __launch_bounds__(256) void apc_apply_kernel(const float* __restrict__ x3, int L,

@@ -3,8 +3,8 @@
 //   score_prep    one workgroup: the rows that have a native residue, packed in sequence order (model trace from
 //                 d_coords[:, 1], native from the block), n, lnorm, d0, d_cut; NaN into every out slot but n_pairs.
 //   score_lddt    rows dealt to the workgroups: integer counts, so lDDT is exact and order-free.
-//   score_search  one workgroup per seed of the superposition search; the last arriver (agent-scope ticket, as in
-//                 recycle_delta_kernel) reduces the seeds' records in seed order and writes the header and the deviations.
+//   score_search  one workgroup per seed of the superposition search; the last arriver (agent-scope ticket, common.h)
+//                 reduces the seeds' records in seed order and writes the header and the deviations.
 // Float64 from the float32 coordinates throughout; every sum has a fixed per-thread order, a fixed butterfly inside a
 // wave (both partners of an exchange form a + b, so all 64 lanes hold the same bits) and a fixed order over the four
 // waves' partial sums in LDS: the same bits on every run, and every thread of a workgroup takes the same branch.
@@ -141,16 +141,6 @@ __device__ inline void score_block_sum(double (&v)[K], double (*wred)[16]) {
   for (int k = 0; k < K; ++k) v[k] = ((wred[0][k] + wred[1][k]) + wred[2][k]) + wred[3][k];
 }
 
-__device__ inline void score_store(double* p, double v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ inline double score_load(double* p) {
-  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_AGENT));
-}
-
 struct ScoreArgs {
   const float* coords;   // [L][5][3] the backbone; the model trace is atom 1
   float* blk;            // the score block: [0, 3L) native (in), 3L lnorm (in), the rest out
@@ -196,10 +186,11 @@ __global__ __launch_bounds__(SC_THREADS) void score_prep_kernel(ScoreArgs a) {
     }
   }
   const float nan = __builtin_nanf("");
-  float* out = a.blk + 3 * L + 1;
-  for (int i = tid; i < 2 * L + 23; i += SC_THREADS) out[i] = i == 0 ? (float)n : nan;
+  const ScoreLayout lay = score_layout(L);
+  float* out = a.blk + lay.out;
+  for (int i = tid; i < lay.total - lay.out; i += SC_THREADS) out[i] = i == 0 ? (float)n : nan;
   if (tid == 0) {
-    const double given = (double)a.blk[3 * L];
+    const double given = (double)a.blk[lay.lnorm];
     const double lnorm = given == 0.0 ? (double)n : given;
     const double d0 = lnorm > 15.0 ? fmax(1.24 * cbrt(lnorm - 15.0) - 1.8, 0.5) : 0.5;
     a.hdr[HDR_N] = (double)n;
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_lddt_kernel(ScoreArgs a) {
   float* qn = sm + 3 * n;
   for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = a.pm[i]; qn[i] = a.qn[i]; }
   __syncthreads();
-  float* out = a.blk + 3 * L + 24;
+  float* out = a.blk + score_layout(L).lddt_res;
   unsigned long long tot_pres = 0ull, tot_part = 0ull;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     int pres = 0, part = 0;
@@ -362,13 +353,12 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
 
   if (tid == 0) {
     double* rec = a.rec + (int64_t)blockIdx.x * SCORE_REC;
-    score_store(rec + REC_TM, best_tm);
-    for (int c = 0; c < 5; ++c) score_store(rec + REC_CNT + c, best_cnt[c]);
-    for (int c = 0; c < 9; ++c) score_store(rec + REC_R + c, best_R[c]);
-    for (int c = 0; c < 3; ++c) score_store(rec + REC_T + c, best_t[c]);
-    score_store(rec + REC_RMSD, rmsd);
-    const unsigned before = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    sh_last = before == (unsigned)nseeds - 1u ? 1 : 0;     // the last arriver: every record is behind its owner's release
+    agent_store_f64(rec + REC_TM, best_tm);
+    for (int c = 0; c < 5; ++c) agent_store_f64(rec + REC_CNT + c, best_cnt[c]);
+    for (int c = 0; c < 9; ++c) agent_store_f64(rec + REC_R + c, best_R[c]);
+    for (int c = 0; c < 3; ++c) agent_store_f64(rec + REC_T + c, best_t[c]);
+    agent_store_f64(rec + REC_RMSD, rmsd);
+    sh_last = ticket_take_last(a.ticket, (unsigned)nseeds) ? 1 : 0;     // every record is behind its owner's release
     if (sh_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
   __syncthreads();
@@ -381,9 +371,9 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   double cmax[5] = {0, 0, 0, 0, 0};
   for (int s = tid; s < nseeds; s += SC_THREADS) {
     double* rec = a.rec + (int64_t)s * SCORE_REC;
-    const double tm = score_load(rec + REC_TM);
+    const double tm = agent_load_f64(rec + REC_TM);
     if (tm > top) { top = tm; top_seed = s; }          // s rises: the first of equals stays
-    for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], score_load(rec + REC_CNT + c));
+    for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], agent_load_f64(rec + REC_CNT + c));
   }
   for (int off = 32; off > 0; off >>= 1) {
     const double o_top = __shfl_xor(top, off, 64);
@@ -403,11 +393,11 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
       if (wred[k][0] > top || (wred[k][0] == top && sh_seed[k] < top_seed)) { top = wred[k][0]; top_seed = sh_seed[k]; }
       for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], wred[k][1 + c]);
     }
-    float* out = a.blk + 3 * L;
+    float* out = a.blk + score_layout(L).lnorm;        // the header
     const float nan = __builtin_nanf("");
     const bool found = top_seed != 0x7fffffff;         // false only if every seed's tm is NaN
     double* rec = a.rec + (int64_t)(found ? top_seed : 0) * SCORE_REC;
-    out[2] = (float)score_load(a.rec + REC_RMSD);
+    out[2] = (float)agent_load_f64(a.rec + REC_RMSD);
     out[3] = found ? (float)top : nan;
     out[4] = (float)((((cmax[1] + cmax[2]) + cmax[3]) + cmax[4]) / 4.0 / lnorm);
     out[5] = (float)((((cmax[0] + cmax[1]) + cmax[2]) + cmax[3]) / 4.0 / lnorm);
@@ -415,19 +405,19 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
     out[6] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
     for (int c = 0; c < 5; ++c) out[7 + c] = (float)cmax[c];
     for (int c = 0; c < 12; ++c) {
-      const double v = score_load(rec + REC_R + c);
+      const double v = agent_load_f64(rec + REC_R + c);
       bc[c] = v;
       out[12 + c] = found ? (float)v : nan;
     }
     sh_last = found ? 1 : 0;
-    __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket_reset(a.ticket);
   }
   __syncthreads();
   if (!sh_last) return;                                // the deviations stay NaN
   double R[9], t[3];
   for (int c = 0; c < 9; ++c) R[c] = bc[c];
   for (int c = 0; c < 3; ++c) t[c] = bc[9 + c];
-  float* dev = a.blk + 4 * L + 24;
+  float* dev = a.blk + score_layout(L).deviation;
   for (int k = tid; k < n; k += SC_THREADS) dev[a.idx[k]] = (float)score_dev(R, t, pm + 3 * k, qn + 3 * k);
 }
 

@@ -890,13 +890,8 @@ __global__ __launch_bounds__(256) void head_conf_kernel(const float* __restrict_
   const int i = blockIdx.x;
   double rsum = 0.0;
   for (int j = threadIdx.x; j < L; j += 256) rsum += (double)head1[(int64_t)i * L + j];
-  red[threadIdx.x] = rsum;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) conf[i] = (float)(red[0] / (double)L);
+  const double total = block_tree_sum_f64<256>(rsum, red);
+  if (threadIdx.x == 0) conf[i] = (float)(total / (double)L);
 }
 
 // dm = |(h + h^T)/2| ; M_ij = 0.5*((dm_0j^2 + dm_i0^2) - dm_ij^2), every step rounded to f32

@@ -25,18 +25,21 @@ Differences from the reference, all additive or forced by the environment:
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes as C
 import json
 import os
 import sys
 import threading
 import time
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import _lib
 from . import score as _score
+from .score import Outputs, distmap_floats, split_conf_buffer, split_distmap_buffer    # noqa: F401 (re-exports)
 
 default_device = "cuda"
 default_iterations = 10
@@ -150,21 +153,6 @@ def converge_to_mA(converge):
     return int(round(tol * 1000.0))
 
 
-def distmap_floats(L, on=True):
-    """Floats the `d_conf` buffer of a prediction of length L must hold: L, or L + L*L + 3 with option "emit_distmap"."""
-    L = int(L)
-    return L + L * L + 3 if on else L
-
-
-def split_distmap_buffer(buf, L):
-    """The three parts of an "emit_distmap" output buffer (a 1-D tensor or array of distmap_floats(L) floats), as views:
-    confs (L,), distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms] (include/dmpfold_hip.h)."""
-    L = int(L)
-    if buf.ndim != 1 or buf.shape[0] != distmap_floats(L):
-        raise ValueError(f"an emit_distmap buffer of length {L} has {distmap_floats(L)} floats, got shape {tuple(buf.shape)}")
-    return buf[:L], buf[L:L + L * L].reshape(L, L), buf[L + L * L:]
-
-
 def save_distmap_npy(path, distmap):
     """The (L, L) map as a float32 .npy file (what `dmpfold --distmap` and `dmpfold-batch --distmap` write)."""
     arr = distmap.detach().cpu().numpy() if isinstance(distmap, torch.Tensor) else np.asarray(distmap)
@@ -239,6 +227,26 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
+def _stage(device, L, template_ca, native, emit, score, emit_alloc=None):
+    """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
+    The `d_conf` buffer behind the Outputs is sized for the options as the context holds them - the library cannot check
+    it, writes L + L*L + 3 floats with "emit_distmap" on (`emit_alloc`: sized as if it were) and reads and writes 5L + 24
+    more behind them with "score_native" on: the native trace goes there (no `native` = no row present: n_pairs 0, NaN scores)."""
+    d_tpl = None
+    if template_ca is not None:
+        d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
+        if d_tpl.shape[0] != L:
+            raise RuntimeError(f"Sizes of tensors must match: template has {d_tpl.shape[0]} CA atoms, "
+                               f"alignment has {L} columns")
+    coords = torch.empty((L, 5, 3), dtype=torch.float32, device=device)
+    buf = torch.empty((_score.conf_floats(L, emit if emit_alloc is None else emit_alloc, score),), dtype=torch.float32, device=device)
+    out = split_conf_buffer(buf, L, emit, score, coords)
+    if score:
+        block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
+        out.score_block.copy_(torch.from_numpy(block))
+    return d_tpl, out
+
+
 class Engine:
     """Owns one `dmp_ctx` (device buffers + packed weights) on one GPU."""
 
@@ -254,6 +262,7 @@ class Engine:
                                                C.byref(self._ctx)))
         self.weights_tag = None
         self.last_fallback = False     # the last predict_*_checked call fell back to conv_mode 2
+        self._score = None             # (score block, L) of the last prediction
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
@@ -326,7 +335,7 @@ class Engine:
     def scores(self):
         """The scores of the last prediction as score.unpack_scores gives them, None if it ran without option
         "score_native".  Synchronises with the GPU."""
-        if getattr(self, "_score", None) is None:
+        if self._score is None:
             return None
         block, L = self._score
         torch.cuda.synchronize(self.device)
@@ -335,7 +344,7 @@ class Engine:
     @property
     def score_block(self):
         """The last prediction's score block on the GPU (5L + 24 floats, a view of the buffer handed to the library), or None."""
-        return None if getattr(self, "_score", None) is None else self._score[0]
+        return None if self._score is None else self._score[0]
 
     @property
     def passes_run(self):
@@ -345,69 +354,56 @@ class Engine:
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
                        minsteps=default_minsteps, converge=None, distmap=False, native=None):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        if converge is not None:
-            # the option is read when the prediction begins: set for this call, then as it was
-            before = self.get_option("recycle_tol_mA")
-            self.set_option("recycle_tol_mA", converge_to_mA(converge))
-            try:
-                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
-            finally:
-                self.set_option("recycle_tol_mA", before)
+        with self._call_options(converge, distmap, native):
+            return self._run(d_msa, template_ca, iterations, minsteps, native).public(distmap, score=False)
+
+    @contextlib.contextmanager
+    def _call_options(self, converge, distmap, native):
+        """The options one call asks for - read when the prediction begins - set for its duration, then as they were.
+        `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" set by hand stay set."""
+        want = {} if converge is None else {"recycle_tol_mA": converge_to_mA(converge)}    # (raises before anything changes)
         if distmap and not self.get_option("emit_distmap"):
-            self.set_option("emit_distmap", 1)
-            try:
-                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, True, native)
-            finally:
-                self.set_option("emit_distmap", 0)
+            want["emit_distmap"] = 1
         if native is not None and not self.get_option("score_native"):
-            self.set_option("score_native", 1)
-            try:
-                return self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
-            finally:
-                self.set_option("score_native", 0)
-        # the buffer is sized by the options as the context holds them: the library writes L + L*L + 3 floats with
-        # "emit_distmap" on, and reads and writes 5L + 24 more behind them with "score_native" on
-        emit = bool(self.get_option("emit_distmap"))
-        score = bool(self.get_option("score_native"))
+            want["score_native"] = 1
+        before = {}
+        try:
+            for name, value in want.items():
+                before[name] = self.get_option(name)
+                self.set_option(name, value)
+            yield
+        finally:
+            for name, value in before.items():
+                self.set_option(name, value)
+
+    def _run(self, d_msa, template_ca, iterations, minsteps, native):
+        """One prediction with the options as the context holds them -> Outputs."""
+        emit, score = bool(self.get_option("emit_distmap")), bool(self.get_option("score_native"))
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         with torch.cuda.device(self.device):
-            coords = torch.empty((L, 5, 3), dtype=torch.float32, device=self.device)
-            confs = torch.empty((_score.conf_floats(L, emit, score),), dtype=torch.float32, device=self.device)
             self._score = None
+            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score)
             if score:
-                # the library reads the native trace from the block: no native = no row present (n_pairs 0, NaN scores)
-                block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
-                view = confs[_score.score_offset(L, emit):]
-                view.copy_(torch.from_numpy(block))
-                self._score = (view, L)
-            d_tpl, lt = None, 0
-            if template_ca is not None:
-                d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(self.device)
-                lt = d_tpl.shape[0]
-                if lt != L:
-                    raise RuntimeError(f"Sizes of tensors must match: template has {lt} CA atoms, "
-                                       f"alignment has {L} columns")
+                self._score = (out.score_block, L)
             if self._stream is not None:
                 # an engine with its own stream: order it after the producer of the inputs and tell the
                 # caching allocator that these blocks are in use there
                 self._stream.wait_stream(torch.cuda.current_stream(self.device))
-                for x in (coords, confs, d_msa, d_tpl):
+                for x in (out.coords, out.confs, d_msa, d_tpl):
                     if x is not None:
                         x.record_stream(self._stream)
             _lib.check(self.lib.dmp_predict(
                 self._ctx, d_msa.data_ptr(), n, L,
-                d_tpl.data_ptr() if d_tpl is not None else None, lt,
+                d_tpl.data_ptr() if d_tpl is not None else None, L if d_tpl is not None else 0,
                 int(max(iterations, 0)), int(max(minsteps, 0)),
-                coords.data_ptr(), confs.data_ptr(), self.stream()))
+                out.coords.data_ptr(), out.confs.data_ptr(), self.stream()))
             # d_msa / d_tpl are stream-ordered temporaries: keep them alive until the work is queued
             self._keep = (d_msa, d_tpl)
-        if emit and distmap:
-            return (coords,) + split_distmap_buffer(confs[:distmap_floats(L)], L)
-        return coords, confs[:L]
+        return out
 
     def set_option(self, name, value):
         """Additive engine options, e.g. ("conv_f32_exact", 1); see include/dmpfold_hip.h."""
@@ -447,49 +443,35 @@ class Engine:
                                minsteps=default_minsteps, converge=None, distmap=False, native=None):
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`: see `predict`; a repeat of
         the prediction returns the repeat's map and scores)."""
-        if converge is not None:
-            before = self.get_option("recycle_tol_mA")
-            self.set_option("recycle_tol_mA", converge_to_mA(converge))
-            try:
-                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, distmap, native)
-            finally:
-                self.set_option("recycle_tol_mA", before)
-        if distmap and not self.get_option("emit_distmap"):
-            self.set_option("emit_distmap", 1)
-            try:
-                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, True, native)
-            finally:
-                self.set_option("emit_distmap", 0)
-        if native is not None and not self.get_option("score_native"):
-            self.set_option("score_native", 1)
-            try:
-                return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, None, distmap, native)
-            finally:
-                self.set_option("score_native", 0)
-        out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)     # 2 tensors, or 4 with `distmap`
-        bits = self.sync_faults()
-        self.last_fallback = False
-        if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
-            # the persistent chain's row barriers timed out (its workgroups were not all resident: another process
-            # on this GPU holds CUs with a launch of the same kind): the launch-per-row form has no such requirement
-            print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
-                  "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
-            self.set_option("vgru_persistent", 0)
-            out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
+        return self._checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native).public(distmap, score=False)
+
+    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native):
+        """`predict_device_checked` -> Outputs; the repeats run with the call's options still set."""
+        with self._call_options(converge, distmap, native):
+            out = self._run(d_msa, template_ca, iterations, minsteps, native)
             bits = self.sync_faults()
-        if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
-            print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
-                  "re-running this alignment with conv_mode=2 (bf16 split, no range limit)",
-                  file=sys.stderr)
-            self.last_fallback = True
-            self.set_option("conv_mode", 2)
-            try:
-                out = self.predict_device(d_msa, template_ca, iterations, minsteps, None, distmap, native)
+            self.last_fallback = False
+            if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
+                # the persistent chain's row barriers timed out (its workgroups were not all resident: another process
+                # on this GPU holds CUs with a launch of the same kind): the launch-per-row form has no such requirement
+                print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
+                      "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
+                self.set_option("vgru_persistent", 0)
+                out = self._run(d_msa, template_ca, iterations, minsteps, native)
                 bits = self.sync_faults()
-            finally:
-                self.set_option("conv_mode", 0)
-        raise_for_faults(bits)
-        return out
+            if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
+                print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
+                      "re-running this alignment with conv_mode=2 (bf16 split, no range limit)",
+                      file=sys.stderr)
+                self.last_fallback = True
+                self.set_option("conv_mode", 2)
+                try:
+                    out = self._run(d_msa, template_ca, iterations, minsteps, native)
+                    bits = self.sync_faults()
+                finally:
+                    self.set_option("conv_mode", 0)
+            raise_for_faults(bits)
+            return out
 
     def fetch(self, name, numel):
         out = torch.empty((int(numel),), dtype=torch.float32, device=self.device)
@@ -510,12 +492,18 @@ class _PipelineEngine(Engine):
         self._stream = torch.cuda.ExternalStream(stream_ptr, device=device)
         self.weights_tag = None
         self.last_fallback = False
+        self._score = None
 
     def close(self):
         self._ctx = C.c_void_p()
 
     def __del__(self):
         pass
+
+
+# A target in a `Pipeline`: what stays alive until its result is handed out and what a repeat needs.  `out`: its Outputs,
+# `ready`: the event behind the producer of its inputs, `native`: as given to `submit`, None if the target is not scored.
+_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready native")
 
 
 # ticket states of the C pipeline (include/dmpfold_hip.h, DMP_TICKET_*)
@@ -568,7 +556,7 @@ class Pipeline:
             self.set_distmap(True)
         if score:
             self.set_score(True)
-        self._jobs = {}               # ticket -> (d_msa, iterations, minsteps, d_tpl, coords, confs, ready event, long buffer?): kept alive
+        self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
     def set_option(self, name, value):
@@ -588,15 +576,6 @@ class Pipeline:
         """Option "score_native" on every engine: targets submitted from now on are scored against the `native` given to
         `submit` (none given: no row present, n_pairs 0); idle pipeline only."""
         self.set_option("score_native", 1 if on else 0)
-
-    @staticmethod
-    def _outputs(job):
-        coords, confs, emit, score = job[4], job[5], job[7], job[8]
-        L = coords.shape[0]
-        tail = (confs[_score.score_offset(L, emit):],) if score else ()      # the "score_native" block, the last element
-        if emit:                                           # an "emit_distmap" buffer: confs | map | info
-            return (coords,) + split_distmap_buffer(confs[:distmap_floats(L)], L) + tail
-        return (coords, confs[:L]) + tail
 
     def close(self):
         if self._p:
@@ -624,14 +603,7 @@ class Pipeline:
         if L > self.engines[0].max_L or n > self.engines[0].max_N:
             raise RuntimeError(f"alignment {n} x {L} exceeds the pipeline capacity "
                                f"{self.engines[0].max_N} x {self.engines[0].max_L}")
-        d_tpl = None
         with torch.cuda.device(self.device):
-            if template_ca is not None:
-                d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(self.device).contiguous()
-                if d_tpl.shape[0] != L:
-                    raise RuntimeError(f"Sizes of tensors must match: template has {d_tpl.shape[0]} CA atoms, "
-                                       f"alignment has {L} columns")
-            coords = torch.empty((L, 5, 3), dtype=torch.float32, device=self.device)
             # the library cannot check the buffer: it is sized by the option as the engines hold it, whichever way it was
             # set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
             flags = [bool(e.get_option("emit_distmap")) for e in self.engines]
@@ -641,10 +613,8 @@ class Pipeline:
             if any(sflags) and not (score and emit == any(flags)):
                 raise RuntimeError("score_native: the engines of a pipeline must agree on \"score_native\" and \"emit_distmap\" "
                                    "(the score block's place in the buffer depends on both); use set_score / set_distmap")
-            confs = torch.empty((_score.conf_floats(L, any(flags), score),), dtype=torch.float32, device=self.device)
-            if score:                                     # written on the current stream: `ready` below is behind it
-                block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
-                confs[_score.score_offset(L, emit):].copy_(torch.from_numpy(block))
+            # (the native block is written on the current stream: `ready` below is behind it)
+            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, emit_alloc=any(flags))
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -652,15 +622,14 @@ class Pipeline:
         # Inputs and outputs are used on the stream of whichever engine takes the target (and, as a rider, on a group
         # leader's): the caching allocator has to know before it recycles their blocks.
         for e in self.engines:
-            for x in (coords, confs, d_msa, d_tpl):
+            for x in (out.coords, out.confs, d_msa, d_tpl):
                 if x is not None:
                     x.record_stream(e._stream)
         t = _lib.check(self.lib.dmp_pipeline_submit(
             self._p, d_msa.data_ptr(), n, L, d_tpl.data_ptr() if d_tpl is not None else None,
-            int(max(iterations, 0)), int(max(minsteps, 0)), coords.data_ptr(), confs.data_ptr(),
+            int(max(iterations, 0)), int(max(minsteps, 0)), out.coords.data_ptr(), out.confs.data_ptr(),
             C.c_void_p(ready.cuda_event)))
-        self._jobs[t] = (d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, coords, confs, ready, emit, score,
-                         native if score else None)
+        self._jobs[t] = _Job(d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, out, ready, native if score else None)
         self._reap()
         return t
 
@@ -702,10 +671,13 @@ class Pipeline:
         self._raise_failed()
 
     def result(self, ticket):
+        return self._result(ticket).public()
+
+    def _result(self, ticket):
         job = self._jobs.pop(ticket)
         self._handed.append(ticket)
         self._reap()
-        return self._outputs(job)
+        return job.out
 
     # ---- streaming use (dmpfold2_amd.batch): submit / step / poll, no barrier between targets ----------------
     def step(self, rounds=32):
@@ -737,7 +709,7 @@ class Pipeline:
                 return out
 
     def peek(self, ticket):
-        return self._outputs(self._jobs[ticket])
+        return self._jobs[ticket].out.public()
 
     def stats(self):
         v = (C.c_longlong * 11)()
@@ -777,19 +749,17 @@ class Pipeline:
             for t in tickets:
                 st, bits, rc = self._status(t)
                 job = self._jobs.get(t)
-                res = self.result(t)
+                res = self._result(t)
                 if st == _T_FAILED:
                     out[t] = _lib.DmpError(_lib.load().dmp_last_error().decode("utf-8", "replace") or f"error {rc}")
                     continue
                 if bits:
-                    d_msa, nloops, minsteps, d_tpl = job[:4]
+                    emit, nat = res.distmap is not None, job.native
+                    if res.score_block is not None and nat is None:
+                        nat = np.full((job.d_msa.shape[1], 3), np.nan, dtype=np.float32)
                     try:
-                        if job[8]:
-                            nat = job[9] if job[9] is not None else np.full((d_msa.shape[1], 3), np.nan, dtype=np.float32)
-                            res = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps, distmap=job[7], native=nat)
-                            res = tuple(res) + (eng.score_block,)
-                        else:
-                            res = eng.predict_device_checked(d_msa, d_tpl, nloops, minsteps, distmap=job[7])
+                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat)
+                        res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
                         if not eng.get_option("vgru_persistent"):
@@ -800,7 +770,7 @@ class Pipeline:
                     except (IndexError, _lib.DmpError) as exc:
                         out[t] = exc
                         continue
-                out[t] = res
+                out[t] = res.public()
         finally:
             eng.set_option("conv_mode", mode0)
         return out

@@ -10,6 +10,8 @@ maximum, and nobody has compared the values with that program's.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 AA3 = "ALA ARG ASN ASP CYS GLN GLU GLY HIS ILE LEU LYS MET PHE PRO SER THR TRP TYR VAL".split()
@@ -37,6 +39,49 @@ def conf_floats(L, distmap=False, score=False):
 def score_offset(L, distmap=False):
     """Where the score block begins in the `d_conf` buffer (S0 of include/dmpfold_hip.h)."""
     return conf_floats(L, distmap, False)
+
+
+def distmap_floats(L, on=True):
+    """Floats the `d_conf` buffer of a prediction of length L must hold: L, or L + L*L + 3 with option "emit_distmap"."""
+    return conf_floats(L, on)
+
+
+class Outputs(namedtuple("Outputs", "coords confs distmap info score_block", defaults=(None, None, None))):
+    """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
+    confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
+    score_block (5L + 24,) - None for what is absent."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, public, distmap, score):
+        """The inverse of `public` for a caller that knows which options were on."""
+        public = tuple(public)
+        return cls(*public[:2], *(public[2:4] if distmap else (None, None)), public[4 if distmap else 2] if score else None)
+
+    def public(self, distmap=True, score=True):
+        """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
+        block if present and wanted."""
+        return ((self.coords, self.confs) + ((self.distmap, self.info) if distmap and self.distmap is not None else ())
+                + ((self.score_block,) if score and self.score_block is not None else ()))
+
+
+def split_conf_buffer(buf, L, emit=False, score=False, coords=None):
+    """The parts of a `d_conf` buffer (a 1-D tensor or array of at least conf_floats(L, emit, score) floats) at the offsets of
+    include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through)."""
+    L = int(L)
+    if buf.ndim != 1 or buf.shape[0] < conf_floats(L, emit, score):
+        raise ValueError(f"a d_conf buffer of length {L} has {conf_floats(L, emit, score)} floats, got shape {tuple(buf.shape)}")
+    s0 = score_offset(L, emit)
+    return Outputs(coords, buf[:L], buf[L:L + L * L].reshape(L, L) if emit else None, buf[L + L * L:s0] if emit else None,
+                   buf[s0:s0 + score_floats(L)] if score else None)
+
+
+def split_distmap_buffer(buf, L):
+    """The three parts of an "emit_distmap" output buffer (a 1-D tensor or array of distmap_floats(L) floats), as views:
+    confs (L,), distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms] (include/dmpfold_hip.h)."""
+    if buf.ndim != 1 or buf.shape[0] != distmap_floats(L):
+        raise ValueError(f"an emit_distmap buffer of length {L} has {distmap_floats(L)} floats, got shape {tuple(buf.shape)}")
+    return split_conf_buffer(buf, L, True)[1:4]
 
 
 def read_native_ca(pdb, chain=None):

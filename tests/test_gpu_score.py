@@ -354,6 +354,87 @@ def test_pipeline(synth_sd, streams):
         single.close()
 
 
+# ------------------------------------------------------------------------------------------------ 6b. all three options
+@pytest.fixture(scope="module")
+def single_and_pipe(synth_sd):
+    """A lone engine with "tridiag_cluster" 0, as the scheduler's engines, and a two-stream pipeline with the three options on."""
+    from dmpfold2_amd.predict import Engine, Pipeline
+    dev, sdt = torch.device("cuda:0"), _tensors(synth_sd)
+    single = Engine(dev, 96, 16)
+    single.set_weights(sdt)
+    single.set_option("precision", 2)
+    single.set_option("tridiag_cluster", 0)
+    pipe = Pipeline(dev, 96, 16, sdt, streams=2, precision=2, converge=BOUNDARY_TOL, distmap=True, score=True)
+    yield single, pipe
+    pipe.close()
+    single.close()
+
+
+BOUNDARY_TOL = 1e-3         # Angstrom: "recycle_tol_mA" = 1
+
+
+def _bits(x):
+    return (x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)).reshape(-1).view(np.uint32)
+
+
+@pytest.mark.parametrize("L", [8, 63, 64, 96])
+def test_all_three_options_at_workgroup_boundaries(single_and_pipe, L):
+    """N = 16, -n 2 -m 0 with "recycle_tol_mA", "emit_distmap" and "score_native" on, the native the model's own trace moved
+    rigidly.  L = 8: the network's minimum, fewer rows than threads; 63 / 64: one and two workgroups in the reductions of
+    recycle_delta and emit_distmap; 96: three, an odd count of partial sums.  The engine's result, the raw buffer of a
+    dmp_predict call and the pipeline's result agree bit for bit in every part (NaN slots included); the guard behind
+    conf_floats(L, True, True) floats stays; map_rms and pass_delta[1:] agree with their float64 restatements at the
+    bounds of test_gpu_distmap.py (1e-6 relative) and test_gpu_recycle_converge.py (1e-5 relative)."""
+    from dmpfold2_amd import synth
+    from test_recycle_converge_cpu import recycle_deltas
+    single, pipe = single_and_pipe
+    aln = np.ascontiguousarray(O.encode_aln(synth.synth_msa(L, 16, 2000 + L)))
+    plain, _ = single.predict(aln, None, 2, 0)
+    single.sync_check()
+    R, t, native = _moved(plain[:, 1].cpu().numpy(), 30 + L)
+    coords, confs, dm, info = single.predict(aln, None, 2, 0, converge=BOUNDARY_TOL, distmap=True, native=native)
+    single.sync_check()
+    assert [single.get_option(k) for k in ("recycle_tol_mA", "emit_distmap", "score_native")] == [0, 0, 0]
+    block, sc, P = single.score_block, single.scores, single.passes_run
+    assert sc["n_pairs"] == L and info[1].item() == float(P) and 2 <= P <= 3
+    # the float64 restatements
+    ca = coords[:, 1].cpu().numpy().astype(np.float64)
+    d = ca[:, None, :] - ca[None, :, :]
+    iu = np.triu_indices(L, 1)
+    e = dm.cpu().numpy().astype(np.float64)[iu] - np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])[iu]
+    want_rms = float(np.sqrt((e * e).mean()))
+    delta = single.fetch("pass_delta", P).cpu().numpy()
+    own = recycle_deltas(single.fetch("ca_pass", P * L * 3).cpu().numpy().reshape(P, L, 3))
+    print("L", L, "passes", P, "map_rms", float(info[2]), "restated", want_rms, "pass_delta", delta, "restated", own, file=sys.stderr)
+    assert abs(float(info[2]) - want_rms) <= 1e-6 * want_rms
+    assert delta.shape == (P,) and np.isinf(delta[0]) and (np.abs(delta[1:] - own[1:]) <= 1e-5 * own[1:]).all(), (delta, own)
+    # the raw call into a poisoned buffer: the same bits, nothing behind the layout's end
+    n_out = S.conf_floats(L, True, True)
+    d_msa = torch.from_numpy(aln).to(single.device)
+    raw_c = torch.full((15 * L + GUARD,), float("nan"), dtype=torch.float32, device=single.device)
+    buf = torch.full((n_out + GUARD,), float("nan"), dtype=torch.float32, device=single.device)
+    buf[S.score_offset(L, True):n_out] = torch.from_numpy(S.pack_native(native, 0.0, L)).to(single.device)
+    for k, v in (("recycle_tol_mA", 1), ("emit_distmap", 1), ("score_native", 1)):
+        single.set_option(k, v)
+    try:
+        rc = single.lib.dmp_predict(single.ctx, d_msa.data_ptr(), 16, L, None, 0, 2, 0, raw_c.data_ptr(), buf.data_ptr(), single.stream())
+        assert rc == 0, single.lib.dmp_last_error()
+        single.sync_check()
+    finally:
+        for k in ("recycle_tol_mA", "emit_distmap", "score_native"):
+            single.set_option(k, 0)
+    assert bool(torch.isnan(buf[n_out:]).all()) and bool(torch.isnan(raw_c[15 * L:]).all()), "a guard float was written"
+    whole = np.concatenate([_bits(x) for x in (confs, dm, info, block)])
+    assert whole.size == n_out and np.array_equal(_bits(buf[:n_out]), whole) and np.array_equal(_bits(raw_c[:15 * L]), _bits(coords))
+    # the pipeline
+    ticket = pipe.submit(d_msa, 2, 0, native=native)
+    res = pipe.collect([ticket])[ticket]
+    assert not isinstance(res, Exception), res
+    assert len(res) == 5 and [tuple(x.shape) for x in res] == [(L, 5, 3), (L,), (L, L), (3,), (5 * L + 24,)]
+    for name, a, b in zip(("coords", "confs", "distmap", "info", "score block"), res, (coords, confs, dm, info, block)):
+        assert np.array_equal(_bits(a), _bits(b)), (L, name)
+
+
 # ------------------------------------------------------------------------------------------------ 7. software-latched fault
 def test_latched_fault_gives_nan_in_every_out_slot(eng):
     """A residue code of 22 raises the device-side flag DMP_FAULT_BAD_CODE (a software flag, not a GPU fault): every out
