@@ -20,7 +20,8 @@
 // Two forms, same interface (vgru_group_setup / vgru_group_steps / vgru_group_output):
 //   * the PERSISTENT weight-stationary launch (round 4, the default on a 256-CU device): the whole chain in
 //     one launch, columns partitioned over the XCDs, hidden units over the CUs of an XCD, weights resident
-//     in registers and LDS, XCD-local row barriers - see vgru_persist_kernel;
+//     in registers and LDS, XCD-local row barriers - see vgru_persist_kernel; what it shares with the float32 kernel
+//     (slice claim, tile table, reduction through LDS) and with both others (row barrier) is the vp_* functions of vgru.h;
 //   * one launch PER ROW (round 3, option "vgru_persistent" = 0 and the fallback on other devices): the
 //     group step kernel below, replayed from hipGraph chains of 128 (or 16) nodes.
 #include "common.h"
@@ -453,26 +454,14 @@ void vgru_persist_kernel(VStatic st, const VGroupRec* __restrict__ rec, VPSync* 
   vp_f32x4* red = reinterpret_cast<vp_f32x4*>(vp_smem + VP_WL0_SLOTS * 16);
   float* tab = reinterpret_cast<float*>(vp_smem + (VP_WL0_SLOTS + VP_RED_SLOTS) * 16);
   __shared__ int sh_u, sh_abort;
-  // this XCD's column tiles: {rows N, columns L, first column of the tile in ITS alignment, member} and the members'
-  // alignments - from the group record in global memory once per launch (a tile's bookkeeping was a chain of four to
-  // six dependent scalar loads at the head of every tile before)
+  // this XCD's column tiles and the members' alignments (vp_tile_table, vgru.h)
   __shared__ int sh_tile[VP_MAX_XCD_TILES][4];
   __shared__ unsigned long long sh_msa[VG_MAX_MEMBERS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   unsigned xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  xcc &= 7u;
-  if (tid == 0) {
-    sh_u = (int)__hip_atomic_fetch_add(&sync->count[xcc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sh_abort = 0;
-  }
-  __syncthreads();
-  const int u = sh_u;                                  // this workgroup's hidden-unit slice on its XCD
-  if (u >= 32) {                                       // more than 32 workgroups landed on this XCD: another one is short
-    if (tid == 0) atomicOr(fault, DMP_FAULT_VGRU_HANDOFF);
-    return;
-  }
+  int u;                                               // this workgroup's hidden-unit slice on its XCD
+  if (!vp_claim_slice(sync, fault, 1, tid, &sh_u, &sh_abort, xcc, u)) return;     // always with the row barrier
   const int j0 = 16 * u, lr = lane & 15, lq = lane >> 4;
   const int Lb = ntiles * VG_TB;
   const int c_lo = (int)(((long long)ntiles * xcc) / 8), c_hi = (int)(((long long)ntiles * (xcc + 1)) / 8);
@@ -510,33 +499,8 @@ void vgru_persist_kernel(VStatic st, const VGroupRec* __restrict__ rec, VPSync* 
   const int nmem = rec->nmem;
   __syncthreads();
 
-  // member of a column tile / is the tile computed at row t (layer 0: t < N; layer 1, one row behind: 1 <= t <= N)
-  auto member_of = [&](int ct) {
-    int mi = 0;
-    for (int m = 1; m < VG_MAX_MEMBERS; ++m)
-      if (m < nmem && ct >= rec->mem[m].tile0) mi = m;
-    return mi;
-  };
-  if (c_hi - c_lo > VP_MAX_XCD_TILES) {                 // (the host never builds such a group: 8 x 2048 columns = 64 tiles per XCD)
-    if (tid == 0) atomicOr(fault, DMP_FAULT_VGRU_HANDOFF);
-    return;
-  }
-  for (int i = tid; i < c_hi - c_lo; i += 256) {
-    const int mi = member_of(c_lo + i);
-    sh_tile[i][0] = rec->mem[mi].N;
-    sh_tile[i][1] = rec->mem[mi].L;
-    sh_tile[i][2] = (c_lo + i - rec->mem[mi].tile0) * VG_TB;
-    sh_tile[i][3] = mi;
-  }
-  if (tid < VG_MAX_MEMBERS) sh_msa[tid] = tid < nmem ? (unsigned long long)rec->mem[tid].msa : 0ull;
-  __syncthreads();
-  auto next_active = [&](int ct, int t) {               // first tile >= ct of this XCD that is computed at row t, or c_hi
-    for (; ct < c_hi; ++ct) {
-      const int N = __builtin_amdgcn_readfirstlane(sh_tile[ct - c_lo][0]);
-      if (t < N || (t >= 1 && t <= N)) break;
-    }
-    return ct;
-  };
+  if (!vp_tile_table(rec, nmem, c_lo, c_hi, tid, fault, sh_tile, sh_msa)) return;
+  auto next_active = [&](int ct, int t) { return vp_next_active(sh_tile, c_lo, c_hi, ct, t); };
   // State pieces of this wave's K quarter for one column tile: [k-step][piece][column half], as buffer loads the
   // compiler tracks itself (raw_buffer_load with the sc1 bit: past the L1, served by the XCD's L2).  A first version
   // used inline-assembly loads with hand-counted waits, as the launch-per-row kernel does; with registers carried
@@ -657,32 +621,19 @@ void vgru_persist_kernel(VStatic st, const VGroupRec* __restrict__ rec, VPSync* 
       }
       vp_mfma_results_ready(a1);
       // ---- partial sums of the four K quarters meet in LDS
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) red[(w * 14 + g * 2 + nt) * 64 + lane] = a0[g][nt];
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) red[(w * 14 + 6 + g * 2 + nt) * 64 + lane] = a1[g][nt];
+      vp_store_partials(red, w, lane, a0, a1);
       __syncthreads();
       if (fl ? act1 : act0) {
         const int nq = fl ? 4 : 3, base = fl ? 6 : 0;
         vp_f32x4 sum[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          if (q < nq) {
-            const int a = base + q * 2 + fnt;
-            sum[q] = ((red[(0 * 14 + a) * 64 + flane] + red[(1 * 14 + a) * 64 + flane]) + red[(2 * 14 + a) * 64 + flane]) +
-                     red[(3 * 14 + a) * 64 + flane];
-          }
+          if (q < nq) sum[q] = vp_quarter_sum(red, base + q * 2 + fnt, flane);
         }
         if (fl == 0) {
-          const float* tr = tab + (0 * 24 + code) * 16 + 4 * fg;
-          const float* tz = tab + (1 * 24 + code) * 16 + 4 * fg;
-          const float* tn = tab + (2 * 24 + code) * 16 + 4 * fg;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { sum[0][i] += tr[i]; sum[1][i] += tz[i]; sum[3][i] = tn[i]; }
+          sum[0] += vp_onehot_term(tab, 0, code, fg);
+          sum[1] += vp_onehot_term(tab, 1, code, fg);
+          sum[3] = vp_onehot_term(tab, 2, code, fg);
         }
         const float br[4] = {bR.x, bR.y, bR.z, bR.w}, bz[4] = {bZ.x, bZ.y, bZ.z, bZ.w};
         const float bi[4] = {bI.x, bI.y, bI.z, bI.w}, bh[4] = {bH.x, bH.y, bH.z, bH.w};
@@ -710,28 +661,7 @@ void vgru_persist_kernel(VStatic st, const VGroupRec* __restrict__ rec, VPSync* 
       __syncthreads();                                 // `red` is free for the next tile
       ct = nx;
     }
-    // ---- row boundary: every workgroup of this XCD has written its rows of the new state
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's stores have reached the L2
-    __syncthreads();
-    const unsigned epoch = (unsigned)(t - t_lo + 1);
-    if (tid == 0) asm volatile("global_store_dword %0, %1, off" :: "v"(&sync->flag[xcc][u]), "v"(epoch) : "memory");
-    if (w == 0) {
-      const unsigned* fp = &sync->flag[xcc][lane & 31];
-      bool ok = false;
-      const unsigned bound = t == t_lo ? VP_BARRIER_SPINS_FIRST : VP_BARRIER_SPINS;      // vgru.h: the first barrier is the residency wait
-      for (unsigned spins = 0; spins < bound && !ok; ++spins) {
-        unsigned v;
-        asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(fp) : "memory");
-        ok = __builtin_amdgcn_ballot_w64(v < epoch) == 0ull;
-      }
-      if (!ok && lane == 0) { atomicOr(fault, DMP_FAULT_VGRU_HANDOFF); sh_abort = 1; }
-    }
-    __syncthreads();
-    // A workgroup of this XCD is missing for good (not resident, or one XCD got a 33rd workgroup and another is short):
-    // the fault bit is raised and the outputs of this prediction become NaN - leave the row loop now, the whole
-    // workgroup together, instead of waiting the full bound again at each of the up to 3001 rows that are left
-    // (seconds per row = a GPU that looks hung for hours before dmp_sync_faults returns).
-    if (sh_abort) break;
+    if (vp_row_barrier(sync, fault, xcc, u, w, lane, tid, t, t_lo, &sh_abort)) break;
   }
 }
 
@@ -739,11 +669,8 @@ void vgru_persist_kernel(VStatic st, const VGroupRec* __restrict__ rec, VPSync* 
 static int vgru2_nw(int ntiles) { return ntiles >= 24 ? 4 : (ntiles >= 12 ? 2 : 1); }
 static int vgru2_cgs(int ntiles) { return ntiles >= 24 ? 2 : 1; }
 
-static int vgru2_graph(dmp_ctx* c, int ntiles, int nw, int cgs, int len, hipGraphExec_t* out) {
-  const int grid = vgru2_grid(ntiles, nw, cgs);
-  const int64_t key = ((int64_t)1 << 62) | ((int64_t)cgs << 52) | ((int64_t)nw << 48) | ((int64_t)ntiles << 16) | len;
-  auto it = c->vgru_graphs.find(key);
-  if (it != c->vgru_graphs.end()) { *out = (hipGraphExec_t)it->second; return DMP_OK; }
+// the weight pieces and the state buffers of context c, for the step kernel and the persistent one
+static VStatic vgru_static(const dmp_ctx* c) {
   const Weights& W = c->W;
   VStatic st{};
   for (int l = 0; l < 2; ++l) {
@@ -753,6 +680,15 @@ static int vgru2_graph(dmp_ctx* c, int ntiles, int nw, int cgs, int len, hipGrap
     for (int p = 0; p < 2; ++p) { st.hT[l][p] = c->hT[l][p]; st.hH[l][p] = c->hH[l][p]; }
   }
   st.bias[0] = W.v_b0; st.bias[1] = W.v_b1;
+  return st;
+}
+
+static int vgru2_graph(dmp_ctx* c, int ntiles, int nw, int cgs, int len, hipGraphExec_t* out) {
+  const int grid = vgru2_grid(ntiles, nw, cgs);
+  const int64_t key = ((int64_t)1 << 62) | ((int64_t)cgs << 52) | ((int64_t)nw << 48) | ((int64_t)ntiles << 16) | len;
+  auto it = c->vgru_graphs.find(key);
+  if (it != c->vgru_graphs.end()) { *out = (hipGraphExec_t)it->second; return DMP_OK; }
+  VStatic st = vgru_static(c);
   const VGroupRec* rec = reinterpret_cast<const VGroupRec*>(c->vgru_run);
   void* fn = nw == 4 ? (void*)vgru2_step_kernel<4> : (nw == 2 ? (void*)vgru2_step_kernel<2> : (void*)vgru2_step_kernel<1>);
   hipGraph_t g;
@@ -849,15 +785,7 @@ int vgru_group_steps(dmp_ctx* lead, int t_lo, int t_hi, hipStream_t s) {
   VGroupRec* rec = reinterpret_cast<VGroupRec*>(lead->vgru_run);
   if (lead->vgru_persist && lead->vgru_persist_ok) {
     // one launch for all the rows: XCD-local row barriers inside (vgru_persist_kernel)
-    const Weights& W = lead->W;
-    VStatic st{};
-    for (int l = 0; l < 2; ++l) {
-      st.wx[l] = reinterpret_cast<const uint4*>(W.v_wx[l]);
-      st.wh[l] = reinterpret_cast<const uint4*>(W.v_wh[l]);
-      st.inv_scale[l] = W.v_inv_scale[l];
-      for (int p = 0; p < 2; ++p) { st.hT[l][p] = lead->hT[l][p]; st.hH[l][p] = lead->hH[l][p]; }
-    }
-    st.bias[0] = W.v_b0; st.bias[1] = W.v_b1;
+    const VStatic st = vgru_static(lead);
     if (t_lo >= t_hi) return DMP_OK;
     VPSync* sync = reinterpret_cast<VPSync*>(lead->vgru_sync);
     // needs every one of its 256 workgroups resident (row barriers): ordered against the process's other persistent

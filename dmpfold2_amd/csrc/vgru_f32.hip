@@ -4,7 +4,9 @@
 // Selected with option "precision" = 1 (together with the exact-f32 convolution, conv_mode 1) or "vgru_f32" = 1; the
 // default path stays the split-f16 form of vgru.hip (three f16 MFMAs per float32 product, 5.3 x the matrix-core rate).
 //
-// Same decomposition as vgru_persist_kernel (vgru.hip), because a float32 weight is as many bytes as its two f16 pieces:
+// Same decomposition as vgru_persist_kernel (vgru.hip), because a float32 weight is as many bytes as its two f16 pieces
+// (what the kernels share as code - slice claim, tile table, reduction through LDS, GRU cell, row barrier, the launcher -
+// is in vgru.h; this file holds the float32 products):
 //   * weight-stationary and persistent: the group's column tiles are partitioned over the 8 XCDs, the hidden units over the
 //     32 CUs of an XCD (CU u: units 16u .. 16u+15 of both layers, all gates, all three products), K over the 4 waves of a
 //     CU; wave w keeps its K quarter of the two layer-1 products in 192 AGPRs (A operands of the MFMA straight from the
@@ -25,15 +27,6 @@
 #include "vgru.h"
 
 namespace dmp {
-
-struct VStaticF32 {
-  const float4* wh0;        // layer-0 recurrent weights  [gate 3][k/4 = 128][512 j] x float4 (k % 4)
-  const float4* wx1;        // layer-1 input weights      (same layout)
-  const float4* wh1;        // layer-1 recurrent weights
-  const float* wx0;         // layer-0 input weights with the embedding folded in: [gate 3][code 22][512 j]
-  const float* bias[2];     // [layer]: [4][512]: r (b_ir+b_hr), z (b_iz+b_hz), b_in, b_hn
-  float* hT[2][2];          // [layer][parity] float32 state [128][Lb][4]
-};
 
 // The inline-assembly MFMAs are invisible to the compiler's hazard recogniser in BOTH directions.  Found on the GPU (first
 // build of this kernel, tools/debug_vgru_f32.py): the compiler sinks the zero-initialisation of an accumulator
@@ -60,8 +53,6 @@ __device__ __forceinline__ void vf_mfma_results_ready(vp_f32x4 (&a)[4][2]) {
                                        "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]), "+v"(a[3][1]));
 }
 
-__device__ __forceinline__ float vf_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 constexpr int VF_SS = 8;                                  // super-steps (16 k) of a wave's K quarter
 static_assert(4 * VF_SS * 3 * 64 == VP_WL0_SLOTS, "layer 0's float32 weights fill the LDS area of the f16 pieces");
 
@@ -78,24 +69,8 @@ void vgru_persist_f32_kernel(VStaticF32 st, const VGroupRec* __restrict__ rec, V
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   unsigned xcc;
-  if (barrier) {
-    // the XCD this workgroup really runs on (its L2 is where the row barrier's plain stores stop)
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7u;
-    if (tid == 0) {
-      sh_u = (int)__hip_atomic_fetch_add(&sync->count[xcc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      sh_abort = 0;
-    }
-  } else {
-    xcc = blockIdx.x & 7u;                               // one row per launch: nothing depends on the placement
-    if (tid == 0) { sh_u = (int)(blockIdx.x >> 3); sh_abort = 0; }
-  }
-  __syncthreads();
-  const int u = sh_u;                                    // this workgroup's hidden-unit slice on its XCD
-  if (u >= 32) {                                         // more than 32 workgroups landed on this XCD: another one is short
-    if (tid == 0) atomicOr(fault, DMP_FAULT_VGRU_HANDOFF);
-    return;
-  }
+  int u;                                                 // this workgroup's hidden-unit slice on its XCD
+  if (!vp_claim_slice(sync, fault, barrier, tid, &sh_u, &sh_abort, xcc, u)) return;
   const int j0 = 16 * u, lr = lane & 15, lq = lane >> 4;
   const int Lb = ntiles * VG_TB;
   const int c_lo = (int)(((long long)ntiles * xcc) / 8), c_hi = (int)(((long long)ntiles * (xcc + 1)) / 8);
@@ -127,28 +102,8 @@ void vgru_persist_f32_kernel(VStaticF32 st, const VGroupRec* __restrict__ rec, V
   const float4 bI = *reinterpret_cast<const float4*>(st.bias[fl] + 1024 + j4);
   const float4 bH = *reinterpret_cast<const float4*>(st.bias[fl] + 1536 + j4);
   const int nmem = rec->nmem;
-  if (c_hi - c_lo > VP_MAX_XCD_TILES) {                  // (the host never builds such a group: 8 x 2048 columns = 64 tiles per XCD)
-    if (tid == 0) atomicOr(fault, DMP_FAULT_VGRU_HANDOFF);
-    return;
-  }
-  for (int i = tid; i < c_hi - c_lo; i += 256) {
-    int mi = 0;
-    for (int m = 1; m < VG_MAX_MEMBERS; ++m)
-      if (m < nmem && c_lo + i >= rec->mem[m].tile0) mi = m;
-    sh_tile[i][0] = rec->mem[mi].N;
-    sh_tile[i][1] = rec->mem[mi].L;
-    sh_tile[i][2] = (c_lo + i - rec->mem[mi].tile0) * VG_TB;
-    sh_tile[i][3] = mi;
-  }
-  if (tid < VG_MAX_MEMBERS) sh_msa[tid] = tid < nmem ? (unsigned long long)rec->mem[tid].msa : 0ull;
-  __syncthreads();
-  auto next_active = [&](int ct, int t) {                // first tile >= ct of this XCD that is computed at row t, or c_hi
-    for (; ct < c_hi; ++ct) {
-      const int N = __builtin_amdgcn_readfirstlane(sh_tile[ct - c_lo][0]);
-      if (t < N || (t >= 1 && t <= N)) break;            // layer 0: t < N; layer 1, one row behind: 1 <= t <= N
-    }
-    return ct;
-  };
+  if (!vp_tile_table(rec, nmem, c_lo, c_hi, tid, fault, sh_tile, sh_msa)) return;
+  auto next_active = [&](int ct, int t) { return vp_next_active(sh_tile, c_lo, c_hi, ct, t); };
   typedef unsigned vf_u32x4v __attribute__((vector_size(16)));
   constexpr int VF_SC1 = 16;                             // cache-policy bit of the buffer loads: past the L1, served by the L2
   // super-step ss of a tile's state (both layers, both column halves) -> register slot
@@ -250,69 +205,33 @@ void vgru_persist_f32_kernel(VStaticF32 st, const VGroupRec* __restrict__ rec, V
       }
       vf_mfma_results_ready(a1);
       // ---- partial sums of the four K quarters meet in LDS
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) red[(w * 14 + g * 2 + nt) * 64 + lane] = a0[g][nt];
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) red[(w * 14 + 6 + g * 2 + nt) * 64 + lane] = a1[g][nt];
+      vp_store_partials(red, w, lane, a0, a1);
       __syncthreads();
       if (fl ? act1 : act0) {
         const int nq = fl ? 4 : 3, base = fl ? 6 : 0;
         vp_f32x4 sum[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          if (q < nq) {
-            const int a = base + q * 2 + fnt;
-            sum[q] = ((red[(0 * 14 + a) * 64 + flane] + red[(1 * 14 + a) * 64 + flane]) + red[(2 * 14 + a) * 64 + flane]) +
-                     red[(3 * 14 + a) * 64 + flane];
-          }
+          if (q < nq) sum[q] = vp_quarter_sum(red, base + q * 2 + fnt, flane);
         }
         if (fl == 0) {
-          const float* tr = tab + (0 * 24 + code) * 16 + 4 * fg;
-          const float* tz = tab + (1 * 24 + code) * 16 + 4 * fg;
-          const float* tn = tab + (2 * 24 + code) * 16 + 4 * fg;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { sum[0][i] += tr[i]; sum[1][i] += tz[i]; sum[3][i] = tn[i]; }
+          sum[0] += vp_onehot_term(tab, 0, code, fg);
+          sum[1] += vp_onehot_term(tab, 1, code, fg);
+          sum[3] = vp_onehot_term(tab, 2, code, fg);
         }
         const float br[4] = {bR.x, bR.y, bR.z, bR.w}, bz[4] = {bZ.x, bZ.y, bZ.z, bZ.w};
         const float bi[4] = {bI.x, bI.y, bI.z, bI.w}, bh[4] = {bH.x, bH.y, bH.z, bH.w};
         float hn[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          // network.py:224 -> ATen's GRU cell: r = sigmoid(i_r + h_r), z = sigmoid(i_z + h_z),
-          // n = tanh(i_n + r * h_n), h' = (h - n) * z + n
-          const float rg = vf_sigmoid(sum[0][i] + br[i]);
-          const float zg = vf_sigmoid(sum[1][i] + bz[i]);
-          const float ng = tanhf((sum[3][i] + bi[i]) + rg * (sum[2][i] + bh[i]));
-          hn[i] = (hp[i] - ng) * zg + ng;
-        }
+        for (int i = 0; i < 4; ++i)
+          hn[i] = vp_gru_cell(sum[0][i], sum[1][i], sum[2][i], sum[3][i], br[i], bz[i], bi[i], bh[i], hp[i]);
         *reinterpret_cast<float4*>(hnext + hoff) = make_float4(hn[0], hn[1], hn[2], hn[3]);
       }
       __syncthreads();                                   // `red` is free for the next tile
       ct = nx;
     }
     if (!barrier) break;                                 // one row per launch: the kernel boundary is the barrier
-    // ---- row boundary: every workgroup of this XCD has written its rows of the new state
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's stores have reached the L2
-    __syncthreads();
-    const unsigned epoch = (unsigned)(t - t_lo + 1);
-    if (tid == 0) asm volatile("global_store_dword %0, %1, off" :: "v"(&sync->flag[xcc][u]), "v"(epoch) : "memory");
-    if (w == 0) {
-      const unsigned* fp = &sync->flag[xcc][lane & 31];
-      bool ok = false;
-      const unsigned bound = t == t_lo ? VP_BARRIER_SPINS_FIRST : VP_BARRIER_SPINS;      // vgru.h: the first barrier is the residency wait
-      for (unsigned spins = 0; spins < bound && !ok; ++spins) {
-        unsigned v;
-        asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(fp) : "memory");
-        ok = __builtin_amdgcn_ballot_w64(v < epoch) == 0ull;
-      }
-      if (!ok && lane == 0) { atomicOr(fault, DMP_FAULT_VGRU_HANDOFF); sh_abort = 1; }
-    }
-    __syncthreads();
-    if (sh_abort) break;                                 // a workgroup is missing for good: leave together (vgru.hip)
+    if (vp_row_barrier(sync, fault, xcc, u, w, lane, tid, t, t_lo, &sh_abort)) break;
   }
 }
 
@@ -324,39 +243,7 @@ int vgru_f32_kernel_attrs(dmp_ctx* c) {
 
 // rows [t_lo, t_hi) of the group set up on `lead` (vgru_group_setup), float32
 int vgru_f32_group_steps(dmp_ctx* lead, int t_lo, int t_hi, hipStream_t s) {
-  const int nt = lead->vg_ntiles;
-  if (t_hi > lead->vg_maxN + 1) t_hi = lead->vg_maxN + 1;
-  if (t_lo < 0) t_lo = 0;
-  if (t_lo >= t_hi) return DMP_OK;
-  const Weights& W = lead->W;
-  VStaticF32 st{};
-  st.wh0 = reinterpret_cast<const float4*>(W.v_f32[0]);
-  st.wx1 = reinterpret_cast<const float4*>(W.v_f32[1]);
-  st.wh1 = reinterpret_cast<const float4*>(W.v_f32[2]);
-  st.wx0 = W.v_wx0f;
-  st.bias[0] = W.v_b0; st.bias[1] = W.v_b1;
-  for (int l = 0; l < 2; ++l)
-    for (int p = 0; p < 2; ++p) st.hT[l][p] = lead->hT[l][p];
-  const VGroupRec* rec = reinterpret_cast<const VGroupRec*>(lead->vgru_run);
-  VPSync* sync = reinterpret_cast<VPSync*>(lead->vgru_sync);
-  // A device without 256 CUs in 8 XCDs (partitioned / CPX modes: vgru_persist_ok is false) gets the launch-per-row form
-  // below: with the barrier off the kernel takes its (XCD, slice) from the block id and depends on no placement.
-  if (lead->vgru_persist && lead->vgru_persist_ok) {
-    // needs every one of its 256 workgroups resident (row barriers): ordered against the process's other persistent
-    // launches and cluster kernels on this device (CoResident, common.h)
-    CoResident guard(lead, s, true);
-    if (guard.status()) return guard.status();
-    DMP_HIP(hipMemsetAsync(sync, 0, sizeof(VPSync), s));
-    hipLaunchKernelGGL(vgru_persist_f32_kernel, dim3(VP_GRID - (lead->vgru_debug_drop_wg ? 1 : 0)), dim3(256), VP_LDS_BYTES, s, st, rec,
-                       sync, lead->seq_abort, t_lo, t_hi, nt, 1);
-    DMP_LAUNCH_CHECK();
-    return guard.done();
-  }
-  for (int t = t_lo; t < t_hi; ++t)
-    hipLaunchKernelGGL(vgru_persist_f32_kernel, dim3(VP_GRID), dim3(256), VP_LDS_BYTES, s, st, rec, sync, lead->seq_abort,
-                       t, t + 1, nt, 0);
-  DMP_LAUNCH_CHECK();
-  return DMP_OK;
+  return vgru_f32_launch(vgru_persist_f32_kernel, lead, t_lo, t_hi, s);
 }
 
 }  // namespace dmp

@@ -27,22 +27,14 @@
 // Summation order (K quarters in wave order, the slice's K-step order, piece products (w0 x2) (w1 x1) (w0 x1) (w2 x0)
 // (w1 x0) (w0 x0)) does not depend on the grouping: a member's result is the same bits alone, in any group and as a rider;
 // the launch-per-row fallback is the same kernel with the barrier off.
+// The argument struct, the launcher and the row barrier are the float32 form's (vgru.h).  The slice claim, the tile table,
+// the reduction and the GRU cell below repeat the text of vgru.h's vp_* functions on purpose: this kernel fills the
+// register file (14 spilled), calling them changed its register allocation and cost 4 % of the chain time.
 #include "vgru.h"
 
 namespace dmp {
 
 typedef __bf16 vx_bf16x8 __attribute__((ext_vector_type(8)));
-
-struct VStaticX3 {
-  const float4* wh0;        // layer-0 recurrent weights  [gate 3][k/4 = 128][512 j] x float4 (k % 4)  (the float32 pack)
-  const float4* wx1;        // layer-1 input weights      (same layout)
-  const float4* wh1;        // layer-1 recurrent weights
-  const float* wx0;         // layer-0 input weights with the embedding folded in: [gate 3][code 22][512 j]
-  const float* bias[2];     // [layer]: [4][512]: r (b_ir+b_hr), z (b_iz+b_hz), b_in, b_hn
-  float* hT[2][2];          // [layer][parity] float32 state [128][Lb][4]
-  uint4* wq;                // the weight pieces a wave streams instead of holding: [workgroup 256][wave 4][K step 4][6][lane 64]
-};
-
 
 // x == p[0] + p[1] + p[2] exactly (round-to-nearest pieces, conv_bf16.h split3_bf16), eight values at a time
 __device__ __forceinline__ void vx_split8(const float (&w)[8], vx_bf16x8 (&p)[3]) {
@@ -158,7 +150,7 @@ __device__ __forceinline__ void vx_tile_products(vp_f32x4 (&a0)[3][2], vp_f32x4 
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void vgru_persist_x3_kernel(VStaticX3 st, const VGroupRec* __restrict__ rec, VPSync* __restrict__ sync,
+void vgru_persist_x3_kernel(VStaticF32 st, const VGroupRec* __restrict__ rec, VPSync* __restrict__ sync,
                             int* __restrict__ fault, int t_lo, int t_hi, int ntiles, int barrier) {
   extern __shared__ __attribute__((aligned(16))) unsigned char vx_smem[];
   vx_bf16x8* wl0 = reinterpret_cast<vx_bf16x8*>(vx_smem);                                    // [wave][K step][gate][piece 0 1][lane]
@@ -377,24 +369,7 @@ void vgru_persist_x3_kernel(VStaticX3 st, const VGroupRec* __restrict__ rec, VPS
       ct = nx;
     }
     if (!barrier) break;                                 // one row per launch: the kernel boundary is the barrier
-    // ---- row boundary: every workgroup of this XCD has written its rows of the new state
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's stores have reached the L2
-    __syncthreads();
-    const unsigned epoch = (unsigned)(t - t_lo + 1);
-    if (tid == 0) asm volatile("global_store_dword %0, %1, off" :: "v"(&sync->flag[xcc][u]), "v"(epoch) : "memory");
-    if (w == 0) {
-      const unsigned* fp = &sync->flag[xcc][lane & 31];
-      bool ok = false;
-      const unsigned bound = t == t_lo ? VP_BARRIER_SPINS_FIRST : VP_BARRIER_SPINS;      // vgru.h: the first barrier is the residency wait
-      for (unsigned spins = 0; spins < bound && !ok; ++spins) {
-        unsigned v;
-        asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(fp) : "memory");
-        ok = __builtin_amdgcn_ballot_w64(v < epoch) == 0ull;
-      }
-      if (!ok && lane == 0) { atomicOr(fault, DMP_FAULT_VGRU_HANDOFF); sh_abort = 1; }
-    }
-    __syncthreads();
-    if (sh_abort) break;                                 // a workgroup is missing for good: leave together (vgru.hip)
+    if (vp_row_barrier(sync, fault, xcc, u, w, lane, tid, t, t_lo, &sh_abort)) break;
   }
 }
 
@@ -408,38 +383,7 @@ int vgru_x3_kernel_attrs(dmp_ctx* c) {
 
 // rows [t_lo, t_hi) of the group set up on `lead` (vgru_group_setup), exact three-piece bf16 products
 int vgru_x3_group_steps(dmp_ctx* lead, int t_lo, int t_hi, hipStream_t s) {
-  const int nt = lead->vg_ntiles;
-  if (t_hi > lead->vg_maxN + 1) t_hi = lead->vg_maxN + 1;
-  if (t_lo < 0) t_lo = 0;
-  if (t_lo >= t_hi) return DMP_OK;
-  const Weights& W = lead->W;
-  VStaticX3 st{};
-  st.wh0 = reinterpret_cast<const float4*>(W.v_f32[0]);
-  st.wx1 = reinterpret_cast<const float4*>(W.v_f32[1]);
-  st.wh1 = reinterpret_cast<const float4*>(W.v_f32[2]);
-  st.wx0 = W.v_wx0f;
-  st.bias[0] = W.v_b0; st.bias[1] = W.v_b1;
-  for (int l = 0; l < 2; ++l)
-    for (int p = 0; p < 2; ++p) st.hT[l][p] = lead->hT[l][p];
-  st.wq = reinterpret_cast<uint4*>(lead->vgru_wq);
-  const VGroupRec* rec = reinterpret_cast<const VGroupRec*>(lead->vgru_run);
-  VPSync* sync = reinterpret_cast<VPSync*>(lead->vgru_sync);
-  // (a device without 256 CUs in 8 XCDs gets the launch-per-row form: with the barrier off the kernel takes its (XCD,
-  // slice) from the block id and depends on no placement)
-  if (lead->vgru_persist && lead->vgru_persist_ok) {
-    CoResident guard(lead, s, true);
-    if (guard.status()) return guard.status();
-    DMP_HIP(hipMemsetAsync(sync, 0, sizeof(VPSync), s));
-    hipLaunchKernelGGL(vgru_persist_x3_kernel, dim3(VP_GRID - (lead->vgru_debug_drop_wg ? 1 : 0)), dim3(256), VP_LDS_BYTES, s, st, rec,
-                       sync, lead->seq_abort, t_lo, t_hi, nt, 1);
-    DMP_LAUNCH_CHECK();
-    return guard.done();
-  }
-  for (int t = t_lo; t < t_hi; ++t)
-    hipLaunchKernelGGL(vgru_persist_x3_kernel, dim3(VP_GRID), dim3(256), VP_LDS_BYTES, s, st, rec, sync, lead->seq_abort,
-                       t, t + 1, nt, 0);
-  DMP_LAUNCH_CHECK();
-  return DMP_OK;
+  return vgru_f32_launch(vgru_persist_x3_kernel, lead, t_lo, t_hi, s);
 }
 
 }  // namespace dmp
