@@ -144,12 +144,14 @@ def ca_only_text(coords, confs, alnmat):
     return "\n".join(out)
 
 
-def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None):
+def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
     npz gains n_pairs, lnorm, rmsd, tm, gdt_ts, gdt_ha, lddt, counts, R, t, lddt_res and deviation; pdb / ca get
-    <stem>.scores.json (the line `dmpfold --native` prints)."""
+    <stem>.scores.json (the line `dmpfold --native` prints).  With `alignment` (the dict of score.unpack_alignment,
+    --structures): npz gains the header fields of score.ALIGN_NAMES, ali, ali_R, ali_t and ali_deviation; pdb / ca get
+    <stem>.alignment.json (the line `dmpfold --compare` prints)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -163,6 +165,12 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
                           "counts": np.asarray(scores["counts"], dtype=np.int32)})
             extra.update({k: np.float32(scores[k]) for k in _score.SCORE_NAMES[1:]})
             extra.update({k: np.asarray(scores[k], dtype=np.float32) for k in ("R", "t", "lddt_res", "deviation")})
+        if alignment is not None:
+            extra.update({k: (np.int32 if k in ("n_ali", "seed_offset", "seeds") else np.float32)(alignment[k])
+                          for k in _score.ALIGN_NAMES})
+            extra.update({"ali": np.asarray(alignment["ali"], dtype=np.int32), "ali_R": np.asarray(alignment["R"], dtype=np.float32),
+                          "ali_t": np.asarray(alignment["t"], dtype=np.float32),
+                          "ali_deviation": np.asarray(alignment["deviation"], dtype=np.float32)})
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
@@ -171,6 +179,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     if scores is not None:
         with open(stem + ".scores.json", "w") as fh:
             fh.write(json.dumps(_score.scores_json(scores)) + "\n")
+    if alignment is not None:
+        with open(stem + ".alignment.json", "w") as fh:
+            fh.write(json.dumps(_score.alignment_json(alignment)) + "\n")
     path = stem + ".pdb"
     with open(path, "w") as fh:
         fh.write(pdb_text(coords, confs, alnmat) if fmt == "pdb" else ca_only_text(coords, confs, alnmat))
@@ -219,11 +230,15 @@ def cost_order(targets, iterations):
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
-              converge=None, stats_out=None, distmap=False, natives=None):
+              converge=None, stats_out=None, distmap=False, natives=None, structures=None):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
     unscored.  `stats_out` then receives "scores": {stem: the dict of score.scores_json}.
+    `structures`: a directory of structures of any length and sequence, <stem>.pdb for the target <stem>.aln / .a3m: such a
+    target's model is aligned with the structure's first chain on the GPU (Pipeline.set_align) and the alignment is written
+    with it (write_result); a target without a file is predicted without one.  `stats_out` then receives "alignments":
+    {stem: the header fields of score.alignment_json}.
     `distmap`: every target's chosen-pass distance map is brought back and written too (write_result).
     `converge` (Angstrom, None = off): targets stop recycling once converged (Pipeline.set_converge); `stats_out`, a
     dict, then receives this rank's "passes_run" and "passes_saved".
@@ -253,6 +268,21 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     any_a3m = any(a.endswith(".a3m") for a, _ in targets)
     max_L = max(8, max(L for L, _ in mine_scans))
     max_N = MAX_SEQS if any_a3m else max(1, min(MAX_SEQS, max(N for _, N in mine_scans)))
+    struct_ca = {}                                      # stem -> C-alpha trace of the structure to align with
+    if structures:
+        from .predict import MAX_L
+        for a, _ in targets:
+            stem = os.path.splitext(os.path.basename(a))[0]
+            path = os.path.join(structures, stem + ".pdb")
+            if os.path.exists(path):
+                ca = _score.read_native_ca(path)[0]
+                if 3 <= ca.shape[0] <= MAX_L:
+                    struct_ca[stem] = ca
+                else:
+                    print(f"dmpfold-batch: {path}: {ca.shape[0]} C-alpha atoms, outside [3, {MAX_L}]: {stem} is predicted "
+                          "without an alignment", file=sys.stderr)
+        # the engines hold both traces: their capacity covers the longest structure too
+        max_L = max([max_L] + [ca.shape[0] for ca in struct_ca.values()])
     t0 = time.perf_counter()
     pipe, dev, copy_stream = None, None, None
     failed, outputs, parsed, faulted = [], [], {}, []
@@ -270,6 +300,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_distmap(True)
             if natives:
                 pipe.set_score(True)
+            if structures:
+                pipe.set_align(True)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -302,16 +334,22 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             done.append(copying.pop(0)[:2])
 
     scored, all_scores = set(), {}
+    aligned, all_alignments = set(), {}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        out = Outputs.of(public, distmap, bool(natives))
+        out = Outputs.of(public, distmap, bool(natives), bool(structures))
         aln_path, alnmat, _ = parsed.pop(t)
         sc = None
         if out.score_block is not None and t in scored:
             sc = _score.unpack_scores(out.score_block, alnmat.shape[1])
             all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = _score.scores_json(sc)
-        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap, out.info, sc))
+        al = None
+        if out.align_block is not None and t in aligned:
+            al = _score.unpack_alignment(out.align_block, alnmat.shape[1])
+            js = _score.alignment_json(al)
+            all_alignments[os.path.splitext(os.path.basename(aln_path))[0]] = {k: js[k] for k in ("m",) + _score.ALIGN_NAMES}
+        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap, out.info, sc, al))
 
     def finish(item):
         t, public = item
@@ -354,10 +392,14 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                     d_msa = h_msa
                 # the pinned source stays alive in `parsed` until the target is written; the engine that takes the
                 # target orders its stream behind the stream that is current at submission (the copy stream)
-                t = p.submit(d_msa, iterations, minsteps, template_ca=tpl, **({"native": nat} if nat is not None else {}))
+                strc = struct_ca.get(os.path.splitext(os.path.basename(aln_path))[0])
+                t = p.submit(d_msa, iterations, minsteps, template_ca=tpl, **({"native": nat} if nat is not None else {}),
+                             **({"structure": strc} if strc is not None else {}))
                 parsed[t] = (aln_path, alnmat, h_msa)
                 if nat is not None:
                     scored.add(t)
+                if strc is not None:
+                    aligned.add(t)
         except (IndexError, ValueError, OSError, UnicodeDecodeError, RuntimeError) as exc:
             # unknown residue letter / ragged rows / unreadable file / larger than the scan said: this target only
             failed.append((aln_path, exc))
@@ -420,6 +462,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             stats_out["passes_run"], stats_out["passes_saved"] = st["passes_run"], st["passes_saved"]
         if stats_out is not None and natives:
             stats_out["scores"] = all_scores
+        if stats_out is not None and structures:
+            stats_out["alignments"] = all_alignments
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
@@ -450,6 +494,11 @@ def batch_parser():
                     help="directory of native structures, <stem>.pdb per target: such targets are scored on the GPU (TM-score, "
                          "GDT, RMSD, lDDT-CA); the summary gains the per-target scores, their means and medians; npz gains the "
                          "arrays, pdb / ca write <stem>.scores.json; a target without a file is predicted unscored")
+    ap.add_argument("--structures", default=None, metavar="DIR",
+                    help="directory of structures of any length and sequence, <stem>.pdb per target: such a target's model is "
+                         "aligned with the structure's first chain on the GPU (structural alignment, TM-scores by both lengths); "
+                         "the summary gains each target's header fields; npz gains the arrays, pdb / ca write "
+                         "<stem>.alignment.json; a target without a file is predicted without an alignment")
     return ap
 
 
@@ -491,7 +540,8 @@ def main(argv=None):
         n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                   weights_file=args.model_weights, streams=args.streams,
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
-                                  converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives)
+                                  converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
+                                  structures=args.structures)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -503,6 +553,8 @@ def main(argv=None):
         n, elapsed, status, broke = 0, 0.0, 2, 1
     if args.natives and world > 1:                   # host side, through the job's key-value store: read behind the reduction
         job_store.set(f"dmpfold_batch_scores/{rank}", json.dumps(passes.get("scores", {})))
+    if args.structures and world > 1:
+        job_store.set(f"dmpfold_batch_alignments/{rank}", json.dumps(passes.get("alignments", {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
         passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
@@ -519,6 +571,11 @@ def main(argv=None):
             for r in range(1, world):
                 scores.update(json.loads(job_store.get(f"dmpfold_batch_scores/{r}").decode()))
             summary.update(score_summary(dict(sorted(scores.items()))))
+        if args.structures:
+            alis = dict(passes.get("alignments", {}))
+            for r in range(1, world):
+                alis.update(json.loads(job_store.get(f"dmpfold_batch_alignments/{r}").decode()))
+            summary["aligned_targets"], summary["alignments"] = len(alis), dict(sorted(alis.items()))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

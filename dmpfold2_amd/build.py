@@ -17,15 +17,16 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libdmpfold_hip.so")
 SOURCES = ["api.hip", "pipeline.hip", "gemm.hip", "msa.hip", "dca.hip", "gru.hip", "vgru.hip", "vgru_f32.hip", "vgru_x3.hip", "trunk.hip", "train.hip", "mds.hip",
-           "coords.hip", "score.hip"]
+           "coords.hip", "score.hip", "align.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # coords.hip: no SLP vectoriser = no packed-f32 instructions.  The vectoriser turns the cross products of the
 # backbone kernel into v_pk_mul_f32 ... op_sel:[0,1] op_sel_hi:[1,0], which returns 0 in lanes 48..63 when
 # f16 / bf16 MFMA waves share the SIMD (tools/isa_lint.py guards every kernel against it).
 # gru.hip: the same for the matrix-vector loop of seq_gru_kernel (v_pk_fma_f32 ... op_sel:[0,1,0] appeared when the gate
 # evaluation was spread over the lanes).
-# score.hip: float64 throughout, nothing to pack; the flag keeps it so.
-PER_FILE_FLAGS = {"coords.hip": ["-fno-slp-vectorize"], "gru.hip": ["-fno-slp-vectorize"], "score.hip": ["-fno-slp-vectorize"]}
+# score.hip, align.hip: float64 throughout, nothing to pack; the flag keeps it so.
+PER_FILE_FLAGS = {"coords.hip": ["-fno-slp-vectorize"], "gru.hip": ["-fno-slp-vectorize"], "score.hip": ["-fno-slp-vectorize"],
+                  "align.hip": ["-fno-slp-vectorize"]}
 
 
 def per_file_flags(src: str) -> list:
@@ -51,7 +52,7 @@ def _stale(target, deps):
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "conv_bf16.h", "conv_f16.h", "vgru.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "conv_bf16.h", "conv_f16.h", "vgru.h", "score_common.h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "dmpfold_hip.h"))
     extra = os.environ.get("DMP_EXTRA_HIPCC_FLAGS", "").split()      # tuning experiments (-DVG_CH=1 ...)
     lib = os.environ.get("DMP_LIB_OUT", LIB)

@@ -1,0 +1,423 @@
+// option "align_structure": the final C-alpha trace aligned with a structure of any length and sequence (include/dmpfold_hip.h
+// has the layout of the align block and the definition of every number).  Three launches in dmp_predict_end behind score_native:
+//   align_prep    one workgroup: m validated, both traces packed (model from d_coords[:, 1], structure from the block), the
+//                 constants; NaN into every out slot.
+//   align_thread  stage 1, one workgroup per gapless threading (offset k): the shrinking-set loop of score_common.h on the
+//                 overlap, one record (tm) per seed; the last arriver (agent-scope ticket, common.h) ranks the records and
+//                 writes the AL_T survivors.
+//   align_refine  stage 2, one workgroup per survivor: superposition, dynamic programme as an anti-diagonal wavefront
+//                 (three rotating diagonals of H and of the diag flag in LDS, one barrier per diagonal, the directions one
+//                 byte per cell in a per-workgroup scratch in global memory), serial traceback, until the alignment
+//                 repeats; the last arriver picks the winner and writes the header, ali and the deviations.
+// Float64 from the float32 coordinates, contraction off, every sum in the fixed order of score_block_sum; every candidate
+// of a DP cell is one float64 add of two defined values, so H does not depend on the order the cells are evaluated in.
+// Every loop is bounded whatever the input holds, and every branch with a barrier inside is uniform over the workgroup.
+#include "score_common.h"
+
+namespace dmp {
+
+constexpr int AL_T = ALIGN_SURVIVORS;   // seeds refined
+constexpr int AL_ROUNDS = 10;           // superposition / DP rounds per survivor
+constexpr int AL_SLICE = (DMP_MAX_L + 1 + SC_THREADS - 1) / SC_THREADS;   // rows i = tid + 256 k of a diagonal per thread
+constexpr double AL_GAP = -0.6;         // added to a gap step that follows a diag step
+// header of the scratch
+constexpr int AH_VALID = 0, AH_N = 1, AH_M = 2, AH_LMIN = 3, AH_MINOV = 4, AH_SEEDS = 5, AH_D0S = 6, AH_DCUT = 7;
+
+__device__ __forceinline__ void agent_store_i32(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int agent_load_i32(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct AlignArgs {
+  const float* coords;   // [L][5][3] the backbone; the model trace is atom 1
+  float* blk;            // the align block: [0] m (in), [1, 25 + 2L) out, then the structure's trace (in)
+  int L, max_L;
+  float* pm;             // [L][3] model trace
+  float* qs;             // [m][3] structure trace
+  double* hdr;           // [8]
+  double* rec;           // [L + max_L + 1] tm of every seed of stage 1
+  int* surv;             // [1 + AL_T] how many survivors, their seed numbers in rank order
+  double* btm;           // [AL_T] stage 2: a survivor's best tm ...
+  int* bali;             // [AL_T][1 + 2 max_L] ... and its alignment: K, then K pairs (i, j)
+  unsigned char* dir;    // [AL_T][(max_L + 1)^2] directions of the DP in flight, one byte per cell
+  unsigned* ticket;      // [2] stage 1, stage 2: zero between launches
+};
+
+// ---------------------------------------------------------------------------------------
+// align_prep
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SC_THREADS) void align_prep_kernel(AlignArgs a) {
+  __shared__ int bad[SC_THREADS];
+  const int L = a.L, tid = threadIdx.x;
+  const AlignLayout lay = align_layout(L);
+  const float nan = __builtin_nanf("");
+  for (int i = 1 + tid; i < lay.in; i += SC_THREADS) a.blk[i] = nan;
+  const float mf = a.blk[0];
+  const bool m_ok = mf >= 3.f && mf <= (float)a.max_L && mf == floorf(mf);      // a NaN fails the comparisons
+  const int m = m_ok ? (int)mf : 0;                                              // 0: nothing beyond [0] is read
+  int mine = 0;
+  for (int i = tid; i < 3 * m; i += SC_THREADS) {
+    const float x = a.blk[lay.in + i];
+    mine |= x != x ? 1 : 0;
+    a.qs[i] = x;
+  }
+  for (int i = tid; i < 3 * L; i += SC_THREADS) a.pm[i] = a.coords[15 * (int64_t)(i / 3) + 3 + i % 3];
+  bad[tid] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    int any = 0;
+    for (int k = 0; k < SC_THREADS; ++k) any |= bad[k];
+    const int n = L, lmin = n < m ? n : m;
+    const int minov = lmin / 2 > (lmin < 5 ? lmin : 5) ? lmin / 2 : (lmin < 5 ? lmin : 5);
+    const double d0s = score_d0((double)lmin);
+    a.hdr[AH_VALID] = m_ok && !any ? 1.0 : 0.0;
+    a.hdr[AH_N] = (double)n;
+    a.hdr[AH_M] = (double)m;
+    a.hdr[AH_LMIN] = (double)lmin;
+    a.hdr[AH_MINOV] = (double)minov;
+    a.hdr[AH_SEEDS] = (double)(n + m - 2 * minov + 1);
+    a.hdr[AH_D0S] = d0s;
+    a.hdr[AH_DCUT] = fmin(fmax(d0s, 4.5), 8.0);
+    a.surv[0] = 0;
+  }
+}
+
+// the pairs of seed s: (i0 + t, i0 + k + t), t < ov
+__device__ inline void align_seed(int s, int n, int m, int minov, int& k, int& i0, int& ov) {
+  k = s - (n - minov);
+  i0 = k < 0 ? -k : 0;
+  ov = (n < m - k ? n : m - k) - i0;
+}
+
+// ---------------------------------------------------------------------------------------
+// align_thread: stage 1, one workgroup per offset
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SC_THREADS) void align_thread_kernel(AlignArgs a) {
+  extern __shared__ float sm[];          // 2 x 3 ov coordinates, then ov flags
+  __shared__ double wred[SC_WAVES][16];
+  __shared__ double bc[12];
+  __shared__ int sh_last, sh_seed[SC_WAVES], sh_chosen[AL_T], sh_found;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (a.hdr[AH_VALID] == 0.0) return;
+  const int n = (int)a.hdr[AH_N], m = (int)a.hdr[AH_M], minov = (int)a.hdr[AH_MINOV];
+  int nseeds = (int)a.hdr[AH_SEEDS];
+  if (nseeds > (int)gridDim.x) nseeds = (int)gridDim.x;      // never: the grid is L + max_L + 1 >= n + m - 2 minov + 1
+  if ((int)blockIdx.x >= nseeds) return;
+  const double lmin = a.hdr[AH_LMIN], d0s = a.hdr[AH_D0S], d_cut = a.hdr[AH_DCUT];
+  int k, i0, ov;
+  align_seed((int)blockIdx.x, n, m, minov, k, i0, ov);
+  float* pm = sm;
+  float* qn = sm + 3 * ov;
+  unsigned char* fl = reinterpret_cast<unsigned char*>(sm + 6 * ov);
+  for (int i = tid; i < 3 * ov; i += SC_THREADS) { pm[i] = a.pm[3 * i0 + i]; qn[i] = a.qs[3 * (i0 + k) + i]; }
+  for (int t = tid; t < ov; t += SC_THREADS) fl[t] = 1;
+  __syncthreads();
+  SeedBest best;
+  score_seed_loop(pm, qn, fl, ov, lmin, d0s, d_cut, wred, bc, best);
+  if (tid == 0) {
+    agent_store_f64(a.rec + blockIdx.x, best.tm);
+    sh_last = ticket_take_last(a.ticket, (unsigned)nseeds) ? 1 : 0;
+    if (sh_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  }
+  __syncthreads();
+  if (!sh_last) return;
+
+  // the last arriver: the AL_T best seeds in rank order (ties: the lower number), one maximum search per rank
+  for (int r = 0; r < AL_T; ++r) {
+    double top = -__builtin_inf();
+    int top_seed = 0x7fffffff;
+    for (int s = tid; s < nseeds; s += SC_THREADS) {
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= sh_chosen[q] == s;
+      const double tm = agent_load_f64(a.rec + s);
+      if (!taken && tm > top) { top = tm; top_seed = s; }      // s rises: the first of equals stays; a NaN is never taken
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const double o_top = __shfl_xor(top, off, 64);
+      const int o_seed = __shfl_xor(top_seed, off, 64);
+      if (o_top > top || (o_top == top && o_seed < top_seed)) { top = o_top; top_seed = o_seed; }
+    }
+    __syncthreads();
+    if (lane == 0) { wred[wv][0] = top; sh_seed[wv] = top_seed; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int q = 1; q < SC_WAVES; ++q)
+        if (wred[q][0] > top || (wred[q][0] == top && sh_seed[q] < top_seed)) { top = wred[q][0]; top_seed = sh_seed[q]; }
+      sh_found = top_seed != 0x7fffffff ? 1 : 0;
+      if (sh_found) {
+        sh_chosen[r] = top_seed;
+        a.surv[1 + r] = top_seed;
+        a.surv[0] = r + 1;
+      }
+    }
+    __syncthreads();
+    if (!sh_found) break;                // uniform: fewer than AL_T seeds (or nothing but NaN left)
+  }
+  if (tid == 0) ticket_reset(a.ticket);
+}
+
+// ---------------------------------------------------------------------------------------
+// align_refine: stage 2, one workgroup per survivor
+// ---------------------------------------------------------------------------------------
+// LDS of align_refine in bytes: three diagonals of H, then what the superposition (2 x 3L floats, L flags) and the dynamic
+// programme (the structure's 3 max_L floats, three diagonals of the flag) use in turn, then three pair lists of L (i, j).
+struct AlignLds { int un, lists, total; };
+__host__ __device__ inline AlignLds align_lds(int L, int max_L) {
+  const int h = 3 * (L + 1) * 8;
+  const int sup = 24 * L + L, dp = 12 * max_L + 3 * (L + 1);
+  const int un = ((sup > dp ? sup : dp) + 7) / 8 * 8;
+  return {h, h + un, h + un + 3 * 2 * L * 2};
+}
+
+// n packed pairs from a list into pm2 / qn2, the flags set: the start of a superposition
+__device__ inline void align_pack(const AlignArgs& a, const unsigned short* li, const unsigned short* lj, int K, float* pm2,
+                                  float* qn2, unsigned char* fl) {
+  for (int t = threadIdx.x; t < K; t += SC_THREADS) {
+    const int i = li[t], j = lj[t];
+    for (int c = 0; c < 3; ++c) { pm2[3 * t + c] = a.pm[3 * i + c]; qn2[3 * t + c] = a.qs[3 * j + c]; }
+    fl[t] = 1;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
+  extern __shared__ double smd[];
+  __shared__ double wred[SC_WAVES][16];
+  __shared__ double bc[12];
+  __shared__ int sh_flag, sh_K, sh_off, sh_diff, sh_last, sh_win;
+  const int tid = threadIdx.x, L = a.L;
+  if (a.hdr[AH_VALID] == 0.0) return;
+  const int nsurv = a.surv[0];
+  if ((int)blockIdx.x >= nsurv) return;                      // (no survivor at all: the out slots stay NaN)
+  const int n = (int)a.hdr[AH_N], m = (int)a.hdr[AH_M], minov = (int)a.hdr[AH_MINOV];
+  const double lmin = a.hdr[AH_LMIN], d0s = a.hdr[AH_D0S], d_cut = a.hdr[AH_DCUT];
+  const AlignLds lds = align_lds(L, a.max_L);
+  unsigned char* base = reinterpret_cast<unsigned char*>(smd);
+  double* Hb = smd;                                          // [3][L + 1]
+  float* pm2 = reinterpret_cast<float*>(base + lds.un);      // superposition: [K][3], [K][3], [K]
+  float* qn2 = pm2 + 3 * L;
+  unsigned char* fl = reinterpret_cast<unsigned char*>(qn2 + 3 * L);
+  float* qs = reinterpret_cast<float*>(base + lds.un);       // dynamic programme: [m][3], [3][L + 1]
+  unsigned char* Db = reinterpret_cast<unsigned char*>(qs + 3 * a.max_L);
+  unsigned short* lst = reinterpret_cast<unsigned short*>(base + lds.lists);
+  unsigned short *ci = lst, *cj = lst + L, *ni = lst + 2 * L, *nj = lst + 3 * L, *bi = lst + 4 * L, *bj = lst + 5 * L;
+  unsigned char* dirp = a.dir + (size_t)blockIdx.x * (size_t)(a.max_L + 1) * (size_t)(a.max_L + 1);
+  const int seed = a.surv[1 + blockIdx.x];
+
+  int K, coff = 0, bK = 0;                                   // the alignment in hand: K pairs from ci / cj [coff]
+  {
+    int k, i0;
+    align_seed(seed, n, m, minov, k, i0, K);
+    for (int t = tid; t < K; t += SC_THREADS) { ci[t] = (unsigned short)(i0 + t); cj[t] = (unsigned short)(i0 + k + t); }
+  }
+  __syncthreads();
+  double best_tm = -1.0;                                     // thread 0
+
+  for (int round = 0; round < AL_ROUNDS; ++round) {
+    align_pack(a, ci + coff, cj + coff, K, pm2, qn2, fl);
+    SeedBest sb;
+    score_seed_loop(pm2, qn2, fl, K, lmin, d0s, d_cut, wred, bc, sb);
+    if (tid == 0) {
+      sh_flag = sb.tm > best_tm ? 1 : 0;
+      if (sh_flag) best_tm = sb.tm;
+      for (int c = 0; c < 9; ++c) bc[c] = sb.R[c];
+      for (int c = 0; c < 3; ++c) bc[9 + c] = sb.t[c];
+    }
+    __syncthreads();
+    if (sh_flag) {
+      for (int t = tid; t < K; t += SC_THREADS) { bi[t] = ci[coff + t]; bj[t] = cj[coff + t]; }
+      bK = K;
+    }
+    if (round == AL_ROUNDS - 1) break;                       // the alignment a further DP gave would never be scored
+    double R[9], tr[3];
+    for (int c = 0; c < 9; ++c) R[c] = bc[c];
+    for (int c = 0; c < 3; ++c) tr[c] = bc[9 + c];
+
+    // the dynamic programme: cell (i, j), 1 <= i <= n, 1 <= j <= m, lies on diagonal d = i + j at index i
+    for (int i = tid; i < 3 * m; i += SC_THREADS) qs[i] = a.qs[i];
+    double rp[AL_SLICE][3];
+#pragma unroll
+    for (int kk = 0; kk < AL_SLICE; ++kk) {
+      const int i = tid + SC_THREADS * kk;
+      rp[kk][0] = rp[kk][1] = rp[kk][2] = 0.0;
+      if (i >= 1 && i <= n) {
+        const double px = a.pm[3 * (i - 1)], py = a.pm[3 * (i - 1) + 1], pz = a.pm[3 * (i - 1) + 2];
+        rp[kk][0] = ((R[0] * px + R[1] * py) + R[2] * pz) + tr[0];
+        rp[kk][1] = ((R[3] * px + R[4] * py) + R[5] * pz) + tr[1];
+        rp[kk][2] = ((R[6] * px + R[7] * py) + R[8] * pz) + tr[2];
+      }
+    }
+    __syncthreads();
+    const double d0sq = d0s * d0s;
+    const int W = L + 1;
+    for (int d = 0; d <= n + m; ++d) {
+      double* Hc = Hb + (d % 3) * W;
+      const double* H1 = Hb + ((d + 2) % 3) * W;             // diagonal d - 1
+      const double* H2 = Hb + ((d + 1) % 3) * W;             // diagonal d - 2
+      unsigned char* Dc = Db + (d % 3) * W;
+      const unsigned char* D1 = Db + ((d + 2) % 3) * W;
+      unsigned char* drow = dirp + (size_t)(d % (m + 1)) * (size_t)(n + 1);
+#pragma unroll
+      for (int kk = 0; kk < AL_SLICE; ++kk) {
+        const int i = tid + SC_THREADS * kk, j = d - i;
+        if (i <= n && j >= 0 && j <= m) {
+          if (i == 0 || j == 0) {
+            Hc[i] = 0.0;
+            Dc[i] = 0;
+          } else {
+            const double ex = rp[kk][0] - (double)qs[3 * (j - 1)], ey = rp[kk][1] - (double)qs[3 * (j - 1) + 1],
+                         ez = rp[kk][2] - (double)qs[3 * (j - 1) + 2];
+            const double dd = (ex * ex + ey * ey) + ez * ez;
+            const double s = 1.0 / (1.0 + dd / d0sq);
+            const double ca = H2[i - 1] + s;
+            const double cb = H1[i - 1] + (D1[i - 1] ? AL_GAP : 0.0);      // up: (i - 1, j)
+            const double cc = H1[i] + (D1[i] ? AL_GAP : 0.0);              // left: (i, j - 1)
+            const double bcm = cb > cc ? cb : cc;
+            const unsigned char dr = ca >= bcm ? 0 : (cb >= cc ? 1 : 2);
+            Hc[i] = dr == 0 ? ca : (dr == 1 ? cb : cc);
+            Dc[i] = dr == 0 ? 1 : 0;
+            drow[i] = dr;
+          }
+        }
+      }
+      __syncthreads();
+    }
+    // the traceback: serial, at most n + m steps; the pairs arrive last first and fill the new list from its end
+    if (tid == 0) {
+      int i = n, j = m, pos = L;
+      for (int step = 0; step < n + m && i > 0 && j > 0; ++step) {
+        const unsigned char dr = dirp[(size_t)((i + j) % (m + 1)) * (size_t)(n + 1) + i];
+        if (dr == 0) {
+          if (pos > 0) { --pos; ni[pos] = (unsigned short)(i - 1); nj[pos] = (unsigned short)(j - 1); }
+          --i; --j;
+        } else if (dr == 1) --i;
+        else --j;
+      }
+      sh_off = pos;
+      sh_K = L - pos;
+      sh_diff = 0;
+    }
+    __syncthreads();
+    const int nK = sh_K, noff = sh_off;
+    if (nK == K)
+      for (int t = tid; t < K; t += SC_THREADS)
+        if (ni[noff + t] != ci[coff + t] || nj[noff + t] != cj[coff + t]) sh_diff = 1;
+    __syncthreads();
+    if ((nK == K && !sh_diff) || nK < 3) break;              // uniform: A' = A, or too few pairs to superpose
+    unsigned short* sw = ci; ci = ni; ni = sw;
+    sw = cj; cj = nj; nj = sw;
+    K = nK;
+    coff = noff;
+    __syncthreads();                                         // (sh_diff is read above, written by thread 0 next round)
+  }
+  __syncthreads();
+
+  // this survivor's record: best tm, its alignment
+  int* rec = a.bali + (size_t)blockIdx.x * (size_t)(1 + 2 * a.max_L);
+  for (int t = tid; t < bK; t += SC_THREADS) { agent_store_i32(rec + 1 + 2 * t, (int)bi[t]); agent_store_i32(rec + 2 + 2 * t, (int)bj[t]); }
+  __syncthreads();
+  if (tid == 0) {
+    agent_store_i32(rec, bK);
+    agent_store_f64(a.btm + blockIdx.x, best_tm);
+    sh_last = ticket_take_last(a.ticket + 1, (unsigned)nsurv) ? 1 : 0;
+    if (sh_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  }
+  __syncthreads();
+  if (!sh_last) return;
+
+  // the last arriver: the winner (largest tm; ties: the lower seed number), the final superpositions, the outputs
+  if (tid == 0) {
+    double top = -__builtin_inf();
+    int win = -1, win_seed = 0x7fffffff;
+    for (int w = 0; w < nsurv; ++w) {
+      const double tm = agent_load_f64(a.btm + w);
+      const int sd = a.surv[1 + w];
+      if (tm > top || (tm == top && sd < win_seed)) { top = tm; win = w; win_seed = sd; }
+    }
+    if (win >= 0 && agent_load_i32(a.bali + (size_t)win * (size_t)(1 + 2 * a.max_L)) < 3) win = -1;
+    sh_win = win;
+    ticket_reset(a.ticket + 1);
+  }
+  __syncthreads();
+  const int win = sh_win;
+  if (win < 0) return;                                       // nothing but NaN: the out slots stay NaN
+  int* wrec = a.bali + (size_t)win * (size_t)(1 + 2 * a.max_L);
+  int wK = agent_load_i32(wrec);
+  if (wK > L) wK = L;                                        // never
+  for (int t = tid; t < wK; t += SC_THREADS) {
+    ci[t] = (unsigned short)agent_load_i32(wrec + 1 + 2 * t);
+    cj[t] = (unsigned short)agent_load_i32(wrec + 2 + 2 * t);
+  }
+  __syncthreads();
+  const double d0n = score_d0((double)n), d0m = score_d0((double)m);
+  align_pack(a, ci, cj, wK, pm2, qn2, fl);
+  SeedBest bn;
+  score_seed_loop(pm2, qn2, fl, wK, (double)n, d0n, d_cut, wred, bc, bn);
+  __syncthreads();
+  for (int t = tid; t < wK; t += SC_THREADS) fl[t] = 1;
+  __syncthreads();
+  SeedBest bm;
+  score_seed_loop(pm2, qn2, fl, wK, (double)m, d0m, d_cut, wred, bc, bm);
+  const AlignLayout lay = align_layout(L);
+  if (tid == 0) {
+    float* out = a.blk;
+    int k, i0, ov;
+    align_seed(a.surv[1 + win], n, m, minov, k, i0, ov);
+    out[1] = (float)wK;
+    out[2] = (float)bn.rmsd;
+    out[3] = (float)bn.tm;
+    out[4] = (float)bm.tm;
+    for (int c = 0; c < 9; ++c) { out[5 + c] = (float)bm.R[c]; bc[c] = bm.R[c]; }
+    for (int c = 0; c < 3; ++c) { out[14 + c] = (float)bm.t[c]; bc[9 + c] = bm.t[c]; }
+    out[17] = (float)d0n;
+    out[18] = (float)d0m;
+    out[19] = (float)k;
+    out[20] = (float)a.hdr[AH_SEEDS];
+    for (int c = 21; c < ALIGN_HEADER + 1; ++c) out[c] = 0.f;
+  }
+  for (int i = tid; i < L; i += SC_THREADS) a.blk[lay.ali + i] = -1.f;      // (the deviations of these rows stay NaN)
+  __syncthreads();
+  double R[9], tr[3];
+  for (int c = 0; c < 9; ++c) R[c] = bc[c];
+  for (int c = 0; c < 3; ++c) tr[c] = bc[9 + c];
+  for (int t = tid; t < wK; t += SC_THREADS) {
+    const int i = ci[t];
+    a.blk[lay.ali + i] = (float)cj[t];
+    a.blk[lay.deviation + i] = (float)score_dev(R, tr, pm2 + 3 * t, qn2 + 3 * t);
+  }
+}
+
+int align_kernel_attrs(dmp_ctx* c) {
+  static_assert(AL_SLICE * SC_THREADS >= DMP_MAX_L + 1, "a thread's slice of a diagonal");
+  static bool done[64] = {};
+  if (c->device >= 0 && c->device < 64 && done[c->device]) return DMP_OK;
+  DMP_HIP(hipFuncSetAttribute((const void*)align_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              align_lds(DMP_MAX_L, DMP_MAX_L).total));
+  if (c->device >= 0 && c->device < 64) done[c->device] = true;
+  return DMP_OK;
+}
+
+int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
+  AlignArgs a{};
+  a.coords = d_coords;
+  a.blk = d_block;
+  a.L = L;
+  a.max_L = c->max_L;
+  a.pm = c->align_pm;
+  a.qs = c->align_qs;
+  a.hdr = c->align_hdr;
+  a.rec = c->align_rec;
+  a.surv = c->align_surv;
+  a.btm = c->align_btm;
+  a.bali = c->align_bali;
+  a.dir = c->align_dir;
+  a.ticket = c->align_ticket;
+  hipLaunchKernelGGL(align_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a);
+  DMP_LAUNCH_CHECK();
+  // a seed's overlap has at most L rows: 6L floats + L flags of LDS, 50 KB at L = 2048
+  hipLaunchKernelGGL(align_thread_kernel, dim3(L + c->max_L + 1), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
+  DMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(align_refine_kernel, dim3(AL_T), dim3(SC_THREADS), align_lds(L, c->max_L).total, s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+}  // namespace dmp

@@ -407,7 +407,8 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // the fault bits are latched into the word dmp_sync_faults reports.
 // `lay`: the d_conf buffer of this prediction (common.h) - the confidences and, with option "emit_distmap", the whole extension
 // become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
-// caller's and stay.
+// caller's and stay.  The same for the align block of option "align_structure": its out slots become NaN, m in front of them and
+// the structure's trace behind them (past lay.total) stay.
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
                                    float* __restrict__ conf, int L, ConfLayout lay, int* __restrict__ report) {
   const int f = words[0];
@@ -415,7 +416,7 @@ __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const float nan = __builtin_nanf("");
   if (i < 15 * L) coords[i] = nan;
-  if (i < lay.score_off || (i >= lay.score_out && i < lay.total)) conf[i] = nan;
+  if (i < lay.score_off || (i >= lay.score_out && i < lay.align_off) || (i >= lay.align_out && i < lay.total)) conf[i] = nan;
   if (i == 0) {
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
@@ -527,18 +528,29 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(score_rec, 6 * L * SCORE_REC);
   A_(score_tot, 2);
   A_(score_ticket, 1);
+  A_(align_pm, 3 * L);
+  A_(align_qs, 3 * L);
+  A_(align_hdr, 8);
+  A_(align_rec, 2 * L + 1);
+  A_(align_surv, 1 + ALIGN_SURVIVORS);
+  A_(align_btm, ALIGN_SURVIVORS);
+  A_(align_bali, ALIGN_SURVIVORS * (1 + 2 * L));
+  A_(align_dir, ALIGN_SURVIVORS * (L + 1) * (L + 1));
+  A_(align_ticket, 2);
 #undef A_
   if (rc) { dmp_ctx_destroy(c); return rc; }
   if (hipMemset(c->seq_abort, 0, 2 * sizeof(int)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->delta_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->rms_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->score_ticket, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  if (hipMemset(c->align_ticket, 0, 2 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   // the word recycle_delta tells the host its stop decision through (read only after the pass tail's event)
   if (hipHostMalloc((void**)&c->delta_host, sizeof(int), hipHostMallocMapped) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   *c->delta_host = 0;
   if ((rc = trunk_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
   if ((rc = mds_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
   if ((rc = gj_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
+  if ((rc = align_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
   if ((rc = vgru_kernel_attrs(c))) { dmp_ctx_destroy(c); return rc; }
   for (int i = 0; i < 2; ++i) {
     hipEvent_t e;
@@ -607,6 +619,11 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->opt.score = value;
     return DMP_OK;
   }
+  if (k == "align_structure") {      // takes effect with the next prediction begun
+    DMP_ARG(value == 0 || value == 1, "align_structure must be 0 or 1, got %d", value);
+    ctx->opt.align = value;
+    return DMP_OK;
+  }
   DMP_ARG(k != "passes_run", "passes_run is read only");
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -650,6 +667,7 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "recycle_tol_mA") { *h_value = ctx->opt.tol_mA; return DMP_OK; }
   if (k == "emit_distmap") { *h_value = ctx->opt.emit; return DMP_OK; }
   if (k == "score_native") { *h_value = ctx->opt.score; return DMP_OK; }
+  if (k == "align_structure") { *h_value = ctx->opt.align; return DMP_OK; }
   if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -1411,11 +1429,13 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // (tools/isa_lint.py).
   rc = ca_to_backbone(c->best_ca, c->best_conf, L, d_coords, d_conf, s);
   if (rc) return rc;
-  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score);
+  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align);
   // option "emit_distmap": the map and {best_pass, passes_run, map_rms} behind the confidences
   if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map_off, d_conf + lay.info_off, s))) return rc;
   // option "score_native": the score block behind that, the native trace and lnorm in it (score.hip)
   if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score_off, s))) return rc;
+  // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
+  if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align_off, s))) return rc;
   hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, lay.total), 256)), dim3(256), 0, s,
                      c->seq_abort, d_coords, d_conf, L, lay, c->end_fault_out);
   DMP_LAUNCH_CHECK();

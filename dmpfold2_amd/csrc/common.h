@@ -63,10 +63,18 @@ __host__ __device__ inline ScoreLayout score_layout(int L) {
   const int hdr = 3 * L, res = hdr + SCORE_HEADER;
   return {hdr, hdr + 1, res, res + L, res + 2 * L};
 }
-struct ConfLayout { int64_t map_off, info_off, score_off, score_out, total; };   // score_off: the end of what "emit_distmap" gives
-__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score) {
+//   | with "align_structure": the align block = [0] m (in) | ALIGN_HEADER floats | ali [L] | deviation [L] | the structure's
+//   trace [3m] (in): every out slot at an offset that does not depend on m.
+constexpr int ALIGN_HEADER = 24;
+struct AlignLayout { int ali, deviation, in; };                         // in: the first float of the structure's trace
+__host__ __device__ inline AlignLayout align_layout(int L) { return {1 + ALIGN_HEADER, 1 + ALIGN_HEADER + L, 1 + ALIGN_HEADER + 2 * L}; }
+// score_off: the end of what "emit_distmap" gives; align_off: the end of the score block; align_out / total: the align
+// block's out slots (total does not count its trailing input, whose length only the caller knows)
+struct ConfLayout { int64_t map_off, info_off, score_off, score_out, align_off, align_out, total; };
+__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0) {
   const int64_t info_off = L + (emit ? (int64_t)L * L : 0), score_off = info_off + (emit ? 3 : 0);
-  return {L, info_off, score_off, score_off + score_layout(L).out, score_off + (score ? score_layout(L).total : 0)};
+  const int64_t align_off = score_off + (score ? score_layout(L).total : 0);
+  return {L, info_off, score_off, score_off + score_layout(L).out, align_off, align_off + 1, align_off + (align ? align_layout(L).in : 0)};
 }
 
 // padded activation geometry: interior [2, 2+L) in both axes, zero elsewhere
@@ -142,7 +150,7 @@ struct dmp_lane {
   long long count = 0;     // conv launches recorded so far (event of launch i: ev[i % RING])
 };
 
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0; };   // options "recycle_tol_mA", "emit_distmap", "score_native"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0; };   // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure"
 
 struct dmp_ctx {
   int device = 0;
@@ -280,6 +288,17 @@ struct dmp_ctx {
   double* score_rec = nullptr;     // [6 max_L][SCORE_REC] one record per seed of the superposition search
   unsigned long long* score_tot = nullptr;   // [2] lDDT: preserved, pairs
   unsigned* score_ticket = nullptr;          // zero between launches
+  // option "align_structure": the model aligned with a structure of any length in the d_conf buffer (align.hip); allocated
+  // with the context
+  float* align_pm = nullptr;       // [max_L][3] model trace
+  float* align_qs = nullptr;       // [max_L][3] the structure's trace
+  double* align_hdr = nullptr;     // [8] valid, n, m, lmin, minov, seeds, d0s, d_cut
+  double* align_rec = nullptr;     // [2 max_L + 1] tm of every gapless threading
+  int* align_surv = nullptr;       // [1 + ALIGN_SURVIVORS] how many seeds go on, which
+  double* align_btm = nullptr;     // [ALIGN_SURVIVORS] best tm of a refined seed ...
+  int* align_bali = nullptr;       // [ALIGN_SURVIVORS][1 + 2 max_L] ... and its alignment
+  unsigned char* align_dir = nullptr;        // [ALIGN_SURVIVORS][(max_L + 1)^2] DP directions, one byte per cell
+  unsigned* align_ticket = nullptr;          // [2] zero between launches
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -556,6 +575,9 @@ int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
 int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_map, float* d_info, hipStream_t s);
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
+constexpr int ALIGN_SURVIVORS = 16; // seeds of the gapless threading that the dynamic programme refines (align.hip)
+int align_kernel_attrs(dmp_ctx* c);   // once per device, at context creation
+int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);

@@ -20,7 +20,9 @@ Differences from the reference, all additive or forced by the environment:
   * `distmap` / `return_distmap` / `dmpfold --distmap FILE`: the predicted C-alpha distance map of the pass the best-of
     rule chose (option "emit_distmap" of include/dmpfold_hip.h) comes back with the structure;
   * `native` / `return_scores` / `dmpfold --native PDB`: the model is scored against a native structure on the GPU
-    (option "score_native": TM-score, GDT, RMSD, lDDT-C-alpha; dmpfold2_amd/score.py has the host side).
+    (option "score_native": TM-score, GDT, RMSD, lDDT-C-alpha; dmpfold2_amd/score.py has the host side);
+  * `compare` / `return_alignment` / `dmpfold --compare PDB`: the model is aligned on the GPU with a structure of any length
+    and sequence (option "align_structure": a structural alignment, both TM-scores, the superposition).
 """
 from __future__ import annotations
 
@@ -227,11 +229,13 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-def _stage(device, L, template_ca, native, emit, score, emit_alloc=None):
+def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=False, structure=None):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is sized for the options as the context holds them - the library cannot check
     it, writes L + L*L + 3 floats with "emit_distmap" on (`emit_alloc`: sized as if it were) and reads and writes 5L + 24
-    more behind them with "score_native" on: the native trace goes there (no `native` = no row present: n_pairs 0, NaN scores)."""
+    more behind them with "score_native" on: the native trace goes there (no `native` = no row present: n_pairs 0, NaN scores);
+    with "align_structure" on (`align`) 25 + 2L + 3m more behind those, m and the rows of `structure` in them (no `structure`:
+    m = 0, which the library answers with NaN)."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -239,8 +243,15 @@ def _stage(device, L, template_ca, native, emit, score, emit_alloc=None):
             raise RuntimeError(f"Sizes of tensors must match: template has {d_tpl.shape[0]} CA atoms, "
                                f"alignment has {L} columns")
     coords = torch.empty((L, 5, 3), dtype=torch.float32, device=device)
-    buf = torch.empty((_score.conf_floats(L, emit if emit_alloc is None else emit_alloc, score),), dtype=torch.float32, device=device)
-    out = split_conf_buffer(buf, L, emit, score, coords)
+    ablock = None
+    if align:
+        ablock = _score.pack_structure(structure, L) if structure is not None else _score.empty_structure(L)
+    align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
+    alloc = emit if emit_alloc is None else emit_alloc
+    buf = torch.empty((_score.conf_floats(L, alloc, score, align_m),), dtype=torch.float32, device=device)
+    out = split_conf_buffer(buf, L, emit, score, coords, align_m)
+    if align:
+        out.align_block.copy_(torch.from_numpy(ablock))
     if score:
         block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
         out.score_block.copy_(torch.from_numpy(block))
@@ -263,6 +274,7 @@ class Engine:
         self.weights_tag = None
         self.last_fallback = False     # the last predict_*_checked call fell back to conv_mode 2
         self._score = None             # (score block, L) of the last prediction
+        self._align = None             # (align block, L) of the last prediction
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
@@ -311,8 +323,11 @@ class Engine:
         self.weights_tag = other.weights_tag
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
-                minsteps=default_minsteps, converge=None, distmap=False, native=None):
+                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `structure` (an (m, 3) array, the C-alpha trace of a structure of any length, 3 <= m <= max_L): the final trace is
+        aligned with it on the GPU (option "align_structure", set for this call only); what the call returns does not
+        change, the result is in `alignment`.
         `native` (an (L, 3) array, one native C-alpha per alignment column, NaN rows where there is none, or a tuple
         (array, lnorm); score.native_rows makes one from a structure): the model is scored against it on the GPU (option
         "score_native", set for this call only); what the call returns does not change, the scores are in `scores`.
@@ -329,7 +344,22 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native)
+        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure)
+
+    @property
+    def alignment(self):
+        """The structural alignment of the last prediction as score.unpack_alignment gives it, None if it ran without option
+        "align_structure".  Synchronises with the GPU."""
+        if self._align is None:
+            return None
+        block, L = self._align
+        torch.cuda.synchronize(self.device)
+        return _score.unpack_alignment(block, L)
+
+    @property
+    def align_block(self):
+        """The last prediction's align block on the GPU (25 + 2L + 3m floats, a view of the buffer handed to the library), or None."""
+        return None if self._align is None else self._align[0]
 
     @property
     def scores(self):
@@ -352,20 +382,24 @@ class Engine:
         return self.get_option("passes_run")
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
-                       minsteps=default_minsteps, converge=None, distmap=False, native=None):
+                       minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        with self._call_options(converge, distmap, native):
-            return self._run(d_msa, template_ca, iterations, minsteps, native).public(distmap, score=False)
+        with self._call_options(converge, distmap, native, structure):
+            return self._run(d_msa, template_ca, iterations, minsteps, native, structure).public(distmap, score=False, align=False)
 
     @contextlib.contextmanager
-    def _call_options(self, converge, distmap, native):
+    def _call_options(self, converge, distmap, native, structure=None):
         """The options one call asks for - read when the prediction begins - set for its duration, then as they were.
-        `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" set by hand stay set."""
+        `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" / "align_structure" set by hand
+        stay set."""
         want = {} if converge is None else {"recycle_tol_mA": converge_to_mA(converge)}    # (raises before anything changes)
         if distmap and not self.get_option("emit_distmap"):
             want["emit_distmap"] = 1
         if native is not None and not self.get_option("score_native"):
             want["score_native"] = 1
+        if structure is not None and not self.get_option("align_structure"):
+            _score.as_structure(structure)                                                 # (a bad shape raises before anything changes)
+            want["align_structure"] = 1
         before = {}
         try:
             for name, value in want.items():
@@ -376,19 +410,24 @@ class Engine:
             for name, value in before.items():
                 self.set_option(name, value)
 
-    def _run(self, d_msa, template_ca, iterations, minsteps, native):
+    def _run(self, d_msa, template_ca, iterations, minsteps, native, structure=None):
         """One prediction with the options as the context holds them -> Outputs."""
         emit, score = bool(self.get_option("emit_distmap")), bool(self.get_option("score_native"))
+        align = bool(self.get_option("align_structure"))
+        if align and structure is not None and _score.as_structure(structure).shape[0] > self.max_L:
+            raise RuntimeError(f"structure has {len(structure)} rows; the engine's capacity is {self.max_L} (max_L)")
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         with torch.cuda.device(self.device):
-            self._score = None
-            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score)
+            self._score = self._align = None
+            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, align=align, structure=structure)
             if score:
                 self._score = (out.score_block, L)
+            if align:
+                self._align = (out.align_block, L)
             if self._stream is not None:
                 # an engine with its own stream: order it after the producer of the inputs and tell the
                 # caching allocator that these blocks are in use there
@@ -429,7 +468,7 @@ class Engine:
         raise_for_faults(self.sync_faults())
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
-                        minsteps=default_minsteps, converge=None, distmap=False, native=None):
+                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
@@ -437,18 +476,20 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native)
+        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
-                               minsteps=default_minsteps, converge=None, distmap=False, native=None):
-        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`: see `predict`; a repeat of
-        the prediction returns the repeat's map and scores)."""
-        return self._checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native).public(distmap, score=False)
+                               minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
+        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`: see `predict`; a
+        repeat of the prediction returns the repeat's map, scores and alignment)."""
+        return self._checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native,
+                             structure).public(distmap, score=False, align=False)
 
-    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native):
-        """`predict_device_checked` -> Outputs; the repeats run with the call's options still set."""
-        with self._call_options(converge, distmap, native):
-            out = self._run(d_msa, template_ca, iterations, minsteps, native)
+    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure=None):
+        """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry `native` and
+        `structure` along."""
+        with self._call_options(converge, distmap, native, structure):
+            out = self._run(d_msa, template_ca, iterations, minsteps, native, structure)
             bits = self.sync_faults()
             self.last_fallback = False
             if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
@@ -457,7 +498,7 @@ class Engine:
                 print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
                       "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
                 self.set_option("vgru_persistent", 0)
-                out = self._run(d_msa, template_ca, iterations, minsteps, native)
+                out = self._run(d_msa, template_ca, iterations, minsteps, native, structure)
                 bits = self.sync_faults()
             if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
                 print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
@@ -466,7 +507,7 @@ class Engine:
                 self.last_fallback = True
                 self.set_option("conv_mode", 2)
                 try:
-                    out = self._run(d_msa, template_ca, iterations, minsteps, native)
+                    out = self._run(d_msa, template_ca, iterations, minsteps, native, structure)
                     bits = self.sync_faults()
                 finally:
                     self.set_option("conv_mode", 0)
@@ -493,6 +534,7 @@ class _PipelineEngine(Engine):
         self.weights_tag = None
         self.last_fallback = False
         self._score = None
+        self._align = None
 
     def close(self):
         self._ctx = C.c_void_p()
@@ -502,8 +544,9 @@ class _PipelineEngine(Engine):
 
 
 # A target in a `Pipeline`: what stays alive until its result is handed out and what a repeat needs.  `out`: its Outputs,
-# `ready`: the event behind the producer of its inputs, `native`: as given to `submit`, None if the target is not scored.
-_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready native")
+# `ready`: the event behind the producer of its inputs, `native`: as given to `submit`, None if the target is not scored,
+# `structure`: as given to `submit`, None if the target is not aligned.
+_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready native structure", defaults=(None,))
 
 
 # ticket states of the C pipeline (include/dmpfold_hip.h, DMP_TICKET_*)
@@ -521,7 +564,7 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False, score=False):
+                 distmap=False, score=False, align=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -529,7 +572,9 @@ class Pipeline:
         `distmap`: every target also returns its chosen pass's distance map and [best_pass, passes_run, map_rms]
         (`set_distmap`): `result`, `peek`, `collect` and `run` then give (coords, confs, distmap, info) per target.
         `score`: every target is scored against the native trace given to `submit` (`set_score`); its score block (5L + 24
-        floats, score.unpack_scores) is then the last element of what those calls give per target."""
+        floats, score.unpack_scores) is then the last element of what those calls give per target.
+        `align`: every target is aligned with the `structure` given to `submit` (`set_align`); its align block (25 + 2L + 3m
+        floats, score.unpack_alignment) is then the last element of what those calls give per target, behind the score block."""
         self.lib = _lib.load()
         self.device = _resolve_device(device)
         S = max(1, int(streams))
@@ -556,6 +601,8 @@ class Pipeline:
             self.set_distmap(True)
         if score:
             self.set_score(True)
+        if align:
+            self.set_align(True)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -577,6 +624,11 @@ class Pipeline:
         `submit` (none given: no row present, n_pairs 0); idle pipeline only."""
         self.set_option("score_native", 1 if on else 0)
 
+    def set_align(self, on):
+        """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
+        `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
+        self.set_option("align_structure", 1 if on else 0)
+
     def close(self):
         if self._p:
             self.lib.dmp_pipeline_destroy(self._p)           # joins the scheduler thread, synchronises the streams
@@ -593,9 +645,11 @@ class Pipeline:
             pass
 
     # ---- submission --------------------------------------------------------------------------
-    def submit(self, d_msa, iterations=default_iterations, minsteps=default_minsteps, template_ca=None, native=None):
+    def submit(self, d_msa, iterations=default_iterations, minsteps=default_minsteps, template_ca=None, native=None,
+               structure=None):
         """Queue one target (uint8 (N, L) tensor on the GPU, optional template CA trace (L, 3));
-        returns a ticket for `result`.  `native`: the trace to score against (Engine.predict), read only with `set_score` on."""
+        returns a ticket for `result`.  `native`: the trace to score against (Engine.predict), read only with `set_score` on.
+        `structure`: the (m, 3) trace to align the model with, read only with `set_align` on."""
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
@@ -613,8 +667,17 @@ class Pipeline:
             if any(sflags) and not (score and emit == any(flags)):
                 raise RuntimeError("score_native: the engines of a pipeline must agree on \"score_native\" and \"emit_distmap\" "
                                    "(the score block's place in the buffer depends on both); use set_score / set_distmap")
-            # (the native block is written on the current stream: `ready` below is behind it)
-            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, emit_alloc=any(flags))
+            aflags = [bool(e.get_option("align_structure")) for e in self.engines]
+            align = all(aflags)
+            if any(aflags) and not (align and emit == any(flags) and score == any(sflags)):
+                raise RuntimeError("align_structure: the engines of a pipeline must agree on \"align_structure\", \"score_native\" "
+                                   "and \"emit_distmap\" (the align block's place in the buffer depends on all three); use "
+                                   "set_align / set_score / set_distmap")
+            if align and structure is not None and _score.as_structure(structure).shape[0] > self.engines[0].max_L:
+                raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {self.engines[0].max_L}")
+            # (the native and align blocks are written on the current stream: `ready` below is behind it)
+            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, emit_alloc=any(flags), align=align,
+                                structure=structure)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -629,7 +692,8 @@ class Pipeline:
             self._p, d_msa.data_ptr(), n, L, d_tpl.data_ptr() if d_tpl is not None else None,
             int(max(iterations, 0)), int(max(minsteps, 0)), out.coords.data_ptr(), out.confs.data_ptr(),
             C.c_void_p(ready.cuda_event)))
-        self._jobs[t] = _Job(d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, out, ready, native if score else None)
+        self._jobs[t] = _Job(d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, out, ready, native if score else None,
+                             structure if align else None)
         self._reap()
         return t
 
@@ -757,8 +821,11 @@ class Pipeline:
                     emit, nat = res.distmap is not None, job.native
                     if res.score_block is not None and nat is None:
                         nat = np.full((job.d_msa.shape[1], 3), np.nan, dtype=np.float32)
+                    strc = job.structure
+                    if res.align_block is not None and strc is None:
+                        strc = np.zeros((0, 3), dtype=np.float32)
                     try:
-                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat)
+                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat, strc)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
@@ -869,7 +936,8 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 # ---------------------------------------------------------------------------
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
-                  return_distmap=False, native=None, return_scores=False, native_chain=None):
+                  return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
+                  compare_chain=None, return_alignment=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -878,7 +946,10 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     as the last element of the returned tuple (after `alnmat` when that is requested too).
     `native` (addition): a PDB file (its chain `native_chain`, default the first, is aligned with the query sequence:
     score.native_from_pdb) or an array as Engine.predict takes it; the model is scored against it on the GPU.  With
-    `return_scores` the dict of score.unpack_scores is appended behind everything else (None without a `native`)."""
+    `return_scores` the dict of score.unpack_scores is appended behind everything else (None without a `native`).
+    `compare` (addition): a PDB file (its chain `compare_chain`, default the first) or an (m, 3) C-alpha trace of a structure of
+    any length and sequence; the model is aligned with it on the GPU (option "align_structure").  With `return_alignment`
+    the dict of score.unpack_alignment is appended last of all, behind the scores (None without a `compare`)."""
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -887,16 +958,28 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     nseqs, length = alnmat.shape
     if isinstance(native, (str, os.PathLike)):
         native = _score.native_from_pdb(aln[0], native, native_chain)
-    scores = None
+    if isinstance(compare, (str, os.PathLike)):
+        path = compare
+        compare = _score.read_native_ca(path, compare_chain)[0]
+        if compare.shape[0] == 0:
+            raise ValueError(f"{path}: no C-alpha atoms" + (f" in chain {compare_chain}" if compare_chain else ""))
+    if compare is not None:
+        compare = _score.as_structure(compare)
+        if not 3 <= compare.shape[0] <= MAX_L:
+            raise ValueError(f"compare: the structure has {compare.shape[0]} C-alpha atoms; 3 to {MAX_L} can be aligned")
+    scores = alignment = None
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
-        eng = get_engine(dev, length, nseqs, weights_file=weights_file)
+        # (the engine holds both traces: its capacity covers the structure to align with, too)
+        eng = get_engine(dev, length if compare is None else max(length, compare.shape[0]), nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap),
-                                  native=native)
+                                  native=native, structure=compare)
         if native is not None and return_scores:
             scores = eng.scores
+        if compare is not None and return_alignment:
+            alignment = eng.alignment
     coords, confs = out[0], out[1]
     ret = (coords, confs) + ((alnmat,) if return_alnmat else ()) + ((out[2],) if return_distmap else ())
-    return ret + ((scores,) if return_scores else ())
+    return ret + ((scores,) if return_scores else ()) + ((alignment,) if return_alignment else ())
 
 
 def pdb_text(coords, confs, alnmat):
@@ -920,7 +1003,7 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208), -c / --converge, --distmap and --native."""
+    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native and --compare."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -948,6 +1031,14 @@ def dmpfold_parser():
                         help="chain of --native (default: its first)")
     parser.add_argument("--scores", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --native to FILE instead of standard error")
+    parser.add_argument("--compare", type=str, default=None, required=False, metavar="PDB",
+                        help="align the model on the GPU with this structure of any length and sequence (structural alignment, "
+                             "TM-scores by both lengths, superposition); the result goes to standard error as one JSON line, the "
+                             "model on standard output is unchanged")
+    parser.add_argument("--compare-chain", type=str, default=None, required=False, metavar="C",
+                        help="chain of --compare (default: its first)")
+    parser.add_argument("--alignment", type=str, default=None, required=False, metavar="FILE",
+                        help="write the JSON line of --compare to FILE instead of standard error")
     return parser
 
 
@@ -958,10 +1049,19 @@ def run_dmpfold(argv=None):
                         template=args.template, iterations=args.iterations,
                         minsteps=args.minsteps, weights_file=args.model_weights,
                         return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None,
-                        native=args.native, return_scores=args.native is not None, native_chain=args.native_chain)
+                        native=args.native, return_scores=args.native is not None, native_chain=args.native_chain,
+                        compare=args.compare, compare_chain=args.compare_chain, return_alignment=args.compare is not None)
     coords, confs, alnmat = out[:3]
     if args.distmap is not None:
         save_distmap_npy(args.distmap, out[3])
+    if args.compare is not None:
+        line = json.dumps(_score.alignment_json(out[-1])) + "\n"
+        out = out[:-1]
+        if args.alignment is not None:
+            with open(args.alignment, "w") as fh:
+                fh.write(line)
+        else:
+            sys.stderr.write(line)
     if args.native is not None:
         line = json.dumps(_score.scores_json(out[-1])) + "\n"
         if args.scores is not None:

@@ -29,11 +29,27 @@ def score_floats(L):
     return 5 * int(L) + SCORE_HEADER
 
 
-def conf_floats(L, distmap=False, score=False):
+ALIGN_HEADER = 24                    # floats between m and the per-residue arrays of the align block
+ALIGN_NAMES = ("n_ali", "rmsd_ali", "tm_model", "tm_struct", "d0_model", "d0_struct", "seed_offset", "seeds")
+
+
+def align_floats(L, m):
+    """Floats of the align block of a prediction of length L aligned with a structure of m rows."""
+    return 1 + ALIGN_HEADER + 2 * int(L) + 3 * int(m)
+
+
+def conf_floats(L, distmap=False, score=False, align_m=None):
     """Floats the `d_conf` buffer of a prediction of length L must hold: the confidences, the L*L + 3 floats of option
-    "emit_distmap" and the 5L + 24 floats of option "score_native", in this order."""
+    "emit_distmap", the 5L + 24 floats of option "score_native" and, with `align_m` (the structure's rows; not None), the
+    25 + 2L + 3m floats of option "align_structure", in this order."""
     L = int(L)
-    return L + (L * L + 3 if distmap else 0) + (score_floats(L) if score else 0)
+    return (L + (L * L + 3 if distmap else 0) + (score_floats(L) if score else 0)
+            + (align_floats(L, align_m) if align_m is not None else 0))
+
+
+def align_offset(L, distmap=False, score=False):
+    """Where the align block begins in the `d_conf` buffer (A0 of include/dmpfold_hip.h)."""
+    return conf_floats(L, distmap, score)
 
 
 def score_offset(L, distmap=False):
@@ -46,34 +62,39 @@ def distmap_floats(L, on=True):
     return conf_floats(L, on)
 
 
-class Outputs(namedtuple("Outputs", "coords confs distmap info score_block", defaults=(None, None, None))):
+class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block", defaults=(None, None, None, None))):
     """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
-    score_block (5L + 24,) - None for what is absent."""
+    score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,) - None for what is absent."""
     __slots__ = ()
 
     @classmethod
-    def of(cls, public, distmap, score):
+    def of(cls, public, distmap, score, align=False):
         """The inverse of `public` for a caller that knows which options were on."""
         public = tuple(public)
-        return cls(*public[:2], *(public[2:4] if distmap else (None, None)), public[4 if distmap else 2] if score else None)
+        at = 4 if distmap else 2
+        return cls(*public[:2], *(public[2:4] if distmap else (None, None)), public[at] if score else None,
+                   public[at + (1 if score else 0)] if align else None)
 
-    def public(self, distmap=True, score=True):
+    def public(self, distmap=True, score=True, align=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
-        block if present and wanted."""
+        block if present and wanted, then the align block if present and wanted."""
         return ((self.coords, self.confs) + ((self.distmap, self.info) if distmap and self.distmap is not None else ())
-                + ((self.score_block,) if score and self.score_block is not None else ()))
+                + ((self.score_block,) if score and self.score_block is not None else ())
+                + ((self.align_block,) if align and self.align_block is not None else ()))
 
 
-def split_conf_buffer(buf, L, emit=False, score=False, coords=None):
-    """The parts of a `d_conf` buffer (a 1-D tensor or array of at least conf_floats(L, emit, score) floats) at the offsets of
-    include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through)."""
+def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None):
+    """The parts of a `d_conf` buffer (a 1-D tensor or array of at least conf_floats(L, emit, score, align_m) floats) at the
+    offsets of include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through)."""
     L = int(L)
-    if buf.ndim != 1 or buf.shape[0] < conf_floats(L, emit, score):
-        raise ValueError(f"a d_conf buffer of length {L} has {conf_floats(L, emit, score)} floats, got shape {tuple(buf.shape)}")
+    if buf.ndim != 1 or buf.shape[0] < conf_floats(L, emit, score, align_m):
+        raise ValueError(f"a d_conf buffer of length {L} has {conf_floats(L, emit, score, align_m)} floats, got shape {tuple(buf.shape)}")
     s0 = score_offset(L, emit)
+    a0 = align_offset(L, emit, score)
     return Outputs(coords, buf[:L], buf[L:L + L * L].reshape(L, L) if emit else None, buf[L + L * L:s0] if emit else None,
-                   buf[s0:s0 + score_floats(L)] if score else None)
+                   buf[s0:s0 + score_floats(L)] if score else None,
+                   buf[a0:a0 + align_floats(L, align_m)] if align_m is not None else None)
 
 
 def split_distmap_buffer(buf, L):
@@ -219,4 +240,74 @@ def scores_json(scores):
     for name in SCORE_NAMES[1:]:
         out[name] = num(scores[name])
     out["counts"] = [int(c) for c in scores["counts"]]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# option "align_structure" (include/dmpfold_hip.h): the model aligned with a structure of any length and sequence on the
+# GPU - TM-align's KIND of search (gapless threadings, then superposition and dynamic programming in turn), not its
+# bits: one family of initial alignments, one gap penalty, 16 refinements.  Any alignment gives a lower bound of the
+# best TM-score; nobody has compared the values with that program's.
+# ---------------------------------------------------------------------------------------------------------------------
+def as_structure(ca):
+    """What the front ends accept as `structure` -> float32 (m, 3), contiguous."""
+    ca = np.ascontiguousarray(np.asarray(ca, dtype=np.float32))
+    if ca.ndim != 2 or ca.shape[1] != 3:
+        raise ValueError(f"structure must be a C-alpha trace (m, 3); got {ca.shape}")
+    return ca
+
+
+def pack_structure(ca, L, m_value=None):
+    """The align block (float32 (25 + 2L + 3m,)) with its two inputs filled in - m in front, the trace at the end - and NaN
+    in the out slots.  `m_value`: what to write as m instead of the trace's length (tests of the library's validation)."""
+    ca = as_structure(ca)
+    m, L = ca.shape[0], int(L)
+    block = np.full(align_floats(L, m), np.nan, dtype=np.float32)
+    block[0] = float(m if m_value is None else m_value)
+    block[1 + ALIGN_HEADER + 2 * L:] = ca.reshape(-1)
+    return block
+
+
+def empty_structure(L):
+    """An align block without a structure: m = 0, which the library answers with NaN in every out slot."""
+    return pack_structure(np.zeros((0, 3), dtype=np.float32), L)
+
+
+def unpack_alignment(block, L):
+    """An align block (array or tensor) -> dict: n_ali (int), rmsd_ali, tm_model, tm_struct, d0_model, d0_struct (float),
+    seed_offset, seeds (int), R (3, 3) and t (3,) with structure ~ R model + t, ali (L,) int - the structure's row aligned
+    with model residue i, or -1 -, deviation (L,), and the inputs back: m, structure (m, 3).  A block the library answered
+    with NaN (a bad m, a NaN coordinate, a fault) gives n_ali 0, NaN floats and ali all -1."""
+    L = int(L)
+    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    m = (b.shape[0] - (1 + ALIGN_HEADER + 2 * L)) // 3 if b.ndim == 1 else -1
+    if m < 0 or b.shape[0] != align_floats(L, m):
+        raise ValueError(f"an align block of length {L} has 25 + 2L + 3m floats, got shape {tuple(b.shape)}")
+    h = b[1:1 + ALIGN_HEADER]
+
+    def whole(v):
+        return int(v) if v == v else 0
+    out = {"n_ali": whole(h[0]), "rmsd_ali": float(h[1]), "tm_model": float(h[2]), "tm_struct": float(h[3]),
+           "R": h[4:13].reshape(3, 3).copy(), "t": h[13:16].copy(), "d0_model": float(h[16]), "d0_struct": float(h[17]),
+           "seed_offset": whole(h[18]), "seeds": whole(h[19])}
+    ali = b[1 + ALIGN_HEADER:1 + ALIGN_HEADER + L]
+    out["ali"] = np.where(ali == ali, ali, -1.0).astype(np.int64)
+    out["deviation"] = b[1 + ALIGN_HEADER + L:1 + ALIGN_HEADER + 2 * L].copy()
+    out["m"] = float(b[0])
+    out["structure"] = b[1 + ALIGN_HEADER + 2 * L:].reshape(m, 3).copy()
+    return out
+
+
+def alignment_json(al):
+    """`unpack_alignment` as a JSON-ready dict (what `dmpfold --compare` prints and `dmpfold-batch --structures` writes):
+    the header fields, R, t and ali; NaN becomes None."""
+    def num(v):
+        v = float(v)
+        return v if v == v else None
+    out = {"m": num(al["m"])}
+    for name in ALIGN_NAMES:
+        out[name] = int(al[name]) if name in ("n_ali", "seed_offset", "seeds") else num(al[name])
+    out["R"] = [[num(v) for v in row] for row in np.asarray(al["R"])]
+    out["t"] = [num(v) for v in np.asarray(al["t"])]
+    out["ali"] = [int(v) for v in al["ali"]]
     return out

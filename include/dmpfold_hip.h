@@ -232,10 +232,65 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * |d_model - d_native| is below it; per residue preserved / (4 x partners), globally total preserved / (4 x total pairs)
  * (0 without any pair), from integer counts: exact and order-free.
  * THIS IS THE TM-SCORE PROGRAM'S KIND OF SEARCH, NOT ITS BITS: any superposition gives a lower bound of the true maximum,
- * and nobody has compared the values with that program's.  MaxSub and sequence-independent alignment are not offered.
+ * and nobody has compared the values with that program's.  MaxSub is not offered; a sequence-independent alignment is
+ * what option "align_structure" below gives.
  * Cost with the option on: three launches in dmp_predict_end (csrc/score.hip: score_prep, score_lddt, score_search - one
  * workgroup per seed, both traces and the set S in LDS, 6L floats + L flags; sums in a fixed order, the same bits on
- * every run).  A context holds 6 max_L records of 20 doubles. */
+ * every run).  A context holds 6 max_L records of 20 doubles.
+ * "align_structure" (0 or 1, default 0; any other value: DMP_ERR_ARG): align the model with a structure of any length and
+ * sequence on the device - a structural alignment found by superposition and dynamic programming in turn.  Read when a
+ * prediction begins and held for it.  With it 0 nothing is launched, nothing extra is read or written, and every output is
+ * bit for bit what it is without the option.  With it 1 dmp_predict_end launches the alignment behind "score_native", on
+ * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
+ * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
+ * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native"; the library cannot check
+ * the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
+ *   0                    in   m, the number of rows of the structure, as a float
+ *   1                    out  n_ali: aligned pairs
+ *   2                    out  rmsd_ali: Kabsch RMSD over the aligned pairs [Angstrom]
+ *   3                    out  tm_model: TM-score normalised by L
+ *   4                    out  tm_struct: TM-score normalised by m
+ *   5 .. 16              out  R (row-major 3 x 3) and t of the superposition that gave tm_struct: structure ~ R model + t
+ *   17, 18               out  d0_model = d0(L), d0_struct = d0(m)
+ *   19                   out  seed_offset: the k of the winning seed (may be negative)
+ *   20                   out  seeds: how many offsets stage 1 scored
+ *   21 .. 24             out  zero
+ *   [25, 25 + L)         out  ali[i]: row of the structure aligned with model residue i, or -1
+ *   [25 + L, 25 + 2L)    out  deviation of residue i from its partner under R, t [Angstrom]; NaN where ali[i] = -1
+ *   [25 + 2L, .. + 3m)   in   the structure's C-alpha trace, (x, y, z) per row, in chain order
+ * An m that is not an integer in [3, max_L], or a NaN among the 3m coordinates, gives NaN in every out slot and no fault;
+ * with such an m nothing beyond offset 0 is read.  A prediction that latched a device-side fault returns NaN in every out
+ * slot; the inputs are left alone.
+ * The definition (float64 from the float32 coordinates, contraction off, every sum in a fixed order, each output rounded
+ * once to float32).  For a length l, d0(l) = max(1.24 (l - 15)^(1/3) - 1.8, 0.5) for l > 15, else 0.5.  lmin = min(n, m),
+ * d0s = d0(lmin), d_cut = min(max(d0s, 4.5), 8).
+ * superpose(A, d0, lnorm), for an alignment A = pairs (i, j) in increasing order, is the loop of one seed of "score_native"
+ * on the packed pairs: start with S = A and repeat at most 20 times: Kabsch superposition of the model on the structure
+ * over S; deviations d of all pairs of A; tm = sum 1 / (1 + (d / d0)^2) / lnorm; keep the best tm with its R, t (strict
+ * comparison: the earliest of equals stays); S' = {d < d_cut}; stop if |S'| < 3 or S' = S.
+ * Stage 1 scores every gapless threading: minov = max(lmin / 2 (integer division), min(5, lmin)); seed k pairs i with
+ * j = i + k for every k whose overlap is at least minov, numbered by rising k (n + m - 2 minov + 1 <= 2 max_L seeds); its
+ * score is superpose(A_k, d0s, lmin).tm.  The 16 best seeds go on (by score, ties to the lower number; all, if fewer).
+ * Stage 2 refines each of them in at most 10 rounds from A = A_k: (1) (tm, R, t) = superpose(A, d0s, lmin); if tm beats the
+ * seed's best so far (strict) record (tm, A); (2) s_ij = 1 / (1 + d_ij^2 / d0s^2), d_ij^2 = |R p_i + t - q_j|^2; (3) the
+ * dynamic programme over i = 1..n, j = 1..m, H = 0 and D = 0 on the border: a = H[i-1][j-1] + s_ij,
+ * b = H[i-1][j] + (D[i-1][j] ? -0.6 : 0), c = H[i][j-1] + (D[i][j-1] ? -0.6 : 0), H[i][j] = max(a, b, c), the direction diag
+ * if a >= max(b, c), else up if b >= c, else left, D[i][j] = (direction is diag); (4) trace back from (n, m) along the
+ * directions until i = 0 or j = 0, every diag step aligns (i, j): A'; (5) stop if A' = A or |A'| < 3, else A = A'.  (The
+ * tenth round ends after (1): what a further programme gave would never be scored.)  Every candidate of (3) is a single
+ * float64 add of two defined values, so H does not depend on the order the cells are evaluated in.
+ * The result: the seed with the largest recorded tm, ties to the lower seed number; A* its alignment.  tm_model =
+ * superpose(A*, d0(n), n).tm; tm_struct, R, t = superpose(A*, d0(m), m); rmsd_ali = the RMSD of the plain Kabsch
+ * superposition over all of A*; ali from A*, the deviations from R, t.
+ * THIS IS TM-ALIGN'S KIND OF SEARCH, NOT ITS BITS: one family of initial alignments (the gapless threadings), one gap
+ * penalty, 16 refinements.  Any alignment it returns gives a valid lower bound of the best TM-score; nobody has compared
+ * the values with that program's.
+ * Cost with the option on: three launches in dmp_predict_end (csrc/align.hip: align_prep; align_thread - one workgroup per
+ * offset, L + max_L + 1 launched; align_refine - 16 workgroups of 256 threads, the programme as an anti-diagonal wavefront:
+ * three rotating diagonals of H and D in LDS, one barrier per diagonal, s_ij formed on the fly, the traceback serial).
+ * A context holds, ALLOCATED AT ITS CREATION and counted in "device_mib", 16 (max_L + 1)^2 bytes for the directions (one
+ * byte per cell and workgroup; 64 MiB at max_L = 2048), 16 alignments of 2 max_L ints and 2 max_L + 1 seed records. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
@@ -409,7 +464,8 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
  * to learn whether to go on, and returns with the remaining work enqueued as always.
  * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN INTO THEM
- * (layout: dmp_ctx_set_option). */
+ * (layout: dmp_ctx_set_option); WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m AND THE STRUCTURE'S
+ * TRACE WRITTEN INTO THEM. */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
                 int Lt, int nloops, int refine_steps, float* d_coords, float* d_conf,
                 void* stream);
@@ -466,7 +522,7 @@ int dmp_predict_set_vgru_result(dmp_ctx* ctx, const float* d_vout, void* event);
  * d_conf (L); a prediction during which a device-side fault was recorded returns NaN.
  * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * IF IT BEGAN WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE; the native trace and lnorm are read
- * from them here. */
+ * from them here; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m and the structure's trace read here. */
 int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream);
 int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream);
 int dmp_ctx_pending(dmp_ctx* ctx);
@@ -526,7 +582,7 @@ int dmp_pipeline_set_option(dmp_pipeline* p, const char* name, int value);
 /* d_coords: L x 5 x 3 floats, d_conf: L floats.  WITH OPTION "emit_distmap" = 1 ON THE PIPELINE d_conf MUST HOLD
  * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run.
  * WITH OPTION "score_native" = 1 ON THE PIPELINE d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN
- * INTO THEM BEFORE ready_event. */
+ * INTO THEM BEFORE ready_event; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, LIKEWISE. */
 int64_t dmp_pipeline_submit(dmp_pipeline* p, const uint8_t* d_msa, int N, int L, const float* d_template_ca, int nloops,
                             int refine_steps, float* d_coords, float* d_conf, void* ready_event);
 int dmp_pipeline_wait(dmp_pipeline* p, int what);
