@@ -12,17 +12,24 @@
 // accumulator q (rows 2q, 2q+1 of the 16 x 16 tile) at tap (dy, dx) reads the B fragment "row pair r = 2q + dy at
 // column offset dx": one fragment (x 3 pieces) serves every (q, dy) with 2q + dy = r.  A tap column dx is two passes -
 // taps dy = 0, 2, 4 against r = 0, 2, .., 18 and taps dy = 1, 3 against r = 1, 3, .., 17 - with the pass's weight
-// fragments (9 / 6 x 16 bytes per lane) in registers and a per-wave weight buffer of 3 tap slots (9 KB) refilled by
-// LDS-DMA for the next pass as soon as the fragments are in registers.  72 LDS reads per tap column and wave instead
-// of 135 for the same 240 MFMAs (the round-1 kernel went tap by tap: 3 weight + 24 activation fragments per tap).
+// fragments (9 / 6 x 16 bytes per lane) in registers.  72 LDS reads per tap column and wave instead of 135 for the same
+// 240 MFMAs (the round-1 kernel went tap by tap: 3 weight + 24 activation fragments per tap).
+//
+// Weights go straight from global memory to registers: a wave owns its 32 conv channels, so nobody else would read a
+// staged copy, and the packed layout already makes one 16-byte load one MFMA A operand.  Each pass's fragments are loaded
+// one pass ahead (15 fragments = 60 registers at the peak), at the head of the pass that runs on the other set.  LDS holds
+// nothing but the halo tile, twice: the tile of stage g + 1 is DMA'd into buffer (g + 1) & 1 from inside the first pass of
+// stage g, and a stage begins with one wait + ONE barrier (all pieces of tile g have landed, and every wave is done
+// reading the buffer that is overwritten next).
 //
 // Layouts (one 16-byte load = one MFMA operand)
 //   activations  xs[piece 3][c/8 16][P][P][8]   bf16, zero border (same geometry as the f32 planes)
 //   weights      wq[split 4][cgrp 8][dx 5][wave 4][dy: 0 2 4 1 3][piece 3][cg 2][m 32][8]   bf16
 //                (conv channel = split*128 + wave*32 + m, input channel = cgrp*16 + cg*8 + e):
-//                one wave's operands for one pass are 9 / 6 KB contiguous = 1 KB LDS-DMA pieces
-// Workgroup = 4 waves x (32 conv channels each) x one 16x16 (small L: 8x16, CqShape) pixel tile; 8 input stages of 16 channels, whose 20 x 20
-// halo tile (3 pieces) is shared by the waves (2 barriers per stage); no workgroup barrier inside a stage.
+//                one wave's operands for one pass are 9 / 6 KB contiguous: fragment (tap t, piece p) = 1 KB
+// Workgroup = 4 waves x (32 conv channels each) x one 16x16 (small L: 8x16, CqShape) pixel tile; 8 input stages of 16
+// channels, whose 20 x 20 halo tile (3 pieces) is shared by the waves (1 barrier per stage, two tile buffers); no
+// workgroup barrier inside a stage.
 // Lane -> pixel of a fragment follows the lane groups ds_read_b128 is served in (conv_f16.h): conflict free at any
 // row pitch >= 20.
 #pragma once
@@ -51,9 +58,8 @@ template <int NQ> struct CqShape {
 };
 constexpr int CQ_WSLOT = 3 * 2 * 32;                                  // 192 slots = 3 KB per wave and tap
 constexpr int CQ_WCOL = 5 * CQ_WSLOT;                                 // one tap column of one wave in the packed weights
-constexpr int CQ_WBUF = 3 * CQ_WSLOT;                                 // per-wave LDS weight buffer: 3 tap slots
-template <int NQ> constexpr int convq_lds_bytes() { return CqShape<NQ>::IN_BYTES + 4 * CQ_WBUF * 16; }     // 75776 / 60416
-constexpr int CONVQ_LDS_BYTES = convq_lds_bytes<8>();                 // two workgroups per CU
+template <int NQ> constexpr int convq_lds_bytes() { return 2 * CqShape<NQ>::IN_BYTES; }     // two halo tiles: 77824 / 47104
+constexpr int CONVQ_LDS_BYTES = convq_lds_bytes<8>();                 // two workgroups per CU (155648 of 163840 bytes)
 
 // round-to-nearest-even float32 -> bf16 bits
 __host__ __device__ inline uint16_t cq_bf16_rne(float f) {
@@ -124,8 +130,10 @@ __device__ __forceinline__ void cq_lane_pixel(int li, int& row, int& x) {
 // against the row pairs r = PAR, PAR + 2, .. < 19 read from the halo tile at `il`; the next row pair's three pieces are
 // requested before this one's MFMAs.  Per fragment the smallest products go first: w0 x2, w1 x1, w2 x0 (2^-16), then
 // w0 x1, w1 x0 (2^-8), then w0 x0 - each product type over the pass's taps, i.e. over different accumulators.
-template <int NQ, int NT, int PAR>
-__device__ __forceinline__ void cq_column_pass(const uint4 (&a)[NT][3], const uint4* il, cq_f32x16 (&acc)[NQ]) {
+// `mid` runs once between two row pairs, behind the first row pair that uses the pass's last tap: every weight fragment
+// has been waited for by then, so what it issues to the vector-memory queue has no wait of this pass behind it.
+template <int NQ, int NT, int PAR, class MID>
+__device__ __forceinline__ void cq_column_pass(const uint4 (&a)[NT][3], const uint4* il, cq_f32x16 (&acc)[NQ], MID&& mid) {
   constexpr int PIECE = CqShape<NQ>::PIECE, RP = CqShape<NQ>::RP;
   uint4 bn0 = il[PAR * CQ_PITCH], bn1 = il[PAR * CQ_PITCH + PIECE], bn2 = il[PAR * CQ_PITCH + 2 * PIECE];
 #pragma unroll
@@ -148,8 +156,27 @@ __device__ __forceinline__ void cq_column_pass(const uint4 (&a)[NT][3], const ui
     CQ_TAPS(1, b0)
     CQ_TAPS(0, b0)
 #undef CQ_TAPS
+    if (r == PAR + 2 * (NT - 1)) mid();
   }
 }
+
+// The weight fragments of one pass, straight from the packed weights into registers: fragment (tap t, piece p) of a
+// wave is 64 consecutive 16-byte slots (one per lane) at slot t * CQ_WSLOT + p * 64 of the pass; `src` includes the lane.
+template <int NT>
+__device__ __forceinline__ void cq_load_weights(const uint4* __restrict__ src, uint4 (&a)[NT][3]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int p = 0; p < 3; ++p) a[t][p] = src[t * CQ_WSLOT + p * 64];
+}
+
+#ifdef CQ_CLOCK_STAMPS
+// Diagnostic build only (-DCQ_CLOCK_STAMPS, never the library's): the first lane of every workgroup stamps the shader
+// clock and the 100 MHz reference clock around the stage loop; cycles / ticks x 100 MHz is the clock the chip held under
+// the kernel.  The stamps go to a buffer of their own that no kernel reads (dmp_debug_conv_clock copies it to the host).
+constexpr int CQ_STAMP_BLOCKS = 2048;
+__device__ unsigned long long cq_clock_stamps[CQ_STAMP_BLOCKS][2];
+#endif
 
 // number of workgroups to launch for tiles x tiles 16 x 16 pixel tiles cut into `bands` row bands each: the XCD-aware
 // block map of conv_f16.h (block b runs on XCD b % 8; XCD x works on ONE channel split (x & 3) of a contiguous half of
@@ -196,9 +223,7 @@ __global__ __launch_bounds__(256, 2) void conv5x5_bf16x6_kernel(const uint16_t* 
   }
 
   const uint4* in_l = reinterpret_cast<const uint4*>(cq_smem);
-  const uint4* w_l = reinterpret_cast<const uint4*>(cq_smem + SH::IN_BYTES) + wave * CQ_WBUF;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)cq_smem;
-  const unsigned w_lds_addr = lds_base + SH::IN_BYTES + wave * (CQ_WBUF * 16);
 
   // input-tile DMA plan: slot s = e*256 + tid (IN_PAD slots: the pad slots and the slots of the row pitch beyond the
   // 20 halo columns re-read a valid pixel)
@@ -216,12 +241,20 @@ __global__ __launch_bounds__(256, 2) void conv5x5_bf16x6_kernel(const uint16_t* 
     xx = xx < CQ_HCOLS ? xx : 0;
     in_src[e] = (int)(((int64_t)(p * 16 + cg) * P + ty0 + yy) * P + tx0 + xx);
   }
-  const uint4* wq4 = reinterpret_cast<const uint4*>(wq) + (int64_t)split * 8 * 5 * 4 * CQ_WCOL +
-                     (int64_t)wave * CQ_WCOL + lane;
+  // the halo tile of input stage g into LDS buffer g & 1: this wave's 64-slot pieces
+  auto tile_dma = [&](int g) {
+    const uint4* src = xs4 + (int64_t)g * 2 * PP;
+    const unsigned dst = lds_base + (g & 1) * SH::IN_BYTES + (wave * 64) * 16;
+#pragma unroll
+    for (int e = 0; e < SH::IN_PAD / 256; ++e) cq_dma16(src + in_src[e], dst + e * 4096);
+    if (wave * 64 < SH::IN_PAD % 256) cq_dma16(src + in_src[NE - 1], dst + (SH::IN_PAD / 256) * 4096);
+  };
+  // tap column c = g * 5 + dx of this wave in the packed weights: even pass at + 0, odd pass at + 3 * CQ_WSLOT
+  const uint4* wcol = reinterpret_cast<const uint4*>(wq) + (int64_t)split * 8 * 5 * 4 * CQ_WCOL +
+                      (int64_t)wave * CQ_WCOL + lane;
   int prow, px;
   cq_lane_pixel(li, prow, px);
   const int b_base = (kk * SH::HALO + prow) * CQ_PITCH + px;      // + r * CQ_PITCH + dx (+ piece stride)
-  const int a_off = kk * 32 + li;
 
   cq_f32x16 acc[NQ];
 #pragma unroll
@@ -229,60 +262,59 @@ __global__ __launch_bounds__(256, 2) void conv5x5_bf16x6_kernel(const uint16_t* 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 
-  // pass h = 2 * (g * 5 + dx) + odd: stream its 3 (even) or 2 (odd) tap slots into this wave's buffer
-  auto wdma = [&](int h) {
-    const int odd = h & 1;
-    const uint4* src = wq4 + (int64_t)(h >> 1) * 4 * CQ_WCOL + odd * 3 * CQ_WSLOT;
-    if (odd) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) cq_dma16(src + 64 * i, w_lds_addr + 1024 * i);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) cq_dma16(src + 64 * i, w_lds_addr + 1024 * i);
-    }
-  };
-  wdma(0);
+  // Weight fragments of the even (ae) and the odd (ao) pass of a tap column.  Each set is loaded one pass ahead, at the
+  // head of the pass that uses the other one (sched_barrier: left to itself the compiler sinks the loads to the end of
+  // that pass), so a load has a whole pass (>= 2300 MFMA cycles) to come back from L2.
+  uint4 ae[3][3], ao[2][3];
+  tile_dma(0);
+  cq_load_weights<3>(wcol, ae);
+  __builtin_amdgcn_sched_barrier(0);
+#ifdef CQ_CLOCK_STAMPS
+  const unsigned long long st_clk = __builtin_amdgcn_s_memtime(), st_real = __builtin_amdgcn_s_memrealtime();
+#endif
 
   for (int g = 0; g < 8; ++g) {
-    __syncthreads();                                   // every wave is done with the previous tile
-    {
-      const uint4* src = xs4 + (int64_t)g * 2 * PP;
-      const unsigned dst = lds_base + (wave * 64) * 16;
-#pragma unroll
-      for (int e = 0; e < SH::IN_PAD / 256; ++e) cq_dma16(src + in_src[e], dst + e * 4096);
-      if (wave * 64 < SH::IN_PAD % 256) cq_dma16(src + in_src[NE - 1], dst + (SH::IN_PAD / 256) * 4096);
-    }
+    // Tile g was issued early in stage g - 1 and the first pass's weights one pass ago: nothing younger is in flight, so
+    // this drains a queue that is already empty (g = 0: the prologue's loads).  ONE barrier per stage: every wave's pieces
+    // of tile g are in LDS, and every wave is done reading buffer (g + 1) & 1, which tile g + 1 is about to overwrite.
     cq_wait_vm<0>();
-    __syncthreads();                                   // the tile of every wave has landed
+    __syncthreads();
+    const uint4* in_g = in_l + (g & 1) * SH::IN_PAD + b_base;
 #pragma unroll 1
     for (int dx = 0; dx < 5; ++dx) {
-      const uint4* il = in_l + b_base + dx;
-      const int h0 = 2 * (g * 5 + dx);
+      const uint4* il = in_g + dx;
       {
-        // this pass's weights: issued one pass ago (at the head of a stage everything was drained with the tile)
-        cq_wait_vm<0>();
-        uint4 a[3][3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int p = 0; p < 3; ++p) a[t][p] = w_l[t * CQ_WSLOT + p * 64 + a_off];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        wdma(h0 + 1);                                  // the buffer is free: stream the next pass
-        cq_column_pass<NQ, 3, 0>(a, il, acc);
+        __builtin_amdgcn_sched_barrier(0);
+        cq_load_weights<2>(wcol + 3 * CQ_WSLOT, ao);
+        __builtin_amdgcn_sched_barrier(0);
+        // The next tile goes out from inside the stage's first pass, behind the pass's last wait for a weight fragment:
+        // vmcnt counts in issue order, so a wait for weights issued before the DMA does not wait for it, and the next
+        // wait (head of the following pass) comes most of a pass later.
+        cq_column_pass<NQ, 3, 0>(ae, il, acc, [&] {
+          if (dx == 0 && g < 7) {
+            __builtin_amdgcn_sched_barrier(0);
+            tile_dma(g + 1);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        });
       }
       {
-        cq_wait_vm<0>();
-        uint4 a[2][3];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int p = 0; p < 3; ++p) a[t][p] = w_l[t * CQ_WSLOT + p * 64 + a_off];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (h0 + 2 < 80) wdma(h0 + 2);
-        cq_column_pass<NQ, 2, 1>(a, il, acc);
+        // the next column's even pass (after the last column: the same column again, unused, instead of a branch)
+        const uint4* wnext = wcol + (g * 5 + dx < 39 ? 4 * CQ_WCOL : 0);
+        __builtin_amdgcn_sched_barrier(0);
+        cq_load_weights<3>(wnext, ae);
+        __builtin_amdgcn_sched_barrier(0);
+        cq_column_pass<NQ, 2, 1>(ao, il, acc, [] {});
+        wcol = wnext;
       }
     }
   }
+#ifdef CQ_CLOCK_STAMPS
+  if (tid == 0 && id < CQ_STAMP_BLOCKS) {
+    cq_clock_stamps[id][0] = __builtin_amdgcn_s_memtime() - st_clk;
+    cq_clock_stamps[id][1] = __builtin_amdgcn_s_memrealtime() - st_real;
+  }
+#endif
 
   // ---- epilogue: bias, 4-way max, store, per-channel partial sums per 8-row half tile (no cross-wave reduction:
   // a wave owns its 32 conv channels = 8 maxout channels for all pixels of the tile)

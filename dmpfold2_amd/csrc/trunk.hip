@@ -926,3 +926,13 @@ int head_gram_padded(dmp_ctx* c, const float* d_xpad, int L, float* d_conf, floa
 }
 
 }  // namespace dmp
+
+#ifdef CQ_CLOCK_STAMPS
+// Diagnostic build only (conv_bf16.h): the clock stamps of the bf16x6 launches so far, [blocks][2] = shader cycles and
+// 100 MHz ticks around the stage loop of every workgroup, copied to the host after a device synchronise.
+extern "C" int dmp_debug_conv_clock(unsigned long long* host, int blocks) {
+  if (!host || blocks < 1 || blocks > dmp::CQ_STAMP_BLOCKS) return -1;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(dmp::cq_clock_stamps), sizeof(unsigned long long) * 2 * blocks) == hipSuccess ? 0 : -1;
+}
+#endif
