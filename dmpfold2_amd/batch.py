@@ -144,14 +144,17 @@ def ca_only_text(coords, confs, alnmat):
     return "\n".join(out)
 
 
-def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None):
+def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
+                 hits=None, hits_top=10):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
     npz gains n_pairs, lnorm, rmsd, tm, gdt_ts, gdt_ha, lddt, counts, R, t, lddt_res and deviation; pdb / ca get
     <stem>.scores.json (the line `dmpfold --native` prints).  With `alignment` (the dict of score.unpack_alignment,
     --structures): npz gains the header fields of score.ALIGN_NAMES, ali, ali_R, ali_t and ali_deviation; pdb / ca get
-    <stem>.alignment.json (the line `dmpfold --compare` prints)."""
+    <stem>.alignment.json (the line `dmpfold --compare` prints).  With `hits` (the dict of Engine.hits: hits, rank, names;
+    --library): npz gains hit_rank, hit_tm_model, hit_tm_struct (per entry, in the library's order) and hit_names; pdb / ca get
+    <stem>.hits.json (the line `dmpfold --search` prints, the best `hits_top`)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -171,6 +174,11 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             extra.update({"ali": np.asarray(alignment["ali"], dtype=np.int32), "ali_R": np.asarray(alignment["R"], dtype=np.float32),
                           "ali_t": np.asarray(alignment["t"], dtype=np.float32),
                           "ali_deviation": np.asarray(alignment["deviation"], dtype=np.float32)})
+        if hits is not None:
+            extra.update({"hit_rank": np.asarray(hits["rank"], dtype=np.int32),
+                          "hit_tm_model": np.asarray([h["tm_model"] for h in hits["hits"]], dtype=np.float32),
+                          "hit_tm_struct": np.asarray([h["tm_struct"] for h in hits["hits"]], dtype=np.float32),
+                          "hit_names": np.asarray(hits["names"], dtype=np.str_)})
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
@@ -182,6 +190,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     if alignment is not None:
         with open(stem + ".alignment.json", "w") as fh:
             fh.write(json.dumps(_score.alignment_json(alignment)) + "\n")
+    if hits is not None:
+        with open(stem + ".hits.json", "w") as fh:
+            fh.write(json.dumps(_score.hits_json(hits, hits["names"], hits_top)) + "\n")
     path = stem + ".pdb"
     with open(path, "w") as fh:
         fh.write(pdb_text(coords, confs, alnmat) if fmt == "pdb" else ca_only_text(coords, confs, alnmat))
@@ -230,7 +241,7 @@ def cost_order(targets, iterations):
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
-              converge=None, stats_out=None, distmap=False, natives=None, structures=None):
+              converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
@@ -239,6 +250,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     target's model is aligned with the structure's first chain on the GPU (Pipeline.set_align) and the alignment is written
     with it (write_result); a target without a file is predicted without one.  `stats_out` then receives "alignments":
     {stem: the header fields of score.alignment_json}.
+    `library`: a fold library (a score.Library, a directory of PDB files or an .npz of tools/make_library.py): every
+    target's model is aligned with every entry on the GPU (Pipeline.set_search) and the ranking is written with it
+    (write_result); `stats_out` then receives "hits": {stem: the best `search_top` of score.hits_json, without R and t}.
     `distmap`: every target's chosen-pass distance map is brought back and written too (write_result).
     `converge` (Angstrom, None = off): targets stop recycling once converged (Pipeline.set_converge); `stats_out`, a
     dict, then receives this rank's "passes_run" and "passes_saved".
@@ -283,6 +297,12 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                           "without an alignment", file=sys.stderr)
         # the engines hold both traces: their capacity covers the longest structure too
         max_L = max([max_L] + [ca.shape[0] for ca in struct_ca.values()])
+    if isinstance(library, (str, os.PathLike)):
+        library = _score.Library.open(library)
+    if library is not None:
+        from .predict import MAX_L
+        library.check(MAX_L)
+        max_L = max(max_L, library.max_m)               # the engines' capacity bounds every entry's length
     t0 = time.perf_counter()
     pipe, dev, copy_stream = None, None, None
     failed, outputs, parsed, faulted = [], [], {}, []
@@ -302,6 +322,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_score(True)
             if structures:
                 pipe.set_align(True)
+            if library is not None:
+                pipe.set_search(library)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -335,10 +357,11 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     scored, all_scores = set(), {}
     aligned, all_alignments = set(), {}
+    all_hits = {}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        out = Outputs.of(public, distmap, bool(natives), bool(structures))
+        out = Outputs.of(public, distmap, bool(natives), bool(structures), library is not None)
         aln_path, alnmat, _ = parsed.pop(t)
         sc = None
         if out.score_block is not None and t in scored:
@@ -349,7 +372,13 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             al = _score.unpack_alignment(out.align_block, alnmat.shape[1])
             js = _score.alignment_json(al)
             all_alignments[os.path.splitext(os.path.basename(aln_path))[0]] = {k: js[k] for k in ("m",) + _score.ALIGN_NAMES}
-        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap, out.info, sc, al))
+        hits = None
+        if out.search_block is not None:
+            hits = dict(_score.unpack_search(out.search_block, alnmat.shape[1], library.lengths), names=list(library.names))
+            all_hits[os.path.splitext(os.path.basename(aln_path))[0]] = [
+                {k: v for k, v in h.items() if k not in ("R", "t")} for h in _score.hits_json(hits, library.names, search_top)["hits"]]
+        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap, out.info, sc, al, hits,
+                                    search_top))
 
     def finish(item):
         t, public = item
@@ -464,6 +493,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             stats_out["scores"] = all_scores
         if stats_out is not None and structures:
             stats_out["alignments"] = all_alignments
+        if stats_out is not None and library is not None:
+            stats_out["hits"] = all_hits
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
@@ -499,6 +530,12 @@ def batch_parser():
                          "aligned with the structure's first chain on the GPU (structural alignment, TM-scores by both lengths); "
                          "the summary gains each target's header fields; npz gains the arrays, pdb / ca write "
                          "<stem>.alignment.json; a target without a file is predicted without an alignment")
+    ap.add_argument("--library", default=None, metavar="DIR|FILE.npz",
+                    help="fold library (a directory of PDB files or an .npz of tools/make_library.py): every target's model is "
+                         "aligned with every entry on the GPU and the entries are ranked by TM-score; the summary gains each "
+                         "target's top hits; npz gains hit_rank, hit_tm_model, hit_tm_struct and hit_names, pdb / ca write "
+                         "<stem>.hits.json")
+    ap.add_argument("--search-top", type=int, default=10, metavar="N", help="hits per target to report with --library (default 10)")
     return ap
 
 
@@ -541,7 +578,7 @@ def main(argv=None):
                                   weights_file=args.model_weights, streams=args.streams,
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
-                                  structures=args.structures)
+                                  structures=args.structures, library=args.library, search_top=args.search_top)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -555,6 +592,8 @@ def main(argv=None):
         job_store.set(f"dmpfold_batch_scores/{rank}", json.dumps(passes.get("scores", {})))
     if args.structures and world > 1:
         job_store.set(f"dmpfold_batch_alignments/{rank}", json.dumps(passes.get("alignments", {})))
+    if args.library and world > 1:
+        job_store.set(f"dmpfold_batch_hits/{rank}", json.dumps(passes.get("hits", {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
         passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
@@ -576,6 +615,11 @@ def main(argv=None):
             for r in range(1, world):
                 alis.update(json.loads(job_store.get(f"dmpfold_batch_alignments/{r}").decode()))
             summary["aligned_targets"], summary["alignments"] = len(alis), dict(sorted(alis.items()))
+        if args.library:
+            hits = dict(passes.get("hits", {}))
+            for r in range(1, world):
+                hits.update(json.loads(job_store.get(f"dmpfold_batch_hits/{r}").decode()))
+            summary["searched_targets"], summary["hits"] = len(hits), dict(sorted(hits.items()))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

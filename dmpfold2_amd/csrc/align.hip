@@ -9,6 +9,8 @@
 //                 (three rotating diagonals of H and of the diag flag in LDS, one barrier per diagonal, the directions one
 //                 byte per cell in a per-workgroup scratch in global memory), serial traceback, until the alignment
 //                 repeats; the last arriver picks the winner and writes the header, ali and the deviations.
+// Option "search_structures" runs the same three stages over the K entries of a library, the entry as blockIdx.y, in chunks of
+// as many entries as the scratch budget holds, between search_prep (lengths validated, trace offsets, NaN fill) and search_rank.
 // Float64 from the float32 coordinates, contraction off, every sum in the fixed order of score_block_sum; every candidate
 // of a DP cell is one float64 add of two defined values, so H does not depend on the order the cells are evaluated in.
 // Every loop is bounded whatever the input holds, and every branch with a barrier inside is uniform over the workgroup.
@@ -28,34 +30,41 @@ __device__ __forceinline__ int agent_load_i32(int* p) { return __hip_atomic_load
 
 struct AlignArgs {
   const float* coords;   // [L][5][3] the backbone; the model trace is atom 1
-  float* blk;            // the align block: [0] m (in), [1, 25 + 2L) out, then the structure's trace (in)
-  int L, max_L;
+  float mf;              // m as the caller wrote it (a float; validated in align_prep)
+  float* out;            // [ALIGN_HEADER] the header: out[c - 1] is offset c of an align block
+  float* ali;            // [L], then deviation [L]
+  const float* trace;    // [m][3] the structure's trace (in)
+  int L, max_m;          // max_m: the bound on m (the context's max_L; "search_max_m" in a search)
+  size_t dir_stride, bali_stride;   // per survivor: bytes of `dir`, ints of `bali`
   float* pm;             // [L][3] model trace
   float* qs;             // [m][3] structure trace
   double* hdr;           // [8]
-  double* rec;           // [L + max_L + 1] tm of every seed of stage 1
+  double* rec;           // [L + max_m + 1] tm of every seed of stage 1
   int* surv;             // [1 + AL_T] how many survivors, their seed numbers in rank order
   double* btm;           // [AL_T] stage 2: a survivor's best tm ...
-  int* bali;             // [AL_T][1 + 2 max_L] ... and its alignment: K, then K pairs (i, j)
-  unsigned char* dir;    // [AL_T][(max_L + 1)^2] directions of the DP in flight, one byte per cell
+  int* bali;             // [AL_T][bali_stride >= 1 + 2 min(L, max_m)] ... and its alignment: K, then K pairs (i, j)
+  unsigned char* dir;    // [AL_T][dir_stride >= (L + 1)(max_m + 1)] directions of the DP in flight, one byte per cell
   unsigned* ticket;      // [2] stage 1, stage 2: zero between launches
 };
 
 // ---------------------------------------------------------------------------------------
 // align_prep
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SC_THREADS) void align_prep_kernel(AlignArgs a) {
+// The three kernels' bodies are device functions of one AlignArgs: the single-partner launches pass theirs as the kernel
+// argument, the batch launches of option "search_structures" form one per entry (blockIdx.y) from the search block and the
+// entry's slot - the same code either way, so an entry's floats are "align_structure"'s bit for bit.
+__device__ __forceinline__ void align_prep_body(const AlignArgs& a) {
   __shared__ int bad[SC_THREADS];
   const int L = a.L, tid = threadIdx.x;
-  const AlignLayout lay = align_layout(L);
   const float nan = __builtin_nanf("");
-  for (int i = 1 + tid; i < lay.in; i += SC_THREADS) a.blk[i] = nan;
-  const float mf = a.blk[0];
-  const bool m_ok = mf >= 3.f && mf <= (float)a.max_L && mf == floorf(mf);      // a NaN fails the comparisons
+  for (int i = tid; i < ALIGN_HEADER; i += SC_THREADS) a.out[i] = nan;
+  for (int i = tid; i < 2 * L; i += SC_THREADS) a.ali[i] = nan;
+  const float mf = a.mf;
+  const bool m_ok = mf >= 3.f && mf <= (float)a.max_m && mf == floorf(mf);      // a NaN fails the comparisons
   const int m = m_ok ? (int)mf : 0;                                              // 0: nothing beyond [0] is read
   int mine = 0;
   for (int i = tid; i < 3 * m; i += SC_THREADS) {
-    const float x = a.blk[lay.in + i];
+    const float x = a.trace[i];
     mine |= x != x ? 1 : 0;
     a.qs[i] = x;
   }
@@ -90,7 +99,7 @@ __device__ inline void align_seed(int s, int n, int m, int minov, int& k, int& i
 // ---------------------------------------------------------------------------------------
 // align_thread: stage 1, one workgroup per offset
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SC_THREADS) void align_thread_kernel(AlignArgs a) {
+__device__ __forceinline__ void align_thread_body(const AlignArgs& a) {
   extern __shared__ float sm[];          // 2 x 3 ov coordinates, then ov flags
   __shared__ double wred[SC_WAVES][16];
   __shared__ double bc[12];
@@ -99,7 +108,7 @@ __global__ __launch_bounds__(SC_THREADS) void align_thread_kernel(AlignArgs a) {
   if (a.hdr[AH_VALID] == 0.0) return;
   const int n = (int)a.hdr[AH_N], m = (int)a.hdr[AH_M], minov = (int)a.hdr[AH_MINOV];
   int nseeds = (int)a.hdr[AH_SEEDS];
-  if (nseeds > (int)gridDim.x) nseeds = (int)gridDim.x;      // never: the grid is L + max_L + 1 >= n + m - 2 minov + 1
+  if (nseeds > (int)gridDim.x) nseeds = (int)gridDim.x;      // never: the grid is L + max_m + 1 >= n + m - 2 minov + 1
   if ((int)blockIdx.x >= nseeds) return;
   const double lmin = a.hdr[AH_LMIN], d0s = a.hdr[AH_D0S], d_cut = a.hdr[AH_DCUT];
   int k, i0, ov;
@@ -158,11 +167,11 @@ __global__ __launch_bounds__(SC_THREADS) void align_thread_kernel(AlignArgs a) {
 // align_refine: stage 2, one workgroup per survivor
 // ---------------------------------------------------------------------------------------
 // LDS of align_refine in bytes: three diagonals of H, then what the superposition (2 x 3L floats, L flags) and the dynamic
-// programme (the structure's 3 max_L floats, three diagonals of the flag) use in turn, then three pair lists of L (i, j).
+// programme (the structure's 3 max_m floats, three diagonals of the flag) use in turn, then three pair lists of L (i, j).
 struct AlignLds { int un, lists, total; };
-__host__ __device__ inline AlignLds align_lds(int L, int max_L) {
+__host__ __device__ inline AlignLds align_lds(int L, int max_m) {
   const int h = 3 * (L + 1) * 8;
-  const int sup = 24 * L + L, dp = 12 * max_L + 3 * (L + 1);
+  const int sup = 24 * L + L, dp = 12 * max_m + 3 * (L + 1);
   const int un = ((sup > dp ? sup : dp) + 7) / 8 * 8;
   return {h, h + un, h + un + 3 * 2 * L * 2};
 }
@@ -178,7 +187,7 @@ __device__ inline void align_pack(const AlignArgs& a, const unsigned short* li, 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
+__device__ __forceinline__ void align_refine_body(const AlignArgs& a) {
   extern __shared__ double smd[];
   __shared__ double wred[SC_WAVES][16];
   __shared__ double bc[12];
@@ -189,17 +198,17 @@ __global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
   if ((int)blockIdx.x >= nsurv) return;                      // (no survivor at all: the out slots stay NaN)
   const int n = (int)a.hdr[AH_N], m = (int)a.hdr[AH_M], minov = (int)a.hdr[AH_MINOV];
   const double lmin = a.hdr[AH_LMIN], d0s = a.hdr[AH_D0S], d_cut = a.hdr[AH_DCUT];
-  const AlignLds lds = align_lds(L, a.max_L);
+  const AlignLds lds = align_lds(L, a.max_m);
   unsigned char* base = reinterpret_cast<unsigned char*>(smd);
   double* Hb = smd;                                          // [3][L + 1]
   float* pm2 = reinterpret_cast<float*>(base + lds.un);      // superposition: [K][3], [K][3], [K]
   float* qn2 = pm2 + 3 * L;
   unsigned char* fl = reinterpret_cast<unsigned char*>(qn2 + 3 * L);
   float* qs = reinterpret_cast<float*>(base + lds.un);       // dynamic programme: [m][3], [3][L + 1]
-  unsigned char* Db = reinterpret_cast<unsigned char*>(qs + 3 * a.max_L);
+  unsigned char* Db = reinterpret_cast<unsigned char*>(qs + 3 * a.max_m);
   unsigned short* lst = reinterpret_cast<unsigned short*>(base + lds.lists);
   unsigned short *ci = lst, *cj = lst + L, *ni = lst + 2 * L, *nj = lst + 3 * L, *bi = lst + 4 * L, *bj = lst + 5 * L;
-  unsigned char* dirp = a.dir + (size_t)blockIdx.x * (size_t)(a.max_L + 1) * (size_t)(a.max_L + 1);
+  unsigned char* dirp = a.dir + (size_t)blockIdx.x * a.dir_stride;
   const int seed = a.surv[1 + blockIdx.x];
 
   int K, coff = 0, bK = 0;                                   // the alignment in hand: K pairs from ci / cj [coff]
@@ -311,7 +320,7 @@ __global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
   __syncthreads();
 
   // this survivor's record: best tm, its alignment
-  int* rec = a.bali + (size_t)blockIdx.x * (size_t)(1 + 2 * a.max_L);
+  int* rec = a.bali + (size_t)blockIdx.x * a.bali_stride;
   for (int t = tid; t < bK; t += SC_THREADS) { agent_store_i32(rec + 1 + 2 * t, (int)bi[t]); agent_store_i32(rec + 2 + 2 * t, (int)bj[t]); }
   __syncthreads();
   if (tid == 0) {
@@ -332,14 +341,14 @@ __global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
       const int sd = a.surv[1 + w];
       if (tm > top || (tm == top && sd < win_seed)) { top = tm; win = w; win_seed = sd; }
     }
-    if (win >= 0 && agent_load_i32(a.bali + (size_t)win * (size_t)(1 + 2 * a.max_L)) < 3) win = -1;
+    if (win >= 0 && agent_load_i32(a.bali + (size_t)win * a.bali_stride) < 3) win = -1;
     sh_win = win;
     ticket_reset(a.ticket + 1);
   }
   __syncthreads();
   const int win = sh_win;
   if (win < 0) return;                                       // nothing but NaN: the out slots stay NaN
-  int* wrec = a.bali + (size_t)win * (size_t)(1 + 2 * a.max_L);
+  int* wrec = a.bali + (size_t)win * a.bali_stride;
   int wK = agent_load_i32(wrec);
   if (wK > L) wK = L;                                        // never
   for (int t = tid; t < wK; t += SC_THREADS) {
@@ -356,9 +365,8 @@ __global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
   __syncthreads();
   SeedBest bm;
   score_seed_loop(pm2, qn2, fl, wK, (double)m, d0m, d_cut, wred, bc, bm);
-  const AlignLayout lay = align_layout(L);
   if (tid == 0) {
-    float* out = a.blk;
+    float* out = a.out - 1;                                  // out[c]: offset c of an align block
     int k, i0, ov;
     align_seed(a.surv[1 + win], n, m, minov, k, i0, ov);
     out[1] = (float)wK;
@@ -373,34 +381,195 @@ __global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) {
     out[20] = (float)a.hdr[AH_SEEDS];
     for (int c = 21; c < ALIGN_HEADER + 1; ++c) out[c] = 0.f;
   }
-  for (int i = tid; i < L; i += SC_THREADS) a.blk[lay.ali + i] = -1.f;      // (the deviations of these rows stay NaN)
+  for (int i = tid; i < L; i += SC_THREADS) a.ali[i] = -1.f;      // (the deviations of these rows stay NaN)
   __syncthreads();
   double R[9], tr[3];
   for (int c = 0; c < 9; ++c) R[c] = bc[c];
   for (int c = 0; c < 3; ++c) tr[c] = bc[9 + c];
   for (int t = tid; t < wK; t += SC_THREADS) {
     const int i = ci[t];
-    a.blk[lay.ali + i] = (float)cj[t];
-    a.blk[lay.deviation + i] = (float)score_dev(R, tr, pm2 + 3 * t, qn2 + 3 * t);
+    a.ali[i] = (float)cj[t];
+    a.ali[L + i] = (float)score_dev(R, tr, pm2 + 3 * t, qn2 + 3 * t);
+  }
+}
+
+// the single-partner launches of option "align_structure"
+__global__ __launch_bounds__(SC_THREADS) void align_prep_kernel(AlignArgs a, const float* m_in) {
+  a.mf = m_in[0];
+  align_prep_body(a);
+}
+__global__ __launch_bounds__(SC_THREADS) void align_thread_kernel(AlignArgs a) { align_thread_body(a); }
+__global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) { align_refine_body(a); }
+
+// ---------------------------------------------------------------------------------------
+// option "search_structures": the same three stages over a chunk of entries (blockIdx.y), between search_prep and search_rank
+// ---------------------------------------------------------------------------------------
+struct SearchArgs {
+  const float* coords;   // [L][5][3]
+  float* conf;           // the d_conf buffer; the search block begins at B0 (search_base), which search_prep leaves in the table
+  ConfLayout lay;
+  int align;             // option "align_structure" of this prediction: its block lies in front of B0
+  int L, max_L, max_m, K;
+  unsigned char* ws;     // the scratch: table, tickets, slots (common.h)
+  SearchSlot slot;
+  const int* fault;      // the fault word of the prediction in flight
+};
+
+__device__ __forceinline__ int64_t* search_tab(const SearchArgs& sa) { return reinterpret_cast<int64_t*>(sa.ws); }
+
+// Entry k = first + blockIdx.y in slot blockIdx.y.  False (uniform over the workgroup) for an index that is no entry.  With
+// an invalid m_k somewhere the table says so: the entry then reads as m = 0 and nothing of its trace is touched.
+__device__ __forceinline__ bool search_entry(const SearchArgs& sa, int first, AlignArgs& a) {
+  const int y = (int)blockIdx.y, k = first + y;
+  if (y >= SEARCH_CHUNK_MAX || k < 0 || k >= sa.K) return false;
+  const int64_t* tab = search_tab(sa);
+  const bool ok = tab[0] == 1;
+  float* b = sa.conf + tab[1];
+  const SearchLayout lay = search_layout(sa.L, sa.K);
+  unsigned char* sl = sa.ws + SEARCH_HEAD_BYTES + (size_t)y * (size_t)sa.slot.total;
+  a.coords = sa.coords;
+  a.mf = ok ? b[k] : 0.f;
+  a.out = b + lay.hdr + (int64_t)ALIGN_HEADER * k;
+  a.ali = b + lay.res + 2 * (int64_t)sa.L * k;
+  a.trace = b + lay.in + (ok ? 3 * tab[2 + k] : 0);
+  a.L = sa.L;
+  a.max_m = sa.max_m;
+  a.dir_stride = (size_t)(sa.L + 1) * (size_t)(sa.max_m + 1);
+  a.bali_stride = (size_t)(1 + 2 * sa.L);
+  a.pm = reinterpret_cast<float*>(sl + sa.slot.pm);
+  a.qs = reinterpret_cast<float*>(sl + sa.slot.qs);
+  a.hdr = reinterpret_cast<double*>(sl + sa.slot.hdr);
+  a.rec = reinterpret_cast<double*>(sl + sa.slot.rec);
+  a.surv = reinterpret_cast<int*>(sl + sa.slot.surv);
+  a.btm = reinterpret_cast<double*>(sl + sa.slot.btm);
+  a.bali = reinterpret_cast<int*>(sl + sa.slot.bali);
+  a.dir = sl + sa.slot.dir;
+  a.ticket = reinterpret_cast<unsigned*>(sa.ws + SEARCH_TAB_BYTES) + 2 * y;
+  return true;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void align_prep_batch_kernel(SearchArgs sa, int first) {
+  AlignArgs a;
+  if (search_entry(sa, first, a)) align_prep_body(a);
+}
+__global__ __launch_bounds__(SC_THREADS) void align_thread_batch_kernel(SearchArgs sa, int first) {
+  AlignArgs a;
+  if (search_entry(sa, first, a)) align_thread_body(a);
+}
+__global__ __launch_bounds__(SC_THREADS) void align_refine_batch_kernel(SearchArgs sa, int first) {
+  AlignArgs a;
+  if (search_entry(sa, first, a)) align_refine_body(a);
+}
+
+// search_prep, one workgroup: B0 by the rule of common.h; every m_k an integer in [3, max_m]?; the rows in front of each
+// entry (thread t sums entries 16 t .. 16 t + 15, thread 0 scans the 256 sums: integers, order-free); NaN into every out slot.
+__global__ __launch_bounds__(SC_THREADS) void search_prep_kernel(SearchArgs sa) {
+  constexpr int PER = SEARCH_MAX / SC_THREADS;
+  __shared__ int bad[SC_THREADS];
+  __shared__ int64_t part[SC_THREADS];
+  __shared__ int sh_ok;
+  const int tid = threadIdx.x, K = sa.K, L = sa.L;
+  const int64_t B0 = search_base(sa.lay, L, sa.align, sa.align ? sa.conf[sa.lay.align_off] : 0.f, sa.max_L);
+  float* b = sa.conf + B0;
+  int64_t* tab = search_tab(sa);
+  int mine = 0, mk[PER];
+  int64_t sum = 0;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int k = PER * tid + q;
+    mk[q] = 0;
+    if (k < K) {
+      const float mf = b[k];
+      const bool ok = mf >= 3.f && mf <= (float)sa.max_m && mf == floorf(mf);
+      mine |= ok ? 0 : 1;
+      mk[q] = ok ? (int)mf : 0;
+      sum += mk[q];
+    }
+  }
+  bad[tid] = mine;
+  part[tid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    int any = 0;
+    int64_t run = 0;
+    for (int t = 0; t < SC_THREADS; ++t) {
+      any |= bad[t];
+      const int64_t v = part[t];
+      part[t] = run;
+      run += v;
+    }
+    sh_ok = any ? 0 : 1;
+    tab[0] = sh_ok;
+    tab[1] = B0;
+  }
+  __syncthreads();
+  const bool ok = sh_ok != 0;
+  int64_t run = part[tid];
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int k = PER * tid + q;
+    if (k < K) tab[2 + k] = ok ? run : 0;
+    run += mk[q];
+  }
+  const SearchLayout lay = search_layout(L, K);
+  const float nan = __builtin_nanf("");
+  for (int64_t i = lay.rank + tid; i < lay.in; i += SC_THREADS) b[i] = nan;
+}
+
+// search_rank, one workgroup: rank[r] = the entry with the r-th largest tm_model, by counting - entry k comes behind every
+// entry with a larger value and every equal one of a lower index; the NaN entries last, in index order.  A prediction that
+// latched a fault gets NaN in every out slot instead (the fault latch of api.hip does not know B0).
+__global__ __launch_bounds__(SC_THREADS) void search_rank_kernel(SearchArgs sa) {
+  __shared__ float tm[SEARCH_MAX];
+  const int tid = threadIdx.x, K = sa.K;
+  const int64_t* tab = search_tab(sa);
+  float* b = sa.conf + tab[1];
+  const SearchLayout lay = search_layout(sa.L, K);
+  if (*sa.fault != 0) {                                      // uniform
+    const float nan = __builtin_nanf("");
+    for (int64_t i = lay.rank + tid; i < lay.in; i += SC_THREADS) b[i] = nan;
+    return;
+  }
+  for (int k = tid; k < K; k += SC_THREADS) tm[k] = b[lay.hdr + (int64_t)ALIGN_HEADER * k + 2];
+  __syncthreads();
+  for (int k = tid; k < K; k += SC_THREADS) {
+    const float v = tm[k];
+    const bool vnan = v != v;
+    int pos = 0;
+    for (int j = 0; j < K; ++j) {
+      const float u = tm[j];
+      const bool unan = u != u;
+      const bool before = vnan ? (!unan || j < k) : (!unan && (u > v || (u == v && j < k)));
+      pos += before ? 1 : 0;
+    }
+    if (pos < K) b[lay.rank + pos] = (float)k;               // a permutation: always
   }
 }
 
 int align_kernel_attrs(dmp_ctx* c) {
   static_assert(AL_SLICE * SC_THREADS >= DMP_MAX_L + 1, "a thread's slice of a diagonal");
+  static_assert(SEARCH_MAX % SC_THREADS == 0, "search_prep: a whole number of entries per thread");
   static bool done[64] = {};
   if (c->device >= 0 && c->device < 64 && done[c->device]) return DMP_OK;
   DMP_HIP(hipFuncSetAttribute((const void*)align_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              align_lds(DMP_MAX_L, DMP_MAX_L).total));
+  DMP_HIP(hipFuncSetAttribute((const void*)align_refine_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               align_lds(DMP_MAX_L, DMP_MAX_L).total));
   if (c->device >= 0 && c->device < 64) done[c->device] = true;
   return DMP_OK;
 }
 
 int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
+  const AlignLayout lay = align_layout(L);
   AlignArgs a{};
   a.coords = d_coords;
-  a.blk = d_block;
+  a.out = d_block + 1;
+  a.ali = d_block + lay.ali;
+  a.trace = d_block + lay.in;
   a.L = L;
-  a.max_L = c->max_L;
+  a.max_m = c->max_L;
+  a.dir_stride = (size_t)(c->max_L + 1) * (size_t)(c->max_L + 1);
+  a.bali_stride = (size_t)(1 + 2 * c->max_L);
   a.pm = c->align_pm;
   a.qs = c->align_qs;
   a.hdr = c->align_hdr;
@@ -410,12 +579,57 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
   a.bali = c->align_bali;
   a.dir = c->align_dir;
   a.ticket = c->align_ticket;
-  hipLaunchKernelGGL(align_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a);
+  hipLaunchKernelGGL(align_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a, (const float*)d_block);
   DMP_LAUNCH_CHECK();
   // a seed's overlap has at most L rows: 6L floats + L flags of LDS, 50 KB at L = 2048
   hipLaunchKernelGGL(align_thread_kernel, dim3(L + c->max_L + 1), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(align_refine_kernel, dim3(AL_T), dim3(SC_THREADS), align_lds(L, c->max_L).total, s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+int search_wg_per_cu(int L, int max_m, int* out) {
+  DMP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(out, (const void*)align_refine_batch_kernel, SC_THREADS,
+                                                       (size_t)align_lds(L, max_m).total));
+  if (*out > 8) *out = 8;      // 256-thread workgroups: the hardware admits at most 8 per CU whatever the query answers
+  return DMP_OK;
+}
+
+// search_prep, then the three stages per chunk of C consecutive entries (one slot each), then search_rank.  Everything is
+// sized from (L, max_m) here; no length comes back from the device.
+int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
+  SearchArgs sa{};
+  sa.coords = d_coords;
+  sa.conf = d_conf;
+  sa.lay = lay;
+  sa.align = c->run.align;
+  sa.L = L;
+  sa.max_L = c->max_L;
+  sa.max_m = c->run.search_mm > 0 ? c->run.search_mm : c->max_L;
+  sa.K = c->run.search;
+  sa.ws = c->search_ws;
+  sa.slot = search_slot(L, sa.max_m);
+  sa.fault = c->seq_abort;
+  const int C = search_chunk_entries(L, sa.max_m, c->run.search_chunk);
+  DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws_bytes,
+          "search_structures: the scratch does not hold a chunk of %d entries at L = %d, search_max_m = %d", C, L, sa.max_m);
+  c->search_last_L = L;
+  c->search_last_mm = sa.max_m;
+  c->search_last_C = C;
+  hipLaunchKernelGGL(search_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
+  DMP_LAUNCH_CHECK();
+  for (int first = 0; first < sa.K; first += C) {
+    const int cn = std::min(C, sa.K - first);
+    hipLaunchKernelGGL(align_prep_batch_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, sa, first);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(align_thread_batch_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS),
+                       sizeof(float) * 6 * L + round_up(L, 16), s, sa, first);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(align_refine_batch_kernel, dim3(AL_T, cn), dim3(SC_THREADS), align_lds(L, sa.max_m).total, s, sa, first);
+    DMP_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(search_rank_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

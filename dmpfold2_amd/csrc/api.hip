@@ -408,7 +408,8 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // `lay`: the d_conf buffer of this prediction (common.h) - the confidences and, with option "emit_distmap", the whole extension
 // become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
 // caller's and stay.  The same for the align block of option "align_structure": its out slots become NaN, m in front of them and
-// the structure's trace behind them (past lay.total) stay.
+// the structure's trace behind them (past lay.total) stay.  (The search block of option "search_structures" lies at an offset only
+// the device knows: search_rank, the launch in front of this one, reads the same word and does the same there.)
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
                                    float* __restrict__ conf, int L, ConfLayout lay, int* __restrict__ report) {
   const int f = words[0];
@@ -421,6 +422,35 @@ __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ 
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
   }
+}
+
+// Option "search_structures": the scratch of a chunk, allocated when the option first becomes positive on a context (and
+// again, larger, if "search_max_m" grows afterwards) and counted in "device_mib".  It holds the table, the tickets and, for
+// every length the context takes, the slots of a whole chunk at this max_m.
+static int search_reserve(dmp_ctx* c) {
+  if (c->opt.search <= 0) return DMP_OK;
+  const int mm = c->opt.search_mm > 0 ? c->opt.search_mm : c->max_L;
+  int64_t need = 0;
+  for (int L = 8; L <= c->max_L; ++L)
+    need = std::max<int64_t>(need, (int64_t)search_chunk_entries(L, mm, 0) * search_slot(L, mm).total);
+  need += SEARCH_HEAD_BYTES;
+  if (c->search_ws && c->search_ws_bytes >= need) return DMP_OK;
+  int prev = 0;
+  DMP_HIP(hipGetDevice(&prev));
+  DMP_HIP(hipSetDevice(c->device));
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, (size_t)need);
+  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)SEARCH_HEAD_BYTES);      // the tickets: zero between launches
+  if (e == hipSuccess && c->search_ws) e = hipFree(c->search_ws);           // (waits for the work that uses it)
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (p) (void)hipFree(p);
+    return hip_fail(e, "search scratch", __FILE__, __LINE__);
+  }
+  c->bytes += need - c->search_ws_bytes;
+  c->search_ws = (unsigned char*)p;
+  c->search_ws_bytes = need;
+  return DMP_OK;
 }
 
 }  // namespace dmp
@@ -624,7 +654,29 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->opt.align = value;
     return DMP_OK;
   }
+  if (k == "search_structures") {    // takes effect with the next prediction begun
+    DMP_ARG(value >= 0 && value <= DMP_SEARCH_MAX, "search_structures must be 0 or 1 .. %d, got %d", DMP_SEARCH_MAX, value);
+    const int before = ctx->opt.search;
+    ctx->opt.search = value;
+    const int rc = search_reserve(ctx);
+    if (rc) ctx->opt.search = before;
+    return rc;
+  }
+  if (k == "search_max_m") {         // the caller's bound on every entry's length; 0 = max_L
+    DMP_ARG(value == 0 || (value >= 3 && value <= ctx->max_L), "search_max_m must be 0 or 3 .. max_L = %d, got %d", ctx->max_L, value);
+    const int before = ctx->opt.search_mm;
+    ctx->opt.search_mm = value;
+    const int rc = search_reserve(ctx);
+    if (rc) ctx->opt.search_mm = before;
+    return rc;
+  }
+  if (k == "search_chunk") {         // tests only: at most this many entries per chunk (0 = what the budget gives)
+    DMP_ARG(value >= 0, "search_chunk must be >= 0, got %d", value);
+    ctx->opt.search_chunk = value;
+    return DMP_OK;
+  }
   DMP_ARG(k != "passes_run", "passes_run is read only");
+  DMP_ARG(k != "search_chunk_used" && k != "search_wg_per_cu", "%s is read only", name);
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
 }
@@ -668,6 +720,15 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "emit_distmap") { *h_value = ctx->opt.emit; return DMP_OK; }
   if (k == "score_native") { *h_value = ctx->opt.score; return DMP_OK; }
   if (k == "align_structure") { *h_value = ctx->opt.align; return DMP_OK; }
+  if (k == "search_structures") { *h_value = ctx->opt.search; return DMP_OK; }
+  if (k == "search_max_m") { *h_value = ctx->opt.search_mm; return DMP_OK; }
+  if (k == "search_chunk") { *h_value = ctx->opt.search_chunk; return DMP_OK; }
+  // read only, of the last prediction that searched: entries per chunk; resident align_refine workgroups per CU
+  if (k == "search_chunk_used") { *h_value = ctx->search_last_C; return DMP_OK; }
+  if (k == "search_wg_per_cu") {
+    *h_value = 0;
+    return ctx->search_last_C ? search_wg_per_cu(ctx->search_last_L, ctx->search_last_mm, h_value) : DMP_OK;
+  }
   if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
   set_error("unknown option %s", name);
   return DMP_ERR_ARG;
@@ -691,6 +752,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->bwd_ws) (void)hipFree(c->bwd_ws);
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
+  if (c->search_ws) (void)hipFree(c->search_ws);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
   for (void* e : c->unit_ev)
@@ -1436,6 +1498,8 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score_off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align_off, s))) return rc;
+  // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)
+  if (c->run.search > 0 && (rc = search_structures(c, d_coords, L, d_conf, lay, s))) return rc;
   hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, lay.total), 256)), dim3(256), 0, s,
                      c->seq_abort, d_coords, d_conf, L, lay, c->end_fault_out);
   DMP_LAUNCH_CHECK();

@@ -77,6 +77,48 @@ __host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, in
   return {L, info_off, score_off, score_off + score_layout(L).out, align_off, align_off + 1, align_off + (align ? align_layout(L).in : 0)};
 }
 
+//   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
+//   (search_base below): m_k [K] (in) | rank [K] | K headers of ALIGN_HEADER floats | K x (ali [L], deviation [L]) | the
+//   entries' traces [3 sum m_k] (in).
+// m' of the B0 rule: the align block's m if that is an integer in [3, max_L], else 0 (a NaN fails the comparisons)
+__host__ __device__ inline int64_t search_base(const ConfLayout& lay, int L, int align, float align_m, int max_L) {
+  const bool ok = align_m >= 3.f && align_m <= (float)max_L && align_m == floorf(align_m);
+  return lay.align_off + (align ? align_layout(L).in + 3 * (int64_t)(ok ? (int)align_m : 0) : 0);
+}
+struct SearchLayout { int64_t rank, hdr, res, in; };                    // relative to B0; res: entry k's ali, deviation at res + 2Lk
+__host__ __device__ inline SearchLayout search_layout(int L, int K) {
+  return {K, 2 * (int64_t)K, (2 + ALIGN_HEADER) * (int64_t)K, (2 + ALIGN_HEADER) * (int64_t)K + 2 * (int64_t)L * K};
+}
+// One entry's working set in the search scratch (bytes from the slot's start, every part 16-aligned): what a context holds
+// once for "align_structure", here sized from (L, max_m) - the model trace, the entry's trace, the header, the seed records,
+// the survivors, their best tm and alignments, the directions of the 16 dynamic programmes in flight.
+struct SearchSlot { int64_t pm, qs, hdr, rec, surv, btm, bali, dir, total; };
+__host__ __device__ inline SearchSlot search_slot(int L, int max_m) {
+  auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
+  SearchSlot s;
+  s.pm = 0;
+  s.qs = s.pm + up(12 * (int64_t)L);
+  s.hdr = s.qs + up(12 * (int64_t)max_m);
+  s.rec = s.hdr + 64;
+  s.surv = s.rec + up(8 * (int64_t)(L + max_m + 1));
+  s.btm = s.surv + up(4 * (1 + 16));
+  s.bali = s.btm + 8 * 16;
+  s.dir = s.bali + up(4 * 16 * (int64_t)(1 + 2 * L));
+  s.total = s.dir + up(16 * (int64_t)(L + 1) * (max_m + 1));
+  return s;
+}
+// in front of the slots: the table search_prep writes ([0] every m_k valid, [1] B0, [2 + k] rows in front of entry k), then
+// two tickets per slot (zero between launches, at a place that does not depend on L)
+constexpr int SEARCH_MAX = DMP_SEARCH_MAX, SEARCH_CHUNK_MAX = 256;
+constexpr int64_t SEARCH_BUDGET = (int64_t)DMP_SEARCH_BUDGET_MIB << 20;
+constexpr int64_t SEARCH_TAB_BYTES = 8 * (2 + (int64_t)SEARCH_MAX), SEARCH_HEAD_BYTES = SEARCH_TAB_BYTES + 4 * 2 * SEARCH_CHUNK_MAX;
+// entries per chunk: as many slots as the budget holds, 1 .. 256; `cap` > 0 (option "search_chunk") lowers it
+inline int search_chunk_entries(int L, int max_m, int cap) {
+  int64_t C = SEARCH_BUDGET / search_slot(L, max_m).total;
+  C = C < 1 ? 1 : (C > SEARCH_CHUNK_MAX ? SEARCH_CHUNK_MAX : C);
+  return cap > 0 && cap < C ? cap : (int)C;
+}
+
 // padded activation geometry: interior [2, 2+L) in both axes, zero elsewhere
 inline int act_tiles(int L) { return cdiv(L, CONV_TILE); }
 inline int act_pitch(int L) { return act_tiles(L) * CONV_TILE + 4; }
@@ -150,7 +192,8 @@ struct dmp_lane {
   long long count = 0;     // conv launches recorded so far (event of launch i: ev[i % RING])
 };
 
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0; };   // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure"
+// options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0; };
 
 struct dmp_ctx {
   int device = 0;
@@ -299,6 +342,11 @@ struct dmp_ctx {
   int* align_bali = nullptr;       // [ALIGN_SURVIVORS][1 + 2 max_L] ... and its alignment
   unsigned char* align_dir = nullptr;        // [ALIGN_SURVIVORS][(max_L + 1)^2] DP directions, one byte per cell
   unsigned* align_ticket = nullptr;          // [2] zero between launches
+  // option "search_structures": one allocation made when the option first becomes positive (api.hip: search_reserve) - the
+  // table, the tickets, then the slots of a chunk (search_slot above)
+  unsigned char* search_ws = nullptr;
+  int64_t search_ws_bytes = 0;
+  int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -578,6 +626,9 @@ int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipSt
 constexpr int ALIGN_SURVIVORS = 16; // seeds of the gapless threading that the dynamic programme refines (align.hip)
 int align_kernel_attrs(dmp_ctx* c);   // once per device, at context creation
 int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
+// option "search_structures" (align.hip): the model aligned with each of the K entries of the search block, then ranked
+int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
+int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the batch launch
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);

@@ -229,13 +229,14 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=False, structure=None):
+def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=False, structure=None, library=None, max_L=None):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is sized for the options as the context holds them - the library cannot check
     it, writes L + L*L + 3 floats with "emit_distmap" on (`emit_alloc`: sized as if it were) and reads and writes 5L + 24
     more behind them with "score_native" on: the native trace goes there (no `native` = no row present: n_pairs 0, NaN scores);
     with "align_structure" on (`align`) 25 + 2L + 3m more behind those, m and the rows of `structure` in them (no `structure`:
-    m = 0, which the library answers with NaN)."""
+    m = 0, which the library answers with NaN); with "search_structures" on (`library`, a score.Library; `max_L`: the
+    context's, for the rule of B0) the search block behind those, filled from the library's copy on the GPU."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -248,8 +249,14 @@ def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=F
         ablock = _score.pack_structure(structure, L) if structure is not None else _score.empty_structure(L)
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     alloc = emit if emit_alloc is None else emit_alloc
-    buf = torch.empty((_score.conf_floats(L, alloc, score, align_m),), dtype=torch.float32, device=device)
-    out = split_conf_buffer(buf, L, emit, score, coords, align_m)
+    search = None if library is None else (len(library), library.rows, max_L)
+    floats = _score.conf_floats(L, alloc, score, align_m)
+    if search is not None:
+        floats = max(floats, _score.search_offset(L, alloc, score, align_m, max_L) + _score.search_floats(L, *search[:2]))
+    buf = torch.empty((floats,), dtype=torch.float32, device=device)
+    out = split_conf_buffer(buf, L, emit, score, coords, align_m, search)
+    if search is not None:
+        library.fill_block(out.search_block, L)
     if align:
         out.align_block.copy_(torch.from_numpy(ablock))
     if score:
@@ -275,6 +282,7 @@ class Engine:
         self.last_fallback = False     # the last predict_*_checked call fell back to conv_mode 2
         self._score = None             # (score block, L) of the last prediction
         self._align = None             # (align block, L) of the last prediction
+        self._search = None            # (search block, L, library) of the last prediction
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
@@ -323,8 +331,11 @@ class Engine:
         self.weights_tag = other.weights_tag
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
-                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
+                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `library` (a score.Library of K structures, each 3 .. max_L rows): the final trace is aligned with every one of them on
+        the GPU (option "search_structures", set for this call only, "search_max_m" = the longest entry); what the call
+        returns does not change, the results and the ranking are in `hits`.
         `structure` (an (m, 3) array, the C-alpha trace of a structure of any length, 3 <= m <= max_L): the final trace is
         aligned with it on the GPU (option "align_structure", set for this call only); what the call returns does not
         change, the result is in `alignment`.
@@ -344,7 +355,22 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure)
+        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library)
+
+    @property
+    def hits(self):
+        """The search of the last prediction as score.unpack_search gives it, with the library's `names` beside `hits` and
+        `rank`; None if it ran without option "search_structures".  Synchronises with the GPU."""
+        if self._search is None:
+            return None
+        block, L, library = self._search
+        torch.cuda.synchronize(self.device)
+        return dict(_score.unpack_search(block, L, library.lengths), names=list(library.names))
+
+    @property
+    def search_block(self):
+        """The last prediction's search block on the GPU (26K + 2LK + 3M floats, a view of the buffer handed to the library), or None."""
+        return None if self._search is None else self._search[0]
 
     @property
     def alignment(self):
@@ -382,13 +408,14 @@ class Engine:
         return self.get_option("passes_run")
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
-                       minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
+                       minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        with self._call_options(converge, distmap, native, structure):
-            return self._run(d_msa, template_ca, iterations, minsteps, native, structure).public(distmap, score=False, align=False)
+        with self._call_options(converge, distmap, native, structure, library):
+            return self._run(d_msa, template_ca, iterations, minsteps, native, structure,
+                             library).public(distmap, score=False, align=False, search=False)
 
     @contextlib.contextmanager
-    def _call_options(self, converge, distmap, native, structure=None):
+    def _call_options(self, converge, distmap, native, structure=None, library=None):
         """The options one call asks for - read when the prediction begins - set for its duration, then as they were.
         `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" / "align_structure" set by hand
         stay set."""
@@ -400,6 +427,10 @@ class Engine:
         if structure is not None and not self.get_option("align_structure"):
             _score.as_structure(structure)                                                 # (a bad shape raises before anything changes)
             want["align_structure"] = 1
+        if library is not None and not self.get_option("search_structures"):
+            library.check(self.max_L)                                                      # (raises, naming the entry)
+            want["search_max_m"] = library.max_m          # before the option itself: the scratch is sized from it
+            want["search_structures"] = len(library)
         before = {}
         try:
             for name, value in want.items():
@@ -407,23 +438,32 @@ class Engine:
                 self.set_option(name, value)
             yield
         finally:
-            for name, value in before.items():
+            for name, value in reversed(list(before.items())):
                 self.set_option(name, value)
 
-    def _run(self, d_msa, template_ca, iterations, minsteps, native, structure=None):
+    def _run(self, d_msa, template_ca, iterations, minsteps, native, structure=None, library=None):
         """One prediction with the options as the context holds them -> Outputs."""
         emit, score = bool(self.get_option("emit_distmap")), bool(self.get_option("score_native"))
         align = bool(self.get_option("align_structure"))
         if align and structure is not None and _score.as_structure(structure).shape[0] > self.max_L:
             raise RuntimeError(f"structure has {len(structure)} rows; the engine's capacity is {self.max_L} (max_L)")
+        search = self.get_option("search_structures")
+        if search:
+            if library is None or len(library) != search:
+                raise RuntimeError(f"search_structures is {search}: the prediction needs a library of that many entries"
+                                   + ("" if library is None else f", got {len(library)}"))
+            library.check(self.get_option("search_max_m") or self.max_L)
         assert d_msa.dtype == torch.uint8 and d_msa.is_contiguous() and d_msa.device == self.device
         n, L = d_msa.shape
         if L < 8:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         with torch.cuda.device(self.device):
-            self._score = self._align = None
-            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, align=align, structure=structure)
+            self._score = self._align = self._search = None
+            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, align=align, structure=structure,
+                                library=library if search else None, max_L=self.max_L)
+            if search:
+                self._search = (out.search_block, L, library)
             if score:
                 self._score = (out.score_block, L)
             if align:
@@ -468,7 +508,7 @@ class Engine:
         raise_for_faults(self.sync_faults())
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
-                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
+                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
@@ -476,20 +516,20 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure)
+        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
-                               minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None):
-        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`: see `predict`; a
-        repeat of the prediction returns the repeat's map, scores and alignment)."""
+                               minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
+        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`: see
+        `predict`; a repeat of the prediction returns the repeat's map, scores, alignment and hits)."""
         return self._checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native,
-                             structure).public(distmap, score=False, align=False)
+                             structure, library).public(distmap, score=False, align=False, search=False)
 
-    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure=None):
+    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure=None, library=None):
         """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry `native` and
         `structure` along."""
-        with self._call_options(converge, distmap, native, structure):
-            out = self._run(d_msa, template_ca, iterations, minsteps, native, structure)
+        with self._call_options(converge, distmap, native, structure, library):
+            out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
             bits = self.sync_faults()
             self.last_fallback = False
             if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
@@ -498,7 +538,7 @@ class Engine:
                 print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
                       "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
                 self.set_option("vgru_persistent", 0)
-                out = self._run(d_msa, template_ca, iterations, minsteps, native, structure)
+                out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
                 bits = self.sync_faults()
             if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
                 print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
@@ -507,7 +547,7 @@ class Engine:
                 self.last_fallback = True
                 self.set_option("conv_mode", 2)
                 try:
-                    out = self._run(d_msa, template_ca, iterations, minsteps, native, structure)
+                    out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
                     bits = self.sync_faults()
                 finally:
                     self.set_option("conv_mode", 0)
@@ -535,6 +575,7 @@ class _PipelineEngine(Engine):
         self.last_fallback = False
         self._score = None
         self._align = None
+        self._search = None
 
     def close(self):
         self._ctx = C.c_void_p()
@@ -546,7 +587,8 @@ class _PipelineEngine(Engine):
 # A target in a `Pipeline`: what stays alive until its result is handed out and what a repeat needs.  `out`: its Outputs,
 # `ready`: the event behind the producer of its inputs, `native`: as given to `submit`, None if the target is not scored,
 # `structure`: as given to `submit`, None if the target is not aligned.
-_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready native structure", defaults=(None,))
+# `library`: the score.Library the target searches, None if it does not.
+_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready native structure library", defaults=(None, None))
 
 
 # ticket states of the C pipeline (include/dmpfold_hip.h, DMP_TICKET_*)
@@ -564,7 +606,7 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False, score=False, align=False):
+                 distmap=False, score=False, align=False, search=None):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -574,8 +616,11 @@ class Pipeline:
         `score`: every target is scored against the native trace given to `submit` (`set_score`); its score block (5L + 24
         floats, score.unpack_scores) is then the last element of what those calls give per target.
         `align`: every target is aligned with the `structure` given to `submit` (`set_align`); its align block (25 + 2L + 3m
-        floats, score.unpack_alignment) is then the last element of what those calls give per target, behind the score block."""
+        floats, score.unpack_alignment) is then the last element of what those calls give per target, behind the score block.
+        `search` (a score.Library): every target is aligned with every entry of it (`set_search`); its search block (26K + 2LK
+        + 3M floats, score.unpack_search) is then the last element of all."""
         self.lib = _lib.load()
+        self._search = None
         self.device = _resolve_device(device)
         S = max(1, int(streams))
         self._p = C.c_void_p()
@@ -603,6 +648,8 @@ class Pipeline:
             self.set_score(True)
         if align:
             self.set_align(True)
+        if search is not None:
+            self.set_search(search)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -628,6 +675,18 @@ class Pipeline:
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
         self.set_option("align_structure", 1 if on else 0)
+
+    def set_search(self, library):
+        """Option "search_structures" on every engine: targets submitted from now on are aligned with every entry of `library`
+        (a score.Library; None = off); idle pipeline only."""
+        if library is None:
+            self.set_option("search_structures", 0)
+            self.set_option("search_max_m", 0)
+        else:
+            library.check(self.engines[0].max_L)
+            self.set_option("search_max_m", library.max_m)
+            self.set_option("search_structures", len(library))
+        self._search = library
 
     def close(self):
         if self._p:
@@ -675,9 +734,19 @@ class Pipeline:
                                    "set_align / set_score / set_distmap")
             if align and structure is not None and _score.as_structure(structure).shape[0] > self.engines[0].max_L:
                 raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {self.engines[0].max_L}")
-            # (the native and align blocks are written on the current stream: `ready` below is behind it)
+            kflags = [e.get_option("search_structures") for e in self.engines]
+            search = kflags[0]
+            if any(kflags) and not (all(k == search for k in kflags) and emit == any(flags) and score == any(sflags)
+                                    and align == any(aflags)):
+                raise RuntimeError("search_structures: the engines of a pipeline must agree on \"search_structures\", "
+                                   "\"align_structure\", \"score_native\" and \"emit_distmap\" (the search block's place in the "
+                                   "buffer depends on all four); use set_search / set_align / set_score / set_distmap")
+            library = self._search if search else None
+            if search and (library is None or len(library) != search):
+                raise RuntimeError(f"search_structures is {search} on the engines: give the library to set_search")
+            # (the native, align and search blocks are written on the current stream: `ready` below is behind it)
             d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, emit_alloc=any(flags), align=align,
-                                structure=structure)
+                                structure=structure, library=library, max_L=self.engines[0].max_L)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -693,7 +762,7 @@ class Pipeline:
             int(max(iterations, 0)), int(max(minsteps, 0)), out.coords.data_ptr(), out.confs.data_ptr(),
             C.c_void_p(ready.cuda_event)))
         self._jobs[t] = _Job(d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, out, ready, native if score else None,
-                             structure if align else None)
+                             structure if align else None, library)
         self._reap()
         return t
 
@@ -825,7 +894,7 @@ class Pipeline:
                     if res.align_block is not None and strc is None:
                         strc = np.zeros((0, 3), dtype=np.float32)
                     try:
-                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat, strc)
+                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat, strc, job.library)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
@@ -937,7 +1006,7 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
                   return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
-                  compare_chain=None, return_alignment=False):
+                  compare_chain=None, return_alignment=False, search=None, return_hits=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -949,7 +1018,10 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     `return_scores` the dict of score.unpack_scores is appended behind everything else (None without a `native`).
     `compare` (addition): a PDB file (its chain `compare_chain`, default the first) or an (m, 3) C-alpha trace of a structure of
     any length and sequence; the model is aligned with it on the GPU (option "align_structure").  With `return_alignment`
-    the dict of score.unpack_alignment is appended last of all, behind the scores (None without a `compare`)."""
+    the dict of score.unpack_alignment is appended behind the scores (None without a `compare`).
+    `search` (addition): a score.Library, a directory of PDB files or an .npz of tools/make_library.py; the model is aligned
+    with every entry on the GPU (option "search_structures").  With `return_hits` the dict of Engine.hits (hits, rank, names)
+    is appended last of all (None without a `search`)."""
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -967,19 +1039,26 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
         compare = _score.as_structure(compare)
         if not 3 <= compare.shape[0] <= MAX_L:
             raise ValueError(f"compare: the structure has {compare.shape[0]} C-alpha atoms; 3 to {MAX_L} can be aligned")
-    scores = alignment = None
+    if isinstance(search, (str, os.PathLike)):
+        search = _score.Library.open(search)
+    if search is not None:
+        search.check(MAX_L)
+    scores = alignment = hits = None
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
         # (the engine holds both traces: its capacity covers the structure to align with, too)
-        eng = get_engine(dev, length if compare is None else max(length, compare.shape[0]), nseqs, weights_file=weights_file)
+        cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
+        eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap),
-                                  native=native, structure=compare)
+                                  native=native, structure=compare, library=search)
+        if search is not None and return_hits:
+            hits = eng.hits
         if native is not None and return_scores:
             scores = eng.scores
         if compare is not None and return_alignment:
             alignment = eng.alignment
     coords, confs = out[0], out[1]
     ret = (coords, confs) + ((alnmat,) if return_alnmat else ()) + ((out[2],) if return_distmap else ())
-    return ret + ((scores,) if return_scores else ()) + ((alignment,) if return_alignment else ())
+    return ret + ((scores,) if return_scores else ()) + ((alignment,) if return_alignment else ()) + ((hits,) if return_hits else ())
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1003,7 +1082,7 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native and --compare."""
+    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --compare and --search."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -1039,6 +1118,14 @@ def dmpfold_parser():
                         help="chain of --compare (default: its first)")
     parser.add_argument("--alignment", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --compare to FILE instead of standard error")
+    parser.add_argument("--search", type=str, default=None, required=False, metavar="DIR|FILE.npz",
+                        help="align the model on the GPU with every structure of a fold library (a directory of PDB files or an "
+                             ".npz of tools/make_library.py) and rank them by TM-score; the best hits go to standard error as one "
+                             "JSON line, the model on standard output is unchanged")
+    parser.add_argument("--search-top", type=int, default=10, required=False, metavar="N",
+                        help="how many hits of --search to report (default 10)")
+    parser.add_argument("--hits", type=str, default=None, required=False, metavar="FILE",
+                        help="write the JSON line of --search to FILE instead of standard error")
     return parser
 
 
@@ -1050,8 +1137,17 @@ def run_dmpfold(argv=None):
                         minsteps=args.minsteps, weights_file=args.model_weights,
                         return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None,
                         native=args.native, return_scores=args.native is not None, native_chain=args.native_chain,
-                        compare=args.compare, compare_chain=args.compare_chain, return_alignment=args.compare is not None)
+                        compare=args.compare, compare_chain=args.compare_chain, return_alignment=args.compare is not None,
+                        search=args.search, return_hits=args.search is not None)
     coords, confs, alnmat = out[:3]
+    if args.search is not None:
+        line = json.dumps(_score.hits_json(out[-1], out[-1]["names"], args.search_top)) + "\n"
+        out = out[:-1]
+        if args.hits is not None:
+            with open(args.hits, "w") as fh:
+                fh.write(line)
+        else:
+            sys.stderr.write(line)
     if args.distmap is not None:
         save_distmap_npy(args.distmap, out[3])
     if args.compare is not None:

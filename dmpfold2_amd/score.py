@@ -62,39 +62,50 @@ def distmap_floats(L, on=True):
     return conf_floats(L, on)
 
 
-class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block", defaults=(None, None, None, None))):
+class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block",
+                         defaults=(None, None, None, None, None))):
     """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
-    score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,) - None for what is absent."""
+    score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
+    (26K + 2LK + 3M,) - None for what is absent."""
     __slots__ = ()
 
     @classmethod
-    def of(cls, public, distmap, score, align=False):
+    def of(cls, public, distmap, score, align=False, search=False):
         """The inverse of `public` for a caller that knows which options were on."""
         public = tuple(public)
         at = 4 if distmap else 2
         return cls(*public[:2], *(public[2:4] if distmap else (None, None)), public[at] if score else None,
-                   public[at + (1 if score else 0)] if align else None)
+                   public[at + (1 if score else 0)] if align else None,
+                   public[at + (1 if score else 0) + (1 if align else 0)] if search else None)
 
-    def public(self, distmap=True, score=True, align=True):
+    def public(self, distmap=True, score=True, align=True, search=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
-        block if present and wanted, then the align block if present and wanted."""
+        block, the align block and the search block, each if present and wanted."""
         return ((self.coords, self.confs) + ((self.distmap, self.info) if distmap and self.distmap is not None else ())
                 + ((self.score_block,) if score and self.score_block is not None else ())
-                + ((self.align_block,) if align and self.align_block is not None else ()))
+                + ((self.align_block,) if align and self.align_block is not None else ())
+                + ((self.search_block,) if search and self.search_block is not None else ()))
 
 
-def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None):
+def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None, search=None):
     """The parts of a `d_conf` buffer (a 1-D tensor or array of at least conf_floats(L, emit, score, align_m) floats) at the
-    offsets of include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through)."""
+    offsets of include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through).  `search`: (K, M, max_L) of
+    option "search_structures" - the search block then lies at search_offset(L, emit, score, align_m, max_L)."""
     L = int(L)
-    if buf.ndim != 1 or buf.shape[0] < conf_floats(L, emit, score, align_m):
-        raise ValueError(f"a d_conf buffer of length {L} has {conf_floats(L, emit, score, align_m)} floats, got shape {tuple(buf.shape)}")
+    need = conf_floats(L, emit, score, align_m)
+    b0 = None
+    if search is not None:
+        b0 = search_offset(L, emit, score, align_m, search[2])
+        need = max(need, b0 + search_floats(L, search[0], search[1]))
+    if buf.ndim != 1 or buf.shape[0] < need:
+        raise ValueError(f"a d_conf buffer of length {L} has {need} floats, got shape {tuple(buf.shape)}")
     s0 = score_offset(L, emit)
     a0 = align_offset(L, emit, score)
     return Outputs(coords, buf[:L], buf[L:L + L * L].reshape(L, L) if emit else None, buf[L + L * L:s0] if emit else None,
                    buf[s0:s0 + score_floats(L)] if score else None,
-                   buf[a0:a0 + align_floats(L, align_m)] if align_m is not None else None)
+                   buf[a0:a0 + align_floats(L, align_m)] if align_m is not None else None,
+                   buf[b0:b0 + search_floats(L, search[0], search[1])] if search is not None else None)
 
 
 def split_distmap_buffer(buf, L):
@@ -311,3 +322,173 @@ def alignment_json(al):
     out["t"] = [num(v) for v in np.asarray(al["t"])]
     out["ali"] = [int(v) for v in al["ali"]]
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# option "search_structures" (include/dmpfold_hip.h): the model aligned with each of the K structures of a library in one
+# prediction, and the ranking by tm_model.  Entry k's numbers are exactly what "align_structure" gives for that structure
+# alone - the same kind of search, the same lower bound, not compared with TM-align.
+# ---------------------------------------------------------------------------------------------------------------------
+SEARCH_MAX = 4096                    # DMP_SEARCH_MAX
+
+
+def search_floats(L, K, M):
+    """Floats of the search block of a prediction of length L searching K entries of M rows in all."""
+    L, K = int(L), int(K)
+    return (2 + ALIGN_HEADER) * K + 2 * L * K + 3 * int(M)
+
+
+def align_m_rule(m, max_L):
+    """m' of the rule for B0: the align block's m if that is an integer in [3, max_L], else 0 (None: no align block)."""
+    if m is None:
+        return 0
+    m = float(m)
+    return int(m) if m == m and 3 <= m <= int(max_L) and m == int(m) else 0
+
+
+def search_offset(L, distmap=False, score=False, align_m=None, max_L=None):
+    """Where the search block begins in the `d_conf` buffer (B0 of include/dmpfold_hip.h): the end of what the other options
+    give.  `align_m`: the m the align block holds (None = "align_structure" off); the library counts 3m of it only if it is
+    an integer in [3, `max_L`] (`max_L` None: whatever the block's writer allocated, i.e. any whole m >= 0 counts)."""
+    if align_m is None:
+        return conf_floats(L, distmap, score)
+    mp = int(align_m) if max_L is None else align_m_rule(align_m, max_L)
+    return conf_floats(L, distmap, score, mp)
+
+
+class Library:
+    """A fold library: names, lengths and one concatenated float32 C-alpha trace (M, 3), M = sum of the lengths."""
+
+    def __init__(self, names, lengths, ca):
+        self.names = [str(n) for n in names]
+        self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        self.ca = np.ascontiguousarray(np.asarray(ca, dtype=np.float32).reshape(-1, 3))
+        if len(self.names) != self.lengths.shape[0] or int(self.lengths.sum()) != self.ca.shape[0]:
+            raise ValueError(f"library: {len(self.names)} names, {self.lengths.shape[0]} lengths summing to "
+                             f"{int(self.lengths.sum())}, {self.ca.shape[0]} rows")
+        if not 1 <= len(self.names) <= SEARCH_MAX:
+            raise ValueError(f"library: {len(self.names)} entries; 1 to {SEARCH_MAX} can be searched")
+        self._device = {}                # device -> the packed inputs there (they do not depend on L)
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def rows(self):
+        return int(self.ca.shape[0])
+
+    @property
+    def max_m(self):
+        return int(self.lengths.max())
+
+    def entry(self, k):
+        """Entry k's trace (m_k, 3)."""
+        o = int(self.lengths[:k].sum())
+        return self.ca[o:o + int(self.lengths[k])]
+
+    def check(self, capacity):
+        """Raises ValueError naming the first entry with fewer than 3 rows or more than `capacity`."""
+        for name, m in zip(self.names, self.lengths):
+            if m < 3 or m > int(capacity):
+                raise ValueError(f"library entry {name}: {int(m)} C-alpha atoms; 3 to {int(capacity)} can be aligned")
+
+    @classmethod
+    def from_traces(cls, traces, names=None):
+        traces = [as_structure(t) for t in traces]
+        names = [f"entry{k}" for k in range(len(traces))] if names is None else names
+        return cls(names, [t.shape[0] for t in traces], np.concatenate(traces) if traces else np.zeros((0, 3), np.float32))
+
+    @classmethod
+    def from_dir(cls, path):
+        """Every *.pdb of a directory (first chain; read_native_ca), names = the stems, in sorted order."""
+        import glob
+        import os
+        files = sorted(glob.glob(os.path.join(path, "*.pdb")))
+        if not files:
+            raise ValueError(f"{path}: no *.pdb files")
+        return cls.from_traces([read_native_ca(f)[0] for f in files], [os.path.splitext(os.path.basename(f))[0] for f in files])
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls([str(n) for n in z["names"]], z["lengths"], z["ca"])
+
+    @classmethod
+    def open(cls, path):
+        """A directory of PDB files or an .npz written by `save`."""
+        import os
+        return cls.from_dir(path) if os.path.isdir(path) else cls.load(path)
+
+    def save(self, path):
+        with open(path, "wb") as fh:
+            np.savez(fh, names=np.asarray(self.names, dtype=np.str_), lengths=self.lengths, ca=self.ca)
+
+    def device_inputs(self, device):
+        """(lengths as float32 (K,), traces (3M,)) on `device`: uploaded once per device, kept on the library."""
+        import torch
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = (torch.from_numpy(self.lengths.astype(np.float32)).to(device),
+                                 torch.from_numpy(self.ca.reshape(-1)).to(device))
+        return self._device[key]
+
+    def fill_block(self, block, L):
+        """The inputs of a search block on the GPU (a tensor of search_floats(L, K, M)) filled device to device, NaN elsewhere."""
+        lens, ca = self.device_inputs(block.device)
+        K = len(self)
+        block[:K].copy_(lens)
+        block[K:block.shape[0] - ca.shape[0]].fill_(float("nan"))
+        block[block.shape[0] - ca.shape[0]:].copy_(ca)
+
+
+def pack_library(library, L, lengths=None):
+    """The search block (float32 (26K + 2LK + 3M,)) with its inputs filled in - the lengths in front, the traces at the end -
+    and NaN in the out slots.  `lengths`: what to write as the m_k instead (tests of the library's validation)."""
+    K, L = len(library), int(L)
+    block = np.full(search_floats(L, K, library.rows), np.nan, dtype=np.float32)
+    block[:K] = library.lengths if lengths is None else np.asarray(lengths, dtype=np.float32)
+    block[block.shape[0] - 3 * library.rows:] = library.ca.reshape(-1)
+    return block
+
+
+def unpack_search(block, L, lengths):
+    """A search block (array or tensor) of a library with these `lengths` -> dict: hits, a list of K dicts in the shape
+    `unpack_alignment` gives (m, structure and all), and rank (K,) int - the entries by falling tm_model, ties to the lower
+    index, NaN last.  A block the library answered with NaN in rank (a latched fault) gives rank 0 .. K-1."""
+    L = int(L)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    K, M = lengths.shape[0], int(lengths.sum())
+    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    if b.ndim != 1 or b.shape[0] != search_floats(L, K, M):
+        raise ValueError(f"a search block of length {L}, {K} entries, {M} rows has {search_floats(L, K, M)} floats, got shape {tuple(b.shape)}")
+    hdr, res, tr = 2 * K, (2 + ALIGN_HEADER) * K, (2 + ALIGN_HEADER) * K + 2 * L * K
+    hits, o = [], 0
+    for k in range(K):
+        m = int(lengths[k])
+        one = np.concatenate([b[k:k + 1], b[hdr + ALIGN_HEADER * k:hdr + ALIGN_HEADER * (k + 1)], b[res + 2 * L * k:res + 2 * L * (k + 1)],
+                              b[tr + 3 * o:tr + 3 * (o + m)]])
+        hits.append(unpack_alignment(one, L))
+        o += m
+    rank = b[K:2 * K]
+    return {"hits": hits, "rank": rank.astype(np.int64) if np.all(rank == rank) else np.arange(K, dtype=np.int64)}
+
+
+def host_rank(tm):
+    """The ranking rule on the host: by falling value, ties to the lower index, NaN last in index order."""
+    tm = np.asarray(tm, dtype=np.float32)
+    return np.asarray(sorted(range(len(tm)), key=lambda k: (tm[k] != tm[k], -float(tm[k]) if tm[k] == tm[k] else 0.0, k)), dtype=np.int64)
+
+
+def hits_json(search, names, top=10):
+    """`unpack_search` as a JSON-ready dict (what `dmpfold --search` prints and `dmpfold-batch --library` writes): the best
+    `top` entries in rank order, each with name, tm_model, tm_struct, rmsd_ali, n_ali, R, t; NaN becomes None."""
+    def num(v):
+        v = float(v)
+        return v if v == v else None
+    out = []
+    for k in [int(k) for k in search["rank"][:max(int(top), 0)]]:
+        h = search["hits"][k]
+        out.append({"name": str(names[k]), "index": k, "tm_model": num(h["tm_model"]), "tm_struct": num(h["tm_struct"]),
+                    "rmsd_ali": num(h["rmsd_ali"]), "n_ali": int(h["n_ali"]),
+                    "R": [[num(v) for v in row] for row in np.asarray(h["R"])], "t": [num(v) for v in np.asarray(h["t"])]})
+    return {"entries": len(names), "hits": out}

@@ -79,6 +79,10 @@ const char* dmp_last_error(void);
  * alignment's length before anything is computed.  The largest configuration of BASELINE.json (L = 1000) needs
  * 8.5 GB of the 288; L = 2048 with 3000 rows about 60 GB. */
 #define DMP_MAX_L 2048
+/* option "search_structures" (dmp_ctx_set_option): the most entries one prediction searches, and the scratch budget in
+ * MiB that decides how many of them are in flight at a time */
+#define DMP_SEARCH_MAX 4096
+#define DMP_SEARCH_BUDGET_MIB 256
 int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out);
 void dmp_ctx_destroy(dmp_ctx* ctx);
 /* (device memory held by the context: option "device_mib" of dmp_ctx_get_option, read only) */
@@ -290,7 +294,51 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * offset, L + max_L + 1 launched; align_refine - 16 workgroups of 256 threads, the programme as an anti-diagonal wavefront:
  * three rotating diagonals of H and D in LDS, one barrier per diagonal, s_ij formed on the fly, the traceback serial).
  * A context holds, ALLOCATED AT ITS CREATION and counted in "device_mib", 16 (max_L + 1)^2 bytes for the directions (one
- * byte per cell and workgroup; 64 MiB at max_L = 2048), 16 alignments of 2 max_L ints and 2 max_L + 1 seed records. */
+ * byte per cell and workgroup; 64 MiB at max_L = 2048), 16 alignments of 2 max_L ints and 2 max_L + 1 seed records.
+ * "search_structures" (0, the default, or K = 1 .. DMP_SEARCH_MAX = 4096; any other value: DMP_ERR_ARG): align the model with
+ * each of the K structures of a library in the one call, and rank them - fold recognition with the prediction that is
+ * already on the device.  Read when a prediction begins and held for it.  With it 0 nothing is launched, read or written, and
+ * every output is bit for bit what it is without the option.  THE RESULT FOR ENTRY k IS DEFINED AS EXACTLY WHAT
+ * "align_structure" RETURNS FOR THAT STRUCTURE ALONE: the definition above is the only one, and the same device functions
+ * evaluate it (csrc/align.hip), so the floats are equal bit for bit.  The coordinates, the confidences and the blocks of the
+ * other options do not change by a bit.
+ * "search_max_m" (0, the default = the context's max_L, or 3 .. max_L; anything else: DMP_ERR_ARG): the caller's bound on
+ * every entry's length.  The library sizes its scratch slots, its launches and the LDS of align_refine from (L,
+ * search_max_m) on the host; it never reads a length back from the device, and dmp_predict_end stays asynchronous.
+ * "search_chunk" (TESTS ONLY; n >= 0, default 0): at most n entries per chunk when n > 0 (see below).
+ * WITH K > 0 THE d_conf ARGUMENT MUST HOLD THE SEARCH BLOCK AT B0 = THE END OF WHAT THE OTHER OPTIONS GIVE: A0 (above)
+ * without "align_structure"; with it B0 = A0 + 25 + 2L + 3m', m' = the align block's m if that is an integer in [3, max_L],
+ * else 0 (search_prep forms B0 on the device by this rule; a host layer that knows m uses the same).  THE CALLER WRITES ITS
+ * TWO INPUTS BEFORE THE CALL.  Every output lies at an offset that depends on K and L only; the variable-length input comes
+ * last.  Offsets relative to B0, M = the sum of the m_k:
+ *   [0, K)                        in   m_k, the rows of entry k, as floats
+ *   [K, 2K)                       out  rank[r]: the index of the entry with the r-th largest tm_model
+ *   [2K, 26K)                     out  entry k's header at 2K + 24k: the 24 floats an align block holds at offsets 1 .. 24
+ *   [26K, 26K + 2LK)              out  entry k's ali[L] then deviation[L] at 26K + 2Lk, as offsets 25 .. 25 + 2L of an align block
+ *   [26K + 2LK, .. + 3M)          in   the entries' C-alpha traces, entry after entry, (x, y, z) per row
+ * Ranking: by falling tm_model (the float32 value of the header), ties to the lower index; entries whose tm_model is NaN
+ * come last, in index order.  The ranks are floats, exact below 2^24.
+ * If any m_k is not an integer in [3, search_max_m], nothing beyond [0, K) is read, every out slot behind the ranks is NaN,
+ * rank is 0 .. K-1, and there is no fault.  A NaN among entry k's coordinates makes that entry's 24 + 2L floats NaN and no
+ * other's (it is ranked last).  A prediction that latched a device-side fault returns NaN in every out slot, the ranks
+ * included (search_rank reads the fault word; the latch kernel does not know B0); the inputs are left alone.
+ * Launches with the option on, all on the prediction's stream, behind "align_structure": search_prep (one workgroup: the m_k
+ * validated, the prefix sums of the trace offsets, B0, NaN into every out slot), then per CHUNK of C consecutive entries
+ * align_prep (1 x c workgroups), align_thread (L + search_max_m + 1 by c) and align_refine (16 by c; c = the chunk's entries,
+ * the entry is blockIdx.y), then search_rank (one workgroup: rank by counting, order-free): 2 + 3 ceil(K / C) launches.
+ * A SLOT holds one entry's working set, every part rounded up to 16 bytes: 16 (L + 1)(search_max_m + 1) bytes of
+ * directions, L + search_max_m + 1 seed records of 8 bytes, 16 candidate alignments of 1 + 2L ints, both traces (12 L and
+ * 12 search_max_m bytes) and 272 bytes of header, survivors and their scores.  C = clamp(DMP_SEARCH_BUDGET_MIB (256 MiB) /
+ * slot, 1, 256); "search_chunk" lowers it.  Chunk boundaries do not change a bit of any output.  align_refine's dynamic LDS
+ * is sized from search_max_m in these launches (24 (L + 1) + max(25 L, 12 search_max_m + 3 (L + 1)) + 12 L bytes: 17.9 KB at
+ * L = 300, search_max_m = 500, against 35.5 KB with search_max_m = 2048), so that several workgroups share a CU.
+ * THE SCRATCH - the largest chunk over every L <= max_L at this search_max_m, 34 KB of table and tickets in front - IS
+ * ALLOCATED WHEN "search_structures" FIRST BECOMES POSITIVE ON A CONTEXT (again, larger, if "search_max_m" grows later) and
+ * counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the option as it was.  Nothing
+ * is allocated for a context that never turns the option on.  Read-only, of the last prediction that searched:
+ * "search_chunk_used" (C) and "search_wg_per_cu" (resident align_refine workgroups per CU at that shape).
+ * THIS IS TM-ALIGN'S KIND OF SEARCH, a lower bound of the best TM-score per entry, not compared with that program
+ * (see "align_structure").  Measured cost: profiles/search.txt. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
@@ -465,7 +513,7 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
  * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN INTO THEM
  * (layout: dmp_ctx_set_option); WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m AND THE STRUCTURE'S
- * TRACE WRITTEN INTO THEM. */
+ * TRACE WRITTEN INTO THEM; WITH OPTION "search_structures" = K THE SEARCH BLOCK (26K + 2LK + 3M FLOATS) BEHIND ALL OF THEM. */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
                 int Lt, int nloops, int refine_steps, float* d_coords, float* d_conf,
                 void* stream);
@@ -522,7 +570,8 @@ int dmp_predict_set_vgru_result(dmp_ctx* ctx, const float* d_vout, void* event);
  * d_conf (L); a prediction during which a device-side fault was recorded returns NaN.
  * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * IF IT BEGAN WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE; the native trace and lnorm are read
- * from them here; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m and the structure's trace read here. */
+ * from them here; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m and the structure's trace read here;
+ * WITH OPTION "search_structures" = K the search block behind all of them, the m_k and the traces read here. */
 int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream);
 int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream);
 int dmp_ctx_pending(dmp_ctx* ctx);
@@ -582,7 +631,8 @@ int dmp_pipeline_set_option(dmp_pipeline* p, const char* name, int value);
 /* d_coords: L x 5 x 3 floats, d_conf: L floats.  WITH OPTION "emit_distmap" = 1 ON THE PIPELINE d_conf MUST HOLD
  * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run.
  * WITH OPTION "score_native" = 1 ON THE PIPELINE d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN
- * INTO THEM BEFORE ready_event; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, LIKEWISE. */
+ * INTO THEM BEFORE ready_event; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, LIKEWISE;
+ * WITH OPTION "search_structures" = K THE SEARCH BLOCK BEHIND ALL OF THEM, LIKEWISE. */
 int64_t dmp_pipeline_submit(dmp_pipeline* p, const uint8_t* d_msa, int N, int L, const float* d_template_ca, int nloops,
                             int refine_steps, float* d_coords, float* d_conf, void* ready_event);
 int dmp_pipeline_wait(dmp_pipeline* p, int what);
