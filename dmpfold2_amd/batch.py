@@ -145,7 +145,7 @@ def ca_only_text(coords, confs, alnmat):
 
 
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
-                 hits=None, hits_top=10):
+                 hits=None, hits_top=10, map_scores=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
@@ -154,7 +154,11 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     --structures): npz gains the header fields of score.ALIGN_NAMES, ali, ali_R, ali_t and ali_deviation; pdb / ca get
     <stem>.alignment.json (the line `dmpfold --compare` prints).  With `hits` (the dict of Engine.hits: hits, rank, names;
     --library): npz gains hit_rank, hit_tm_model, hit_tm_struct (per entry, in the library's order) and hit_names; pdb / ca get
-    <stem>.hits.json (the line `dmpfold --search` prints, the best `hits_top`)."""
+    <stem>.hits.json (the line `dmpfold --search` prints, the best `hits_top`).  With `map_scores` (the dict of
+    score.unpack_map_scores, --natives --score-map; only beside `scores`): npz gains map_n, map_ln, map_pairs, map_lddt,
+    map_mae, map_rmse, map_bias, map_lddt_res and map_counts (int32 (4, 10): per class short, medium, long, medium + long the
+    candidates, native contacts, hits and taken of the lists L, L/2, L/5, true positives and predicted contacts at 8 A);
+    <stem>.scores.json gains the key "map"."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -168,6 +172,14 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
                           "counts": np.asarray(scores["counts"], dtype=np.int32)})
             extra.update({k: np.float32(scores[k]) for k in _score.SCORE_NAMES[1:]})
             extra.update({k: np.asarray(scores[k], dtype=np.float32) for k in ("R", "t", "lddt_res", "deviation")})
+        if map_scores is not None:
+            extra.update({"map_n": np.int32(map_scores["n"]), "map_ln": np.float32(map_scores["ln"]),
+                          "map_pairs": np.int32(map_scores["pairs"]),
+                          "map_lddt_res": np.asarray(map_scores["map_lddt_res"], dtype=np.float32),
+                          "map_counts": np.asarray([[cl["candidates"], cl["native_contacts"]] + cl["hits"] + cl["taken"]
+                                                    + [cl["tp"], cl["predicted"]]
+                                                    for cl in (map_scores["classes"][c] for c in _score.MAP_CLASSES)], dtype=np.int32)})
+            extra.update({k: np.float32(map_scores[k]) for k in _score.MAP_NAMES})
         if alignment is not None:
             extra.update({k: (np.int32 if k in ("n_ali", "seed_offset", "seeds") else np.float32)(alignment[k])
                           for k in _score.ALIGN_NAMES})
@@ -186,7 +198,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
         save_distmap_npy(stem + ".distmap.npy", distmap)
     if scores is not None:
         with open(stem + ".scores.json", "w") as fh:
-            fh.write(json.dumps(_score.scores_json(scores)) + "\n")
+            js = _score.scores_json(scores)
+            if map_scores is not None:
+                js["map"] = _score.map_scores_json(map_scores)
+            fh.write(json.dumps(js) + "\n")
     if alignment is not None:
         with open(stem + ".alignment.json", "w") as fh:
             fh.write(json.dumps(_score.alignment_json(alignment)) + "\n")
@@ -241,11 +256,14 @@ def cost_order(targets, iterations):
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
-              converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10):
+              converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10,
+              score_map=False):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
     unscored.  `stats_out` then receives "scores": {stem: the dict of score.scores_json}.
+    `score_map` (needs `natives`): a scored target's predicted distance map is scored against its native too
+    (Pipeline.set_score_map); its scores gain the key "map" (score.map_scores_json) wherever they are written.
     `structures`: a directory of structures of any length and sequence, <stem>.pdb for the target <stem>.aln / .a3m: such a
     target's model is aligned with the structure's first chain on the GPU (Pipeline.set_align) and the alignment is written
     with it (write_result); a target without a file is predicted without one.  `stats_out` then receives "alignments":
@@ -264,6 +282,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     written as they complete), and a failing target never costs the others their results."""
     if fmt not in ("pdb", "ca", "npz"):
         raise ValueError(f"unknown output format {fmt!r} (pdb, ca, npz)")
+    if score_map and not natives:
+        raise ValueError("score_map scores the distance maps against native structures: give `natives`")
     check_output_stems(targets)
     os.makedirs(out_dir, exist_ok=True)
     # sharding needs only (L, N) estimates from a header scan: a rank parses its own targets and nobody else's
@@ -320,6 +340,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_distmap(True)
             if natives:
                 pipe.set_score(True)
+            if score_map:
+                pipe.set_score_map(True)          # (turns the distance map on: it is written only with `distmap`)
             if structures:
                 pipe.set_align(True)
             if library is not None:
@@ -361,12 +383,16 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        out = Outputs.of(public, distmap, bool(natives), bool(structures), library is not None)
+        out = Outputs.of(public, distmap or score_map, bool(natives), bool(structures), library is not None, score_map)
         aln_path, alnmat, _ = parsed.pop(t)
-        sc = None
+        sc = ms = None
         if out.score_block is not None and t in scored:
             sc = _score.unpack_scores(out.score_block, alnmat.shape[1])
-            all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = _score.scores_json(sc)
+            js = _score.scores_json(sc)
+            if out.map_block is not None:
+                ms = _score.unpack_map_scores(out.map_block, alnmat.shape[1])
+                js["map"] = _score.map_scores_json(ms)
+            all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = js
         al = None
         if out.align_block is not None and t in aligned:
             al = _score.unpack_alignment(out.align_block, alnmat.shape[1])
@@ -377,8 +403,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             hits = dict(_score.unpack_search(out.search_block, alnmat.shape[1], library.lengths), names=list(library.names))
             all_hits[os.path.splitext(os.path.basename(aln_path))[0]] = [
                 {k: v for k, v in h.items() if k not in ("R", "t")} for h in _score.hits_json(hits, library.names, search_top)["hits"]]
-        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap, out.info, sc, al, hits,
-                                    search_top))
+        outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap if distmap else None,
+                                    out.info if distmap else None, sc, al, hits, search_top, ms))
 
     def finish(item):
         t, public = item
@@ -525,6 +551,11 @@ def batch_parser():
                     help="directory of native structures, <stem>.pdb per target: such targets are scored on the GPU (TM-score, "
                          "GDT, RMSD, lDDT-CA); the summary gains the per-target scores, their means and medians; npz gains the "
                          "arrays, pdb / ca write <stem>.scores.json; a target without a file is predicted unscored")
+    ap.add_argument("--score-map", action="store_true",
+                    help="with --natives: also score every such target's predicted distance map against its native on the GPU "
+                         "(contact precision of the top L, L/2, L/5 per separation class, lDDT and distance error of the map); "
+                         "the summary's scores gain the key \"map\" with means and medians of its figures, npz gains the map_* "
+                         "arrays, <stem>.scores.json gains \"map\"")
     ap.add_argument("--structures", default=None, metavar="DIR",
                     help="directory of structures of any length and sequence, <stem>.pdb per target: such a target's model is "
                          "aligned with the structure's first chain on the GPU (structural alignment, TM-scores by both lengths); "
@@ -547,6 +578,13 @@ def score_summary(scores):
         vals = [s[name] for s in scores.values() if s.get(name) is not None]
         out["mean_" + name] = float(np.mean(vals)) if vals else None
         out["median_" + name] = float(np.median(vals)) if vals else None
+    flat = {stem: _score.map_scores_flat(s["map"]) for stem, s in scores.items() if s.get("map") is not None}
+    if flat:                                         # --score-map: the map's figures the same way
+        out["map_scored_targets"] = len(flat)
+        for name in next(iter(flat.values())):
+            vals = [f[name] for f in flat.values() if f.get(name) is not None]
+            out["mean_" + name] = float(np.mean(vals)) if vals else None
+            out["median_" + name] = float(np.median(vals)) if vals else None
     return out
 
 
@@ -555,6 +593,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not args.list and not args.input:
         ap.error("give -l targets.txt and / or -i alignments ...")
+    if args.score_map and not args.natives:
+        ap.error("--score-map scores the distance maps against native structures: give --natives DIR")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -578,7 +618,8 @@ def main(argv=None):
                                   weights_file=args.model_weights, streams=args.streams,
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
-                                  structures=args.structures, library=args.library, search_top=args.search_top)
+                                  structures=args.structures, library=args.library, search_top=args.search_top,
+                                  score_map=args.score_map)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)

@@ -407,9 +407,11 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // the fault bits are latched into the word dmp_sync_faults reports.
 // `lay`: the d_conf buffer of this prediction (common.h) - the confidences and, with option "emit_distmap", the whole extension
 // become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
-// caller's and stay.  The same for the align block of option "align_structure": its out slots become NaN, m in front of them and
-// the structure's trace behind them (past lay.total) stay.  (The search block of option "search_structures" lies at an offset only
-// the device knows: search_rank, the launch in front of this one, reads the same word and does the same there.)
+// caller's and stay.  The map-score block of option "score_map" lies between the score block's end (lay.smap_off) and
+// lay.align_off and is all outputs: the range [lay.score_out, lay.align_off) below takes it in.  The same for the align block
+// of option "align_structure": its out slots become NaN, m in front of them and the structure's trace behind them (past
+// lay.total) stay.  (The search block of option "search_structures" lies at an offset only the device knows: search_rank,
+// the launch in front of this one, reads the same word and does the same there.)
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
                                    float* __restrict__ conf, int L, ConfLayout lay, int* __restrict__ report) {
   const int f = words[0];
@@ -558,6 +560,10 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(score_rec, 6 * L * SCORE_REC);
   A_(score_tot, 2);
   A_(score_ticket, 1);
+  A_(map_cnt, 14);
+  A_(map_partial, 3 * 64);
+  A_(map_sums, 3);
+  A_(map_ticket, 3);
   A_(align_pm, 3 * L);
   A_(align_qs, 3 * L);
   A_(align_hdr, 8);
@@ -574,6 +580,8 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   if (hipMemset(c->rms_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->score_ticket, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->align_ticket, 0, 2 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  if (hipMemset(c->map_cnt, 0, 14 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
+  if (hipMemset(c->map_ticket, 0, 3 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   // the word recycle_delta tells the host its stop decision through (read only after the pass tail's event)
   if (hipHostMalloc((void**)&c->delta_host, sizeof(int), hipHostMallocMapped) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   *c->delta_host = 0;
@@ -649,6 +657,11 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->opt.score = value;
     return DMP_OK;
   }
+  if (k == "score_map") {            // takes effect with the next prediction begun, which needs the two options it reads from
+    DMP_ARG(value == 0 || value == 1, "score_map must be 0 or 1, got %d", value);
+    ctx->opt.smap = value;
+    return DMP_OK;
+  }
   if (k == "align_structure") {      // takes effect with the next prediction begun
     DMP_ARG(value == 0 || value == 1, "align_structure must be 0 or 1, got %d", value);
     ctx->opt.align = value;
@@ -719,6 +732,7 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "recycle_tol_mA") { *h_value = ctx->opt.tol_mA; return DMP_OK; }
   if (k == "emit_distmap") { *h_value = ctx->opt.emit; return DMP_OK; }
   if (k == "score_native") { *h_value = ctx->opt.score; return DMP_OK; }
+  if (k == "score_map") { *h_value = ctx->opt.smap; return DMP_OK; }
   if (k == "align_structure") { *h_value = ctx->opt.align; return DMP_OK; }
   if (k == "search_structures") { *h_value = ctx->opt.search; return DMP_OK; }
   if (k == "search_max_m") { *h_value = ctx->opt.search_mm; return DMP_OK; }
@@ -1280,6 +1294,8 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   DMP_ARG(d_template_ca == nullptr || Lt == L,
           "template has %d CA atoms but the alignment has %d columns", Lt, L);
   dmp_ctx* c = ctx;
+  DMP_ARG(!c->opt.smap || c->opt.emit, "score_map scores the map of option emit_distmap, which is 0: set emit_distmap to 1");
+  DMP_ARG(!c->opt.smap || c->opt.score, "score_map reads the native trace of option score_native, which is 0: set score_native to 1");
   DMP_ARG(c->vg_waiters == 0, "members of the vertical-GRU group this context led have not taken their results yet");
   DMP_ARG(c->vg_leader == nullptr || c->vg_leader == c, "this context still waits for the vertical GRU of its group");
   c->vg_leader = nullptr;
@@ -1491,11 +1507,13 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // (tools/isa_lint.py).
   rc = ca_to_backbone(c->best_ca, c->best_conf, L, d_coords, d_conf, s);
   if (rc) return rc;
-  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align);
+  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align, c->run.smap);
   // option "emit_distmap": the map and {best_pass, passes_run, map_rms} behind the confidences
   if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map_off, d_conf + lay.info_off, s))) return rc;
   // option "score_native": the score block behind that, the native trace and lnorm in it (score.hip)
   if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score_off, s))) return rc;
+  // option "score_map": the map-score block behind that, from best_dm and the score block's inputs (mapscore.hip)
+  if (c->run.smap && (rc = score_map(c, L, d_conf + lay.score_off, d_conf + lay.smap_off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align_off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

@@ -68,13 +68,20 @@ __host__ __device__ inline ScoreLayout score_layout(int L) {
 constexpr int ALIGN_HEADER = 24;
 struct AlignLayout { int ali, deviation, in; };                         // in: the first float of the structure's trace
 __host__ __device__ inline AlignLayout align_layout(int L) { return {1 + ALIGN_HEADER, 1 + ALIGN_HEADER + L, 1 + ALIGN_HEADER + 2 * L}; }
-// score_off: the end of what "emit_distmap" gives; align_off: the end of the score block; align_out / total: the align
-// block's out slots (total does not count its trailing input, whose length only the caller knows)
-struct ConfLayout { int64_t map_off, info_off, score_off, score_out, align_off, align_out, total; };
-__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0) {
+//   | with "score_map": the map-score block = MAPSCORE_HEADER floats | map_lddt_res [L], all of it out, between the score block
+//   and the align block.
+constexpr int MAPSCORE_HEADER = 64;
+__host__ __device__ inline int mapscore_floats(int L) { return MAPSCORE_HEADER + L; }
+// score_off: the end of what "emit_distmap" gives; smap_off: the end of the score block; align_off: the end of the map-score
+// block; align_out / total: the align block's out slots (total does not count its trailing input, whose length only the
+// caller knows)
+struct ConfLayout { int64_t map_off, info_off, score_off, score_out, smap_off, align_off, align_out, total; };
+__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0, int smap = 0) {
   const int64_t info_off = L + (emit ? (int64_t)L * L : 0), score_off = info_off + (emit ? 3 : 0);
-  const int64_t align_off = score_off + (score ? score_layout(L).total : 0);
-  return {L, info_off, score_off, score_off + score_layout(L).out, align_off, align_off + 1, align_off + (align ? align_layout(L).in : 0)};
+  const int64_t smap_off = score_off + (score ? score_layout(L).total : 0);
+  const int64_t align_off = smap_off + (smap ? mapscore_floats(L) : 0);
+  return {L, info_off, score_off, score_off + score_layout(L).out, smap_off, align_off, align_off + 1,
+          align_off + (align ? align_layout(L).in : 0)};
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -192,8 +199,9 @@ struct dmp_lane {
   long long count = 0;     // conv launches recorded so far (event of launch i: ev[i % RING])
 };
 
-// options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0; };
+// options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
+// "score_map"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0; };
 
 struct dmp_ctx {
   int device = 0;
@@ -331,6 +339,11 @@ struct dmp_ctx {
   double* score_rec = nullptr;     // [6 max_L][SCORE_REC] one record per seed of the superposition search
   unsigned long long* score_tot = nullptr;   // [2] lDDT: preserved, pairs
   unsigned* score_ticket = nullptr;          // zero between launches
+  // option "score_map": the chosen pass's distance map scored against the native trace (mapscore.hip); 1.7 KB
+  unsigned* map_cnt = nullptr;     // [14] integer counts, zero between launches
+  double* map_partial = nullptr;   // [3][64] per-workgroup error sums
+  double* map_sums = nullptr;      // [3] their totals
+  unsigned* map_ticket = nullptr;  // [3] zero between launches
   // option "align_structure": the model aligned with a structure of any length in the d_conf buffer (align.hip); allocated
   // with the context
   float* align_pm = nullptr;       // [max_L][3] model trace
@@ -623,6 +636,8 @@ int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
 int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_map, float* d_info, hipStream_t s);
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
+// option "score_map" (mapscore.hip): best_dm against the native trace of the score block, into the map-score block
+int score_map(dmp_ctx* c, int L, const float* d_score_block, float* d_block, hipStream_t s);
 constexpr int ALIGN_SURVIVORS = 16; // seeds of the gapless threading that the dynamic programme refines (align.hip)
 int align_kernel_attrs(dmp_ctx* c);   // once per device, at context creation
 int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);

@@ -229,14 +229,16 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=False, structure=None, library=None, max_L=None):
+def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=False, structure=None, library=None, max_L=None,
+           score_map=False):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is sized for the options as the context holds them - the library cannot check
     it, writes L + L*L + 3 floats with "emit_distmap" on (`emit_alloc`: sized as if it were) and reads and writes 5L + 24
     more behind them with "score_native" on: the native trace goes there (no `native` = no row present: n_pairs 0, NaN scores);
     with "align_structure" on (`align`) 25 + 2L + 3m more behind those, m and the rows of `structure` in them (no `structure`:
     m = 0, which the library answers with NaN); with "search_structures" on (`library`, a score.Library; `max_L`: the
-    context's, for the rule of B0) the search block behind those, filled from the library's copy on the GPU."""
+    context's, for the rule of B0) the search block behind those, filled from the library's copy on the GPU; with "score_map"
+    on (`score_map`) 64 + L floats, all outputs, between the score block and the align block."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -250,11 +252,11 @@ def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=F
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     alloc = emit if emit_alloc is None else emit_alloc
     search = None if library is None else (len(library), library.rows, max_L)
-    floats = _score.conf_floats(L, alloc, score, align_m)
+    floats = _score.conf_floats(L, alloc, score, align_m, score_map)
     if search is not None:
-        floats = max(floats, _score.search_offset(L, alloc, score, align_m, max_L) + _score.search_floats(L, *search[:2]))
+        floats = max(floats, _score.search_offset(L, alloc, score, align_m, max_L, score_map) + _score.search_floats(L, *search[:2]))
     buf = torch.empty((floats,), dtype=torch.float32, device=device)
-    out = split_conf_buffer(buf, L, emit, score, coords, align_m, search)
+    out = split_conf_buffer(buf, L, emit, score, coords, align_m, search, score_map)
     if search is not None:
         library.fill_block(out.search_block, L)
     if align:
@@ -283,6 +285,7 @@ class Engine:
         self._score = None             # (score block, L) of the last prediction
         self._align = None             # (align block, L) of the last prediction
         self._search = None            # (search block, L, library) of the last prediction
+        self._map = None               # (map-score block, L) of the last prediction
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
@@ -331,8 +334,13 @@ class Engine:
         self.weights_tag = other.weights_tag
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
-                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
+                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
+                score_map=False):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `score_map` (needs `native`): the chosen pass's predicted distance map is scored against the native too (option
+        "score_map", set for this call only together with "emit_distmap" and "score_native"): contact precision of the top
+        L, L/2 and L/5 per separation class and the map's own distance agreement; what the call returns does not change,
+        the result is in `map_scores`.
         `library` (a score.Library of K structures, each 3 .. max_L rows): the final trace is aligned with every one of them on
         the GPU (option "search_structures", set for this call only, "search_max_m" = the longest entry); what the call
         returns does not change, the results and the ranking are in `hits`.
@@ -355,7 +363,23 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library)
+        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library,
+                                   score_map)
+
+    @property
+    def map_scores(self):
+        """The map scores of the last prediction as score.unpack_map_scores gives them, None if it ran without option
+        "score_map".  Synchronises with the GPU."""
+        if self._map is None:
+            return None
+        block, L = self._map
+        torch.cuda.synchronize(self.device)
+        return _score.unpack_map_scores(block, L)
+
+    @property
+    def map_score_block(self):
+        """The last prediction's map-score block on the GPU (64 + L floats, a view of the buffer handed to the library), or None."""
+        return None if self._map is None else self._map[0]
 
     @property
     def hits(self):
@@ -408,20 +432,25 @@ class Engine:
         return self.get_option("passes_run")
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
-                       minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
+                       minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
+                       score_map=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        with self._call_options(converge, distmap, native, structure, library):
+        with self._call_options(converge, distmap, native, structure, library, score_map):
             return self._run(d_msa, template_ca, iterations, minsteps, native, structure,
-                             library).public(distmap, score=False, align=False, search=False)
+                             library).public(distmap, score=False, align=False, search=False, score_map=False)
 
     @contextlib.contextmanager
-    def _call_options(self, converge, distmap, native, structure=None, library=None):
+    def _call_options(self, converge, distmap, native, structure=None, library=None, score_map=False):
         """The options one call asks for - read when the prediction begins - set for its duration, then as they were.
         `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" / "align_structure" set by hand
         stay set."""
         want = {} if converge is None else {"recycle_tol_mA": converge_to_mA(converge)}    # (raises before anything changes)
-        if distmap and not self.get_option("emit_distmap"):
+        if score_map and native is None and not self.get_option("score_native"):
+            raise ValueError("score_map scores the distance map against a native structure: give `native`")
+        if (distmap or score_map) and not self.get_option("emit_distmap"):
             want["emit_distmap"] = 1
+        if score_map and not self.get_option("score_map"):
+            want["score_map"] = 1                         # (the library looks at the three together when the prediction begins)
         if native is not None and not self.get_option("score_native"):
             want["score_native"] = 1
         if structure is not None and not self.get_option("align_structure"):
@@ -447,6 +476,7 @@ class Engine:
         align = bool(self.get_option("align_structure"))
         if align and structure is not None and _score.as_structure(structure).shape[0] > self.max_L:
             raise RuntimeError(f"structure has {len(structure)} rows; the engine's capacity is {self.max_L} (max_L)")
+        smap = bool(self.get_option("score_map"))
         search = self.get_option("search_structures")
         if search:
             if library is None or len(library) != search:
@@ -459,9 +489,11 @@ class Engine:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         with torch.cuda.device(self.device):
-            self._score = self._align = self._search = None
+            self._score = self._align = self._search = self._map = None
             d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, align=align, structure=structure,
-                                library=library if search else None, max_L=self.max_L)
+                                library=library if search else None, max_L=self.max_L, score_map=smap and emit and score)
+            if out.map_block is not None:
+                self._map = (out.map_block, L)
             if search:
                 self._search = (out.search_block, L, library)
             if score:
@@ -508,7 +540,8 @@ class Engine:
         raise_for_faults(self.sync_faults())
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
-                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
+                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
+                        score_map=False):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
@@ -516,19 +549,22 @@ class Engine:
         alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
         with torch.cuda.device(self.device):
             d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library)
+        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library,
+                                           score_map)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
-                               minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None):
-        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`: see
-        `predict`; a repeat of the prediction returns the repeat's map, scores, alignment and hits)."""
+                               minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
+                               score_map=False):
+        """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
+        `score_map`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment and hits)."""
         return self._checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native,
-                             structure, library).public(distmap, score=False, align=False, search=False)
+                             structure, library, score_map).public(distmap, score=False, align=False, search=False, score_map=False)
 
-    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure=None, library=None):
+    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure=None, library=None,
+                 score_map=False):
         """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry `native` and
         `structure` along."""
-        with self._call_options(converge, distmap, native, structure, library):
+        with self._call_options(converge, distmap, native, structure, library, score_map):
             out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
             bits = self.sync_faults()
             self.last_fallback = False
@@ -576,6 +612,7 @@ class _PipelineEngine(Engine):
         self._score = None
         self._align = None
         self._search = None
+        self._map = None
 
     def close(self):
         self._ctx = C.c_void_p()
@@ -606,7 +643,7 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False, score=False, align=False, search=None):
+                 distmap=False, score=False, align=False, search=None, score_map=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -618,7 +655,9 @@ class Pipeline:
         `align`: every target is aligned with the `structure` given to `submit` (`set_align`); its align block (25 + 2L + 3m
         floats, score.unpack_alignment) is then the last element of what those calls give per target, behind the score block.
         `search` (a score.Library): every target is aligned with every entry of it (`set_search`); its search block (26K + 2LK
-        + 3M floats, score.unpack_search) is then the last element of all."""
+        + 3M floats, score.unpack_search) is then the last element of all.
+        `score_map`: every target's distance map is scored against its native too (`set_score_map`, which turns `distmap`
+        and `score` on); its map-score block (64 + L floats, score.unpack_map_scores) then comes behind even the search block."""
         self.lib = _lib.load()
         self._search = None
         self.device = _resolve_device(device)
@@ -650,6 +689,8 @@ class Pipeline:
             self.set_align(True)
         if search is not None:
             self.set_search(search)
+        if score_map:
+            self.set_score_map(True)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -670,6 +711,15 @@ class Pipeline:
         """Option "score_native" on every engine: targets submitted from now on are scored against the `native` given to
         `submit` (none given: no row present, n_pairs 0); idle pipeline only."""
         self.set_option("score_native", 1 if on else 0)
+
+    def set_score_map(self, on):
+        """Option "score_map" on every engine: the distance map of targets submitted from now on is scored against the
+        `native` given to `submit`.  Turning it on turns "emit_distmap" and "score_native" on, which it needs; turning it off
+        leaves them as they are.  Idle pipeline only."""
+        if on:
+            self.set_distmap(True)
+            self.set_score(True)
+        self.set_option("score_map", 1 if on else 0)
 
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
@@ -726,6 +776,11 @@ class Pipeline:
             if any(sflags) and not (score and emit == any(flags)):
                 raise RuntimeError("score_native: the engines of a pipeline must agree on \"score_native\" and \"emit_distmap\" "
                                    "(the score block's place in the buffer depends on both); use set_score / set_distmap")
+            mflags = [bool(e.get_option("score_map")) for e in self.engines]
+            smap = all(mflags)
+            if any(mflags) and not (smap and emit and score):
+                raise RuntimeError("score_map: the engines of a pipeline must agree on \"score_map\" and all have \"emit_distmap\" "
+                                   "and \"score_native\" on; use set_score_map")
             aflags = [bool(e.get_option("align_structure")) for e in self.engines]
             align = all(aflags)
             if any(aflags) and not (align and emit == any(flags) and score == any(sflags)):
@@ -746,7 +801,7 @@ class Pipeline:
                 raise RuntimeError(f"search_structures is {search} on the engines: give the library to set_search")
             # (the native, align and search blocks are written on the current stream: `ready` below is behind it)
             d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, emit_alloc=any(flags), align=align,
-                                structure=structure, library=library, max_L=self.engines[0].max_L)
+                                structure=structure, library=library, max_L=self.engines[0].max_L, score_map=smap)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -894,7 +949,8 @@ class Pipeline:
                     if res.align_block is not None and strc is None:
                         strc = np.zeros((0, 3), dtype=np.float32)
                     try:
-                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat, strc, job.library)
+                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat, strc, job.library,
+                                           res.map_block is not None)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
@@ -1006,7 +1062,7 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
                   return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
-                  compare_chain=None, return_alignment=False, search=None, return_hits=False):
+                  compare_chain=None, return_alignment=False, search=None, return_hits=False, return_map_scores=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -1021,7 +1077,11 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     the dict of score.unpack_alignment is appended behind the scores (None without a `compare`).
     `search` (addition): a score.Library, a directory of PDB files or an .npz of tools/make_library.py; the model is aligned
     with every entry on the GPU (option "search_structures").  With `return_hits` the dict of Engine.hits (hits, rank, names)
-    is appended last of all (None without a `search`)."""
+    is appended behind those (None without a `search`).
+    `return_map_scores` (addition; needs `native`): the predicted distance map is scored against the native too (option
+    "score_map") and the dict of score.unpack_map_scores is appended last of all."""
+    if return_map_scores and native is None:
+        raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -1043,13 +1103,15 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
         search = _score.Library.open(search)
     if search is not None:
         search.check(MAX_L)
-    scores = alignment = hits = None
+    scores = alignment = hits = map_scores = None
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
         # (the engine holds both traces: its capacity covers the structure to align with, too)
         cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap),
-                                  native=native, structure=compare, library=search)
+                                  native=native, structure=compare, library=search, score_map=bool(return_map_scores))
+        if return_map_scores:
+            map_scores = eng.map_scores
         if search is not None and return_hits:
             hits = eng.hits
         if native is not None and return_scores:
@@ -1058,7 +1120,8 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
             alignment = eng.alignment
     coords, confs = out[0], out[1]
     ret = (coords, confs) + ((alnmat,) if return_alnmat else ()) + ((out[2],) if return_distmap else ())
-    return ret + ((scores,) if return_scores else ()) + ((alignment,) if return_alignment else ()) + ((hits,) if return_hits else ())
+    return (ret + ((scores,) if return_scores else ()) + ((alignment,) if return_alignment else ()) + ((hits,) if return_hits else ())
+            + ((map_scores,) if return_map_scores else ()))
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1082,7 +1145,7 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --compare and --search."""
+    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --compare and --search."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -1108,6 +1171,10 @@ def dmpfold_parser():
                              "go to standard error as one JSON line, the model on standard output is unchanged")
     parser.add_argument("--native-chain", type=str, default=None, required=False, metavar="C",
                         help="chain of --native (default: its first)")
+    parser.add_argument("--score-map", action="store_true", default=False,
+                        help="with --native: also score the predicted distance map against the native on the GPU (contact precision "
+                             "of the top L, L/2, L/5 per separation class, lDDT and distance error of the map); the JSON line of "
+                             "--native gains the key \"map\"")
     parser.add_argument("--scores", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --native to FILE instead of standard error")
     parser.add_argument("--compare", type=str, default=None, required=False, metavar="PDB",
@@ -1131,15 +1198,21 @@ def dmpfold_parser():
 
 def run_dmpfold(argv=None):
     """Command-line entry point with the reference's flags (predict.py:160-208)."""
-    args = dmpfold_parser().parse_args(argv)
+    parser = dmpfold_parser()
+    args = parser.parse_args(argv)
+    if args.score_map and args.native is None:
+        parser.error("--score-map scores the distance map against a native structure: give --native")
     out = aln_to_coords(args.input_file, device=args.device,
                         template=args.template, iterations=args.iterations,
                         minsteps=args.minsteps, weights_file=args.model_weights,
                         return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None,
                         native=args.native, return_scores=args.native is not None, native_chain=args.native_chain,
                         compare=args.compare, compare_chain=args.compare_chain, return_alignment=args.compare is not None,
-                        search=args.search, return_hits=args.search is not None)
+                        search=args.search, return_hits=args.search is not None, return_map_scores=args.score_map)
     coords, confs, alnmat = out[:3]
+    map_scores = None
+    if args.score_map:
+        map_scores, out = out[-1], out[:-1]
     if args.search is not None:
         line = json.dumps(_score.hits_json(out[-1], out[-1]["names"], args.search_top)) + "\n"
         out = out[:-1]
@@ -1159,7 +1232,10 @@ def run_dmpfold(argv=None):
         else:
             sys.stderr.write(line)
     if args.native is not None:
-        line = json.dumps(_score.scores_json(out[-1])) + "\n"
+        js = _score.scores_json(out[-1])
+        if map_scores is not None:
+            js["map"] = _score.map_scores_json(map_scores)
+        line = json.dumps(js) + "\n"
         if args.scores is not None:
             with open(args.scores, "w") as fh:
                 fh.write(line)

@@ -38,17 +38,30 @@ def align_floats(L, m):
     return 1 + ALIGN_HEADER + 2 * int(L) + 3 * int(m)
 
 
-def conf_floats(L, distmap=False, score=False, align_m=None):
+MAPSCORE_HEADER = 64                 # floats in front of the per-residue array of the map-score block
+
+
+def mapscore_floats(L):
+    """Floats of the map-score block (option "score_map") of a prediction of length L."""
+    return MAPSCORE_HEADER + int(L)
+
+
+def conf_floats(L, distmap=False, score=False, align_m=None, score_map=False):
     """Floats the `d_conf` buffer of a prediction of length L must hold: the confidences, the L*L + 3 floats of option
-    "emit_distmap", the 5L + 24 floats of option "score_native" and, with `align_m` (the structure's rows; not None), the
-    25 + 2L + 3m floats of option "align_structure", in this order."""
+    "emit_distmap", the 5L + 24 floats of option "score_native", the 64 + L floats of option "score_map" and, with `align_m`
+    (the structure's rows; not None), the 25 + 2L + 3m floats of option "align_structure", in this order."""
     L = int(L)
-    return (L + (L * L + 3 if distmap else 0) + (score_floats(L) if score else 0)
+    return (L + (L * L + 3 if distmap else 0) + (score_floats(L) if score else 0) + (mapscore_floats(L) if score_map else 0)
             + (align_floats(L, align_m) if align_m is not None else 0))
 
 
-def align_offset(L, distmap=False, score=False):
+def align_offset(L, distmap=False, score=False, score_map=False):
     """Where the align block begins in the `d_conf` buffer (A0 of include/dmpfold_hip.h)."""
+    return conf_floats(L, distmap, score, None, score_map)
+
+
+def mapscore_offset(L, distmap=True, score=True):
+    """Where the map-score block begins in the `d_conf` buffer (M0 of include/dmpfold_hip.h): the end of the score block."""
     return conf_floats(L, distmap, score)
 
 
@@ -62,50 +75,57 @@ def distmap_floats(L, on=True):
     return conf_floats(L, on)
 
 
-class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block",
-                         defaults=(None, None, None, None, None))):
+class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block",
+                         defaults=(None, None, None, None, None, None))):
     """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
     score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
-    (26K + 2LK + 3M,) - None for what is absent."""
+    (26K + 2LK + 3M,), with "score_map" map_block (64 + L,) - None for what is absent."""
     __slots__ = ()
 
     @classmethod
-    def of(cls, public, distmap, score, align=False, search=False):
+    def of(cls, public, distmap, score, align=False, search=False, score_map=False):
         """The inverse of `public` for a caller that knows which options were on."""
         public = tuple(public)
         at = 4 if distmap else 2
+        end = at + (1 if score else 0) + (1 if align else 0) + (1 if search else 0)
         return cls(*public[:2], *(public[2:4] if distmap else (None, None)), public[at] if score else None,
                    public[at + (1 if score else 0)] if align else None,
-                   public[at + (1 if score else 0) + (1 if align else 0)] if search else None)
+                   public[at + (1 if score else 0) + (1 if align else 0)] if search else None,
+                   public[end] if score_map else None)
 
-    def public(self, distmap=True, score=True, align=True, search=True):
+    def public(self, distmap=True, score=True, align=True, search=True, score_map=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
-        block, the align block and the search block, each if present and wanted."""
+        block, the align block, the search block and - last, though it lies behind the score block in the buffer - the
+        map-score block, each if present and wanted."""
         return ((self.coords, self.confs) + ((self.distmap, self.info) if distmap and self.distmap is not None else ())
                 + ((self.score_block,) if score and self.score_block is not None else ())
                 + ((self.align_block,) if align and self.align_block is not None else ())
-                + ((self.search_block,) if search and self.search_block is not None else ()))
+                + ((self.search_block,) if search and self.search_block is not None else ())
+                + ((self.map_block,) if score_map and self.map_block is not None else ()))
 
 
-def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None, search=None):
-    """The parts of a `d_conf` buffer (a 1-D tensor or array of at least conf_floats(L, emit, score, align_m) floats) at the
-    offsets of include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through).  `search`: (K, M, max_L) of
-    option "search_structures" - the search block then lies at search_offset(L, emit, score, align_m, max_L)."""
+def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None, search=None, score_map=False):
+    """The parts of a `d_conf` buffer (a 1-D tensor or array of at least conf_floats(L, emit, score, align_m, score_map)
+    floats) at the offsets of include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through).  `search`:
+    (K, M, max_L) of option "search_structures" - the search block then lies at search_offset(L, emit, score, align_m, max_L,
+    score_map)."""
     L = int(L)
-    need = conf_floats(L, emit, score, align_m)
+    need = conf_floats(L, emit, score, align_m, score_map)
     b0 = None
     if search is not None:
-        b0 = search_offset(L, emit, score, align_m, search[2])
+        b0 = search_offset(L, emit, score, align_m, search[2], score_map)
         need = max(need, b0 + search_floats(L, search[0], search[1]))
     if buf.ndim != 1 or buf.shape[0] < need:
         raise ValueError(f"a d_conf buffer of length {L} has {need} floats, got shape {tuple(buf.shape)}")
     s0 = score_offset(L, emit)
-    a0 = align_offset(L, emit, score)
+    m0 = mapscore_offset(L, emit, score)
+    a0 = align_offset(L, emit, score, score_map)
     return Outputs(coords, buf[:L], buf[L:L + L * L].reshape(L, L) if emit else None, buf[L + L * L:s0] if emit else None,
                    buf[s0:s0 + score_floats(L)] if score else None,
                    buf[a0:a0 + align_floats(L, align_m)] if align_m is not None else None,
-                   buf[b0:b0 + search_floats(L, search[0], search[1])] if search is not None else None)
+                   buf[b0:b0 + search_floats(L, search[0], search[1])] if search is not None else None,
+                   buf[m0:m0 + mapscore_floats(L)] if score_map else None)
 
 
 def split_distmap_buffer(buf, L):
@@ -255,6 +275,81 @@ def scores_json(scores):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# option "score_map" (include/dmpfold_hip.h): the predicted distance map scored against the same native - contact precision
+# of the top L, L/2 and L/5 predictions per sequence-separation class, the contacts at the 8 A threshold, and the distance
+# agreement of the map itself (lDDT of the map, per residue and global; mean absolute error, RMSE, bias).  The library
+# returns integer counts; the ratios are formed here.  THE REFERENCE HAS NO SUCH QUANTITY.
+# ---------------------------------------------------------------------------------------------------------------------
+MAP_CLASSES = ("short", "medium", "long", "medium_long")       # separations 6-11, 12-23, >= 24, >= 12
+MAP_LISTS = ("L", "L2", "L5")                                  # the top ln, ln / 2, ln / 5 of a class
+MAP_NAMES = ("map_lddt", "map_mae", "map_rmse", "map_bias")
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else float("nan")
+
+
+def unpack_map_scores(block, L):
+    """A map-score block (64 + L floats, array or tensor) -> dict: n, ln, pairs (ordered pairs within 15 A), map_lddt,
+    map_mae, map_rmse, map_bias, map_lddt_res (L,), and classes: {short, medium, long, medium_long} -> dict of the counts
+    candidates, native_contacts, tp, predicted (at the 8 A threshold), hits and taken (3 ints each: the lists L, L/2, L/5) and
+    the ratios formed from them: precision (3 floats, hits / taken), precision_8A (tp / predicted), recall_8A (tp /
+    native_contacts), f1_8A - NaN where the denominator is 0.  A block the library answered with NaN (a latched fault) gives
+    zero counts and NaN floats."""
+    L = int(L)
+    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    if b.ndim != 1 or b.shape[0] != mapscore_floats(L):
+        raise ValueError(f"a map-score block of length {L} has {mapscore_floats(L)} floats, got shape {tuple(b.shape)}")
+
+    def whole(v):
+        return int(v) if v == v else 0
+    out = {"n": whole(b[0]), "ln": float(b[1]), "pairs": whole(b[50])}
+    for k, name in enumerate(MAP_NAMES):
+        out[name] = float(b[51 + k])
+    out["map_lddt_res"] = b[MAPSCORE_HEADER:].copy()
+    out["classes"] = {}
+    for c, cname in enumerate(MAP_CLASSES):
+        s = b[2 + 12 * c:14 + 12 * c]
+        cl = {"candidates": whole(s[0]), "native_contacts": whole(s[1]), "hits": [whole(v) for v in s[2:5]],
+              "taken": [whole(v) for v in s[5:8]], "tp": whole(s[8]), "predicted": whole(s[9])}
+        cl["precision"] = [_ratio(h, t) for h, t in zip(cl["hits"], cl["taken"])]
+        p, r = _ratio(cl["tp"], cl["predicted"]), _ratio(cl["tp"], cl["native_contacts"])
+        cl["precision_8A"], cl["recall_8A"] = p, r
+        cl["f1_8A"] = _ratio(2 * cl["tp"], cl["predicted"] + cl["native_contacts"])
+        out["classes"][cname] = cl
+    return out
+
+
+def map_scores_json(ms):
+    """`unpack_map_scores` without the per-residue array as a JSON-ready dict (the value of "map" in what `dmpfold --native
+    --score-map` prints and `dmpfold-batch --natives --score-map` writes); NaN becomes None."""
+    def num(v):
+        v = float(v)
+        return v if v == v else None
+    out = {"n": int(ms["n"]), "ln": num(ms["ln"]), "pairs": int(ms["pairs"])}
+    for name in MAP_NAMES:
+        out[name] = num(ms[name])
+    for cname in MAP_CLASSES:
+        cl = ms["classes"][cname]
+        out[cname] = {k: ([int(v) for v in cl[k]] if isinstance(cl[k], list) else int(cl[k]))
+                      for k in ("candidates", "native_contacts", "hits", "taken", "tp", "predicted")}
+        out[cname]["precision"] = dict(zip(MAP_LISTS, (num(v) for v in cl["precision"])))
+        for k in ("precision_8A", "recall_8A", "f1_8A"):
+            out[cname][k] = num(cl[k])
+    return out
+
+
+def map_scores_flat(js):
+    """The scalar figures of `map_scores_json` by name - map_lddt, map_mae, map_rmse, map_bias and <class>_<list> for the
+    twelve list precisions - for tables, means and medians."""
+    out = {name: js.get(name) for name in MAP_NAMES}
+    for cname in MAP_CLASSES:
+        for lname in MAP_LISTS:
+            out[f"{cname}_{lname}"] = js[cname]["precision"][lname]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # option "align_structure" (include/dmpfold_hip.h): the model aligned with a structure of any length and sequence on the
 # GPU - TM-align's KIND of search (gapless threadings, then superposition and dynamic programming in turn), not its
 # bits: one family of initial alignments, one gap penalty, 16 refinements.  Any alignment gives a lower bound of the
@@ -346,14 +441,14 @@ def align_m_rule(m, max_L):
     return int(m) if m == m and 3 <= m <= int(max_L) and m == int(m) else 0
 
 
-def search_offset(L, distmap=False, score=False, align_m=None, max_L=None):
+def search_offset(L, distmap=False, score=False, align_m=None, max_L=None, score_map=False):
     """Where the search block begins in the `d_conf` buffer (B0 of include/dmpfold_hip.h): the end of what the other options
     give.  `align_m`: the m the align block holds (None = "align_structure" off); the library counts 3m of it only if it is
     an integer in [3, `max_L`] (`max_L` None: whatever the block's writer allocated, i.e. any whole m >= 0 counts)."""
     if align_m is None:
-        return conf_floats(L, distmap, score)
+        return conf_floats(L, distmap, score, None, score_map)
     mp = int(align_m) if max_L is None else align_m_rule(align_m, max_L)
-    return conf_floats(L, distmap, score, mp)
+    return conf_floats(L, distmap, score, mp, score_map)
 
 
 class Library:

@@ -241,14 +241,67 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * Cost with the option on: three launches in dmp_predict_end (csrc/score.hip: score_prep, score_lddt, score_search - one
  * workgroup per seed, both traces and the set S in LDS, 6L floats + L flags; sums in a fixed order, the same bits on
  * every run).  A context holds 6 max_L records of 20 doubles.
+ * "score_map" (0 or 1, default 0; any other value: DMP_ERR_ARG): score the chosen pass's predicted distance map - the map
+ * "emit_distmap" returns - against the native trace of "score_native" on the device: contact precision of the top L, L/2
+ * and L/5 predictions in the short, medium and long sequence-separation classes, and the distance error of the map itself,
+ * per residue and in total.  Beside "score_native"'s lddt of the MODEL it tells which half of a prediction lost the
+ * accuracy: the network that produces the map, or the embedding, coordinate GRU and minimiser that realise it.  Read when a
+ * prediction begins and held for it.  IT NEEDS "emit_distmap" = 1 AND "score_native" = 1: a prediction begun with it on and
+ * either of them off fails with DMP_ERR_ARG and a message naming the missing option.  With it 0 nothing is launched, read,
+ * written or allocated, and every offset and output is bit for bit what it is without the option.  With it 1 THE d_conf
+ * ARGUMENT MUST HOLD M0 + 64 + L FLOATS, M0 = THE END OF THE SCORE BLOCK = L + L*L + 3 + 5L + 24: there sits the MAP-SCORE
+ * BLOCK, all of it outputs (its inputs are the score block's native trace and lnorm), and A0 and B0 below move behind it.
+ * The coordinates, the confidences, the map extension and the score block do not change by a bit.
+ * Rows and pairs.  P = the rows whose native x is not NaN, n = |P|; ln = lnorm if lnorm > 0, else n.  Candidates are the
+ * pairs i < j, both in P, by their separation s = j - i in alignment columns: class c = 0 (short) 6 <= s <= 11, c = 1
+ * (medium) 12 <= s <= 23, c = 2 (long) s >= 24, c = 3 (medium + long) s >= 12; N_c = the candidates of class c.
+ * Contacts.  A native contact holds iff (dx*dx + dy*dy) + dz*dz < 64.0f in float32 from the float32 native coordinates,
+ * every operation rounded, nothing contracted, no square root.  A predicted contact holds iff dm[i][j] < 8.0f.  The
+ * diagonal of dm is never used.
+ * Ranked lists.  The candidates of a class are ordered by the key (bit pattern of dm[i][j] as an unsigned 32-bit integer, i,
+ * j), ascending: dm is not negative, so this is numeric order, NaN last, ties to the lower (i, j).  For d in {1, 2, 5}:
+ * k_d = max(1, floor(ln / d)), t_{c,d} = min(k_d, N_c), h_{c,d} = the native contacts among the first t_{c,d} candidates.
+ * Distance agreement.  The pair set and the native distance are those of "score_native"'s lDDT-C-alpha - the ordered pairs
+ * i != j of present rows with native distance dn < 15 Angstrom, float64 from the float32 coordinates - and the model's
+ * distance is replaced by dm[i][j]: a pair is preserved at 0.5, 1, 2, 4 if |dm - dn| is below it; map_lddt per residue and
+ * in total from integer counts, preserved / (4 x partners) (in total 0 without any pair).  Over the same pairs map_mae =
+ * mean |dm - dn|, map_rmse = sqrt(mean (dm - dn)^2), map_bias = mean (dm - dn): float64 sums in a fixed order, each output
+ * rounded once to float32.  Offsets relative to M0:
+ *   0                    n
+ *   1                    ln
+ *   2 + 12c + 0          N_c                                          (c = 0 .. 3)
+ *   2 + 12c + 1          native contacts among the candidates of class c
+ *   2 + 12c + 2 .. 4     h_{c,d} for d = 1, 2, 5
+ *   2 + 12c + 5 .. 7     t_{c,d} for d = 1, 2, 5
+ *   2 + 12c + 8          true positives at the threshold: candidates that are a predicted AND a native contact
+ *   2 + 12c + 9          predicted contacts among the candidates
+ *   2 + 12c + 10, 11     zero
+ *   50                   ordered pairs within 15 Angstrom
+ *   51 .. 54             map_lddt, map_mae, map_rmse, map_bias
+ *   55 .. 63             zero
+ *   [64, 64 + L)         per-residue map_lddt; NaN where the native row is absent, 0 where the residue has no partner
+ * Every count is an integer below 2^24 stored as a float.  The precisions h / t, and precision, recall and F1 at the
+ * threshold, are formed on the host (NaN where a denominator is 0).  n < 2: the counts are 0, offsets 51 .. 54 NaN, no
+ * fault.  A prediction that latched a device-side fault returns NaN in every slot.
+ * THE REFERENCE HAS NO SUCH QUANTITY, and nobody has compared these figures with another contact-evaluation program's;
+ * the definition above is the only one (tests/test_mapscore_cpu.py restates it in NumPy).
+ * Cost with the option on: two launches in dmp_predict_end behind "score_native" (csrc/mapscore.hip).  mapscore_count:
+ * rows dealt to at most 64 workgroups; integer counts go thread -> LDS -> one integer atomic per workgroup and counter,
+ * the three error sums through the fixed-order float64 grid sum, whose last arriver writes the header.  mapscore_select:
+ * one workgroup per (class, list), twelve; a radix select of the t-th smallest of the unique 54-bit keys bits(dm) << 22 |
+ * (i L + j) - digit histograms in LDS, the class's pairs re-read once per digit, the pair index's digits only where a list
+ * ends inside a run of equal values - then h as the count of native contacts
+ * with a key not above it, so ties are no separate path.  No float atomics: the same bits on every run.  A context holds
+ * 1.7 KB for this (14 counters, 3 x 64 partial sums, 3 totals, 3 tickets).  Measured cost: 6.6 ms at L = 2048, 0.2 ms at
+ * L = 300 (profiles/mapscore.txt).
  * "align_structure" (0 or 1, default 0; any other value: DMP_ERR_ARG): align the model with a structure of any length and
  * sequence on the device - a structural alignment found by superposition and dynamic programming in turn.  Read when a
  * prediction begins and held for it.  With it 0 nothing is launched, nothing extra is read or written, and every output is
  * bit for bit what it is without the option.  With it 1 dmp_predict_end launches the alignment behind "score_native", on
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
- * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native"; the library cannot check
- * the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map";
+ * the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
@@ -512,7 +565,8 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
  * to learn whether to go on, and returns with the remaining work enqueued as always.
  * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN INTO THEM
- * (layout: dmp_ctx_set_option); WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m AND THE STRUCTURE'S
+ * (layout: dmp_ctx_set_option); WITH OPTION "score_map" = 1 64 + L MORE BEHIND THOSE (all outputs);
+ * WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m AND THE STRUCTURE'S
  * TRACE WRITTEN INTO THEM; WITH OPTION "search_structures" = K THE SEARCH BLOCK (26K + 2LK + 3M FLOATS) BEHIND ALL OF THEM. */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
                 int Lt, int nloops, int refine_steps, float* d_coords, float* d_conf,
@@ -570,7 +624,8 @@ int dmp_predict_set_vgru_result(dmp_ctx* ctx, const float* d_vout, void* event);
  * d_conf (L); a prediction during which a device-side fault was recorded returns NaN.
  * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * IF IT BEGAN WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE; the native trace and lnorm are read
- * from them here; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m and the structure's trace read here;
+ * from them here; WITH OPTION "score_map" = 1 64 + L MORE BEHIND THOSE;
+ * WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m and the structure's trace read here;
  * WITH OPTION "search_structures" = K the search block behind all of them, the m_k and the traces read here. */
 int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream);
 int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream);
@@ -631,7 +686,8 @@ int dmp_pipeline_set_option(dmp_pipeline* p, const char* name, int value);
 /* d_coords: L x 5 x 3 floats, d_conf: L floats.  WITH OPTION "emit_distmap" = 1 ON THE PIPELINE d_conf MUST HOLD
  * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run.
  * WITH OPTION "score_native" = 1 ON THE PIPELINE d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN
- * INTO THEM BEFORE ready_event; WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, LIKEWISE;
+ * INTO THEM BEFORE ready_event; WITH OPTION "score_map" = 1 64 + L MORE BEHIND THOSE (all outputs);
+ * WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, LIKEWISE;
  * WITH OPTION "search_structures" = K THE SEARCH BLOCK BEHIND ALL OF THEM, LIKEWISE. */
 int64_t dmp_pipeline_submit(dmp_pipeline* p, const uint8_t* d_msa, int N, int L, const float* d_template_ca, int nloops,
                             int refine_steps, float* d_coords, float* d_conf, void* ready_event);
