@@ -383,7 +383,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        out = Outputs.of(public, distmap or score_map, bool(natives), bool(structures), library is not None, score_map)
+        out = Outputs.of(public, distmap=distmap or score_map, score=bool(natives), align=bool(structures), search=library is not None,
+                         score_map=score_map)
         aln_path, alnmat, _ = parsed.pop(t)
         sc = ms = None
         if out.score_block is not None and t in scored:

@@ -23,6 +23,10 @@ Differences from the reference, all additive or forced by the environment:
     (option "score_native": TM-score, GDT, RMSD, lDDT-C-alpha; dmpfold2_amd/score.py has the host side);
   * `compare` / `return_alignment` / `dmpfold --compare PDB`: the model is aligned on the GPU with a structure of any length
     and sequence (option "align_structure": a structural alignment, both TM-scores, the superposition).
+
+Plumbing: a public method gathers what its call asks for besides the prediction into one `Extras` in its first lines and
+everything below it carries that record; the caller's `d_conf` buffer is described by one `score.Layout`, made in `_stage`
+from the options as the context holds them (`Flags`), which also cuts the buffer into the views of an `Outputs`.
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ import torch
 
 from . import _lib
 from . import score as _score
-from .score import Outputs, distmap_floats, split_conf_buffer, split_distmap_buffer    # noqa: F401 (re-exports)
+from .score import Layout, Outputs, distmap_floats, split_conf_buffer, split_distmap_buffer    # noqa: F401 (re-exports)
 
 default_device = "cuda"
 default_iterations = 10
@@ -229,16 +233,45 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=False, structure=None, library=None, max_L=None,
-           score_map=False):
+class Extras(namedtuple("Extras", "distmap native structure library score_map", defaults=(False, None, None, None, False))):
+    """What one call asks for besides the prediction itself, as `Engine.predict` documents each: `distmap` (return the
+    map), `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map).
+    The public methods build one in their first lines; everything below them takes and carries the record."""
+    __slots__ = ()
+
+
+# The options that decide the layout of a `d_conf` buffer, in the order of a row of `agree_options`.
+LAYOUT_OPTIONS = ("emit_distmap", "score_native", "score_map", "align_structure", "search_structures")
+
+# The layout options as one prediction runs with them: `emit` .. `align` bools, `search` the K of "search_structures";
+# `alloc`: size the buffer as if "emit_distmap" were on (a pipeline whose engines disagree on that option alone);
+# `max_L`: the context's, for the rule of B0.
+Flags = namedtuple("Flags", "emit alloc score score_map align search max_L", defaults=(None,))
+
+
+def agree_options(rows):
+    """The one rule for the engines of a pipeline, which share a buffer whichever of them runs a target.  `rows`: per engine
+    the values of LAYOUT_OPTIONS.  Where nothing beyond the map is on anywhere the engines may differ in "emit_distmap": the
+    buffer is then sized for the map (`alloc`) and only the confidences are handed out (`emit`).  Otherwise every engine must
+    hold the same five values, and "score_map" needs "emit_distmap" and "score_native" on: RuntimeError if not.  -> Flags."""
+    rows = [tuple(bool(v) for v in r[:4]) + (int(r[4]),) for r in rows]
+    if any(any(r[1:]) for r in rows):
+        emit, score, score_map = rows[0][:3]
+        if any(r != rows[0] for r in rows) or (score_map and not (emit and score)):
+            raise RuntimeError("the engines of a pipeline must agree on \"emit_distmap\", \"score_native\", \"score_map\", "
+                               "\"align_structure\" and \"search_structures\" (where each block lies in the buffer depends on "
+                               "those in front of it), and \"score_map\" needs \"emit_distmap\" and \"score_native\" on; use "
+                               "set_distmap / set_score / set_score_map / set_align / set_search")
+    emits = [r[0] for r in rows]
+    return Flags(all(emits), any(emits), *rows[0][1:])
+
+
+def _stage(device, L, template_ca, flags, extras):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
-    The `d_conf` buffer behind the Outputs is sized for the options as the context holds them - the library cannot check
-    it, writes L + L*L + 3 floats with "emit_distmap" on (`emit_alloc`: sized as if it were) and reads and writes 5L + 24
-    more behind them with "score_native" on: the native trace goes there (no `native` = no row present: n_pairs 0, NaN scores);
-    with "align_structure" on (`align`) 25 + 2L + 3m more behind those, m and the rows of `structure` in them (no `structure`:
-    m = 0, which the library answers with NaN); with "search_structures" on (`library`, a score.Library; `max_L`: the
-    context's, for the rule of B0) the search block behind those, filled from the library's copy on the GPU; with "score_map"
-    on (`score_map`) 64 + L floats, all outputs, between the score block and the align block."""
+    The `d_conf` buffer behind the Outputs is laid out (score.Layout) for the options as the context holds them (`flags`) -
+    the library cannot check it - and its input blocks are filled from `extras`: with "score_native" on the native trace (no
+    `native` = no row present: n_pairs 0, NaN scores); with "align_structure" on m and the rows of `structure` (none: m = 0,
+    which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -247,24 +280,27 @@ def _stage(device, L, template_ca, native, emit, score, emit_alloc=None, align=F
                                f"alignment has {L} columns")
     coords = torch.empty((L, 5, 3), dtype=torch.float32, device=device)
     ablock = None
-    if align:
-        ablock = _score.pack_structure(structure, L) if structure is not None else _score.empty_structure(L)
+    if flags.align:
+        ablock = _score.pack_structure(extras.structure, L) if extras.structure is not None else _score.empty_structure(L)
+    library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
-    alloc = emit if emit_alloc is None else emit_alloc
-    search = None if library is None else (len(library), library.rows, max_L)
-    floats = _score.conf_floats(L, alloc, score, align_m, score_map)
-    if search is not None:
-        floats = max(floats, _score.search_offset(L, alloc, score, align_m, max_L, score_map) + _score.search_floats(L, *search[:2]))
-    buf = torch.empty((floats,), dtype=torch.float32, device=device)
-    out = split_conf_buffer(buf, L, emit, score, coords, align_m, search, score_map)
-    if search is not None:
+    lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
+                 flags.max_L)
+    floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
+    out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
+    if library is not None:
         library.fill_block(out.search_block, L)
-    if align:
+    if flags.align:
         out.align_block.copy_(torch.from_numpy(ablock))
-    if score:
+    if flags.score:
+        native = extras.native
         block = _score.pack_native(*_score.as_native(native, L), L) if native is not None else _score.empty_native(L)
         out.score_block.copy_(torch.from_numpy(block))
     return d_tpl, out
+
+
+# The last prediction of an engine: its Outputs (without the coordinates), its length and the library it searched.
+_Last = namedtuple("_Last", "out L library")
 
 
 class Engine:
@@ -282,10 +318,7 @@ class Engine:
                                                C.byref(self._ctx)))
         self.weights_tag = None
         self.last_fallback = False     # the last predict_*_checked call fell back to conv_mode 2
-        self._score = None             # (score block, L) of the last prediction
-        self._align = None             # (align block, L) of the last prediction
-        self._search = None            # (search block, L, library) of the last prediction
-        self._map = None               # (map-score block, L) of the last prediction
+        self._forget_last()
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
@@ -360,71 +393,51 @@ class Engine:
         after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
         call synchronises with the GPU once per pass."""
-        alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
-        with torch.cuda.device(self.device):
-            d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library,
-                                   score_map)
+        extras = Extras(distmap, native, structure, library, score_map)
+        return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
+
+    def _forget_last(self):
+        self._last = _Last(Outputs(None, None), 0, None)
+
+    # The blocks of the last prediction on the GPU, views of the buffer handed to the library; None where the option was off.
+    score_block = property(lambda self: self._last.out.score_block, doc='"score_native": 5L + 24 floats, or None')
+    map_score_block = property(lambda self: self._last.out.map_block, doc='"score_map": 64 + L floats, or None')
+    align_block = property(lambda self: self._last.out.align_block, doc='"align_structure": 25 + 2L + 3m floats, or None')
+    search_block = property(lambda self: self._last.out.search_block, doc='"search_structures": 26K + 2LK + 3M floats, or None')
+
+    def _unpacked(self, field, unpack):
+        """A block of the last prediction through `unpack`(block, L), None without it.  Synchronises with the GPU."""
+        block = getattr(self._last.out, field)
+        if block is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        return unpack(block, self._last.L)
 
     @property
     def map_scores(self):
         """The map scores of the last prediction as score.unpack_map_scores gives them, None if it ran without option
         "score_map".  Synchronises with the GPU."""
-        if self._map is None:
-            return None
-        block, L = self._map
-        torch.cuda.synchronize(self.device)
-        return _score.unpack_map_scores(block, L)
-
-    @property
-    def map_score_block(self):
-        """The last prediction's map-score block on the GPU (64 + L floats, a view of the buffer handed to the library), or None."""
-        return None if self._map is None else self._map[0]
+        return self._unpacked("map_block", _score.unpack_map_scores)
 
     @property
     def hits(self):
         """The search of the last prediction as score.unpack_search gives it, with the library's `names` beside `hits` and
         `rank`; None if it ran without option "search_structures".  Synchronises with the GPU."""
-        if self._search is None:
-            return None
-        block, L, library = self._search
-        torch.cuda.synchronize(self.device)
-        return dict(_score.unpack_search(block, L, library.lengths), names=list(library.names))
-
-    @property
-    def search_block(self):
-        """The last prediction's search block on the GPU (26K + 2LK + 3M floats, a view of the buffer handed to the library), or None."""
-        return None if self._search is None else self._search[0]
+        library = self._last.library
+        return self._unpacked("search_block", lambda block, L: dict(_score.unpack_search(block, L, library.lengths),
+                                                                    names=list(library.names)))
 
     @property
     def alignment(self):
         """The structural alignment of the last prediction as score.unpack_alignment gives it, None if it ran without option
         "align_structure".  Synchronises with the GPU."""
-        if self._align is None:
-            return None
-        block, L = self._align
-        torch.cuda.synchronize(self.device)
-        return _score.unpack_alignment(block, L)
-
-    @property
-    def align_block(self):
-        """The last prediction's align block on the GPU (25 + 2L + 3m floats, a view of the buffer handed to the library), or None."""
-        return None if self._align is None else self._align[0]
+        return self._unpacked("align_block", _score.unpack_alignment)
 
     @property
     def scores(self):
         """The scores of the last prediction as score.unpack_scores gives them, None if it ran without option
         "score_native".  Synchronises with the GPU."""
-        if self._score is None:
-            return None
-        block, L = self._score
-        torch.cuda.synchronize(self.device)
-        return _score.unpack_scores(block, L)
-
-    @property
-    def score_block(self):
-        """The last prediction's score block on the GPU (5L + 24 floats, a view of the buffer handed to the library), or None."""
-        return None if self._score is None else self._score[0]
+        return self._unpacked("score_block", _score.unpack_scores)
 
     @property
     def passes_run(self):
@@ -435,31 +448,38 @@ class Engine:
                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
                        score_map=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        with self._call_options(converge, distmap, native, structure, library, score_map):
-            return self._run(d_msa, template_ca, iterations, minsteps, native, structure,
-                             library).public(distmap, score=False, align=False, search=False, score_map=False)
+        extras = Extras(distmap, native, structure, library, score_map)
+        return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras)
+
+    def _upload(self, alnmat):
+        with torch.cuda.device(self.device):
+            return torch.from_numpy(np.ascontiguousarray(alnmat, dtype=np.uint8)).to(self.device)
+
+    def _predict(self, d_msa, template_ca, iterations, minsteps, converge, extras):
+        with self._call_options(converge, extras):
+            return self._run(d_msa, template_ca, iterations, minsteps, extras).public(extras.distmap, blocks=False)
 
     @contextlib.contextmanager
-    def _call_options(self, converge, distmap, native, structure=None, library=None, score_map=False):
+    def _call_options(self, converge, extras):
         """The options one call asks for - read when the prediction begins - set for its duration, then as they were.
         `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" / "align_structure" set by hand
         stay set."""
         want = {} if converge is None else {"recycle_tol_mA": converge_to_mA(converge)}    # (raises before anything changes)
-        if score_map and native is None and not self.get_option("score_native"):
+        if extras.score_map and extras.native is None and not self.get_option("score_native"):
             raise ValueError("score_map scores the distance map against a native structure: give `native`")
-        if (distmap or score_map) and not self.get_option("emit_distmap"):
+        if (extras.distmap or extras.score_map) and not self.get_option("emit_distmap"):
             want["emit_distmap"] = 1
-        if score_map and not self.get_option("score_map"):
+        if extras.score_map and not self.get_option("score_map"):
             want["score_map"] = 1                         # (the library looks at the three together when the prediction begins)
-        if native is not None and not self.get_option("score_native"):
+        if extras.native is not None and not self.get_option("score_native"):
             want["score_native"] = 1
-        if structure is not None and not self.get_option("align_structure"):
-            _score.as_structure(structure)                                                 # (a bad shape raises before anything changes)
+        if extras.structure is not None and not self.get_option("align_structure"):
+            _score.as_structure(extras.structure)                                          # (a bad shape raises before anything changes)
             want["align_structure"] = 1
-        if library is not None and not self.get_option("search_structures"):
-            library.check(self.max_L)                                                      # (raises, naming the entry)
-            want["search_max_m"] = library.max_m          # before the option itself: the scratch is sized from it
-            want["search_structures"] = len(library)
+        if extras.library is not None and not self.get_option("search_structures"):
+            extras.library.check(self.max_L)                                               # (raises, naming the entry)
+            want["search_max_m"] = extras.library.max_m   # before the option itself: the scratch is sized from it
+            want["search_structures"] = len(extras.library)
         before = {}
         try:
             for name, value in want.items():
@@ -470,14 +490,12 @@ class Engine:
             for name, value in reversed(list(before.items())):
                 self.set_option(name, value)
 
-    def _run(self, d_msa, template_ca, iterations, minsteps, native, structure=None, library=None):
-        """One prediction with the options as the context holds them -> Outputs."""
-        emit, score = bool(self.get_option("emit_distmap")), bool(self.get_option("score_native"))
-        align = bool(self.get_option("align_structure"))
+    def _run(self, d_msa, template_ca, iterations, minsteps, extras):
+        """One prediction with the options as the context holds them (not as the call asked) -> Outputs."""
+        emit, score, smap, align, search = (self.get_option(name) for name in LAYOUT_OPTIONS)
+        structure, library = extras.structure, extras.library
         if align and structure is not None and _score.as_structure(structure).shape[0] > self.max_L:
             raise RuntimeError(f"structure has {len(structure)} rows; the engine's capacity is {self.max_L} (max_L)")
-        smap = bool(self.get_option("score_map"))
-        search = self.get_option("search_structures")
         if search:
             if library is None or len(library) != search:
                 raise RuntimeError(f"search_structures is {search}: the prediction needs a library of that many entries"
@@ -488,18 +506,11 @@ class Engine:
         if L < 8:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
+        flags = Flags(bool(emit), bool(emit), bool(score), bool(smap and emit and score), bool(align), search, self.max_L)
         with torch.cuda.device(self.device):
-            self._score = self._align = self._search = self._map = None
-            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, align=align, structure=structure,
-                                library=library if search else None, max_L=self.max_L, score_map=smap and emit and score)
-            if out.map_block is not None:
-                self._map = (out.map_block, L)
-            if search:
-                self._search = (out.search_block, L, library)
-            if score:
-                self._score = (out.score_block, L)
-            if align:
-                self._align = (out.align_block, L)
+            self._forget_last()
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
+            self._last = _Last(out._replace(coords=None), L, library if search else None)
             if self._stream is not None:
                 # an engine with its own stream: order it after the producer of the inputs and tell the
                 # caching allocator that these blocks are in use there
@@ -546,27 +557,26 @@ class Engine:
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
         which has float32's range, at about half the convolution rate."""
-        alnmat = np.ascontiguousarray(alnmat, dtype=np.uint8)
-        with torch.cuda.device(self.device):
-            d_msa = torch.from_numpy(alnmat).to(self.device)
-        return self.predict_device_checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure, library,
-                                           score_map)
+        extras = Extras(distmap, native, structure, library, score_map)
+        out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
+        return out.public(extras.distmap, blocks=False)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
                                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
                                score_map=False):
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
         `score_map`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment and hits)."""
-        return self._checked(d_msa, template_ca, iterations, minsteps, converge, distmap, native,
-                             structure, library, score_map).public(distmap, score=False, align=False, search=False, score_map=False)
+        extras = Extras(distmap, native, structure, library, score_map)
+        return self._checked(d_msa, template_ca, iterations, minsteps, converge, extras).public(extras.distmap, blocks=False)
 
-    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, distmap, native, structure=None, library=None,
-                 score_map=False):
-        """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry `native` and
-        `structure` along."""
-        with self._call_options(converge, distmap, native, structure, library, score_map):
-            out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
-            bits = self.sync_faults()
+    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, extras):
+        """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry the call's
+        extras along."""
+        def run():
+            return self._run(d_msa, template_ca, iterations, minsteps, extras), self.sync_faults()
+
+        with self._call_options(converge, extras):
+            out, bits = run()
             self.last_fallback = False
             if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
                 # the persistent chain's row barriers timed out (its workgroups were not all resident: another process
@@ -574,8 +584,7 @@ class Engine:
                 print("dmpfold2_amd: the persistent vertical-GRU launch could not get the whole GPU; re-running this "
                       "alignment (and every later one on this engine) with one launch per alignment row", file=sys.stderr)
                 self.set_option("vgru_persistent", 0)
-                out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
-                bits = self.sync_faults()
+                out, bits = run()
             if bits == FAULT_F16_RANGE and self.get_option("conv_mode") == 0:
                 print("dmpfold2_amd: activations left the f16 range of the split-product convolution; "
                       "re-running this alignment with conv_mode=2 (bf16 split, no range limit)",
@@ -583,8 +592,7 @@ class Engine:
                 self.last_fallback = True
                 self.set_option("conv_mode", 2)
                 try:
-                    out = self._run(d_msa, template_ca, iterations, minsteps, native, structure, library)
-                    bits = self.sync_faults()
+                    out, bits = run()
                 finally:
                     self.set_option("conv_mode", 0)
             raise_for_faults(bits)
@@ -609,10 +617,7 @@ class _PipelineEngine(Engine):
         self._stream = torch.cuda.ExternalStream(stream_ptr, device=device)
         self.weights_tag = None
         self.last_fallback = False
-        self._score = None
-        self._align = None
-        self._search = None
-        self._map = None
+        self._forget_last()
 
     def close(self):
         self._ctx = C.c_void_p()
@@ -622,10 +627,9 @@ class _PipelineEngine(Engine):
 
 
 # A target in a `Pipeline`: what stays alive until its result is handed out and what a repeat needs.  `out`: its Outputs,
-# `ready`: the event behind the producer of its inputs, `native`: as given to `submit`, None if the target is not scored,
-# `structure`: as given to `submit`, None if the target is not aligned.
-# `library`: the score.Library the target searches, None if it does not.
-_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready native structure library", defaults=(None, None))
+# `ready`: the event behind the producer of its inputs, `extras`: the native, structure and library the target was staged
+# with - each None where its option was off.
+_Job = namedtuple("_Job", "d_msa iterations minsteps d_tpl out ready extras")
 
 
 # ticket states of the C pipeline (include/dmpfold_hip.h, DMP_TICKET_*)
@@ -767,41 +771,18 @@ class Pipeline:
             raise RuntimeError(f"alignment {n} x {L} exceeds the pipeline capacity "
                                f"{self.engines[0].max_N} x {self.engines[0].max_L}")
         with torch.cuda.device(self.device):
-            # the library cannot check the buffer: it is sized by the option as the engines hold it, whichever way it was
-            # set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
-            flags = [bool(e.get_option("emit_distmap")) for e in self.engines]
-            emit = all(flags)                             # the extension is handed out only if whichever engine runs it writes it
-            sflags = [bool(e.get_option("score_native")) for e in self.engines]
-            score = all(sflags)
-            if any(sflags) and not (score and emit == any(flags)):
-                raise RuntimeError("score_native: the engines of a pipeline must agree on \"score_native\" and \"emit_distmap\" "
-                                   "(the score block's place in the buffer depends on both); use set_score / set_distmap")
-            mflags = [bool(e.get_option("score_map")) for e in self.engines]
-            smap = all(mflags)
-            if any(mflags) and not (smap and emit and score):
-                raise RuntimeError("score_map: the engines of a pipeline must agree on \"score_map\" and all have \"emit_distmap\" "
-                                   "and \"score_native\" on; use set_score_map")
-            aflags = [bool(e.get_option("align_structure")) for e in self.engines]
-            align = all(aflags)
-            if any(aflags) and not (align and emit == any(flags) and score == any(sflags)):
-                raise RuntimeError("align_structure: the engines of a pipeline must agree on \"align_structure\", \"score_native\" "
-                                   "and \"emit_distmap\" (the align block's place in the buffer depends on all three); use "
-                                   "set_align / set_score / set_distmap")
-            if align and structure is not None and _score.as_structure(structure).shape[0] > self.engines[0].max_L:
-                raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {self.engines[0].max_L}")
-            kflags = [e.get_option("search_structures") for e in self.engines]
-            search = kflags[0]
-            if any(kflags) and not (all(k == search for k in kflags) and emit == any(flags) and score == any(sflags)
-                                    and align == any(aflags)):
-                raise RuntimeError("search_structures: the engines of a pipeline must agree on \"search_structures\", "
-                                   "\"align_structure\", \"score_native\" and \"emit_distmap\" (the search block's place in the "
-                                   "buffer depends on all four); use set_search / set_align / set_score / set_distmap")
-            library = self._search if search else None
-            if search and (library is None or len(library) != search):
-                raise RuntimeError(f"search_structures is {search} on the engines: give the library to set_search")
+            # the library cannot check the buffer: it is sized by the options as the engines hold them, whichever way they
+            # were set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
+            flags = agree_options([e.get_option(name) for name in LAYOUT_OPTIONS] for e in self.engines)
+            flags = flags._replace(max_L=self.engines[0].max_L)
+            if flags.align and structure is not None and _score.as_structure(structure).shape[0] > flags.max_L:
+                raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {flags.max_L}")
+            if flags.search and (self._search is None or len(self._search) != flags.search):
+                raise RuntimeError(f"search_structures is {flags.search} on the engines: give the library to set_search")
+            extras = Extras(native=native if flags.score else None, structure=structure if flags.align else None,
+                            library=self._search if flags.search else None)
             # (the native, align and search blocks are written on the current stream: `ready` below is behind it)
-            d_tpl, out = _stage(self.device, L, template_ca, native, emit, score, emit_alloc=any(flags), align=align,
-                                structure=structure, library=library, max_L=self.engines[0].max_L, score_map=smap)
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -816,8 +797,7 @@ class Pipeline:
             self._p, d_msa.data_ptr(), n, L, d_tpl.data_ptr() if d_tpl is not None else None,
             int(max(iterations, 0)), int(max(minsteps, 0)), out.coords.data_ptr(), out.confs.data_ptr(),
             C.c_void_p(ready.cuda_event)))
-        self._jobs[t] = _Job(d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, out, ready, native if score else None,
-                             structure if align else None, library)
+        self._jobs[t] = _Job(d_msa, int(max(iterations, 0)), int(max(minsteps, 0)), d_tpl, out, ready, extras)
         self._reap()
         return t
 
@@ -942,15 +922,16 @@ class Pipeline:
                     out[t] = _lib.DmpError(_lib.load().dmp_last_error().decode("utf-8", "replace") or f"error {rc}")
                     continue
                 if bits:
-                    emit, nat = res.distmap is not None, job.native
-                    if res.score_block is not None and nat is None:
-                        nat = np.full((job.d_msa.shape[1], 3), np.nan, dtype=np.float32)
-                    strc = job.structure
-                    if res.align_block is not None and strc is None:
-                        strc = np.zeros((0, 3), dtype=np.float32)
+                    # what the target ran with, for one engine alone: a block that was there without its input gets the
+                    # input that means "none" (an all-NaN native, a structure of 0 rows)
+                    emit, extras = res.distmap is not None, job.extras
+                    if res.score_block is not None and extras.native is None:
+                        extras = extras._replace(native=np.full((job.d_msa.shape[1], 3), np.nan, dtype=np.float32))
+                    if res.align_block is not None and extras.structure is None:
+                        extras = extras._replace(structure=np.zeros((0, 3), dtype=np.float32))
+                    extras = extras._replace(distmap=emit, score_map=res.map_block is not None)
                     try:
-                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, emit, nat, strc, job.library,
-                                           res.map_block is not None)
+                        rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, extras)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
                         if eng.last_fallback:
                             eng.set_option("conv_mode", 2)
@@ -1080,7 +1061,24 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     is appended behind those (None without a `search`).
     `return_map_scores` (addition; needs `native`): the predicted distance map is scored against the native too (option
     "score_map") and the dict of score.unpack_map_scores is appended last of all."""
-    if return_map_scores and native is None:
+    r = _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
+                      compare_chain, search, distmap=return_distmap, scores=return_scores, alignment=return_alignment,
+                      hits=return_hits, map_scores=return_map_scores)
+    return ((r.coords, r.confs) + ((r.alnmat,) if return_alnmat else ()) + ((r.distmap,) if return_distmap else ())
+            + ((r.scores,) if return_scores else ()) + ((r.alignment,) if return_alignment else ())
+            + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ()))
+
+
+# What `aln_to_coords` computes, by name: each of distmap, scores, alignment, hits and map_scores None unless it was wanted
+# (and, for scores, alignment and hits, unless its input - native, compare, search - was given).
+Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores")
+
+
+def _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
+                  compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False):
+    """`aln_to_coords` -> Prediction; the five flags are its return_distmap, return_scores, return_alignment, return_hits and
+    return_map_scores."""
+    if map_scores and native is None:
         raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
@@ -1103,25 +1101,17 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
         search = _score.Library.open(search)
     if search is not None:
         search.check(MAX_L)
-    scores = alignment = hits = map_scores = None
     with device_lock(dev):                  # re-entrant like the reference's function: callers of one GPU take turns
         # (the engine holds both traces: its capacity covers the structure to align with, too)
         cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
-        out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(return_distmap),
-                                  native=native, structure=compare, library=search, score_map=bool(return_map_scores))
-        if return_map_scores:
-            map_scores = eng.map_scores
-        if search is not None and return_hits:
-            hits = eng.hits
-        if native is not None and return_scores:
-            scores = eng.scores
-        if compare is not None and return_alignment:
-            alignment = eng.alignment
-    coords, confs = out[0], out[1]
-    ret = (coords, confs) + ((alnmat,) if return_alnmat else ()) + ((out[2],) if return_distmap else ())
-    return (ret + ((scores,) if return_scores else ()) + ((alignment,) if return_alignment else ()) + ((hits,) if return_hits else ())
-            + ((map_scores,) if return_map_scores else ()))
+        out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
+                                  native=native, structure=compare, library=search, score_map=bool(map_scores))
+        return Prediction(out[0], out[1], alnmat, out[2] if distmap else None,
+                          map_scores=eng.map_scores if map_scores else None,
+                          hits=eng.hits if search is not None and hits else None,
+                          scores=eng.scores if native is not None and scores else None,
+                          alignment=eng.alignment if compare is not None and alignment else None)
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1202,43 +1192,24 @@ def run_dmpfold(argv=None):
     args = parser.parse_args(argv)
     if args.score_map and args.native is None:
         parser.error("--score-map scores the distance map against a native structure: give --native")
-    out = aln_to_coords(args.input_file, device=args.device,
-                        template=args.template, iterations=args.iterations,
-                        minsteps=args.minsteps, weights_file=args.model_weights,
-                        return_alnmat=True, converge=args.converge, return_distmap=args.distmap is not None,
-                        native=args.native, return_scores=args.native is not None, native_chain=args.native_chain,
-                        compare=args.compare, compare_chain=args.compare_chain, return_alignment=args.compare is not None,
-                        search=args.search, return_hits=args.search is not None, return_map_scores=args.score_map)
-    coords, confs, alnmat = out[:3]
-    map_scores = None
-    if args.score_map:
-        map_scores, out = out[-1], out[:-1]
+    r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
+                      args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
+                      distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
+                      hits=args.search is not None, map_scores=args.score_map)
+
+    def json_line(obj, path):
+        """one JSON line to the file `path`, or to standard error without one"""
+        with (open(path, "w") if path is not None else contextlib.nullcontext(sys.stderr)) as fh:
+            fh.write(json.dumps(obj) + "\n")
     if args.search is not None:
-        line = json.dumps(_score.hits_json(out[-1], out[-1]["names"], args.search_top)) + "\n"
-        out = out[:-1]
-        if args.hits is not None:
-            with open(args.hits, "w") as fh:
-                fh.write(line)
-        else:
-            sys.stderr.write(line)
+        json_line(_score.hits_json(r.hits, r.hits["names"], args.search_top), args.hits)
     if args.distmap is not None:
-        save_distmap_npy(args.distmap, out[3])
+        save_distmap_npy(args.distmap, r.distmap)
     if args.compare is not None:
-        line = json.dumps(_score.alignment_json(out[-1])) + "\n"
-        out = out[:-1]
-        if args.alignment is not None:
-            with open(args.alignment, "w") as fh:
-                fh.write(line)
-        else:
-            sys.stderr.write(line)
+        json_line(_score.alignment_json(r.alignment), args.alignment)
     if args.native is not None:
-        js = _score.scores_json(out[-1])
-        if map_scores is not None:
-            js["map"] = _score.map_scores_json(map_scores)
-        line = json.dumps(js) + "\n"
-        if args.scores is not None:
-            with open(args.scores, "w") as fh:
-                fh.write(line)
-        else:
-            sys.stderr.write(line)
-    sys.stdout.write(pdb_text(coords, confs, alnmat))
+        js = _score.scores_json(r.scores)
+        if r.map_scores is not None:
+            js["map"] = _score.map_scores_json(r.map_scores)
+        json_line(js, args.scores)
+    sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

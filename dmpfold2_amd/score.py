@@ -4,6 +4,9 @@ The library compares the model's C-alpha trace with a native trace that the call
 in the score block behind the confidences.  This module makes that block from a PDB file - parsing, a global sequence
 alignment of the query against the native chain - and takes it apart again.  Nothing here touches the GPU.
 
+`Layout` is the one Python statement of where each block lies in that buffer (the twin of conf_layout() in csrc/common.h);
+conf_floats, score_offset, mapscore_offset, align_offset, search_offset and split_conf_buffer are views of it.
+
 The scores are TM-score, GDT_TS / GDT_HA, Kabsch RMSD and lDDT-C-alpha as include/dmpfold_hip.h defines them: the
 TM-score program's KIND of search over superpositions, not its bits - any superposition gives a lower bound of the true
 maximum, and nobody has compared the values with that program's.
@@ -22,6 +25,22 @@ _THREE_TO_ONE["MSE"] = "M"           # selenomethionine, as structure files of e
 SCORE_HEADER = 24                    # floats between the native trace and the per-residue arrays
 SCORE_NAMES = ("n_pairs", "rmsd", "tm", "gdt_ts", "gdt_ha", "lddt")
 COUNT_CUTOFFS = (0.5, 1.0, 2.0, 4.0, 8.0)
+
+
+def _num(v):
+    """A float for JSON: NaN becomes None."""
+    v = float(v)
+    return v if v == v else None
+
+
+def _whole(v):
+    """A count the library wrote as a float: NaN (a block it answered with NaN) reads as 0."""
+    return int(v) if v == v else 0
+
+
+def _host(block):
+    """A block (array, or tensor on any device) as a float32 array on the host."""
+    return np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
 
 
 def score_floats(L):
@@ -46,33 +65,79 @@ def mapscore_floats(L):
     return MAPSCORE_HEADER + int(L)
 
 
+class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_L",
+                        defaults=(False, False, False, None, None, None))):
+    """Where everything lies in the `d_conf` buffer of a prediction of length L: the Python twin of ConfLayout / conf_layout()
+    / search_base() of csrc/common.h, in the order of include/dmpfold_hip.h.  Made from what decides it - `distmap`, `score`,
+    `score_map`: options "emit_distmap", "score_native", "score_map" on; `align_m`: the m the align block holds (None =
+    "align_structure" off); `search`: (K, M) of option "search_structures" (None = off); `max_L`: the context's, for the rule
+    of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0 counts).  Every offset is stated once,
+    each from the one in front of it:
+
+      [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
+      (64 + L) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
+
+    and `total` is the floats the buffer must hold."""
+    __slots__ = ()
+
+    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None):
+        return super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
+                               None if search is None else (int(search[0]), int(search[1])), max_L)
+
+    info_off = property(lambda s: s.L + (s.L * s.L if s.distmap else 0))
+    score_off = property(lambda s: s.info_off + (3 if s.distmap else 0))                                    # S0
+    mapscore_off = property(lambda s: s.score_off + (score_floats(s.L) if s.score else 0))                  # M0
+    align_off = property(lambda s: s.mapscore_off + (mapscore_floats(s.L) if s.score_map else 0))           # A0
+    # the end of the align block as its writer allocated it (an align_m that is no number raises ValueError) ...
+    align_end = property(lambda s: s.align_off + (align_floats(s.L, s.align_m) if s.align_m is not None else 0))
+    # ... and B0, its end as the library counts it: 3m of it only if m is an integer in [3, max_L]
+    search_off = property(lambda s: s.align_end if s.align_m is None or s.max_L is None
+                          else s.align_off + align_floats(s.L, align_m_rule(s.align_m, s.max_L)))
+    search_end = property(lambda s: s.search_off + (search_floats(s.L, *s.search) if s.search is not None else 0))
+    total = property(lambda s: s.align_end if s.search is None else max(s.align_end, s.search_end))
+
+    def split(self, buf, coords=None):
+        """The parts of a `d_conf` buffer (a 1-D tensor or array of at least `total` floats) as the views of an `Outputs`
+        (`coords` is passed through)."""
+        L = self.L
+        if buf.ndim != 1 or buf.shape[0] < self.total:
+            raise ValueError(f"a d_conf buffer of length {L} has {self.total} floats, got shape {tuple(buf.shape)}")
+
+        def part(on, at, end):
+            return buf[at:end] if on else None
+        return Outputs(coords, buf[:L], buf[L:self.info_off].reshape(L, L) if self.distmap else None,
+                       part(self.distmap, self.info_off, self.score_off), part(self.score, self.score_off, self.mapscore_off),
+                       part(self.align_m is not None, self.align_off, self.align_end),
+                       part(self.search is not None, self.search_off, self.search_end),
+                       part(self.score_map, self.mapscore_off, self.align_off))
+
+
+# The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
 def conf_floats(L, distmap=False, score=False, align_m=None, score_map=False):
     """Floats the `d_conf` buffer of a prediction of length L must hold: the confidences, the L*L + 3 floats of option
     "emit_distmap", the 5L + 24 floats of option "score_native", the 64 + L floats of option "score_map" and, with `align_m`
     (the structure's rows; not None), the 25 + 2L + 3m floats of option "align_structure", in this order."""
-    L = int(L)
-    return (L + (L * L + 3 if distmap else 0) + (score_floats(L) if score else 0) + (mapscore_floats(L) if score_map else 0)
-            + (align_floats(L, align_m) if align_m is not None else 0))
+    return Layout(L, distmap, score, score_map, align_m).total
 
 
 def align_offset(L, distmap=False, score=False, score_map=False):
     """Where the align block begins in the `d_conf` buffer (A0 of include/dmpfold_hip.h)."""
-    return conf_floats(L, distmap, score, None, score_map)
+    return Layout(L, distmap, score, score_map).align_off
 
 
 def mapscore_offset(L, distmap=True, score=True):
     """Where the map-score block begins in the `d_conf` buffer (M0 of include/dmpfold_hip.h): the end of the score block."""
-    return conf_floats(L, distmap, score)
+    return Layout(L, distmap, score).mapscore_off
 
 
 def score_offset(L, distmap=False):
     """Where the score block begins in the `d_conf` buffer (S0 of include/dmpfold_hip.h)."""
-    return conf_floats(L, distmap, False)
+    return Layout(L, distmap).score_off
 
 
 def distmap_floats(L, on=True):
     """Floats the `d_conf` buffer of a prediction of length L must hold: L, or L + L*L + 3 with option "emit_distmap"."""
-    return conf_floats(L, on)
+    return Layout(L, on).total
 
 
 class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block",
@@ -86,23 +151,19 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
     @classmethod
     def of(cls, public, distmap, score, align=False, search=False, score_map=False):
         """The inverse of `public` for a caller that knows which options were on."""
-        public = tuple(public)
-        at = 4 if distmap else 2
-        end = at + (1 if score else 0) + (1 if align else 0) + (1 if search else 0)
-        return cls(*public[:2], *(public[2:4] if distmap else (None, None)), public[at] if score else None,
-                   public[at + (1 if score else 0)] if align else None,
-                   public[at + (1 if score else 0) + (1 if align else 0)] if search else None,
-                   public[end] if score_map else None)
+        rest = iter(public)          # (the fields stand in the tuple's order: the map-score block is the last of both)
+        return cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map)))
 
-    def public(self, distmap=True, score=True, align=True, search=True, score_map=True):
+    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
         block, the align block, the search block and - last, though it lies behind the score block in the buffer - the
-        map-score block, each if present and wanted."""
-        return ((self.coords, self.confs) + ((self.distmap, self.info) if distmap and self.distmap is not None else ())
-                + ((self.score_block,) if score and self.score_block is not None else ())
-                + ((self.align_block,) if align and self.align_block is not None else ())
-                + ((self.search_block,) if search and self.search_block is not None else ())
-                + ((self.map_block,) if score_map and self.map_block is not None else ()))
+        map-score block, each if present and wanted.  `blocks=False`: none of the four blocks, whatever else is said - what
+        a call of an `Engine` returns, `public(distmap, blocks=False)`."""
+        if not blocks:
+            score = align = search = score_map = False
+        groups = ((distmap, (self.distmap, self.info)), (score, (self.score_block,)), (align, (self.align_block,)),
+                  (search, (self.search_block,)), (score_map, (self.map_block,)))
+        return (self.coords, self.confs) + tuple(x for want, group in groups if want and group[0] is not None for x in group)
 
 
 def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None, search=None, score_map=False):
@@ -110,22 +171,7 @@ def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None
     floats) at the offsets of include/dmpfold_hip.h, as the views of an `Outputs` (`coords` is passed through).  `search`:
     (K, M, max_L) of option "search_structures" - the search block then lies at search_offset(L, emit, score, align_m, max_L,
     score_map)."""
-    L = int(L)
-    need = conf_floats(L, emit, score, align_m, score_map)
-    b0 = None
-    if search is not None:
-        b0 = search_offset(L, emit, score, align_m, search[2], score_map)
-        need = max(need, b0 + search_floats(L, search[0], search[1]))
-    if buf.ndim != 1 or buf.shape[0] < need:
-        raise ValueError(f"a d_conf buffer of length {L} has {need} floats, got shape {tuple(buf.shape)}")
-    s0 = score_offset(L, emit)
-    m0 = mapscore_offset(L, emit, score)
-    a0 = align_offset(L, emit, score, score_map)
-    return Outputs(coords, buf[:L], buf[L:L + L * L].reshape(L, L) if emit else None, buf[L + L * L:s0] if emit else None,
-                   buf[s0:s0 + score_floats(L)] if score else None,
-                   buf[a0:a0 + align_floats(L, align_m)] if align_m is not None else None,
-                   buf[b0:b0 + search_floats(L, search[0], search[1])] if search is not None else None,
-                   buf[m0:m0 + mapscore_floats(L)] if score_map else None)
+    return Layout(L, emit, score, score_map, align_m, search and search[:2], search and search[2]).split(buf, coords)
 
 
 def split_distmap_buffer(buf, L):
@@ -133,7 +179,7 @@ def split_distmap_buffer(buf, L):
     confs (L,), distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms] (include/dmpfold_hip.h)."""
     if buf.ndim != 1 or buf.shape[0] != distmap_floats(L):
         raise ValueError(f"an emit_distmap buffer of length {L} has {distmap_floats(L)} floats, got shape {tuple(buf.shape)}")
-    return split_conf_buffer(buf, L, True)[1:4]
+    return Layout(L, True).split(buf)[1:4]
 
 
 def read_native_ca(pdb, chain=None):
@@ -244,7 +290,7 @@ def unpack_scores(block, L):
     counts (5 ints: rows within 0.5, 1, 2, 4, 8 A), R (3, 3) and t (3,) with native ~ R model + t, lddt_res (L,),
     deviation (L,), and the inputs back: lnorm, native (L, 3)."""
     L = int(L)
-    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    b = _host(block)
     if b.ndim != 1 or b.shape[0] != score_floats(L):
         raise ValueError(f"a score block of length {L} has {score_floats(L)} floats, got shape {tuple(b.shape)}")
     h = b[3 * L:]
@@ -264,12 +310,9 @@ def unpack_scores(block, L):
 def scores_json(scores):
     """The scalar part of `unpack_scores` as a JSON-ready dict (what `dmpfold --native` prints and `dmpfold-batch --natives`
     writes); NaN becomes None."""
-    def num(v):
-        v = float(v)
-        return v if v == v else None
-    out = {"n_pairs": int(scores["n_pairs"]), "lnorm": num(scores["lnorm"])}
+    out = {"n_pairs": int(scores["n_pairs"]), "lnorm": _num(scores["lnorm"])}
     for name in SCORE_NAMES[1:]:
-        out[name] = num(scores[name])
+        out[name] = _num(scores[name])
     out["counts"] = [int(c) for c in scores["counts"]]
     return out
 
@@ -297,21 +340,18 @@ def unpack_map_scores(block, L):
     native_contacts), f1_8A - NaN where the denominator is 0.  A block the library answered with NaN (a latched fault) gives
     zero counts and NaN floats."""
     L = int(L)
-    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    b = _host(block)
     if b.ndim != 1 or b.shape[0] != mapscore_floats(L):
         raise ValueError(f"a map-score block of length {L} has {mapscore_floats(L)} floats, got shape {tuple(b.shape)}")
-
-    def whole(v):
-        return int(v) if v == v else 0
-    out = {"n": whole(b[0]), "ln": float(b[1]), "pairs": whole(b[50])}
+    out = {"n": _whole(b[0]), "ln": float(b[1]), "pairs": _whole(b[50])}
     for k, name in enumerate(MAP_NAMES):
         out[name] = float(b[51 + k])
     out["map_lddt_res"] = b[MAPSCORE_HEADER:].copy()
     out["classes"] = {}
     for c, cname in enumerate(MAP_CLASSES):
         s = b[2 + 12 * c:14 + 12 * c]
-        cl = {"candidates": whole(s[0]), "native_contacts": whole(s[1]), "hits": [whole(v) for v in s[2:5]],
-              "taken": [whole(v) for v in s[5:8]], "tp": whole(s[8]), "predicted": whole(s[9])}
+        cl = {"candidates": _whole(s[0]), "native_contacts": _whole(s[1]), "hits": [_whole(v) for v in s[2:5]],
+              "taken": [_whole(v) for v in s[5:8]], "tp": _whole(s[8]), "predicted": _whole(s[9])}
         cl["precision"] = [_ratio(h, t) for h, t in zip(cl["hits"], cl["taken"])]
         p, r = _ratio(cl["tp"], cl["predicted"]), _ratio(cl["tp"], cl["native_contacts"])
         cl["precision_8A"], cl["recall_8A"] = p, r
@@ -323,19 +363,16 @@ def unpack_map_scores(block, L):
 def map_scores_json(ms):
     """`unpack_map_scores` without the per-residue array as a JSON-ready dict (the value of "map" in what `dmpfold --native
     --score-map` prints and `dmpfold-batch --natives --score-map` writes); NaN becomes None."""
-    def num(v):
-        v = float(v)
-        return v if v == v else None
-    out = {"n": int(ms["n"]), "ln": num(ms["ln"]), "pairs": int(ms["pairs"])}
+    out = {"n": int(ms["n"]), "ln": _num(ms["ln"]), "pairs": int(ms["pairs"])}
     for name in MAP_NAMES:
-        out[name] = num(ms[name])
+        out[name] = _num(ms[name])
     for cname in MAP_CLASSES:
         cl = ms["classes"][cname]
         out[cname] = {k: ([int(v) for v in cl[k]] if isinstance(cl[k], list) else int(cl[k]))
                       for k in ("candidates", "native_contacts", "hits", "taken", "tp", "predicted")}
-        out[cname]["precision"] = dict(zip(MAP_LISTS, (num(v) for v in cl["precision"])))
+        out[cname]["precision"] = dict(zip(MAP_LISTS, (_num(v) for v in cl["precision"])))
         for k in ("precision_8A", "recall_8A", "f1_8A"):
-            out[cname][k] = num(cl[k])
+            out[cname][k] = _num(cl[k])
     return out
 
 
@@ -385,17 +422,14 @@ def unpack_alignment(block, L):
     with model residue i, or -1 -, deviation (L,), and the inputs back: m, structure (m, 3).  A block the library answered
     with NaN (a bad m, a NaN coordinate, a fault) gives n_ali 0, NaN floats and ali all -1."""
     L = int(L)
-    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    b = _host(block)
     m = (b.shape[0] - (1 + ALIGN_HEADER + 2 * L)) // 3 if b.ndim == 1 else -1
     if m < 0 or b.shape[0] != align_floats(L, m):
         raise ValueError(f"an align block of length {L} has 25 + 2L + 3m floats, got shape {tuple(b.shape)}")
     h = b[1:1 + ALIGN_HEADER]
-
-    def whole(v):
-        return int(v) if v == v else 0
-    out = {"n_ali": whole(h[0]), "rmsd_ali": float(h[1]), "tm_model": float(h[2]), "tm_struct": float(h[3]),
+    out = {"n_ali": _whole(h[0]), "rmsd_ali": float(h[1]), "tm_model": float(h[2]), "tm_struct": float(h[3]),
            "R": h[4:13].reshape(3, 3).copy(), "t": h[13:16].copy(), "d0_model": float(h[16]), "d0_struct": float(h[17]),
-           "seed_offset": whole(h[18]), "seeds": whole(h[19])}
+           "seed_offset": _whole(h[18]), "seeds": _whole(h[19])}
     ali = b[1 + ALIGN_HEADER:1 + ALIGN_HEADER + L]
     out["ali"] = np.where(ali == ali, ali, -1.0).astype(np.int64)
     out["deviation"] = b[1 + ALIGN_HEADER + L:1 + ALIGN_HEADER + 2 * L].copy()
@@ -407,14 +441,11 @@ def unpack_alignment(block, L):
 def alignment_json(al):
     """`unpack_alignment` as a JSON-ready dict (what `dmpfold --compare` prints and `dmpfold-batch --structures` writes):
     the header fields, R, t and ali; NaN becomes None."""
-    def num(v):
-        v = float(v)
-        return v if v == v else None
-    out = {"m": num(al["m"])}
+    out = {"m": _num(al["m"])}
     for name in ALIGN_NAMES:
-        out[name] = int(al[name]) if name in ("n_ali", "seed_offset", "seeds") else num(al[name])
-    out["R"] = [[num(v) for v in row] for row in np.asarray(al["R"])]
-    out["t"] = [num(v) for v in np.asarray(al["t"])]
+        out[name] = int(al[name]) if name in ("n_ali", "seed_offset", "seeds") else _num(al[name])
+    out["R"] = [[_num(v) for v in row] for row in np.asarray(al["R"])]
+    out["t"] = [_num(v) for v in np.asarray(al["t"])]
     out["ali"] = [int(v) for v in al["ali"]]
     return out
 
@@ -445,10 +476,7 @@ def search_offset(L, distmap=False, score=False, align_m=None, max_L=None, score
     """Where the search block begins in the `d_conf` buffer (B0 of include/dmpfold_hip.h): the end of what the other options
     give.  `align_m`: the m the align block holds (None = "align_structure" off); the library counts 3m of it only if it is
     an integer in [3, `max_L`] (`max_L` None: whatever the block's writer allocated, i.e. any whole m >= 0 counts)."""
-    if align_m is None:
-        return conf_floats(L, distmap, score, None, score_map)
-    mp = int(align_m) if max_L is None else align_m_rule(align_m, max_L)
-    return conf_floats(L, distmap, score, mp, score_map)
+    return Layout(L, distmap, score, score_map, align_m, None, max_L).search_off
 
 
 class Library:
@@ -553,7 +581,7 @@ def unpack_search(block, L, lengths):
     L = int(L)
     lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     K, M = lengths.shape[0], int(lengths.sum())
-    b = np.asarray(block.detach().cpu().numpy() if hasattr(block, "detach") else block, dtype=np.float32)
+    b = _host(block)
     if b.ndim != 1 or b.shape[0] != search_floats(L, K, M):
         raise ValueError(f"a search block of length {L}, {K} entries, {M} rows has {search_floats(L, K, M)} floats, got shape {tuple(b.shape)}")
     hdr, res, tr = 2 * K, (2 + ALIGN_HEADER) * K, (2 + ALIGN_HEADER) * K + 2 * L * K
@@ -577,13 +605,10 @@ def host_rank(tm):
 def hits_json(search, names, top=10):
     """`unpack_search` as a JSON-ready dict (what `dmpfold --search` prints and `dmpfold-batch --library` writes): the best
     `top` entries in rank order, each with name, tm_model, tm_struct, rmsd_ali, n_ali, R, t; NaN becomes None."""
-    def num(v):
-        v = float(v)
-        return v if v == v else None
     out = []
     for k in [int(k) for k in search["rank"][:max(int(top), 0)]]:
         h = search["hits"][k]
-        out.append({"name": str(names[k]), "index": k, "tm_model": num(h["tm_model"]), "tm_struct": num(h["tm_struct"]),
-                    "rmsd_ali": num(h["rmsd_ali"]), "n_ali": int(h["n_ali"]),
-                    "R": [[num(v) for v in row] for row in np.asarray(h["R"])], "t": [num(v) for v in np.asarray(h["t"])]})
+        out.append({"name": str(names[k]), "index": k, "tm_model": _num(h["tm_model"]), "tm_struct": _num(h["tm_struct"]),
+                    "rmsd_ali": _num(h["rmsd_ali"]), "n_ali": int(h["n_ali"]),
+                    "R": [[_num(v) for v in row] for row in np.asarray(h["R"])], "t": [_num(v) for v in np.asarray(h["t"])]})
     return {"entries": len(names), "hits": out}

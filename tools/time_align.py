@@ -64,7 +64,7 @@ def measure(L, args, weights):
     eng.set_weights(weights)
     d_msa = torch.from_numpy(np.ascontiguousarray(alnmat)).to(eng.device)
     coords = torch.empty((L, 5, 3), dtype=torch.float32, device=eng.device)
-    conf = torch.empty((S.conf_floats(L, False, False, L),), dtype=torch.float32, device=eng.device)
+    conf = torch.empty((S.Layout(L, align_m=L).total,), dtype=torch.float32, device=eng.device)
     end_ms(eng, d_msa, coords, conf)
     structure = gapped_copy(coords[:, 1].cpu().numpy(), L)
     assert structure.shape == (L, 3)

@@ -65,7 +65,8 @@ def measure(L, args, weights):
     eng.set_weights(weights)
     d_msa = torch.from_numpy(np.ascontiguousarray(alnmat)).to(eng.device)
     coords = torch.empty((L, 5, 3), dtype=torch.float32, device=eng.device)
-    conf = torch.empty((S.conf_floats(L, True, True, None, True),), dtype=torch.float32, device=eng.device)
+    lay = S.Layout(L, distmap=True, score=True, score_map=True)
+    conf = torch.empty((lay.total,), dtype=torch.float32, device=eng.device)
     set_options(eng, SETTINGS[0])
     end_ms(eng, d_msa, coords, conf)
     model = coords[:, 1].cpu().numpy()
@@ -78,8 +79,7 @@ def measure(L, args, weights):
     native = model.astype(np.float64) @ R.T + 7.0 + rng.normal(scale=1.5 / np.sqrt(3.0), size=model.shape)
     native[L // 3:L // 3 + L // 8] += 9.0
     native = native.astype(np.float32)
-    s0, m0 = S.score_offset(L, True), S.mapscore_offset(L)
-    conf[s0:m0] = torch.from_numpy(S.pack_native(native, 0.0, L)).to(eng.device)
+    conf[lay.score_off:lay.mapscore_off] = torch.from_numpy(S.pack_native(native, 0.0, L)).to(eng.device)
     ts = [[], [], []]
     for rep in range(args.repeats + 2):
         for k, names in enumerate(SETTINGS):
@@ -89,7 +89,7 @@ def measure(L, args, weights):
                 ts[k].append(t)
     set_options(eng, ())
     med = [float(np.median(t)) for t in ts]
-    ms = S.unpack_map_scores(conf[m0:m0 + S.mapscore_floats(L)], L)
+    ms = S.unpack_map_scores(lay.split(conf).map_block, L)
     line = ("L=%d precision %d, medians of %d: dmp_predict_end with emit_distmap %.3f ms (min %.3f, max %.3f); + score_native %.3f ms "
             "(min %.3f, max %.3f): its own cost %+.3f ms; + score_map %.3f ms (min %.3f, max %.3f): its cost %+.3f ms; "
             "map_lddt %.4f mae %.3f long L/5 %d of %d"

@@ -51,7 +51,7 @@ def measure(L, args, weights):
     eng.set_weights(weights)
     d_msa = torch.from_numpy(np.ascontiguousarray(alnmat)).to(eng.device)
     coords = torch.empty((L, 5, 3), dtype=torch.float32, device=eng.device)
-    conf = torch.empty((S.conf_floats(L, False, True),), dtype=torch.float32, device=eng.device)
+    conf = torch.empty((S.Layout(L, score=True).total,), dtype=torch.float32, device=eng.device)
     end_ms(eng, d_msa, coords, conf)
     model = coords[:, 1].cpu().numpy()
     rng = np.random.default_rng(L)
