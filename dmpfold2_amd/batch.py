@@ -145,7 +145,7 @@ def ca_only_text(coords, confs, alnmat):
 
 
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
-                 hits=None, hits_top=10, map_scores=None):
+                 hits=None, hits_top=10, map_scores=None, pass_scores=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
@@ -158,7 +158,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     score.unpack_map_scores, --natives --score-map; only beside `scores`): npz gains map_n, map_ln, map_pairs, map_lddt,
     map_mae, map_rmse, map_bias, map_lddt_res and map_counts (int32 (4, 10): per class short, medium, long, medium + long the
     candidates, native contacts, hits and taken of the lists L, L/2, L/5, true positives and predicted contacts at 8 A);
-    <stem>.scores.json gains the key "map"."""
+    <stem>.scores.json gains the key "map".  With `pass_scores` (the dict of score.unpack_pass_scores, --natives
+    --score-passes; only beside `scores`): npz gains pass_rows, pass_best, pass_tm_best, pass_lddt_best (int32, -1 for none),
+    pass_regret_tm, pass_regret_lddt and one float32 array (R,) per column, pass_conf_mean, pass_delta, pass_tm, pass_gdt_ts,
+    pass_gdt_ha, pass_rmsd, pass_lddt; <stem>.scores.json gains the key "passes"."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -180,6 +183,12 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
                                                     + [cl["tp"], cl["predicted"]]
                                                     for cl in (map_scores["classes"][c] for c in _score.MAP_CLASSES)], dtype=np.int32)})
             extra.update({k: np.float32(map_scores[k]) for k in _score.MAP_NAMES})
+        if pass_scores is not None:
+            extra.update({"pass_rows": np.int32(pass_scores["rows"]), "pass_regret_tm": np.float32(pass_scores["regret_tm"]),
+                          "pass_regret_lddt": np.float32(pass_scores["regret_lddt"])})
+            extra.update({"pass_" + k: np.int32(-1 if pass_scores[name] is None else pass_scores[name])
+                          for k, name in (("best", "best_pass"), ("tm_best", "tm_pass"), ("lddt_best", "lddt_pass"))})
+            extra.update({"pass_" + k: np.asarray(pass_scores[k], dtype=np.float32) for k in _score.PASS_COLUMNS})
         if alignment is not None:
             extra.update({k: (np.int32 if k in ("n_ali", "seed_offset", "seeds") else np.float32)(alignment[k])
                           for k in _score.ALIGN_NAMES})
@@ -201,6 +210,8 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             js = _score.scores_json(scores)
             if map_scores is not None:
                 js["map"] = _score.map_scores_json(map_scores)
+            if pass_scores is not None:
+                js["passes"] = _score.pass_scores_json(pass_scores)
             fh.write(json.dumps(js) + "\n")
     if alignment is not None:
         with open(stem + ".alignment.json", "w") as fh:
@@ -257,13 +268,15 @@ def cost_order(targets, iterations):
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
               converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10,
-              score_map=False):
+              score_map=False, score_passes=False):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
     unscored.  `stats_out` then receives "scores": {stem: the dict of score.scores_json}.
     `score_map` (needs `natives`): a scored target's predicted distance map is scored against its native too
     (Pipeline.set_score_map); its scores gain the key "map" (score.map_scores_json) wherever they are written.
+    `score_passes` (needs `natives`): every recycling pass of a scored target is scored against its native too
+    (Pipeline.set_score_passes); its scores gain the key "passes" (score.pass_scores_json) wherever they are written.
     `structures`: a directory of structures of any length and sequence, <stem>.pdb for the target <stem>.aln / .a3m: such a
     target's model is aligned with the structure's first chain on the GPU (Pipeline.set_align) and the alignment is written
     with it (write_result); a target without a file is predicted without one.  `stats_out` then receives "alignments":
@@ -284,6 +297,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         raise ValueError(f"unknown output format {fmt!r} (pdb, ca, npz)")
     if score_map and not natives:
         raise ValueError("score_map scores the distance maps against native structures: give `natives`")
+    if score_passes and not natives:
+        raise ValueError("score_passes scores every pass against native structures: give `natives`")
     check_output_stems(targets)
     os.makedirs(out_dir, exist_ok=True)
     # sharding needs only (L, N) estimates from a header scan: a rank parses its own targets and nobody else's
@@ -342,6 +357,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_score(True)
             if score_map:
                 pipe.set_score_map(True)          # (turns the distance map on: it is written only with `distmap`)
+            if score_passes:
+                pipe.set_score_passes(True)
             if structures:
                 pipe.set_align(True)
             if library is not None:
@@ -384,15 +401,18 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
         out = Outputs.of(public, distmap=distmap or score_map, score=bool(natives), align=bool(structures), search=library is not None,
-                         score_map=score_map)
+                         score_map=score_map, passes=score_passes)
         aln_path, alnmat, _ = parsed.pop(t)
-        sc = ms = None
+        sc = ms = ps = None
         if out.score_block is not None and t in scored:
             sc = _score.unpack_scores(out.score_block, alnmat.shape[1])
             js = _score.scores_json(sc)
             if out.map_block is not None:
                 ms = _score.unpack_map_scores(out.map_block, alnmat.shape[1])
                 js["map"] = _score.map_scores_json(ms)
+            if out.pass_block is not None:
+                ps = _score.unpack_pass_scores(out.pass_block, _score.pass_rows(iterations))
+                js["passes"] = _score.pass_scores_json(ps)
             all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = js
         al = None
         if out.align_block is not None and t in aligned:
@@ -405,7 +425,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             all_hits[os.path.splitext(os.path.basename(aln_path))[0]] = [
                 {k: v for k, v in h.items() if k not in ("R", "t")} for h in _score.hits_json(hits, library.names, search_top)["hits"]]
         outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap if distmap else None,
-                                    out.info if distmap else None, sc, al, hits, search_top, ms))
+                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps))
 
     def finish(item):
         t, public = item
@@ -557,6 +577,12 @@ def batch_parser():
                          "(contact precision of the top L, L/2, L/5 per separation class, lDDT and distance error of the map); "
                          "the summary's scores gain the key \"map\" with means and medians of its figures, npz gains the map_* "
                          "arrays, <stem>.scores.json gains \"map\"")
+    ap.add_argument("--score-passes", action="store_true",
+                    help="with --natives: score every recycling pass of every such target against its native on the GPU (per "
+                         "pass: mean confidence logit, convergence delta, TM-score, GDT, RMSD, lDDT-CA); the summary's scores "
+                         "gain the key \"passes\" and the summary the share of targets whose chosen pass was the best one, the "
+                         "regrets, the mean TM-score by pass and what each convergence tolerance would have cost; npz gains the "
+                         "pass_* arrays, <stem>.scores.json gains \"passes\"")
     ap.add_argument("--structures", default=None, metavar="DIR",
                     help="directory of structures of any length and sequence, <stem>.pdb per target: such a target's model is "
                          "aligned with the structure's first chain on the GPU (structural alignment, TM-scores by both lengths); "
@@ -569,6 +595,42 @@ def batch_parser():
                          "<stem>.hits.json")
     ap.add_argument("--search-top", type=int, default=10, metavar="N", help="hits per target to report with --library (default 10)")
     return ap
+
+
+CONVERGE_SWEEP = (0.05, 0.1, 0.2, 0.5, 1.0)          # Angstrom: the tolerances the summary of --score-passes tries
+
+
+def pass_summary(tables, tolerances=CONVERGE_SWEEP):
+    """{stem: the dict of score.pass_scores_json} of full-depth runs -> the summary's part for --score-passes, over the
+    targets whose table holds a pass and a TM-score: how often the pass the confidence picked was the best by TM-score, mean
+    and median of the regrets, the mean TM-score by pass index (each over the targets that ran that pass), and the
+    convergence sweep - per tolerance the mean passes score.simulate_converge says a `--converge` run would have run and
+    the mean TM-score lost against the full-depth choice (tm of the pass kept at full depth minus tm of the pass kept by
+    the stop, both from the table)."""
+    tabs = [_score.pass_scores_from_json(t) for t in tables.values()]
+    tabs = [t for t in tabs if t["rows"] > 0 and t["tm_pass"] is not None]
+    out = {"pass_scored_targets": len(tabs)}
+    if not tabs:
+        return out
+    out["best_is_tm_pass"] = float(np.mean([t["best_pass"] == t["tm_pass"] for t in tabs]))
+    for name in ("regret_tm", "regret_lddt"):
+        vals = [t[name] for t in tabs if t[name] == t[name]]
+        out["mean_" + name] = float(np.mean(vals)) if vals else None
+        out["median_" + name] = float(np.median(vals)) if vals else None
+    depth = max(t["rows"] for t in tabs)
+    by_pass = [[float(t["tm"][p]) for t in tabs if p < t["rows"] and t["tm"][p] == t["tm"][p]] for p in range(depth)]
+    out["mean_tm_by_pass"] = [float(np.mean(v)) if v else None for v in by_pass]
+    sweep = []
+    for tol in tolerances:
+        runs, lost = [], []
+        for t in tabs:
+            full = _score.simulate_converge(t["conf_mean"], t["delta"], None)
+            run, best = _score.simulate_converge(t["conf_mean"], t["delta"], tol)
+            runs.append(run)
+            lost.append(float(t["tm"][full[1]]) - float(t["tm"][best]))
+        sweep.append({"tol": tol, "mean_passes": float(np.mean(runs)), "mean_tm_lost": float(np.mean(lost))})
+    out["converge_sweep"] = sweep
+    return out
 
 
 def score_summary(scores):
@@ -586,6 +648,9 @@ def score_summary(scores):
             vals = [f[name] for f in flat.values() if f.get(name) is not None]
             out["mean_" + name] = float(np.mean(vals)) if vals else None
             out["median_" + name] = float(np.median(vals)) if vals else None
+    tables = {stem: s["passes"] for stem, s in scores.items() if s.get("passes") is not None}
+    if tables:                                       # --score-passes: the pass tables' aggregates
+        out.update(pass_summary(tables))
     return out
 
 
@@ -596,6 +661,9 @@ def main(argv=None):
         ap.error("give -l targets.txt and / or -i alignments ...")
     if args.score_map and not args.natives:
         ap.error("--score-map scores the distance maps against native structures: give --natives DIR")
+
+    if args.score_passes and not args.natives:
+        ap.error("--score-passes scores every pass against native structures: give --natives DIR")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -620,7 +688,7 @@ def main(argv=None):
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
                                   structures=args.structures, library=args.library, search_top=args.search_top,
-                                  score_map=args.score_map)
+                                  score_map=args.score_map, score_passes=args.score_passes)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)

@@ -407,8 +407,9 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // the fault bits are latched into the word dmp_sync_faults reports.
 // `lay`: the d_conf buffer of this prediction (common.h) - the confidences and, with option "emit_distmap", the whole extension
 // become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
-// caller's and stay.  The map-score block of option "score_map" lies between the score block's end (lay.smap_off) and
-// lay.align_off and is all outputs: the range [lay.score_out, lay.align_off) below takes it in.  The same for the align block
+// caller's and stay.  The map-score block of option "score_map" and the pass block of option "score_passes" lie between the
+// score block's end (lay.smap_off) and lay.align_off and are all outputs: the range [lay.score_out, lay.align_off) below
+// takes them in.  The same for the align block
 // of option "align_structure": its out slots become NaN, m in front of them and the structure's trace behind them (past
 // lay.total) stay.  (The search block of option "search_structures" lies at an offset only the device knows: search_rank,
 // the launch in front of this one, reads the same word and does the same there.)
@@ -452,6 +453,28 @@ static int search_reserve(dmp_ctx* c) {
   c->bytes += need - c->search_ws_bytes;
   c->search_ws = (unsigned char*)p;
   c->search_ws_bytes = need;
+  return DMP_OK;
+}
+
+// Option "score_passes": the scratch of a chunk of passes, allocated when the option first becomes 1 on a context and counted
+// in "device_mib" (score.hip has its layout).  The tickets in front are zero between launches.
+static int passes_reserve(dmp_ctx* c) {
+  if (c->pass_ws) return DMP_OK;
+  const int64_t need = score_passes_bytes(c->max_L);
+  int prev = 0;
+  DMP_HIP(hipGetDevice(&prev));
+  DMP_HIP(hipSetDevice(c->device));
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, (size_t)need);
+  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)score_passes_head_bytes());
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (p) (void)hipFree(p);
+    return hip_fail(e, "pass-score scratch", __FILE__, __LINE__);
+  }
+  c->bytes += need;
+  c->pass_ws = (unsigned char*)p;
+  c->pass_ws_bytes = need;
   return DMP_OK;
 }
 
@@ -662,6 +685,20 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->opt.smap = value;
     return DMP_OK;
   }
+  if (k == "score_passes") {         // takes effect with the next prediction begun, which needs "score_native" on
+    DMP_ARG(value == 0 || value == 1, "score_passes must be 0 or 1, got %d", value);
+    if (value) {
+      const int rc = passes_reserve(ctx);           // a failure leaves the option as it was
+      if (rc) return rc;
+    }
+    ctx->opt.passes = value;
+    return DMP_OK;
+  }
+  if (k == "score_passes_chunk") {   // tests only: at most this many passes per chunk (0 = what the budget gives)
+    DMP_ARG(value >= 0, "score_passes_chunk must be >= 0, got %d", value);
+    ctx->opt.passes_chunk = value;
+    return DMP_OK;
+  }
   if (k == "align_structure") {      // takes effect with the next prediction begun
     DMP_ARG(value == 0 || value == 1, "align_structure must be 0 or 1, got %d", value);
     ctx->opt.align = value;
@@ -733,6 +770,8 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "emit_distmap") { *h_value = ctx->opt.emit; return DMP_OK; }
   if (k == "score_native") { *h_value = ctx->opt.score; return DMP_OK; }
   if (k == "score_map") { *h_value = ctx->opt.smap; return DMP_OK; }
+  if (k == "score_passes") { *h_value = ctx->opt.passes; return DMP_OK; }
+  if (k == "score_passes_chunk") { *h_value = ctx->opt.passes_chunk; return DMP_OK; }
   if (k == "align_structure") { *h_value = ctx->opt.align; return DMP_OK; }
   if (k == "search_structures") { *h_value = ctx->opt.search; return DMP_OK; }
   if (k == "search_max_m") { *h_value = ctx->opt.search_mm; return DMP_OK; }
@@ -767,6 +806,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->search_ws) (void)hipFree(c->search_ws);
+  if (c->pass_ws) (void)hipFree(c->pass_ws);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
   for (void* e : c->unit_ev)
@@ -1296,6 +1336,7 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   dmp_ctx* c = ctx;
   DMP_ARG(!c->opt.smap || c->opt.emit, "score_map scores the map of option emit_distmap, which is 0: set emit_distmap to 1");
   DMP_ARG(!c->opt.smap || c->opt.score, "score_map reads the native trace of option score_native, which is 0: set score_native to 1");
+  DMP_ARG(!c->opt.passes || c->opt.score, "score_passes scores every pass against the native trace of option score_native, which is 0: set score_native to 1");
   DMP_ARG(c->vg_waiters == 0, "members of the vertical-GRU group this context led have not taken their results yet");
   DMP_ARG(c->vg_leader == nullptr || c->vg_leader == c, "this context still waits for the vertical GRU of its group");
   c->vg_leader = nullptr;
@@ -1312,6 +1353,7 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   c->run = c->opt;
   c->gate_pass = 0;
   c->run_nloops = nloops < 0 ? 0 : nloops;
+  c->run_depth = c->run_nloops;
   c->run_refine = refine_steps < 0 ? 0 : refine_steps;
   c->run_msa = d_msa;
   c->run_template = d_template_ca;
@@ -1507,13 +1549,18 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // (tools/isa_lint.py).
   rc = ca_to_backbone(c->best_ca, c->best_conf, L, d_coords, d_conf, s);
   if (rc) return rc;
-  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align, c->run.smap);
+  // option "score_passes": R rows, one per pass the prediction was asked for; those of the passes that ran hold a pass
+  // (run_depth: a convergence stop shortens run_nloops, the caller sized the buffer from what it asked for)
+  const int pass_R = c->run.passes ? std::min(c->run_depth + 1, c->max_passes) : 0;
+  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align, c->run.smap, pass_R);
   // option "emit_distmap": the map and {best_pass, passes_run, map_rms} behind the confidences
   if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map_off, d_conf + lay.info_off, s))) return rc;
   // option "score_native": the score block behind that, the native trace and lnorm in it (score.hip)
   if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score_off, s))) return rc;
   // option "score_map": the map-score block behind that, from best_dm and the score block's inputs (mapscore.hip)
   if (c->run.smap && (rc = score_map(c, L, d_conf + lay.score_off, d_conf + lay.smap_off, s))) return rc;
+  // option "score_passes": the pass block behind that, from ca_pass, conf_means and what score_native packed (score.hip)
+  if (pass_R && (rc = score_passes(c, L, pass_R, std::min(c->passes_done, c->max_passes), d_conf + lay.pass_off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align_off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

@@ -72,16 +72,21 @@ __host__ __device__ inline AlignLayout align_layout(int L) { return {1 + ALIGN_H
 //   and the align block.
 constexpr int MAPSCORE_HEADER = 64;
 __host__ __device__ inline int mapscore_floats(int L) { return MAPSCORE_HEADER + L; }
-// score_off: the end of what "emit_distmap" gives; smap_off: the end of the score block; align_off: the end of the map-score
-// block; align_out / total: the align block's out slots (total does not count its trailing input, whose length only the
-// caller knows)
-struct ConfLayout { int64_t map_off, info_off, score_off, score_out, smap_off, align_off, align_out, total; };
-__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0, int smap = 0) {
+//   | with "score_passes": the pass block = PASS_HEADER floats | R rows of PASS_ROW floats, R = min(nloops + 1, max_passes),
+//   all of it out, between the map-score block and the align block.
+constexpr int PASS_HEADER = 16, PASS_ROW = 8, PASS_MAX = 128;
+__host__ __device__ inline int pass_floats(int R) { return PASS_HEADER + PASS_ROW * R; }
+// score_off: the end of what "emit_distmap" gives; smap_off: the end of the score block; pass_off: the end of the map-score
+// block; align_off: the end of the pass block (`passes`: its rows R, 0 = none); align_out / total: the align block's out slots
+// (total does not count its trailing input, whose length only the caller knows)
+struct ConfLayout { int64_t map_off, info_off, score_off, score_out, smap_off, align_off, align_out, total, pass_off; };
+__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0, int smap = 0, int passes = 0) {
   const int64_t info_off = L + (emit ? (int64_t)L * L : 0), score_off = info_off + (emit ? 3 : 0);
   const int64_t smap_off = score_off + (score ? score_layout(L).total : 0);
-  const int64_t align_off = smap_off + (smap ? mapscore_floats(L) : 0);
+  const int64_t pass_off = smap_off + (smap ? mapscore_floats(L) : 0);
+  const int64_t align_off = pass_off + (passes ? pass_floats(passes) : 0);
   return {L, info_off, score_off, score_off + score_layout(L).out, smap_off, align_off, align_off + 1,
-          align_off + (align ? align_layout(L).in : 0)};
+          align_off + (align ? align_layout(L).in : 0), pass_off};
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -200,14 +205,15 @@ struct dmp_lane {
 };
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "score_map"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0; };
+// "score_map", "score_passes", "score_passes_chunk"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0; };
 
 struct dmp_ctx {
   int device = 0;
   dmp_lane* lane = nullptr;                // = lane_hold.get()
   std::shared_ptr<dmp_lane> lane_hold;     // dmp_ctx_share_lane: the lane lives as long as a context refers to it
   int run_nloops = 0, run_refine = 0;
+  int run_depth = 0;                       // run_nloops as the prediction began with it (a convergence stop lowers run_nloops)
   int max_L = 0, max_N = 0;
   int64_t bytes = 0;
   dmp::Weights W;
@@ -360,6 +366,10 @@ struct dmp_ctx {
   unsigned char* search_ws = nullptr;
   int64_t search_ws_bytes = 0;
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
+  // option "score_passes": one allocation made when the option first becomes 1 (api.hip: passes_reserve) - the tickets and
+  // the delta's partial sums, then the slots of a chunk of passes (score.hip: pass_slot)
+  unsigned char* pass_ws = nullptr;
+  int64_t pass_ws_bytes = 0;
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -632,10 +642,18 @@ int fill_f32(float* d, int64_t n, float v, hipStream_t s);
 int select_best(dmp_ctx* c, const float* d_conf, const float* d_ca, int L, int pass, int rec_cap,
                 hipStream_t s);
 int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, hipStream_t s);
+// option "score_passes": d_p of passes 1 .. rows - 1 from ca_pass, into offset 1 of each row of the pass block (rows at d_rows)
+int pass_deltas(dmp_ctx* c, int L, int rows, float* d_rows, double* d_partial, unsigned* d_counter, hipStream_t s);
 int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
 int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_map, float* d_info, hipStream_t s);
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
+// option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
+// before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
+constexpr int64_t PASS_BUDGET = (int64_t)DMP_PASSES_BUDGET_MIB << 20;
+int64_t score_passes_bytes(int max_L);          // the scratch a context of this capacity needs
+int64_t score_passes_head_bytes();              // ... of which the part that is zero between launches (in front)
+int score_passes(dmp_ctx* c, int L, int R, int rows, float* d_block, hipStream_t s);
 // option "score_map" (mapscore.hip): best_dm against the native trace of the score block, into the map-score block
 int score_map(dmp_ctx* c, int L, const float* d_score_block, float* d_block, hipStream_t s);
 constexpr int ALIGN_SURVIVORS = 16; // seeds of the gapless threading that the dynamic programme refines (align.hip)

@@ -153,6 +153,30 @@ __host__ __device__ inline int recycle_delta_groups(int L) {
   return g < 1 ? 1 : (g > RD_MAX_WG ? RD_MAX_WG : g);
 }
 
+// The one statement of d_p, which recycle_delta_kernel and pass_delta_kernel (option "score_passes") both evaluate: this
+// thread's share of the pair sum over the two traces in LDS - workgroup blockIdx.x of gridDim.x, the same grid width in both
+// kernels - and the value from the grid's total.
+__device__ __forceinline__ double recycle_delta_pairs(const float* xa, const float* xb, int L) {
+  const int tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+  double acc = 0.0;
+  for (int i = g; i < L - 1; i += G) {
+    const double ax = xa[3 * i], ay = xa[3 * i + 1], az = xa[3 * i + 2];
+    const double bx = xb[3 * i], by = xb[3 * i + 1], bz = xb[3 * i + 2];
+    for (int j = i + 1 + tid; j < L; j += RD_THREADS) {
+      const double ux = (double)xa[3 * j] - ax, uy = (double)xa[3 * j + 1] - ay, uz = (double)xa[3 * j + 2] - az;
+      const double vx = (double)xb[3 * j] - bx, vy = (double)xb[3 * j + 1] - by, vz = (double)xb[3 * j + 2] - bz;
+      const double da = sqrt(fmax((ux * ux + uy * uy) + uz * uz, 1e-8));
+      const double db = sqrt(fmax((vx * vx + vy * vy) + vz * vz, 1e-8));
+      const double e = da - db;
+      acc += e * e;
+    }
+  }
+  return acc;
+}
+__device__ __forceinline__ float recycle_delta_value(double sum, int L) {
+  return (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
+}
+
 struct RecycleDeltaArgs {
   const float* ca;       // [L][3] this pass's trace
   const float* seed;     // [L][3] the trace whose distance map seeded this pass (null: pass 0, no delta)
@@ -168,7 +192,7 @@ struct RecycleDeltaArgs {
 __global__ __launch_bounds__(RD_THREADS) void recycle_delta_kernel(RecycleDeltaArgs a) {
   extern __shared__ float sm[];          // 2 x 3L coordinates
   __shared__ double red[RD_THREADS];
-  const int L = a.L, tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
+  const int L = a.L, tid = threadIdx.x, g = blockIdx.x;
   if (g == 0)
     for (int i = tid; i < 3 * L; i += RD_THREADS) a.keep[i] = a.ca[i];
   if (!a.seed) {                         // pass 0 (one workgroup): nothing to compare with
@@ -182,22 +206,10 @@ __global__ __launch_bounds__(RD_THREADS) void recycle_delta_kernel(RecycleDeltaA
   float* xb = sm + 3 * L;
   for (int i = tid; i < 3 * L; i += RD_THREADS) { xa[i] = a.ca[i]; xb[i] = a.seed[i]; }
   __syncthreads();
-  double acc = 0.0;
-  for (int i = g; i < L - 1; i += G) {
-    const double ax = xa[3 * i], ay = xa[3 * i + 1], az = xa[3 * i + 2];
-    const double bx = xb[3 * i], by = xb[3 * i + 1], bz = xb[3 * i + 2];
-    for (int j = i + 1 + tid; j < L; j += RD_THREADS) {
-      const double ux = (double)xa[3 * j] - ax, uy = (double)xa[3 * j + 1] - ay, uz = (double)xa[3 * j + 2] - az;
-      const double vx = (double)xb[3 * j] - bx, vy = (double)xb[3 * j + 1] - by, vz = (double)xb[3 * j + 2] - bz;
-      const double da = sqrt(fmax((ux * ux + uy * uy) + uz * uz, 1e-8));
-      const double db = sqrt(fmax((vx * vx + vy * vy) + vz * vz, 1e-8));
-      const double e = da - db;
-      acc += e * e;
-    }
-  }
+  const double acc = recycle_delta_pairs(xa, xb, L);
   double sum;
   if (grid_sum_f64<RD_THREADS>(acc, red, a.partial, a.counter, &sum)) {
-    const float d = (float)sqrt(sum / (0.5 * (double)L * (double)(L - 1)));
+    const float d = recycle_delta_value(sum, L);
     if (a.pass < a.rec_cap) a.pass_delta[a.pass] = d;
     const int stop = d <= a.tol ? 1 : 0;           // false for NaN
     *a.host_word = ((a.pass + 1) << 1) | stop;
@@ -217,6 +229,41 @@ int recycle_delta(dmp_ctx* c, const float* d_ca, int L, int pass, int rec_cap, h
   a.host_word = c->delta_host;
   const int G = pass > 0 ? recycle_delta_groups(L) : 1;
   hipLaunchKernelGGL(recycle_delta_kernel, dim3(G), dim3(RD_THREADS), pass > 0 ? sizeof(float) * 6 * L : 0, s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// Option "score_passes": d_p of every recorded pass p >= 1 in one launch at the prediction's end, the pass as blockIdx.y.
+// select_best recorded in ca_pass[p - 1] the very trace recycle_delta keeps as pass p's seed (pass 0's after its
+// minimiser steps), so the operands, the grid width, the sums' order and with them the bits are those of pass_delta[p] -
+// whether or not "recycle_tol_mA" ran.  Each pass has its own partial sums and its own ticket.
+struct PassDeltaArgs {
+  const float* ca_pass;  // [rows][L][3]
+  int L;
+  float* rows;           // the pass block's rows: d_p goes to rows[PASS_ROW * p + 1]
+  double* partial;       // [rows][RD_MAX_WG]
+  unsigned* counter;     // [rows] zero between launches
+};
+
+__global__ __launch_bounds__(RD_THREADS) void pass_delta_kernel(PassDeltaArgs a) {
+  extern __shared__ float sm[];          // 2 x 3L coordinates
+  __shared__ double red[RD_THREADS];
+  const int L = a.L, tid = threadIdx.x, p = (int)blockIdx.y + 1;
+  float* xa = sm;
+  float* xb = sm + 3 * L;
+  const float* ca = a.ca_pass + (int64_t)p * 3 * L;
+  for (int i = tid; i < 3 * L; i += RD_THREADS) { xa[i] = ca[i]; xb[i] = ca[i - 3 * L]; }
+  __syncthreads();
+  const double acc = recycle_delta_pairs(xa, xb, L);
+  double sum;
+  if (grid_sum_f64<RD_THREADS>(acc, red, a.partial + (int64_t)p * RD_MAX_WG, a.counter + p, &sum))
+    a.rows[PASS_ROW * p + 1] = recycle_delta_value(sum, L);
+}
+
+int pass_deltas(dmp_ctx* c, int L, int rows, float* d_rows, double* d_partial, unsigned* d_counter, hipStream_t s) {
+  if (rows < 2) return DMP_OK;
+  PassDeltaArgs a{c->ca_pass, L, d_rows, d_partial, d_counter};
+  hipLaunchKernelGGL(pass_delta_kernel, dim3(recycle_delta_groups(L), rows - 1), dim3(RD_THREADS), sizeof(float) * 6 * L, s, a);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

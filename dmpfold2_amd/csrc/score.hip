@@ -5,6 +5,8 @@
 //   score_lddt    rows dealt to the workgroups: integer counts, so lDDT is exact and order-free.
 //   score_search  one workgroup per seed of the superposition search; the last arriver (agent-scope ticket, common.h)
 //                 reduces the seeds' records in seed order and writes the header and the deviations.
+// Option "score_passes" (at the end of this file) runs score_lddt and score_search over the recorded passes' traces, the pass
+// as blockIdx.y, with the native that score_prep packed.
 // Float64 from the float32 coordinates throughout; every sum has a fixed per-thread order, a fixed butterfly inside a
 // wave (both partners of an exchange form a + b, so all 64 lanes hold the same bits) and a fixed order over the four
 // waves' partial sums in LDS: the same bits on every run, and every thread of a workgroup takes the same branch.
@@ -49,17 +51,26 @@ __device__ inline double score_dist(const float* a, const float* b) {
 }
 
 
+// One description for both uses.  "score_native": one model trace (atom 1 of the backbone: `model` = d_coords + 3, 15 floats
+// between rows), a grid with gridDim.y = 1, `rows` null, the results into the score block.  "score_passes": the model traces
+// are ca_pass[pass0 + blockIdx.y] (3 floats between rows, 3L between traces); the packed native, the row index and the
+// header are the ones score_prep made for the score block of the same call; every pass has its own packed model, totals,
+// records and ticket (`*_stride` apart), and its five scores go to its row of the pass block.
 struct ScoreArgs {
-  const float* coords;   // [L][5][3] the backbone; the model trace is atom 1
+  const float* model;    // the model trace's first row
+  int model_row;         // floats between its rows
+  int64_t model_stride;  // floats between the traces of consecutive passes
   float* blk;            // the score block: [0, 3L) native (in), 3L lnorm (in), the rest out
   int L;
-  float* pm;             // [n][3] packed model trace
+  float* pm;             // [n][3] packed model trace (pass y: + y * pm_stride)
   float* qn;             // [n][3] packed native trace
   int* idx;              // [n] alignment column of a packed row
   double* hdr;           // [8]
-  double* rec;           // [seeds][SCORE_REC]
-  unsigned long long* tot;   // [2] lDDT: preserved, pairs
-  unsigned* ticket;      // zero between launches
+  double* rec;           // [seeds][SCORE_REC] (pass y: + y * rec_stride)
+  unsigned long long* tot;   // [2] lDDT: preserved, pairs (pass y: + y * tot_stride)
+  unsigned* ticket;      // zero between launches (pass y: + y)
+  int64_t pm_stride, rec_stride, tot_stride;
+  float* rows;           // null, or row 0 of this launch's passes in the pass block
 };
 
 // ---------------------------------------------------------------------------------------
@@ -86,7 +97,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_prep_kernel(ScoreArgs a) {
     const float x = a.blk[3 * i];
     if (x == x) {
       for (int c = 0; c < 3; ++c) {
-        a.pm[3 * at + c] = a.coords[15 * (int64_t)i + 3 + c];
+        a.pm[3 * at + c] = a.model[a.model_row * (int64_t)i + c];
         a.qn[3 * at + c] = a.blk[3 * i + c];
       }
       a.idx[at] = i;
@@ -110,6 +121,21 @@ __global__ __launch_bounds__(SC_THREADS) void score_prep_kernel(ScoreArgs a) {
   }
 }
 
+// score_pass_prep: pass blockIdx.y's trace packed by the row index score_prep left; its lDDT totals cleared
+__global__ __launch_bounds__(SC_THREADS) void score_pass_prep_kernel(ScoreArgs a) {
+  const int n = (int)a.hdr[HDR_N], y = blockIdx.y;
+  const int k = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (k < n) {
+    const float* src = a.model + y * a.model_stride + a.model_row * (int64_t)a.idx[k];
+    float* dst = a.pm + y * a.pm_stride + 3 * k;
+    for (int c = 0; c < 3; ++c) dst[c] = src[c];
+  }
+  if (k == 0) {
+    a.tot[y * a.tot_stride] = 0ull;
+    a.tot[y * a.tot_stride + 1] = 0ull;
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // score_lddt: superposition-free, integer counts
 // ---------------------------------------------------------------------------------------
@@ -125,9 +151,11 @@ __global__ __launch_bounds__(SC_THREADS) void score_lddt_kernel(ScoreArgs a) {
   if (n < 3) return;                     // every out slot but n_pairs stays NaN
   float* pm = sm;
   float* qn = sm + 3 * n;
-  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = a.pm[i]; qn[i] = a.qn[i]; }
+  const float* gpm = a.pm + blockIdx.y * a.pm_stride;
+  unsigned long long* tot = a.tot + blockIdx.y * a.tot_stride;
+  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = gpm[i]; qn[i] = a.qn[i]; }
   __syncthreads();
-  float* out = a.blk + score_layout(L).lddt_res;
+  float* out = a.rows ? nullptr : a.blk + score_layout(L).lddt_res;     // the passes have no per-residue arrays
   unsigned long long tot_pres = 0ull, tot_part = 0ull;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     int pres = 0, part = 0;
@@ -150,14 +178,14 @@ __global__ __launch_bounds__(SC_THREADS) void score_lddt_kernel(ScoreArgs a) {
     if (tid == 0) {
       pres = part = 0;
       for (int k = 0; k < SC_WAVES; ++k) { pres += ired[k][0]; part += ired[k][1]; }
-      out[a.idx[i]] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
+      if (out) out[a.idx[i]] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
       tot_pres += (unsigned long long)pres;
       tot_part += (unsigned long long)part;
     }
   }
   if (tid == 0) {
-    __hip_atomic_fetch_add(&a.tot[0], tot_pres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(&a.tot[1], tot_part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&tot[0], tot_pres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&tot[1], tot_part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -187,7 +215,10 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   float* pm = sm;
   float* qn = sm + 3 * n;
   unsigned char* fl = reinterpret_cast<unsigned char*>(sm + 6 * n);
-  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = a.pm[i]; qn[i] = a.qn[i]; }
+  const float* gpm = a.pm + blockIdx.y * a.pm_stride;
+  double* grec = a.rec + blockIdx.y * a.rec_stride;
+  unsigned* ticket = a.ticket + blockIdx.y;
+  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = gpm[i]; qn[i] = a.qn[i]; }
   for (int k = tid; k < n; k += SC_THREADS) fl[k] = (k >= start && k < start + frag) ? 1 : 0;
   __syncthreads();
 
@@ -198,13 +229,13 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   const double *best_R = best.R, *best_t = best.t, *best_cnt = best.cnt;
 
   if (tid == 0) {
-    double* rec = a.rec + (int64_t)blockIdx.x * SCORE_REC;
+    double* rec = grec + (int64_t)blockIdx.x * SCORE_REC;
     agent_store_f64(rec + REC_TM, best_tm);
     for (int c = 0; c < 5; ++c) agent_store_f64(rec + REC_CNT + c, best_cnt[c]);
     for (int c = 0; c < 9; ++c) agent_store_f64(rec + REC_R + c, best_R[c]);
     for (int c = 0; c < 3; ++c) agent_store_f64(rec + REC_T + c, best_t[c]);
     agent_store_f64(rec + REC_RMSD, rmsd);
-    sh_last = ticket_take_last(a.ticket, (unsigned)nseeds) ? 1 : 0;     // every record is behind its owner's release
+    sh_last = ticket_take_last(ticket, (unsigned)nseeds) ? 1 : 0;     // every record is behind its owner's release
     if (sh_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
   __syncthreads();
@@ -216,7 +247,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   int top_seed = 0x7fffffff;
   double cmax[5] = {0, 0, 0, 0, 0};
   for (int s = tid; s < nseeds; s += SC_THREADS) {
-    double* rec = a.rec + (int64_t)s * SCORE_REC;
+    double* rec = grec + (int64_t)s * SCORE_REC;
     const double tm = agent_load_f64(rec + REC_TM);
     if (tm > top) { top = tm; top_seed = s; }          // s rises: the first of equals stays
     for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], agent_load_f64(rec + REC_CNT + c));
@@ -239,27 +270,35 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
       if (wred[k][0] > top || (wred[k][0] == top && sh_seed[k] < top_seed)) { top = wred[k][0]; top_seed = sh_seed[k]; }
       for (int c = 0; c < 5; ++c) cmax[c] = fmax(cmax[c], wred[k][1 + c]);
     }
-    float* out = a.blk + score_layout(L).lnorm;        // the header
     const float nan = __builtin_nanf("");
     const bool found = top_seed != 0x7fffffff;         // false only if every seed's tm is NaN
-    double* rec = a.rec + (int64_t)(found ? top_seed : 0) * SCORE_REC;
-    out[2] = (float)agent_load_f64(a.rec + REC_RMSD);
-    out[3] = found ? (float)top : nan;
-    out[4] = (float)((((cmax[1] + cmax[2]) + cmax[3]) + cmax[4]) / 4.0 / lnorm);
-    out[5] = (float)((((cmax[0] + cmax[1]) + cmax[2]) + cmax[3]) / 4.0 / lnorm);
-    const unsigned long long pres = a.tot[0], part = a.tot[1];     // score_lddt ran before this launch
-    out[6] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
-    for (int c = 0; c < 5; ++c) out[7 + c] = (float)cmax[c];
-    for (int c = 0; c < 12; ++c) {
-      const double v = agent_load_f64(rec + REC_R + c);
-      bc[c] = v;
-      out[12 + c] = found ? (float)v : nan;
+    double* rec = grec + (int64_t)(found ? top_seed : 0) * SCORE_REC;
+    const float f_rmsd = (float)agent_load_f64(grec + REC_RMSD);
+    const float f_tm = found ? (float)top : nan;
+    const float f_ts = (float)((((cmax[1] + cmax[2]) + cmax[3]) + cmax[4]) / 4.0 / lnorm);
+    const float f_ha = (float)((((cmax[0] + cmax[1]) + cmax[2]) + cmax[3]) / 4.0 / lnorm);
+    const unsigned long long* tot = a.tot + blockIdx.y * a.tot_stride;
+    const unsigned long long pres = tot[0], part = tot[1];         // score_lddt ran before this launch
+    const float f_lddt = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
+    if (a.rows) {                                      // a pass: its five scores into its row, nothing else
+      float* row = a.rows + PASS_ROW * (int64_t)blockIdx.y;
+      row[2] = f_tm; row[3] = f_ts; row[4] = f_ha; row[5] = f_rmsd; row[6] = f_lddt;
+      sh_last = 0;
+    } else {
+      float* out = a.blk + score_layout(L).lnorm;      // the header
+      out[2] = f_rmsd; out[3] = f_tm; out[4] = f_ts; out[5] = f_ha; out[6] = f_lddt;
+      for (int c = 0; c < 5; ++c) out[7 + c] = (float)cmax[c];
+      for (int c = 0; c < 12; ++c) {
+        const double v = agent_load_f64(rec + REC_R + c);
+        bc[c] = v;
+        out[12 + c] = found ? (float)v : nan;
+      }
+      sh_last = found ? 1 : 0;
     }
-    sh_last = found ? 1 : 0;
-    ticket_reset(a.ticket);
+    ticket_reset(ticket);
   }
   __syncthreads();
-  if (!sh_last) return;                                // the deviations stay NaN
+  if (!sh_last) return;                                // the deviations stay NaN (a pass has none)
   double R[9], t[3];
   for (int c = 0; c < 9; ++c) R[c] = bc[c];
   for (int c = 0; c < 3; ++c) t[c] = bc[9 + c];
@@ -269,7 +308,8 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
 
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
   ScoreArgs a{};
-  a.coords = d_coords;
+  a.model = d_coords + 3;
+  a.model_row = 15;
   a.blk = d_block;
   a.L = L;
   a.pm = c->score_pm;
@@ -285,6 +325,114 @@ int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipSt
   DMP_LAUNCH_CHECK();
   // the records hold 6 max_L seeds >= 1 + 5L; 6L floats + L flags of LDS: 50 KB at L = 2048
   hipLaunchKernelGGL(score_search_kernel, dim3(score_seeds(L)), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// option "score_passes": the pass block (include/dmpfold_hip.h)
+// ---------------------------------------------------------------------------------------
+// The scratch (dmp_ctx::pass_ws).  In front, at places that do not depend on L and zero between launches: PASS_MAX tickets
+// of the search, PASS_MAX tickets of the delta; then the delta's partial sums [PASS_MAX][64]; then the slots of a chunk.  A
+// slot is one pass's working set: the seed records, the packed trace, the lDDT totals (every part 16-aligned).
+constexpr int64_t PASS_TICKET_BYTES = 2 * 4 * (int64_t)PASS_MAX;
+constexpr int64_t PASS_HEAD_BYTES = PASS_TICKET_BYTES + 8 * 64 * (int64_t)PASS_MAX;
+struct PassSlot { int64_t rec, pm, tot, total; };
+inline PassSlot pass_slot(int L) {
+  auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
+  PassSlot p;
+  p.rec = 0;
+  p.pm = up(8 * (int64_t)SCORE_REC * score_seeds(L));
+  p.tot = p.pm + up(12 * (int64_t)L);
+  p.total = p.tot + 16;
+  return p;
+}
+// passes per chunk: as many slots as the budget holds, 1 .. PASS_MAX; `cap` > 0 (option "score_passes_chunk") lowers it
+inline int pass_chunk(int L, int cap) {
+  int64_t C = PASS_BUDGET / pass_slot(L).total;
+  C = C < 1 ? 1 : (C > PASS_MAX ? PASS_MAX : C);
+  return cap > 0 && cap < C ? cap : (int)C;
+}
+int64_t score_passes_head_bytes() { return PASS_TICKET_BYTES; }
+int64_t score_passes_bytes(int max_L) {
+  int64_t need = 0;
+  for (int L = 8; L <= max_L; ++L) need = std::max<int64_t>(need, pass_chunk(L, 0) * pass_slot(L).total);
+  return PASS_HEAD_BYTES + need;
+}
+
+// pass_fill: what the block holds before the scores arrive.  Row p < rows: conf_mean, delta (+inf for pass 0; pass_deltas
+// fills in the others), NaN in the five scores, zero; row p >= rows: NaN.  The header is pass_header's.
+__global__ __launch_bounds__(SC_THREADS) void pass_fill_kernel(float* blk, int R, int rows, const float* conf_means) {
+  const float nan = __builtin_nanf("");
+  for (int i = threadIdx.x; i < pass_floats(R); i += SC_THREADS) {
+    float v = 0.f;
+    if (i >= PASS_HEADER) {
+      const int p = (i - PASS_HEADER) / PASS_ROW, q = (i - PASS_HEADER) % PASS_ROW;
+      v = p >= rows ? nan : q == 0 ? conf_means[p] : q == 1 ? (p == 0 ? __builtin_inff() : nan) : q == 7 ? 0.f : nan;
+    }
+    blk[i] = v;
+  }
+}
+
+// pass_header: one thread reads the finished rows in pass order (at most 128 of them)
+__global__ void pass_header_kernel(float* blk, int rows, const float* best_pass) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float nan = __builtin_nanf("");
+  const float* row = blk + PASS_HEADER;
+  const float bp = best_pass[0];
+  const int b = bp < (float)PASS_MAX ? (int)bp : -1;   // best_pass < passes_run, so a pass below the cap has a row
+  blk[0] = (float)rows;
+  blk[1] = bp;
+  for (int q = 0; q < 2; ++q) {                        // tm (offset 2 of a row), then lddt (offset 6)
+    const int o = q == 0 ? 2 : 6;
+    int top = -1;
+    for (int p = 0; p < rows; ++p) {
+      const float v = row[PASS_ROW * p + o];
+      if (v == v && (top < 0 || v > row[PASS_ROW * top + o])) top = p;       // strict: the lowest of equals stays
+    }
+    blk[2 + q] = top < 0 ? nan : (float)top;
+    const float vb = b >= 0 && b < rows ? row[PASS_ROW * b + o] : nan;
+    blk[4 + q] = top >= 0 && vb == vb ? row[PASS_ROW * top + o] - vb : nan;
+  }
+}
+
+int score_passes(dmp_ctx* c, int L, int R, int rows, float* d_block, hipStream_t s) {
+  unsigned* tickets = reinterpret_cast<unsigned*>(c->pass_ws);
+  double* partial = reinterpret_cast<double*>(c->pass_ws + PASS_TICKET_BYTES);
+  unsigned char* slots = c->pass_ws + PASS_HEAD_BYTES;
+  float* d_rows = d_block + PASS_HEADER;
+  hipLaunchKernelGGL(pass_fill_kernel, dim3(1), dim3(SC_THREADS), 0, s, d_block, R, rows, c->conf_means);
+  DMP_LAUNCH_CHECK();
+  int rc = pass_deltas(c, L, rows, d_rows, partial, tickets + PASS_MAX, s);
+  if (rc) return rc;
+  const PassSlot sl = pass_slot(L);
+  const int C = pass_chunk(L, c->run.passes_chunk);
+  ScoreArgs a{};
+  a.model_row = 3;
+  a.model_stride = 3 * (int64_t)L;
+  a.L = L;
+  a.qn = c->score_qn;                                  // score_native of this call left them: the same native, the same rows
+  a.idx = c->score_idx;
+  a.hdr = c->score_hdr;
+  a.rec = reinterpret_cast<double*>(slots + sl.rec);
+  a.pm = reinterpret_cast<float*>(slots + sl.pm);
+  a.tot = reinterpret_cast<unsigned long long*>(slots + sl.tot);
+  a.ticket = tickets;
+  a.rec_stride = sl.total / 8;
+  a.pm_stride = sl.total / 4;
+  a.tot_stride = sl.total / 8;
+  for (int p0 = 0; p0 < rows; p0 += C) {               // the chunks reuse the slots: the stream orders them
+    const int np = std::min(C, rows - p0);
+    a.model = c->ca_pass + (int64_t)p0 * 3 * L;
+    a.rows = d_rows + PASS_ROW * (int64_t)p0;
+    hipLaunchKernelGGL(score_pass_prep_kernel, dim3(cdiv(L, SC_THREADS), np), dim3(SC_THREADS), 0, s, a);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(score_lddt_kernel, dim3(score_lddt_groups(L), np), dim3(SC_THREADS), sizeof(float) * 6 * L, s, a);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(score_search_kernel, dim3(score_seeds(L), np), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
+    DMP_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(pass_header_kernel, dim3(1), dim3(64), 0, s, d_block, rows, c->best_pass);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

@@ -233,9 +233,11 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-class Extras(namedtuple("Extras", "distmap native structure library score_map", defaults=(False, None, None, None, False))):
+class Extras(namedtuple("Extras", "distmap native structure library score_map score_passes",
+                        defaults=(False, None, None, None, False, False))):
     """What one call asks for besides the prediction itself, as `Engine.predict` documents each: `distmap` (return the
-    map), `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map).
+    map), `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map),
+    `score_passes` (score every recycling pass).
     The public methods build one in their first lines; everything below them takes and carries the record."""
     __slots__ = ()
 
@@ -245,8 +247,19 @@ LAYOUT_OPTIONS = ("emit_distmap", "score_native", "score_map", "align_structure"
 
 # The layout options as one prediction runs with them: `emit` .. `align` bools, `search` the K of "search_structures";
 # `alloc`: size the buffer as if "emit_distmap" were on (a pipeline whose engines disagree on that option alone);
-# `max_L`: the context's, for the rule of B0.
-Flags = namedtuple("Flags", "emit alloc score score_map align search max_L", defaults=(None,))
+# `max_L`: the context's, for the rule of B0; `passes`: the rows R of the pass block of "score_passes" (None = off), which
+# follow the prediction's own depth.
+Flags = namedtuple("Flags", "emit alloc score score_map align search max_L passes", defaults=(None, None))
+
+
+def agree_passes(values, score, iterations):
+    """The `passes` of a prediction's Flags from option "score_passes" as every engine that may run it holds it: they must
+    agree, and the option needs "score_native" (`score`) - RuntimeError if not.  -> R = score.pass_rows(iterations), or None."""
+    values = [bool(v) for v in values]
+    if any(v != values[0] for v in values) or (values[0] and not score):
+        raise RuntimeError("the engines must agree on \"score_passes\", and it needs \"score_native\" on; use set_score_passes")
+    return _score.pass_rows(iterations) if values[0] else None
+
 
 
 def agree_options(rows):
@@ -285,7 +298,7 @@ def _stage(device, L, template_ca, flags, extras):
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L)
+                 flags.max_L, passes=flags.passes)
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
     if library is not None:
@@ -368,8 +381,12 @@ class Engine:
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
                 minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                score_map=False):
+                score_map=False, score_passes=False):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `score_passes` (needs `native`): every recycling pass's trace - not only the one the best-of rule kept - is scored
+        against the native on the GPU (option "score_passes", set for this call only together with "score_native"), with
+        its mean confidence logit and its convergence delta beside the scores; what the call returns does not change, the
+        table is in `pass_scores`.
         `score_map` (needs `native`): the chosen pass's predicted distance map is scored against the native too (option
         "score_map", set for this call only together with "emit_distmap" and "score_native"): contact precision of the top
         L, L/2 and L/5 per separation class and the map's own distance agreement; what the call returns does not change,
@@ -393,7 +410,7 @@ class Engine:
         after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
         call synchronises with the GPU once per pass."""
-        extras = Extras(distmap, native, structure, library, score_map)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes)
         return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
 
     def _forget_last(self):
@@ -402,6 +419,7 @@ class Engine:
     # The blocks of the last prediction on the GPU, views of the buffer handed to the library; None where the option was off.
     score_block = property(lambda self: self._last.out.score_block, doc='"score_native": 5L + 24 floats, or None')
     map_score_block = property(lambda self: self._last.out.map_block, doc='"score_map": 64 + L floats, or None')
+    pass_block = property(lambda self: self._last.out.pass_block, doc='"score_passes": 16 + 8R floats, or None')
     align_block = property(lambda self: self._last.out.align_block, doc='"align_structure": 25 + 2L + 3m floats, or None')
     search_block = property(lambda self: self._last.out.search_block, doc='"search_structures": 26K + 2LK + 3M floats, or None')
 
@@ -418,6 +436,13 @@ class Engine:
         """The map scores of the last prediction as score.unpack_map_scores gives them, None if it ran without option
         "score_map".  Synchronises with the GPU."""
         return self._unpacked("map_block", _score.unpack_map_scores)
+
+    @property
+    def pass_scores(self):
+        """The pass table of the last prediction as score.unpack_pass_scores gives it, None if it ran without option
+        "score_passes".  Synchronises with the GPU."""
+        return self._unpacked("pass_block", lambda block, L: _score.unpack_pass_scores(
+            block, (block.shape[0] - _score.PASS_HEADER) // _score.PASS_ROW))
 
     @property
     def hits(self):
@@ -446,9 +471,9 @@ class Engine:
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                       score_map=False):
+                       score_map=False, score_passes=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        extras = Extras(distmap, native, structure, library, score_map)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes)
         return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras)
 
     def _upload(self, alnmat):
@@ -471,8 +496,12 @@ class Engine:
             want["emit_distmap"] = 1
         if extras.score_map and not self.get_option("score_map"):
             want["score_map"] = 1                         # (the library looks at the three together when the prediction begins)
+        if extras.score_passes and extras.native is None and not self.get_option("score_native"):
+            raise ValueError("score_passes scores every pass against a native structure: give `native`")
         if extras.native is not None and not self.get_option("score_native"):
             want["score_native"] = 1
+        if extras.score_passes and not self.get_option("score_passes"):
+            want["score_passes"] = 1                      # (behind "score_native", which the library asks for at begin)
         if extras.structure is not None and not self.get_option("align_structure"):
             _score.as_structure(extras.structure)                                          # (a bad shape raises before anything changes)
             want["align_structure"] = 1
@@ -506,7 +535,8 @@ class Engine:
         if L < 8:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
-        flags = Flags(bool(emit), bool(emit), bool(score), bool(smap and emit and score), bool(align), search, self.max_L)
+        flags = Flags(bool(emit), bool(emit), bool(score), bool(smap and emit and score), bool(align), search, self.max_L,
+                      agree_passes([self.get_option("score_passes")], score, iterations))
         with torch.cuda.device(self.device):
             self._forget_last()
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
@@ -552,21 +582,22 @@ class Engine:
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
                         minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                        score_map=False):
+                        score_map=False, score_passes=False):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
         which has float32's range, at about half the convolution rate."""
-        extras = Extras(distmap, native, structure, library, score_map)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes)
         out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
         return out.public(extras.distmap, blocks=False)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
                                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                               score_map=False):
+                               score_map=False, score_passes=False):
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
-        `score_map`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment and hits)."""
-        extras = Extras(distmap, native, structure, library, score_map)
+        `score_map`, `score_passes`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment
+        and hits)."""
+        extras = Extras(distmap, native, structure, library, score_map, score_passes)
         return self._checked(d_msa, template_ca, iterations, minsteps, converge, extras).public(extras.distmap, blocks=False)
 
     def _checked(self, d_msa, template_ca, iterations, minsteps, converge, extras):
@@ -647,7 +678,7 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False, score=False, align=False, search=None, score_map=False):
+                 distmap=False, score=False, align=False, search=None, score_map=False, score_passes=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -661,7 +692,10 @@ class Pipeline:
         `search` (a score.Library): every target is aligned with every entry of it (`set_search`); its search block (26K + 2LK
         + 3M floats, score.unpack_search) is then the last element of all.
         `score_map`: every target's distance map is scored against its native too (`set_score_map`, which turns `distmap`
-        and `score` on); its map-score block (64 + L floats, score.unpack_map_scores) then comes behind even the search block."""
+        and `score` on); its map-score block (64 + L floats, score.unpack_map_scores) then comes behind even the search block.
+        `score_passes`: every recycling pass of every target is scored against its native (`set_score_passes`, which turns
+        `score` on); its pass block (16 + 8R floats, R = min(iterations + 1, 128) of that submission,
+        score.unpack_pass_scores) is then the last element of all."""
         self.lib = _lib.load()
         self._search = None
         self.device = _resolve_device(device)
@@ -695,6 +729,8 @@ class Pipeline:
             self.set_search(search)
         if score_map:
             self.set_score_map(True)
+        if score_passes:
+            self.set_score_passes(True)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -724,6 +760,14 @@ class Pipeline:
             self.set_distmap(True)
             self.set_score(True)
         self.set_option("score_map", 1 if on else 0)
+
+    def set_score_passes(self, on):
+        """Option "score_passes" on every engine: every recycling pass of targets submitted from now on is scored against the
+        `native` given to `submit`.  Turning it on turns "score_native" on, which it needs; turning it off leaves that as it
+        is.  Idle pipeline only."""
+        if on:
+            self.set_score(True)
+        self.set_option("score_passes", 1 if on else 0)
 
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
@@ -774,7 +818,8 @@ class Pipeline:
             # the library cannot check the buffer: it is sized by the options as the engines hold them, whichever way they
             # were set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
             flags = agree_options([e.get_option(name) for name in LAYOUT_OPTIONS] for e in self.engines)
-            flags = flags._replace(max_L=self.engines[0].max_L)
+            flags = flags._replace(max_L=self.engines[0].max_L,
+                                   passes=agree_passes([e.get_option("score_passes") for e in self.engines], flags.score, iterations))
             if flags.align and structure is not None and _score.as_structure(structure).shape[0] > flags.max_L:
                 raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {flags.max_L}")
             if flags.search and (self._search is None or len(self._search) != flags.search):
@@ -929,7 +974,8 @@ class Pipeline:
                         extras = extras._replace(native=np.full((job.d_msa.shape[1], 3), np.nan, dtype=np.float32))
                     if res.align_block is not None and extras.structure is None:
                         extras = extras._replace(structure=np.zeros((0, 3), dtype=np.float32))
-                    extras = extras._replace(distmap=emit, score_map=res.map_block is not None)
+                    extras = extras._replace(distmap=emit, score_map=res.map_block is not None,
+                                             score_passes=res.pass_block is not None)
                     try:
                         rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, extras)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
@@ -1043,7 +1089,8 @@ def get_engine(device, L, N, weights_file=None, state_dict=None):
 def aln_to_coords(input_file, device=default_device, template=None, iterations=default_iterations,
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
                   return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
-                  compare_chain=None, return_alignment=False, search=None, return_hits=False, return_map_scores=False):
+                  compare_chain=None, return_alignment=False, search=None, return_hits=False, return_map_scores=False,
+                  return_pass_scores=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -1060,26 +1107,32 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     with every entry on the GPU (option "search_structures").  With `return_hits` the dict of Engine.hits (hits, rank, names)
     is appended behind those (None without a `search`).
     `return_map_scores` (addition; needs `native`): the predicted distance map is scored against the native too (option
-    "score_map") and the dict of score.unpack_map_scores is appended last of all."""
+    "score_map") and the dict of score.unpack_map_scores is appended behind those.
+    `return_pass_scores` (addition; needs `native`): every recycling pass is scored against the native (option
+    "score_passes") and the dict of score.unpack_pass_scores is appended last of all."""
     r = _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                       compare_chain, search, distmap=return_distmap, scores=return_scores, alignment=return_alignment,
-                      hits=return_hits, map_scores=return_map_scores)
+                      hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores)
     return ((r.coords, r.confs) + ((r.alnmat,) if return_alnmat else ()) + ((r.distmap,) if return_distmap else ())
             + ((r.scores,) if return_scores else ()) + ((r.alignment,) if return_alignment else ())
-            + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ()))
+            + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ())
+            + ((r.pass_scores,) if return_pass_scores else ()))
 
 
 # What `aln_to_coords` computes, by name: each of distmap, scores, alignment, hits and map_scores None unless it was wanted
 # (and, for scores, alignment and hits, unless its input - native, compare, search - was given).
-Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores")
+Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores", defaults=(None,))
 
 
 def _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
-                  compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False):
-    """`aln_to_coords` -> Prediction; the five flags are its return_distmap, return_scores, return_alignment, return_hits and
-    return_map_scores."""
+                  compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
+                  pass_scores=False):
+    """`aln_to_coords` -> Prediction; the six flags are its return_distmap, return_scores, return_alignment, return_hits,
+    return_map_scores and return_pass_scores."""
     if map_scores and native is None:
         raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
+    if pass_scores and native is None:
+        raise ValueError("return_pass_scores scores every pass against a native structure: give `native`")
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -1106,9 +1159,11 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
         cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
-                                  native=native, structure=compare, library=search, score_map=bool(map_scores))
+                                  native=native, structure=compare, library=search, score_map=bool(map_scores),
+                                  score_passes=bool(pass_scores))
         return Prediction(out[0], out[1], alnmat, out[2] if distmap else None,
                           map_scores=eng.map_scores if map_scores else None,
+                          pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
                           scores=eng.scores if native is not None and scores else None,
                           alignment=eng.alignment if compare is not None and alignment else None)
@@ -1135,7 +1190,8 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --compare and --search."""
+    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --score-passes, --compare
+    and --search."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -1165,6 +1221,10 @@ def dmpfold_parser():
                         help="with --native: also score the predicted distance map against the native on the GPU (contact precision "
                              "of the top L, L/2, L/5 per separation class, lDDT and distance error of the map); the JSON line of "
                              "--native gains the key \"map\"")
+    parser.add_argument("--score-passes", action="store_true", default=False,
+                        help="with --native: score every recycling pass against the native on the GPU, not only the one the "
+                             "confidence picked (per pass: mean confidence logit, convergence delta, TM-score, GDT, RMSD, lDDT-CA; "
+                             "which pass was best, and what the choice cost); the JSON line of --native gains the key \"passes\"")
     parser.add_argument("--scores", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --native to FILE instead of standard error")
     parser.add_argument("--compare", type=str, default=None, required=False, metavar="PDB",
@@ -1192,10 +1252,12 @@ def run_dmpfold(argv=None):
     args = parser.parse_args(argv)
     if args.score_map and args.native is None:
         parser.error("--score-map scores the distance map against a native structure: give --native")
+    if args.score_passes and args.native is None:
+        parser.error("--score-passes scores every pass against a native structure: give --native")
     r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
                       args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
                       distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
-                      hits=args.search is not None, map_scores=args.score_map)
+                      hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1211,5 +1273,7 @@ def run_dmpfold(argv=None):
         js = _score.scores_json(r.scores)
         if r.map_scores is not None:
             js["map"] = _score.map_scores_json(r.map_scores)
+        if r.pass_scores is not None:
+            js["passes"] = _score.pass_scores_json(r.pass_scores)
         json_line(js, args.scores)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

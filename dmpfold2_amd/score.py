@@ -65,29 +65,49 @@ def mapscore_floats(L):
     return MAPSCORE_HEADER + int(L)
 
 
-class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_L",
-                        defaults=(False, False, False, None, None, None))):
+PASS_HEADER = 16                     # floats in front of the rows of the pass block
+PASS_ROW = 8                         # floats of a row
+PASS_MAX = 128                       # the context's max_passes: later passes have no recorded trace
+PASS_COLUMNS = ("conf_mean", "delta", "tm", "gdt_ts", "gdt_ha", "rmsd", "lddt")
+PASS_FIELDS = ("rows", "best_pass", "tm_pass", "lddt_pass", "regret_tm", "regret_lddt")
+
+
+def pass_rows(iterations):
+    """R of the pass block of a prediction asked for `iterations` recycling passes: min(iterations + 1, 128)."""
+    return min(max(int(iterations), 0) + 1, PASS_MAX)
+
+
+def pass_floats(R):
+    """Floats of the pass block (option "score_passes") of R rows."""
+    return PASS_HEADER + PASS_ROW * int(R)
+
+
+class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_L passes",
+                        defaults=(False, False, False, None, None, None, None))):
     """Where everything lies in the `d_conf` buffer of a prediction of length L: the Python twin of ConfLayout / conf_layout()
     / search_base() of csrc/common.h, in the order of include/dmpfold_hip.h.  Made from what decides it - `distmap`, `score`,
     `score_map`: options "emit_distmap", "score_native", "score_map" on; `align_m`: the m the align block holds (None =
     "align_structure" off); `search`: (K, M) of option "search_structures" (None = off); `max_L`: the context's, for the rule
-    of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0 counts).  Every offset is stated once,
-    each from the one in front of it:
+    of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0 counts); `passes` (keyword): the rows R
+    of the pass block of option "score_passes" (None = off).  Every offset is stated once, each from the one in front of it:
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
-      (64 + L) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
+      (64 + L) | pass_off (T0): pass block (16 + 8R) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off
+      (B0): search block (26K + 2LK + 3M)
 
     and `total` is the floats the buffer must hold."""
     __slots__ = ()
 
-    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None):
+    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None):
         return super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
-                               None if search is None else (int(search[0]), int(search[1])), max_L)
+                               None if search is None else (int(search[0]), int(search[1])), max_L,
+                               None if passes is None else int(passes))
 
     info_off = property(lambda s: s.L + (s.L * s.L if s.distmap else 0))
     score_off = property(lambda s: s.info_off + (3 if s.distmap else 0))                                    # S0
     mapscore_off = property(lambda s: s.score_off + (score_floats(s.L) if s.score else 0))                  # M0
-    align_off = property(lambda s: s.mapscore_off + (mapscore_floats(s.L) if s.score_map else 0))           # A0
+    pass_off = property(lambda s: s.mapscore_off + (mapscore_floats(s.L) if s.score_map else 0))            # T0
+    align_off = property(lambda s: s.pass_off + (pass_floats(s.passes) if s.passes is not None else 0))     # A0
     # the end of the align block as its writer allocated it (an align_m that is no number raises ValueError) ...
     align_end = property(lambda s: s.align_off + (align_floats(s.L, s.align_m) if s.align_m is not None else 0))
     # ... and B0, its end as the library counts it: 3m of it only if m is an integer in [3, max_L]
@@ -109,7 +129,8 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
                        part(self.distmap, self.info_off, self.score_off), part(self.score, self.score_off, self.mapscore_off),
                        part(self.align_m is not None, self.align_off, self.align_end),
                        part(self.search is not None, self.search_off, self.search_end),
-                       part(self.score_map, self.mapscore_off, self.align_off))
+                       part(self.score_map, self.mapscore_off, self.pass_off),
+                       part(self.passes is not None, self.pass_off, self.align_off))
 
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
@@ -140,29 +161,30 @@ def distmap_floats(L, on=True):
     return Layout(L, on).total
 
 
-class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block",
-                         defaults=(None, None, None, None, None, None))):
+class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block pass_block",
+                         defaults=(None, None, None, None, None, None, None))):
     """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
     score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
-    (26K + 2LK + 3M,), with "score_map" map_block (64 + L,) - None for what is absent."""
+    (26K + 2LK + 3M,), with "score_map" map_block (64 + L,), with "score_passes" pass_block (16 + 8R,) - None for what is
+    absent."""
     __slots__ = ()
 
     @classmethod
-    def of(cls, public, distmap, score, align=False, search=False, score_map=False):
+    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False):
         """The inverse of `public` for a caller that knows which options were on."""
-        rest = iter(public)          # (the fields stand in the tuple's order: the map-score block is the last of both)
-        return cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map)))
+        rest = iter(public)          # (the fields stand in the tuple's order: the pass block is the last of both)
+        return cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map, passes)))
 
-    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True):
+    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
-        block, the align block, the search block and - last, though it lies behind the score block in the buffer - the
-        map-score block, each if present and wanted.  `blocks=False`: none of the four blocks, whatever else is said - what
-        a call of an `Engine` returns, `public(distmap, blocks=False)`."""
+        block, the align block, the search block and - though they lie behind the score block in the buffer - the map-score
+        block and, last, the pass block, each if present and wanted.  `blocks=False`: none of the five blocks, whatever else
+        is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
         if not blocks:
-            score = align = search = score_map = False
+            score = align = search = score_map = passes = False
         groups = ((distmap, (self.distmap, self.info)), (score, (self.score_block,)), (align, (self.align_block,)),
-                  (search, (self.search_block,)), (score_map, (self.map_block,)))
+                  (search, (self.search_block,)), (score_map, (self.map_block,)), (passes, (self.pass_block,)))
         return (self.coords, self.confs) + tuple(x for want, group in groups if want and group[0] is not None for x in group)
 
 
@@ -384,6 +406,108 @@ def map_scores_flat(js):
         for lname in MAP_LISTS:
             out[f"{cname}_{lname}"] = js[cname]["precision"][lname]
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# option "score_passes" (include/dmpfold_hip.h): every recycling pass's trace scored against the same native, with the
+# number the best-of rule compared (conf_mean) and the convergence measure (delta) beside the scores.  Row p's scores are
+# exactly what "score_native" gives for ca_pass[p]; its delta is exactly what "recycle_tol_mA" compares.
+# ---------------------------------------------------------------------------------------------------------------------
+def _pass_index(v):
+    """A pass index the library wrote as a float -> int, None for NaN."""
+    return int(v) if v == v else None
+
+
+def unpack_pass_scores(block, R):
+    """A pass block (16 + 8R floats, array or tensor) -> dict: R, rows (int: the rows that hold a pass), best_pass, tm_pass,
+    lddt_pass (int, or None where the library wrote NaN), regret_tm, regret_lddt (float) and one float32 array (R,) per
+    column: conf_mean, delta, tm, gdt_ts, gdt_ha, rmsd, lddt - NaN at and beyond `rows`.  A block the library answered with
+    NaN (a latched fault) gives rows 0 and None / NaN elsewhere."""
+    R = int(R)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != pass_floats(R):
+        raise ValueError(f"a pass block of {R} rows has {pass_floats(R)} floats, got shape {tuple(b.shape)}")
+    out = {"R": R, "rows": _whole(b[0]), "best_pass": _pass_index(b[1]), "tm_pass": _pass_index(b[2]),
+           "lddt_pass": _pass_index(b[3]), "regret_tm": float(b[4]), "regret_lddt": float(b[5])}
+    table = b[PASS_HEADER:].reshape(R, PASS_ROW)
+    for k, name in enumerate(PASS_COLUMNS):
+        out[name] = table[:, k].copy()
+    return out
+
+
+def _num_inf(v):
+    """A float for JSON: NaN becomes None, an infinity the string "inf" / "-inf" (pass 0's delta)."""
+    v = float(v)
+    if v != v:
+        return None
+    return v if abs(v) != float("inf") else ("inf" if v > 0 else "-inf")
+
+
+def _from_json(v):
+    return float("nan") if v is None else float(v)
+
+
+def pass_scores_json(ps):
+    """`unpack_pass_scores` as a JSON-ready dict (the value of "passes" in what `dmpfold --native --score-passes` prints and
+    `dmpfold-batch --natives --score-passes` writes): the header fields and one list per column; NaN becomes None, pass 0's
+    delta the string "inf"."""
+    out = {"R": int(ps["R"]), "rows": int(ps["rows"])}
+    for name in PASS_FIELDS[1:4]:
+        out[name] = None if ps[name] is None else int(ps[name])
+    for name in PASS_FIELDS[4:]:
+        out[name] = _num(ps[name])
+    for name in PASS_COLUMNS:
+        out[name] = [_num_inf(v) for v in ps[name]]
+    return out
+
+
+def pass_scores_from_json(js):
+    """The inverse of `pass_scores_json`: the dict `unpack_pass_scores` gives."""
+    out = {"R": int(js["R"]), "rows": int(js["rows"])}
+    for name in PASS_FIELDS[1:4]:
+        out[name] = None if js[name] is None else int(js[name])
+    for name in PASS_FIELDS[4:]:
+        out[name] = _from_json(js[name])
+    for name in PASS_COLUMNS:
+        out[name] = np.asarray([_from_json(v) for v in js[name]], dtype=np.float32)
+    return out
+
+
+def simulate_converge(conf_mean, delta, tol_angstrom):
+    """What a run with the convergence stop at `tol_angstrom` (the `converge` of the front ends, option "recycle_tol_mA" =
+    converge_to_mA of it) would have done, decided from a full-depth pass table alone -> (passes_run, best_pass).  The stop
+    falls behind the first pass p >= 1 with float32(delta[p]) <= float32(tol_mA) * float32(1e-3), the library's comparison in
+    its float32 arithmetic (false for NaN); without one, or with the tolerance 0 (off), every row ran.  best_pass is the
+    strict '>' scan over conf_mean[0 .. passes_run - 1]: the earliest of equals stays.  Rows that hold no pass (NaN
+    conf_mean at the table's end) do not count."""
+    conf = np.asarray(conf_mean, dtype=np.float32).reshape(-1)
+    delta = np.asarray(delta, dtype=np.float32).reshape(-1)
+    n = conf.shape[0]
+    while n > 0 and conf[n - 1] != conf[n - 1]:
+        n -= 1
+    tol_mA = tolerance_mA(tol_angstrom)
+    tol = np.float32(tol_mA) * np.float32(1e-3)
+    run = n
+    if tol_mA > 0:
+        for p in range(1, n):
+            if delta[p] <= tol:
+                run = p + 1
+                break
+    best = 0
+    for p in range(1, run):
+        if conf[p] > conf[best]:
+            best = p
+    return run, best
+
+
+def tolerance_mA(tol_angstrom):
+    """A tolerance in Angstrom as the whole milli-Angstrom option "recycle_tol_mA" takes (None and 0 = off)."""
+    if tol_angstrom is None:
+        return 0
+    t = float(tol_angstrom)
+    if not t >= 0.0:
+        raise ValueError(f"a convergence tolerance must be >= 0 Angstrom, got {tol_angstrom}")
+    return int(round(t * 1000.0))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -83,6 +83,7 @@ const char* dmp_last_error(void);
  * MiB that decides how many of them are in flight at a time */
 #define DMP_SEARCH_MAX 4096
 #define DMP_SEARCH_BUDGET_MIB 256
+#define DMP_PASSES_BUDGET_MIB 64      /* option "score_passes": scratch of a chunk of passes */
 int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out);
 void dmp_ctx_destroy(dmp_ctx* ctx);
 /* (device memory held by the context: option "device_mib" of dmp_ctx_get_option, read only) */
@@ -294,14 +295,62 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * with a key not above it, so ties are no separate path.  No float atomics: the same bits on every run.  A context holds
  * 1.7 KB for this (14 counters, 3 x 64 partial sums, 3 totals, 3 tickets).  Measured cost: 6.6 ms at L = 2048, 0.2 ms at
  * L = 300 (profiles/mapscore.txt).
+ * "score_passes" (0 or 1, default 0; any other value: DMP_ERR_ARG): score EVERY recycling pass's C-alpha trace against the
+ * native trace of "score_native" on the device, not only the pass the best-of rule kept, and hand out beside the scores the
+ * number that rule compared and the convergence measure of "recycle_tol_mA": one full-depth run then tells how many passes
+ * were worth running, whether the confidence picked the right one, and what any convergence tolerance would have cost
+ * (dmpfold2_amd/score.py: simulate_converge).  Read when a prediction begins and held for it.  IT NEEDS "score_native" = 1:
+ * a prediction begun with it on and that option off fails with DMP_ERR_ARG and a message naming the missing option.  With
+ * it 0 nothing is launched, read, written or allocated, and every offset and output is bit for bit what it is without the
+ * option.  With it 1 THE d_conf ARGUMENT MUST HOLD T0 + 16 + 8R FLOATS, T0 = THE END OF THE MAP-SCORE BLOCK (THE END OF THE
+ * SCORE BLOCK WITHOUT "score_map"), R = min(nloops + 1, 128) WITH THE nloops THE PREDICTION WAS BEGUN WITH: there sits the
+ * PASS BLOCK, all of it outputs, and A0 and B0 below move behind it.  128 is the number of passes a context records a trace
+ * for; later passes run and may be kept, but have no row.  Everything else in the buffer does not change by a bit.
+ * Offsets relative to T0:
+ *   0                    rows = min(passes run, 128): the rows that hold a pass (fewer than R after a convergence stop)
+ *   1                    best_pass: the pass the best-of rule kept (the value "emit_distmap" reports)
+ *   2                    tm_pass: the row with the largest tm (float32 comparison, ties to the lowest pass, NaN rows skipped);
+ *                        NaN if there is none
+ *   3                    lddt_pass: the same for lddt
+ *   4                    regret_tm = tm[tm_pass] - tm[best_pass], one float32 subtraction of the stored floats; NaN if
+ *                        best_pass >= 128 or either operand is NaN
+ *   5                    regret_lddt, likewise
+ *   6 .. 15              zero
+ *   16 + 8p + 0          conf_mean of pass p: the mean confidence logit the strict '>' of the best-of rule compared
+ *   16 + 8p + 1          delta of pass p: d_p exactly as "recycle_tol_mA" defines it (+inf for pass 0), computed whether or
+ *                        not that option is on
+ *   16 + 8p + 2 .. 6     tm, gdt_ts, gdt_ha, rmsd, lddt of pass p
+ *   16 + 8p + 7          zero
+ * Rows at and beyond `rows` are NaN in all eight floats.  THERE IS ONE DEFINITION, BY REFERENCE: row p's five scores are
+ * exactly what "score_native" returns when the model trace is the one recorded for pass p - the same native, lnorm, seeds,
+ * iteration and summation order, evaluated by the same device functions, so where the final trace IS that pass's trace
+ * (refine_steps = 0) the row has the bits of the score block - and its delta is exactly what "recycle_tol_mA" records for
+ * that pass, evaluated by the same device function.  THE TRACE OF PASS 0 IS THE REFINED ONE WHEN refine_steps > 0 (the trace
+ * that seeded pass 1); THE LATER PASSES' TRACES ARE UNREFINED, as the network produced them: with refine_steps > 0 the row
+ * of best_pass is therefore not the score block's, which scores the final, refined trace.  A native with fewer than 3
+ * present rows gives NaN at offsets 2 .. 6 of every row and 2 .. 5 of the header; conf_mean and delta stay; no fault.  A
+ * prediction that latched a device-side fault returns NaN in the whole block.  No per-pass R, t, per-residue arrays or map
+ * scores are kept.
+ * Cost with the option on: in dmp_predict_end behind "score_map" and in front of "align_structure", on the prediction's
+ * stream, nothing synchronises - pass_fill, pass_delta (coords.hip: the delta's sum with the pass as blockIdx.y), then per
+ * chunk of passes score_pass_prep, score_lddt and score_search (csrc/score.hip: the kernels of "score_native" with the pass
+ * as blockIdx.y; the packed native and the row index are those score_prep made for the score block of the same call; each
+ * pass has its own packed model, lDDT totals, seed records and ticket), then pass_header, one workgroup.  No float atomics:
+ * the same bits on every run.  Scratch: a slot per pass in flight - score_seeds(L) <= 1 + 5L records of 20 doubles (8262 records,
+ * 1.3 MB at L = 2048), the packed trace, the totals - under a budget of DMP_PASSES_BUDGET_MIB (64 MiB): C = clamp(budget / slot,
+ * 1, 128) consecutive passes per chunk, 49 at L = 2048, every pass in one chunk up to about L = 790.  Chunk boundaries do not
+ * change a bit.  The scratch (the largest chunk of any length up to max_L, plus 66 KB of tickets and partial sums) is
+ * allocated when the option first becomes 1 on a context and counted in "device_mib"; an allocation failure is an error of
+ * dmp_ctx_set_option and leaves the option as it was.  Measured cost: profiles/passes.txt.
+ * "score_passes_chunk" (TESTS ONLY; n >= 0, default 0): at most n passes per chunk when n > 0.
  * "align_structure" (0 or 1, default 0; any other value: DMP_ERR_ARG): align the model with a structure of any length and
  * sequence on the device - a structural alignment found by superposition and dynamic programming in turn.  Read when a
  * prediction begins and held for it.  With it 0 nothing is launched, nothing extra is read or written, and every output is
  * bit for bit what it is without the option.  With it 1 dmp_predict_end launches the alignment behind "score_native", on
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
- * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map";
- * the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
+ * + 16 + 8R with "score_passes"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
