@@ -22,7 +22,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // Eight consecutive channels of one pixel -> the 16-byte operands of the split-product
-// convolutions.  MODE 0: two f16 pieces (conv_f16.h), MODE 2: three bf16 pieces (conv_bf16.h).
+// convolutions (conv_split.h).  MODE 0: two f16 pieces (conv_f16.h), MODE 2: three bf16 pieces (conv_bf16.h).
 // `slot` is the uint4 index inside one piece plane set, `piece_stride` the uint4 count per piece.
 // MODE 0: the pieces are those of xscale * o (a power of two per block: exact, undone in the convolution's epilogue),
 // so that the low pieces of the bulk of the activations are normal f16 numbers whatever the trunk's activation
@@ -663,14 +663,11 @@ int act_split(dmp_ctx* c, const float* d_xpad, int L, int block, hipStream_t s) 
 int trunk_kernel_attrs(dmp_ctx* c) {
   static bool done[64] = {};
   if (c->device >= 0 && c->device < 64 && done[c->device]) return DMP_OK;
-  DMP_HIP(hipFuncSetAttribute((const void*)conv5x5_bf16x6_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              convq_lds_bytes<8>()));
-  DMP_HIP(hipFuncSetAttribute((const void*)conv5x5_bf16x6_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              convq_lds_bytes<4>()));
-  DMP_HIP(hipFuncSetAttribute((const void*)conv5x5_f16x3_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              convh_lds_bytes<8>()));
-  DMP_HIP(hipFuncSetAttribute((const void*)conv5x5_f16x3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              convh_lds_bytes<4>()));
+  auto lds = [](const void* k, int bytes) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+  DMP_HIP(lds((const void*)conv5x5_bf16x6_kernel<8>, convq_lds_bytes<8>()));
+  DMP_HIP(lds((const void*)conv5x5_bf16x6_kernel<4>, convq_lds_bytes<4>()));
+  DMP_HIP(lds((const void*)conv5x5_f16x3_kernel<8>, convh_lds_bytes<8>()));
+  DMP_HIP(lds((const void*)conv5x5_f16x3_kernel<4>, convh_lds_bytes<4>()));
   if (c->device >= 0 && c->device < 64) done[c->device] = true;
   return DMP_OK;
 }
@@ -688,22 +685,22 @@ int conv5x5_maxout_padded(dmp_ctx* c, int block, const float* d_xpad, int L, flo
       if (rc) return rc;
     }
     // tile shape: 16 x 16 pixels, or 8 x 16 where the 16 x 16 shape would leave half the CUs without a workgroup
-    // (L <= 80; conv_f16.h ChShape: the same bits either way).  Both write their InstanceNorm partial sums per half tile.
+    // (L <= 80; conv_split.h CsShape: the same bits either way).  Both write their InstanceNorm partial sums per half tile.
     const int bands = c->conv_tile_bands > 0 ? c->conv_tile_bands : conv_split_rows(tiles);
     const float scale = c->act_scaling ? B.wh_inv_scale / B.x_scale : B.wh_inv_scale;
     if (c->conv_mode == 2) {
       if (bands == 2)
-        hipLaunchKernelGGL(conv5x5_bf16x6_kernel<4>, dim3(conv_bf16_grid(tiles, 2)), dim3(256), convq_lds_bytes<4>(), s,
+        hipLaunchKernelGGL(conv5x5_bf16x6_kernel<4>, dim3(conv_split_grid(tiles, 2)), dim3(256), convq_lds_bytes<4>(), s,
                            c->xsplit, B.wq, B.bias, L, P, tiles, nwork, d_u, c->part);
       else
-        hipLaunchKernelGGL(conv5x5_bf16x6_kernel<8>, dim3(conv_bf16_grid(tiles, 1)), dim3(256), convq_lds_bytes<8>(), s,
+        hipLaunchKernelGGL(conv5x5_bf16x6_kernel<8>, dim3(conv_split_grid(tiles, 1)), dim3(256), convq_lds_bytes<8>(), s,
                            c->xsplit, B.wq, B.bias, L, P, tiles, nwork, d_u, c->part);
     } else {
       if (bands == 2)
-        hipLaunchKernelGGL(conv5x5_f16x3_kernel<4>, dim3(conv_f16_grid(tiles, 2)), dim3(256), convh_lds_bytes<4>(), s,
+        hipLaunchKernelGGL(conv5x5_f16x3_kernel<4>, dim3(conv_split_grid(tiles, 2)), dim3(256), convh_lds_bytes<4>(), s,
                            c->xsplit, B.wh, B.bias, scale, L, P, tiles, nwork, d_u, c->part);
       else
-        hipLaunchKernelGGL(conv5x5_f16x3_kernel<8>, dim3(conv_f16_grid(tiles, 1)), dim3(256), convh_lds_bytes<8>(), s,
+        hipLaunchKernelGGL(conv5x5_f16x3_kernel<8>, dim3(conv_split_grid(tiles, 1)), dim3(256), convh_lds_bytes<8>(), s,
                            c->xsplit, B.wh, B.bias, scale, L, P, tiles, nwork, d_u, c->part);
     }
     DMP_LAUNCH_CHECK();

@@ -63,9 +63,9 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(d_wq, wq.data(), wq.size() * 2, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_b, bias.data(), 512 * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_xs, xs.data(), xs.size() * 2, hipMemcpyHostToDevice));
-  CK(hipFuncSetAttribute((const void*)conv5x5_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+  CK(hipFuncSetAttribute((const void*)conv5x5_f16x3_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                          CONVH_LDS_BYTES));
-  const int grid = conv_f16_grid(tiles), nwork = tiles * tiles * 4;
+  const int grid = conv_split_grid(tiles), nwork = tiles * tiles * 4;
 
   // a chain-like C-alpha trace and confidence logits
   std::vector<float> ca((size_t)3 * L), lg(L);
@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
       for (int k = 0; k < SLOTS; ++k) {
         if (phase == 1 && (k & 7) == 0)
           for (int c = 0; c < 2; ++c)
-            hipLaunchKernelGGL(conv5x5_f16x3_kernel, dim3(grid), dim3(256), CONVH_LDS_BYTES, sa, d_xs, d_wq,
+            hipLaunchKernelGGL(conv5x5_f16x3_kernel<8>, dim3(grid), dim3(256), CONVH_LDS_BYTES, sa, d_xs, d_wq,
                                d_b, 1.0f / scale, LC, P, tiles, nwork, d_u, d_part);
         launch_bb(k);
       }

@@ -35,7 +35,7 @@ while time.time() - t0 < 2.5:
     for _ in range(10):
         st.trunk_pass(z0, dmap)
     torch.cuda.synchronize()
-blocks = 8 * ((19 * 19 + 1) // 2)                    # conv_bf16_grid(19 tiles)
+blocks = 8 * ((19 * 19 + 1) // 2)                    # conv_split_grid(19 tiles)
 buf = np.zeros((blocks, 2), dtype=np.uint64)
 st.lib.dmp_debug_conv_clock.restype = C.c_int
 st.lib.dmp_debug_conv_clock.argtypes = [C.c_void_p, C.c_int]

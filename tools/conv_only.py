@@ -4,7 +4,7 @@ kernel of the chosen arithmetic, plus the small norm kernels between them) a few
 HBM traffic to calibrate FETCH_SIZE / WRITE_SIZE on this chip:
   * a 256 MiB torch fill (write only, 16 B per lane),
   * a 256 MiB torch copy (read + write, 16 B per lane).
-    rocprofv3 --pmc ... --kernel-trace --output-format csv -d out -- python tools/conv_only.py [passes] [L] [conv_mode]
+    rocprofv3 --pmc ... --output-format csv -d out -- python tools/conv_only.py [passes] [L] [conv_mode]
 """
 import os
 import sys

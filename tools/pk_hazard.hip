@@ -162,9 +162,9 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(d_wq, wq.data(), wq.size() * 2, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_b, bias.data(), 512 * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_xs, xs.data(), xs.size() * 2, hipMemcpyHostToDevice));
-  CK(hipFuncSetAttribute((const void*)conv5x5_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+  CK(hipFuncSetAttribute((const void*)conv5x5_f16x3_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                          CONVH_LDS_BYTES));
-  const int grid = conv_f16_grid(tiles), nwork = tiles * tiles * 4;
+  const int grid = conv_split_grid(tiles), nwork = tiles * tiles * 4;
 
   // the test kernel's operands: s in [0.5, 1.5), b in [0.9995, 1.0005)
   const int nthreads = wgs * 256;
@@ -188,7 +188,7 @@ int main(int argc, char** argv) {
     CK(hipEventRecord(e0, sb));
     for (int l = 0; l < launches; ++l) {
       if (phase == 1)
-        hipLaunchKernelGGL(conv5x5_f16x3_kernel, dim3(grid), dim3(256), CONVH_LDS_BYTES, sa, d_xs, d_wq, d_b,
+        hipLaunchKernelGGL(conv5x5_f16x3_kernel<8>, dim3(grid), dim3(256), CONVH_LDS_BYTES, sa, d_xs, d_wq, d_b,
                            1.0f / scale, L, P, tiles, nwork, d_u, d_part);
       hipLaunchKernelGGL(pk_test_kernel, dim3(wgs), dim3(256), 0, sb, d_in, R, d_bad, d_first, d_sink);
     }

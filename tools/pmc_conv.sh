@@ -1,15 +1,15 @@
 #!/bin/bash
-# GPU box: PMC passes (separate rocprofv3 --pmc runs) of the convolution kernel of one arithmetic setting, one trunk pass at
+# GPU box: PMC passes (separate rocprofv3 --pmc runs, counters only: no tracing option) of the convolution kernel of one arithmetic setting, one trunk pass at
 # length L (16 launches): tools/pmc_conv.sh <conv_mode 0|1|2> [L] [tag]  -> gpurun_out/pmc/<tag>*.  Prints the per-launch means.
-R=${GRAFT_REPO_ROOT:-/root/repo}; mode=${1:-2}; L=${2:-300}; tag=${3:-m$mode}
+R=$(cd "$(dirname "$0")/.." && pwd); mode=${1:-2}; L=${2:-300}; tag=${3:-m$mode}
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $R/gpurun_out/pmc
-run() { name=$1; shift; rm -rf $R/gpurun_out/pmc/$name; timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $R/gpurun_out/pmc/$name -o $name -- python $R/tools/conv_only.py 1 $L $mode > $R/gpurun_out/pmc/$name.log 2>&1; echo "$name rc=$?"; }
-run ${tag}_sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS
-run ${tag}_sq2 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE
-run ${tag}_fetch FETCH_SIZE
-run ${tag}_write WRITE_SIZE
-find $R/gpurun_out/pmc -name "*kernel_trace.csv" -size +20M -delete
+O=$_      # the directory just made: the passes write below it
+run() { name=$1; shift; rm -rf $O/$name; timeout -k 10 240 rocprofv3 --pmc "$@" --output-format csv -d $O/$name -o $name -- python $R/tools/conv_only.py 1 $L $mode > $O/$name.log 2>&1; rc=$?; echo "$name rc=$rc"; return $rc; }
+run ${tag}_sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS &&
+run ${tag}_sq2 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE &&
+run ${tag}_fetch FETCH_SIZE &&
+run ${tag}_write WRITE_SIZE || exit 1      # a pass that fails ends the script: nothing more is started on the GPU
 python3 - <<PY
 import csv, glob, collections
 agg = collections.defaultdict(list)

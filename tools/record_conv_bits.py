@@ -1,12 +1,15 @@
 #!/usr/bin/env python
-"""Record the bits of the bf16x6 convolution (option "conv_mode" 2) at the sizes where the kernel can go wrong.
+"""Record the bits of a split-product convolution - bf16x6 (option "conv_mode" 2) or f16x3 (0, default "act_scaling") - at
+the sizes where the kernel can go wrong.
 
-    python tools/record_conv_bits.py [out.json]          (default: tests/golden/conv_bf16_bits.json)
+    python tools/record_conv_bits.py [conv_mode [out.json]]      (default: 2 -> tests/golden/conv_bf16_bits.json,
+                                                                            0 -> tests/golden/conv_f16_bits.json)
 
 Runs the stage-level convolution (tests/abi.py Stages.conv) on host-generated inputs and writes the SHA-256 of the output
 `u` and of the InstanceNorm statistics per case.  Run it on the build whose bits are the reference (the commit before a
-change of conv_bf16.h that must not change them) and commit the JSON; tests/test_gpu_conv_bits.py asserts that the
-current build gives the same digests.  The cases and the inputs are defined here, once, for both.
+change of conv_split.h, conv_bf16.h or conv_f16.h that must not change them) and commit the JSON;
+tests/test_gpu_conv_bits.py asserts that the current build gives the same digests.  The cases and the inputs are defined
+here, once, for both modes and for both sides.
 """
 import hashlib
 import json
@@ -16,7 +19,8 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "conv_bf16_bits.json")
+GOLDEN = {mode: os.path.join(ROOT, "tests", "golden", name)
+          for mode, name in ((2, "conv_bf16_bits.json"), (0, "conv_f16_bits.json"))}
 
 # (L, "conv_tile_bands"): 0 = chosen by length (8 x 16 tiles up to L = 80, 16 x 16 above)
 SIZES = [
@@ -44,18 +48,18 @@ def digest(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
-def make_stages(state_dict=None):
+def make_stages(state_dict=None, mode=2):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from abi import Stages
     from dmpfold2_amd import synth
     st = Stages(state_dict if state_dict is not None else synth.synth_weights(0, coord_scale=5.0), max_L=MAX_L, max_N=64)
-    st.eng.set_option("conv_mode", 2)
+    st.eng.set_option("conv_mode", mode)
     return st
 
 
 def run_cases(st):
-    """{case name: {"u": sha256, "stats": sha256}} of every case on the Stages `st` (conv_mode 2 set by the caller)"""
+    """{case name: {"u": sha256, "stats": sha256}} of every case on the Stages `st` (conv_mode set by make_stages)"""
     out = {}
     try:
         for L, bands in SIZES:
@@ -72,14 +76,15 @@ def run_cases(st):
 
 
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else GOLDEN
-    st = make_stages()
+    mode = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+    path = sys.argv[2] if len(sys.argv) > 2 else GOLDEN[mode]
+    st = make_stages(mode=mode)
     try:
         got = run_cases(st)
     finally:
         st.eng.close()
     with open(path, "w") as f:
-        json.dump({"conv_mode": 2, "input": "numpy default_rng(7000 + L).standard_normal((128, L, L)) * 3, float32",
+        json.dump({"conv_mode": mode, "input": "numpy default_rng(7000 + L).standard_normal((128, L, L)) * 3, float32",
                    "weights": "synth.synth_weights(0, coord_scale=5.0)", "cases": got}, f, indent=1, sort_keys=True)
         f.write("\n")
     print(f"{len(got)} cases -> {path}")
