@@ -145,7 +145,7 @@ def ca_only_text(coords, confs, alnmat):
 
 
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
-                 hits=None, hits_top=10, map_scores=None, pass_scores=None):
+                 hits=None, hits_top=10, map_scores=None, pass_scores=None, ss=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
@@ -161,7 +161,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     <stem>.scores.json gains the key "map".  With `pass_scores` (the dict of score.unpack_pass_scores, --natives
     --score-passes; only beside `scores`): npz gains pass_rows, pass_best, pass_tm_best, pass_lddt_best (int32, -1 for none),
     pass_regret_tm, pass_regret_lddt and one float32 array (R,) per column, pass_conf_mean, pass_delta, pass_tm, pass_gdt_ts,
-    pass_gdt_ha, pass_rmsd, pass_lddt; <stem>.scores.json gains the key "passes"."""
+    pass_gdt_ha, pass_rmsd, pass_lddt; <stem>.scores.json gains the key "passes".  With `ss` (the dict of score.unpack_ss,
+    --ss): npz gains ss8 (the string), ss_bp (int32 (L, 2): the two bridge partners), ss_e_acc, ss_e_don (float32 (L,)),
+    ss_p_acc, ss_p_don (int32 (L,)) and, with a whole native, ss8_native, ss_q3 and ss_q8; pdb / ca get <stem>.ss.json (the
+    line `dmpfold --ss` prints)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -189,6 +192,13 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             extra.update({"pass_" + k: np.int32(-1 if pass_scores[name] is None else pass_scores[name])
                           for k, name in (("best", "best_pass"), ("tm_best", "tm_pass"), ("lddt_best", "lddt_pass"))})
             extra.update({"pass_" + k: np.asarray(pass_scores[k], dtype=np.float32) for k in _score.PASS_COLUMNS})
+        if ss is not None:
+            extra.update({"ss8": np.asarray(ss["ss8"], dtype=np.str_), "ss_bp": np.stack([ss["bp1"], ss["bp2"]], axis=1).astype(np.int32),
+                          "ss_e_acc": np.asarray(ss["e_acc"], dtype=np.float32), "ss_e_don": np.asarray(ss["e_don"], dtype=np.float32),
+                          "ss_p_acc": np.asarray(ss["p_acc"], dtype=np.int32), "ss_p_don": np.asarray(ss["p_don"], dtype=np.int32)})
+            if ss["has_native"]:
+                extra.update({"ss8_native": np.asarray(ss["ss8_native"], dtype=np.str_), "ss_q3": np.float32(ss["q3"]),
+                              "ss_q8": np.float32(ss["q8"])})
         if alignment is not None:
             extra.update({k: (np.int32 if k in ("n_ali", "seed_offset", "seeds") else np.float32)(alignment[k])
                           for k in _score.ALIGN_NAMES})
@@ -213,6 +223,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             if pass_scores is not None:
                 js["passes"] = _score.pass_scores_json(pass_scores)
             fh.write(json.dumps(js) + "\n")
+    if ss is not None:
+        with open(stem + ".ss.json", "w") as fh:
+            fh.write(json.dumps(_score.ss_json(ss)) + "\n")
     if alignment is not None:
         with open(stem + ".alignment.json", "w") as fh:
             fh.write(json.dumps(_score.alignment_json(alignment)) + "\n")
@@ -268,7 +281,7 @@ def cost_order(targets, iterations):
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
               converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10,
-              score_map=False, score_passes=False):
+              score_map=False, score_passes=False, ss=False):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
@@ -277,6 +290,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     (Pipeline.set_score_map); its scores gain the key "map" (score.map_scores_json) wherever they are written.
     `score_passes` (needs `natives`): every recycling pass of a scored target is scored against its native too
     (Pipeline.set_score_passes); its scores gain the key "passes" (score.pass_scores_json) wherever they are written.
+    `ss`: every target's backbone gets its secondary structure assigned on the GPU (Pipeline.set_ss; with `natives`, a
+    target whose native covers every column also gets the native's and Q3 / Q8) and it is written with the target
+    (write_result); `stats_out` then receives "ss": {stem: the dict of score.ss_json}.
     `structures`: a directory of structures of any length and sequence, <stem>.pdb for the target <stem>.aln / .a3m: such a
     target's model is aligned with the structure's first chain on the GPU (Pipeline.set_align) and the alignment is written
     with it (write_result); a target without a file is predicted without one.  `stats_out` then receives "alignments":
@@ -359,6 +375,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_score_map(True)          # (turns the distance map on: it is written only with `distmap`)
             if score_passes:
                 pipe.set_score_passes(True)
+            if ss:
+                pipe.set_ss(True)
             if structures:
                 pipe.set_align(True)
             if library is not None:
@@ -397,11 +415,12 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     scored, all_scores = set(), {}
     aligned, all_alignments = set(), {}
     all_hits = {}
+    all_ss = {}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
         out = Outputs.of(public, distmap=distmap or score_map, score=bool(natives), align=bool(structures), search=library is not None,
-                         score_map=score_map, passes=score_passes)
+                         score_map=score_map, passes=score_passes, ss=ss)
         aln_path, alnmat, _ = parsed.pop(t)
         sc = ms = ps = None
         if out.score_block is not None and t in scored:
@@ -424,8 +443,12 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             hits = dict(_score.unpack_search(out.search_block, alnmat.shape[1], library.lengths), names=list(library.names))
             all_hits[os.path.splitext(os.path.basename(aln_path))[0]] = [
                 {k: v for k, v in h.items() if k not in ("R", "t")} for h in _score.hits_json(hits, library.names, search_top)["hits"]]
+        sec = None
+        if out.ss_block is not None:
+            sec = _score.unpack_ss(out.ss_block, alnmat.shape[1])
+            all_ss[os.path.splitext(os.path.basename(aln_path))[0]] = _score.ss_json(sec)
         outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap if distmap else None,
-                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps))
+                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps, sec))
 
     def finish(item):
         t, public = item
@@ -542,6 +565,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             stats_out["alignments"] = all_alignments
         if stats_out is not None and library is not None:
             stats_out["hits"] = all_hits
+        if stats_out is not None and ss:
+            stats_out["ss"] = all_ss
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
@@ -594,6 +619,11 @@ def batch_parser():
                          "target's top hits; npz gains hit_rank, hit_tm_model, hit_tm_struct and hit_names, pdb / ca write "
                          "<stem>.hits.json")
     ap.add_argument("--search-top", type=int, default=10, metavar="N", help="hits per target to report with --library (default 10)")
+    ap.add_argument("--ss", action="store_true",
+                    help="assign secondary structure to every target's backbone on the GPU from its hydrogen bonds; the summary "
+                         "gains every target's eight-state string and helix / strand / coil fractions with their means and "
+                         "medians (with --natives also mean Q3 / Q8 over the targets whose native covers every column); npz "
+                         "gains ss8, ss_bp and the energy arrays, pdb / ca write <stem>.ss.json")
     return ap
 
 
@@ -630,6 +660,23 @@ def pass_summary(tables, tolerances=CONVERGE_SWEEP):
             lost.append(float(t["tm"][full[1]]) - float(t["tm"][best]))
         sweep.append({"tol": tol, "mean_passes": float(np.mean(runs)), "mean_tm_lost": float(np.mean(lost))})
     out["converge_sweep"] = sweep
+    return out
+
+
+def ss_summary(ss):
+    """{stem: the dict of score.ss_json} -> the summary's part for --ss: per target the eight-state string and the three
+    fractions (and q3, q8 where it had a whole native), mean and median of the fractions, mean Q3 / Q8 over the targets that
+    have them."""
+    out = {"ss_targets": len(ss), "ss": {stem: {k: v[k] for k in ("ss8", "helix", "strand", "coil", "q3", "q8") if k in v}
+                                         for stem, v in ss.items()}}
+    for name in ("helix", "strand", "coil"):
+        vals = [v[name] for v in ss.values()]
+        out["mean_" + name] = float(np.mean(vals)) if vals else None
+        out["median_" + name] = float(np.median(vals)) if vals else None
+    for name in ("q3", "q8"):
+        vals = [v[name] for v in ss.values() if v.get(name) is not None]
+        if vals:
+            out["mean_" + name] = float(np.mean(vals))
     return out
 
 
@@ -688,7 +735,7 @@ def main(argv=None):
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
                                   structures=args.structures, library=args.library, search_top=args.search_top,
-                                  score_map=args.score_map, score_passes=args.score_passes)
+                                  score_map=args.score_map, score_passes=args.score_passes, ss=args.ss)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -704,6 +751,8 @@ def main(argv=None):
         job_store.set(f"dmpfold_batch_alignments/{rank}", json.dumps(passes.get("alignments", {})))
     if args.library and world > 1:
         job_store.set(f"dmpfold_batch_hits/{rank}", json.dumps(passes.get("hits", {})))
+    if args.ss and world > 1:
+        job_store.set(f"dmpfold_batch_ss/{rank}", json.dumps(passes.get("ss", {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
         passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
@@ -730,6 +779,11 @@ def main(argv=None):
             for r in range(1, world):
                 hits.update(json.loads(job_store.get(f"dmpfold_batch_hits/{r}").decode()))
             summary["searched_targets"], summary["hits"] = len(hits), dict(sorted(hits.items()))
+        if args.ss:
+            sec = dict(passes.get("ss", {}))
+            for r in range(1, world):
+                sec.update(json.loads(job_store.get(f"dmpfold_batch_ss/{r}").decode()))
+            summary.update(ss_summary(dict(sorted(sec.items()))))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

@@ -409,7 +409,8 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
 // caller's and stay.  The map-score block of option "score_map" and the pass block of option "score_passes" lie between the
 // score block's end (lay.smap_off) and lay.align_off and are all outputs: the range [lay.score_out, lay.align_off) below
-// takes them in.  The same for the align block
+// takes them in; so is the SS block of option "assign_ss" at [lay.ss_off, lay.align_off), named on its own because without
+// "score_native" lay.score_out lies inside it.  The same for the align block
 // of option "align_structure": its out slots become NaN, m in front of them and the structure's trace behind them (past
 // lay.total) stay.  (The search block of option "search_structures" lies at an offset only the device knows: search_rank,
 // the launch in front of this one, reads the same word and does the same there.)
@@ -420,7 +421,9 @@ __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const float nan = __builtin_nanf("");
   if (i < 15 * L) coords[i] = nan;
-  if (i < lay.score_off || (i >= lay.score_out && i < lay.align_off) || (i >= lay.align_out && i < lay.total)) conf[i] = nan;
+  if (i < lay.score_off || (i >= lay.score_out && i < lay.align_off) || (i >= lay.ss_off && i < lay.align_off) ||
+      (i >= lay.align_out && i < lay.total))
+    conf[i] = nan;
   if (i == 0) {
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
@@ -475,6 +478,28 @@ static int passes_reserve(dmp_ctx* c) {
   c->bytes += need;
   c->pass_ws = (unsigned char*)p;
   c->pass_ws_bytes = need;
+  return DMP_OK;
+}
+
+// Option "assign_ss": the scratch of the secondary-structure assignment, allocated when the option first becomes 1 on a
+// context and counted in "device_mib" (ss.hip has its layout).  The counters and the ticket in front are zero between launches.
+static int ss_reserve(dmp_ctx* c) {
+  if (c->ss_ws) return DMP_OK;
+  const int64_t need = assign_ss_bytes(c->max_L);
+  int prev = 0;
+  DMP_HIP(hipGetDevice(&prev));
+  DMP_HIP(hipSetDevice(c->device));
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, (size_t)need);
+  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)assign_ss_head_bytes());
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (p) (void)hipFree(p);
+    return hip_fail(e, "secondary-structure scratch", __FILE__, __LINE__);
+  }
+  c->bytes += need;
+  c->ss_ws = (unsigned char*)p;
+  c->ss_ws_bytes = need;
   return DMP_OK;
 }
 
@@ -699,6 +724,15 @@ int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
     ctx->opt.passes_chunk = value;
     return DMP_OK;
   }
+  if (k == "assign_ss") {            // takes effect with the next prediction begun
+    DMP_ARG(value == 0 || value == 1, "assign_ss must be 0 or 1, got %d", value);
+    if (value) {
+      const int rc = ss_reserve(ctx);               // a failure leaves the option as it was
+      if (rc) return rc;
+    }
+    ctx->opt.ss = value;
+    return DMP_OK;
+  }
   if (k == "align_structure") {      // takes effect with the next prediction begun
     DMP_ARG(value == 0 || value == 1, "align_structure must be 0 or 1, got %d", value);
     ctx->opt.align = value;
@@ -772,6 +806,7 @@ int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   if (k == "score_map") { *h_value = ctx->opt.smap; return DMP_OK; }
   if (k == "score_passes") { *h_value = ctx->opt.passes; return DMP_OK; }
   if (k == "score_passes_chunk") { *h_value = ctx->opt.passes_chunk; return DMP_OK; }
+  if (k == "assign_ss") { *h_value = ctx->opt.ss; return DMP_OK; }
   if (k == "align_structure") { *h_value = ctx->opt.align; return DMP_OK; }
   if (k == "search_structures") { *h_value = ctx->opt.search; return DMP_OK; }
   if (k == "search_max_m") { *h_value = ctx->opt.search_mm; return DMP_OK; }
@@ -807,6 +842,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->search_ws) (void)hipFree(c->search_ws);
   if (c->pass_ws) (void)hipFree(c->pass_ws);
+  if (c->ss_ws) (void)hipFree(c->ss_ws);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
   for (void* e : c->unit_ev)
@@ -1271,6 +1307,7 @@ static int issue_front_end_unit(dmp_ctx* c, hipStream_t s) {
     }
     used = side;
     rc = msa_weights(c, d_msa, N, L, c->w, side);
+    if (!rc && c->run.ss) rc = ss_capture_pro(c, d_msa, L, side);       // option "assign_ss": the first row's proline flags
     if (!rc && N > 1) rc = cov_build(c, d_msa, c->w, N, L, c->cov, side, true);
   } else if (u <= c->fe_inv + c->fe_vgru) {
     // alternate GRU chunk / inverse chunk while both kinds remain
@@ -1552,7 +1589,7 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // option "score_passes": R rows, one per pass the prediction was asked for; those of the passes that ran hold a pass
   // (run_depth: a convergence stop shortens run_nloops, the caller sized the buffer from what it asked for)
   const int pass_R = c->run.passes ? std::min(c->run_depth + 1, c->max_passes) : 0;
-  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align, c->run.smap, pass_R);
+  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align, c->run.smap, pass_R, c->run.ss);
   // option "emit_distmap": the map and {best_pass, passes_run, map_rms} behind the confidences
   if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map_off, d_conf + lay.info_off, s))) return rc;
   // option "score_native": the score block behind that, the native trace and lnorm in it (score.hip)
@@ -1561,6 +1598,8 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.smap && (rc = score_map(c, L, d_conf + lay.score_off, d_conf + lay.smap_off, s))) return rc;
   // option "score_passes": the pass block behind that, from ca_pass, conf_means and what score_native packed (score.hip)
   if (pass_R && (rc = score_passes(c, L, pass_R, std::min(c->passes_done, c->max_passes), d_conf + lay.pass_off, s))) return rc;
+  // option "assign_ss": the SS block behind that, from d_coords and - with "score_native" - the score block's native trace (ss.hip)
+  if (c->run.ss && (rc = assign_ss(c, d_coords, L, c->run.score ? d_conf + lay.score_off : nullptr, d_conf + lay.ss_off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align_off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

@@ -76,17 +76,22 @@ __host__ __device__ inline int mapscore_floats(int L) { return MAPSCORE_HEADER +
 //   all of it out, between the map-score block and the align block.
 constexpr int PASS_HEADER = 16, PASS_ROW = 8, PASS_MAX = 128;
 __host__ __device__ inline int pass_floats(int R) { return PASS_HEADER + PASS_ROW * R; }
+//   | with "assign_ss": the SS block = SS_HEADER floats | eight per-residue arrays [L], all of it out, between the pass block
+//   and the align block.
+constexpr int SS_HEADER = 32;
+__host__ __device__ inline int ss_floats(int L) { return SS_HEADER + 8 * L; }
 // score_off: the end of what "emit_distmap" gives; smap_off: the end of the score block; pass_off: the end of the map-score
-// block; align_off: the end of the pass block (`passes`: its rows R, 0 = none); align_out / total: the align block's out slots
+// block; ss_off: the end of the pass block (`passes`: its rows R, 0 = none); align_off: the end of the SS block; align_out / total: the align block's out slots
 // (total does not count its trailing input, whose length only the caller knows)
-struct ConfLayout { int64_t map_off, info_off, score_off, score_out, smap_off, align_off, align_out, total, pass_off; };
-__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0, int smap = 0, int passes = 0) {
+struct ConfLayout { int64_t map_off, info_off, score_off, score_out, smap_off, align_off, align_out, total, pass_off, ss_off; };
+__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0, int smap = 0, int passes = 0, int ss = 0) {
   const int64_t info_off = L + (emit ? (int64_t)L * L : 0), score_off = info_off + (emit ? 3 : 0);
   const int64_t smap_off = score_off + (score ? score_layout(L).total : 0);
   const int64_t pass_off = smap_off + (smap ? mapscore_floats(L) : 0);
-  const int64_t align_off = pass_off + (passes ? pass_floats(passes) : 0);
+  const int64_t ss_off = pass_off + (passes ? pass_floats(passes) : 0);
+  const int64_t align_off = ss_off + (ss ? ss_floats(L) : 0);
   return {L, info_off, score_off, score_off + score_layout(L).out, smap_off, align_off, align_off + 1,
-          align_off + (align ? align_layout(L).in : 0), pass_off};
+          align_off + (align ? align_layout(L).in : 0), pass_off, ss_off};
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -205,8 +210,8 @@ struct dmp_lane {
 };
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "score_map", "score_passes", "score_passes_chunk"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0; };
+// "score_map", "score_passes", "score_passes_chunk", "assign_ss"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0; };
 
 struct dmp_ctx {
   int device = 0;
@@ -370,6 +375,11 @@ struct dmp_ctx {
   // the delta's partial sums, then the slots of a chunk of passes (score.hip: pass_slot)
   unsigned char* pass_ws = nullptr;
   int64_t pass_ws_bytes = 0;
+  // option "assign_ss": one allocation made when the option first becomes 1 (api.hip: ss_reserve) - the counters and the
+  // ticket, the proline flags, per entity the hydrogens, the donor flags and the two bit matrices, the native's backbone
+  // (ss.hip: ss_scratch)
+  unsigned char* ss_ws = nullptr;
+  int64_t ss_ws_bytes = 0;
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -662,6 +672,14 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
 // option "search_structures" (align.hip): the model aligned with each of the K entries of the search block, then ranked
 int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
 int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the batch launch
+// option "assign_ss" (ss.hip): the proline flags of the alignment's first row (front end), then at the prediction's end the SS
+// block from d_coords and, with d_native (the score block's trace) not null, from the native's rebuilt backbone
+int64_t assign_ss_bytes(int max_L);             // the scratch a context of this capacity needs
+int64_t assign_ss_head_bytes();                 // ... of which the part that is zero between launches (in front)
+int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
+int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
+// the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
+int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);
 int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);

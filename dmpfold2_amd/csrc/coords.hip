@@ -628,13 +628,10 @@ __device__ __forceinline__ V3 ext_at(const float* ca, int L, int t) {
   return add(z0, mul(unit(cross(sub(z0, z1), sub(z2, z1))), 3.82f));
 }
 
-__global__ __launch_bounds__(256) void backbone_kernel(const float* __restrict__ ca,
-                                                       const float* __restrict__ logit, int L,
-                                                       float sxc, float syc,
-                                                       float* __restrict__ coords,
-                                                       float* __restrict__ conf) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= L) return;
+// N, CA, C, O, CB of residue r from the trace: the one statement both kernels below evaluate, so that a native trace
+// (option "assign_ss") gets the backbone the model's trace would get, bit for bit
+__device__ __forceinline__ void backbone_residue(const float* __restrict__ ca, int L, int r, float sxc, float syc,
+                                                 float* __restrict__ coords) {
   const V3 e0 = ext_at(ca, L, r), e1 = ext_at(ca, L, r + 1), e2 = ext_at(ca, L, r + 2);
   const V3 prev = sub(e0, e1), nxt = sub(e2, e1);
   const V3 mid0 = dvd(add(e1, e0), 2.0f);          // between ext[r] and ext[r+1]
@@ -664,15 +661,46 @@ __global__ __launch_bounds__(256) void backbone_kernel(const float* __restrict__
   o[6] = c_at.x; o[7] = c_at.y; o[8] = c_at.z;
   o[9] = o_at.x; o[10] = o_at.y; o[11] = o_at.z;
   o[12] = cb.x;  o[13] = cb.y;  o[14] = cb.z;
+}
+
+__global__ __launch_bounds__(256) void backbone_kernel(const float* __restrict__ ca,
+                                                       const float* __restrict__ logit, int L,
+                                                       float sxc, float syc,
+                                                       float* __restrict__ coords,
+                                                       float* __restrict__ conf) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= L) return;
+  backbone_residue(ca, L, r, sxc, syc, coords);
   conf[r] = 1.0f / (1.0f + expf(-logit[r]));
+}
+
+__global__ __launch_bounds__(256) void backbone_trace_kernel(const float* __restrict__ ca, int L, float sxc, float syc,
+                                                             float* __restrict__ coords) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= L) return;
+  backbone_residue(ca, L, r, sxc, syc, coords);
+}
+
+static void backbone_constants(float* sxc, float* syc) {
+  const double ang = 3.14159265358979323846 / 2.0 - asin(1.0 / sqrt(3.0));
+  *sxc = (float)(1.5 * cos(ang));
+  *syc = (float)(1.5 * sin(ang));
 }
 
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s) {
-  const double ang = 3.14159265358979323846 / 2.0 - asin(1.0 / sqrt(3.0));
-  const float sxc = (float)(1.5 * cos(ang)), syc = (float)(1.5 * sin(ang));
+  float sxc, syc;
+  backbone_constants(&sxc, &syc);
   hipLaunchKernelGGL(backbone_kernel, dim3(cdiv(L, 256)), dim3(256), 0, s, d_ca, d_logit, L, sxc,
                      syc, d_coords, d_conf_out);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s) {
+  float sxc, syc;
+  backbone_constants(&sxc, &syc);
+  hipLaunchKernelGGL(backbone_trace_kernel, dim3(cdiv(L, 256)), dim3(256), 0, s, d_ca, L, sxc, syc, d_coords);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

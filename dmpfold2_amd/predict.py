@@ -233,13 +233,18 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-class Extras(namedtuple("Extras", "distmap native structure library score_map score_passes",
-                        defaults=(False, None, None, None, False, False))):
+class Extras(_score._Beside, namedtuple("Extras", "distmap native structure library score_map score_passes",
+                                        defaults=(False, None, None, None, False, False))):
     """What one call asks for besides the prediction itself, as `Engine.predict` documents each: `distmap` (return the
     map), `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map),
-    `score_passes` (score every recycling pass).
+    `score_passes` (score every recycling pass) and, a keyword carried beside the tuple's six fields, `ss` (assign secondary
+    structure).
     The public methods build one in their first lines; everything below them takes and carries the record."""
-    __slots__ = ()
+    _beside = ("ss", False)
+    ss = False
+
+    def __new__(cls, *args, ss=False, **kw):
+        return super().__new__(cls, *args, **kw)._with(bool(ss))
 
 
 # The options that decide the layout of a `d_conf` buffer, in the order of a row of `agree_options`.
@@ -248,8 +253,17 @@ LAYOUT_OPTIONS = ("emit_distmap", "score_native", "score_map", "align_structure"
 # The layout options as one prediction runs with them: `emit` .. `align` bools, `search` the K of "search_structures";
 # `alloc`: size the buffer as if "emit_distmap" were on (a pipeline whose engines disagree on that option alone);
 # `max_L`: the context's, for the rule of B0; `passes`: the rows R of the pass block of "score_passes" (None = off), which
-# follow the prediction's own depth.
-Flags = namedtuple("Flags", "emit alloc score score_map align search max_L passes", defaults=(None, None))
+# follow the prediction's own depth; `ss`: option "assign_ss" on.
+Flags = namedtuple("Flags", "emit alloc score score_map align search max_L passes ss", defaults=(None, None, False))
+
+
+def agree_ss(values):
+    """The `ss` of a prediction's Flags from option "assign_ss" as every engine that may run it holds it: they must agree -
+    RuntimeError if not."""
+    values = [bool(v) for v in values]
+    if any(v != values[0] for v in values):
+        raise RuntimeError("the engines must agree on \"assign_ss\" (the blocks behind the SS block move with it); use set_ss")
+    return values[0]
 
 
 def agree_passes(values, score, iterations):
@@ -298,7 +312,7 @@ def _stage(device, L, template_ca, flags, extras):
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, passes=flags.passes)
+                 flags.max_L, passes=flags.passes, ss=flags.ss)
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
     if library is not None:
@@ -381,8 +395,11 @@ class Engine:
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
                 minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                score_map=False, score_passes=False):
+                score_map=False, score_passes=False, ss=False):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
+        `ss`: secondary structure is assigned to the final backbone on the GPU from its hydrogen bonds (option "assign_ss", set
+        for this call only) and, with `native` given whole (no NaN row), to the native's backbone rebuilt from its trace; what
+        the call returns does not change, the result is in `ss` (score.unpack_ss) and `ss_block`.
         `score_passes` (needs `native`): every recycling pass's trace - not only the one the best-of rule kept - is scored
         against the native on the GPU (option "score_passes", set for this call only together with "score_native"), with
         its mean confidence logit and its convergence delta beside the scores; what the call returns does not change, the
@@ -410,7 +427,7 @@ class Engine:
         after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
         call synchronises with the GPU once per pass."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
         return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
 
     def _forget_last(self):
@@ -422,6 +439,13 @@ class Engine:
     pass_block = property(lambda self: self._last.out.pass_block, doc='"score_passes": 16 + 8R floats, or None')
     align_block = property(lambda self: self._last.out.align_block, doc='"align_structure": 25 + 2L + 3m floats, or None')
     search_block = property(lambda self: self._last.out.search_block, doc='"search_structures": 26K + 2LK + 3M floats, or None')
+    ss_block = property(lambda self: self._last.out.ss_block, doc='"assign_ss": 32 + 8L floats, or None')
+
+    @property
+    def ss(self):
+        """The secondary structure of the last prediction as score.unpack_ss gives it, None if it ran without option
+        "assign_ss".  Synchronises with the GPU."""
+        return self._unpacked("ss_block", _score.unpack_ss)
 
     def _unpacked(self, field, unpack):
         """A block of the last prediction through `unpack`(block, L), None without it.  Synchronises with the GPU."""
@@ -471,9 +495,9 @@ class Engine:
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                       score_map=False, score_passes=False):
+                       score_map=False, score_passes=False, ss=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
         return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras)
 
     def _upload(self, alnmat):
@@ -502,6 +526,8 @@ class Engine:
             want["score_native"] = 1
         if extras.score_passes and not self.get_option("score_passes"):
             want["score_passes"] = 1                      # (behind "score_native", which the library asks for at begin)
+        if extras.ss and not self.get_option("assign_ss"):
+            want["assign_ss"] = 1
         if extras.structure is not None and not self.get_option("align_structure"):
             _score.as_structure(extras.structure)                                          # (a bad shape raises before anything changes)
             want["align_structure"] = 1
@@ -536,7 +562,7 @@ class Engine:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         flags = Flags(bool(emit), bool(emit), bool(score), bool(smap and emit and score), bool(align), search, self.max_L,
-                      agree_passes([self.get_option("score_passes")], score, iterations))
+                      agree_passes([self.get_option("score_passes")], score, iterations), bool(self.get_option("assign_ss")))
         with torch.cuda.device(self.device):
             self._forget_last()
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
@@ -582,22 +608,22 @@ class Engine:
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
                         minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                        score_map=False, score_passes=False):
+                        score_map=False, score_passes=False, ss=False):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
         which has float32's range, at about half the convolution rate."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
         out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
         return out.public(extras.distmap, blocks=False)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
                                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                               score_map=False, score_passes=False):
+                               score_map=False, score_passes=False, ss=False):
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
-        `score_map`, `score_passes`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment
+        `score_map`, `score_passes`, `ss`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment
         and hits)."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
         return self._checked(d_msa, template_ca, iterations, minsteps, converge, extras).public(extras.distmap, blocks=False)
 
     def _checked(self, d_msa, template_ca, iterations, minsteps, converge, extras):
@@ -678,7 +704,7 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False, score=False, align=False, search=None, score_map=False, score_passes=False):
+                 distmap=False, score=False, align=False, search=None, score_map=False, score_passes=False, ss=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -695,7 +721,9 @@ class Pipeline:
         and `score` on); its map-score block (64 + L floats, score.unpack_map_scores) then comes behind even the search block.
         `score_passes`: every recycling pass of every target is scored against its native (`set_score_passes`, which turns
         `score` on); its pass block (16 + 8R floats, R = min(iterations + 1, 128) of that submission,
-        score.unpack_pass_scores) is then the last element of all."""
+        score.unpack_pass_scores) is then the last element of all.
+        `ss`: every target's backbone gets its secondary structure assigned (`set_ss`); its SS block (32 + 8L floats,
+        score.unpack_ss) then comes behind even the pass block."""
         self.lib = _lib.load()
         self._search = None
         self.device = _resolve_device(device)
@@ -731,6 +759,8 @@ class Pipeline:
             self.set_score_map(True)
         if score_passes:
             self.set_score_passes(True)
+        if ss:
+            self.set_ss(True)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -768,6 +798,11 @@ class Pipeline:
         if on:
             self.set_score(True)
         self.set_option("score_passes", 1 if on else 0)
+
+    def set_ss(self, on):
+        """Option "assign_ss" on every engine: targets submitted from now on get the secondary structure of their backbone
+        (and, with `set_score` on and a whole native given to `submit`, of the native's); idle pipeline only."""
+        self.set_option("assign_ss", 1 if on else 0)
 
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
@@ -819,7 +854,8 @@ class Pipeline:
             # were set (set_distmap, set_option, an engine's own set_option - then the largest any engine would write)
             flags = agree_options([e.get_option(name) for name in LAYOUT_OPTIONS] for e in self.engines)
             flags = flags._replace(max_L=self.engines[0].max_L,
-                                   passes=agree_passes([e.get_option("score_passes") for e in self.engines], flags.score, iterations))
+                                   passes=agree_passes([e.get_option("score_passes") for e in self.engines], flags.score, iterations),
+                                   ss=agree_ss(e.get_option("assign_ss") for e in self.engines))
             if flags.align and structure is not None and _score.as_structure(structure).shape[0] > flags.max_L:
                 raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {flags.max_L}")
             if flags.search and (self._search is None or len(self._search) != flags.search):
@@ -975,7 +1011,7 @@ class Pipeline:
                     if res.align_block is not None and extras.structure is None:
                         extras = extras._replace(structure=np.zeros((0, 3), dtype=np.float32))
                     extras = extras._replace(distmap=emit, score_map=res.map_block is not None,
-                                             score_passes=res.pass_block is not None)
+                                             score_passes=res.pass_block is not None, ss=res.ss_block is not None)
                     try:
                         rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, extras)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
@@ -1090,7 +1126,7 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
                   return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
                   compare_chain=None, return_alignment=False, search=None, return_hits=False, return_map_scores=False,
-                  return_pass_scores=False):
+                  return_pass_scores=False, return_ss=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -1109,26 +1145,28 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     `return_map_scores` (addition; needs `native`): the predicted distance map is scored against the native too (option
     "score_map") and the dict of score.unpack_map_scores is appended behind those.
     `return_pass_scores` (addition; needs `native`): every recycling pass is scored against the native (option
-    "score_passes") and the dict of score.unpack_pass_scores is appended last of all."""
+    "score_passes") and the dict of score.unpack_pass_scores is appended behind those.
+    `return_ss` (addition): secondary structure is assigned to the final backbone on the GPU (option "assign_ss"; with a whole
+    `native` also to the native's rebuilt backbone, with Q3 / Q8) and the dict of score.unpack_ss is appended last of all."""
     r = _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                       compare_chain, search, distmap=return_distmap, scores=return_scores, alignment=return_alignment,
-                      hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores)
+                      hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores, ss=return_ss)
     return ((r.coords, r.confs) + ((r.alnmat,) if return_alnmat else ()) + ((r.distmap,) if return_distmap else ())
             + ((r.scores,) if return_scores else ()) + ((r.alignment,) if return_alignment else ())
             + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ())
-            + ((r.pass_scores,) if return_pass_scores else ()))
+            + ((r.pass_scores,) if return_pass_scores else ()) + ((r.ss,) if return_ss else ()))
 
 
 # What `aln_to_coords` computes, by name: each of distmap, scores, alignment, hits and map_scores None unless it was wanted
 # (and, for scores, alignment and hits, unless its input - native, compare, search - was given).
-Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores", defaults=(None,))
+Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores ss", defaults=(None, None))
 
 
 def _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                   compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
-                  pass_scores=False):
-    """`aln_to_coords` -> Prediction; the six flags are its return_distmap, return_scores, return_alignment, return_hits,
-    return_map_scores and return_pass_scores."""
+                  pass_scores=False, ss=False):
+    """`aln_to_coords` -> Prediction; the seven flags are its return_distmap, return_scores, return_alignment, return_hits,
+    return_map_scores, return_pass_scores and return_ss."""
     if map_scores and native is None:
         raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
     if pass_scores and native is None:
@@ -1160,8 +1198,8 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
                                   native=native, structure=compare, library=search, score_map=bool(map_scores),
-                                  score_passes=bool(pass_scores))
-        return Prediction(out[0], out[1], alnmat, out[2] if distmap else None,
+                                  score_passes=bool(pass_scores), ss=bool(ss))
+        return Prediction(out[0], out[1], alnmat, out[2] if distmap else None, ss=eng.ss if ss else None,
                           map_scores=eng.map_scores if map_scores else None,
                           pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
@@ -1190,8 +1228,8 @@ def pdb_text(coords, confs, alnmat):
 
 
 def dmpfold_parser():
-    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --score-passes, --compare
-    and --search."""
+    """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --score-passes, --compare,
+    --search and --ss."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -1243,6 +1281,13 @@ def dmpfold_parser():
                         help="how many hits of --search to report (default 10)")
     parser.add_argument("--hits", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --search to FILE instead of standard error")
+    parser.add_argument("--ss", action="store_true", default=False,
+                        help="assign secondary structure to the model's backbone on the GPU from its hydrogen bonds (eight-state and "
+                             "three-state strings, counts, helix / strand / coil fractions; with --native given whole also the "
+                             "native's and Q3 / Q8); the result goes to standard error as one JSON line, the model on standard "
+                             "output is unchanged")
+    parser.add_argument("--ss-file", type=str, default=None, required=False, metavar="FILE",
+                        help="write the JSON line of --ss to FILE instead of standard error")
     return parser
 
 
@@ -1257,7 +1302,7 @@ def run_dmpfold(argv=None):
     r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
                       args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
                       distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
-                      hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes)
+                      hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes, ss=args.ss)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1276,4 +1321,6 @@ def run_dmpfold(argv=None):
         if r.pass_scores is not None:
             js["passes"] = _score.pass_scores_json(r.pass_scores)
         json_line(js, args.scores)
+    if args.ss:
+        json_line(_score.ss_json(r.ss), args.ss_file)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

@@ -82,32 +82,80 @@ def pass_floats(R):
     return PASS_HEADER + PASS_ROW * int(R)
 
 
-class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_L passes",
-                        defaults=(False, False, False, None, None, None, None))):
+SS_HEADER = 32                       # floats in front of the per-residue arrays of the SS block
+SS_ARRAYS = 8                        # per-residue arrays of L floats behind it
+SS_CODES = "-STIGBEH"                # code 0 .. 7 of a residue -> its letter
+SS_THREE = "CCCHHEEH"                # ... -> its three-state letter: helix (H, G, I), strand (E, B), coil (the rest)
+
+
+def ss_floats(L):
+    """Floats of the SS block (option "assign_ss") of a prediction of length L."""
+    return SS_HEADER + SS_ARRAYS * int(L)
+
+
+class _Beside:
+    """For a namedtuple subclass that carries ONE more, keyword-only value beside the tuple (`_beside` = (name, default)).
+    The tuple itself - its fields, its length, its positional order, which callers rely on - stays as it is; `_replace`,
+    ==, hash and repr know the value, and an instance made without it holds the default."""
+    _beside = None
+
+    def _with(self, value):
+        setattr(self, self._beside[0], value)
+        return self
+
+    def _replace(self, **kw):
+        name = self._beside[0]
+        value = kw.pop(name, getattr(self, name))
+        return super()._replace(**kw)._with(value)
+
+    def __eq__(self, other):
+        name, default = self._beside
+        return tuple.__eq__(self, other) is True and _same(getattr(self, name), getattr(other, name, default))
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return tuple.__hash__(self)
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", {self._beside[0]}={getattr(self, self._beside[0])!r})"
+
+
+def _same(a, b):
+    return a is b or (not hasattr(a, "shape") and not hasattr(b, "shape") and a == b)
+
+
+class Layout(_Beside, namedtuple("Layout", "L distmap score score_map align_m search max_L passes",
+                                 defaults=(False, False, False, None, None, None, None))):
     """Where everything lies in the `d_conf` buffer of a prediction of length L: the Python twin of ConfLayout / conf_layout()
     / search_base() of csrc/common.h, in the order of include/dmpfold_hip.h.  Made from what decides it - `distmap`, `score`,
     `score_map`: options "emit_distmap", "score_native", "score_map" on; `align_m`: the m the align block holds (None =
     "align_structure" off); `search`: (K, M) of option "search_structures" (None = off); `max_L`: the context's, for the rule
     of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0 counts); `passes` (keyword): the rows R
-    of the pass block of option "score_passes" (None = off).  Every offset is stated once, each from the one in front of it:
+    of the pass block of option "score_passes" (None = off); `ss` (keyword, carried beside the tuple's eight fields, default
+    off): option "assign_ss" on.  Every offset is stated once, each from the one in front of it:
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
-      (64 + L) | pass_off (T0): pass block (16 + 8R) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off
-      (B0): search block (26K + 2LK + 3M)
+      (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | align_off (A0): align block
+      (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
 
     and `total` is the floats the buffer must hold."""
-    __slots__ = ()
+    _beside = ("ss", False)
+    ss = False
 
-    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None):
+    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None, *,
+                ss=False):
         return super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
-                               None if passes is None else int(passes))
+                               None if passes is None else int(passes))._with(bool(ss))
 
     info_off = property(lambda s: s.L + (s.L * s.L if s.distmap else 0))
     score_off = property(lambda s: s.info_off + (3 if s.distmap else 0))                                    # S0
     mapscore_off = property(lambda s: s.score_off + (score_floats(s.L) if s.score else 0))                  # M0
     pass_off = property(lambda s: s.mapscore_off + (mapscore_floats(s.L) if s.score_map else 0))            # T0
-    align_off = property(lambda s: s.pass_off + (pass_floats(s.passes) if s.passes is not None else 0))     # A0
+    ss_off = property(lambda s: s.pass_off + (pass_floats(s.passes) if s.passes is not None else 0))        # U0
+    align_off = property(lambda s: s.ss_off + (ss_floats(s.L) if s.ss else 0))                              # A0
     # the end of the align block as its writer allocated it (an align_m that is no number raises ValueError) ...
     align_end = property(lambda s: s.align_off + (align_floats(s.L, s.align_m) if s.align_m is not None else 0))
     # ... and B0, its end as the library counts it: 3m of it only if m is an integer in [3, max_L]
@@ -130,7 +178,11 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
                        part(self.align_m is not None, self.align_off, self.align_end),
                        part(self.search is not None, self.search_off, self.search_end),
                        part(self.score_map, self.mapscore_off, self.pass_off),
-                       part(self.passes is not None, self.pass_off, self.align_off))
+                       part(self.passes is not None, self.pass_off, self.ss_off))._with(self.ss_block(buf))
+
+    def ss_block(self, buf):
+        """The SS block of a `d_conf` buffer as a view (32 + 8L floats), None with `ss` off."""
+        return buf[self.ss_off:self.align_off] if self.ss else None
 
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
@@ -161,30 +213,36 @@ def distmap_floats(L, on=True):
     return Layout(L, on).total
 
 
-class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block pass_block",
-                         defaults=(None, None, None, None, None, None, None))):
+class Outputs(_Beside, namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block pass_block",
+                                  defaults=(None, None, None, None, None, None, None))):
     """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
     score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
     (26K + 2LK + 3M,), with "score_map" map_block (64 + L,), with "score_passes" pass_block (16 + 8R,) - None for what is
-    absent."""
-    __slots__ = ()
+    absent.  With "assign_ss" the SS block (32 + 8L,) is `ss_block`, carried beside the tuple's nine fields (None otherwise)."""
+    _beside = ("ss_block", None)
+    ss_block = None
+
+    def __new__(cls, *args, ss_block=None, **kw):
+        return super().__new__(cls, *args, **kw)._with(ss_block)
 
     @classmethod
-    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False):
+    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False, ss=False):
         """The inverse of `public` for a caller that knows which options were on."""
         rest = iter(public)          # (the fields stand in the tuple's order: the pass block is the last of both)
-        return cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map, passes)))
+        out = cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map, passes)))
+        return out._with(next(rest) if ss else None)
 
-    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True):
+    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True, ss=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
         block, the align block, the search block and - though they lie behind the score block in the buffer - the map-score
-        block and, last, the pass block, each if present and wanted.  `blocks=False`: none of the five blocks, whatever else
-        is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
+        block, the pass block and, last of all, the SS block, each if present and wanted.  `blocks=False`: none of the six
+        blocks, whatever else is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
         if not blocks:
-            score = align = search = score_map = passes = False
+            score = align = search = score_map = passes = ss = False
         groups = ((distmap, (self.distmap, self.info)), (score, (self.score_block,)), (align, (self.align_block,)),
-                  (search, (self.search_block,)), (score_map, (self.map_block,)), (passes, (self.pass_block,)))
+                  (search, (self.search_block,)), (score_map, (self.map_block,)), (passes, (self.pass_block,)),
+                  (ss, (self.ss_block,)))
         return (self.coords, self.confs) + tuple(x for want, group in groups if want and group[0] is not None for x in group)
 
 
@@ -470,6 +528,65 @@ def pass_scores_from_json(js):
         out[name] = _from_json(js[name])
     for name in PASS_COLUMNS:
         out[name] = np.asarray([_from_json(v) for v in js[name]], dtype=np.float32)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# option "assign_ss" (include/dmpfold_hip.h): secondary structure of the final backbone from its hydrogen bonds, on the GPU.
+# DSSP's KIND of assignment, not its bits: no two-best-partner rule, no bulges, no sheet labels, no chain breaks; nobody has
+# compared the strings with that program's.  The library returns codes and integer counts; strings and ratios are formed here.
+# ---------------------------------------------------------------------------------------------------------------------
+def _letters(codes, table):
+    return "".join(table[int(v)] if v == v and 0 <= v < len(table) else "?" for v in codes)
+
+
+def _index(a):
+    """Indices the library wrote as floats -> int64, -1 for NaN."""
+    return np.where(a == a, a, -1.0).astype(np.int64)
+
+
+def unpack_ss(block, L):
+    """An SS block (32 + 8L floats, array or tensor) -> dict: ss8 (a string of L letters from "-STIGBEH"), ss3 (H, E, C),
+    n_hb, counts ({letter: residues}), n_parallel, n_antiparallel (bridge pairs), helix, strand, coil (fractions of L), e_acc,
+    p_acc, e_don, p_don (the lowest hydrogen-bond energy of each residue as acceptor / donor and its partner, -1 for none), bp1,
+    bp2 (the two lowest-numbered bridge partners, -1 where absent), has_native; with a native also ss8_native, ss3_native,
+    counts_native, q3_match, q8_match and q3, q8 (the matches over L).  A block the library answered with NaN (a latched fault)
+    gives '?' in the strings, zero counts and -1 partners."""
+    L = int(L)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != ss_floats(L):
+        raise ValueError(f"an SS block of length {L} has {ss_floats(L)} floats, got shape {tuple(b.shape)}")
+    arr = b[SS_HEADER:].reshape(SS_ARRAYS, L)
+    out = {"ss8": _letters(arr[0], SS_CODES), "ss3": _letters(arr[0], SS_THREE), "n_hb": _whole(b[0]),
+           "counts": {SS_CODES[k]: _whole(b[1 + k]) for k in range(8)}, "n_parallel": _whole(b[9]), "n_antiparallel": _whole(b[10])}
+    three = {"helix": "HGI", "strand": "EB", "coil": "-ST"}
+    for name, letters in three.items():
+        out[name] = sum(out["counts"][c] for c in letters) / float(L)
+    out["e_acc"], out["p_acc"] = arr[1].copy(), _index(arr[2])
+    out["e_don"], out["p_don"] = arr[3].copy(), _index(arr[4])
+    out["bp1"], out["bp2"] = _index(arr[5]), _index(arr[6])
+    out["has_native"] = bool(_whole(b[11]))
+    if out["has_native"]:
+        out["ss8_native"], out["ss3_native"] = _letters(arr[7], SS_CODES), _letters(arr[7], SS_THREE)
+        out["counts_native"] = {SS_CODES[k]: _whole(b[14 + k]) for k in range(8)}
+        out["q3_match"], out["q8_match"] = _whole(b[12]), _whole(b[13])
+        out["q3"], out["q8"] = out["q3_match"] / float(L), out["q8_match"] / float(L)
+    return out
+
+
+SS_JSON_KEYS = ("ss8", "ss3", "n_hb", "counts", "n_parallel", "n_antiparallel", "helix", "strand", "coil", "has_native",
+                "ss8_native", "ss3_native", "counts_native", "q3_match", "q8_match", "q3", "q8")
+
+
+def ss_json(ss, arrays=False):
+    """`unpack_ss` as a JSON-ready dict (what `dmpfold --ss` prints and `dmpfold-batch --ss` writes): the strings, the
+    counts and the fractions; with `arrays` also the per-residue energies and partners as lists (NaN becomes None)."""
+    out = {k: ss[k] for k in SS_JSON_KEYS if k in ss}
+    if arrays:
+        for k in ("e_acc", "e_don"):
+            out[k] = [_num(v) for v in ss[k]]
+        for k in ("p_acc", "p_don", "bp1", "bp2"):
+            out[k] = [int(v) for v in ss[k]]
     return out
 
 

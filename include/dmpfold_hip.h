@@ -343,6 +343,76 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * allocated when the option first becomes 1 on a context and counted in "device_mib"; an allocation failure is an error of
  * dmp_ctx_set_option and leaves the option as it was.  Measured cost: profiles/passes.txt.
  * "score_passes_chunk" (TESTS ONLY; n >= 0, default 0): at most n passes per chunk when n > 0.
+ * "assign_ss" (0 or 1, default 0; any other value: DMP_ERR_ARG): assign secondary structure to the final backbone that
+ * dmp_predict_end has just written into d_coords, from its hydrogen bonds, on the device - helix, strand and coil content
+ * and the strand pairing without a native, a partner structure or a second program.  Read when a prediction begins and held
+ * for it.  With it 0 nothing is launched, read, written or allocated, and every offset and output is bit for bit what it is
+ * without the option.  With it 1 THE d_conf ARGUMENT MUST HOLD U0 + 32 + 8L FLOATS, U0 = THE END OF WHAT "emit_distmap",
+ * "score_native", "score_map" AND "score_passes" GIVE (the end of the pass block, T0 + 16 + 8R, with "score_passes"): there
+ * sits the SS BLOCK, all of it outputs, and A0 and B0 below move behind it (search_prep's rule for B0 starts from the moved
+ * A0).  Everything else in the buffer does not change by a bit.  If "score_native" is on too and every one of the L native
+ * rows is present (no NaN x), the native is assigned as well: its trace is rebuilt into a backbone by the very device
+ * function that builds the model's from its trace (csrc/coords.hip, float32), into scratch, the same P_i apply, and the
+ * block gains the native's codes and the Q3 / Q8 agreement counts; otherwise has_native = 0.  So a native that is exactly
+ * the model's returned C-alpha trace gives ss_native equal to ss, bit for bit.  Counts are integers below 2^24, stored as
+ * floats.  Offsets relative to U0:
+ *   0                    n_hb: pairs (i, j) with hb(i, j) true (model)
+ *   1 .. 8               residues of the model with code 0 .. 7
+ *   9, 10                parallel and antiparallel bridge pairs, i < j (model)
+ *   11                   has_native (0 or 1)
+ *   12, 13               q3_match, q8_match: residues whose three-state / eight-state code equals the native's (0 if
+ *                        has_native = 0)
+ *   14 .. 21             residues of the native with code 0 .. 7 (0 if has_native = 0)
+ *   22 .. 31             zero
+ *   [32, 32 + L)         ss: code of model residue i
+ *   [32 + L, 32 + 2L)    e_acc[i]: min over the valid j of E(i, j), float64 rounded once to float32; 0 if there is no valid j
+ *   [32 + 2L, 32 + 3L)   p_acc[i]: that j, ties to the lower j; -1 if none
+ *   [32 + 3L, 32 + 5L)   e_don[j] and p_don[j], likewise over i (the bond residue j's N-H donates)
+ *   [32 + 5L, 32 + 7L)   bp1, bp2: the two lowest-numbered bridge partners of i, of either type; -1 where absent
+ *   [32 + 7L, 32 + 8L)   ss_native: code of native residue i; NaN in all L if has_native = 0
+ * A prediction that latched a device-side fault returns NaN in the whole block.
+ * The definition, the only one (Kabsch & Sander, Biopolymers 22, 2577, 1983, restated; tests/test_ss_cpu.py restates it in
+ * NumPy).  Arithmetic: float64 formed from the float32 coordinates, contraction off, every operation in the order written.
+ * Residue i has atoms N_i, CA_i, C_i, O_i from d_coords; P_i is true if column i of the alignment's first row is proline
+ * (code 14); d(a, b) = sqrt((dx dx + dy dy) + dz dz).
+ * Amide hydrogen: for i >= 1, v = C_{i-1} - O_{i-1}, vv = (vx vx + vy vy) + vz vz, H_i = N_i + v / sqrt(vv) per component.
+ * Residue i is a DONOR iff i >= 1, P_i is false and vv > 0.
+ * Energy E(i, j), the C=O of i accepting the N-H of j, is defined for j a donor and |i - j| >= 2: if any of d(O_i, N_j),
+ * d(C_i, H_j), d(O_i, H_j), d(C_i, N_j) is below 0.5 then E = -9.9, otherwise E = max(27.888 (((1 / d(O_i, N_j) +
+ * 1 / d(C_i, H_j)) - 1 / d(O_i, H_j)) - 1 / d(C_i, N_j)), -9.9).  hb(i, j) = E(i, j) < -0.5, false where E is not defined
+ * or an index is outside [0, L).  The valid j of e_acc[i] are those for which E(i, j) is defined; a minimum is taken by
+ * strict '<' over rising index.
+ * Turns: t_n(i) = hb(i, i + n), n = 3, 4, 5.
+ * Helices: Hf(k) iff some i in [1, L - 5] has t_4(i - 1), t_4(i) and i <= k <= i + 3.  Gf: for every i in [1, L - 4] with
+ * t_3(i - 1) and t_3(i) and no k in i .. i + 2 having Hf, residues i .. i + 2 get Gf.  If: for every i in [1, L - 6] with
+ * t_5(i - 1) and t_5(i) and no k in i .. i + 4 having Hf or Gf, residues i .. i + 4 get If.  All three are functions of hb
+ * inside a fixed window.
+ * Bridges, defined for 1 <= i, j <= L - 2 with |i - j| >= 3 (false elsewhere): P(i, j) = [hb(i - 1, j) and hb(j, i + 1)] or
+ * [hb(j - 1, i) and hb(i, j + 1)]; A(i, j) = [hb(i, j) and hb(j, i)] or [hb(i - 1, j + 1) and hb(j - 1, i + 1)].  Ef(i) iff
+ * some j has P(i, j) and (P(i - 1, j - 1) or P(i + 1, j + 1)), or A(i, j) and (A(i - 1, j + 1) or A(i + 1, j - 1)).  Bf(i)
+ * iff i has a bridge at all.  The bridge partners of i are the j with P(i, j) or A(i, j).
+ * Turn residues: Tf(k) iff some n, i has t_n(i) and i < k < i + n.
+ * Bends: for 2 <= k <= L - 3, a = CA_k - CA_{k-2}, b = CA_{k+2} - CA_k, Sf(k) iff a.b < 0.3420201433256687 (sqrt(a.a)
+ * sqrt(b.b)), each dot product as (x x + y y) + z z.
+ * Code(k) is the first that holds of H = 7 (Hf), E = 6 (Ef), B = 5 (Bf), G = 4 (Gf), I = 3 (If), T = 2 (Tf), S = 1 (Sf),
+ * else 0 ('-').  The three-state reduction formed for Q3: 7, 4, 3 -> helix; 6, 5 -> strand; the rest -> coil.
+ * THIS IS DSSP'S KIND OF ASSIGNMENT, NOT ITS BITS: there is no two-best-partner rule, no bulges, no sheet labels and no
+ * chain breaks, and NOBODY HAS COMPARED THE STRINGS WITH THAT PROGRAM'S.  The backbone is the one the reference's
+ * Levitt-style reconstruction places from the C-alpha trace (network.py:141-177), not an experimental one.
+ * Cost with the option on: one launch in the front end (ss_capture_pro, beside the alignment's weights: the proline flags
+ * of the first row, kept for the end) and, in dmp_predict_end behind "score_passes" and in front of "align_structure", on
+ * the prediction's stream, three launches (csrc/ss.hip) - ss_prep (hydrogens and donor flags; has_native), ss_hbond (one
+ * workgroup per residue, entity and side: the energies of a row of acceptor i or a column of donor j by the same device
+ * function, the minimum of (E, index) pairs, the row of the bit matrix hb or of its transpose from the waves' ballots),
+ * ss_assign (one thread per residue: the helix flags through LDS, the bridges from the set bits of two rows, integer
+ * counts thread -> LDS -> one integer atomic per workgroup and counter, the last arriver writes the header) - and a fourth
+ * with the native (its backbone).  No float atomics: the same bits on every run.  Scratch: both bit matrices of both
+ * entities (4 x max_L x 2 ceil(max_L / 64) words, 2 MiB at max_L = 2048), the hydrogens, the donor and proline flags, the
+ * native's backbone, 21 counters and a ticket - 2.3 MiB at max_L = 2048 - allocated when the option first becomes 1 on a
+ * context and counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the option as it
+ * was.  Measured cost of dmp_predict_end with the option on (profiles/ss.txt; a collapsed model with 2.6 million hydrogen
+ * bonds at L = 2048): 0.11 ms at L = 96, 0.29 ms at 300, 1.29 ms at 1000, 2.78 ms at 2048; with the native's leg 0.14,
+ * 0.31, 1.35 and 2.86 ms - above "score_native" alone (1.10 ms at L = 2048) from L = 300 on.
  * "align_structure" (0 or 1, default 0; any other value: DMP_ERR_ARG): align the model with a structure of any length and
  * sequence on the device - a structural alignment found by superposition and dynamic programming in turn.  Read when a
  * prediction begins and held for it.  With it 0 nothing is launched, nothing extra is read or written, and every output is
@@ -350,7 +420,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
@@ -615,6 +685,7 @@ int dmp_ca_to_backbone(dmp_ctx* ctx, const float* d_ca, const float* d_conf_logi
  * WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN INTO THEM
  * (layout: dmp_ctx_set_option); WITH OPTION "score_map" = 1 64 + L MORE BEHIND THOSE (all outputs);
+ * WITH OPTION "assign_ss" = 1 32 + 8L MORE BEHIND THOSE AND THE PASS BLOCK (all outputs);
  * WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m AND THE STRUCTURE'S
  * TRACE WRITTEN INTO THEM; WITH OPTION "search_structures" = K THE SEARCH BLOCK (26K + 2LK + 3M FLOATS) BEHIND ALL OF THEM. */
 int dmp_predict(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, const float* d_template_ca,
@@ -674,6 +745,7 @@ int dmp_predict_set_vgru_result(dmp_ctx* ctx, const float* d_vout, void* event);
  * IF THE PREDICTION BEGAN WITH OPTION "emit_distmap" = 1 d_conf MUST HOLD L + L*L + 3 FLOATS (layout: dmp_ctx_set_option).
  * IF IT BEGAN WITH OPTION "score_native" = 1 d_conf MUST HOLD 5L + 24 FLOATS MORE; the native trace and lnorm are read
  * from them here; WITH OPTION "score_map" = 1 64 + L MORE BEHIND THOSE;
+ * WITH OPTION "assign_ss" = 1 32 + 8L MORE BEHIND THOSE AND THE PASS BLOCK (the secondary structure is assigned here);
  * WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, m and the structure's trace read here;
  * WITH OPTION "search_structures" = K the search block behind all of them, the m_k and the traces read here. */
 int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream);
@@ -736,6 +808,7 @@ int dmp_pipeline_set_option(dmp_pipeline* p, const char* name, int value);
  * L + L*L + 3 FLOATS (layout: dmp_ctx_set_option); its tail then carries this ticket's own best_pass and passes_run.
  * WITH OPTION "score_native" = 1 ON THE PIPELINE d_conf MUST HOLD 5L + 24 FLOATS MORE, THE NATIVE TRACE AND lnorm WRITTEN
  * INTO THEM BEFORE ready_event; WITH OPTION "score_map" = 1 64 + L MORE BEHIND THOSE (all outputs);
+ * WITH OPTION "assign_ss" = 1 32 + 8L MORE BEHIND THOSE AND THE PASS BLOCK (all outputs);
  * WITH OPTION "align_structure" = 1 25 + 2L + 3m MORE BEHIND THOSE, LIKEWISE;
  * WITH OPTION "search_structures" = K THE SEARCH BLOCK BEHIND ALL OF THEM, LIKEWISE. */
 int64_t dmp_pipeline_submit(dmp_pipeline* p, const uint8_t* d_msa, int N, int L, const float* d_template_ca, int nloops,
