@@ -1116,6 +1116,8 @@ int dmp_stem_bwd(dmp_ctx* ctx, const float* d_u, const uint8_t* d_idx, const flo
   CHECK_CAP(L, 1);
   CHECK_W();
   DMP_ARG(d_u && d_idx && d_dy && d_mat1d && d_dmap && d_dw && d_dparams && d_dmat1d, "null argument");
+  DMP_ARG(ctx->planes_L == L, "dmp_stem_static has not run for this target on this context: its last target had L = %d, "
+                              "this one has L = %d (the covariance planes belong to that one)", ctx->planes_L, L);
   return stem_bwd(ctx, d_u, d_idx, d_dy, d_mat1d, d_dmap, L, d_dw, d_dparams, d_dmat1d, STREAM);
 }
 

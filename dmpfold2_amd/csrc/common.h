@@ -293,6 +293,8 @@ struct dmp_ctx {
   // pair trunk
   float* z0 = nullptr;      // [384][L][L]
   float* planes = nullptr;  // [442][L][L]: the coupling channels 21a+b and the contact channel as planes (stem_static's B operand)
+  int planes_L = 0;         // what the last stem_static left there: its target's length (0: none ran yet) and whether it had
+  bool planes_live = false; // covariance features (false: a single-sequence target, the planes were not written); stem_bwd reads both
   float* dmap = nullptr;    // [L][L]
   float* u = nullptr;       // [128][L][L]
   float* xa = nullptr;      // padded activations

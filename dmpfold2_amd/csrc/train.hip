@@ -817,6 +817,10 @@ __global__ __launch_bounds__(256) void stem_bias_dist_kernel(const float* __rest
     dw[(int64_t)o * STEM_IN + (STEM_IN - 1)] = (float)(((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
   }
 }
+// dW[o][512 .. 953] = 0: the covariance and contact columns of a target without features      grid: 384   block: 256
+__global__ __launch_bounds__(256) void stem_zero_cov_dw_kernel(float* __restrict__ dw) {
+  for (int q = threadIdx.x; q < NS * NS + 1; q += 256) dw[(int64_t)blockIdx.x * STEM_IN + WIDTH + q] = 0.f;
+}
 // dW[o0 + o][c] = sum_i mat1d[c][i] T[(o L + i)][c]        grid: (2, ST_OCH)   block: 256 (thread = sequence channel c)
 __global__ __launch_bounds__(256) void stem_outer_dw_kernel(const float* __restrict__ T, const float* __restrict__ mat1d, int L,
                                                             int o0, float* __restrict__ dw) {
@@ -838,7 +842,8 @@ __global__ __launch_bounds__(64) void stem_dmat1d_kernel(const float* __restrict
 }
 
 // d_dw: 384 x 955 (resnet.0.lin.weight.grad); d_dparams: [lin.bias.grad 384][norm.weight.grad 128][norm.bias.grad 128];
-// d_dmat1d: 512 x L.  dmp_stem_static must have run for this target on this context (the covariance planes).
+// d_dmat1d: 512 x L.  dmp_stem_static must have run for this target on this context (the covariance planes): the entry
+// point refuses another length (c->planes_L); without features (c->planes_live false) columns 512 .. 953 of d_dw are 0.
 int stem_bwd(dmp_ctx* c, const float* d_u, const uint8_t* d_idx, const float* d_dy, const float* d_mat1d,
              const float* d_dmap, int L, float* d_dw, float* d_dparams, float* d_dmat1d, hipStream_t s) {
   const Weights& W = c->W;
@@ -862,10 +867,16 @@ int stem_bwd(dmp_ctx* c, const float* d_u, const uint8_t* d_idx, const float* d_
   DMP_LAUNCH_CHECK();
   GemmArgs g{};
   g.alpha = 1.f; g.beta = 0.f; g.bias_n = nullptr; g.lower_tiles = false;
-  // covariance channels 512 .. 953: dW[:, 512 + q] = DZ planes^T
-  g.A = dz; g.sam = LL; g.sak = 1; g.B = c->planes; g.sbk = 1; g.sbn = LL; g.C = d_dw + WIDTH; g.ldc = STEM_IN;
-  g.M = STEM_OUT; g.N = NS * NS + 1; g.K = LL;
-  if ((rc = gemm_f32(g, s))) return rc;
+  // covariance channels 512 .. 953: dW[:, 512 + q] = DZ planes^T; a target without features (dmp_stem_static with
+  // d_inv = NULL did not write the planes: they hold an earlier target's, or nothing) has zero channels there
+  if (c->planes_live) {
+    g.A = dz; g.sam = LL; g.sak = 1; g.B = c->planes; g.sbk = 1; g.sbn = LL; g.C = d_dw + WIDTH; g.ldc = STEM_IN;
+    g.M = STEM_OUT; g.N = NS * NS + 1; g.K = LL;
+    if ((rc = gemm_f32(g, s))) return rc;
+  } else {
+    hipLaunchKernelGGL(stem_zero_cov_dw_kernel, dim3(STEM_OUT), dim3(256), 0, s, d_dw);
+    DMP_LAUNCH_CHECK();
+  }
   // outer-product channels: panels of ST_OCH stem channels, T[(o, i)][c] = sum_j dz[o][i][j] mat1d[c][j]
   for (int o0 = 0; o0 < STEM_OUT; o0 += ST_OCH) {
     g.A = dz + (int64_t)o0 * LL; g.sam = L; g.sak = 1; g.B = d_mat1d; g.sbk = 1; g.sbn = L; g.C = panel; g.ldc = WIDTH;

@@ -274,6 +274,8 @@ int stem_static(dmp_ctx* c, const float* d_mat1d, const float* d_inv, const floa
     DMP_HIP(hipMemcpyAsync(c->planes + (int64_t)NS * NS * LL, d_contacts, sizeof(float) * LL, hipMemcpyDeviceToDevice, s));
     planes = c->planes;
   }
+  c->planes_L = L;                                        // for the stem's backward (train.hip), which reads the planes again
+  c->planes_live = planes != nullptr;
   hipLaunchKernelGGL(stem_static_kernel, dim3((unsigned)cdiv64(LL, 64)), dim3(256), 0, s, W.stemT, W.stem_b,
                      d_mat1d, planes, L, d_z0);
   DMP_LAUNCH_CHECK();

@@ -641,7 +641,10 @@ int dmp_head_conv_bwd(dmp_ctx* ctx, const float* d_x, const float* d_g, int L, f
  * dmp_stem_maxout_winners: from d_z0 (dmp_stem_static) and d_dmap the maxout output d_u (128 x L x L, before the
  * InstanceNorm) and the winner of every triple, d_idx (128 x L x L bytes, 0..2).  dmp_stem_bwd: d_dy = gradient w.r.t. the
  * stem's output; outputs d_dw (384 x 955 = resnet.0.lin.weight.grad), d_dparams (640 floats: lin.bias.grad 384,
- * norm.weight.grad 128, norm.bias.grad 128) and d_dmat1d (512 x L: what flows on into the sequence trunk).  With these and
+ * norm.weight.grad 128, norm.bias.grad 128) and d_dmat1d (512 x L: what flows on into the sequence trunk).  The context
+ * remembers what its last dmp_stem_static (or prediction) left in the planes: dmp_stem_bwd returns DMP_ERR_ARG, with nothing
+ * enqueued, when that target's length was not L (or none ran yet), and after a dmp_stem_static without features (d_inv =
+ * d_contacts = NULL) columns 512 .. 953 of d_dw are exactly 0 - the planes are not read.  With these and
  * the block / head entry points above a caller runs autograd's backward through the whole of net.resnet
  * (tests/test_gpu_train.py). */
 int dmp_stem_maxout_winners(dmp_ctx* ctx, const float* d_z0, const float* d_dmap, int L, float* d_u, uint8_t* d_idx, void* stream);

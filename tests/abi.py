@@ -30,13 +30,18 @@ class Stages:
     GUARD_PENDING_BYTES = 1 << 30      # outputs held for the guard check before one is made on the spot
 
     def poisoned(self, shape, dtype=torch.float32):
-        """An output of `shape`: NaN, followed by a NaN guard tail of GUARD elements (checked by check_guards)."""
+        """An output of `shape`: NaN, followed by a NaN guard tail of GUARD elements (checked by check_guards); for uint8
+        (the winner buffers of the training slice) the poison and the guard are 0xFF."""
         n = 1
         for d in shape:
             n *= int(d)
         if self._guard_bytes > self.GUARD_PENDING_BYTES:
             self.check_guards()        # bound the memory held by tests that never check
-        buf = torch.full((n + self.GUARD,), float("nan"), dtype=dtype, device=self.dev)
+        if dtype.is_floating_point:
+            buf = torch.full((n + self.GUARD,), float("nan"), dtype=dtype, device=self.dev)
+        else:                          # the winners (uint8): 0xFF is no winner, so an unwritten byte is visible too
+            assert dtype == torch.uint8
+            buf = torch.full((n + self.GUARD,), 0xFF, dtype=dtype, device=self.dev)
         self._guards.append((buf, n))
         self._guard_bytes += buf.numel() * buf.element_size()
         return buf[:n].view(shape)
@@ -45,12 +50,13 @@ class Stages:
         return self.poisoned(shape)
 
     def check_guards(self):
-        """Wait for the queued work; every guard tail since the last check must still be NaN.  Forgets those guards."""
+        """Wait for the queued work; every guard tail since the last check must still be NaN (0xFF after a uint8 output).
+        Forgets those guards."""
         torch.cuda.synchronize(self.dev)
         guards, self._guards, self._guard_bytes = self._guards, [], 0
         for buf, n in guards:
             tail = buf[n:]
-            bad = int((~torch.isnan(tail)).sum())
+            bad = int((~torch.isnan(tail)).sum()) if tail.dtype.is_floating_point else int((tail != 0xFF).sum())
             assert bad == 0, f"{bad} of the {tail.numel()} guard elements after an output of {n} elements were written"
 
     def to(self, a, dtype=torch.float32):
@@ -148,7 +154,7 @@ class Stages:
         """the float32 forward of a training step: maxout output + the winner of every quadruple (uint8)"""
         L = x.shape[-1]
         u = self.f32(128, L, L)
-        idx = torch.empty((128, L, L), dtype=torch.uint8, device=self.dev)
+        idx = self.poisoned((128, L, L), torch.uint8)
         self.call("dmp_block_conv5x5_maxout_winners", block, x, L, u, idx)
         return u, idx
 
@@ -161,7 +167,7 @@ class Stages:
     def stem_winners(self, z0, dmap):
         L = dmap.shape[0]
         u = self.f32(128, L, L)
-        idx = torch.empty((128, L, L), dtype=torch.uint8, device=self.dev)
+        idx = self.poisoned((128, L, L), torch.uint8)
         self.call("dmp_stem_maxout_winners", z0, dmap, L, u, idx)
         return u, idx
 
