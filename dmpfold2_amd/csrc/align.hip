@@ -47,6 +47,24 @@ struct AlignArgs {
   unsigned* ticket;      // [2] stage 1, stage 2: zero between launches
 };
 
+// What of an AlignArgs lies in a scratch: the parts of the slot at `sl` (common.h: search_slot(L, max_m)) and its two tickets.
+// "align_structure" fills its one on the host, "search_structures" one per entry on the device.
+__host__ __device__ inline void align_slot_args(AlignArgs& a, unsigned char* sl, const SearchSlot& slot, int L, int max_m, unsigned* tickets) {
+  a.L = L;
+  a.max_m = max_m;
+  a.dir_stride = (size_t)(L + 1) * (size_t)(max_m + 1);
+  a.bali_stride = (size_t)(1 + 2 * L);
+  a.pm = reinterpret_cast<float*>(sl + slot.pm);
+  a.qs = reinterpret_cast<float*>(sl + slot.qs);
+  a.hdr = reinterpret_cast<double*>(sl + slot.hdr);
+  a.rec = reinterpret_cast<double*>(sl + slot.rec);
+  a.surv = reinterpret_cast<int*>(sl + slot.surv);
+  a.btm = reinterpret_cast<double*>(sl + slot.btm);
+  a.bali = reinterpret_cast<int*>(sl + slot.bali);
+  a.dir = sl + slot.dir;
+  a.ticket = tickets;
+}
+
 // ---------------------------------------------------------------------------------------
 // align_prep
 // ---------------------------------------------------------------------------------------
@@ -432,19 +450,7 @@ __device__ __forceinline__ bool search_entry(const SearchArgs& sa, int first, Al
   a.out = b + lay.hdr + (int64_t)ALIGN_HEADER * k;
   a.ali = b + lay.res + 2 * (int64_t)sa.L * k;
   a.trace = b + lay.in + (ok ? 3 * tab[2 + k] : 0);
-  a.L = sa.L;
-  a.max_m = sa.max_m;
-  a.dir_stride = (size_t)(sa.L + 1) * (size_t)(sa.max_m + 1);
-  a.bali_stride = (size_t)(1 + 2 * sa.L);
-  a.pm = reinterpret_cast<float*>(sl + sa.slot.pm);
-  a.qs = reinterpret_cast<float*>(sl + sa.slot.qs);
-  a.hdr = reinterpret_cast<double*>(sl + sa.slot.hdr);
-  a.rec = reinterpret_cast<double*>(sl + sa.slot.rec);
-  a.surv = reinterpret_cast<int*>(sl + sa.slot.surv);
-  a.btm = reinterpret_cast<double*>(sl + sa.slot.btm);
-  a.bali = reinterpret_cast<int*>(sl + sa.slot.bali);
-  a.dir = sl + sa.slot.dir;
-  a.ticket = reinterpret_cast<unsigned*>(sa.ws + SEARCH_TAB_BYTES) + 2 * y;
+  align_slot_args(a, sl, sa.slot, sa.L, sa.max_m, reinterpret_cast<unsigned*>(sa.ws + SEARCH_TAB_BYTES) + 2 * y);
   return true;
 }
 
@@ -469,7 +475,7 @@ __global__ __launch_bounds__(SC_THREADS) void search_prep_kernel(SearchArgs sa) 
   __shared__ int64_t part[SC_THREADS];
   __shared__ int sh_ok;
   const int tid = threadIdx.x, K = sa.K, L = sa.L;
-  const int64_t B0 = search_base(sa.lay, L, sa.align, sa.align ? sa.conf[sa.lay.align_off] : 0.f, sa.max_L);
+  const int64_t B0 = search_base(sa.lay, L, sa.align, sa.align ? sa.conf[sa.lay.align.off] : 0.f, sa.max_L);
   float* b = sa.conf + B0;
   int64_t* tab = search_tab(sa);
   int mine = 0, mk[PER];
@@ -559,6 +565,10 @@ int align_kernel_attrs(dmp_ctx* c) {
   return DMP_OK;
 }
 
+// The scratch of "align_structure" (dmp_ctx::align_ws): the head - the two tickets - then the one slot, the largest a length takes.
+constexpr int64_t ALIGN_HEAD_BYTES = 16;
+ScratchNeed align_structure_need(int max_L) { return {ALIGN_HEAD_BYTES + search_slot(max_L, max_L).total, ALIGN_HEAD_BYTES}; }
+
 int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
   const AlignLayout lay = align_layout(L);
   AlignArgs a{};
@@ -566,19 +576,7 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
   a.out = d_block + 1;
   a.ali = d_block + lay.ali;
   a.trace = d_block + lay.in;
-  a.L = L;
-  a.max_m = c->max_L;
-  a.dir_stride = (size_t)(c->max_L + 1) * (size_t)(c->max_L + 1);
-  a.bali_stride = (size_t)(1 + 2 * c->max_L);
-  a.pm = c->align_pm;
-  a.qs = c->align_qs;
-  a.hdr = c->align_hdr;
-  a.rec = c->align_rec;
-  a.surv = c->align_surv;
-  a.btm = c->align_btm;
-  a.bali = c->align_bali;
-  a.dir = c->align_dir;
-  a.ticket = c->align_ticket;
+  align_slot_args(a, c->align_ws.p + ALIGN_HEAD_BYTES, search_slot(L, c->max_L), L, c->max_L, reinterpret_cast<unsigned*>(c->align_ws.p));
   hipLaunchKernelGGL(align_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a, (const float*)d_block);
   DMP_LAUNCH_CHECK();
   // a seed's overlap has at most L rows: 6L floats + L flags of LDS, 50 KB at L = 2048
@@ -608,11 +606,11 @@ int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, c
   sa.max_L = c->max_L;
   sa.max_m = c->run.search_mm > 0 ? c->run.search_mm : c->max_L;
   sa.K = c->run.search;
-  sa.ws = c->search_ws;
+  sa.ws = c->search_ws.p;
   sa.slot = search_slot(L, sa.max_m);
   sa.fault = c->seq_abort;
   const int C = search_chunk_entries(L, sa.max_m, c->run.search_chunk);
-  DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws_bytes,
+  DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws.bytes,
           "search_structures: the scratch does not hold a chunk of %d entries at L = %d, search_max_m = %d", C, L, sa.max_m);
   c->search_last_L = L;
   c->search_last_mm = sa.max_m;

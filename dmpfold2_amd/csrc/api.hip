@@ -405,15 +405,11 @@ static int coords_from_mds(dmp_ctx* c, const float* mat1d, const float* mds, int
 // End of a prediction: if a device-side fault was recorded while it ran, its outputs become NaN (an
 // invalid structure can never be mistaken for a result, and a batch can tell WHICH target failed) and
 // the fault bits are latched into the word dmp_sync_faults reports.
-// `lay`: the d_conf buffer of this prediction (common.h) - the confidences and, with option "emit_distmap", the whole extension
-// become NaN, and so do the outputs of the score block of option "score_native"; its inputs (the native trace and lnorm) are the
-// caller's and stay.  The map-score block of option "score_map" and the pass block of option "score_passes" lie between the
-// score block's end (lay.smap_off) and lay.align_off and are all outputs: the range [lay.score_out, lay.align_off) below
-// takes them in; so is the SS block of option "assign_ss" at [lay.ss_off, lay.align_off), named on its own because without
-// "score_native" lay.score_out lies inside it.  The same for the align block
-// of option "align_structure": its out slots become NaN, m in front of them and the structure's trace behind them (past
-// lay.total) stay.  (The search block of option "search_structures" lies at an offset only the device knows: search_rank,
-// the launch in front of this one, reads the same word and does the same there.)
+// `lay`: the d_conf buffer of this prediction (common.h).  What the prediction writes there becomes NaN - every block's out
+// range as the layout states it (conf_is_out) - and what the caller put there stays: the native trace and lnorm of the score
+// block, m in front of the align block and the structure's trace behind it (past lay.total).  (The search block of option
+// "search_structures" lies at an offset only the device knows: search_rank, the launch in front of this one, reads the same word
+// and does the same there.)
 __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ coords,
                                    float* __restrict__ conf, int L, ConfLayout lay, int* __restrict__ report) {
   const int f = words[0];
@@ -421,87 +417,170 @@ __global__ void fault_latch_kernel(int* __restrict__ words, float* __restrict__ 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const float nan = __builtin_nanf("");
   if (i < 15 * L) coords[i] = nan;
-  if (i < lay.score_off || (i >= lay.score_out && i < lay.align_off) || (i >= lay.ss_off && i < lay.align_off) ||
-      (i >= lay.align_out && i < lay.total))
-    conf[i] = nan;
+  if (conf_is_out(lay, i)) conf[i] = nan;
   if (i == 0) {
     atomicOr(&words[1], f);
     if (report) *report = f;          // the pipeline's per-ticket fault word (pinned host memory)
   }
 }
 
-// Option "search_structures": the scratch of a chunk, allocated when the option first becomes positive on a context (and
-// again, larger, if "search_max_m" grows afterwards) and counted in "device_mib".  It holds the table, the tickets and, for
-// every length the context takes, the slots of a whole chunk at this max_m.
+// One scratch of the frame (common.h: Scratch) brought to `need` bytes, the first `head` of them zero: nothing to do if it holds
+// that many already; else a new allocation on the context's device, the old one freed, "device_mib" following.  A failure leaves
+// the scratch and the count as they were.
+static int scratch_reserve(dmp_ctx* c, Scratch& w, int64_t need, int64_t head, const char* what) {
+  if (w.p && w.bytes >= need) return DMP_OK;
+  int prev = 0;
+  DMP_HIP(hipGetDevice(&prev));
+  DMP_HIP(hipSetDevice(c->device));
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, (size_t)need);
+  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)head);
+  if (e == hipSuccess && w.p) e = hipFree(w.p);                             // (waits for the work that uses it)
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (p) (void)hipFree(p);
+    return hip_fail(e, what, __FILE__, __LINE__);
+  }
+  c->bytes += need - w.bytes;
+  w = {(unsigned char*)p, need};
+  return DMP_OK;
+}
+static int scratch_reserve(dmp_ctx* c, Scratch& w, ScratchNeed n, const char* what) { return scratch_reserve(c, w, n.bytes, n.head, what); }
+
+// Option "search_structures": the scratch of a chunk, reserved when the option first becomes positive on a context (and again,
+// larger, if "search_max_m" grows afterwards).  It holds the table, the tickets and, for every length the context takes, the
+// slots of a whole chunk at this max_m.
 static int search_reserve(dmp_ctx* c) {
   if (c->opt.search <= 0) return DMP_OK;
   const int mm = c->opt.search_mm > 0 ? c->opt.search_mm : c->max_L;
   int64_t need = 0;
   for (int L = 8; L <= c->max_L; ++L)
     need = std::max<int64_t>(need, (int64_t)search_chunk_entries(L, mm, 0) * search_slot(L, mm).total);
-  need += SEARCH_HEAD_BYTES;
-  if (c->search_ws && c->search_ws_bytes >= need) return DMP_OK;
-  int prev = 0;
-  DMP_HIP(hipGetDevice(&prev));
-  DMP_HIP(hipSetDevice(c->device));
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, (size_t)need);
-  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)SEARCH_HEAD_BYTES);      // the tickets: zero between launches
-  if (e == hipSuccess && c->search_ws) e = hipFree(c->search_ws);           // (waits for the work that uses it)
-  (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    if (p) (void)hipFree(p);
-    return hip_fail(e, "search scratch", __FILE__, __LINE__);
-  }
-  c->bytes += need - c->search_ws_bytes;
-  c->search_ws = (unsigned char*)p;
-  c->search_ws_bytes = need;
-  return DMP_OK;
+  return scratch_reserve(c, c->search_ws, SEARCH_HEAD_BYTES + need, SEARCH_HEAD_BYTES, "search scratch");
 }
-
-// Option "score_passes": the scratch of a chunk of passes, allocated when the option first becomes 1 on a context and counted
-// in "device_mib" (score.hip has its layout).  The tickets in front are zero between launches.
+// Options "score_passes" and "assign_ss": reserved when the option first becomes 1 on a context (score.hip, ss.hip have the layouts).
 static int passes_reserve(dmp_ctx* c) {
-  if (c->pass_ws) return DMP_OK;
-  const int64_t need = score_passes_bytes(c->max_L);
-  int prev = 0;
-  DMP_HIP(hipGetDevice(&prev));
-  DMP_HIP(hipSetDevice(c->device));
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, (size_t)need);
-  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)score_passes_head_bytes());
-  (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    if (p) (void)hipFree(p);
-    return hip_fail(e, "pass-score scratch", __FILE__, __LINE__);
-  }
-  c->bytes += need;
-  c->pass_ws = (unsigned char*)p;
-  c->pass_ws_bytes = need;
+  return c->opt.passes ? scratch_reserve(c, c->pass_ws, score_passes_need(c->max_L), "pass-score scratch") : DMP_OK;
+}
+static int ss_reserve(dmp_ctx* c) {
+  return c->opt.ss ? scratch_reserve(c, c->ss_ws, assign_ss_need(c->max_L), "secondary-structure scratch") : DMP_OK;
+}
+
+// ---- the options --------------------------------------------------------------------------------------------------------
+// One table; dmp_ctx_set_option and dmp_ctx_get_option walk it.  A NEW OPTION IS ONE ROW: its name, where the value lives (a
+// member of the context or of its TailOpts `opt`), what the setter accepts - any value kept as 0 / 1 (FLAG), a range, or the
+// values of a bit mask - with the message for the rest, and who may write it.  The few options that do more name a hook:
+// `check` (a range that depends on the context), `set` (a value that lands somewhere else), `reserve` (scratch the new value
+// needs: called with the value in place, a failure puts the old one back), `get` (a value that is computed).
+enum OptAccess { OPT_RW, OPT_READ_ONLY /* "... is read only" */, OPT_GET_ONLY /* the setter has never known the name */ };
+constexpr int FLAG = INT32_MIN;      // as `lo`: any value, kept as value != 0
+struct Option {
+  const char* name;
+  int dmp_ctx::*at;                  // where the value lives: in the context ...
+  int TailOpts::*tail;               // ... or in ctx->opt (they take effect with the next prediction begun)
+  int lo, hi;                        // accepted: lo <= value <= hi ...
+  unsigned only;                     // ... and, if not 0, bit `value` set
+  const char* message;               // for the rest: a format of the value
+  OptAccess access;
+  int (*check)(const dmp_ctx*, int);
+  int (*set)(dmp_ctx*, int);
+  int (*reserve)(dmp_ctx*);
+  int (*get)(const dmp_ctx*, const char*, int*);
+  bool family;                       // the name is a prefix: "act_scale_log2_block<k>"
+};
+
+static int set_conv_f32_exact(dmp_ctx* c, int v) { c->conv_mode = v ? 1 : 0; return DMP_OK; }
+static int get_conv_f32_exact(const dmp_ctx* c, const char*, int* out) { *out = c->conv_mode == 1; return DMP_OK; }
+// "precision".  0: float32-grade split-f16 products in the convolutions and the vertical GRU (22-bit operands; the fast mode);
+// 1: the reference's arithmetic instruction for instruction - float32 MFMAs in both, library gate functions;
+// 2: full-width operands at the 16-bit matrix cores' rate - every float32 operand of the convolutions split EXACTLY
+//    into three bf16 pieces (3 x 8 = 24 significand bits), the six piece products above 2^-24 accumulated in float32
+//    (conv_bf16.h), and the vertical GRU the same way (vgru_x3.hip) with the library gate functions of setting 1
+static int set_precision(dmp_ctx* c, int v) { c->conv_mode = v; c->vgru_f32 = v == 2 ? 2 : -1; return DMP_OK; }
+static int get_precision(const dmp_ctx* c, const char*, int* out) {       // 0 / 1 / 2, or -1 for a mixed setting
+  const int v = vgru_runs_f32(c);
+  *out = c->conv_mode == v ? v : -1;
+  return DMP_OK;
+}
+static int get_vgru_f32(const dmp_ctx* c, const char*, int* out) { *out = vgru_runs_f32(c); return DMP_OK; }     // what the next prediction will run
+static int get_vgru_persistent(const dmp_ctx* c, const char*, int* out) { *out = c->vgru_persist && c->vgru_persist_ok; return DMP_OK; }
+static int get_device_mib(const dmp_ctx* c, const char*, int* out) { *out = (int)((c->bytes + (1 << 20) - 1) >> 20); return DMP_OK; }
+// 1 once every launch of the group chain this context leads has been issued (the scheduler hands the riders' results over from
+// then on)
+static int get_chain_issued(const dmp_ctx* c, const char*, int* out) {
+  *out = c->vg_leader == c && __atomic_load_n(&c->vg_done_issued, __ATOMIC_ACQUIRE) ? 1 : 0;
+  return DMP_OK;
+}
+static int get_act_scale(const dmp_ctx* c, const char* name, int* out) {  // log2 of the piece scale of block 1..16's input
+  const int b = atoi(name + 20);
+  DMP_ARG(b >= 1 && b <= NBLOCK && c->W.ready, "act_scale_log2_block<k>: k in 1..16, weights finalized");
+  int e;
+  std::frexp(c->W.blk[b - 1].x_scale, &e);
+  *out = e - 1;
+  return DMP_OK;
+}
+// of the last prediction that searched: resident align_refine workgroups per CU
+static int get_search_wg_per_cu(const dmp_ctx* c, const char*, int* out) {
+  *out = 0;
+  return c->search_last_C ? search_wg_per_cu(c->search_last_L, c->search_last_mm, out) : DMP_OK;
+}
+static int check_search_max_m(const dmp_ctx* c, int v) {                  // the caller's bound on every entry's length; 0 = max_L
+  DMP_ARG(v == 0 || (v >= 3 && v <= c->max_L), "search_max_m must be 0 or 3 .. max_L = %d, got %d", c->max_L, v);
   return DMP_OK;
 }
 
-// Option "assign_ss": the scratch of the secondary-structure assignment, allocated when the option first becomes 1 on a
-// context and counted in "device_mib" (ss.hip has its layout).  The counters and the ticket in front are zero between launches.
-static int ss_reserve(dmp_ctx* c) {
-  if (c->ss_ws) return DMP_OK;
-  const int64_t need = assign_ss_bytes(c->max_L);
-  int prev = 0;
-  DMP_HIP(hipGetDevice(&prev));
-  DMP_HIP(hipSetDevice(c->device));
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, (size_t)need);
-  if (e == hipSuccess) e = hipMemset(p, 0, (size_t)assign_ss_head_bytes());
-  (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    if (p) (void)hipFree(p);
-    return hip_fail(e, "secondary-structure scratch", __FILE__, __LINE__);
-  }
-  c->bytes += need;
-  c->ss_ws = (unsigned char*)p;
-  c->ss_ws_bytes = need;
-  return DMP_OK;
+#define DMP_STR_(x) #x
+#define DMP_STR(x) DMP_STR_(x)
+#define CTX(m) &dmp_ctx::m, nullptr
+#define TAIL(m) nullptr, &TailOpts::m
+#define ANY INT32_MIN + 1, INT32_MAX, 0, ""
+static const Option OPTIONS[] = {
+    {"conv_f32_exact", nullptr, nullptr, FLAG, 0, 0, "", OPT_RW, nullptr, set_conv_f32_exact, nullptr, get_conv_f32_exact},
+    {"tridiag_single", CTX(tridiag_single), FLAG},
+    {"tridiag_cluster", CTX(tridiag_cluster), FLAG},
+    {"cluster_local", CTX(cluster_local), FLAG},
+    {"refine_single", CTX(refine_single), FLAG},
+    {"gj_pairs", CTX(gj_pairs), FLAG},
+    {"gj_diag_blocked", CTX(gj_diag_blocked), FLAG},
+    {"gj_lookahead", CTX(gj_lookahead), 0, 2, 0, "gj_lookahead must be 0, 1 or 2"},
+    {"gj_diag_groups", CTX(gj_diag_groups), 2, 8, 1u << 2 | 1u << 4 | 1u << 8, "gj_diag_groups must be 2, 4 or 8"},
+    {"act_scaling", CTX(act_scaling), FLAG},
+    {"conv_tile_bands", CTX(conv_tile_bands), 0, 2, 0, "conv_tile_bands must be 0 (by length), 1 (16 x 16) or 2 (8 x 16)"},
+    {"vgru_persistent", CTX(vgru_persist), FLAG, 0, 0, "", OPT_RW, nullptr, nullptr, nullptr, get_vgru_persistent},
+    {"vgru_debug_drop_wg", CTX(vgru_debug_drop_wg), FLAG},                                                      // tests only
+    {"vgru_f32", CTX(vgru_f32), -1, 2, 0, "vgru_f32 must be -1 (follow conv_mode), 0, 1 or 2", OPT_RW, nullptr, nullptr, nullptr, get_vgru_f32},
+    {"precision", nullptr, nullptr, 0, 2, 0, "precision must be 0 (split f16), 1 (float32 MFMA) or 2 (exact bf16 x 3 split)", OPT_RW,
+     nullptr, set_precision, nullptr, get_precision},
+    {"conv_mode", CTX(conv_mode), 0, 2, 0, "conv_mode must be 0 (f16x3), 1 (exact f32) or 2 (bf16x6)"},
+    {"recycle_tol_mA", TAIL(tol_mA), 0, INT32_MAX, 0, "recycle_tol_mA must be >= 0 (milli-Angstrom; 0 = fixed depth), got %d"},
+    {"emit_distmap", TAIL(emit), 0, 1, 0, "emit_distmap must be 0 or 1, got %d"},
+    {"score_native", TAIL(score), 0, 1, 0, "score_native must be 0 or 1, got %d"},
+    {"score_map", TAIL(smap), 0, 1, 0, "score_map must be 0 or 1, got %d"},                 // the next prediction needs the two options it reads from
+    {"score_passes", TAIL(passes), 0, 1, 0, "score_passes must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, passes_reserve},       // needs "score_native" on
+    {"score_passes_chunk", TAIL(passes_chunk), 0, INT32_MAX, 0, "score_passes_chunk must be >= 0, got %d"},    // tests only: passes per chunk, 0 = what the budget gives
+    {"assign_ss", TAIL(ss), 0, 1, 0, "assign_ss must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, ss_reserve},
+    {"align_structure", TAIL(align), 0, 1, 0, "align_structure must be 0 or 1, got %d"},
+    {"search_structures", TAIL(search), 0, DMP_SEARCH_MAX, 0, "search_structures must be 0 or 1 .. " DMP_STR(DMP_SEARCH_MAX) ", got %d", OPT_RW,
+     nullptr, nullptr, search_reserve},
+    {"search_max_m", TAIL(search_mm), ANY, OPT_RW, check_search_max_m, nullptr, search_reserve},
+    {"search_chunk", TAIL(search_chunk), 0, INT32_MAX, 0, "search_chunk must be >= 0, got %d"},                // tests only: entries per chunk, 0 = what the budget gives
+    {"passes_run", CTX(passes_done), ANY, OPT_READ_ONLY},                                   // trunk passes of the last prediction
+    {"search_chunk_used", CTX(search_last_C), ANY, OPT_READ_ONLY},                          // of the last prediction that searched: entries per chunk
+    {"search_wg_per_cu", nullptr, nullptr, ANY, OPT_READ_ONLY, nullptr, nullptr, nullptr, get_search_wg_per_cu},
+    {"device_mib", nullptr, nullptr, ANY, OPT_GET_ONLY, nullptr, nullptr, nullptr, get_device_mib},
+    {"chain_issued", nullptr, nullptr, ANY, OPT_GET_ONLY, nullptr, nullptr, nullptr, get_chain_issued},
+    {"act_scale_log2_block", nullptr, nullptr, ANY, OPT_GET_ONLY, nullptr, nullptr, nullptr, get_act_scale, true},
+};
+#undef CTX
+#undef TAIL
+#undef ANY
+
+static const Option* option_row(const char* name) {
+  for (const Option& o : OPTIONS)
+    if (o.family ? strncmp(name, o.name, strlen(o.name)) == 0 : strcmp(name, o.name) == 0) return &o;
+  return nullptr;
 }
+static int& option_value(dmp_ctx* c, const Option& o) { return o.at ? c->*o.at : c->opt.*o.tail; }
 
 }  // namespace dmp
 
@@ -601,35 +680,15 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(best_dm, LL);
   A_(rms_partial, 64);
   A_(rms_counter, 1);
-  A_(score_pm, 3 * L);
-  A_(score_qn, 3 * L);
-  A_(score_idx, L);
-  A_(score_hdr, 8);
-  A_(score_rec, 6 * L * SCORE_REC);
-  A_(score_tot, 2);
-  A_(score_ticket, 1);
-  A_(map_cnt, 14);
-  A_(map_partial, 3 * 64);
-  A_(map_sums, 3);
-  A_(map_ticket, 3);
-  A_(align_pm, 3 * L);
-  A_(align_qs, 3 * L);
-  A_(align_hdr, 8);
-  A_(align_rec, 2 * L + 1);
-  A_(align_surv, 1 + ALIGN_SURVIVORS);
-  A_(align_btm, ALIGN_SURVIVORS);
-  A_(align_bali, ALIGN_SURVIVORS * (1 + 2 * L));
-  A_(align_dir, ALIGN_SURVIVORS * (L + 1) * (L + 1));
-  A_(align_ticket, 2);
 #undef A_
+  // the scratches of "score_native", "score_map" and "align_structure" (the other options reserve theirs when first set)
+  if (!rc) rc = scratch_reserve(c, c->score_ws, score_native_need(max_L), "score scratch");
+  if (!rc) rc = scratch_reserve(c, c->map_ws, score_map_need(), "map-score scratch");
+  if (!rc) rc = scratch_reserve(c, c->align_ws, align_structure_need(max_L), "align scratch");
   if (rc) { dmp_ctx_destroy(c); return rc; }
   if (hipMemset(c->seq_abort, 0, 2 * sizeof(int)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->delta_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   if (hipMemset(c->rms_counter, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
-  if (hipMemset(c->score_ticket, 0, sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
-  if (hipMemset(c->align_ticket, 0, 2 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
-  if (hipMemset(c->map_cnt, 0, 14 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
-  if (hipMemset(c->map_ticket, 0, 3 * sizeof(unsigned)) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   // the word recycle_delta tells the host its stop decision through (read only after the pass tail's event)
   if (hipHostMalloc((void**)&c->delta_host, sizeof(int), hipHostMallocMapped) != hipSuccess) { dmp_ctx_destroy(c); return DMP_ERR_HIP; }
   *c->delta_host = 0;
@@ -659,167 +718,27 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
 
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value) {
   DMP_ARG(ctx && name, "null argument");
-  const std::string k(name);
-  if (k == "conv_f32_exact") { ctx->conv_mode = value ? 1 : 0; return DMP_OK; }
-  if (k == "tridiag_single") { ctx->tridiag_single = value ? 1 : 0; return DMP_OK; }
-  if (k == "tridiag_cluster") { ctx->tridiag_cluster = value ? 1 : 0; return DMP_OK; }
-  if (k == "cluster_local") { ctx->cluster_local = value ? 1 : 0; return DMP_OK; }
-  if (k == "refine_single") { ctx->refine_single = value ? 1 : 0; return DMP_OK; }
-  if (k == "gj_pairs") { ctx->gj_pairs = value != 0; return DMP_OK; }
-  if (k == "gj_diag_blocked") { ctx->gj_diag_blocked = value != 0; return DMP_OK; }
-  if (k == "gj_lookahead") { DMP_ARG(value >= 0 && value <= 2, "gj_lookahead must be 0, 1 or 2"); ctx->gj_lookahead = value; return DMP_OK; }
-  if (k == "gj_diag_groups") { DMP_ARG(value == 2 || value == 4 || value == 8, "gj_diag_groups must be 2, 4 or 8"); ctx->gj_diag_groups = value; return DMP_OK; }
-  if (k == "act_scaling") { ctx->act_scaling = value ? 1 : 0; return DMP_OK; }
-  if (k == "conv_tile_bands") { DMP_ARG(value >= 0 && value <= 2, "conv_tile_bands must be 0 (by length), 1 (16 x 16) or 2 (8 x 16)"); ctx->conv_tile_bands = value; return DMP_OK; }
-  if (k == "vgru_persistent") { ctx->vgru_persist = value ? 1 : 0; return DMP_OK; }
-  if (k == "vgru_debug_drop_wg") { ctx->vgru_debug_drop_wg = value ? 1 : 0; return DMP_OK; }     // tests only
-  if (k == "vgru_f32") { DMP_ARG(value >= -1 && value <= 2, "vgru_f32 must be -1 (follow conv_mode), 0, 1 or 2"); ctx->vgru_f32 = value; return DMP_OK; }
-  if (k == "precision") {
-    // 0: float32-grade split-f16 products in the convolutions and the vertical GRU (22-bit operands; the fast mode);
-    // 1: the reference's arithmetic instruction for instruction - float32 MFMAs in both, library gate functions;
-    // 2: full-width operands at the 16-bit matrix cores' rate - every float32 operand of the convolutions split EXACTLY
-    //    into three bf16 pieces (3 x 8 = 24 significand bits), the six piece products above 2^-24 accumulated in float32
-    //    (conv_bf16.h), and the vertical GRU the same way (vgru_x3.hip) with the library gate functions of setting 1
-    DMP_ARG(value >= 0 && value <= 2, "precision must be 0 (split f16), 1 (float32 MFMA) or 2 (exact bf16 x 3 split)");
-    ctx->conv_mode = value;
-    ctx->vgru_f32 = value == 2 ? 2 : -1;
-    return DMP_OK;
-  }
-  if (k == "conv_mode") {
-    DMP_ARG(value >= 0 && value <= 2, "conv_mode must be 0 (f16x3), 1 (exact f32) or 2 (bf16x6)");
-    ctx->conv_mode = value;
-    return DMP_OK;
-  }
-  if (k == "recycle_tol_mA") {       // takes effect with the next prediction begun
-    DMP_ARG(value >= 0, "recycle_tol_mA must be >= 0 (milli-Angstrom; 0 = fixed depth), got %d", value);
-    ctx->opt.tol_mA = value;
-    return DMP_OK;
-  }
-  if (k == "emit_distmap") {         // takes effect with the next prediction begun
-    DMP_ARG(value == 0 || value == 1, "emit_distmap must be 0 or 1, got %d", value);
-    ctx->opt.emit = value;
-    return DMP_OK;
-  }
-  if (k == "score_native") {         // takes effect with the next prediction begun
-    DMP_ARG(value == 0 || value == 1, "score_native must be 0 or 1, got %d", value);
-    ctx->opt.score = value;
-    return DMP_OK;
-  }
-  if (k == "score_map") {            // takes effect with the next prediction begun, which needs the two options it reads from
-    DMP_ARG(value == 0 || value == 1, "score_map must be 0 or 1, got %d", value);
-    ctx->opt.smap = value;
-    return DMP_OK;
-  }
-  if (k == "score_passes") {         // takes effect with the next prediction begun, which needs "score_native" on
-    DMP_ARG(value == 0 || value == 1, "score_passes must be 0 or 1, got %d", value);
-    if (value) {
-      const int rc = passes_reserve(ctx);           // a failure leaves the option as it was
-      if (rc) return rc;
-    }
-    ctx->opt.passes = value;
-    return DMP_OK;
-  }
-  if (k == "score_passes_chunk") {   // tests only: at most this many passes per chunk (0 = what the budget gives)
-    DMP_ARG(value >= 0, "score_passes_chunk must be >= 0, got %d", value);
-    ctx->opt.passes_chunk = value;
-    return DMP_OK;
-  }
-  if (k == "assign_ss") {            // takes effect with the next prediction begun
-    DMP_ARG(value == 0 || value == 1, "assign_ss must be 0 or 1, got %d", value);
-    if (value) {
-      const int rc = ss_reserve(ctx);               // a failure leaves the option as it was
-      if (rc) return rc;
-    }
-    ctx->opt.ss = value;
-    return DMP_OK;
-  }
-  if (k == "align_structure") {      // takes effect with the next prediction begun
-    DMP_ARG(value == 0 || value == 1, "align_structure must be 0 or 1, got %d", value);
-    ctx->opt.align = value;
-    return DMP_OK;
-  }
-  if (k == "search_structures") {    // takes effect with the next prediction begun
-    DMP_ARG(value >= 0 && value <= DMP_SEARCH_MAX, "search_structures must be 0 or 1 .. %d, got %d", DMP_SEARCH_MAX, value);
-    const int before = ctx->opt.search;
-    ctx->opt.search = value;
-    const int rc = search_reserve(ctx);
-    if (rc) ctx->opt.search = before;
-    return rc;
-  }
-  if (k == "search_max_m") {         // the caller's bound on every entry's length; 0 = max_L
-    DMP_ARG(value == 0 || (value >= 3 && value <= ctx->max_L), "search_max_m must be 0 or 3 .. max_L = %d, got %d", ctx->max_L, value);
-    const int before = ctx->opt.search_mm;
-    ctx->opt.search_mm = value;
-    const int rc = search_reserve(ctx);
-    if (rc) ctx->opt.search_mm = before;
-    return rc;
-  }
-  if (k == "search_chunk") {         // tests only: at most this many entries per chunk (0 = what the budget gives)
-    DMP_ARG(value >= 0, "search_chunk must be >= 0, got %d", value);
-    ctx->opt.search_chunk = value;
-    return DMP_OK;
-  }
-  DMP_ARG(k != "passes_run", "passes_run is read only");
-  DMP_ARG(k != "search_chunk_used" && k != "search_wg_per_cu", "%s is read only", name);
-  set_error("unknown option %s", name);
-  return DMP_ERR_ARG;
+  const Option* o = option_row(name);
+  DMP_ARG(o && o->access != OPT_GET_ONLY, "unknown option %s", name);
+  DMP_ARG(o->access != OPT_READ_ONLY, "%s is read only", name);
+  if (o->lo != FLAG) DMP_ARG(value >= o->lo && value <= o->hi && (!o->only || (o->only >> value & 1u)), o->message, value);
+  int rc = o->check ? o->check(ctx, value) : DMP_OK;
+  if (rc) return rc;
+  if (o->set) return o->set(ctx, value);
+  int& at = option_value(ctx, *o);
+  const int before = at;
+  at = o->lo == FLAG ? value != 0 : value;
+  if (o->reserve && (rc = o->reserve(ctx))) at = before;               // a failure leaves the option as it was
+  return rc;
 }
 
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value) {
   DMP_ARG(ctx && name && h_value, "null argument");
-  const std::string k(name);
-  if (k == "conv_mode") { *h_value = ctx->conv_mode; return DMP_OK; }
-  if (k == "conv_f32_exact") { *h_value = ctx->conv_mode == 1; return DMP_OK; }
-  if (k == "act_scaling") { *h_value = ctx->act_scaling; return DMP_OK; }
-  if (k == "conv_tile_bands") { *h_value = ctx->conv_tile_bands; return DMP_OK; }
-  if (k == "device_mib") { *h_value = (int)((ctx->bytes + (1 << 20) - 1) >> 20); return DMP_OK; }    // read only
-  if (k == "vgru_persistent") { *h_value = ctx->vgru_persist && ctx->vgru_persist_ok; return DMP_OK; }
-  if (k == "vgru_debug_drop_wg") { *h_value = ctx->vgru_debug_drop_wg; return DMP_OK; }
-  if (k == "vgru_f32") { *h_value = vgru_runs_f32(ctx); return DMP_OK; }          // what the next prediction will run
-  if (k == "precision") {                                                          // 0 / 1 / 2, or -1 for a mixed setting
-    const int v = vgru_runs_f32(ctx);
-    *h_value = ctx->conv_mode == v ? v : -1;
-    return DMP_OK;
-  }
-  // read-only: 1 once every launch of the group chain this context leads has been issued (the scheduler hands the
-  // riders' results over from then on)
-  if (k == "chain_issued") { *h_value = ctx->vg_leader == ctx && __atomic_load_n(&ctx->vg_done_issued, __ATOMIC_ACQUIRE) ? 1 : 0; return DMP_OK; }
-  if (k.rfind("act_scale_log2_block", 0) == 0) {      // read-only: log2 of the piece scale of block 1..16's input
-    const int b = atoi(k.c_str() + 20);
-    DMP_ARG(b >= 1 && b <= NBLOCK && ctx->W.ready, "act_scale_log2_block<k>: k in 1..16, weights finalized");
-    int e;
-    std::frexp(ctx->W.blk[b - 1].x_scale, &e);
-    *h_value = e - 1;
-    return DMP_OK;
-  }
-  if (k == "tridiag_single") { *h_value = ctx->tridiag_single; return DMP_OK; }
-  if (k == "tridiag_cluster") { *h_value = ctx->tridiag_cluster; return DMP_OK; }
-  if (k == "cluster_local") { *h_value = ctx->cluster_local; return DMP_OK; }
-  if (k == "refine_single") { *h_value = ctx->refine_single; return DMP_OK; }
-  if (k == "gj_diag_groups") { *h_value = ctx->gj_diag_groups; return DMP_OK; }
-  if (k == "gj_lookahead") { *h_value = ctx->gj_lookahead; return DMP_OK; }
-  if (k == "gj_pairs") { *h_value = ctx->gj_pairs; return DMP_OK; }
-  if (k == "gj_diag_blocked") { *h_value = ctx->gj_diag_blocked; return DMP_OK; }
-  if (k == "recycle_tol_mA") { *h_value = ctx->opt.tol_mA; return DMP_OK; }
-  if (k == "emit_distmap") { *h_value = ctx->opt.emit; return DMP_OK; }
-  if (k == "score_native") { *h_value = ctx->opt.score; return DMP_OK; }
-  if (k == "score_map") { *h_value = ctx->opt.smap; return DMP_OK; }
-  if (k == "score_passes") { *h_value = ctx->opt.passes; return DMP_OK; }
-  if (k == "score_passes_chunk") { *h_value = ctx->opt.passes_chunk; return DMP_OK; }
-  if (k == "assign_ss") { *h_value = ctx->opt.ss; return DMP_OK; }
-  if (k == "align_structure") { *h_value = ctx->opt.align; return DMP_OK; }
-  if (k == "search_structures") { *h_value = ctx->opt.search; return DMP_OK; }
-  if (k == "search_max_m") { *h_value = ctx->opt.search_mm; return DMP_OK; }
-  if (k == "search_chunk") { *h_value = ctx->opt.search_chunk; return DMP_OK; }
-  // read only, of the last prediction that searched: entries per chunk; resident align_refine workgroups per CU
-  if (k == "search_chunk_used") { *h_value = ctx->search_last_C; return DMP_OK; }
-  if (k == "search_wg_per_cu") {
-    *h_value = 0;
-    return ctx->search_last_C ? search_wg_per_cu(ctx->search_last_L, ctx->search_last_mm, h_value) : DMP_OK;
-  }
-  if (k == "passes_run") { *h_value = ctx->passes_done; return DMP_OK; }      // read only: trunk passes of the last prediction
-  set_error("unknown option %s", name);
-  return DMP_ERR_ARG;
+  const Option* o = option_row(name);
+  DMP_ARG(o, "unknown option %s", name);
+  if (o->get) return o->get(ctx, name, h_value);
+  *h_value = option_value(const_cast<dmp_ctx*>(ctx), *o);
+  return DMP_OK;
 }
 
 int dmp_sync_faults(dmp_ctx* ctx, void* stream, int* h_bits) {
@@ -840,9 +759,8 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->bwd_ws) (void)hipFree(c->bwd_ws);
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
-  if (c->search_ws) (void)hipFree(c->search_ws);
-  if (c->pass_ws) (void)hipFree(c->pass_ws);
-  if (c->ss_ws) (void)hipFree(c->ss_ws);
+  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->ss_ws})
+    if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
   for (void* e : c->unit_ev)
@@ -1591,19 +1509,19 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // option "score_passes": R rows, one per pass the prediction was asked for; those of the passes that ran hold a pass
   // (run_depth: a convergence stop shortens run_nloops, the caller sized the buffer from what it asked for)
   const int pass_R = c->run.passes ? std::min(c->run_depth + 1, c->max_passes) : 0;
-  const ConfLayout lay = conf_layout(L, c->run.emit, c->run.score, c->run.align, c->run.smap, pass_R, c->run.ss);
+  const ConfLayout lay = conf_layout(L, c->run, pass_R);
   // option "emit_distmap": the map and {best_pass, passes_run, map_rms} behind the confidences
-  if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map_off, d_conf + lay.info_off, s))) return rc;
+  if (c->run.emit && (rc = emit_distmap(c, c->best_ca, L, c->passes_done, d_conf + lay.map.off, d_conf + lay.info.off, s))) return rc;
   // option "score_native": the score block behind that, the native trace and lnorm in it (score.hip)
-  if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score_off, s))) return rc;
+  if (c->run.score && (rc = score_native(c, d_coords, L, d_conf + lay.score.off, s))) return rc;
   // option "score_map": the map-score block behind that, from best_dm and the score block's inputs (mapscore.hip)
-  if (c->run.smap && (rc = score_map(c, L, d_conf + lay.score_off, d_conf + lay.smap_off, s))) return rc;
+  if (c->run.smap && (rc = score_map(c, L, d_conf + lay.score.off, d_conf + lay.smap.off, s))) return rc;
   // option "score_passes": the pass block behind that, from ca_pass, conf_means and what score_native packed (score.hip)
-  if (pass_R && (rc = score_passes(c, L, pass_R, std::min(c->passes_done, c->max_passes), d_conf + lay.pass_off, s))) return rc;
+  if (pass_R && (rc = score_passes(c, L, pass_R, std::min(c->passes_done, c->max_passes), d_conf + lay.pass.off, s))) return rc;
   // option "assign_ss": the SS block behind that, from d_coords and - with "score_native" - the score block's native trace (ss.hip)
-  if (c->run.ss && (rc = assign_ss(c, d_coords, L, c->run.score ? d_conf + lay.score_off : nullptr, d_conf + lay.ss_off, s))) return rc;
+  if (c->run.ss && (rc = assign_ss(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.ss.off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
-  if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align_off, s))) return rc;
+  if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)
   if (c->run.search > 0 && (rc = search_structures(c, d_coords, L, d_conf, lay, s))) return rc;
   hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, lay.total), 256)), dim3(256), 0, s,

@@ -9,6 +9,10 @@
 #include <memory>
 #include "../../include/dmpfold_hip.h"
 
+// options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
+// "score_map", "score_passes", "score_passes_chunk", "assign_ss"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0; };
+
 namespace dmp {
 
 constexpr int WIDTH = 512;     // GRU width
@@ -80,18 +84,34 @@ __host__ __device__ inline int pass_floats(int R) { return PASS_HEADER + PASS_RO
 //   and the align block.
 constexpr int SS_HEADER = 32;
 __host__ __device__ inline int ss_floats(int L) { return SS_HEADER + 8 * L; }
-// score_off: the end of what "emit_distmap" gives; smap_off: the end of the score block; pass_off: the end of the map-score
-// block; ss_off: the end of the pass block (`passes`: its rows R, 0 = none); align_off: the end of the SS block; align_out / total: the align block's out slots
-// (total does not count its trailing input, whose length only the caller knows)
-struct ConfLayout { int64_t map_off, info_off, score_off, score_out, smap_off, align_off, align_out, total, pass_off, ss_off; };
-__host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, int align = 0, int smap = 0, int passes = 0, int ss = 0) {
-  const int64_t info_off = L + (emit ? (int64_t)L * L : 0), score_off = info_off + (emit ? 3 : 0);
-  const int64_t smap_off = score_off + (score ? score_layout(L).total : 0);
-  const int64_t pass_off = smap_off + (smap ? mapscore_floats(L) : 0);
-  const int64_t ss_off = pass_off + (passes ? pass_floats(passes) : 0);
-  const int64_t align_off = ss_off + (ss ? ss_floats(L) : 0);
-  return {L, info_off, score_off, score_off + score_layout(L).out, smap_off, align_off, align_off + 1,
-          align_off + (align ? align_layout(L).in : 0), pass_off, ss_off};
+// The blocks in buffer order.  A block states where it begins, how many floats in front are the caller's input and where what
+// the library writes ends; a block whose option is off is empty (off = end).  `passes`: the rows R of the pass block, 0 =
+// none.  The align block's trailing input, whose length only the caller knows, lies behind `total`.
+struct ConfBlock { int64_t off, in, end; };                              // [off, off + in) in, [off + in, end) out
+struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, align; int64_t total; };
+__host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int passes) {
+  ConfLayout lay;
+  int64_t at = 0;
+  auto block = [&at](int64_t in, int64_t floats) { const ConfBlock b{at, in < floats ? in : floats, at + floats}; at += floats; return b; };
+  lay.conf = block(0, L);
+  lay.map = block(0, o.emit ? (int64_t)L * L : 0);
+  lay.info = block(0, o.emit ? 3 : 0);
+  lay.score = block(score_layout(L).out, o.score ? score_layout(L).total : 0);
+  // the two blocks that are written from the score block in front of them: dmp_predict_begin_units rejects them without
+  // "score_native", and the layout of such a call states what the fault latch has always taken for it - nothing is written
+  // in front of where a score block's first out slot would lie
+  const int64_t behind = o.score ? 0 : lay.score.off + score_layout(L).out;
+  lay.smap = block(behind > at ? behind - at : 0, o.smap ? mapscore_floats(L) : 0);
+  lay.pass = block(behind > at ? behind - at : 0, passes ? pass_floats(passes) : 0);
+  lay.ss = block(0, o.ss ? ss_floats(L) : 0);
+  lay.align = block(1, o.align ? align_layout(L).in : 0);
+  lay.total = at;
+  return lay;
+}
+// true for the floats a prediction writes: what becomes NaN when it latched a fault (api.hip)
+__host__ __device__ inline bool conf_is_out(const ConfLayout& lay, int64_t i) {
+  auto out = [i](const ConfBlock& b) { return i >= b.off + b.in && i < b.end; };
+  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.align);
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -100,15 +120,20 @@ __host__ __device__ inline ConfLayout conf_layout(int L, int emit, int score, in
 // m' of the B0 rule: the align block's m if that is an integer in [3, max_L], else 0 (a NaN fails the comparisons)
 __host__ __device__ inline int64_t search_base(const ConfLayout& lay, int L, int align, float align_m, int max_L) {
   const bool ok = align_m >= 3.f && align_m <= (float)max_L && align_m == floorf(align_m);
-  return lay.align_off + (align ? align_layout(L).in + 3 * (int64_t)(ok ? (int)align_m : 0) : 0);
+  return lay.align.off + (align ? align_layout(L).in + 3 * (int64_t)(ok ? (int)align_m : 0) : 0);
 }
 struct SearchLayout { int64_t rank, hdr, res, in; };                    // relative to B0; res: entry k's ali, deviation at res + 2Lk
 __host__ __device__ inline SearchLayout search_layout(int L, int K) {
   return {K, 2 * (int64_t)K, (2 + ALIGN_HEADER) * (int64_t)K, (2 + ALIGN_HEADER) * (int64_t)K + 2 * (int64_t)L * K};
 }
-// One entry's working set in the search scratch (bytes from the slot's start, every part 16-aligned): what a context holds
-// once for "align_structure", here sized from (L, max_m) - the model trace, the entry's trace, the header, the seed records,
-// the survivors, their best tm and alignments, the directions of the 16 dynamic programmes in flight.
+// The device scratch of one option at a prediction's end: one allocation (api.hip: scratch_reserve), carved by a layout function
+// beside the option's kernels; the head in front of it is zero between launches.
+struct Scratch { unsigned char* p = nullptr; int64_t bytes = 0; };
+struct ScratchNeed { int64_t bytes, head; };                            // what a context needs of one, of which the head
+
+// One alignment's working set (bytes from the slot's start, every part 16-aligned), sized from (L, max_m): the model trace,
+// the partner's trace, the header, the seed records, the survivors, their best tm and alignments, the directions of the 16
+// dynamic programmes in flight.  An entry of "search_structures" has one per chunk slot; "align_structure" is a chunk of one.
 struct SearchSlot { int64_t pm, qs, hdr, rec, surv, btm, bali, dir, total; };
 __host__ __device__ inline SearchSlot search_slot(int L, int max_m) {
   auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
@@ -208,10 +233,6 @@ struct dmp_lane {
   void* last = nullptr;    // event recorded after the most recent conv launch
   long long count = 0;     // conv launches recorded so far (event of launch i: ev[i % RING])
 };
-
-// options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "score_map", "score_passes", "score_passes_chunk", "assign_ss"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0; };
 
 struct dmp_ctx {
   int device = 0;
@@ -344,44 +365,17 @@ struct dmp_ctx {
   float* best_dm = nullptr;        // [max_L][max_L] dm of that pass (coords.hip: keep_best_dm; only with the option on)
   double* rms_partial = nullptr;   // [64] per-workgroup sums of emit_distmap
   unsigned* rms_counter = nullptr;
-  // option "score_native": the model scored against a native C-alpha trace in the d_conf buffer (include/dmpfold_hip.h)
-  float* score_pm = nullptr;       // [max_L][3] model trace, rows with a native residue only (score.hip: score_prep)
-  float* score_qn = nullptr;       // [max_L][3] native trace, the same rows
-  int* score_idx = nullptr;        // [max_L] alignment column of each such row
-  double* score_hdr = nullptr;     // [8] n, lnorm, d0, d_cut
-  double* score_rec = nullptr;     // [6 max_L][SCORE_REC] one record per seed of the superposition search
-  unsigned long long* score_tot = nullptr;   // [2] lDDT: preserved, pairs
-  unsigned* score_ticket = nullptr;          // zero between launches
-  // option "score_map": the chosen pass's distance map scored against the native trace (mapscore.hip); 1.7 KB
-  unsigned* map_cnt = nullptr;     // [14] integer counts, zero between launches
-  double* map_partial = nullptr;   // [3][64] per-workgroup error sums
-  double* map_sums = nullptr;      // [3] their totals
-  unsigned* map_ticket = nullptr;  // [3] zero between launches
-  // option "align_structure": the model aligned with a structure of any length in the d_conf buffer (align.hip); allocated
-  // with the context
-  float* align_pm = nullptr;       // [max_L][3] model trace
-  float* align_qs = nullptr;       // [max_L][3] the structure's trace
-  double* align_hdr = nullptr;     // [8] valid, n, m, lmin, minov, seeds, d0s, d_cut
-  double* align_rec = nullptr;     // [2 max_L + 1] tm of every gapless threading
-  int* align_surv = nullptr;       // [1 + ALIGN_SURVIVORS] how many seeds go on, which
-  double* align_btm = nullptr;     // [ALIGN_SURVIVORS] best tm of a refined seed ...
-  int* align_bali = nullptr;       // [ALIGN_SURVIVORS][1 + 2 max_L] ... and its alignment
-  unsigned char* align_dir = nullptr;        // [ALIGN_SURVIVORS][(max_L + 1)^2] DP directions, one byte per cell
-  unsigned* align_ticket = nullptr;          // [2] zero between launches
-  // option "search_structures": one allocation made when the option first becomes positive (api.hip: search_reserve) - the
-  // table, the tickets, then the slots of a chunk (search_slot above)
-  unsigned char* search_ws = nullptr;
-  int64_t search_ws_bytes = 0;
+  // The options at a prediction's end own one Scratch each (api.hip: scratch_reserve; the layout function named here carves it).
+  // The first three are allocated with the context, the others when their option first asks for them ("search_structures":
+  // again, larger, if "search_max_m" grows); all of them count in "device_mib".
+  dmp::Scratch score_ws;           // "score_native": the ticket | the packed native, its columns, the header | one pass slot (score.hip: score_scratch)
+  dmp::Scratch map_ws;             // "score_map": the counters and tickets | the error sums (mapscore.hip: MapScratch)
+  dmp::Scratch align_ws;           // "align_structure": the two tickets | one slot (align.hip: ALIGN_HEAD_BYTES, search_slot above)
+  dmp::Scratch search_ws;          // "search_structures": the table and the tickets | the slots of a chunk (SEARCH_HEAD_BYTES, search_slot)
+  dmp::Scratch pass_ws;            // "score_passes": the tickets | the delta's partial sums, the slots of a chunk of passes (score.hip: pass_slot)
+  dmp::Scratch ss_ws;              // "assign_ss": the counters and the ticket | the proline flags, per entity the hydrogens, the donor
+                                   // flags and the two bit matrices, the native's backbone (ss.hip: ss_scratch)
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
-  // option "score_passes": one allocation made when the option first becomes 1 (api.hip: passes_reserve) - the tickets and
-  // the delta's partial sums, then the slots of a chunk of passes (score.hip: pass_slot)
-  unsigned char* pass_ws = nullptr;
-  int64_t pass_ws_bytes = 0;
-  // option "assign_ss": one allocation made when the option first becomes 1 (api.hip: ss_reserve) - the counters and the
-  // ticket, the proline flags, per entity the hydrogens, the donor flags and the two bit matrices, the native's backbone
-  // (ss.hip: ss_scratch)
-  unsigned char* ss_ws = nullptr;
-  int64_t ss_ws_bytes = 0;
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
   bool end_refined = false;    // dmp_predict_end_refine already issued for the prediction in flight
@@ -659,12 +653,13 @@ int pass_deltas(dmp_ctx* c, int L, int rows, float* d_rows, double* d_partial, u
 int keep_best_dm(dmp_ctx* c, int L, int pass, hipStream_t s);
 int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_map, float* d_info, hipStream_t s);
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
+// what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
+ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
+    assign_ss_need(int max_L);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
 constexpr int64_t PASS_BUDGET = (int64_t)DMP_PASSES_BUDGET_MIB << 20;
-int64_t score_passes_bytes(int max_L);          // the scratch a context of this capacity needs
-int64_t score_passes_head_bytes();              // ... of which the part that is zero between launches (in front)
 int score_passes(dmp_ctx* c, int L, int R, int rows, float* d_block, hipStream_t s);
 // option "score_map" (mapscore.hip): best_dm against the native trace of the score block, into the map-score block
 int score_map(dmp_ctx* c, int L, const float* d_score_block, float* d_block, hipStream_t s);
@@ -676,8 +671,6 @@ int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, c
 int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the batch launch
 // option "assign_ss" (ss.hip): the proline flags of the alignment's first row (front end), then at the prediction's end the SS
 // block from d_coords and, with d_native (the score block's trace) not null, from the native's rebuilt backbone
-int64_t assign_ss_bytes(int max_L);             // the scratch a context of this capacity needs
-int64_t assign_ss_head_bytes();                 // ... of which the part that is zero between launches (in front)
 int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
 int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)

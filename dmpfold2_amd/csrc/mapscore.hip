@@ -282,16 +282,23 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void mapscore_select_kernel(MapScor
   if (tid == 0) { o[2 + dq] = (float)sh_h; o[5 + dq] = (float)t; }
 }
 
+// The scratch (dmp_ctx::map_ws; common.h: Scratch), bytes from its start.  The head: the counters, then the three tickets; behind
+// it the per-workgroup error sums and their totals.  1.7 KB.
+constexpr int64_t MS_WS_CNT = 0, MS_WS_TICKET = 64, MS_WS_HEAD = 80, MS_WS_PARTIAL = MS_WS_HEAD,
+                  MS_WS_SUMS = MS_WS_PARTIAL + 8 * 3 * MS_MAX_WG, MS_WS_BYTES = MS_WS_SUMS + 32;
+static_assert(4 * MS_COUNTERS <= MS_WS_TICKET && MS_WS_TICKET + 4 * 3 <= MS_WS_HEAD, "the head holds the counters and the tickets");
+ScratchNeed score_map_need() { return {MS_WS_BYTES, MS_WS_HEAD}; }
+
 int score_map(dmp_ctx* c, int L, const float* d_score_block, float* d_block, hipStream_t s) {
   MapScoreArgs a{};
   a.dm = c->best_dm;
   a.nat = d_score_block;
   a.out = d_block;
   a.L = L;
-  a.cnt = c->map_cnt;
-  a.partial = c->map_partial;
-  a.sums = c->map_sums;
-  a.ticket = c->map_ticket;
+  a.cnt = reinterpret_cast<unsigned*>(c->map_ws.p + MS_WS_CNT);
+  a.ticket = reinterpret_cast<unsigned*>(c->map_ws.p + MS_WS_TICKET);
+  a.partial = reinterpret_cast<double*>(c->map_ws.p + MS_WS_PARTIAL);
+  a.sums = reinterpret_cast<double*>(c->map_ws.p + MS_WS_SUMS);
   hipLaunchKernelGGL(mapscore_count_kernel, dim3(mapscore_groups(L)), dim3(SC_THREADS), sizeof(float) * 3 * L, s, a);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(mapscore_select_kernel, dim3(12), dim3(MS_SEL_THREADS), sizeof(float) * 3 * L, s, a);

@@ -306,24 +306,79 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   for (int k = tid; k < n; k += SC_THREADS) dev[a.idx[k]] = (float)score_dev(R, t, pm + 3 * k, qn + 3 * k);
 }
 
+// ---------------------------------------------------------------------------------------
+// the two scratches (common.h: Scratch): bytes from their start, every part 16-aligned
+// ---------------------------------------------------------------------------------------
+// A slot is one model trace's working set: the seed records, the packed trace, the lDDT totals.
+struct PassSlot { int64_t rec, pm, tot, total; };
+inline int64_t up16(int64_t v) { return (v + 15) / 16 * 16; }
+inline PassSlot pass_slot(int L) {
+  PassSlot p;
+  p.rec = 0;
+  p.pm = up16(8 * (int64_t)SCORE_REC * score_seeds(L));
+  p.tot = p.pm + up16(12 * (int64_t)L);
+  p.total = p.tot + 16;
+  return p;
+}
+// "score_native" (dmp_ctx::score_ws), sized for max_L.  The head: the search's ticket.  Then what score_prep packs once per call
+// and "score_passes" reads back - the native rows, their alignment columns, the header - and one slot: the final model is a
+// chunk of one.
+constexpr int64_t SCORE_HEAD_BYTES = 16;
+struct ScoreScratch { int64_t qn, idx, hdr, slot, total; };
+inline ScoreScratch score_scratch(int max_L) {
+  ScoreScratch w;
+  w.qn = SCORE_HEAD_BYTES;
+  w.idx = w.qn + up16(12 * (int64_t)max_L);
+  w.hdr = w.idx + up16(4 * (int64_t)max_L);
+  w.slot = w.hdr + 64;
+  w.total = w.slot + pass_slot(max_L).total;
+  return w;
+}
+// "score_passes" (dmp_ctx::pass_ws).  The head, at places that do not depend on L: PASS_MAX tickets of the search, PASS_MAX
+// tickets of the delta; then the delta's partial sums [PASS_MAX][64]; then the slots of a chunk.
+constexpr int64_t PASS_TICKET_BYTES = 2 * 4 * (int64_t)PASS_MAX;
+constexpr int64_t PASS_HEAD_BYTES = PASS_TICKET_BYTES + 8 * 64 * (int64_t)PASS_MAX;
+// passes per chunk: as many slots as the budget holds, 1 .. PASS_MAX; `cap` > 0 (option "score_passes_chunk") lowers it
+inline int pass_chunk(int L, int cap) {
+  int64_t C = PASS_BUDGET / pass_slot(L).total;
+  C = C < 1 ? 1 : (C > PASS_MAX ? PASS_MAX : C);
+  return cap > 0 && cap < C ? cap : (int)C;
+}
+ScratchNeed score_native_need(int max_L) { return {score_scratch(max_L).total, SCORE_HEAD_BYTES}; }
+ScratchNeed score_passes_need(int max_L) {
+  int64_t need = 0;
+  for (int L = 8; L <= max_L; ++L) need = std::max<int64_t>(need, pass_chunk(L, 0) * pass_slot(L).total);
+  return {PASS_HEAD_BYTES + need, PASS_TICKET_BYTES};
+}
+
+// The parts of a ScoreArgs that lie in the scratches: the native as score_prep packs it, and the slots from `slots` on, one
+// per blockIdx.y.
+static void score_scratch_args(const dmp_ctx* c, unsigned char* slots, const PassSlot& sl, unsigned* tickets, ScoreArgs& a) {
+  const ScoreScratch w = score_scratch(c->max_L);
+  a.qn = reinterpret_cast<float*>(c->score_ws.p + w.qn);
+  a.idx = reinterpret_cast<int*>(c->score_ws.p + w.idx);
+  a.hdr = reinterpret_cast<double*>(c->score_ws.p + w.hdr);
+  a.rec = reinterpret_cast<double*>(slots + sl.rec);
+  a.pm = reinterpret_cast<float*>(slots + sl.pm);
+  a.tot = reinterpret_cast<unsigned long long*>(slots + sl.tot);
+  a.ticket = tickets;
+  a.rec_stride = sl.total / 8;
+  a.pm_stride = sl.total / 4;
+  a.tot_stride = sl.total / 8;
+}
+
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
   ScoreArgs a{};
   a.model = d_coords + 3;
   a.model_row = 15;
   a.blk = d_block;
   a.L = L;
-  a.pm = c->score_pm;
-  a.qn = c->score_qn;
-  a.idx = c->score_idx;
-  a.hdr = c->score_hdr;
-  a.rec = c->score_rec;
-  a.tot = c->score_tot;
-  a.ticket = c->score_ticket;
+  score_scratch_args(c, c->score_ws.p + score_scratch(c->max_L).slot, pass_slot(c->max_L), reinterpret_cast<unsigned*>(c->score_ws.p), a);
   hipLaunchKernelGGL(score_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(score_lddt_kernel, dim3(score_lddt_groups(L)), dim3(SC_THREADS), sizeof(float) * 6 * L, s, a);
   DMP_LAUNCH_CHECK();
-  // the records hold 6 max_L seeds >= 1 + 5L; 6L floats + L flags of LDS: 50 KB at L = 2048
+  // the slot's records hold score_seeds(max_L) >= score_seeds(L) seeds; 6L floats + L flags of LDS: 50 KB at L = 2048
   hipLaunchKernelGGL(score_search_kernel, dim3(score_seeds(L)), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
@@ -332,34 +387,6 @@ int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipSt
 // ---------------------------------------------------------------------------------------
 // option "score_passes": the pass block (include/dmpfold_hip.h)
 // ---------------------------------------------------------------------------------------
-// The scratch (dmp_ctx::pass_ws).  In front, at places that do not depend on L and zero between launches: PASS_MAX tickets
-// of the search, PASS_MAX tickets of the delta; then the delta's partial sums [PASS_MAX][64]; then the slots of a chunk.  A
-// slot is one pass's working set: the seed records, the packed trace, the lDDT totals (every part 16-aligned).
-constexpr int64_t PASS_TICKET_BYTES = 2 * 4 * (int64_t)PASS_MAX;
-constexpr int64_t PASS_HEAD_BYTES = PASS_TICKET_BYTES + 8 * 64 * (int64_t)PASS_MAX;
-struct PassSlot { int64_t rec, pm, tot, total; };
-inline PassSlot pass_slot(int L) {
-  auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
-  PassSlot p;
-  p.rec = 0;
-  p.pm = up(8 * (int64_t)SCORE_REC * score_seeds(L));
-  p.tot = p.pm + up(12 * (int64_t)L);
-  p.total = p.tot + 16;
-  return p;
-}
-// passes per chunk: as many slots as the budget holds, 1 .. PASS_MAX; `cap` > 0 (option "score_passes_chunk") lowers it
-inline int pass_chunk(int L, int cap) {
-  int64_t C = PASS_BUDGET / pass_slot(L).total;
-  C = C < 1 ? 1 : (C > PASS_MAX ? PASS_MAX : C);
-  return cap > 0 && cap < C ? cap : (int)C;
-}
-int64_t score_passes_head_bytes() { return PASS_TICKET_BYTES; }
-int64_t score_passes_bytes(int max_L) {
-  int64_t need = 0;
-  for (int L = 8; L <= max_L; ++L) need = std::max<int64_t>(need, pass_chunk(L, 0) * pass_slot(L).total);
-  return PASS_HEAD_BYTES + need;
-}
-
 // pass_fill: what the block holds before the scores arrive.  Row p < rows: conf_mean, delta (+inf for pass 0; pass_deltas
 // fills in the others), NaN in the five scores, zero; row p >= rows: NaN.  The header is pass_header's.
 __global__ __launch_bounds__(SC_THREADS) void pass_fill_kernel(float* blk, int R, int rows, const float* conf_means) {
@@ -397,30 +424,19 @@ __global__ void pass_header_kernel(float* blk, int rows, const float* best_pass)
 }
 
 int score_passes(dmp_ctx* c, int L, int R, int rows, float* d_block, hipStream_t s) {
-  unsigned* tickets = reinterpret_cast<unsigned*>(c->pass_ws);
-  double* partial = reinterpret_cast<double*>(c->pass_ws + PASS_TICKET_BYTES);
-  unsigned char* slots = c->pass_ws + PASS_HEAD_BYTES;
+  unsigned* tickets = reinterpret_cast<unsigned*>(c->pass_ws.p);
+  double* partial = reinterpret_cast<double*>(c->pass_ws.p + PASS_TICKET_BYTES);
   float* d_rows = d_block + PASS_HEADER;
   hipLaunchKernelGGL(pass_fill_kernel, dim3(1), dim3(SC_THREADS), 0, s, d_block, R, rows, c->conf_means);
   DMP_LAUNCH_CHECK();
   int rc = pass_deltas(c, L, rows, d_rows, partial, tickets + PASS_MAX, s);
   if (rc) return rc;
-  const PassSlot sl = pass_slot(L);
   const int C = pass_chunk(L, c->run.passes_chunk);
   ScoreArgs a{};
   a.model_row = 3;
   a.model_stride = 3 * (int64_t)L;
   a.L = L;
-  a.qn = c->score_qn;                                  // score_native of this call left them: the same native, the same rows
-  a.idx = c->score_idx;
-  a.hdr = c->score_hdr;
-  a.rec = reinterpret_cast<double*>(slots + sl.rec);
-  a.pm = reinterpret_cast<float*>(slots + sl.pm);
-  a.tot = reinterpret_cast<unsigned long long*>(slots + sl.tot);
-  a.ticket = tickets;
-  a.rec_stride = sl.total / 8;
-  a.pm_stride = sl.total / 4;
-  a.tot_stride = sl.total / 8;
+  score_scratch_args(c, c->pass_ws.p + PASS_HEAD_BYTES, pass_slot(L), tickets, a);      // (the native: score_native of this call left it)
   for (int p0 = 0; p0 < rows; p0 += C) {               // the chunks reuse the slots: the stream orders them
     const int np = std::min(C, rows - p0);
     a.model = c->ca_pass + (int64_t)p0 * 3 * L;

@@ -49,8 +49,7 @@ inline SsScratch ss_scratch(int cap) {
   s.total = at;
   return s;
 }
-int64_t assign_ss_bytes(int max_L) { return ss_scratch(max_L).total; }
-int64_t assign_ss_head_bytes() { return SS_HEAD_BYTES; }
+ScratchNeed assign_ss_need(int max_L) { return {ss_scratch(max_L).total, SS_HEAD_BYTES}; }
 
 struct SsEntity {
   const float* bb;         // [L][5][3] N, CA, C, O, CB
@@ -332,14 +331,14 @@ __global__ __launch_bounds__(SS_THREADS) void ss_assign_kernel(SsArgs a) {
 }
 
 int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s) {
-  hipLaunchKernelGGL(ss_capture_pro_kernel, dim3(cdiv(L, 256)), dim3(256), 0, s, d_msa, L, c->ss_ws + ss_scratch(c->max_L).pro);
+  hipLaunchKernelGGL(ss_capture_pro_kernel, dim3(cdiv(L, 256)), dim3(256), 0, s, d_msa, L, c->ss_ws.p + ss_scratch(c->max_L).pro);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }
 
 int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s) {
   const SsScratch sc = ss_scratch(c->max_L);
-  unsigned char* ws = c->ss_ws;
+  unsigned char* ws = c->ss_ws.p;
   SsArgs a{};
   for (int e = 0; e < 2; ++e) {
     a.ent[e].h = (double*)(ws + sc.h[e]);
