@@ -113,6 +113,21 @@ class Stages:
         self.call("dmp_gru_vertical", m, n, L, out)
         return out
 
+    def gru_vertical_group(self, alnmats):
+        """dmp_gru_vertical_group with every member on this one context: the alignments' column tiles side by side in
+        one chain of max N + 1 rows; one (L, 512) output per member.  Waits for the chain (the uploaded codes live here)."""
+        k = len(alnmats)
+        d = [self.to(m, torch.uint8) for m in alnmats]
+        outs = [self.f32(m.shape[1], 512) for m in alnmats]
+        ctxs = (C.c_void_p * k)(*[self.eng.ctx] * k)
+        mp = (C.c_void_p * k)(*[x.data_ptr() for x in d])
+        op = (C.c_void_p * k)(*[x.data_ptr() for x in outs])
+        Ns = (C.c_int * k)(*[m.shape[0] for m in alnmats])
+        Ls = (C.c_int * k)(*[m.shape[1] for m in alnmats])
+        _lib.check(self.lib.dmp_gru_vertical_group(ctxs, k, mp, Ns, Ls, op, self._s()))
+        torch.cuda.synchronize(self.dev)
+        return outs
+
     def gru_bidir(self, which, x):
         T = x.shape[0]
         out = self.f32(T, 512)
