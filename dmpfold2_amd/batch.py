@@ -35,7 +35,8 @@ from . import score as _score
 from .score import Outputs
 from . import shard
 from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
-                      pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy)
+                      pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy, add_restrain_arguments, restrain_cutoff_to_mA,
+                      restrain_report, restrain_to_milli)
 
 
 class BatchFailures(RuntimeError):
@@ -144,8 +145,11 @@ def ca_only_text(coords, confs, alnmat):
     return "\n".join(out)
 
 
+RESTRAIN_COUNTS = ("steps", "restrained_pairs", "clashes")      # the integers of predict.restrain_report
+
+
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
-                 hits=None, hits_top=10, map_scores=None, pass_scores=None, ss=None):
+                 hits=None, hits_top=10, map_scores=None, pass_scores=None, ss=None, restrain=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
@@ -164,7 +168,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     pass_gdt_ha, pass_rmsd, pass_lddt; <stem>.scores.json gains the key "passes".  With `ss` (the dict of score.unpack_ss,
     --ss): npz gains ss8 (the string), ss_bp (int32 (L, 2): the two bridge partners), ss_e_acc, ss_e_don (float32 (L,)),
     ss_p_acc, ss_p_don (int32 (L,)) and, with a whole native, ss8_native, ss_q3 and ss_q8; pdb / ca get <stem>.ss.json (the
-    line `dmpfold --ss` prints)."""
+    line `dmpfold --ss` prints).  With `restrain` (the dict of predict.restrain_report, --restrain): npz gains the scalars
+    restrain_k, restrain_cutoff, restrain_steps, restrain_map_rms, restrain_restrained_pairs, restrain_clashes and
+    restrain_bond_dev_max; pdb / ca get <stem>.restrain.json (the line `dmpfold --restrain` prints)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -199,6 +205,8 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             if ss["has_native"]:
                 extra.update({"ss8_native": np.asarray(ss["ss8_native"], dtype=np.str_), "ss_q3": np.float32(ss["q3"]),
                               "ss_q8": np.float32(ss["q8"])})
+        if restrain is not None:
+            extra.update({"restrain_" + k: (np.int32 if k in RESTRAIN_COUNTS else np.float32)(v) for k, v in restrain.items()})
         if alignment is not None:
             extra.update({k: (np.int32 if k in ("n_ali", "seed_offset", "seeds") else np.float32)(alignment[k])
                           for k in _score.ALIGN_NAMES})
@@ -226,6 +234,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     if ss is not None:
         with open(stem + ".ss.json", "w") as fh:
             fh.write(json.dumps(_score.ss_json(ss)) + "\n")
+    if restrain is not None:
+        with open(stem + ".restrain.json", "w") as fh:
+            fh.write(json.dumps({"restrain": restrain}) + "\n")
     if alignment is not None:
         with open(stem + ".alignment.json", "w") as fh:
             fh.write(json.dumps(_score.alignment_json(alignment)) + "\n")
@@ -281,7 +292,7 @@ def cost_order(targets, iterations):
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
               converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10,
-              score_map=False, score_passes=False, ss=False):
+              score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
@@ -300,6 +311,10 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     `library`: a fold library (a score.Library, a directory of PDB files or an .npz of tools/make_library.py): every
     target's model is aligned with every entry on the GPU (Pipeline.set_search) and the ranking is written with it
     (write_result); `stats_out` then receives "hits": {stem: the best `search_top` of score.hits_json, without R and t}.
+    `restrain` (force constant K, None or 0 = off) and `restrain_cutoff` (Angstrom): every target's final refinement is
+    restrained to its predicted distance map (Pipeline.set_restrain, which turns the distance map on: it is written only with
+    `distmap`); every target's report (predict.restrain_report) is written with it (write_result) and `stats_out` receives
+    "restrain": {stem: the report}.
     `distmap`: every target's chosen-pass distance map is brought back and written too (write_result).
     `converge` (Angstrom, None = off): targets stop recycling once converged (Pipeline.set_converge); `stats_out`, a
     dict, then receives this rank's "passes_run" and "passes_saved".
@@ -315,6 +330,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         raise ValueError("score_map scores the distance maps against native structures: give `natives`")
     if score_passes and not natives:
         raise ValueError("score_passes scores every pass against native structures: give `natives`")
+    restraining = restrain_to_milli(restrain) > 0          # (a bad value raises before any work)
+    restrain_cutoff_to_mA(restrain_cutoff)
     check_output_stems(targets)
     os.makedirs(out_dir, exist_ok=True)
     # sharding needs only (L, N) estimates from a header scan: a rank parses its own targets and nobody else's
@@ -377,6 +394,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_score_passes(True)
             if ss:
                 pipe.set_ss(True)
+            if restraining:
+                pipe.set_restrain(restrain, restrain_cutoff)
             if structures:
                 pipe.set_align(True)
             if library is not None:
@@ -416,10 +435,11 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     aligned, all_alignments = set(), {}
     all_hits = {}
     all_ss = {}
+    all_restrain = {}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        out = Outputs.of(public, distmap=distmap or score_map, score=bool(natives), align=bool(structures), search=library is not None,
+        out = Outputs.of(public, distmap=distmap or score_map or restraining, score=bool(natives), align=bool(structures), search=library is not None,
                          score_map=score_map, passes=score_passes, ss=ss)
         aln_path, alnmat, _ = parsed.pop(t)
         sc = ms = ps = None
@@ -447,8 +467,12 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         if out.ss_block is not None:
             sec = _score.unpack_ss(out.ss_block, alnmat.shape[1])
             all_ss[os.path.splitext(os.path.basename(aln_path))[0]] = _score.ss_json(sec)
+        rep = None
+        if restraining:
+            rep = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap, float(out.info[2]), out.coords)
+            all_restrain[os.path.splitext(os.path.basename(aln_path))[0]] = rep
         outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap if distmap else None,
-                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps, sec))
+                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps, sec, rep))
 
     def finish(item):
         t, public = item
@@ -567,6 +591,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             stats_out["hits"] = all_hits
         if stats_out is not None and ss:
             stats_out["ss"] = all_ss
+        if stats_out is not None and restraining:
+            stats_out["restrain"] = all_restrain
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
@@ -624,6 +650,7 @@ def batch_parser():
                          "gains every target's eight-state string and helix / strand / coil fractions with their means and "
                          "medians (with --natives also mean Q3 / Q8 over the targets whose native covers every column); npz "
                          "gains ss8, ss_bp and the energy arrays, pdb / ca write <stem>.ss.json")
+    add_restrain_arguments(ap)
     return ap
 
 
@@ -677,6 +704,17 @@ def ss_summary(ss):
         vals = [v[name] for v in ss.values() if v.get(name) is not None]
         if vals:
             out["mean_" + name] = float(np.mean(vals))
+    return out
+
+
+def restrain_summary(reports):
+    """{stem: the dict of predict.restrain_report} -> the summary's part for --restrain: every target's report, and mean and
+    median of map_rms, restrained_pairs, clashes and bond_dev_max."""
+    out = {"restrained_targets": len(reports), "restrain": reports}
+    for name in ("map_rms", "restrained_pairs", "clashes", "bond_dev_max"):
+        vals = [r[name] for r in reports.values() if r.get(name) is not None]
+        out["mean_" + name] = float(np.mean(vals)) if vals else None
+        out["median_" + name] = float(np.median(vals)) if vals else None
     return out
 
 
@@ -735,7 +773,8 @@ def main(argv=None):
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
                                   structures=args.structures, library=args.library, search_top=args.search_top,
-                                  score_map=args.score_map, score_passes=args.score_passes, ss=args.ss)
+                                  score_map=args.score_map, score_passes=args.score_passes, ss=args.ss,
+                                  restrain=args.restrain, restrain_cutoff=args.restrain_cutoff)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -753,6 +792,8 @@ def main(argv=None):
         job_store.set(f"dmpfold_batch_hits/{rank}", json.dumps(passes.get("hits", {})))
     if args.ss and world > 1:
         job_store.set(f"dmpfold_batch_ss/{rank}", json.dumps(passes.get("ss", {})))
+    if args.restrain and world > 1:
+        job_store.set(f"dmpfold_batch_restrain/{rank}", json.dumps(passes.get("restrain", {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
         passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
@@ -784,6 +825,11 @@ def main(argv=None):
             for r in range(1, world):
                 sec.update(json.loads(job_store.get(f"dmpfold_batch_ss/{r}").decode()))
             summary.update(ss_summary(dict(sorted(sec.items()))))
+        if args.restrain:
+            reports = dict(passes.get("restrain", {}))
+            for r in range(1, world):
+                reports.update(json.loads(job_store.get(f"dmpfold_batch_restrain/{r}").decode()))
+            summary.update(restrain_summary(dict(sorted(reports.items()))))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

@@ -559,6 +559,8 @@ static const Option OPTIONS[] = {
     {"score_passes", TAIL(passes), 0, 1, 0, "score_passes must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, passes_reserve},       // needs "score_native" on
     {"score_passes_chunk", TAIL(passes_chunk), 0, INT32_MAX, 0, "score_passes_chunk must be >= 0, got %d"},    // tests only: passes per chunk, 0 = what the budget gives
     {"assign_ss", TAIL(ss), 0, 1, 0, "assign_ss must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, ss_reserve},
+    {"restrain_milli", TAIL(restrain), 0, 100000, 0, "restrain_milli must be 0 .. 100000, got %d"},               // force constant k * 1000; 0 = off
+    {"restrain_cut_mA", TAIL(restrain_cut), 0, 100000, 0, "restrain_cut_mA must be 0 .. 100000, got %d"},         // milli-Angstrom
     {"align_structure", TAIL(align), 0, 1, 0, "align_structure must be 0 or 1, got %d"},
     {"search_structures", TAIL(search), 0, DMP_SEARCH_MAX, 0, "search_structures must be 0 or 1 .. " DMP_STR(DMP_SEARCH_MAX) ", got %d", OPT_RW,
      nullptr, nullptr, search_reserve},
@@ -1452,7 +1454,7 @@ int dmp_predict_issue_unit(dmp_ctx* ctx, void* stream) {
     if (!rc) rc = coords_from_mds(c, c->mat1d, c->mds, L, c->ca, s);
     if (!rc && pass == 0 && c->run_refine > 0) rc = refine_coords(c, c->ca, L, c->run_refine, s);
     if (!rc) rc = select_best(c, c->conf, c->ca, L, pass, c->max_passes, s);
-    if (!rc && c->run.emit) rc = keep_best_dm(c, L, pass, s);     // head0 is still this pass's plane here
+    if (!rc && (c->run.emit || c->run.restrain > 0)) rc = keep_best_dm(c, L, pass, s);     // head0 is still this pass's plane here
     if (!rc && c->run.tol_mA > 0) rc = recycle_delta(c, c->ca, L, pass, c->max_passes, s);
   }
   if (rc) { c->xsplit_current = false; return rc; }
@@ -1489,7 +1491,8 @@ static int predict_end_refine(dmp_ctx* ctx, void* stream) {
   int rc;
   DMP_HIP(hipMemcpyAsync(c->best_ca_snapshot, c->best_ca, sizeof(float) * 3 * L,
                          hipMemcpyDeviceToDevice, s));
-  if (c->run_refine > 0 && (rc = refine_coords(c, c->best_ca, L, c->run_refine, s))) return rc;
+  // option "restrain_milli": these steps - and only these - also pull towards best_dm, the chosen pass's map
+  if (c->run_refine > 0 && (rc = refine_coords(c, c->best_ca, L, c->run_refine, s, c->run.restrain > 0))) return rc;
   c->end_refined = true;
   return record_unit(c, s);
 }
@@ -1571,7 +1574,7 @@ int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t ca
   else if (k == "conf_means") { src = ctx->conf_means; n = P; }
   else if (k == "ca_pass") { src = ctx->ca_pass; n = P * L * 3; }
   else if (k == "pass_delta") { src = ctx->pass_delta; n = ctx->run.tol_mA > 0 ? P : 0; }
-  else if (k == "best_dm") { src = ctx->best_dm; n = ctx->run.emit ? L * L : 0; }
+  else if (k == "best_dm") { src = ctx->best_dm; n = ctx->run.emit || ctx->run.restrain > 0 ? L * L : 0; }
   else if (k == "best_pass") { src = ctx->best_pass; n = 1; }
   else if (k == "best_ca") { src = ctx->best_ca_snapshot; n = L * 3; }
   else if (k == "best_ca_refined") { src = ctx->best_ca; n = L * 3; }

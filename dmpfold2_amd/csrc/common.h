@@ -10,8 +10,8 @@
 #include "../../include/dmpfold_hip.h"
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "score_map", "score_passes", "score_passes_chunk", "assign_ss"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0; };
+// "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000; };
 
 namespace dmp {
 
@@ -675,7 +675,8 @@ int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
 int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
 int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);
-int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s);
+// restrain: the final refinement with option "restrain_milli" on - the steps also pull towards c->best_dm (coords.hip)
+int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s, bool restrain = false);
 int ca_to_backbone(const float* d_ca, const float* d_logit, int L, float* d_coords,
                    float* d_conf_out, hipStream_t s);
 }  // namespace dmp

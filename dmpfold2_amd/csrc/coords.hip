@@ -387,7 +387,59 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 // ---------------------------------------------------------------------------------------
 // T threads share a residue j, each summing the steric term over a contiguous slice of the
 // partners i; the slices are then added in order, followed by the two bond terms.
-__global__ __launch_bounds__(1024) void refine_kernel(float* __restrict__ ca, int L, int steps) {
+//
+// Option "restrain_milli" (include/dmpfold_hip.h): the final refinement's steps also pull every pair with |i - j| >= 2
+// whose predicted distance t = best_dm[i][j] lies below the cutoff towards t, a_j -= k clamp(d - t, +-3) (x_j - x_i) / d.
+// The reference has no such term.  The thread that owns residue j reads best_dm[i * L + j] - the map is exactly symmetric
+// (keep_best_dm), and the threads of a wave own neighbouring j, so a wave reads one contiguous piece of row i per partner -
+// from L2 in every step: a workgroup's share of the map is Lg x L floats, read once per step - more than a CU's LDS from
+// about L = 800 on, so it is not staged there at any length (one placement, one set of bits); the map fits the XCD's L2 up to
+// L = 1000 and the Infinity Cache always.  One sqrt and one set of quotients per pair serve both terms.  A map entry that
+// is NaN fails `t < cut` and its pair is skipped.
+struct Restraint {
+  const float* dm;     // [L][L] best_dm
+  float k, cut;        // force constant, cutoff (A)
+};
+
+// The pair loop of both forms of the minimiser: the acceleration of residue j from the partners [i0, i1).  RESTRAIN =
+// false is the reference's steric term alone.
+template <bool RESTRAIN>
+__device__ __forceinline__ void refine_pairs(const float* cur, int L, int j, int i0, int i1, const Restraint& r,
+                                             float& ax, float& ay, float& az) {
+  const float xj = cur[3 * j], yj = cur[3 * j + 1], zj = cur[3 * j + 2];
+  for (int i = i0; i < i1; ++i) {
+    float t = 0.f;
+    if constexpr (RESTRAIN) t = r.dm[(int64_t)i * L + j];       // always in bounds: issued ahead of the sqrt and the divides
+    const float dx = xj - cur[3 * i], dy = yj - cur[3 * i + 1], dz = zj - cur[3 * i + 2];
+    const float d_raw = sqrtf((dx * dx + dy * dy) + dz * dz);
+    const float d = fminf(fmaxf(d_raw, 0.01f), 10.0f);
+    const float viol = (d < 3.0f) ? (3.0f - d) : 0.0f;
+    const float f = 100.0f * viol;
+    if constexpr (!RESTRAIN) {
+      ax += f * (dx / d);
+      ay += f * (dy / d);
+      az += f * (dz / d);
+    } else {
+      // One set of quotients serves both terms: dr = d wherever d < 10, and beyond that f is 0 and f * (dx / d) the same
+      // signed zero as f * (dx / dr) - the steric term keeps the bits of the plain loop.
+      const float dr = fmaxf(d_raw, 0.01f);
+      const float qx = dx / dr, qy = dy / dr, qz = dz / dr;
+      ax += f * qx;
+      ay += f * qy;
+      az += f * qz;
+      if ((i - j >= 2 || j - i >= 2) && t < r.cut) {            // `t < cut` is false for NaN
+        const float e = fminf(fmaxf(dr - t, -3.0f), 3.0f);
+        const float ke = r.k * e;
+        ax -= ke * qx;
+        ay -= ke * qy;
+        az -= ke * qz;
+      }
+    }
+  }
+}
+
+template <bool RESTRAIN>
+__global__ __launch_bounds__(1024) void refine_kernel(float* __restrict__ ca, int L, int steps, Restraint r) {
   extern __shared__ float sm[];          // 2 x 3L coordinates + T x 3L partial sums
   float* cur = sm;
   float* nxt = sm + 3 * L;
@@ -400,18 +452,8 @@ __global__ __launch_bounds__(1024) void refine_kernel(float* __restrict__ ca, in
     for (int idx = threadIdx.x; idx < T * L; idx += 1024) {
       const int j = idx % L, sub = idx / L;
       const int i0 = sub * chunk, i1 = (i0 + chunk < L) ? i0 + chunk : L;
-      const float xj = cur[3 * j], yj = cur[3 * j + 1], zj = cur[3 * j + 2];
       float ax = 0.f, ay = 0.f, az = 0.f;
-      for (int i = i0; i < i1; ++i) {
-        const float dx = xj - cur[3 * i], dy = yj - cur[3 * i + 1], dz = zj - cur[3 * i + 2];
-        float d = sqrtf((dx * dx + dy * dy) + dz * dz);
-        d = fminf(fmaxf(d, 0.01f), 10.0f);
-        const float viol = (d < 3.0f) ? (3.0f - d) : 0.0f;
-        const float f = 100.0f * viol;
-        ax += f * (dx / d);
-        ay += f * (dy / d);
-        az += f * (dz / d);
-      }
+      refine_pairs<RESTRAIN>(cur, L, j, i0, i1, r, ax, ay, az);
       part[(sub * L + j) * 3] = ax;
       part[(sub * L + j) * 3 + 1] = ay;
       part[(sub * L + j) * 3 + 2] = az;
@@ -467,6 +509,7 @@ struct RefineArgs {
   u64* gx;             // [2][3L] granules + [2] placement header, zeroed before the launch
   int* abort_flag;     // bit 2 is set if a hand-off ever times out
   int allow_local;     // 0: never the XCD-local publication
+  Restraint r;         // option "restrain_milli" (the RESTRAIN = true instantiation reads it)
 };
 
 __host__ __device__ inline int refine_slices(int L) {
@@ -476,6 +519,7 @@ __host__ __device__ inline int refine_slices(int L) {
 }
 
 // grid: 8 * RF_G blocks (only ids with id % 8 == xcd work)   block: RF_THREADS   dynamic LDS: see refine_coords
+template <bool RESTRAIN>
 __global__ __launch_bounds__(RF_THREADS) void refine_cluster_kernel(RefineArgs a) {
   extern __shared__ float sm[];          // 3L coordinates + T x 3 Lg partial sums
   __shared__ int sh_abort;
@@ -504,18 +548,8 @@ __global__ __launch_bounds__(RF_THREADS) void refine_cluster_kernel(RefineArgs a
     for (int idx = tid; idx < T * nj; idx += RF_THREADS) {
       const int jl = idx % nj, sub = idx / nj, j = j_lo + jl;
       const int i0 = sub * chunk, i1 = (i0 + chunk < L) ? i0 + chunk : L;
-      const float xj = cur[3 * j], yj = cur[3 * j + 1], zj = cur[3 * j + 2];
       float ax = 0.f, ay = 0.f, az = 0.f;
-      for (int i = i0; i < i1; ++i) {
-        const float dx = xj - cur[3 * i], dy = yj - cur[3 * i + 1], dz = zj - cur[3 * i + 2];
-        float d = sqrtf((dx * dx + dy * dy) + dz * dz);
-        d = fminf(fmaxf(d, 0.01f), 10.0f);
-        const float viol = (d < 3.0f) ? (3.0f - d) : 0.0f;
-        const float f = 100.0f * viol;
-        ax += f * (dx / d);
-        ay += f * (dy / d);
-        az += f * (dz / d);
-      }
+      refine_pairs<RESTRAIN>(cur, L, j, i0, i1, a.r, ax, ay, az);
       part[(sub * nj + jl) * 3] = ax;
       part[(sub * nj + jl) * 3 + 1] = ay;
       part[(sub * nj + jl) * 3 + 2] = az;
@@ -572,12 +606,20 @@ __global__ __launch_bounds__(RF_THREADS) void refine_cluster_kernel(RefineArgs a
   for (int i = tid; i < 3 * nj; i += RF_THREADS) a.ca[3 * j_lo + i] = cur[3 * j_lo + i];
 }
 
-int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s) {
+// `restrain`: the steps of the prediction's final refinement with option "restrain_milli" on - the map is c->best_dm, which
+// keep_best_dm filled in the pass tails, the constants are the prediction's own (c->run)
+int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s, bool restrain) {
   if (steps <= 0) return DMP_OK;
+  Restraint r{};
+  if (restrain) {
+    r.dm = c->best_dm;
+    r.k = (float)c->run.restrain / 1000.0f;
+    r.cut = (float)c->run.restrain_cut / 1000.0f;
+  }
   if ((c->refine_single && L <= 1280) || L < 2 * RF_G) {      // one workgroup: (6 + 3 T) L floats of LDS
     const int T = L >= 1024 ? 1 : (1024 / L > 8 ? 8 : 1024 / L);
-    hipLaunchKernelGGL(refine_kernel, dim3(1), dim3(1024), sizeof(float) * (6 + 3 * T) * L, s, d_ca, L,
-                       steps);
+    const auto kernel = restrain ? refine_kernel<true> : refine_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), sizeof(float) * (6 + 3 * T) * L, s, d_ca, L, steps, r);
     DMP_LAUNCH_CHECK();
     return DMP_OK;
   }
@@ -586,12 +628,13 @@ int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s) {
   a.gx = (u64*)c->refine_gx;
   a.abort_flag = c->seq_abort;
   a.allow_local = c->cluster_local;
+  a.r = r;
   const int Lg = (L + RF_G - 1) / RF_G;
   CoResident guard(c, s, false);                       // not beside a persistent vertical-GRU launch (common.h)
   if (guard.status()) return guard.status();
   DMP_HIP(hipMemsetAsync(c->refine_gx, 0, sizeof(u64) * (2 * 3 * L + 2), s));
-  hipLaunchKernelGGL(refine_cluster_kernel, dim3(8 * RF_G), dim3(RF_THREADS),
-                     sizeof(float) * (3 * L + 3 * refine_slices(L) * Lg), s, a);
+  const auto kernel = restrain ? refine_cluster_kernel<true> : refine_cluster_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(8 * RF_G), dim3(RF_THREADS), sizeof(float) * (3 * L + 3 * refine_slices(L) * Lg), s, a);
   DMP_LAUNCH_CHECK();
   return guard.done();
 }

@@ -22,7 +22,9 @@ Differences from the reference, all additive or forced by the environment:
   * `native` / `return_scores` / `dmpfold --native PDB`: the model is scored against a native structure on the GPU
     (option "score_native": TM-score, GDT, RMSD, lDDT-C-alpha; dmpfold2_amd/score.py has the host side);
   * `compare` / `return_alignment` / `dmpfold --compare PDB`: the model is aligned on the GPU with a structure of any length
-    and sequence (option "align_structure": a structural alignment, both TM-scores, the superposition).
+    and sequence (option "align_structure": a structural alignment, both TM-scores, the superposition);
+  * `restrain` / `return_restrain` / `dmpfold -r K`: the final minimisation also pulls the model towards the predicted
+    distance map (options "restrain_milli" / "restrain_cut_mA"; the reference's minimiser never sees the map).
 
 Plumbing: a public method gathers what its call asks for besides the prediction into one `Extras` in its first lines and
 everything below it carries that record; the caller's `d_conf` buffer is described by one `score.Layout`, made in `_stage`
@@ -159,6 +161,53 @@ def converge_to_mA(converge):
     return int(round(tol * 1000.0))
 
 
+def restrain_to_milli(restrain):
+    """The restraint force constant K of the Python / CLI boundary (float, None = off) as the C option's integer
+    ("restrain_milli", include/dmpfold_hip.h: K * 1000).  Negative, non-finite or > 100 raises ValueError."""
+    if restrain is None:
+        return 0
+    k = float(restrain)
+    if not 0.0 <= k <= 100.0:                   # (false for NaN)
+        raise ValueError(f"restrain must be a finite force constant in 0 .. 100, got {restrain!r}")
+    return int(round(k * 1000.0))
+
+
+def restrain_cutoff_to_mA(cutoff):
+    """The restraint cutoff (Angstrom, 0 .. 100) as the integer of option "restrain_cut_mA"; ValueError for the rest."""
+    a = float(cutoff)
+    if not 0.0 <= a <= 100.0:
+        raise ValueError(f"restrain_cutoff must be a finite distance in 0 .. 100 Angstrom, got {cutoff!r}")
+    return int(round(a * 1000.0))
+
+
+def restrain_options(restrain, cutoff=15.0):
+    """What a call's `restrain` / `restrain_cutoff` ask of the two options: None (`restrain` None: leave them as they
+    stand) or (restrain_milli, restrain_cut_mA).  A bad value raises ValueError - before any work."""
+    return None if restrain is None else (restrain_to_milli(restrain), restrain_cutoff_to_mA(cutoff))
+
+
+def restrain_report(k, cutoff, steps, distmap, map_rms, coords):
+    """The report of a restrained prediction (the JSON line `dmpfold --restrain` writes under the key "restrain"): k,
+    cutoff, steps and map_rms as given, and - formed here in NumPy from the returned map (L, L) and coordinates (L, 5, 3) -
+    restrained_pairs (pairs i < j, |i - j| >= 2, map below the cutoff), clashes (such pairs closer than 3.0 A in the final
+    trace) and bond_dev_max (max |d(i, i + 1) - 3.78|).  What to look at on a map no chain can realise: the restraints then
+    buy map agreement with clashes and stretched bonds."""
+    def host(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    ca = host(coords).reshape(-1, 5, 3)[:, 1].astype(np.float64)
+    L = ca.shape[0]
+    d = np.sqrt(((ca[:, None, :] - ca[None, :, :]) ** 2).sum(-1))
+    far = np.triu(np.ones((L, L), dtype=bool), 2)
+    pairs = None
+    if distmap is not None:
+        with np.errstate(invalid="ignore"):
+            pairs = int((host(distmap).astype(np.float32)[far] < np.float32(cutoff)).sum())
+    return {"k": float(k), "cutoff": float(cutoff), "steps": int(steps),
+            "map_rms": None if map_rms is None else float(map_rms), "restrained_pairs": pairs,
+            "clashes": int((d[far] < 3.0).sum()),
+            "bond_dev_max": float(np.abs(d[np.arange(L - 1), np.arange(1, L)] - 3.78).max())}
+
+
 def save_distmap_npy(path, distmap):
     """The (L, L) map as a float32 .npy file (what `dmpfold --distmap` and `dmpfold-batch --distmap` write)."""
     arr = distmap.detach().cpu().numpy() if isinstance(distmap, torch.Tensor) else np.asarray(distmap)
@@ -174,6 +223,37 @@ def _tolerance_arg(text):
     except ValueError:
         raise argparse.ArgumentTypeError(f"{text!r} is not a tolerance >= 0 (Angstrom)")
     return tol
+
+
+def _restrain_arg(text):
+    """argparse type of -r / --restrain: a float in 0 .. 100."""
+    try:
+        k = float(text)
+        restrain_to_milli(k)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a force constant in 0 .. 100")
+    return k
+
+
+def _cutoff_arg(text):
+    """argparse type of --restrain-cutoff: a float in 0 .. 100 (Angstrom)."""
+    try:
+        a = float(text)
+        restrain_cutoff_to_mA(a)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a cutoff in 0 .. 100 (Angstrom)")
+    return a
+
+
+def add_restrain_arguments(parser, *flags):
+    """--restrain K [--restrain-cutoff A] of `dmpfold` (with -r) and `dmpfold-batch`."""
+    parser.add_argument(*flags, "--restrain", type=_restrain_arg, default=None, required=False, metavar="K",
+                        help="restrain the final minimisation to the predicted distance map with force constant K (0 .. 100; the "
+                             "reference has no such term): pairs at least two residues apart whose predicted distance lies below "
+                             "the cutoff are pulled towards it; a report (map_rms, restrained pairs, clashes, largest bond "
+                             "deviation) goes to standard error as one JSON line; default: the reference's minimisation")
+    parser.add_argument("--restrain-cutoff", type=_cutoff_arg, default=15.0, required=False, metavar="A",
+                        help="with --restrain: only predicted distances below A Angstrom restrain (default 15)")
 
 
 # device-side fault bits (include/dmpfold_hip.h, DMP_FAULT_*)
@@ -395,11 +475,16 @@ class Engine:
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
                 minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                score_map=False, score_passes=False, ss=False):
+                score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
         `ss`: secondary structure is assigned to the final backbone on the GPU from its hydrogen bonds (option "assign_ss", set
         for this call only) and, with `native` given whole (no NaN row), to the native's backbone rebuilt from its trace; what
         the call returns does not change, the result is in `ss` (score.unpack_ss) and `ss_block`.
+        `restrain` (force constant K, 0 .. 100; None = the engine's "restrain_milli" option as it stands, 0 by default) and
+        `restrain_cutoff` (Angstrom): the `minsteps` steps of the FINAL refinement also pull every pair at least two residues
+        apart whose predicted distance lies below the cutoff towards it (options "restrain_milli" / "restrain_cut_mA", set for
+        this call only together with "emit_distmap" - the reference has no such term); what the call returns does not change
+        in shape, the report (map_rms, restrained pairs, clashes, largest bond deviation) is in `restrain`.
         `score_passes` (needs `native`): every recycling pass's trace - not only the one the best-of rule kept - is scored
         against the native on the GPU (option "score_passes", set for this call only together with "score_native"), with
         its mean confidence logit and its convergence delta beside the scores; what the call returns does not change, the
@@ -428,10 +513,24 @@ class Engine:
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
         call synchronises with the GPU once per pass."""
         extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
-        return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
+        return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
+                             restrain_options(restrain, restrain_cutoff))
 
     def _forget_last(self):
         self._last = _Last(Outputs(None, None), 0, None)
+        self._restrained = None       # (restrain_milli, restrain_cut_mA, steps, coords) of a restrained last prediction
+
+    @property
+    def restrain(self):
+        """The report of the last prediction if its final refinement was restrained (restrain_report: k, cutoff, steps,
+        map_rms, restrained_pairs, clashes, bond_dev_max), None otherwise.  Synchronises with the GPU."""
+        if self._restrained is None:
+            return None
+        milli, cut_mA, steps, coords = self._restrained
+        torch.cuda.synchronize(self.device)
+        out = self._last.out
+        return restrain_report(milli * 1e-3, cut_mA * 1e-3, steps, out.distmap, None if out.info is None else out.info[2].item(),
+                               coords)
 
     # The blocks of the last prediction on the GPU, views of the buffer handed to the library; None where the option was off.
     score_block = property(lambda self: self._last.out.score_block, doc='"score_native": 5L + 24 floats, or None')
@@ -495,25 +594,29 @@ class Engine:
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                       score_map=False, score_passes=False, ss=False):
+                       score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
         extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
-        return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras)
+        return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras, restrain_options(restrain, restrain_cutoff))
 
     def _upload(self, alnmat):
         with torch.cuda.device(self.device):
             return torch.from_numpy(np.ascontiguousarray(alnmat, dtype=np.uint8)).to(self.device)
 
-    def _predict(self, d_msa, template_ca, iterations, minsteps, converge, extras):
-        with self._call_options(converge, extras):
+    def _predict(self, d_msa, template_ca, iterations, minsteps, converge, extras, restrain=None):
+        with self._call_options(converge, extras, restrain):
             return self._run(d_msa, template_ca, iterations, minsteps, extras).public(extras.distmap, blocks=False)
 
     @contextlib.contextmanager
-    def _call_options(self, converge, extras):
+    def _call_options(self, converge, extras, restrain=None):
         """The options one call asks for - read when the prediction begins - set for its duration, then as they were.
         `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" / "align_structure" set by hand
-        stay set."""
+        stay set.  `restrain`: None (the two restraint options stay as they stand) or what restrain_options gave."""
         want = {} if converge is None else {"recycle_tol_mA": converge_to_mA(converge)}    # (raises before anything changes)
+        if restrain is not None:
+            want["restrain_milli"], want["restrain_cut_mA"] = restrain
+            if restrain[0] > 0 and not self.get_option("emit_distmap"):
+                want["emit_distmap"] = 1                  # (map_rms comes back with the map)
         if extras.score_map and extras.native is None and not self.get_option("score_native"):
             raise ValueError("score_map scores the distance map against a native structure: give `native`")
         if (extras.distmap or extras.score_map) and not self.get_option("emit_distmap"):
@@ -567,6 +670,9 @@ class Engine:
             self._forget_last()
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
             self._last = _Last(out._replace(coords=None), L, library if search else None)
+            milli = self.get_option("restrain_milli")
+            if milli > 0:
+                self._restrained = (milli, self.get_option("restrain_cut_mA"), int(max(minsteps, 0)), out.coords)
             if self._stream is not None:
                 # an engine with its own stream: order it after the producer of the inputs and tell the
                 # caching allocator that these blocks are in use there
@@ -608,31 +714,33 @@ class Engine:
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
                         minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                        score_map=False, score_passes=False, ss=False):
+                        score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
         which has float32's range, at about half the convolution rate."""
         extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
-        out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras)
+        out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
+                            restrain_options(restrain, restrain_cutoff))
         return out.public(extras.distmap, blocks=False)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
                                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                               score_map=False, score_passes=False, ss=False):
+                               score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
-        `score_map`, `score_passes`, `ss`: see `predict`; a repeat of the prediction returns the repeat's map, scores, alignment
-        and hits)."""
+        `score_map`, `score_passes`, `ss`, `restrain`: see `predict`; a repeat of the prediction returns the repeat's map,
+        scores, alignment and hits)."""
         extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
-        return self._checked(d_msa, template_ca, iterations, minsteps, converge, extras).public(extras.distmap, blocks=False)
+        out = self._checked(d_msa, template_ca, iterations, minsteps, converge, extras, restrain_options(restrain, restrain_cutoff))
+        return out.public(extras.distmap, blocks=False)
 
-    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, extras):
+    def _checked(self, d_msa, template_ca, iterations, minsteps, converge, extras, restrain=None):
         """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry the call's
         extras along."""
         def run():
             return self._run(d_msa, template_ca, iterations, minsteps, extras), self.sync_faults()
 
-        with self._call_options(converge, extras):
+        with self._call_options(converge, extras, restrain):
             out, bits = run()
             self.last_fallback = False
             if bits & FAULT_VGRU_HANDOFF and self.get_option("vgru_persistent"):
@@ -704,7 +812,8 @@ class Pipeline:
     the repeat of faulted targets."""
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
-                 distmap=False, score=False, align=False, search=None, score_map=False, score_passes=False, ss=False):
+                 distmap=False, score=False, align=False, search=None, score_map=False, score_passes=False, ss=False,
+                 restrain=None):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -723,7 +832,9 @@ class Pipeline:
         `score` on); its pass block (16 + 8R floats, R = min(iterations + 1, 128) of that submission,
         score.unpack_pass_scores) is then the last element of all.
         `ss`: every target's backbone gets its secondary structure assigned (`set_ss`); its SS block (32 + 8L floats,
-        score.unpack_ss) then comes behind even the pass block."""
+        score.unpack_ss) then comes behind even the pass block.
+        `restrain` (force constant K, None = off): every target's final refinement is restrained to its predicted distance
+        map (`set_restrain`, which turns `distmap` on; cutoff 15 A - `set_restrain` takes another)."""
         self.lib = _lib.load()
         self._search = None
         self.device = _resolve_device(device)
@@ -761,6 +872,8 @@ class Pipeline:
             self.set_score_passes(True)
         if ss:
             self.set_ss(True)
+        if restrain is not None:
+            self.set_restrain(restrain)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -772,6 +885,17 @@ class Pipeline:
     def set_converge(self, converge):
         """Convergence tolerance (Angstrom; None or 0 = fixed depth) of every target submitted from now on; idle pipeline only."""
         self.set_option("recycle_tol_mA", converge_to_mA(converge))
+
+    def set_restrain(self, restrain, cutoff=15.0):
+        """Options "restrain_milli" / "restrain_cut_mA" on every engine: the final refinement of targets submitted from now on
+        is restrained to their predicted distance map with force constant `restrain` (None or 0 = off) below `cutoff`
+        Angstrom.  Turning it on turns "emit_distmap" on, so that map_rms comes back; turning it off leaves that as it is.
+        Idle pipeline only."""
+        milli, cut_mA = restrain_to_milli(restrain), restrain_cutoff_to_mA(cutoff)     # (raise before anything changes)
+        if milli > 0:
+            self.set_distmap(True)
+        self.set_option("restrain_cut_mA", cut_mA)
+        self.set_option("restrain_milli", milli)
 
     def set_distmap(self, on):
         """Option "emit_distmap" on every engine: targets submitted from now on return their distance map; idle pipeline only."""
@@ -1126,7 +1250,7 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
                   return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
                   compare_chain=None, return_alignment=False, search=None, return_hits=False, return_map_scores=False,
-                  return_pass_scores=False, return_ss=False):
+                  return_pass_scores=False, return_ss=False, restrain=None, restrain_cutoff=15.0, return_restrain=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -1147,26 +1271,34 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     `return_pass_scores` (addition; needs `native`): every recycling pass is scored against the native (option
     "score_passes") and the dict of score.unpack_pass_scores is appended behind those.
     `return_ss` (addition): secondary structure is assigned to the final backbone on the GPU (option "assign_ss"; with a whole
-    `native` also to the native's rebuilt backbone, with Q3 / Q8) and the dict of score.unpack_ss is appended last of all."""
+    `native` also to the native's rebuilt backbone, with Q3 / Q8) and the dict of score.unpack_ss is appended behind those.
+    `restrain` (addition; force constant K in 0 .. 100, None = off) and `restrain_cutoff` (Angstrom): the final refinement also
+    pulls the pairs whose predicted distance lies below the cutoff towards it (Engine.predict; the reference has no such
+    term).  With `return_restrain` the dict of restrain_report is appended last of all (None without a `restrain` > 0)."""
     r = _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                       compare_chain, search, distmap=return_distmap, scores=return_scores, alignment=return_alignment,
-                      hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores, ss=return_ss)
+                      hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores, ss=return_ss,
+                      restrain=restrain, restrain_cutoff=restrain_cutoff)
     return ((r.coords, r.confs) + ((r.alnmat,) if return_alnmat else ()) + ((r.distmap,) if return_distmap else ())
             + ((r.scores,) if return_scores else ()) + ((r.alignment,) if return_alignment else ())
             + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ())
-            + ((r.pass_scores,) if return_pass_scores else ()) + ((r.ss,) if return_ss else ()))
+            + ((r.pass_scores,) if return_pass_scores else ()) + ((r.ss,) if return_ss else ())
+            + ((r.restrain,) if return_restrain else ()))
 
 
 # What `aln_to_coords` computes, by name: each of distmap, scores, alignment, hits and map_scores None unless it was wanted
 # (and, for scores, alignment and hits, unless its input - native, compare, search - was given).
-Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores ss", defaults=(None, None))
+# `restrain`: the report of a restrained final refinement, None without one.
+Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores ss restrain",
+                        defaults=(None, None, None))
 
 
 def _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                   compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
-                  pass_scores=False, ss=False):
+                  pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0):
     """`aln_to_coords` -> Prediction; the seven flags are its return_distmap, return_scores, return_alignment, return_hits,
-    return_map_scores, return_pass_scores and return_ss."""
+    return_map_scores, return_pass_scores and return_ss; `restrain`, `restrain_cutoff` are its own."""
+    restrain_options(restrain, restrain_cutoff)                              # (a bad value raises before any work)
     if map_scores and native is None:
         raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
     if pass_scores and native is None:
@@ -1198,8 +1330,9 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
                                   native=native, structure=compare, library=search, score_map=bool(map_scores),
-                                  score_passes=bool(pass_scores), ss=bool(ss))
+                                  score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain, restrain_cutoff=restrain_cutoff)
         return Prediction(out[0], out[1], alnmat, out[2] if distmap else None, ss=eng.ss if ss else None,
+                          restrain=eng.restrain if restrain is not None else None,
                           map_scores=eng.map_scores if map_scores else None,
                           pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
@@ -1229,7 +1362,7 @@ def pdb_text(coords, confs, alnmat):
 
 def dmpfold_parser():
     """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --score-passes, --compare,
-    --search and --ss."""
+    --search, --ss and -r / --restrain."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -1288,6 +1421,7 @@ def dmpfold_parser():
                              "output is unchanged")
     parser.add_argument("--ss-file", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --ss to FILE instead of standard error")
+    add_restrain_arguments(parser, "-r")
     return parser
 
 
@@ -1302,7 +1436,8 @@ def run_dmpfold(argv=None):
     r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
                       args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
                       distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
-                      hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes, ss=args.ss)
+                      hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes, ss=args.ss,
+                      restrain=args.restrain, restrain_cutoff=args.restrain_cutoff)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1323,4 +1458,6 @@ def run_dmpfold(argv=None):
         json_line(js, args.scores)
     if args.ss:
         json_line(_score.ss_json(r.ss), args.ss_file)
+    if r.restrain is not None:
+        json_line({"restrain": r.restrain}, None)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

@@ -413,6 +413,25 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * was.  Measured cost of dmp_predict_end with the option on (profiles/ss.txt; a collapsed model with 2.6 million hydrogen
  * bonds at L = 2048): 0.11 ms at L = 96, 0.29 ms at 300, 1.29 ms at 1000, 2.78 ms at 2048; with the native's leg 0.14,
  * 0.31, 1.35 and 2.86 ms - above "score_native" alone (1.10 ms at L = 2048) from L = 300 on.
+ * "restrain_milli" (0 .. 100000, default 0 = off; any other value: DMP_ERR_ARG) and "restrain_cut_mA" (0 .. 100000, default
+ * 15000): restrain the prediction's FINAL refinement to the predicted distance map.  THE REFERENCE HAS NO SUCH TERM: its
+ * minimiser (network.py:106-137) knows steric repulsion and the bond and never sees the map.  Both are read when a prediction
+ * begins and held for it; k = (float)restrain_milli / 1000.0f, cut = (float)restrain_cut_mA / 1000.0f (Angstrom).  With
+ * "restrain_milli" 0 nothing changes by a bit.  With it > 0 the pass tails keep the chosen pass's map exactly as they do for
+ * "emit_distmap" (t_ij below; exactly symmetric), and each of the refine_steps steps that dmp_predict_end applies to the best
+ * trace gains a third term.  Float32, every operation in the order written, as the minimiser's own: for residue j and
+ * partner i, dx = x_j - x_i (dy, dz likewise), d_raw = sqrtf((dx dx + dy dy) + dz dz); the steric term is the reference's,
+ * from clamp(d_raw, 0.01, 10); then, if |i - j| >= 2 and t = t_ij < cut (a NaN fails the test and the pair is skipped),
+ *   dr = fmaxf(d_raw, 0.01f), e = fminf(fmaxf(dr - t, -3.0f), 3.0f), a_j -= (k e) (dx / dr)   per component.
+ * The partners are summed in the slices and the order of the plain minimiser, the two bond terms, the clamp of the total
+ * acceleration to +-100 and the step 0.001 are the reference's.  Nothing else changes: the refinement of pass 0's trace that
+ * seeds pass 1, recycling, the best-of choice, "recycle_tol_mA", the recorded ca_pass traces and the layout of d_conf are
+ * what they are without the option; the score, SS, align and search blocks see the restrained trace because they read the
+ * final coordinates.  refine_steps = 0: nothing runs.  "restrain_cut_mA" = 0: no pair qualifies and the result is the plain
+ * refinement's, bit for bit.  No scratch, no allocation; one more read of the map per step (csrc/coords.hip).  Measured
+ * cost of dmp_predict_end with refine_steps = 100, option on against off (profiles/restrain.txt): +0.02 ms at L = 96,
+ * +0.08 ms at 300, +1.04 ms at 1000, +3.93 ms at 2048.  dmp_debug_fetch("best_dm") answers L x L floats when this option
+ * or "emit_distmap" kept the map.
  * "align_structure" (0 or 1, default 0; any other value: DMP_ERR_ARG): align the model with a structure of any length and
  * sequence on the device - a structural alignment found by superposition and dynamic programming in turn.  Read when a
  * prediction begins and held for it.  With it 0 nothing is launched, nothing extra is read or written, and every output is
@@ -842,7 +861,7 @@ int dmp_sync_faults(dmp_ctx* ctx, void* stream, int* h_bits);
  * "mat1d", "conf_means" (P floats), "ca_pass" (P x L x 3), "best_ca" (L x 3, before the final
  * refinement), "inv_cov" (21L x 21L), "mds" (L x 8) and "gram" (L x L) of the last pass, "pass_delta" (P floats: d_p of
  * option "recycle_tol_mA", +inf for pass 0; nothing - 0 floats - if the prediction ran with the option off), "best_dm" (L x L: the
- * chosen pass's distance map of option "emit_distmap"; 0 floats if the prediction ran with the option off) and "best_pass"
+ * chosen pass's distance map of option "emit_distmap" or "restrain_milli"; 0 floats if the prediction ran with both off) and "best_pass"
  * (1 float: the pass the best-of rule kept; always available).  Returns the number of floats written or a negative status. */
 int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t capacity,
                         void* stream);
