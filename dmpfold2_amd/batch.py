@@ -149,7 +149,7 @@ RESTRAIN_COUNTS = ("steps", "restrained_pairs", "clashes")      # the integers o
 
 
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
-                 hits=None, hits_top=10, map_scores=None, pass_scores=None, ss=None, restrain=None):
+                 hits=None, hits_top=10, map_scores=None, pass_scores=None, ss=None, restrain=None, exposure=None):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
@@ -170,7 +170,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     ss_p_acc, ss_p_don (int32 (L,)) and, with a whole native, ss8_native, ss_q3 and ss_q8; pdb / ca get <stem>.ss.json (the
     line `dmpfold --ss` prints).  With `restrain` (the dict of predict.restrain_report, --restrain): npz gains the scalars
     restrain_k, restrain_cutoff, restrain_steps, restrain_map_rms, restrain_restrained_pairs, restrain_clashes and
-    restrain_bond_dev_max; pdb / ca get <stem>.restrain.json (the line `dmpfold --restrain` prints)."""
+    restrain_bond_dev_max; pdb / ca get <stem>.restrain.json (the line `dmpfold --restrain` prints).  With `exposure` (the dict of
+    score.unpack_exposure, --exposure): npz gains exp_n (int32 (L, 5): exposed points of N, CA, C, O, CB, -1 for a glycine's CB),
+    exp_hse_up, exp_hse_down, exp_cn10 (int32 (L,)) and exp_area (float64 (L,): the residue's accessible area in square
+    Angstrom); pdb / ca get <stem>.exposure.json (the line `dmpfold --exposure` prints)."""
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -205,6 +208,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             if ss["has_native"]:
                 extra.update({"ss8_native": np.asarray(ss["ss8_native"], dtype=np.str_), "ss_q3": np.float32(ss["q3"]),
                               "ss_q8": np.float32(ss["q8"])})
+        if exposure is not None:
+            extra.update({"exp_n": np.asarray(exposure["n"], dtype=np.int32), "exp_area": np.asarray(exposure["area_res"], dtype=np.float64)})
+            extra.update({"exp_" + k: np.asarray(exposure[k], dtype=np.int32) for k in ("hse_up", "hse_down", "cn10")})
         if restrain is not None:
             extra.update({"restrain_" + k: (np.int32 if k in RESTRAIN_COUNTS else np.float32)(v) for k, v in restrain.items()})
         if alignment is not None:
@@ -234,6 +240,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     if ss is not None:
         with open(stem + ".ss.json", "w") as fh:
             fh.write(json.dumps(_score.ss_json(ss)) + "\n")
+    if exposure is not None:
+        with open(stem + ".exposure.json", "w") as fh:
+            fh.write(json.dumps({"exposure": _score.exposure_json(exposure)}) + "\n")
     if restrain is not None:
         with open(stem + ".restrain.json", "w") as fh:
             fh.write(json.dumps({"restrain": restrain}) + "\n")
@@ -292,7 +301,7 @@ def cost_order(targets, iterations):
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
               converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10,
-              score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
+              score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
     """Predict this rank's targets; returns (number done, seconds, [output paths]).
     `natives`: a directory of native structures, <stem>.pdb for the target <stem>.aln / .a3m: such a target is scored on
     the GPU (Pipeline.set_score) and its scores are written with it (write_result); a target without a file is predicted
@@ -304,6 +313,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     `ss`: every target's backbone gets its secondary structure assigned on the GPU (Pipeline.set_ss; with `natives`, a
     target whose native covers every column also gets the native's and Q3 / Q8) and it is written with the target
     (write_result); `stats_out` then receives "ss": {stem: the dict of score.ss_json}.
+    `exposure`: every target's backbone gets its solvent exposure counted on the GPU (Pipeline.set_exposure; with `natives`, a
+    target whose native covers every column also gets the native's) and it is written with the target (write_result);
+    `stats_out` then receives "exposure": {stem: the dict of score.exposure_json}.
     `structures`: a directory of structures of any length and sequence, <stem>.pdb for the target <stem>.aln / .a3m: such a
     target's model is aligned with the structure's first chain on the GPU (Pipeline.set_align) and the alignment is written
     with it (write_result); a target without a file is predicted without one.  `stats_out` then receives "alignments":
@@ -394,6 +406,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.set_score_passes(True)
             if ss:
                 pipe.set_ss(True)
+            if exposure:
+                pipe.set_exposure(True)
             if restraining:
                 pipe.set_restrain(restrain, restrain_cutoff)
             if structures:
@@ -435,12 +449,13 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     aligned, all_alignments = set(), {}
     all_hits = {}
     all_ss = {}
+    all_exposure = {}
     all_restrain = {}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
         out = Outputs.of(public, distmap=distmap or score_map or restraining, score=bool(natives), align=bool(structures), search=library is not None,
-                         score_map=score_map, passes=score_passes, ss=ss)
+                         score_map=score_map, passes=score_passes, ss=ss, exposure=exposure)
         aln_path, alnmat, _ = parsed.pop(t)
         sc = ms = ps = None
         if out.score_block is not None and t in scored:
@@ -467,12 +482,16 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         if out.ss_block is not None:
             sec = _score.unpack_ss(out.ss_block, alnmat.shape[1])
             all_ss[os.path.splitext(os.path.basename(aln_path))[0]] = _score.ss_json(sec)
+        exposed = None
+        if out.exposure_block is not None:
+            exposed = _score.unpack_exposure(out.exposure_block, alnmat.shape[1], seq=alnmat[0])
+            all_exposure[os.path.splitext(os.path.basename(aln_path))[0]] = _score.exposure_json(exposed)
         rep = None
         if restraining:
             rep = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap, float(out.info[2]), out.coords)
             all_restrain[os.path.splitext(os.path.basename(aln_path))[0]] = rep
         outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap if distmap else None,
-                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps, sec, rep))
+                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps, sec, rep, exposed))
 
     def finish(item):
         t, public = item
@@ -591,6 +610,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             stats_out["hits"] = all_hits
         if stats_out is not None and ss:
             stats_out["ss"] = all_ss
+        if stats_out is not None and exposure:
+            stats_out["exposure"] = all_exposure
         if stats_out is not None and restraining:
             stats_out["restrain"] = all_restrain
         pipe.close()
@@ -650,6 +671,11 @@ def batch_parser():
                          "gains every target's eight-state string and helix / strand / coil fractions with their means and "
                          "medians (with --natives also mean Q3 / Q8 over the targets whose native covers every column); npz "
                          "gains ss8, ss_bp and the energy arrays, pdb / ca write <stem>.ss.json")
+    ap.add_argument("--exposure", action="store_true",
+                    help="count the solvent exposure of every target's backbone on the GPU (a Shrake-Rupley surface of N, CA, C, O "
+                         "and CB, half-sphere exposure and CB contact number per residue); the summary gains every target's total "
+                         "area, burial ratio and mean counts with their means and medians; npz gains exp_n, exp_hse_up, "
+                         "exp_hse_down, exp_cn10 and exp_area, pdb / ca write <stem>.exposure.json")
     add_restrain_arguments(ap)
     return ap
 
@@ -704,6 +730,23 @@ def ss_summary(ss):
         vals = [v[name] for v in ss.values() if v.get(name) is not None]
         if vals:
             out["mean_" + name] = float(np.mean(vals))
+    return out
+
+
+EXPOSURE_SUMMARY = ("area", "mean_hse_up", "mean_hse_down", "mean_cn10", "mean_cb_exposed", "cb_hydrophobic", "cb_other", "burial_ratio")
+
+
+def exposure_summary(exposure):
+    """{stem: the dict of score.exposure_json} -> the summary's part for --exposure: per target the total area, the means of
+    the three per-residue counts and of cb_exposed, the burial figures (and the three correlations where it had a whole native),
+    and mean and median of each over the targets that have it."""
+    keys = EXPOSURE_SUMMARY + ("r_area", "r_hse_up", "r_cn10")
+    out = {"exposure_targets": len(exposure), "exposure": {stem: {k: v[k] for k in keys if k in v} for stem, v in exposure.items()}}
+    for name in keys:
+        vals = [v[name] for v in exposure.values() if v.get(name) is not None]
+        if vals or name in EXPOSURE_SUMMARY:
+            out["mean_exposure_" + name] = float(np.mean(vals)) if vals else None
+            out["median_exposure_" + name] = float(np.median(vals)) if vals else None
     return out
 
 
@@ -774,7 +817,7 @@ def main(argv=None):
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
                                   structures=args.structures, library=args.library, search_top=args.search_top,
                                   score_map=args.score_map, score_passes=args.score_passes, ss=args.ss,
-                                  restrain=args.restrain, restrain_cutoff=args.restrain_cutoff)
+                                  restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -792,6 +835,8 @@ def main(argv=None):
         job_store.set(f"dmpfold_batch_hits/{rank}", json.dumps(passes.get("hits", {})))
     if args.ss and world > 1:
         job_store.set(f"dmpfold_batch_ss/{rank}", json.dumps(passes.get("ss", {})))
+    if args.exposure and world > 1:
+        job_store.set(f"dmpfold_batch_exposure/{rank}", json.dumps(passes.get("exposure", {})))
     if args.restrain and world > 1:
         job_store.set(f"dmpfold_batch_restrain/{rank}", json.dumps(passes.get("restrain", {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
@@ -825,6 +870,11 @@ def main(argv=None):
             for r in range(1, world):
                 sec.update(json.loads(job_store.get(f"dmpfold_batch_ss/{r}").decode()))
             summary.update(ss_summary(dict(sorted(sec.items()))))
+        if args.exposure:
+            exp = dict(passes.get("exposure", {}))
+            for r in range(1, world):
+                exp.update(json.loads(job_store.get(f"dmpfold_batch_exposure/{r}").decode()))
+            summary.update(exposure_summary(dict(sorted(exp.items()))))
         if args.restrain:
             reports = dict(passes.get("restrain", {}))
             for r in range(1, world):

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libdmpfold_hip.so")
 SOURCES = ["api.hip", "pipeline.hip", "gemm.hip", "msa.hip", "dca.hip", "gru.hip", "vgru.hip", "vgru_f32.hip", "vgru_x3.hip", "trunk.hip", "train.hip", "mds.hip",
-           "coords.hip", "score.hip", "mapscore.hip", "align.hip", "ss.hip"]
+           "coords.hip", "score.hip", "mapscore.hip", "align.hip", "ss.hip", "exposure.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # coords.hip: no SLP vectoriser = no packed-f32 instructions.  The vectoriser turns the cross products of the
 # backbone kernel into v_pk_mul_f32 ... op_sel:[0,1] op_sel_hi:[1,0], which returns 0 in lanes 48..63 when
@@ -28,8 +28,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # mapscore.hip: float64 sums and integer keys, but the native contact test is float32 (three products, two sums per pair):
 # the flag keeps packed-f32 forms out of it.
 # ss.hip: float64 energies and bit look-ups; the flag keeps packed forms out of it as well.
+# exposure.hip: float64 point tests and integer counts; likewise.
 PER_FILE_FLAGS = {"coords.hip": ["-fno-slp-vectorize"], "gru.hip": ["-fno-slp-vectorize"], "score.hip": ["-fno-slp-vectorize"],
-                  "align.hip": ["-fno-slp-vectorize"], "mapscore.hip": ["-fno-slp-vectorize"], "ss.hip": ["-fno-slp-vectorize"]}
+                  "align.hip": ["-fno-slp-vectorize"], "mapscore.hip": ["-fno-slp-vectorize"], "ss.hip": ["-fno-slp-vectorize"],
+                  "exposure.hip": ["-fno-slp-vectorize"]}
 
 
 def per_file_flags(src: str) -> list:
@@ -55,7 +57,7 @@ def _stale(target, deps):
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "conv_split.h", "conv_bf16.h", "conv_f16.h", "vgru.h", "score_common.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "conv_split.h", "conv_bf16.h", "conv_f16.h", "vgru.h", "score_common.h", "exposure_points.h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "dmpfold_hip.h"))
     extra = os.environ.get("DMP_EXTRA_HIPCC_FLAGS", "").split()      # tuning experiments (-DVG_CH=1 ...)
     lib = os.environ.get("DMP_LIB_OUT", LIB)

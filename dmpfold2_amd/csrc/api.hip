@@ -458,12 +458,15 @@ static int search_reserve(dmp_ctx* c) {
     need = std::max<int64_t>(need, (int64_t)search_chunk_entries(L, mm, 0) * search_slot(L, mm).total);
   return scratch_reserve(c, c->search_ws, SEARCH_HEAD_BYTES + need, SEARCH_HEAD_BYTES, "search scratch");
 }
-// Options "score_passes" and "assign_ss": reserved when the option first becomes 1 on a context (score.hip, ss.hip have the layouts).
+// Options "score_passes", "assign_ss" and "exposure": reserved when the option first becomes 1 on a context (score.hip, ss.hip, exposure.hip have the layouts).
 static int passes_reserve(dmp_ctx* c) {
   return c->opt.passes ? scratch_reserve(c, c->pass_ws, score_passes_need(c->max_L), "pass-score scratch") : DMP_OK;
 }
 static int ss_reserve(dmp_ctx* c) {
   return c->opt.ss ? scratch_reserve(c, c->ss_ws, assign_ss_need(c->max_L), "secondary-structure scratch") : DMP_OK;
+}
+static int exposure_reserve(dmp_ctx* c) {
+  return c->opt.exposure ? scratch_reserve(c, c->exposure_ws, exposure_need(c->max_L), "exposure scratch") : DMP_OK;
 }
 
 // ---- the options --------------------------------------------------------------------------------------------------------
@@ -559,6 +562,8 @@ static const Option OPTIONS[] = {
     {"score_passes", TAIL(passes), 0, 1, 0, "score_passes must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, passes_reserve},       // needs "score_native" on
     {"score_passes_chunk", TAIL(passes_chunk), 0, INT32_MAX, 0, "score_passes_chunk must be >= 0, got %d"},    // tests only: passes per chunk, 0 = what the budget gives
     {"assign_ss", TAIL(ss), 0, 1, 0, "assign_ss must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, ss_reserve},
+    {"exposure", TAIL(exposure), 0, 1, 0, "exposure must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, exposure_reserve},
+    {"exposure_chunk", TAIL(exposure_chunk), 0, INT32_MAX, 0, "exposure_chunk must be >= 0, got %d"},          // tests only: list entries per chunk, 0 = what the LDS holds
     {"restrain_milli", TAIL(restrain), 0, 100000, 0, "restrain_milli must be 0 .. 100000, got %d"},               // force constant k * 1000; 0 = off
     {"restrain_cut_mA", TAIL(restrain_cut), 0, 100000, 0, "restrain_cut_mA must be 0 .. 100000, got %d"},         // milli-Angstrom
     {"align_structure", TAIL(align), 0, 1, 0, "align_structure must be 0 or 1, got %d"},
@@ -761,7 +766,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->bwd_ws) (void)hipFree(c->bwd_ws);
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
-  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->ss_ws})
+  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->ss_ws, &c->exposure_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1230,6 +1235,7 @@ static int issue_front_end_unit(dmp_ctx* c, hipStream_t s) {
     used = side;
     rc = msa_weights(c, d_msa, N, L, c->w, side);
     if (!rc && c->run.ss) rc = ss_capture_pro(c, d_msa, L, side);       // option "assign_ss": the first row's proline flags
+    if (!rc && c->run.exposure) rc = exposure_capture_gly(c, d_msa, L, side);   // option "exposure": the first row's glycine flags
     if (!rc && N > 1) rc = cov_build(c, d_msa, c->w, N, L, c->cov, side, true);
   } else if (u <= c->fe_inv + c->fe_vgru) {
     // alternate GRU chunk / inverse chunk while both kinds remain
@@ -1523,6 +1529,8 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (pass_R && (rc = score_passes(c, L, pass_R, std::min(c->passes_done, c->max_passes), d_conf + lay.pass.off, s))) return rc;
   // option "assign_ss": the SS block behind that, from d_coords and - with "score_native" - the score block's native trace (ss.hip)
   if (c->run.ss && (rc = assign_ss(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.ss.off, s))) return rc;
+  // option "exposure": the exposure block behind that, from the same two inputs (exposure.hip)
+  if (c->run.exposure && (rc = exposure(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.exposure.off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)
@@ -1586,6 +1594,12 @@ int64_t dmp_debug_fetch(dmp_ctx* ctx, const char* name, float* d_dst, int64_t ca
     const int layer = k == "vgru_h1";
     src = ctx->hT[layer][ctx->vg_maxN & 1];
     n = (int64_t)WIDTH * ctx->vg_ntiles * 32;
+  }
+  else if (k == "exposure_points") return exposure_points_fetch(d_dst, capacity, STREAM);   // option "exposure": the sphere points as the device holds them
+  else if (k == "exposure_native_backbone") {          // the native's backbone as the last "exposure" + "score_native" prediction rebuilt it
+    const bool on = ctx->exposure_ws.p && ctx->run.exposure && ctx->run.score;
+    src = on ? exposure_native_backbone(ctx) : nullptr;
+    n = on ? 15 * L : 0;
   }
   else { set_error("unknown debug tensor %s", name); return DMP_ERR_ARG; }
   if (n > capacity) { set_error("capacity %lld too small for %s (%lld)", (long long)capacity, name, (long long)n); return DMP_ERR_ARG; }

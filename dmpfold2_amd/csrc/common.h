@@ -10,8 +10,8 @@
 #include "../../include/dmpfold_hip.h"
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000; };
+// "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0; };
 
 namespace dmp {
 
@@ -84,11 +84,15 @@ __host__ __device__ inline int pass_floats(int R) { return PASS_HEADER + PASS_RO
 //   and the align block.
 constexpr int SS_HEADER = 32;
 __host__ __device__ inline int ss_floats(int L) { return SS_HEADER + 8 * L; }
+//   | with "exposure": the exposure block = EXPOSURE_HEADER floats | sixteen per-residue arrays [L] (eight of the model, eight
+//   of the native), all of it out, between the SS block and the align block.
+constexpr int EXPOSURE_HEADER = 32;
+__host__ __device__ inline int exposure_floats(int L) { return EXPOSURE_HEADER + 16 * L; }
 // The blocks in buffer order.  A block states where it begins, how many floats in front are the caller's input and where what
 // the library writes ends; a block whose option is off is empty (off = end).  `passes`: the rows R of the pass block, 0 =
 // none.  The align block's trailing input, whose length only the caller knows, lies behind `total`.
 struct ConfBlock { int64_t off, in, end; };                              // [off, off + in) in, [off + in, end) out
-struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, align; int64_t total; };
+struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, align; int64_t total; };
 __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int passes) {
   ConfLayout lay;
   int64_t at = 0;
@@ -104,6 +108,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
   lay.smap = block(behind > at ? behind - at : 0, o.smap ? mapscore_floats(L) : 0);
   lay.pass = block(behind > at ? behind - at : 0, passes ? pass_floats(passes) : 0);
   lay.ss = block(0, o.ss ? ss_floats(L) : 0);
+  lay.exposure = block(0, o.exposure ? exposure_floats(L) : 0);
   lay.align = block(1, o.align ? align_layout(L).in : 0);
   lay.total = at;
   return lay;
@@ -111,7 +116,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
 // true for the floats a prediction writes: what becomes NaN when it latched a fault (api.hip)
 __host__ __device__ inline bool conf_is_out(const ConfLayout& lay, int64_t i) {
   auto out = [i](const ConfBlock& b) { return i >= b.off + b.in && i < b.end; };
-  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.align);
+  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.align);
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -375,6 +380,8 @@ struct dmp_ctx {
   dmp::Scratch pass_ws;            // "score_passes": the tickets | the delta's partial sums, the slots of a chunk of passes (score.hip: pass_slot)
   dmp::Scratch ss_ws;              // "assign_ss": the counters and the ticket | the proline flags, per entity the hydrogens, the donor
                                    // flags and the two bit matrices, the native's backbone (ss.hip: ss_scratch)
+  dmp::Scratch exposure_ws;        // "exposure": the counters, the ticket and has_native | the glycine flags, the native's backbone
+                                   // (exposure.hip: exposure_scratch)
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
@@ -655,7 +662,7 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 // what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
 ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
-    assign_ss_need(int max_L);
+    assign_ss_need(int max_L), exposure_need(int max_L);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
@@ -673,6 +680,12 @@ int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine wor
 // block from d_coords and, with d_native (the score block's trace) not null, from the native's rebuilt backbone
 int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
 int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
+// option "exposure" (exposure.hip): the glycine flags of the alignment's first row (front end), then at the prediction's end the
+// exposure block from d_coords and, with d_native (the score block's trace) not null, from the native's rebuilt backbone
+int exposure_capture_gly(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
+int exposure(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
+int64_t exposure_points_fetch(float* d_dst, int64_t capacity, hipStream_t s);   // the sphere points as the device holds them -> floats written
+const float* exposure_native_backbone(const dmp_ctx* c);             // the native's rebuilt backbone in the scratch
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
 int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);
 // restrain: the final refinement with option "restrain_milli" on - the steps also pull towards c->best_dm (coords.hip)

@@ -317,14 +317,15 @@ class Extras(_score._Beside, namedtuple("Extras", "distmap native structure libr
                                         defaults=(False, None, None, None, False, False))):
     """What one call asks for besides the prediction itself, as `Engine.predict` documents each: `distmap` (return the
     map), `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map),
-    `score_passes` (score every recycling pass) and, a keyword carried beside the tuple's six fields, `ss` (assign secondary
-    structure).
+    `score_passes` (score every recycling pass) and, keywords carried beside the tuple's six fields, `ss` (assign secondary
+    structure) and `exposure` (solvent exposure of the backbone).
     The public methods build one in their first lines; everything below them takes and carries the record."""
-    _beside = ("ss", False)
+    _beside = (("ss", False), ("exposure", False))
     ss = False
+    exposure = False
 
-    def __new__(cls, *args, ss=False, **kw):
-        return super().__new__(cls, *args, **kw)._with(bool(ss))
+    def __new__(cls, *args, ss=False, exposure=False, **kw):
+        return super().__new__(cls, *args, **kw)._with(bool(ss), bool(exposure))
 
 
 # The options that decide the layout of a `d_conf` buffer, in the order of a row of `agree_options`.
@@ -333,16 +334,16 @@ LAYOUT_OPTIONS = ("emit_distmap", "score_native", "score_map", "align_structure"
 # The layout options as one prediction runs with them: `emit` .. `align` bools, `search` the K of "search_structures";
 # `alloc`: size the buffer as if "emit_distmap" were on (a pipeline whose engines disagree on that option alone);
 # `max_L`: the context's, for the rule of B0; `passes`: the rows R of the pass block of "score_passes" (None = off), which
-# follow the prediction's own depth; `ss`: option "assign_ss" on.
-Flags = namedtuple("Flags", "emit alloc score score_map align search max_L passes ss", defaults=(None, None, False))
+# follow the prediction's own depth; `ss`: option "assign_ss" on; `exposure`: option "exposure" on.
+Flags = namedtuple("Flags", "emit alloc score score_map align search max_L passes ss exposure", defaults=(None, None, False, False))
 
 
-def agree_ss(values):
+def agree_ss(values, option="assign_ss", setter="set_ss"):
     """The `ss` of a prediction's Flags from option "assign_ss" as every engine that may run it holds it: they must agree -
-    RuntimeError if not."""
+    RuntimeError if not.  (`option`, `setter`: the same rule for another option that owns one block, "exposure".)"""
     values = [bool(v) for v in values]
     if any(v != values[0] for v in values):
-        raise RuntimeError("the engines must agree on \"assign_ss\" (the blocks behind the SS block move with it); use set_ss")
+        raise RuntimeError(f"the engines must agree on \"{option}\" (the blocks behind its block move with it); use {setter}")
     return values[0]
 
 
@@ -392,7 +393,7 @@ def _stage(device, L, template_ca, flags, extras):
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, passes=flags.passes, ss=flags.ss)
+                 flags.max_L, passes=flags.passes, ss=flags.ss, exposure=flags.exposure)
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
     if library is not None:
@@ -475,11 +476,15 @@ class Engine:
 
     def predict(self, alnmat, template_ca=None, iterations=default_iterations,
                 minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
+                score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
         """codes (N, L) uint8 -> (coords (L,5,3), confs (L,)) float32 tensors on the GPU.
         `ss`: secondary structure is assigned to the final backbone on the GPU from its hydrogen bonds (option "assign_ss", set
         for this call only) and, with `native` given whole (no NaN row), to the native's backbone rebuilt from its trace; what
         the call returns does not change, the result is in `ss` (score.unpack_ss) and `ss_block`.
+        `exposure`: the solvent exposure of the final backbone is counted on the GPU - exposed sphere points per atom, half-sphere
+        exposure and CB contact number per residue (option "exposure", set for this call only) - and, with `native` given whole,
+        that of the native's rebuilt backbone; what the call returns does not change, the result is in `exposure`
+        (score.unpack_exposure) and `exposure_block`.
         `restrain` (force constant K, 0 .. 100; None = the engine's "restrain_milli" option as it stands, 0 by default) and
         `restrain_cutoff` (Angstrom): the `minsteps` steps of the FINAL refinement also pull every pair at least two residues
         apart whose predicted distance lies below the cutoff towards it (options "restrain_milli" / "restrain_cut_mA", set for
@@ -512,7 +517,7 @@ class Engine:
         after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
         call synchronises with the GPU once per pass."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
         return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
                              restrain_options(restrain, restrain_cutoff))
 
@@ -539,6 +544,13 @@ class Engine:
     align_block = property(lambda self: self._last.out.align_block, doc='"align_structure": 25 + 2L + 3m floats, or None')
     search_block = property(lambda self: self._last.out.search_block, doc='"search_structures": 26K + 2LK + 3M floats, or None')
     ss_block = property(lambda self: self._last.out.ss_block, doc='"assign_ss": 32 + 8L floats, or None')
+    exposure_block = property(lambda self: self._last.out.exposure_block, doc='"exposure": 32 + 16L floats, or None')
+
+    @property
+    def exposure(self):
+        """The solvent exposure of the last prediction as score.unpack_exposure gives it, None if it ran without option
+        "exposure".  Synchronises with the GPU."""
+        return self._unpacked("exposure_block", _score.unpack_exposure)
 
     @property
     def ss(self):
@@ -594,9 +606,9 @@ class Engine:
 
     def predict_device(self, d_msa, template_ca=None, iterations=default_iterations,
                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                       score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
+                       score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
         return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras, restrain_options(restrain, restrain_cutoff))
 
     def _upload(self, alnmat):
@@ -631,6 +643,8 @@ class Engine:
             want["score_passes"] = 1                      # (behind "score_native", which the library asks for at begin)
         if extras.ss and not self.get_option("assign_ss"):
             want["assign_ss"] = 1
+        if extras.exposure and not self.get_option("exposure"):
+            want["exposure"] = 1
         if extras.structure is not None and not self.get_option("align_structure"):
             _score.as_structure(extras.structure)                                          # (a bad shape raises before anything changes)
             want["align_structure"] = 1
@@ -665,7 +679,8 @@ class Engine:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         flags = Flags(bool(emit), bool(emit), bool(score), bool(smap and emit and score), bool(align), search, self.max_L,
-                      agree_passes([self.get_option("score_passes")], score, iterations), bool(self.get_option("assign_ss")))
+                      agree_passes([self.get_option("score_passes")], score, iterations), bool(self.get_option("assign_ss")),
+                      bool(self.get_option("exposure")))
         with torch.cuda.device(self.device):
             self._forget_last()
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
@@ -714,23 +729,23 @@ class Engine:
 
     def predict_checked(self, alnmat, template_ca=None, iterations=default_iterations,
                         minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                        score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
+                        score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
         """`predict`, synchronised and verified.  The default convolution multiplies f16 pieces of its
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
         which has float32's range, at about half the convolution rate."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
         out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
                             restrain_options(restrain, restrain_cutoff))
         return out.public(extras.distmap, blocks=False)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
                                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
-                               score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0):
+                               score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
         `score_map`, `score_passes`, `ss`, `restrain`: see `predict`; a repeat of the prediction returns the repeat's map,
         scores, alignment and hits)."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss)
+        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
         out = self._checked(d_msa, template_ca, iterations, minsteps, converge, extras, restrain_options(restrain, restrain_cutoff))
         return out.public(extras.distmap, blocks=False)
 
@@ -813,7 +828,7 @@ class Pipeline:
 
     def __init__(self, device, max_L, max_N, state_dict, streams=2, precision=None, torch_streams=False, converge=None,
                  distmap=False, score=False, align=False, search=None, score_map=False, score_passes=False, ss=False,
-                 restrain=None):
+                 restrain=None, exposure=False):
         """`torch_streams`: the engines run on PyTorch pool streams handed to the library (dmp_pipeline_create_on) instead of
         the library's own - for a host that wants every stream to be one its allocator knows.
         `converge` (Angstrom, None = off): every target stops recycling once its trace has converged to that tolerance
@@ -833,6 +848,8 @@ class Pipeline:
         score.unpack_pass_scores) is then the last element of all.
         `ss`: every target's backbone gets its secondary structure assigned (`set_ss`); its SS block (32 + 8L floats,
         score.unpack_ss) then comes behind even the pass block.
+        `exposure`: every target's backbone gets its solvent exposure counted (`set_exposure`); its exposure block (32 + 16L
+        floats, score.unpack_exposure) then comes behind even the SS block.
         `restrain` (force constant K, None = off): every target's final refinement is restrained to its predicted distance
         map (`set_restrain`, which turns `distmap` on; cutoff 15 A - `set_restrain` takes another)."""
         self.lib = _lib.load()
@@ -872,6 +889,8 @@ class Pipeline:
             self.set_score_passes(True)
         if ss:
             self.set_ss(True)
+        if exposure:
+            self.set_exposure(True)
         if restrain is not None:
             self.set_restrain(restrain)
         self._jobs = {}               # ticket -> _Job: kept alive
@@ -928,6 +947,11 @@ class Pipeline:
         (and, with `set_score` on and a whole native given to `submit`, of the native's); idle pipeline only."""
         self.set_option("assign_ss", 1 if on else 0)
 
+    def set_exposure(self, on):
+        """Option "exposure" on every engine: targets submitted from now on get the solvent exposure of their backbone counted
+        (and, with `set_score` on and a whole native given to `submit`, of the native's); idle pipeline only."""
+        self.set_option("exposure", 1 if on else 0)
+
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
@@ -979,7 +1003,8 @@ class Pipeline:
             flags = agree_options([e.get_option(name) for name in LAYOUT_OPTIONS] for e in self.engines)
             flags = flags._replace(max_L=self.engines[0].max_L,
                                    passes=agree_passes([e.get_option("score_passes") for e in self.engines], flags.score, iterations),
-                                   ss=agree_ss(e.get_option("assign_ss") for e in self.engines))
+                                   ss=agree_ss(e.get_option("assign_ss") for e in self.engines),
+                                   exposure=agree_ss((e.get_option("exposure") for e in self.engines), "exposure", "set_exposure"))
             if flags.align and structure is not None and _score.as_structure(structure).shape[0] > flags.max_L:
                 raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {flags.max_L}")
             if flags.search and (self._search is None or len(self._search) != flags.search):
@@ -1135,7 +1160,8 @@ class Pipeline:
                     if res.align_block is not None and extras.structure is None:
                         extras = extras._replace(structure=np.zeros((0, 3), dtype=np.float32))
                     extras = extras._replace(distmap=emit, score_map=res.map_block is not None,
-                                             score_passes=res.pass_block is not None, ss=res.ss_block is not None)
+                                             score_passes=res.pass_block is not None, ss=res.ss_block is not None,
+                                             exposure=res.exposure_block is not None)
                     try:
                         rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, extras)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
@@ -1250,7 +1276,8 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
                   minsteps=default_minsteps, weights_file=None, return_alnmat=False, converge=None,
                   return_distmap=False, native=None, return_scores=False, native_chain=None, compare=None,
                   compare_chain=None, return_alignment=False, search=None, return_hits=False, return_map_scores=False,
-                  return_pass_scores=False, return_ss=False, restrain=None, restrain_cutoff=15.0, return_restrain=False):
+                  return_pass_scores=False, return_ss=False, restrain=None, restrain_cutoff=15.0, return_restrain=False,
+                  return_exposure=False):
     """Alignment file -> (coords (L,5,3) [N, CA, C, O, CB], confs (L,)) on `device`,
     plus the uint8 alignment matrix when `return_alnmat` is set (predict.py:74-158).
     `converge` (addition; Angstrom, None = off): stop recycling once a pass changes the seed distance map by no more
@@ -1274,30 +1301,33 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     `native` also to the native's rebuilt backbone, with Q3 / Q8) and the dict of score.unpack_ss is appended behind those.
     `restrain` (addition; force constant K in 0 .. 100, None = off) and `restrain_cutoff` (Angstrom): the final refinement also
     pulls the pairs whose predicted distance lies below the cutoff towards it (Engine.predict; the reference has no such
-    term).  With `return_restrain` the dict of restrain_report is appended last of all (None without a `restrain` > 0)."""
+    term).  With `return_restrain` the dict of restrain_report is appended behind those (None without a `restrain` > 0).
+    `return_exposure` (addition): the solvent exposure of the final backbone is counted on the GPU (option "exposure"; with a
+    whole `native` also that of the native's rebuilt backbone) and the dict of score.unpack_exposure, made with the query's
+    sequence, is appended last of all."""
     r = _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                       compare_chain, search, distmap=return_distmap, scores=return_scores, alignment=return_alignment,
                       hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores, ss=return_ss,
-                      restrain=restrain, restrain_cutoff=restrain_cutoff)
+                      restrain=restrain, restrain_cutoff=restrain_cutoff, exposure=return_exposure)
     return ((r.coords, r.confs) + ((r.alnmat,) if return_alnmat else ()) + ((r.distmap,) if return_distmap else ())
             + ((r.scores,) if return_scores else ()) + ((r.alignment,) if return_alignment else ())
             + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ())
             + ((r.pass_scores,) if return_pass_scores else ()) + ((r.ss,) if return_ss else ())
-            + ((r.restrain,) if return_restrain else ()))
+            + ((r.restrain,) if return_restrain else ()) + ((r.exposure,) if return_exposure else ()))
 
 
 # What `aln_to_coords` computes, by name: each of distmap, scores, alignment, hits and map_scores None unless it was wanted
 # (and, for scores, alignment and hits, unless its input - native, compare, search - was given).
-# `restrain`: the report of a restrained final refinement, None without one.
-Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores ss restrain",
-                        defaults=(None, None, None))
+# `restrain`: the report of a restrained final refinement, None without one; `exposure`: the dict of score.unpack_exposure.
+Prediction = namedtuple("Prediction", "coords confs alnmat distmap scores alignment hits map_scores pass_scores ss restrain exposure",
+                        defaults=(None, None, None, None))
 
 
 def _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
                   compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
-                  pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0):
-    """`aln_to_coords` -> Prediction; the seven flags are its return_distmap, return_scores, return_alignment, return_hits,
-    return_map_scores, return_pass_scores and return_ss; `restrain`, `restrain_cutoff` are its own."""
+                  pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
+    """`aln_to_coords` -> Prediction; the eight flags are its return_distmap, return_scores, return_alignment, return_hits,
+    return_map_scores, return_pass_scores, return_ss and return_exposure; `restrain`, `restrain_cutoff` are its own."""
     restrain_options(restrain, restrain_cutoff)                              # (a bad value raises before any work)
     if map_scores and native is None:
         raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
@@ -1330,8 +1360,13 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
                                   native=native, structure=compare, library=search, score_map=bool(map_scores),
-                                  score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain, restrain_cutoff=restrain_cutoff)
-        return Prediction(out[0], out[1], alnmat, out[2] if distmap else None, ss=eng.ss if ss else None,
+                                  score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain, restrain_cutoff=restrain_cutoff,
+                                  exposure=bool(exposure))
+        exposed = None
+        if exposure:
+            torch.cuda.synchronize(eng.device)
+            exposed = _score.unpack_exposure(eng.exposure_block, length, seq=alnmat[0])
+        return Prediction(out[0], out[1], alnmat, out[2] if distmap else None, ss=eng.ss if ss else None, exposure=exposed,
                           restrain=eng.restrain if restrain is not None else None,
                           map_scores=eng.map_scores if map_scores else None,
                           pass_scores=eng.pass_scores if pass_scores else None,
@@ -1362,7 +1397,7 @@ def pdb_text(coords, confs, alnmat):
 
 def dmpfold_parser():
     """The reference's flags (predict.py:160-208), -c / --converge, --distmap, --native, --score-map, --score-passes, --compare,
-    --search, --ss and -r / --restrain."""
+    --search, --ss, --exposure and -r / --restrain."""
     parser = argparse.ArgumentParser(description=(
         "DMPfold2 end-to-end structure prediction on AMD MI355X (HIP engine). "
         "Prints a PDB format model file."))
@@ -1421,6 +1456,14 @@ def dmpfold_parser():
                              "output is unchanged")
     parser.add_argument("--ss-file", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --ss to FILE instead of standard error")
+    parser.add_argument("--exposure", action="store_true", default=False,
+                        help="count the solvent exposure of the model's backbone on the GPU (a Shrake-Rupley surface of N, CA, C, O "
+                             "and CB with 256 points per atom, half-sphere exposure and CB contact number per residue, the burial of "
+                             "the hydrophobic positions; with --native given whole also the native's and their correlations); the "
+                             "result goes to standard error as one JSON line under the key \"exposure\", the model on standard "
+                             "output is unchanged")
+    parser.add_argument("--exposure-file", type=str, default=None, required=False, metavar="FILE",
+                        help="write the JSON line of --exposure to FILE instead of standard error")
     add_restrain_arguments(parser, "-r")
     return parser
 
@@ -1437,7 +1480,7 @@ def run_dmpfold(argv=None):
                       args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
                       distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
                       hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes, ss=args.ss,
-                      restrain=args.restrain, restrain_cutoff=args.restrain_cutoff)
+                      restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1458,6 +1501,8 @@ def run_dmpfold(argv=None):
         json_line(js, args.scores)
     if args.ss:
         json_line(_score.ss_json(r.ss), args.ss_file)
+    if args.exposure:
+        json_line({"exposure": _score.exposure_json(r.exposure)}, args.exposure_file)
     if r.restrain is not None:
         json_line({"restrain": r.restrain}, None)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

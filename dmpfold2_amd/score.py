@@ -93,24 +93,40 @@ def ss_floats(L):
     return SS_HEADER + SS_ARRAYS * int(L)
 
 
-class _Beside:
-    """For a namedtuple subclass that carries ONE more, keyword-only value beside the tuple (`_beside` = (name, default)).
-    The tuple itself - its fields, its length, its positional order, which callers rely on - stays as it is; `_replace`,
-    ==, hash and repr know the value, and an instance made without it holds the default."""
-    _beside = None
+EXPOSURE_HEADER = 32                 # floats in front of the per-residue arrays of the exposure block
+EXPOSURE_ARRAYS = 16                 # per-residue arrays of L floats behind it: eight of the model, eight of the native
+EXPOSURE_POINTS = 256                # sphere points per atom
+EXPOSURE_ATOMS = ("N", "CA", "C", "O", "CB")
+EXPOSURE_RADII = (3.05, 3.27, 3.16, 2.80, 3.20)     # atom radius + the 1.4 A probe (Kabsch & Sander 1983)
+HYDROPHOBIC = "AVILMFWC"
 
-    def _with(self, value):
-        setattr(self, self._beside[0], value)
+
+def exposure_floats(L):
+    """Floats of the exposure block (option "exposure") of a prediction of length L."""
+    return EXPOSURE_HEADER + EXPOSURE_ARRAYS * int(L)
+
+
+class _Beside:
+    """For a namedtuple subclass that carries more, keyword-only values beside the tuple (`_beside` = ((name, default), ...)).
+    The tuple itself - its fields, its length, its positional order, which callers rely on - stays as it is; `_replace`,
+    ==, hash and repr know the values, and an instance made without one holds its default."""
+    _beside = ()
+
+    def _with(self, *values, **named):
+        """The values in the order of `_beside` (those not given stay as they are), or by name."""
+        for (name, _), value in zip(self._beside, values):
+            setattr(self, name, value)
+        for name, value in named.items():
+            setattr(self, name, value)
         return self
 
     def _replace(self, **kw):
-        name = self._beside[0]
-        value = kw.pop(name, getattr(self, name))
-        return super()._replace(**kw)._with(value)
+        values = [kw.pop(name, getattr(self, name)) for name, _ in self._beside]
+        return super()._replace(**kw)._with(*values)
 
     def __eq__(self, other):
-        name, default = self._beside
-        return tuple.__eq__(self, other) is True and _same(getattr(self, name), getattr(other, name, default))
+        return tuple.__eq__(self, other) is True and all(_same(getattr(self, name), getattr(other, name, default))
+                                                          for name, default in self._beside)
 
     def __ne__(self, other):
         return not self == other
@@ -119,7 +135,7 @@ class _Beside:
         return tuple.__hash__(self)
 
     def __repr__(self):
-        return super().__repr__()[:-1] + f", {self._beside[0]}={getattr(self, self._beside[0])!r})"
+        return super().__repr__()[:-1] + "".join(f", {name}={getattr(self, name)!r}" for name, _ in self._beside) + ")"
 
 
 def _same(a, b):
@@ -133,29 +149,31 @@ class Layout(_Beside, namedtuple("Layout", "L distmap score score_map align_m se
     `score_map`: options "emit_distmap", "score_native", "score_map" on; `align_m`: the m the align block holds (None =
     "align_structure" off); `search`: (K, M) of option "search_structures" (None = off); `max_L`: the context's, for the rule
     of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0 counts); `passes` (keyword): the rows R
-    of the pass block of option "score_passes" (None = off); `ss` (keyword, carried beside the tuple's eight fields, default
-    off): option "assign_ss" on.  Every offset is stated once, each from the one in front of it:
+    of the pass block of option "score_passes" (None = off); `ss` and `exposure` (keywords, carried beside the tuple's eight
+    fields, default off): options "assign_ss" and "exposure" on.  Every offset is stated once, each from the one in front of it:
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
-      (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | align_off (A0): align block
-      (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
+      (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | exposure_off (X0): exposure block (32 + 16L) |
+      align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
 
     and `total` is the floats the buffer must hold."""
-    _beside = ("ss", False)
+    _beside = (("ss", False), ("exposure", False))
     ss = False
+    exposure = False
 
     def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None, *,
-                ss=False):
+                ss=False, exposure=False):
         return super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
-                               None if passes is None else int(passes))._with(bool(ss))
+                               None if passes is None else int(passes))._with(bool(ss), bool(exposure))
 
     info_off = property(lambda s: s.L + (s.L * s.L if s.distmap else 0))
     score_off = property(lambda s: s.info_off + (3 if s.distmap else 0))                                    # S0
     mapscore_off = property(lambda s: s.score_off + (score_floats(s.L) if s.score else 0))                  # M0
     pass_off = property(lambda s: s.mapscore_off + (mapscore_floats(s.L) if s.score_map else 0))            # T0
     ss_off = property(lambda s: s.pass_off + (pass_floats(s.passes) if s.passes is not None else 0))        # U0
-    align_off = property(lambda s: s.ss_off + (ss_floats(s.L) if s.ss else 0))                              # A0
+    exposure_off = property(lambda s: s.ss_off + (ss_floats(s.L) if s.ss else 0))                           # X0
+    align_off = property(lambda s: s.exposure_off + (exposure_floats(s.L) if s.exposure else 0))            # A0
     # the end of the align block as its writer allocated it (an align_m that is no number raises ValueError) ...
     align_end = property(lambda s: s.align_off + (align_floats(s.L, s.align_m) if s.align_m is not None else 0))
     # ... and B0, its end as the library counts it: 3m of it only if m is an integer in [3, max_L]
@@ -178,11 +196,15 @@ class Layout(_Beside, namedtuple("Layout", "L distmap score score_map align_m se
                        part(self.align_m is not None, self.align_off, self.align_end),
                        part(self.search is not None, self.search_off, self.search_end),
                        part(self.score_map, self.mapscore_off, self.pass_off),
-                       part(self.passes is not None, self.pass_off, self.ss_off))._with(self.ss_block(buf))
+                       part(self.passes is not None, self.pass_off, self.ss_off))._with(self.ss_block(buf), self.exposure_block(buf))
 
     def ss_block(self, buf):
         """The SS block of a `d_conf` buffer as a view (32 + 8L floats), None with `ss` off."""
-        return buf[self.ss_off:self.align_off] if self.ss else None
+        return buf[self.ss_off:self.exposure_off] if self.ss else None
+
+    def exposure_block(self, buf):
+        """The exposure block of a `d_conf` buffer as a view (32 + 16L floats), None with `exposure` off."""
+        return buf[self.exposure_off:self.align_off] if self.exposure else None
 
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
@@ -219,30 +241,33 @@ class Outputs(_Beside, namedtuple("Outputs", "coords confs distmap info score_bl
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
     score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
     (26K + 2LK + 3M,), with "score_map" map_block (64 + L,), with "score_passes" pass_block (16 + 8R,) - None for what is
-    absent.  With "assign_ss" the SS block (32 + 8L,) is `ss_block`, carried beside the tuple's nine fields (None otherwise)."""
-    _beside = ("ss_block", None)
+    absent.  With "assign_ss" the SS block (32 + 8L,) is `ss_block` and with "exposure" the exposure block (32 + 16L,) is `exposure_block`, both carried beside the tuple's nine
+    fields (None otherwise)."""
+    _beside = (("ss_block", None), ("exposure_block", None))
     ss_block = None
+    exposure_block = None
 
-    def __new__(cls, *args, ss_block=None, **kw):
-        return super().__new__(cls, *args, **kw)._with(ss_block)
+    def __new__(cls, *args, ss_block=None, exposure_block=None, **kw):
+        return super().__new__(cls, *args, **kw)._with(ss_block, exposure_block)
 
     @classmethod
-    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False, ss=False):
+    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False, ss=False, exposure=False):
         """The inverse of `public` for a caller that knows which options were on."""
         rest = iter(public)          # (the fields stand in the tuple's order: the pass block is the last of both)
         out = cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map, passes)))
-        return out._with(next(rest) if ss else None)
+        return out._with(next(rest) if ss else None, next(rest) if exposure else None)
 
-    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True, ss=True):
+    def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True, ss=True,
+               exposure=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
         block, the align block, the search block and - though they lie behind the score block in the buffer - the map-score
-        block, the pass block and, last of all, the SS block, each if present and wanted.  `blocks=False`: none of the six
-        blocks, whatever else is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
+        block, the pass block, the SS block and, last of all, the exposure block, each if present and wanted.  `blocks=False`:
+        none of the seven blocks, whatever else is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
         if not blocks:
-            score = align = search = score_map = passes = ss = False
+            score = align = search = score_map = passes = ss = exposure = False
         groups = ((distmap, (self.distmap, self.info)), (score, (self.score_block,)), (align, (self.align_block,)),
                   (search, (self.search_block,)), (score_map, (self.map_block,)), (passes, (self.pass_block,)),
-                  (ss, (self.ss_block,)))
+                  (ss, (self.ss_block,)), (exposure, (self.exposure_block,)))
         return (self.coords, self.confs) + tuple(x for want, group in groups if want and group[0] is not None for x in group)
 
 
@@ -587,6 +612,120 @@ def ss_json(ss, arrays=False):
             out[k] = [_num(v) for v in ss[k]]
         for k in ("p_acc", "p_don", "bp1", "bp2"):
             out[k] = [int(v) for v in ss[k]]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# option "exposure" (include/dmpfold_hip.h): solvent exposure of the final backbone on the GPU - a Shrake-Rupley surface of
+# the N, CA, C, O and CB atoms (256 points per atom, 1.4 A probe), the half-sphere exposure of every residue (Hamelryck
+# 2005, the CB variant) and a CB contact number.  Shrake & Rupley's KIND of surface on a model WITHOUT SIDE CHAINS: not
+# DSSP's ACC, no relative accessibility, and nobody has compared the figures with another program's.  The library returns
+# integer counts; areas, fractions and correlations are formed here in float64.
+# ---------------------------------------------------------------------------------------------------------------------
+def exposure_points():
+    """The 256 unit vectors of the sphere lattice, float32 (256, 3): a golden spiral formed in float64 and rounded once.
+    csrc/exposure_points.h (tools/make_exposure_points.py) holds these bits."""
+    k = np.arange(EXPOSURE_POINTS, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / float(EXPOSURE_POINTS)
+    r = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32)
+
+
+def _count(a):
+    """Counts the library wrote as floats -> int64, NaN as 0."""
+    return np.where(a == a, a, 0.0).astype(np.int64)
+
+
+def _pearson(x, y):
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    ok = (x == x) & (y == y)
+    if ok.sum() < 2:
+        return float("nan")
+    x, y = x[ok] - x[ok].mean(), y[ok] - y[ok].mean()
+    d = np.sqrt((x * x).sum() * (y * y).sum())
+    return float((x * y).sum() / d) if d > 0 else float("nan")
+
+
+def _mean(v):
+    v = np.asarray(v, dtype=np.float64)
+    v = v[v == v]
+    return float(v.mean()) if v.size else float("nan")
+
+
+def _exposure_leg(header, arr, L):
+    """One entity's seven header floats and eight arrays -> its part of `unpack_exposure`."""
+    n = _index(arr[:5].T)                                                    # (L, 5); -1: a glycine's CB (and NaN)
+    radii = np.asarray(EXPOSURE_RADII, dtype=np.float64)
+    area = 4.0 * np.pi * radii * radii * np.maximum(n, 0).astype(np.float64) / float(EXPOSURE_POINTS)
+    cb = np.where(n[:, 4] >= 0, n[:, 4] / float(EXPOSURE_POINTS), np.nan)
+    out = {"atoms": _whole(header[0]), "sums": [_whole(v) for v in header[1:6]], "buried_atoms": _whole(header[6]),
+           "n": n, "hse_up": _count(arr[5]), "hse_down": _count(arr[6]), "cn10": _count(arr[7]),
+           "area_atom": area, "area_res": area.sum(axis=1), "area": float(area.sum()), "cb_exposed": cb}
+    for name in ("hse_up", "hse_down", "cn10"):
+        out["mean_" + name] = float(out[name].mean()) if L else float("nan")
+    return out
+
+
+def unpack_exposure(block, L, seq=None):
+    """An exposure block (32 + 16L floats, array or tensor) -> dict: points (256), atoms (the atoms present), sums (exposed
+    points of the N, CA, C, O, CB atoms), buried_atoms (atoms without an exposed point), n (L, 5) int - exposed points per atom,
+    -1 for a glycine's CB -, hse_up, hse_down, cn10 (L,) int, and formed here in float64: area_atom (L, 5) = 4 pi R^2 n / 256,
+    area_res (L,), area, cb_exposed (L,) = n_CB / 256 (NaN for glycine), mean_hse_up, mean_hse_down, mean_cn10; has_native,
+    and with a native the same under "native" plus r_area, r_hse_up, r_cn10 (Pearson r between model and native per residue).
+    `seq` (the query as a string or as residue codes): also cb_hydrophobic, cb_other (the mean cb_exposed of A V I L M F W C and
+    of the other non-glycine residues) and burial_ratio, their quotient.  A block the library answered with NaN (a latched
+    fault) gives zero counts and -1 in n."""
+    L = int(L)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != exposure_floats(L):
+        raise ValueError(f"an exposure block of length {L} has {exposure_floats(L)} floats, got shape {tuple(b.shape)}")
+    arr = b[EXPOSURE_HEADER:].reshape(EXPOSURE_ARRAYS, L)
+    out = {"points": _whole(b[0])}
+    out.update(_exposure_leg(b[1:8], arr[:8], L))
+    out["has_native"] = bool(_whole(b[8]))
+    if out["has_native"]:
+        nat = _exposure_leg(b[9:16], arr[8:], L)
+        out["native"] = nat
+        out["r_area"] = _pearson(out["area_res"], nat["area_res"])
+        out["r_hse_up"] = _pearson(out["hse_up"], nat["hse_up"])
+        out["r_cn10"] = _pearson(out["cn10"], nat["cn10"])
+    if seq is not None:
+        letters = seq if isinstance(seq, str) else "".join(AA1[int(c)] if 0 <= int(c) < 20 else "X" for c in np.asarray(seq).reshape(-1)[:L])
+        if len(letters) != L:
+            raise ValueError(f"the sequence has {len(letters)} residues, the block {L}")
+        hyd = np.asarray([c in HYDROPHOBIC for c in letters], dtype=bool)
+        for leg in [out] + ([out["native"]] if out["has_native"] else []):
+            present = leg["cb_exposed"] == leg["cb_exposed"]
+            leg["cb_hydrophobic"], leg["cb_other"] = _mean(leg["cb_exposed"][hyd & present]), _mean(leg["cb_exposed"][~hyd & present])
+            leg["burial_ratio"] = _ratio(leg["cb_hydrophobic"], leg["cb_other"]) if leg["cb_other"] == leg["cb_other"] else float("nan")
+    return out
+
+
+EXPOSURE_SCALARS = ("area", "mean_hse_up", "mean_hse_down", "mean_cn10", "cb_hydrophobic", "cb_other", "burial_ratio")
+
+
+def exposure_json(ex, arrays=False):
+    """`unpack_exposure` as a JSON-ready dict (what `dmpfold --exposure` prints and `dmpfold-batch --exposure` writes): the
+    counts, the total area, the means and, with a native, the same under "native" and the three correlations; with `arrays`
+    also n, hse_up, hse_down, cn10 and area_res as lists.  NaN becomes None."""
+    def leg(d):
+        js = {"atoms": int(d["atoms"]), "sums": [int(v) for v in d["sums"]], "buried_atoms": int(d["buried_atoms"])}
+        js.update({k: _num(d[k]) for k in EXPOSURE_SCALARS if k in d})
+        js["mean_cb_exposed"] = _num(_mean(d["cb_exposed"]))
+        if arrays:
+            js["n"] = [[int(v) for v in row] for row in d["n"]]
+            for k in ("hse_up", "hse_down", "cn10"):
+                js[k] = [int(v) for v in d[k]]
+            js["area_res"] = [_num(v) for v in d["area_res"]]
+        return js
+    out = {"points": int(ex["points"])}
+    out.update(leg(ex))
+    out["has_native"] = bool(ex["has_native"])
+    if ex["has_native"]:
+        out["native"] = leg(ex["native"])
+        for k in ("r_area", "r_hse_up", "r_cn10"):
+            out[k] = _num(ex[k])
     return out
 
 

@@ -413,6 +413,71 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * was.  Measured cost of dmp_predict_end with the option on (profiles/ss.txt; a collapsed model with 2.6 million hydrogen
  * bonds at L = 2048): 0.11 ms at L = 96, 0.29 ms at 300, 1.29 ms at 1000, 2.78 ms at 2048; with the native's leg 0.14,
  * 0.31, 1.35 and 2.86 ms - above "score_native" alone (1.10 ms at L = 2048) from L = 300 on.
+ * "exposure" (0 or 1, default 0; any other value: DMP_ERR_ARG): count the solvent exposure of the final backbone that
+ * dmp_predict_end has just written into d_coords, on the device - is the model compact, are its hydrophobic positions buried,
+ * does each residue see as many neighbours as a folded chain's would - without a native, a partner structure or a second
+ * program.  Three measures: a Shrake-Rupley accessible surface (for every backbone atom the number of exposed sphere
+ * points), the half-sphere exposure of every residue (Hamelryck, Proteins 59, 38, 2005, the CB variant) and a CB contact
+ * number.  Read when a prediction begins and held for it.  With it 0 nothing is launched, read, written or allocated, and
+ * every offset and output is bit for bit what it is without the option.  With it 1 THE d_conf ARGUMENT MUST HOLD X0 + 32 +
+ * 16L FLOATS, X0 = THE END OF THE SS BLOCK (U0 + 32 + 8L with "assign_ss", U0 without): there sits the EXPOSURE BLOCK, all
+ * of it outputs, and A0 and B0 below move behind it (search_prep's rule for B0 starts from the moved A0).  Everything else
+ * in the buffer does not change by a bit.  If "score_native" is on too and every one of the L native rows is present (no NaN
+ * x - the condition of "assign_ss"), the native gets the same three measures: its trace is rebuilt into a backbone by the
+ * very device function that builds the model's (csrc/coords.hip, float32), into scratch, and the same glycine flags apply;
+ * otherwise has_native = 0.  So a native that is exactly the model's returned C-alpha trace gives native arrays equal to the
+ * model's, bit for bit.  Counts are integers below 2^24, stored as floats.  Offsets relative to X0:
+ *   0                    P = 256, the sphere points per atom
+ *   1                    atoms present in the model (5L - glycines)
+ *   2 .. 6               sum of n over the model's N, CA, C, O, CB atoms
+ *   7                    atoms of the model with n = 0
+ *   8                    has_native (0 or 1)
+ *   9 .. 15              the native's atoms present, five sums, atoms with n = 0 (0 if has_native = 0)
+ *   16 .. 31             zero
+ *   [32 + aL, 32 + (a + 1)L), a = 0 .. 4   n of atom a (N, CA, C, O, CB) of model residue i; -1 for a glycine's CB
+ *   a = 5, 6, 7          hse_up, hse_down, cn10 of model residue i
+ *   a = 8 .. 15          the same eight arrays of the native; NaN in all 8L if has_native = 0
+ * A prediction that latched a device-side fault returns NaN in the whole block.  AREAS ARE NOT FORMED ON THE DEVICE: the
+ * accessible area of an atom is 4 pi R_a^2 n / 256, which the host computes in float64 (dmpfold2_amd/score.py).
+ * The definition, the only one (tests/exposure_ref.py restates it in NumPy).  Arithmetic: float64 formed from the float32
+ * coordinates, contraction off, every operation in the order written.
+ * Atoms: residue i has N, CA, C, O and CB from d_coords, atom index a = 0 .. 4.  G_i is true if column i of the alignment's
+ * first row is glycine (code 7): the CB of such a residue is ABSENT from the surface calculation - it neither has points nor
+ * blocks any.  The CB POSITION in d_coords exists for every residue and is used by the two pair counts, glycine included.
+ * Radii: R_a = the atom's radius plus a 1.4 A probe, with the radii of Kabsch & Sander 1983 (N 1.65, CA 1.87, C 1.76, O 1.40,
+ * a side-chain atom 1.80): the double literals 3.05, 3.27, 3.16, 2.80, 3.20.
+ * Sphere points: P = 256 unit vectors u_k on a golden-spiral lattice, z = 1 - (2k + 1) / 256, r = sqrt(1 - z z), phi = k pi
+ * (3 - sqrt 5), u_k = (r cos phi, r sin phi, z), formed in float64 and ROUNDED ONCE TO FLOAT32.  The 768 floats are the
+ * generated header csrc/exposure_points.h (tools/make_exposure_points.py; hexadecimal literals);
+ * dmp_debug_fetch("exposure_points") answers them as the device holds them.
+ * Point test: point k of atom i is p = c_i + R_i u_k, per component one multiply, then one add.  It is BURIED iff some present
+ * atom j != i, from any residue including i's own, has (dx dx + dy dy) + dz dz < R_j R_j with d = p - c_j.  n_i = the points
+ * that are not buried, an integer in [0, 256].  A NaN fails the comparison, as everywhere in this library.  The result is
+ * defined over ALL atoms: the kernel's neighbour filter (|c_i - c_j| < R_i + R_j + 0.01 for some atom i of the residue) only
+ * leaves out atoms that cannot hold a point, with a margin far above the rounding of the test.
+ * Half-sphere exposure: v = CB_i - CA_i; for j != i, w = CA_j - CA_i; near iff (w_x w_x + w_y w_y) + w_z w_z < 169.0; up iff
+ * near and (v_x w_x + v_y w_y) + v_z w_z > 0; down iff near and not up.  hse_up[i], hse_down[i] = the j that are up / down.
+ * Contact number: cn10[i] = #{j != i : |CB_j - CB_i|^2 < 100.0}, d = CB_j - CB_i, the same parenthesisation.
+ * THIS IS SHRAKE & RUPLEY'S KIND OF SURFACE ON A MODEL WITH NO SIDE CHAINS: IT IS NOT DSSP'S ACC, no relative accessibility
+ * is offered, and NOBODY HAS COMPARED THE FIGURES WITH ANOTHER PROGRAM'S.  The backbone is the one the reference's
+ * Levitt-style reconstruction places from the C-alpha trace, not an experimental one.
+ * Cost with the option on: one launch in the front end (exposure_capture_gly, beside ss_capture_pro: the glycine flags of the
+ * first row, kept for the end) and, in dmp_predict_end behind "assign_ss" and in front of "align_structure", on the
+ * prediction's stream and without synchronising, two launches (csrc/exposure.hip) - exposure_surface (one workgroup of 256
+ * threads per residue and entity, thread k owning point k of the residue's five atoms: the threads scan all 5L atoms and
+ * compact the candidates into an LDS list of (x, y, z, R^2) doubles with wave ballots and a prefix; the list is walked by
+ * every wave in step with early exit, in chunks of at most 1024 entries (32 KiB) with the buried bits carried in registers,
+ * so that chunk boundaries do not change a bit; the counts are popcounts of the waves' ballots, the sums go through one
+ * integer atomic per workgroup and counter, the last arriver writes the header) and exposure_pairs (one thread per residue:
+ * the two half-sphere counts and cn10 over LDS tiles) - and two more with the native (its backbone; has_native).  No float
+ * atomics, no waiting between workgroups: the same bits on every run.  Scratch: 14 counters, a ticket and has_native, the
+ * glycine flags and the native's backbone - 61 max_L + 256 bytes, 122 KiB at max_L = 2048 - allocated when the option first
+ * becomes 1 on a context and counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the
+ * option as it was.  Measured cost of dmp_predict_end with the option on (profiles/exposure.txt; a collapsed model, 98 % of
+ * its atoms without an exposed point at L = 2048): 0.27 ms at L = 96, 0.69 ms at 300, 2.13 ms at 1000, 5.18 ms at 2048 -
+ * about twice "assign_ss" on the same model (0.11, 0.29, 1.29, 2.78 ms, profiles/ss.txt) and 2.4 times "score_native" in
+ * the same run at L = 2048; a folded-like native's leg adds under 0.03 ms, a collapsed native's 0.3 to 2.0 ms.
+ * "exposure_chunk" (TESTS ONLY; n >= 0, default 0): at most n list entries per chunk when 0 < n < 1024.
  * "restrain_milli" (0 .. 100000, default 0 = off; any other value: DMP_ERR_ARG) and "restrain_cut_mA" (0 .. 100000, default
  * 15000): restrain the prediction's FINAL refinement to the predicted distance map.  THE REFERENCE HAS NO SUCH TERM: its
  * minimiser (network.py:106-137) knows steric repulsion and the bond and never sees the map.  Both are read when a prediction
@@ -439,7 +504,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
