@@ -36,7 +36,7 @@ from .score import Outputs
 from . import shard
 from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
                       pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy, add_restrain_arguments, restrain_cutoff_to_mA,
-                      restrain_report, restrain_to_milli)
+                      restrain_report, restrain_to_milli, needs_native, NATIVE_NEEDED)
 
 
 class BatchFailures(RuntimeError):
@@ -148,8 +148,22 @@ def ca_only_text(coords, confs, alnmat):
 RESTRAIN_COUNTS = ("steps", "restrained_pairs", "clashes")      # the integers of predict.restrain_report
 
 
-def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, scores=None, alignment=None,
-                 hits=None, hits_top=10, map_scores=None, pass_scores=None, ss=None, restrain=None, exposure=None):
+NESTED = {"score_map": "map", "passes": "passes"}       # the blocks whose JSON form goes inside the scores', and under which key
+
+
+def results_json(results, top=10):
+    """{name: JSON form} of the unpacked results given (each by the `name` of its row of score.BLOCKS), the map scores and the
+    pass table inside the scores' under "map" and "passes" - and only there: without scores they are nowhere."""
+    out = {row.name: row.json(results[row.name], top=top) for row in _score.BLOCKS
+           if results.get(row.name) is not None and row.key not in NESTED}
+    for key, inside in NESTED.items():
+        if results.get(_score.BLOCK[key].name) is not None and "scores" in out:
+            out["scores"][inside] = _score.BLOCK[key].json(results[_score.BLOCK[key].name])
+    return out
+
+
+def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, *, hits_top=10, restrain=None,
+                 **results):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
     (--distmap): npz gains the arrays distmap, best_pass, passes_run and map_rms; pdb / ca get <stem>.distmap.npy beside
     the structure (float32, as `dmpfold --distmap` writes it).  With `scores` (the dict of score.unpack_scores, --natives):
@@ -174,6 +188,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     score.unpack_exposure, --exposure): npz gains exp_n (int32 (L, 5): exposed points of N, CA, C, O, CB, -1 for a glycine's CB),
     exp_hse_up, exp_hse_down, exp_cn10 (int32 (L,)) and exp_area (float64 (L,): the residue's accessible area in square
     Angstrom); pdb / ca get <stem>.exposure.json (the line `dmpfold --exposure` prints)."""
+    unknown = set(results) - {row.name for row in _score.BLOCKS}
+    if unknown:
+        raise TypeError(f"write_result: no result is called {sorted(unknown)}")
+    scores, map_scores, pass_scores, ss, exposure, alignment, hits = (results.get(row.name) for row in _score.BLOCKS)
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -229,29 +247,13 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
         return path
     if distmap is not None:
         save_distmap_npy(stem + ".distmap.npy", distmap)
-    if scores is not None:
-        with open(stem + ".scores.json", "w") as fh:
-            js = _score.scores_json(scores)
-            if map_scores is not None:
-                js["map"] = _score.map_scores_json(map_scores)
-            if pass_scores is not None:
-                js["passes"] = _score.pass_scores_json(pass_scores)
-            fh.write(json.dumps(js) + "\n")
-    if ss is not None:
-        with open(stem + ".ss.json", "w") as fh:
-            fh.write(json.dumps(_score.ss_json(ss)) + "\n")
-    if exposure is not None:
-        with open(stem + ".exposure.json", "w") as fh:
-            fh.write(json.dumps({"exposure": _score.exposure_json(exposure)}) + "\n")
-    if restrain is not None:
-        with open(stem + ".restrain.json", "w") as fh:
-            fh.write(json.dumps({"restrain": restrain}) + "\n")
-    if alignment is not None:
-        with open(stem + ".alignment.json", "w") as fh:
-            fh.write(json.dumps(_score.alignment_json(alignment)) + "\n")
-    if hits is not None:
-        with open(stem + ".hits.json", "w") as fh:
-            fh.write(json.dumps(_score.hits_json(hits, hits["names"], hits_top)) + "\n")
+    forms = results_json(results, hits_top)
+    for name, value in (("exposure", forms.get("exposure")), ("restrain", restrain)):
+        if value is not None:
+            forms[name] = {name: value}                  # (these two lines carry their name)
+    for name, form in forms.items():
+        with open(f"{stem}.{name}.json", "w") as fh:
+            fh.write(json.dumps(form) + "\n")
     path = stem + ".pdb"
     with open(path, "w") as fh:
         fh.write(pdb_text(coords, confs, alnmat) if fmt == "pdb" else ca_only_text(coords, confs, alnmat))
@@ -338,10 +340,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     written as they complete), and a failing target never costs the others their results."""
     if fmt not in ("pdb", "ca", "npz"):
         raise ValueError(f"unknown output format {fmt!r} (pdb, ca, npz)")
-    if score_map and not natives:
-        raise ValueError("score_map scores the distance maps against native structures: give `natives`")
-    if score_passes and not natives:
-        raise ValueError("score_passes scores every pass against native structures: give `natives`")
+    for option, wanted in (("score_map", score_map), ("score_passes", score_passes)):
+        if wanted and not natives:
+            raise ValueError(needs_native(option, option, "`natives`", many=True))
     restraining = restrain_to_milli(restrain) > 0          # (a bad value raises before any work)
     restrain_cutoff_to_mA(restrain_cutoff)
     check_output_stems(targets)
@@ -394,26 +395,14 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
             sd = state_dict if state_dict is not None else load_state_dict(weights_file)
             pipe = Pipeline(dev, max_L, max_N, sd, streams=streams, precision=drop_in_precision())
-            if converge is not None:
-                pipe.set_converge(converge)
-            if distmap:
-                pipe.set_distmap(True)
-            if natives:
-                pipe.set_score(True)
-            if score_map:
-                pipe.set_score_map(True)          # (turns the distance map on: it is written only with `distmap`)
-            if score_passes:
-                pipe.set_score_passes(True)
-            if ss:
-                pipe.set_ss(True)
-            if exposure:
-                pipe.set_exposure(True)
-            if restraining:
-                pipe.set_restrain(restrain, restrain_cutoff)
-            if structures:
-                pipe.set_align(True)
-            if library is not None:
-                pipe.set_search(library)
+            # (score_map and the restraint turn the distance map on: it is written only with `distmap`)
+            for setter, wanted, *value in (("converge", converge is not None, converge), ("distmap", distmap, True),
+                                           ("score", natives, True), ("score_map", score_map, True),
+                                           ("score_passes", score_passes, True), ("ss", ss, True), ("exposure", exposure, True),
+                                           ("restrain", restraining, restrain, restrain_cutoff), ("align", structures, True),
+                                           ("search", library is not None, library)):
+                if wanted:
+                    getattr(pipe, "set_" + setter)(*value)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -445,53 +434,31 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         while copying and (copying[0][2] is None or copying[0][2].query()):
             done.append(copying.pop(0)[:2])
 
-    scored, all_scores = set(), {}
-    aligned, all_alignments = set(), {}
-    all_hits = {}
-    all_ss = {}
-    all_exposure = {}
-    all_restrain = {}
+    scored, aligned = set(), set()                      # the tickets that had a native / a structure
+    asked = {"natives": bool(natives), "structures": bool(structures), "library": library is not None, "ss": ss,
+             "exposure": exposure, "restrain": restraining}
+    blocks_on = {"score": asked["natives"], "align": asked["structures"], "search": asked["library"], "score_map": score_map,
+                 "passes": score_passes, "ss": ss, "exposure": exposure}
+    gathered = {}                                       # {key of `stats_out`: {stem: what the summary takes}}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        out = Outputs.of(public, distmap=distmap or score_map or restraining, score=bool(natives), align=bool(structures), search=library is not None,
-                         score_map=score_map, passes=score_passes, ss=ss, exposure=exposure)
+        out = Outputs.of(public, distmap=distmap or score_map or restraining, **blocks_on)
         aln_path, alnmat, _ = parsed.pop(t)
-        sc = ms = ps = None
-        if out.score_block is not None and t in scored:
-            sc = _score.unpack_scores(out.score_block, alnmat.shape[1])
-            js = _score.scores_json(sc)
-            if out.map_block is not None:
-                ms = _score.unpack_map_scores(out.map_block, alnmat.shape[1])
-                js["map"] = _score.map_scores_json(ms)
-            if out.pass_block is not None:
-                ps = _score.unpack_pass_scores(out.pass_block, _score.pass_rows(iterations))
-                js["passes"] = _score.pass_scores_json(ps)
-            all_scores[os.path.splitext(os.path.basename(aln_path))[0]] = js
-        al = None
-        if out.align_block is not None and t in aligned:
-            al = _score.unpack_alignment(out.align_block, alnmat.shape[1])
-            js = _score.alignment_json(al)
-            all_alignments[os.path.splitext(os.path.basename(aln_path))[0]] = {k: js[k] for k in ("m",) + _score.ALIGN_NAMES}
-        hits = None
-        if out.search_block is not None:
-            hits = dict(_score.unpack_search(out.search_block, alnmat.shape[1], library.lengths), names=list(library.names))
-            all_hits[os.path.splitext(os.path.basename(aln_path))[0]] = [
-                {k: v for k, v in h.items() if k not in ("R", "t")} for h in _score.hits_json(hits, library.names, search_top)["hits"]]
-        sec = None
-        if out.ss_block is not None:
-            sec = _score.unpack_ss(out.ss_block, alnmat.shape[1])
-            all_ss[os.path.splitext(os.path.basename(aln_path))[0]] = _score.ss_json(sec)
-        exposed = None
-        if out.exposure_block is not None:
-            exposed = _score.unpack_exposure(out.exposure_block, alnmat.shape[1], seq=alnmat[0])
-            all_exposure[os.path.splitext(os.path.basename(aln_path))[0]] = _score.exposure_json(exposed)
+        stem = os.path.splitext(os.path.basename(aln_path))[0]
+        had = {"score": t in scored, "score_map": t in scored, "passes": t in scored, "align": t in aligned}
+        results = {row.name: row.unpack(getattr(out, row.field), alnmat.shape[1], library=library, seq=alnmat[0])
+                   for row in _score.BLOCKS if getattr(out, row.field) is not None and had.get(row.key, True)}
+        forms = results_json(results, search_top)
         rep = None
         if restraining:
-            rep = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap, float(out.info[2]), out.coords)
-            all_restrain[os.path.splitext(os.path.basename(aln_path))[0]] = rep
+            rep = forms["restrain"] = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap,
+                                                      float(out.info[2]), out.coords)
+        for name, form in forms.items():
+            key, brief = GATHERED_AS.get(name, (name, None))
+            gathered.setdefault(key, {})[stem] = form if brief is None else brief(form)
         outputs.append(write_result(out_dir, aln_path, out.coords, out.confs, alnmat, fmt, out.distmap if distmap else None,
-                                    out.info if distmap else None, sc, al, hits, search_top, ms, ps, sec, rep, exposed))
+                                    out.info if distmap else None, hits_top=search_top, restrain=rep, **results))
 
     def finish(item):
         t, public = item
@@ -602,18 +569,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         if stats_out is not None and converge is not None:
             st = pipe.stats()
             stats_out["passes_run"], stats_out["passes_saved"] = st["passes_run"], st["passes_saved"]
-        if stats_out is not None and natives:
-            stats_out["scores"] = all_scores
-        if stats_out is not None and structures:
-            stats_out["alignments"] = all_alignments
-        if stats_out is not None and library is not None:
-            stats_out["hits"] = all_hits
-        if stats_out is not None and ss:
-            stats_out["ss"] = all_ss
-        if stats_out is not None and exposure:
-            stats_out["exposure"] = all_exposure
-        if stats_out is not None and restraining:
-            stats_out["restrain"] = all_restrain
+        for key, argument, _ in GATHERED:
+            if stats_out is not None and asked[argument]:
+                stats_out[key] = gathered.get(key, {})
         pipe.close()
     if failed:
         raise BatchFailures(failed, len(outputs), elapsed, outputs)
@@ -782,16 +740,34 @@ def score_summary(scores):
     return out
 
 
+# What a job gathers per target for its summary: (the key in run_batch's `stats_out`, in the job's store and in the summary;
+# the argument that asks for it; the summary's part from {stem: what was gathered}).  GATHERED_AS: a result (by the `name` of its
+# row of score.BLOCKS) that is gathered under another key, in a briefer form than its JSON form.
+GATHERED = (("scores", "natives", score_summary),
+            ("alignments", "structures", lambda found: {"aligned_targets": len(found), "alignments": found}),
+            ("hits", "library", lambda found: {"searched_targets": len(found), "hits": found}),
+            ("ss", "ss", ss_summary), ("exposure", "exposure", exposure_summary), ("restrain", "restrain", restrain_summary))
+GATHERED_AS = {"alignment": ("alignments", lambda form: {k: form[k] for k in ("m",) + _score.ALIGN_NAMES}),
+               "hits": ("hits", lambda form: [{k: v for k, v in hit.items() if k not in ("R", "t")} for hit in form["hits"]])}
+
+
+def gather(key, mine, world, job_store):
+    """{stem: value} of one GATHERED key over the ranks of a job, sorted: this rank's and what ranks 1 .. world - 1 left in
+    the job's store."""
+    found = dict(mine.get(key, {}))
+    for r in range(1, world):
+        found.update(json.loads(job_store.get(f"dmpfold_batch_{key}/{r}").decode()))
+    return dict(sorted(found.items()))
+
+
 def main(argv=None):
     ap = batch_parser()
     args = ap.parse_args(argv)
     if not args.list and not args.input:
         ap.error("give -l targets.txt and / or -i alignments ...")
-    if args.score_map and not args.natives:
-        ap.error("--score-map scores the distance maps against native structures: give --natives DIR")
-
-    if args.score_passes and not args.natives:
-        ap.error("--score-passes scores every pass against native structures: give --natives DIR")
+    for option in NATIVE_NEEDED:
+        if getattr(args, option) and not args.natives:
+            ap.error(needs_native(option, "--" + option.replace("_", "-"), "--natives DIR", many=True))
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -827,18 +803,9 @@ def main(argv=None):
         # this rank had already taken from the shared queue is lost with it: the summary says so
         print(f"dmpfold-batch: rank {rank}: {type(exc).__name__}: {exc}", file=sys.stderr)
         n, elapsed, status, broke = 0, 0.0, 2, 1
-    if args.natives and world > 1:                   # host side, through the job's key-value store: read behind the reduction
-        job_store.set(f"dmpfold_batch_scores/{rank}", json.dumps(passes.get("scores", {})))
-    if args.structures and world > 1:
-        job_store.set(f"dmpfold_batch_alignments/{rank}", json.dumps(passes.get("alignments", {})))
-    if args.library and world > 1:
-        job_store.set(f"dmpfold_batch_hits/{rank}", json.dumps(passes.get("hits", {})))
-    if args.ss and world > 1:
-        job_store.set(f"dmpfold_batch_ss/{rank}", json.dumps(passes.get("ss", {})))
-    if args.exposure and world > 1:
-        job_store.set(f"dmpfold_batch_exposure/{rank}", json.dumps(passes.get("exposure", {})))
-    if args.restrain and world > 1:
-        job_store.set(f"dmpfold_batch_restrain/{rank}", json.dumps(passes.get("restrain", {})))
+    for key, argument, _ in GATHERED:                # host side, through the job's key-value store: read behind the reduction
+        if getattr(args, argument) and world > 1:
+            job_store.set(f"dmpfold_batch_{key}/{rank}", json.dumps(passes.get(key, {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
         passes_all = shard.sum_over_ranks([passes.get("passes_run", 0), passes.get("passes_saved", 0)])
@@ -850,36 +817,9 @@ def main(argv=None):
                                "compare it with the target list" % broke_all)
         if args.converge is not None:
             summary["converge"], summary["passes_run"], summary["passes_saved"] = args.converge, passes_all[0], passes_all[1]
-        if args.natives:
-            scores = dict(passes.get("scores", {}))
-            for r in range(1, world):
-                scores.update(json.loads(job_store.get(f"dmpfold_batch_scores/{r}").decode()))
-            summary.update(score_summary(dict(sorted(scores.items()))))
-        if args.structures:
-            alis = dict(passes.get("alignments", {}))
-            for r in range(1, world):
-                alis.update(json.loads(job_store.get(f"dmpfold_batch_alignments/{r}").decode()))
-            summary["aligned_targets"], summary["alignments"] = len(alis), dict(sorted(alis.items()))
-        if args.library:
-            hits = dict(passes.get("hits", {}))
-            for r in range(1, world):
-                hits.update(json.loads(job_store.get(f"dmpfold_batch_hits/{r}").decode()))
-            summary["searched_targets"], summary["hits"] = len(hits), dict(sorted(hits.items()))
-        if args.ss:
-            sec = dict(passes.get("ss", {}))
-            for r in range(1, world):
-                sec.update(json.loads(job_store.get(f"dmpfold_batch_ss/{r}").decode()))
-            summary.update(ss_summary(dict(sorted(sec.items()))))
-        if args.exposure:
-            exp = dict(passes.get("exposure", {}))
-            for r in range(1, world):
-                exp.update(json.loads(job_store.get(f"dmpfold_batch_exposure/{r}").decode()))
-            summary.update(exposure_summary(dict(sorted(exp.items()))))
-        if args.restrain:
-            reports = dict(passes.get("restrain", {}))
-            for r in range(1, world):
-                reports.update(json.loads(job_store.get(f"dmpfold_batch_restrain/{r}").decode()))
-            summary.update(restrain_summary(dict(sorted(reports.items()))))
+        for key, argument, part in GATHERED:
+            if getattr(args, argument):
+                summary.update(part(gather(key, passes, world, job_store if world > 1 else None)))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

@@ -313,23 +313,46 @@ def drop_in_precision():
     return DROP_IN_PRECISION if v is None else v
 
 
-class Extras(_score._Beside, namedtuple("Extras", "distmap native structure library score_map score_passes",
-                                        defaults=(False, None, None, None, False, False))):
-    """What one call asks for besides the prediction itself, as `Engine.predict` documents each: `distmap` (return the
-    map), `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map),
-    `score_passes` (score every recycling pass) and, keywords carried beside the tuple's six fields, `ss` (assign secondary
-    structure) and `exposure` (solvent exposure of the backbone).
-    The public methods build one in their first lines; everything below them takes and carries the record."""
-    _beside = (("ss", False), ("exposure", False))
-    ss = False
-    exposure = False
+# What one call asks for besides the prediction itself, as `Engine.predict` documents each: `distmap` (return the map),
+# `native` (score against it), `structure` (align with it), `library` (search it), `score_map` (score the map),
+# `score_passes` (score every recycling pass), `ss` (assign secondary structure) and `exposure` (solvent exposure of the
+# backbone).  The public methods build one in their first line (`_asked`); everything below them takes and carries the record.
+Extras = namedtuple("Extras", "distmap native structure library score_map score_passes ss exposure",
+                    defaults=(False, None, None, None, False, False, False, False))
 
-    def __new__(cls, *args, ss=False, exposure=False, **kw):
-        return super().__new__(cls, *args, **kw)._with(bool(ss), bool(exposure))
+
+def _asked(call):
+    """The locals of a public predict method -> (Extras, what restrain_options makes of its `restrain`, `restrain_cutoff`)."""
+    return Extras(*(call[field] for field in Extras._fields)), restrain_options(call["restrain"], call["restrain_cutoff"])
+
+
+# What a call sets for its duration: (field of `Extras`, option), in the order they are set - an option behind what it needs.
+# `native` and `structure` are inputs (None = not given), the rest flags; CALL_CHECKS: what must hold of an input before
+# anything changes.  Convergence, the restraint and the library have arguments of their own: Engine._call_options.
+CALL_OPTIONS = (("distmap", "emit_distmap"), ("score_map", "score_map"), ("native", "score_native"),
+                ("score_passes", "score_passes"), ("ss", "assign_ss"), ("exposure", "exposure"), ("structure", "align_structure"))
+CALL_INPUTS = {"native": lambda L: np.full((L, 3), np.nan, dtype=np.float32),      # an input -> the value that means "none"
+               "structure": lambda L: np.zeros((0, 3), dtype=np.float32)}
+CALL_CHECKS = {"structure": _score.as_structure}
+
+# What an option needs on beside itself (the library looks at them together when a prediction begins).  "score_native" comes
+# with a native only: an option that needs it asks for one (`needs_native`) where none is given.
+NEEDS = {"score_map": ("emit_distmap", "score_native"), "score_passes": ("score_native",), "restrain_milli": ("emit_distmap",)}
+NATIVE_NEEDED = {"score_map": "scores the distance map{s}", "score_passes": "scores every pass"}
+_BLOCK_OF = {row.option: row for row in _score.BLOCKS}
+
+
+def needs_native(option, spelt, give, many=False):
+    """The text of the error for `option` (spelt as its caller spells it) asked for without a native (`give`: what to give)."""
+    return (f"{spelt} {NATIVE_NEEDED[option].format(s='s' if many else '')} against "
+            + ("native structures" if many else "a native structure") + f": give {give}")
 
 
 # The options that decide the layout of a `d_conf` buffer, in the order of a row of `agree_options`.
 LAYOUT_OPTIONS = ("emit_distmap", "score_native", "score_map", "align_structure", "search_structures")
+# The options that own one block and need nothing, by the key of their row in score.BLOCKS: a field of `Flags` and of a
+# `Layout`, a Pipeline's set_<key>; the engines of a pipeline must agree on each (`agree`).
+OWN_BLOCK = ("ss", "exposure")
 
 # The layout options as one prediction runs with them: `emit` .. `align` bools, `search` the K of "search_structures";
 # `alloc`: size the buffer as if "emit_distmap" were on (a pipeline whose engines disagree on that option alone);
@@ -338,13 +361,24 @@ LAYOUT_OPTIONS = ("emit_distmap", "score_native", "score_map", "align_structure"
 Flags = namedtuple("Flags", "emit alloc score score_map align search max_L passes ss exposure", defaults=(None, None, False, False))
 
 
-def agree_ss(values, option="assign_ss", setter="set_ss"):
-    """The `ss` of a prediction's Flags from option "assign_ss" as every engine that may run it holds it: they must agree -
-    RuntimeError if not.  (`option`, `setter`: the same rule for another option that owns one block, "exposure".)"""
+def agree(values, option, setter):
+    """A field of a prediction's Flags from an option that owns one block, as every engine that may run the prediction holds
+    it: they must agree - RuntimeError if not."""
     values = [bool(v) for v in values]
     if any(v != values[0] for v in values):
         raise RuntimeError(f"the engines must agree on \"{option}\" (the blocks behind its block move with it); use {setter}")
     return values[0]
+
+
+def agree_ss(values, option="assign_ss", setter="set_ss"):
+    """`agree` for option "assign_ss" (the name and signature callers know)."""
+    return agree(values, option, setter)
+
+
+def _own_blocks(engines):
+    """{key: `agree` over the engines} of every OWN_BLOCK option."""
+    return {key: agree([e.get_option(_score.BLOCK[key].option) for e in engines], _score.BLOCK[key].option, "set_" + key)
+            for key in OWN_BLOCK}
 
 
 def agree_passes(values, score, iterations):
@@ -393,7 +427,7 @@ def _stage(device, L, template_ca, flags, extras):
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, passes=flags.passes, ss=flags.ss, exposure=flags.exposure)
+                 flags.max_L, flags.passes, **{key: getattr(flags, key) for key in OWN_BLOCK})
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
     if library is not None:
@@ -517,9 +551,8 @@ class Engine:
         after the first pass p >= 1 whose trace changes the seed distance map by no more than that (RMS); the outputs
         are bit for bit those of `iterations` = p.  `passes_run` tells how many trunk passes ran.  With a tolerance the
         call synchronises with the GPU once per pass."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
-        return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
-                             restrain_options(restrain, restrain_cutoff))
+        extras, restrain = _asked(locals())
+        return self._predict(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras, restrain)
 
     def _forget_last(self):
         self._last = _Last(Outputs(None, None), 0, None)
@@ -537,67 +570,18 @@ class Engine:
         return restrain_report(milli * 1e-3, cut_mA * 1e-3, steps, out.distmap, None if out.info is None else out.info[2].item(),
                                coords)
 
-    # The blocks of the last prediction on the GPU, views of the buffer handed to the library; None where the option was off.
-    score_block = property(lambda self: self._last.out.score_block, doc='"score_native": 5L + 24 floats, or None')
-    map_score_block = property(lambda self: self._last.out.map_block, doc='"score_map": 64 + L floats, or None')
-    pass_block = property(lambda self: self._last.out.pass_block, doc='"score_passes": 16 + 8R floats, or None')
-    align_block = property(lambda self: self._last.out.align_block, doc='"align_structure": 25 + 2L + 3m floats, or None')
-    search_block = property(lambda self: self._last.out.search_block, doc='"search_structures": 26K + 2LK + 3M floats, or None')
-    ss_block = property(lambda self: self._last.out.ss_block, doc='"assign_ss": 32 + 8L floats, or None')
-    exposure_block = property(lambda self: self._last.out.exposure_block, doc='"exposure": 32 + 16L floats, or None')
-
-    @property
-    def exposure(self):
-        """The solvent exposure of the last prediction as score.unpack_exposure gives it, None if it ran without option
-        "exposure".  Synchronises with the GPU."""
-        return self._unpacked("exposure_block", _score.unpack_exposure)
-
-    @property
-    def ss(self):
-        """The secondary structure of the last prediction as score.unpack_ss gives it, None if it ran without option
-        "assign_ss".  Synchronises with the GPU."""
-        return self._unpacked("ss_block", _score.unpack_ss)
-
-    def _unpacked(self, field, unpack):
-        """A block of the last prediction through `unpack`(block, L), None without it.  Synchronises with the GPU."""
-        block = getattr(self._last.out, field)
+    # Per row of score.BLOCKS two properties, made behind the class: the block of the last prediction on the GPU, a view of the
+    # buffer handed to the library, under its field's name (score_block, map_score_block, pass_block, ss_block, exposure_block,
+    # align_block, search_block), and its unpacked form under the row's name (scores, map_scores, pass_scores, ss, exposure,
+    # alignment, hits); None where the option was off.
+    def _unpacked(self, row):
+        """The block of a row of score.BLOCKS of the last prediction through the row's unpacker, None without it.
+        Synchronises with the GPU."""
+        block = getattr(self._last.out, row.field)
         if block is None:
             return None
         torch.cuda.synchronize(self.device)
-        return unpack(block, self._last.L)
-
-    @property
-    def map_scores(self):
-        """The map scores of the last prediction as score.unpack_map_scores gives them, None if it ran without option
-        "score_map".  Synchronises with the GPU."""
-        return self._unpacked("map_block", _score.unpack_map_scores)
-
-    @property
-    def pass_scores(self):
-        """The pass table of the last prediction as score.unpack_pass_scores gives it, None if it ran without option
-        "score_passes".  Synchronises with the GPU."""
-        return self._unpacked("pass_block", lambda block, L: _score.unpack_pass_scores(
-            block, (block.shape[0] - _score.PASS_HEADER) // _score.PASS_ROW))
-
-    @property
-    def hits(self):
-        """The search of the last prediction as score.unpack_search gives it, with the library's `names` beside `hits` and
-        `rank`; None if it ran without option "search_structures".  Synchronises with the GPU."""
-        library = self._last.library
-        return self._unpacked("search_block", lambda block, L: dict(_score.unpack_search(block, L, library.lengths),
-                                                                    names=list(library.names)))
-
-    @property
-    def alignment(self):
-        """The structural alignment of the last prediction as score.unpack_alignment gives it, None if it ran without option
-        "align_structure".  Synchronises with the GPU."""
-        return self._unpacked("align_block", _score.unpack_alignment)
-
-    @property
-    def scores(self):
-        """The scores of the last prediction as score.unpack_scores gives them, None if it ran without option
-        "score_native".  Synchronises with the GPU."""
-        return self._unpacked("score_block", _score.unpack_scores)
+        return row.unpack(block, self._last.L, library=self._last.library)
 
     @property
     def passes_run(self):
@@ -608,8 +592,8 @@ class Engine:
                        minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
                        score_map=False, score_passes=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
         """Same as `predict` for residue codes already resident on the GPU (uint8 (N, L))."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
-        return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras, restrain_options(restrain, restrain_cutoff))
+        extras, restrain = _asked(locals())
+        return self._predict(d_msa, template_ca, iterations, minsteps, converge, extras, restrain)
 
     def _upload(self, alnmat):
         with torch.cuda.device(self.device):
@@ -625,29 +609,27 @@ class Engine:
         `converge` None leaves "recycle_tol_mA" as it stands; "emit_distmap" / "score_native" / "align_structure" set by hand
         stay set.  `restrain`: None (the two restraint options stay as they stand) or what restrain_options gave."""
         want = {} if converge is None else {"recycle_tol_mA": converge_to_mA(converge)}    # (raises before anything changes)
+        def turn_on(option, asked_by=None):
+            """An option that is off is wanted on; "score_native" as the need of another only says that a native must be given."""
+            if not self.get_option(option):
+                if asked_by is None or option != "score_native":
+                    want[option] = 1
+                elif extras.native is None:
+                    raise ValueError(needs_native(asked_by, asked_by, "`native`"))
+
         if restrain is not None:
             want["restrain_milli"], want["restrain_cut_mA"] = restrain
-            if restrain[0] > 0 and not self.get_option("emit_distmap"):
-                want["emit_distmap"] = 1                  # (map_rms comes back with the map)
-        if extras.score_map and extras.native is None and not self.get_option("score_native"):
-            raise ValueError("score_map scores the distance map against a native structure: give `native`")
-        if (extras.distmap or extras.score_map) and not self.get_option("emit_distmap"):
-            want["emit_distmap"] = 1
-        if extras.score_map and not self.get_option("score_map"):
-            want["score_map"] = 1                         # (the library looks at the three together when the prediction begins)
-        if extras.score_passes and extras.native is None and not self.get_option("score_native"):
-            raise ValueError("score_passes scores every pass against a native structure: give `native`")
-        if extras.native is not None and not self.get_option("score_native"):
-            want["score_native"] = 1
-        if extras.score_passes and not self.get_option("score_passes"):
-            want["score_passes"] = 1                      # (behind "score_native", which the library asks for at begin)
-        if extras.ss and not self.get_option("assign_ss"):
-            want["assign_ss"] = 1
-        if extras.exposure and not self.get_option("exposure"):
-            want["exposure"] = 1
-        if extras.structure is not None and not self.get_option("align_structure"):
-            _score.as_structure(extras.structure)                                          # (a bad shape raises before anything changes)
-            want["align_structure"] = 1
+            for need in NEEDS["restrain_milli"] if restrain[0] > 0 else ():
+                turn_on(need)                             # (map_rms comes back with the map)
+        for field, option in CALL_OPTIONS:
+            value = getattr(extras, field)
+            if value is None or not (field in CALL_INPUTS or value):
+                continue
+            for need in NEEDS.get(option, ()):
+                turn_on(need, asked_by=option)
+            if field in CALL_CHECKS and not self.get_option(option):
+                CALL_CHECKS[field](value)                 # (a bad shape raises before anything changes)
+            turn_on(option)
         if extras.library is not None and not self.get_option("search_structures"):
             extras.library.check(self.max_L)                                               # (raises, naming the entry)
             want["search_max_m"] = extras.library.max_m   # before the option itself: the scratch is sized from it
@@ -679,8 +661,7 @@ class Engine:
             raise RuntimeError(f"alignment has {L} columns; the network needs at least 8 "
                                "(MDS embedding width, reference network.py:250-253)")
         flags = Flags(bool(emit), bool(emit), bool(score), bool(smap and emit and score), bool(align), search, self.max_L,
-                      agree_passes([self.get_option("score_passes")], score, iterations), bool(self.get_option("assign_ss")),
-                      bool(self.get_option("exposure")))
+                      agree_passes([self.get_option("score_passes")], score, iterations), **_own_blocks([self]))
         with torch.cuda.device(self.device):
             self._forget_last()
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
@@ -734,10 +715,9 @@ class Engine:
         operands and needs |activation| < 6e4; a prediction that leaves that range (never seen with
         InstanceNorm'd trunks, but the trained weights decide) is repeated with the 3-way bf16 split,
         which has float32's range, at about half the convolution rate."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
-        out = self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
-                            restrain_options(restrain, restrain_cutoff))
-        return out.public(extras.distmap, blocks=False)
+        extras, restrain = _asked(locals())
+        return self._checked(self._upload(alnmat), template_ca, iterations, minsteps, converge, extras,
+                             restrain).public(extras.distmap, blocks=False)
 
     def predict_device_checked(self, d_msa, template_ca=None, iterations=default_iterations,
                                minsteps=default_minsteps, converge=None, distmap=False, native=None, structure=None, library=None,
@@ -745,9 +725,8 @@ class Engine:
         """`predict_checked` for residue codes already resident on the GPU (`distmap`, `native`, `structure`, `library`,
         `score_map`, `score_passes`, `ss`, `restrain`: see `predict`; a repeat of the prediction returns the repeat's map,
         scores, alignment and hits)."""
-        extras = Extras(distmap, native, structure, library, score_map, score_passes, ss=ss, exposure=exposure)
-        out = self._checked(d_msa, template_ca, iterations, minsteps, converge, extras, restrain_options(restrain, restrain_cutoff))
-        return out.public(extras.distmap, blocks=False)
+        extras, restrain = _asked(locals())
+        return self._checked(d_msa, template_ca, iterations, minsteps, converge, extras, restrain).public(extras.distmap, blocks=False)
 
     def _checked(self, d_msa, template_ca, iterations, minsteps, converge, extras, restrain=None):
         """`predict_device_checked` -> Outputs; the repeats run with the call's options still set and carry the call's
@@ -783,6 +762,24 @@ class Engine:
         n = _lib.check(self.lib.dmp_debug_fetch(self._ctx, name.encode(), out.data_ptr(),
                                                 int(numel), self.stream()))
         return out[:n]
+
+
+# The properties of an `Engine` per row of score.BLOCKS (see `Engine._unpacked`); RESULT_DOCS: how each result reads.
+RESULT_DOCS = {"scores": "The scores of the last prediction as score.unpack_scores gives them",
+               "map_scores": "The map scores of the last prediction as score.unpack_map_scores gives them",
+               "pass_scores": "The pass table of the last prediction as score.unpack_pass_scores gives it",
+               "ss": "The secondary structure of the last prediction as score.unpack_ss gives it",
+               "exposure": "The solvent exposure of the last prediction as score.unpack_exposure gives it",
+               "alignment": "The structural alignment of the last prediction as score.unpack_alignment gives it",
+               "hits": "The search of the last prediction as score.unpack_search gives it, with the library's `names` beside `hits` "
+                       "and `rank`"}
+for _row in _score.BLOCKS:
+    setattr(Engine, {"map_block": "map_score_block"}.get(_row.field, _row.field),
+            property(lambda self, field=_row.field: getattr(self._last.out, field),
+                     doc=f'"{_row.option}": {_row.shape} floats, or None'))
+    setattr(Engine, _row.name, property(lambda self, row=_row: self._unpacked(row),
+                                        doc=f'{RESULT_DOCS[_row.name]}, None if it ran without option "{_row.option}".  '
+                                            "Synchronises with the GPU."))
 
 
 class _PipelineEngine(Engine):
@@ -873,26 +870,11 @@ class Pipeline:
         prec = precision if precision is not None else _env_precision()
         if prec is not None:
             self.set_option("precision", prec)
-        if converge is not None:
-            self.set_converge(converge)
-        if distmap:
-            self.set_distmap(True)
-        if score:
-            self.set_score(True)
-        if align:
-            self.set_align(True)
-        if search is not None:
-            self.set_search(search)
-        if score_map:
-            self.set_score_map(True)
-        if score_passes:
-            self.set_score_passes(True)
-        if ss:
-            self.set_ss(True)
-        if exposure:
-            self.set_exposure(True)
-        if restrain is not None:
-            self.set_restrain(restrain)
+        asked = locals()
+        for name in ("converge", "distmap", "score", "align", "search", "score_map", "score_passes", "ss", "exposure", "restrain"):
+            value = asked[name]       # (set in this order; a tolerance, a library and a force constant are given unless None)
+            if value is not None and (name in ("converge", "search", "restrain") or value):
+                getattr(self, "set_" + name)(value)
         self._jobs = {}               # ticket -> _Job: kept alive
         self._handed = []             # tickets whose result was handed out before the GPU finished them: released later
 
@@ -911,51 +893,52 @@ class Pipeline:
         Angstrom.  Turning it on turns "emit_distmap" on, so that map_rms comes back; turning it off leaves that as it is.
         Idle pipeline only."""
         milli, cut_mA = restrain_to_milli(restrain), restrain_cutoff_to_mA(cutoff)     # (raise before anything changes)
-        if milli > 0:
-            self.set_distmap(True)
+        for need in NEEDS["restrain_milli"] if milli > 0 else ():
+            self.set_option(need, 1)
         self.set_option("restrain_cut_mA", cut_mA)
         self.set_option("restrain_milli", milli)
 
+    def _set_flag(self, option, on):
+        """An on / off option on every engine; turning it on turns on what it needs (NEEDS) first."""
+        for need in NEEDS.get(option, ()) if on else ():
+            self.set_option(need, 1)
+        self.set_option(option, 1 if on else 0)
+
     def set_distmap(self, on):
         """Option "emit_distmap" on every engine: targets submitted from now on return their distance map; idle pipeline only."""
-        self.set_option("emit_distmap", 1 if on else 0)
+        self._set_flag("emit_distmap", on)
 
     def set_score(self, on):
         """Option "score_native" on every engine: targets submitted from now on are scored against the `native` given to
         `submit` (none given: no row present, n_pairs 0); idle pipeline only."""
-        self.set_option("score_native", 1 if on else 0)
+        self._set_flag("score_native", on)
 
     def set_score_map(self, on):
         """Option "score_map" on every engine: the distance map of targets submitted from now on is scored against the
         `native` given to `submit`.  Turning it on turns "emit_distmap" and "score_native" on, which it needs; turning it off
         leaves them as they are.  Idle pipeline only."""
-        if on:
-            self.set_distmap(True)
-            self.set_score(True)
-        self.set_option("score_map", 1 if on else 0)
+        self._set_flag("score_map", on)
 
     def set_score_passes(self, on):
         """Option "score_passes" on every engine: every recycling pass of targets submitted from now on is scored against the
         `native` given to `submit`.  Turning it on turns "score_native" on, which it needs; turning it off leaves that as it
         is.  Idle pipeline only."""
-        if on:
-            self.set_score(True)
-        self.set_option("score_passes", 1 if on else 0)
+        self._set_flag("score_passes", on)
 
     def set_ss(self, on):
         """Option "assign_ss" on every engine: targets submitted from now on get the secondary structure of their backbone
         (and, with `set_score` on and a whole native given to `submit`, of the native's); idle pipeline only."""
-        self.set_option("assign_ss", 1 if on else 0)
+        self._set_flag("assign_ss", on)
 
     def set_exposure(self, on):
         """Option "exposure" on every engine: targets submitted from now on get the solvent exposure of their backbone counted
         (and, with `set_score` on and a whole native given to `submit`, of the native's); idle pipeline only."""
-        self.set_option("exposure", 1 if on else 0)
+        self._set_flag("exposure", on)
 
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
-        self.set_option("align_structure", 1 if on else 0)
+        self._set_flag("align_structure", on)
 
     def set_search(self, library):
         """Option "search_structures" on every engine: targets submitted from now on are aligned with every entry of `library`
@@ -1003,8 +986,7 @@ class Pipeline:
             flags = agree_options([e.get_option(name) for name in LAYOUT_OPTIONS] for e in self.engines)
             flags = flags._replace(max_L=self.engines[0].max_L,
                                    passes=agree_passes([e.get_option("score_passes") for e in self.engines], flags.score, iterations),
-                                   ss=agree_ss(e.get_option("assign_ss") for e in self.engines),
-                                   exposure=agree_ss((e.get_option("exposure") for e in self.engines), "exposure", "set_exposure"))
+                                   **_own_blocks(self.engines))
             if flags.align and structure is not None and _score.as_structure(structure).shape[0] > flags.max_L:
                 raise RuntimeError(f"structure has {len(structure)} rows; the pipeline's capacity is {flags.max_L}")
             if flags.search and (self._search is None or len(self._search) != flags.search):
@@ -1154,14 +1136,13 @@ class Pipeline:
                 if bits:
                     # what the target ran with, for one engine alone: a block that was there without its input gets the
                     # input that means "none" (an all-NaN native, a structure of 0 rows)
-                    emit, extras = res.distmap is not None, job.extras
-                    if res.score_block is not None and extras.native is None:
-                        extras = extras._replace(native=np.full((job.d_msa.shape[1], 3), np.nan, dtype=np.float32))
-                    if res.align_block is not None and extras.structure is None:
-                        extras = extras._replace(structure=np.zeros((0, 3), dtype=np.float32))
-                    extras = extras._replace(distmap=emit, score_map=res.map_block is not None,
-                                             score_passes=res.pass_block is not None, ss=res.ss_block is not None,
-                                             exposure=res.exposure_block is not None)
+                    emit, extras = res.distmap is not None, job.extras._replace(distmap=res.distmap is not None)
+                    for field, option in CALL_OPTIONS[1:]:
+                        there = getattr(res, _BLOCK_OF[option].field) is not None
+                        if field not in CALL_INPUTS:
+                            extras = extras._replace(**{field: there})
+                        elif there and getattr(extras, field) is None:
+                            extras = extras._replace(**{field: CALL_INPUTS[field](job.d_msa.shape[1])})
                     try:
                         rep = eng._checked(job.d_msa, job.d_tpl, job.iterations, job.minsteps, None, extras)
                         res = rep if emit else rep._replace(distmap=None, info=None)     # (engine 0's "emit_distmap" set by hand)
@@ -1329,10 +1310,9 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
     """`aln_to_coords` -> Prediction; the eight flags are its return_distmap, return_scores, return_alignment, return_hits,
     return_map_scores, return_pass_scores, return_ss and return_exposure; `restrain`, `restrain_cutoff` are its own."""
     restrain_options(restrain, restrain_cutoff)                              # (a bad value raises before any work)
-    if map_scores and native is None:
-        raise ValueError("return_map_scores scores the distance map against a native structure: give `native`")
-    if pass_scores and native is None:
-        raise ValueError("return_pass_scores scores every pass against a native structure: give `native`")
+    for option, wanted in (("score_map", map_scores), ("score_passes", pass_scores)):
+        if wanted and native is None:
+            raise ValueError(needs_native(option, "return_" + _BLOCK_OF[option].name, "`native`"))
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -1472,10 +1452,9 @@ def run_dmpfold(argv=None):
     """Command-line entry point with the reference's flags (predict.py:160-208)."""
     parser = dmpfold_parser()
     args = parser.parse_args(argv)
-    if args.score_map and args.native is None:
-        parser.error("--score-map scores the distance map against a native structure: give --native")
-    if args.score_passes and args.native is None:
-        parser.error("--score-passes scores every pass against a native structure: give --native")
+    for option in NATIVE_NEEDED:
+        if getattr(args, option) and args.native is None:
+            parser.error(needs_native(option, "--" + option.replace("_", "-"), "--native"))
     r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
                       args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
                       distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,

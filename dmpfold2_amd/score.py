@@ -106,80 +106,59 @@ def exposure_floats(L):
     return EXPOSURE_HEADER + EXPOSURE_ARRAYS * int(L)
 
 
-class _Beside:
-    """For a namedtuple subclass that carries more, keyword-only values beside the tuple (`_beside` = ((name, default), ...)).
-    The tuple itself - its fields, its length, its positional order, which callers rely on - stays as it is; `_replace`,
-    ==, hash and repr know the values, and an instance made without one holds its default."""
-    _beside = ()
-
-    def _with(self, *values, **named):
-        """The values in the order of `_beside` (those not given stay as they are), or by name."""
-        for (name, _), value in zip(self._beside, values):
-            setattr(self, name, value)
-        for name, value in named.items():
-            setattr(self, name, value)
-        return self
-
-    def _replace(self, **kw):
-        values = [kw.pop(name, getattr(self, name)) for name, _ in self._beside]
-        return super()._replace(**kw)._with(*values)
-
-    def __eq__(self, other):
-        return tuple.__eq__(self, other) is True and all(_same(getattr(self, name), getattr(other, name, default))
-                                                          for name, default in self._beside)
-
-    def __ne__(self, other):
-        return not self == other
-
-    def __hash__(self):
-        return tuple.__hash__(self)
-
-    def __repr__(self):
-        return super().__repr__()[:-1] + "".join(f", {name}={getattr(self, name)!r}" for name, _ in self._beside) + ")"
-
-
-def _same(a, b):
-    return a is b or (not hasattr(a, "shape") and not hasattr(b, "shape") and a == b)
-
-
-class Layout(_Beside, namedtuple("Layout", "L distmap score score_map align_m search max_L passes",
-                                 defaults=(False, False, False, None, None, None, None))):
+class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_L passes ss exposure",
+                        defaults=(False, False, False, None, None, None, None, False, False))):
     """Where everything lies in the `d_conf` buffer of a prediction of length L: the Python twin of ConfLayout / conf_layout()
     / search_base() of csrc/common.h, in the order of include/dmpfold_hip.h.  Made from what decides it - `distmap`, `score`,
-    `score_map`: options "emit_distmap", "score_native", "score_map" on; `align_m`: the m the align block holds (None =
-    "align_structure" off); `search`: (K, M) of option "search_structures" (None = off); `max_L`: the context's, for the rule
-    of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0 counts); `passes` (keyword): the rows R
-    of the pass block of option "score_passes" (None = off); `ss` and `exposure` (keywords, carried beside the tuple's eight
-    fields, default off): options "assign_ss" and "exposure" on.  Every offset is stated once, each from the one in front of it:
+    `score_map`, `ss`, `exposure`: options "emit_distmap", "score_native", "score_map", "assign_ss", "exposure" on; `align_m`:
+    the m the align block holds (None = "align_structure" off); `search`: (K, M) of option "search_structures" (None = off);
+    `max_L`: the context's, for the rule of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0
+    counts); `passes`: the rows R of the pass block of option "score_passes" (None = off).  The confidences, the map and its
+    info lie in front; behind them the blocks of BLOCKS that are on, each where the one in front of it ends:
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
       (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | exposure_off (X0): exposure block (32 + 16L) |
       align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
 
     and `total` is the floats the buffer must hold."""
-    _beside = (("ss", False), ("exposure", False))
-    ss = False
-    exposure = False
 
-    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None, *,
+    def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None,
                 ss=False, exposure=False):
         return super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
-                               None if passes is None else int(passes))._with(bool(ss), bool(exposure))
+                               None if passes is None else int(passes), bool(ss), bool(exposure))
+
+    def floats(self, row):
+        """The floats a row of BLOCKS takes in this buffer: 0 where its block is off."""
+        value = getattr(self, row.arg)
+        return 0 if value is None or value is False else row.floats(self.L, value)
+
+    def _walk(self):
+        """(row, where its block begins) of every block up to the align block, then (None, where that ends): one running sum.
+        A block's size is asked for only when the walk goes on behind it (an align_m that is no number raises ValueError there)."""
+        at = self.score_off
+        for row in BLOCKS[:-1]:
+            yield row, at
+            at += self.floats(row)
+        yield None, at
+
+    def _begin(self, key):
+        return next(at for row, at in self._walk() if row is None or row.key == key)
 
     info_off = property(lambda s: s.L + (s.L * s.L if s.distmap else 0))
     score_off = property(lambda s: s.info_off + (3 if s.distmap else 0))                                    # S0
-    mapscore_off = property(lambda s: s.score_off + (score_floats(s.L) if s.score else 0))                  # M0
-    pass_off = property(lambda s: s.mapscore_off + (mapscore_floats(s.L) if s.score_map else 0))            # T0
-    ss_off = property(lambda s: s.pass_off + (pass_floats(s.passes) if s.passes is not None else 0))        # U0
-    exposure_off = property(lambda s: s.ss_off + (ss_floats(s.L) if s.ss else 0))                           # X0
-    align_off = property(lambda s: s.exposure_off + (exposure_floats(s.L) if s.exposure else 0))            # A0
-    # the end of the align block as its writer allocated it (an align_m that is no number raises ValueError) ...
-    align_end = property(lambda s: s.align_off + (align_floats(s.L, s.align_m) if s.align_m is not None else 0))
+    mapscore_off = property(lambda s: s._begin("score_map"))                                                # M0
+    pass_off = property(lambda s: s._begin("passes"))                                                       # T0
+    ss_off = property(lambda s: s._begin("ss"))                                                             # U0
+    exposure_off = property(lambda s: s._begin("exposure"))                                                 # X0
+    align_off = property(lambda s: s._begin("align"))                                                       # A0
+    # the end of the align block as its writer allocated it ...
+    align_end = property(lambda s: s._begin(None))
     # ... and B0, its end as the library counts it: 3m of it only if m is an integer in [3, max_L]
     search_off = property(lambda s: s.align_end if s.align_m is None or s.max_L is None
                           else s.align_off + align_floats(s.L, align_m_rule(s.align_m, s.max_L)))
-    search_end = property(lambda s: s.search_off + (search_floats(s.L, *s.search) if s.search is not None else 0))
+    search_end = property(lambda s: s.search_off + s.floats(BLOCK["search"]))
+    # the search block may begin inside what the align block's writer allocated: the buffer holds the larger of the two
     total = property(lambda s: s.align_end if s.search is None else max(s.align_end, s.search_end))
 
     def split(self, buf, coords=None):
@@ -188,23 +167,25 @@ class Layout(_Beside, namedtuple("Layout", "L distmap score score_map align_m se
         L = self.L
         if buf.ndim != 1 or buf.shape[0] < self.total:
             raise ValueError(f"a d_conf buffer of length {L} has {self.total} floats, got shape {tuple(buf.shape)}")
+        marks = list(self._walk())
+        parts = {row.field: buf[at:end] for (row, at), (_, end) in zip(marks, marks[1:]) if end > at}
+        if self.distmap:
+            parts.update(distmap=buf[L:self.info_off].reshape(L, L), info=buf[self.info_off:self.score_off])
+        if self.search is not None:
+            parts["search_block"] = buf[self.search_off:self.search_end]
+        return Outputs(coords, buf[:L], **parts)
 
-        def part(on, at, end):
-            return buf[at:end] if on else None
-        return Outputs(coords, buf[:L], buf[L:self.info_off].reshape(L, L) if self.distmap else None,
-                       part(self.distmap, self.info_off, self.score_off), part(self.score, self.score_off, self.mapscore_off),
-                       part(self.align_m is not None, self.align_off, self.align_end),
-                       part(self.search is not None, self.search_off, self.search_end),
-                       part(self.score_map, self.mapscore_off, self.pass_off),
-                       part(self.passes is not None, self.pass_off, self.ss_off))._with(self.ss_block(buf), self.exposure_block(buf))
+    def _view(self, key, buf):
+        at, floats = self._begin(key), self.floats(BLOCK[key])
+        return buf[at:at + floats] if floats else None
 
     def ss_block(self, buf):
         """The SS block of a `d_conf` buffer as a view (32 + 8L floats), None with `ss` off."""
-        return buf[self.ss_off:self.exposure_off] if self.ss else None
+        return self._view("ss", buf)
 
     def exposure_block(self, buf):
         """The exposure block of a `d_conf` buffer as a view (32 + 16L floats), None with `exposure` off."""
-        return buf[self.exposure_off:self.align_off] if self.exposure else None
+        return self._view("exposure", buf)
 
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
@@ -235,27 +216,29 @@ def distmap_floats(L, on=True):
     return Layout(L, on).total
 
 
-class Outputs(_Beside, namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block pass_block",
-                                  defaults=(None, None, None, None, None, None, None))):
+class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align_block search_block map_block pass_block ss_block "
+                         "exposure_block", defaults=(None,) * 9)):
     """What a prediction gives: coords (L, 5, 3), and the parts of its `d_conf` buffer as views of the one allocation -
     confs (L,), with "emit_distmap" distmap (L, L) and info (3,) = [best_pass, passes_run, map_rms], with "score_native"
     score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
-    (26K + 2LK + 3M,), with "score_map" map_block (64 + L,), with "score_passes" pass_block (16 + 8R,) - None for what is
-    absent.  With "assign_ss" the SS block (32 + 8L,) is `ss_block` and with "exposure" the exposure block (32 + 16L,) is `exposure_block`, both carried beside the tuple's nine
-    fields (None otherwise)."""
-    _beside = (("ss_block", None), ("exposure_block", None))
-    ss_block = None
-    exposure_block = None
+    (26K + 2LK + 3M,), with "score_map" map_block (64 + L,), with "score_passes" pass_block (16 + 8R,), with "assign_ss"
+    ss_block (32 + 8L,), with "exposure" exposure_block (32 + 16L,) - None for what is absent.  The blocks stand in the
+    order they are handed out in (HANDOUT), not the buffer's (BLOCKS, at the end of this module)."""
+    __hash__ = tuple.__hash__
 
-    def __new__(cls, *args, ss_block=None, exposure_block=None, **kw):
-        return super().__new__(cls, *args, **kw)._with(ss_block, exposure_block)
+    def __eq__(self, other):        # (a part is an array or a tensor, whose == is elementwise: parts are the same by identity)
+        return isinstance(other, tuple) and len(self) == len(other) and all(
+            a is b or (not hasattr(a, "shape") and not hasattr(b, "shape") and a == b) for a, b in zip(self, other))
+
+    def __ne__(self, other):
+        return not self == other
 
     @classmethod
     def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False, ss=False, exposure=False):
-        """The inverse of `public` for a caller that knows which options were on."""
-        rest = iter(public)          # (the fields stand in the tuple's order: the pass block is the last of both)
-        out = cls(*(next(rest) if on else None for on in (True, True, distmap, distmap, score, align, search, score_map, passes)))
-        return out._with(next(rest) if ss else None, next(rest) if exposure else None)
+        """The inverse of `public` for a caller that knows which options were on (the keywords stand in HANDOUT's order)."""
+        rest = iter(public)
+        return cls(*(next(rest) if on else None
+                     for on in (True, True, distmap, distmap, score, align, search, score_map, passes, ss, exposure)))
 
     def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True, ss=True,
                exposure=True):
@@ -263,12 +246,12 @@ class Outputs(_Beside, namedtuple("Outputs", "coords confs distmap info score_bl
         block, the align block, the search block and - though they lie behind the score block in the buffer - the map-score
         block, the pass block, the SS block and, last of all, the exposure block, each if present and wanted.  `blocks=False`:
         none of the seven blocks, whatever else is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
-        if not blocks:
-            score = align = search = score_map = passes = ss = exposure = False
-        groups = ((distmap, (self.distmap, self.info)), (score, (self.score_block,)), (align, (self.align_block,)),
-                  (search, (self.search_block,)), (score_map, (self.map_block,)), (passes, (self.pass_block,)),
-                  (ss, (self.ss_block,)), (exposure, (self.exposure_block,)))
-        return (self.coords, self.confs) + tuple(x for want, group in groups if want and group[0] is not None for x in group)
+        wanted = (score, align, search, score_map, passes, ss, exposure)
+        return (self[:2] + (self[2:4] if distmap and self.distmap is not None else ())
+                + tuple(block for block, want in zip(self[4:], wanted) if blocks and want and block is not None))
+
+
+HANDOUT = Outputs._fields[4:]        # the blocks, by field, in the order `public` hands them out and `of` takes them
 
 
 def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None, search=None, score_map=False):
@@ -992,3 +975,48 @@ def hits_json(search, names, top=10):
                     "rmsd_ali": _num(h["rmsd_ali"]), "n_ali": int(h["n_ali"]),
                     "R": [[_num(v) for v in row] for row in np.asarray(h["R"])], "t": [_num(v) for v in np.asarray(h["t"])]})
     return {"entries": len(names), "hits": out}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The blocks behind the confidences, each stated once.  A row of BLOCKS: `key` - what the host calls the block (a keyword of
+# Outputs.public and Outputs.of, of a Pipeline's set_<key>); `option` - the library option that turns it on; `field` - its view
+# in an `Outputs`; `name` - what its unpacked form is called wherever it is handed on (a property of predict.Engine, a field of
+# predict.Prediction, a keyword of batch.write_result); `arg` - the field of a `Layout` that holds what sizes it (None or False
+# = the block is off); `shape` - its floats in words; `floats`(L, that value); `unpack`(block, L, library=, seq=) - the block as a
+# dict, each taking of the keywords what it needs; `json`(that dict, top=) - its JSON form.
+# BLOCKS stands in the BUFFER's order, conf_layout()'s in csrc/common.h; HANDOUT is the order in which Outputs.public hands the
+# blocks out and an `Outputs` holds them.  A new tail option on the host is one row here, its unpacker and its place in HANDOUT.
+# ---------------------------------------------------------------------------------------------------------------------
+Block = namedtuple("Block", "key option field name arg shape floats unpack json")
+
+
+def _of_length(unpack):
+    """An unpacker of (block, L) as a row's `unpack`."""
+    return lambda block, L, **_: unpack(block, L)
+
+
+def _form(to_json):
+    """A JSON form of the unpacked dict alone as a row's `json`."""
+    return lambda unpacked, **_: to_json(unpacked)
+
+
+BLOCKS = (
+    Block("score", "score_native", "score_block", "scores", "score", "5L + 24",
+          lambda L, on: score_floats(L), _of_length(unpack_scores), _form(scores_json)),
+    Block("score_map", "score_map", "map_block", "map_scores", "score_map", "64 + L",
+          lambda L, on: mapscore_floats(L), _of_length(unpack_map_scores), _form(map_scores_json)),
+    Block("passes", "score_passes", "pass_block", "pass_scores", "passes", "16 + 8R",
+          lambda L, R: pass_floats(R), lambda block, L, **_: unpack_pass_scores(block, (block.shape[0] - PASS_HEADER) // PASS_ROW),
+          _form(pass_scores_json)),
+    Block("ss", "assign_ss", "ss_block", "ss", "ss", "32 + 8L",
+          lambda L, on: ss_floats(L), _of_length(unpack_ss), _form(ss_json)),
+    Block("exposure", "exposure", "exposure_block", "exposure", "exposure", "32 + 16L",
+          lambda L, on: exposure_floats(L), lambda block, L, seq=None, **_: unpack_exposure(block, L, seq=seq), _form(exposure_json)),
+    Block("align", "align_structure", "align_block", "alignment", "align_m", "25 + 2L + 3m",
+          align_floats, _of_length(unpack_alignment), _form(alignment_json)),
+    Block("search", "search_structures", "search_block", "hits", "search", "26K + 2LK + 3M",
+          lambda L, KM: search_floats(L, *KM),
+          lambda block, L, library=None, **_: dict(unpack_search(block, L, library.lengths), names=list(library.names)),
+          lambda hits, top=10, **_: hits_json(hits, hits["names"], top)),
+)
+BLOCK = {row.key: row for row in BLOCKS}

@@ -155,7 +155,7 @@ def test_layout_off_is_todays_and_on_moves_what_lies_behind(L):
     for row in GRID:
         off, on = _lay(L, *row), _lay(L, *row, exposure=True)
         assert off.exposure is False and on.exposure is True and off != on and off == _lay(L, *row, exposure=False)
-        assert tuple(off) == tuple(on) and len(off) == 8 and off.ss == on.ss == row[-1]
+        assert S.Layout._fields == ("L", "distmap", "score", "score_map", "align_m", "search", "max_L", "passes", "ss", "exposure") and off.ss == on.ss == row[-1]
         # off: the grid of tests/test_ss_cpu.py, stated again from the lengths of the blocks
         assert off.exposure_off == off.align_off == off.ss_off + (S.ss_floats(L) if row[-1] else 0)
         for name in names:
@@ -167,7 +167,7 @@ def test_layout_off_is_todays_and_on_moves_what_lies_behind(L):
         got, base = on.split(buf), off.split(buf[:off.total])
         assert base.exposure_block is None and got.exposure_block.shape == (32 + 16 * L,) and got.exposure_block[0] == on.exposure_off
         assert (got.ss_block is None) == (not row[-1]) and (got.ss_block is None or got.ss_block.shape == (32 + 8 * L,))
-        for f in S.Outputs._fields + ("ss_block",):
+        for f in S.Outputs._fields[:10]:            # (every part but the exposure block)
             a, b = getattr(got, f), getattr(base, f)
             assert (a is None) == (b is None)
             if a is not None and f != "coords":
@@ -177,10 +177,12 @@ def test_layout_off_is_todays_and_on_moves_what_lies_behind(L):
 
 
 def test_outputs_carry_both_blocks_beside_the_tuple():
-    parts = {name: object() for name in S.Outputs._fields}
+    parts = {name: object() for name in S.Outputs._fields[:9]}
     ss, ex = object(), object()
     out = S.Outputs(**parts, ss_block=ss, exposure_block=ex)
-    assert len(out) == 9 and S.Outputs(**parts).exposure_block is None and S.Outputs(**parts, ss_block=ss).exposure_block is None
+    assert S.Outputs._fields == ("coords", "confs", "distmap", "info", "score_block", "align_block", "search_block", "map_block", "pass_block",
+                                "ss_block", "exposure_block")
+    assert S.Outputs(**parts).exposure_block is None and S.Outputs(**parts, ss_block=ss).exposure_block is None
     pub = out.public()
     assert len(pub) == 11 and pub[-2] is ss and pub[-1] is ex and out.public(exposure=False) == pub[:-1]
     assert out.public(ss=False)[-1] is ex and out.public(blocks=False) == pub[:4]
@@ -243,7 +245,7 @@ def test_unpack_and_json_round_trip(fgx):
 def test_extras_default_and_front_end_arguments():
     from dmpfold2_amd import batch, _lib
     from dmpfold2_amd.predict import dmpfold_parser, Extras, Flags, Prediction, agree_ss
-    assert Extras().exposure is False and Extras(exposure=True).exposure is True and len(Extras()) == 6
+    assert Extras().exposure is False and Extras(exposure=True).exposure is True and Extras._fields == ("distmap", "native", "structure", "library", "score_map", "score_passes", "ss", "exposure")
     assert Extras(exposure=True).ss is False and Extras(ss=True, exposure=True)._replace(distmap=True).exposure is True
     assert Extras(True)._replace(exposure=True).exposure is True and Extras(ss=True)._replace(exposure=True).ss is True
     assert Extras(exposure=True) != Extras() and Extras(exposure=True) == Extras(exposure=True)

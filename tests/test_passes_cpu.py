@@ -29,8 +29,9 @@ def _views(out, fields):
 def test_layout_positional_order_is_unchanged():
     lay = S.Layout(82.0, 1, 1, 0, 61)
     assert lay[:7] == (82, True, True, False, 61, None, None) and lay.passes is None
-    assert S.Layout._fields == ("L", "distmap", "score", "score_map", "align_m", "search", "max_L", "passes")
-    assert S.Outputs._fields[-1] == "pass_block" and S.Outputs._fields[-2] == "map_block"
+    assert S.Layout._fields == ("L", "distmap", "score", "score_map", "align_m", "search", "max_L", "passes", "ss", "exposure")
+    assert S.Outputs._fields == ("coords", "confs", "distmap", "info", "score_block", "align_block", "search_block", "map_block", "pass_block",
+                                 "ss_block", "exposure_block")
     assert S.pass_floats(1) == 24 and S.pass_floats(128) == 16 + 8 * 128
     assert [S.pass_rows(n) for n in (-3, 0, 10, 127, 128, 5000)] == [1, 1, 11, 128, 128, 128]
 
@@ -91,7 +92,7 @@ def test_with_passes_everything_behind_the_block_moves_by_its_size(L, R):
 
 
 def test_public_puts_the_pass_block_last():
-    parts = {name: object() for name in S.Outputs._fields}
+    parts = {name: object() for name in S.Outputs._fields[:9]}          # (of the blocks of its day)
     out = S.Outputs(**parts)
     pub = out.public()
     assert pub[-1] is out.pass_block and pub[-2] is out.map_block and len(pub) == 9
@@ -278,7 +279,7 @@ def test_the_flags_exist_and_need_a_native():
     assert batch.batch_parser().parse_args(["-o", "out", "--natives", "d", "--score-passes"]).score_passes is True
     with pytest.raises(ValueError):
         batch.run_batch([], "out", score_passes=True)
-    assert Extras._fields[-1] == "score_passes" and Extras().score_passes is False
+    assert Extras._fields == ("distmap", "native", "structure", "library", "score_map", "score_passes", "ss", "exposure") and Extras().score_passes is False
     assert agree_passes([0, 0], True, 10) is None and agree_passes([1, 1], True, 10) == 11 and agree_passes([1], True, 500) == 128
     for bad in ([1, 0], [0, 1]):
         with pytest.raises(RuntimeError):

@@ -260,7 +260,7 @@ def test_layout_off_is_todays_and_on_moves_what_lies_behind(L):
     for row in GRID:
         off, on = _lay(L, *row), _lay(L, *row, ss=True)
         assert off.ss is False and off == _lay(L, *row, ss=False) and off != on and on.ss is True
-        assert off.ss_off == off.align_off and tuple(off) == tuple(on) and len(off) == 8
+        assert off.ss_off == off.align_off and S.Layout._fields == ("L", "distmap", "score", "score_map", "align_m", "search", "max_L", "passes", "ss", "exposure")
         for name in names:
             moved = 32 + 8 * L if name in ("align_off", "align_end", "search_off", "search_end", "total") else 0
             assert getattr(on, name) - getattr(off, name) == moved, (row, name)
@@ -270,7 +270,7 @@ def test_layout_off_is_todays_and_on_moves_what_lies_behind(L):
         got, base = on.split(buf), off.split(buf[:off.total])
         assert base.ss_block is None and got.ss_block.shape == (32 + 8 * L,) and got.ss_block[0] == on.ss_off
         assert np.array_equal(on.ss_block(buf), got.ss_block) and off.ss_block(buf) is None
-        for f in S.Outputs._fields:
+        for f in S.Outputs._fields[:9]:             # (every part but the two late blocks)
             a, b = getattr(got, f), getattr(base, f)
             assert (a is None) == (b is None)
             if a is not None and f not in ("coords",):
@@ -280,10 +280,12 @@ def test_layout_off_is_todays_and_on_moves_what_lies_behind(L):
 
 
 def test_outputs_carry_the_block_beside_the_tuple():
-    parts = {name: object() for name in S.Outputs._fields}
+    parts = {name: object() for name in S.Outputs._fields[:9]}
     block = object()
     out = S.Outputs(**parts, ss_block=block)
-    assert len(out) == 9 and S.Outputs(**parts).ss_block is None
+    assert S.Outputs._fields == ("coords", "confs", "distmap", "info", "score_block", "align_block", "search_block", "map_block", "pass_block",
+                                "ss_block", "exposure_block")
+    assert S.Outputs(**parts).ss_block is None
     pub = out.public()
     assert len(pub) == 10 and pub[-1] is block and out.public(ss=False) == pub[:-1] == S.Outputs(**parts).public()
     assert out.public(blocks=False) == pub[:4]
@@ -323,7 +325,7 @@ def test_unpack_and_json_round_trip():
 def test_extras_default_and_front_end_arguments():
     from dmpfold2_amd import batch, _lib
     from dmpfold2_amd.predict import dmpfold_parser, Extras
-    assert Extras().ss is False and Extras(ss=True).ss is True and len(Extras()) == 6
+    assert Extras().ss is False and Extras(ss=True).ss is True and Extras._fields == ("distmap", "native", "structure", "library", "score_map", "score_passes", "ss", "exposure")
     assert Extras(ss=True)._replace(distmap=True).ss is True and Extras(True)._replace(ss=True).ss is True
     args = dmpfold_parser().parse_args(["-i", "x.aln", "--ss", "--ss-file", "x.json"])
     assert args.ss is True and args.ss_file == "x.json"
