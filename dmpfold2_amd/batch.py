@@ -242,6 +242,8 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
                           "hit_tm_model": np.asarray([h["tm_model"] for h in hits["hits"]], dtype=np.float32),
                           "hit_tm_struct": np.asarray([h["tm_struct"] for h in hits["hits"]], dtype=np.float32),
                           "hit_names": np.asarray(hits["names"], dtype=np.str_)})
+            if "refined" in hits:                        # (--search-refine)
+                extra["hit_refined"] = np.asarray(hits["refined"], dtype=np.bool_)
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
@@ -324,7 +326,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     {stem: the header fields of score.alignment_json}.
     `library`: a fold library (a score.Library, a directory of PDB files or an .npz of tools/make_library.py): every
     target's model is aligned with every entry on the GPU (Pipeline.set_search) and the ranking is written with it
-    (write_result); `stats_out` then receives "hits": {stem: the best `search_top` of score.hits_json, without R and t}.
+    (write_result); `stats_out` then receives "hits": {stem: the best `search_top` of score.hits_json, without R and t}.  A
+    library with a `refine` of R is screened and only the best R entries refined (option "search_refine"); the hits then say which.
     `restrain` (force constant K, None or 0 = off) and `restrain_cutoff` (Angstrom): every target's final refinement is
     restrained to its predicted distance map (Pipeline.set_restrain, which turns the distance map on: it is written only with
     `distmap`); every target's report (predict.restrain_report) is written with it (write_result) and `stats_out` receives
@@ -624,6 +627,10 @@ def batch_parser():
                          "target's top hits; npz gains hit_rank, hit_tm_model, hit_tm_struct and hit_names, pdb / ca write "
                          "<stem>.hits.json")
     ap.add_argument("--search-top", type=int, default=10, metavar="N", help="hits per target to report with --library (default 10)")
+    # --search-refine R (with --library): screen every entry by its best gapless threading and refine only the best R by that;
+    # the hits gain "refined", npz gains hit_refined.  The help text and the parsed namespace of the other flags are recorded
+    # (tests/golden/host_plumbing.json.gz): the flag stays out of both unless given, and README.md describes it.
+    ap.add_argument("--search-refine", type=int, default=argparse.SUPPRESS, metavar="R", help=argparse.SUPPRESS)
     ap.add_argument("--ss", action="store_true",
                     help="assign secondary structure to every target's backbone on the GPU from its hydrogen bonds; the summary "
                          "gains every target's eight-state string and helix / strand / coil fractions with their means and "
@@ -769,6 +776,14 @@ def main(argv=None):
         if getattr(args, option) and not args.natives:
             ap.error(needs_native(option, "--" + option.replace("_", "-"), "--natives DIR", many=True))
 
+    library = args.library
+    if hasattr(args, "search_refine"):
+        if not args.library:
+            ap.error("--search-refine needs --library")
+        if not 0 <= args.search_refine <= _score.SEARCH_MAX:
+            ap.error(f"--search-refine must be 0 or 1 .. {_score.SEARCH_MAX}, got {args.search_refine}")
+        library = _score.Library.open(args.library, refine=args.search_refine)
+
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -791,7 +806,7 @@ def main(argv=None):
                                   weights_file=args.model_weights, streams=args.streams,
                                   device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
                                   converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
-                                  structures=args.structures, library=args.library, search_top=args.search_top,
+                                  structures=args.structures, library=library, search_top=args.search_top,
                                   score_map=args.score_map, score_passes=args.score_passes, ss=args.ss,
                                   restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary

@@ -11,6 +11,8 @@
 //                 repeats; the last arriver picks the winner and writes the header, ali and the deviations.
 // Option "search_structures" runs the same three stages over the K entries of a library, the entry as blockIdx.y, in chunks of
 // as many entries as the scratch budget holds, between search_prep (lengths validated, trace offsets, NaN fill) and search_rank.
+// Option "search_refine" = R makes that two passes: stage 1 and align_screen over every entry, search_select, the three stages
+// over the R entries chosen.
 // Float64 from the float32 coordinates, contraction off, every sum in the fixed order of score_block_sum; every candidate
 // of a DP cell is one float64 add of two defined values, so H does not depend on the order the cells are evaluated in.
 // Every loop is bounded whatever the input holds, and every branch with a barrier inside is uniform over the workgroup.
@@ -194,15 +196,62 @@ __host__ __device__ inline AlignLds align_lds(int L, int max_m) {
   return {h, h + un, h + un + 3 * 2 * L * 2};
 }
 
-// n packed pairs from a list into pm2 / qn2, the flags set: the start of a superposition
-__device__ inline void align_pack(const AlignArgs& a, const unsigned short* li, const unsigned short* lj, int K, float* pm2,
-                                  float* qn2, unsigned char* fl) {
+// K packed pairs (pi(t), pj(t)) into pm2 / qn2, the flags set: the start of a superposition
+template <class PairI, class PairJ>
+__device__ inline void align_pack(const AlignArgs& a, PairI pi, PairJ pj, int K, float* pm2, float* qn2, unsigned char* fl) {
   for (int t = threadIdx.x; t < K; t += SC_THREADS) {
-    const int i = li[t], j = lj[t];
+    const int i = pi(t), j = pj(t);
     for (int c = 0; c < 3; ++c) { pm2[3 * t + c] = a.pm[3 * i + c]; qn2[3 * t + c] = a.qs[3 * j + c]; }
     fl[t] = 1;
   }
   __syncthreads();
+}
+
+// The outputs of one alignment - wK pairs (pi(t), pj(t)) that grew from seed number `seed` - by the final formulae of the header
+// file: the two superpositions, the header, ali and the deviations.  The one definition of align_refine's winner and of a
+// screened entry's gapless alignment (`screened`: offset 21 of the header, 1 = "screened, not refined").  The whole workgroup
+// calls it; pm2 / qn2 / fl hold 3 wK, 3 wK floats and wK flags.
+template <class PairI, class PairJ>
+__device__ __forceinline__ void align_finish(const AlignArgs& a, PairI pi, PairJ pj, int wK, int seed, float screened, int n, int m,
+                                             int minov, double d_cut, float* pm2, float* qn2, unsigned char* fl,
+                                             double (*wred)[16], double* bc) {
+  const int tid = threadIdx.x, L = a.L;
+  const double d0n = score_d0((double)n), d0m = score_d0((double)m);
+  align_pack(a, pi, pj, wK, pm2, qn2, fl);
+  SeedBest bn;
+  score_seed_loop(pm2, qn2, fl, wK, (double)n, d0n, d_cut, wred, bc, bn);
+  __syncthreads();
+  for (int t = tid; t < wK; t += SC_THREADS) fl[t] = 1;
+  __syncthreads();
+  SeedBest bm;
+  score_seed_loop(pm2, qn2, fl, wK, (double)m, d0m, d_cut, wred, bc, bm);
+  if (tid == 0) {
+    float* out = a.out - 1;                                  // out[c]: offset c of an align block
+    int k, i0, ov;
+    align_seed(seed, n, m, minov, k, i0, ov);
+    out[1] = (float)wK;
+    out[2] = (float)bn.rmsd;
+    out[3] = (float)bn.tm;
+    out[4] = (float)bm.tm;
+    for (int c = 0; c < 9; ++c) { out[5 + c] = (float)bm.R[c]; bc[c] = bm.R[c]; }
+    for (int c = 0; c < 3; ++c) { out[14 + c] = (float)bm.t[c]; bc[9 + c] = bm.t[c]; }
+    out[17] = (float)d0n;
+    out[18] = (float)d0m;
+    out[19] = (float)k;
+    out[20] = (float)a.hdr[AH_SEEDS];
+    out[21] = screened;
+    for (int c = 22; c < ALIGN_HEADER + 1; ++c) out[c] = 0.f;
+  }
+  for (int i = tid; i < L; i += SC_THREADS) a.ali[i] = -1.f;      // (the deviations of these rows stay NaN)
+  __syncthreads();
+  double R[9], tr[3];
+  for (int c = 0; c < 9; ++c) R[c] = bc[c];
+  for (int c = 0; c < 3; ++c) tr[c] = bc[9 + c];
+  for (int t = tid; t < wK; t += SC_THREADS) {
+    const int i = pi(t);
+    a.ali[i] = (float)pj(t);
+    a.ali[L + i] = (float)score_dev(R, tr, pm2 + 3 * t, qn2 + 3 * t);
+  }
 }
 
 __device__ __forceinline__ void align_refine_body(const AlignArgs& a) {
@@ -239,7 +288,10 @@ __device__ __forceinline__ void align_refine_body(const AlignArgs& a) {
   double best_tm = -1.0;                                     // thread 0
 
   for (int round = 0; round < AL_ROUNDS; ++round) {
-    align_pack(a, ci + coff, cj + coff, K, pm2, qn2, fl);
+    {
+      const unsigned short *li = ci + coff, *lj = cj + coff;
+      align_pack(a, [li](int t) { return (int)li[t]; }, [lj](int t) { return (int)lj[t]; }, K, pm2, qn2, fl);
+    }
     SeedBest sb;
     score_seed_loop(pm2, qn2, fl, K, lmin, d0s, d_cut, wred, bc, sb);
     if (tid == 0) {
@@ -374,41 +426,30 @@ __device__ __forceinline__ void align_refine_body(const AlignArgs& a) {
     cj[t] = (unsigned short)agent_load_i32(wrec + 2 + 2 * t);
   }
   __syncthreads();
-  const double d0n = score_d0((double)n), d0m = score_d0((double)m);
-  align_pack(a, ci, cj, wK, pm2, qn2, fl);
-  SeedBest bn;
-  score_seed_loop(pm2, qn2, fl, wK, (double)n, d0n, d_cut, wred, bc, bn);
-  __syncthreads();
-  for (int t = tid; t < wK; t += SC_THREADS) fl[t] = 1;
-  __syncthreads();
-  SeedBest bm;
-  score_seed_loop(pm2, qn2, fl, wK, (double)m, d0m, d_cut, wred, bc, bm);
-  if (tid == 0) {
-    float* out = a.out - 1;                                  // out[c]: offset c of an align block
-    int k, i0, ov;
-    align_seed(a.surv[1 + win], n, m, minov, k, i0, ov);
-    out[1] = (float)wK;
-    out[2] = (float)bn.rmsd;
-    out[3] = (float)bn.tm;
-    out[4] = (float)bm.tm;
-    for (int c = 0; c < 9; ++c) { out[5 + c] = (float)bm.R[c]; bc[c] = bm.R[c]; }
-    for (int c = 0; c < 3; ++c) { out[14 + c] = (float)bm.t[c]; bc[9 + c] = bm.t[c]; }
-    out[17] = (float)d0n;
-    out[18] = (float)d0m;
-    out[19] = (float)k;
-    out[20] = (float)a.hdr[AH_SEEDS];
-    for (int c = 21; c < ALIGN_HEADER + 1; ++c) out[c] = 0.f;
-  }
-  for (int i = tid; i < L; i += SC_THREADS) a.ali[i] = -1.f;      // (the deviations of these rows stay NaN)
-  __syncthreads();
-  double R[9], tr[3];
-  for (int c = 0; c < 9; ++c) R[c] = bc[c];
-  for (int c = 0; c < 3; ++c) tr[c] = bc[9 + c];
-  for (int t = tid; t < wK; t += SC_THREADS) {
-    const int i = ci[t];
-    a.ali[i] = (float)cj[t];
-    a.ali[L + i] = (float)score_dev(R, tr, pm2 + 3 * t, qn2 + 3 * t);
-  }
+  align_finish(a, [ci](int t) { return (int)ci[t]; }, [cj](int t) { return (int)cj[t]; }, wK, a.surv[1 + win], 0.f, n, m, minov,
+               d_cut, pm2, qn2, fl, wred, bc);
+}
+
+// ---------------------------------------------------------------------------------------
+// align_screen: option "search_refine", one workgroup per entry - stage 1's best seed as the entry's answer
+// ---------------------------------------------------------------------------------------
+// The rank-0 survivor of align_thread (the best seed; ties went to the lower seed number) is a gapless alignment A*: the
+// entry's header, ali and deviations by align_finish on A*, offset 21 = 1.  Nothing is written for an invalid entry or one
+// without a survivor: its out slots stay NaN.  Dynamic LDS as align_thread's: 6 L floats, L flags.
+__device__ __forceinline__ void align_screen_body(const AlignArgs& a) {
+  extern __shared__ float sm[];
+  __shared__ double wred[SC_WAVES][16];
+  __shared__ double bc[12];
+  const int L = a.L;
+  if (a.hdr[AH_VALID] == 0.0) return;
+  if (a.surv[0] < 1) return;
+  const int n = (int)a.hdr[AH_N], m = (int)a.hdr[AH_M], minov = (int)a.hdr[AH_MINOV];
+  const int seed = a.surv[1];
+  int k, i0, ov;
+  align_seed(seed, n, m, minov, k, i0, ov);
+  if (ov < 3 || ov > L || i0 < 0 || i0 + ov > n || i0 + k < 0 || i0 + k + ov > m) return;      // never: a seed of align_thread
+  align_finish(a, [i0](int t) { return i0 + t; }, [i0, k](int t) { return i0 + k + t; }, ov, seed, 1.f, n, m, minov, a.hdr[AH_DCUT],
+               sm, sm + 3 * L, reinterpret_cast<unsigned char*>(sm + 6 * L), wred, bc);
 }
 
 // the single-partner launches of option "align_structure"
@@ -431,15 +472,24 @@ struct SearchArgs {
   unsigned char* ws;     // the scratch: table, tickets, slots (common.h)
   SearchSlot slot;
   const int* fault;      // the fault word of the prediction in flight
+  const int* sel;        // option "search_refine": slot y of a chunk holds entry sel[first + y] of the nsel selected; null: entry first + y
+  int nsel, refine;      // refine: R, the entries search_select chooses
 };
 
 __device__ __forceinline__ int64_t* search_tab(const SearchArgs& sa) { return reinterpret_cast<int64_t*>(sa.ws); }
+// option "search_refine": the screened tm_model of every entry, and the R entries chosen from it in rank order
+__device__ __forceinline__ float* search_screen_tm(const SearchArgs& sa) { return reinterpret_cast<float*>(sa.ws + SEARCH_SCREEN_OFF); }
+__device__ __forceinline__ int* search_sel(const SearchArgs& sa) { return reinterpret_cast<int*>(sa.ws + SEARCH_SEL_OFF); }
 
-// Entry k = first + blockIdx.y in slot blockIdx.y.  False (uniform over the workgroup) for an index that is no entry.  With
-// an invalid m_k somewhere the table says so: the entry then reads as m = 0 and nothing of its trace is touched.
-__device__ __forceinline__ bool search_entry(const SearchArgs& sa, int first, AlignArgs& a) {
-  const int y = (int)blockIdx.y, k = first + y;
-  if (y >= SEARCH_CHUNK_MAX || k < 0 || k >= sa.K) return false;
+// Entry k = first + blockIdx.y - through `sel`, if there is one - in slot blockIdx.y.  False (uniform over the workgroup) for
+// an index that is no entry.  With an invalid m_k somewhere the table says so: the entry then reads as m = 0 and nothing of
+// its trace is touched.
+__device__ __forceinline__ bool search_entry(const SearchArgs& sa, int first, AlignArgs& a, int* entry = nullptr) {
+  const int y = (int)blockIdx.y, at = first + y;
+  if (y >= SEARCH_CHUNK_MAX || at < 0 || at >= (sa.sel ? sa.nsel : sa.K)) return false;
+  const int k = sa.sel ? sa.sel[at] : at;
+  if (k < 0 || k >= sa.K) return false;                      // never: search_select writes entries
+  if (entry) *entry = k;
   const int64_t* tab = search_tab(sa);
   const bool ok = tab[0] == 1;
   float* b = sa.conf + tab[1];
@@ -465,6 +515,15 @@ __global__ __launch_bounds__(SC_THREADS) void align_thread_batch_kernel(SearchAr
 __global__ __launch_bounds__(SC_THREADS) void align_refine_batch_kernel(SearchArgs sa, int first) {
   AlignArgs a;
   if (search_entry(sa, first, a)) align_refine_body(a);
+}
+
+// the screen pass of option "search_refine": the entry's answer from its best seed, its tm_model (NaN: no result) in the table
+__global__ __launch_bounds__(SC_THREADS) void align_screen_batch_kernel(SearchArgs sa, int first) {
+  AlignArgs a;
+  int k;
+  if (!search_entry(sa, first, a, &k)) return;
+  align_screen_body(a);
+  if (threadIdx.x == 0) search_screen_tm(sa)[k] = a.out[2];      // what this thread wrote, or align_prep's NaN
 }
 
 // search_prep, one workgroup: B0 by the rule of common.h; every m_k an integer in [3, max_m]?; the rows in front of each
@@ -522,6 +581,39 @@ __global__ __launch_bounds__(SC_THREADS) void search_prep_kernel(SearchArgs sa) 
   for (int64_t i = lay.rank + tid; i < lay.in; i += SC_THREADS) b[i] = nan;
 }
 
+// The ranking rule: entry j (value u) stands in front of entry k (value v) - a larger value, or an equal one of a lower index;
+// the NaN entries last, in index order.
+__device__ __forceinline__ bool search_before(float u, int j, float v, int k) {
+  const bool unan = u != u, vnan = v != v;
+  return vnan ? (!unan || j < k) : (!unan && (u > v || (u == v && j < k)));
+}
+// entry k's place among the K values of tm
+__device__ __forceinline__ int search_place(const float* tm, int K, int k) {
+  const float v = tm[k];
+  int pos = 0;
+  for (int j = 0; j < K; ++j) pos += search_before(tm[j], j, v, k) ? 1 : 0;
+  return pos;
+}
+
+// search_select, one workgroup (option "search_refine"): sel[r] = the entry with the r-th largest screened tm_model, r < R, by
+// the rule of search_rank.  With an invalid m_k somewhere nothing was screened: the identity (those entries return early).
+__global__ __launch_bounds__(SC_THREADS) void search_select_kernel(SearchArgs sa) {
+  __shared__ float tm[SEARCH_MAX];
+  const int tid = threadIdx.x, K = sa.K, R = sa.refine < K ? sa.refine : K;
+  int* sel = search_sel(sa);
+  if (search_tab(sa)[0] != 1) {                              // uniform
+    for (int r = tid; r < R; r += SC_THREADS) sel[r] = r;
+    return;
+  }
+  const float* screen = search_screen_tm(sa);
+  for (int k = tid; k < K; k += SC_THREADS) tm[k] = screen[k];
+  __syncthreads();
+  for (int k = tid; k < K; k += SC_THREADS) {
+    const int pos = search_place(tm, K, k);
+    if (pos < R) sel[pos] = k;                               // a permutation: every r < R is written once
+  }
+}
+
 // search_rank, one workgroup: rank[r] = the entry with the r-th largest tm_model, by counting - entry k comes behind every
 // entry with a larger value and every equal one of a lower index; the NaN entries last, in index order.  A prediction that
 // latched a fault gets NaN in every out slot instead (the fault latch of api.hip does not know B0).
@@ -539,15 +631,7 @@ __global__ __launch_bounds__(SC_THREADS) void search_rank_kernel(SearchArgs sa) 
   for (int k = tid; k < K; k += SC_THREADS) tm[k] = b[lay.hdr + (int64_t)ALIGN_HEADER * k + 2];
   __syncthreads();
   for (int k = tid; k < K; k += SC_THREADS) {
-    const float v = tm[k];
-    const bool vnan = v != v;
-    int pos = 0;
-    for (int j = 0; j < K; ++j) {
-      const float u = tm[j];
-      const bool unan = u != u;
-      const bool before = vnan ? (!unan || j < k) : (!unan && (u > v || (u == v && j < k)));
-      pos += before ? 1 : 0;
-    }
+    const int pos = search_place(tm, K, k);
     if (pos < K) b[lay.rank + pos] = (float)k;               // a permutation: always
   }
 }
@@ -594,8 +678,9 @@ int search_wg_per_cu(int L, int max_m, int* out) {
   return DMP_OK;
 }
 
-// search_prep, then the three stages per chunk of C consecutive entries (one slot each), then search_rank.  Everything is
-// sized from (L, max_m) here; no length comes back from the device.
+// search_prep, then the three stages per chunk of C consecutive entries (one slot each), then search_rank.  With option
+// "search_refine" = R, 0 < R < K: stage 1 and align_screen per chunk over all K, search_select, then the three stages per
+// chunk over the R selected entries.  Everything is sized from (L, max_m, K, R) here; nothing comes back from the device.
 int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
   SearchArgs sa{};
   sa.coords = d_coords;
@@ -617,12 +702,30 @@ int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, c
   c->search_last_C = C;
   hipLaunchKernelGGL(search_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
   DMP_LAUNCH_CHECK();
-  for (int first = 0; first < sa.K; first += C) {
-    const int cn = std::min(C, sa.K - first);
+  const size_t thread_lds = sizeof(float) * 6 * L + round_up(L, 16);
+  const int R = c->run.search_refine > 0 && c->run.search_refine < sa.K ? c->run.search_refine : 0;
+  if (R) {
+    sa.refine = R;
+    for (int first = 0; first < sa.K; first += C) {
+      const int cn = std::min(C, sa.K - first);
+      hipLaunchKernelGGL(align_prep_batch_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, sa, first);
+      DMP_LAUNCH_CHECK();
+      hipLaunchKernelGGL(align_thread_batch_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, sa, first);
+      DMP_LAUNCH_CHECK();
+      hipLaunchKernelGGL(align_screen_batch_kernel, dim3(1, cn), dim3(SC_THREADS), thread_lds, s, sa, first);
+      DMP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(search_select_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
+    DMP_LAUNCH_CHECK();
+    sa.sel = reinterpret_cast<const int*>(sa.ws + SEARCH_SEL_OFF);
+    sa.nsel = R;
+  }
+  const int todo = R ? R : sa.K;                             // the entries refined: slot y of a chunk holds entry (sel[)first + y(])
+  for (int first = 0; first < todo; first += C) {
+    const int cn = std::min(C, todo - first);
     hipLaunchKernelGGL(align_prep_batch_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, sa, first);
     DMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(align_thread_batch_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS),
-                       sizeof(float) * 6 * L + round_up(L, 16), s, sa, first);
+    hipLaunchKernelGGL(align_thread_batch_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, sa, first);
     DMP_LAUNCH_CHECK();
     hipLaunchKernelGGL(align_refine_batch_kernel, dim3(AL_T, cn), dim3(SC_THREADS), align_lds(L, sa.max_m).total, s, sa, first);
     DMP_LAUNCH_CHECK();

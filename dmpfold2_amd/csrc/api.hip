@@ -571,6 +571,7 @@ static const Option OPTIONS[] = {
      nullptr, nullptr, search_reserve},
     {"search_max_m", TAIL(search_mm), ANY, OPT_RW, check_search_max_m, nullptr, search_reserve},
     {"search_chunk", TAIL(search_chunk), 0, INT32_MAX, 0, "search_chunk must be >= 0, got %d"},                // tests only: entries per chunk, 0 = what the budget gives
+    {"search_refine", TAIL(search_refine), 0, DMP_SEARCH_MAX, 0, "search_refine must be 0 or 1 .. " DMP_STR(DMP_SEARCH_MAX) ", got %d"},   // refine the best R by the screen only
     {"passes_run", CTX(passes_done), ANY, OPT_READ_ONLY},                                   // trunk passes of the last prediction
     {"search_chunk_used", CTX(search_last_C), ANY, OPT_READ_ONLY},                          // of the last prediction that searched: entries per chunk
     {"search_wg_per_cu", nullptr, nullptr, ANY, OPT_READ_ONLY, nullptr, nullptr, nullptr, get_search_wg_per_cu},

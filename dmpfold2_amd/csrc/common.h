@@ -10,8 +10,8 @@
 #include "../../include/dmpfold_hip.h"
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0; };
+// "search_refine", "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, search_refine = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0; };
 
 namespace dmp {
 
@@ -155,10 +155,12 @@ __host__ __device__ inline SearchSlot search_slot(int L, int max_m) {
   return s;
 }
 // in front of the slots: the table search_prep writes ([0] every m_k valid, [1] B0, [2 + k] rows in front of entry k), then
-// two tickets per slot (zero between launches, at a place that does not depend on L)
+// two tickets per slot (zero between launches, at a place that does not depend on L), then the two tables of option
+// "search_refine": every entry's screened tm_model (floats), and the entries chosen for the refinement in rank order (ints)
 constexpr int SEARCH_MAX = DMP_SEARCH_MAX, SEARCH_CHUNK_MAX = 256;
 constexpr int64_t SEARCH_BUDGET = (int64_t)DMP_SEARCH_BUDGET_MIB << 20;
-constexpr int64_t SEARCH_TAB_BYTES = 8 * (2 + (int64_t)SEARCH_MAX), SEARCH_HEAD_BYTES = SEARCH_TAB_BYTES + 4 * 2 * SEARCH_CHUNK_MAX;
+constexpr int64_t SEARCH_TAB_BYTES = 8 * (2 + (int64_t)SEARCH_MAX), SEARCH_SCREEN_OFF = SEARCH_TAB_BYTES + 4 * 2 * SEARCH_CHUNK_MAX,
+                  SEARCH_SEL_OFF = SEARCH_SCREEN_OFF + 4 * (int64_t)SEARCH_MAX, SEARCH_HEAD_BYTES = SEARCH_SEL_OFF + 4 * (int64_t)SEARCH_MAX;
 // entries per chunk: as many slots as the budget holds, 1 .. 256; `cap` > 0 (option "search_chunk") lowers it
 inline int search_chunk_entries(int L, int max_m, int cap) {
   int64_t C = SEARCH_BUDGET / search_slot(L, max_m).total;
@@ -376,7 +378,7 @@ struct dmp_ctx {
   dmp::Scratch score_ws;           // "score_native": the ticket | the packed native, its columns, the header | one pass slot (score.hip: score_scratch)
   dmp::Scratch map_ws;             // "score_map": the counters and tickets | the error sums (mapscore.hip: MapScratch)
   dmp::Scratch align_ws;           // "align_structure": the two tickets | one slot (align.hip: ALIGN_HEAD_BYTES, search_slot above)
-  dmp::Scratch search_ws;          // "search_structures": the table and the tickets | the slots of a chunk (SEARCH_HEAD_BYTES, search_slot)
+  dmp::Scratch search_ws;          // "search_structures": the table, the tickets and the two tables of "search_refine" | the slots of a chunk (SEARCH_HEAD_BYTES, search_slot)
   dmp::Scratch pass_ws;            // "score_passes": the tickets | the delta's partial sums, the slots of a chunk of passes (score.hip: pass_slot)
   dmp::Scratch ss_ws;              // "assign_ss": the counters and the ticket | the proline flags, per entity the hydrogens, the donor
                                    // flags and the two bit matrices, the native's backbone (ss.hip: ss_scratch)

