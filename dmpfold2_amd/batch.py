@@ -34,7 +34,7 @@ import torch
 from . import score as _score
 from .score import Outputs
 from . import shard
-from .predict import (MAX_SEQS, Pipeline, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
+from .predict import (MAX_SEQS, Pipeline, domains_options, _tolerance_arg, drop_in_precision, default_iterations, default_minsteps, encode_aln, load_state_dict,
                       pdb_text, read_a3m, read_aln, read_template_ca, save_distmap_npy, add_restrain_arguments, restrain_cutoff_to_mA,
                       restrain_report, restrain_to_milli, needs_native, NATIVE_NEEDED)
 
@@ -187,11 +187,14 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     restrain_bond_dev_max; pdb / ca get <stem>.restrain.json (the line `dmpfold --restrain` prints).  With `exposure` (the dict of
     score.unpack_exposure, --exposure): npz gains exp_n (int32 (L, 5): exposed points of N, CA, C, O, CB, -1 for a glycine's CB),
     exp_hse_up, exp_hse_down, exp_cn10 (int32 (L,)) and exp_area (float64 (L,): the residue's accessible area in square
-    Angstrom); pdb / ca get <stem>.exposure.json (the line `dmpfold --exposure` prints)."""
+    Angstrom); pdb / ca get <stem>.exposure.json (the line `dmpfold --exposure` prints).  With `domains` (the dict of
+    score.unpack_domains, --domains): npz gains dom_label (int32 (L,): every residue's domain) and dom_table (int32 (domains, 8):
+    size, segments, lowest residue, contact pairs inside and to the rest, ext and denominator of the cut, level); pdb / ca get
+    <stem>.domains.json (the line `dmpfold --domains` prints)."""
     unknown = set(results) - {row.name for row in _score.BLOCKS}
     if unknown:
         raise TypeError(f"write_result: no result is called {sorted(unknown)}")
-    scores, map_scores, pass_scores, ss, exposure, alignment, hits = (results.get(row.name) for row in _score.BLOCKS)
+    scores, map_scores, pass_scores, ss, exposure, domains, alignment, hits = (results.get(row.name) for row in _score.BLOCKS)
     stem = os.path.join(out_dir, os.path.splitext(os.path.basename(aln_path))[0])
     if fmt == "npz":
         path = stem + ".npz"
@@ -229,6 +232,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
         if exposure is not None:
             extra.update({"exp_n": np.asarray(exposure["n"], dtype=np.int32), "exp_area": np.asarray(exposure["area_res"], dtype=np.float64)})
             extra.update({"exp_" + k: np.asarray(exposure[k], dtype=np.int32) for k in ("hse_up", "hse_down", "cn10")})
+        if domains is not None:
+            extra.update({"dom_label": np.asarray(domains["labels"], dtype=np.int32),
+                          "dom_table": np.asarray([[row[k] for k in _score.DOMAINS_COLUMNS] for row in domains["table"]],
+                                                  dtype=np.int32).reshape(-1, len(_score.DOMAINS_COLUMNS))})
         if restrain is not None:
             extra.update({"restrain_" + k: (np.int32 if k in RESTRAIN_COUNTS else np.float32)(v) for k, v in restrain.items()})
         if alignment is not None:
@@ -250,9 +257,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     if distmap is not None:
         save_distmap_npy(stem + ".distmap.npy", distmap)
     forms = results_json(results, hits_top)
-    for name, value in (("exposure", forms.get("exposure")), ("restrain", restrain)):
+    for name, value in (("exposure", forms.get("exposure")), ("domains", forms.get("domains")), ("restrain", restrain)):
         if value is not None:
-            forms[name] = {name: value}                  # (these two lines carry their name)
+            forms[name] = {name: value}                  # (these lines carry their name)
     for name, form in forms.items():
         with open(f"{stem}.{name}.json", "w") as fh:
             fh.write(json.dumps(form) + "\n")
@@ -300,6 +307,25 @@ def cost_order(targets, iterations):
     scans = [scan_target(a) for a, _ in targets]
     costs = [shard.estimate_cost(L, N, iterations) for L, N in scans]
     return sorted(range(len(targets)), key=lambda i: (-costs[i], i)), scans
+
+
+# --domains: what run_batch asks of its pipeline beside its own arguments, whose list callers know by position -
+# (tau, min_size, min_segment) or None; `batch_domains` sets it for the duration of a block.
+_DOMAINS = None
+
+
+@contextlib.contextmanager
+def batch_domains(tau=0.25, min_size=40, min_segment=10):
+    """Every run_batch inside the block also splits every target's model into structural domains on the GPU
+    (Pipeline.use_domains): the parse is written with the target (write_result) and `stats_out` receives "domains":
+    {stem: the dict of score.domains_json}."""
+    global _DOMAINS
+    domains_options(tau, min_size, min_segment)                              # (a bad value raises before any work)
+    before, _DOMAINS = _DOMAINS, (tau, min_size, min_segment)
+    try:
+        yield
+    finally:
+        _DOMAINS = before
 
 
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
@@ -387,6 +413,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         from .predict import MAX_L
         library.check(MAX_L)
         max_L = max(max_L, library.max_m)               # the engines' capacity bounds every entry's length
+    domains = _DOMAINS                                  # (batch_domains)
     t0 = time.perf_counter()
     pipe, dev, copy_stream = None, None, None
     failed, outputs, parsed, faulted = [], [], {}, []
@@ -406,6 +433,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                                            ("search", library is not None, library)):
                 if wanted:
                     getattr(pipe, "set_" + setter)(*value)
+            if domains is not None:
+                pipe.use_domains(True, *domains)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -439,9 +468,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     scored, aligned = set(), set()                      # the tickets that had a native / a structure
     asked = {"natives": bool(natives), "structures": bool(structures), "library": library is not None, "ss": ss,
-             "exposure": exposure, "restrain": restraining}
+             "exposure": exposure, "restrain": restraining, "domains": domains is not None}
     blocks_on = {"score": asked["natives"], "align": asked["structures"], "search": asked["library"], "score_map": score_map,
-                 "passes": score_passes, "ss": ss, "exposure": exposure}
+                 "passes": score_passes, "ss": ss, "exposure": exposure, "domains": domains is not None}
     gathered = {}                                       # {key of `stats_out`: {stem: what the summary takes}}
 
     def write(t, public):
@@ -450,7 +479,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         aln_path, alnmat, _ = parsed.pop(t)
         stem = os.path.splitext(os.path.basename(aln_path))[0]
         had = {"score": t in scored, "score_map": t in scored, "passes": t in scored, "align": t in aligned}
-        results = {row.name: row.unpack(getattr(out, row.field), alnmat.shape[1], library=library, seq=alnmat[0])
+        results = {row.name: row.unpack(getattr(out, row.field), alnmat.shape[1], library=library, seq=alnmat[0],
+                                        coords=out.coords, confs=out.confs)
                    for row in _score.BLOCKS if getattr(out, row.field) is not None and had.get(row.key, True)}
         forms = results_json(results, search_top)
         rep = None
@@ -631,6 +661,13 @@ def batch_parser():
     # the hits gain "refined", npz gains hit_refined.  The help text and the parsed namespace of the other flags are recorded
     # (tests/golden/host_plumbing.json.gz): the flag stays out of both unless given, and README.md describes it.
     ap.add_argument("--search-refine", type=int, default=argparse.SUPPRESS, metavar="R", help=argparse.SUPPRESS)
+    # --domains [--domains-tau Q --domains-min-size N --domains-min-segment N]: split every target's model into structural domains
+    # on the GPU; the summary gains every target's domain count with mean, median and the share of multi-domain targets, npz
+    # gains dom_label and dom_table, pdb / ca write <stem>.domains.json.  Hidden like --search-refine, for the same reason.
+    ap.add_argument("--domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    ap.add_argument("--domains-tau", type=float, default=argparse.SUPPRESS, metavar="Q", help=argparse.SUPPRESS)
+    ap.add_argument("--domains-min-size", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
+    ap.add_argument("--domains-min-segment", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
     ap.add_argument("--ss", action="store_true",
                     help="assign secondary structure to every target's backbone on the GPU from its hydrogen bonds; the summary "
                          "gains every target's eight-state string and helix / strand / coil fractions with their means and "
@@ -715,6 +752,18 @@ def exposure_summary(exposure):
     return out
 
 
+def domains_summary(domains):
+    """{stem: the dict of score.domains_json} -> the summary's part for --domains: per target the number of domains, of
+    discontinuous ones and the sizes; mean and median of the domain count and the share of targets with more than one domain."""
+    counts = [v["domains"] for v in domains.values()]
+    return {"domain_targets": len(domains),
+            "domains": {stem: {"domains": v["domains"], "discontinuous": v["discontinuous"], "sizes": [row["size"] for row in v["table"]]}
+                        for stem, v in domains.items()},
+            "mean_domains": float(np.mean(counts)) if counts else None,
+            "median_domains": float(np.median(counts)) if counts else None,
+            "multi_domain_share": float(np.mean([c > 1 for c in counts])) if counts else None}
+
+
 def restrain_summary(reports):
     """{stem: the dict of predict.restrain_report} -> the summary's part for --restrain: every target's report, and mean and
     median of map_rms, restrained_pairs, clashes and bond_dev_max."""
@@ -753,7 +802,8 @@ def score_summary(scores):
 GATHERED = (("scores", "natives", score_summary),
             ("alignments", "structures", lambda found: {"aligned_targets": len(found), "alignments": found}),
             ("hits", "library", lambda found: {"searched_targets": len(found), "hits": found}),
-            ("ss", "ss", ss_summary), ("exposure", "exposure", exposure_summary), ("restrain", "restrain", restrain_summary))
+            ("ss", "ss", ss_summary), ("exposure", "exposure", exposure_summary), ("restrain", "restrain", restrain_summary),
+            ("domains", "domains", domains_summary))
 GATHERED_AS = {"alignment": ("alignments", lambda form: {k: form[k] for k in ("m",) + _score.ALIGN_NAMES}),
                "hits": ("hits", lambda form: [{k: v for k, v in hit.items() if k not in ("R", "t")} for hit in form["hits"]])}
 
@@ -784,6 +834,14 @@ def main(argv=None):
             ap.error(f"--search-refine must be 0 or 1 .. {_score.SEARCH_MAX}, got {args.search_refine}")
         library = _score.Library.open(args.library, refine=args.search_refine)
 
+    dom_given = {k: getattr(args, "domains_" + k) for k in ("tau", "min_size", "min_segment") if hasattr(args, "domains_" + k)}
+    if dom_given and not hasattr(args, "domains"):
+        ap.error("--domains-tau, --domains-min-size and --domains-min-segment need --domains")
+    try:
+        domains_options(**dom_given)                     # (a bad value is an error of the command line)
+    except ValueError as exc:
+        ap.error(str(exc))
+
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -802,13 +860,14 @@ def main(argv=None):
     store = job_store if (world > 1 and not args.static_shards) else None
     passes = {}
     try:
-        n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
-                                  weights_file=args.model_weights, streams=args.streams,
-                                  device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
-                                  converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
-                                  structures=args.structures, library=library, search_top=args.search_top,
-                                  score_map=args.score_map, score_passes=args.score_passes, ss=args.ss,
-                                  restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
+        with (batch_domains(**dom_given) if hasattr(args, "domains") else contextlib.nullcontext()):
+            n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
+                                      weights_file=args.model_weights, streams=args.streams,
+                                      device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
+                                      converge=args.converge, stats_out=passes, distmap=args.distmap, natives=args.natives,
+                                      structures=args.structures, library=library, search_top=args.search_top,
+                                      score_map=args.score_map, score_passes=args.score_passes, ss=args.ss,
+                                      restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
     except BatchFailures as bf:                      # keep going: the other ranks wait in job_summary
         for aln_path, exc in bf.failed:
             print(f"dmpfold-batch: {aln_path}: {type(exc).__name__}: {exc}", file=sys.stderr)
@@ -819,7 +878,7 @@ def main(argv=None):
         print(f"dmpfold-batch: rank {rank}: {type(exc).__name__}: {exc}", file=sys.stderr)
         n, elapsed, status, broke = 0, 0.0, 2, 1
     for key, argument, _ in GATHERED:                # host side, through the job's key-value store: read behind the reduction
-        if getattr(args, argument) and world > 1:
+        if getattr(args, argument, None) and world > 1:
             job_store.set(f"dmpfold_batch_{key}/{rank}", json.dumps(passes.get(key, {})))
     total, tmax, failed_all, broke_all = shard.job_summary(n, elapsed, failures=(n_failed, broke))
     if args.converge is not None:
@@ -833,7 +892,7 @@ def main(argv=None):
         if args.converge is not None:
             summary["converge"], summary["passes_run"], summary["passes_saved"] = args.converge, passes_all[0], passes_all[1]
         for key, argument, part in GATHERED:
-            if getattr(args, argument):
+            if getattr(args, argument, None):
                 summary.update(part(gather(key, passes, world, job_store if world > 1 else None)))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:

@@ -469,6 +469,11 @@ static int exposure_reserve(dmp_ctx* c) {
   return c->opt.exposure ? scratch_reserve(c, c->exposure_ws, exposure_need(c->max_L), "exposure scratch") : DMP_OK;
 }
 
+// Option "domains": likewise (domains.hip has the layout and the byte count).
+static int domains_reserve(dmp_ctx* c) {
+  return c->opt.domains ? scratch_reserve(c, c->domains_ws, domains_need(c->max_L), "domain scratch") : DMP_OK;
+}
+
 // ---- the options --------------------------------------------------------------------------------------------------------
 // One table; dmp_ctx_set_option and dmp_ctx_get_option walk it.  A NEW OPTION IS ONE ROW: its name, where the value lives (a
 // member of the context or of its TailOpts `opt`), what the setter accepts - any value kept as 0 / 1 (FLAG), a range, or the
@@ -564,6 +569,10 @@ static const Option OPTIONS[] = {
     {"assign_ss", TAIL(ss), 0, 1, 0, "assign_ss must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, ss_reserve},
     {"exposure", TAIL(exposure), 0, 1, 0, "exposure must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, exposure_reserve},
     {"exposure_chunk", TAIL(exposure_chunk), 0, INT32_MAX, 0, "exposure_chunk must be >= 0, got %d"},          // tests only: list entries per chunk, 0 = what the LDS holds
+    {"domains", TAIL(domains), 0, 1, 0, "domains must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, domains_reserve},
+    {"domains_tau_milli", TAIL(dom_tau), 1, 1000, 0, "domains_tau_milli must be 1 .. 1000, got %d"},              // the largest ext / (min(int_A, int_B) + ext) that splits, * 1000
+    {"domains_min_size", TAIL(dom_min_size), 8, 1024, 0, "domains_min_size must be 8 .. 1024, got %d"},
+    {"domains_min_segment", TAIL(dom_min_segment), 1, 64, 0, "domains_min_segment must be 1 .. 64, got %d"},      // at most domains_min_size when a prediction begins
     {"restrain_milli", TAIL(restrain), 0, 100000, 0, "restrain_milli must be 0 .. 100000, got %d"},               // force constant k * 1000; 0 = off
     {"restrain_cut_mA", TAIL(restrain_cut), 0, 100000, 0, "restrain_cut_mA must be 0 .. 100000, got %d"},         // milli-Angstrom
     {"align_structure", TAIL(align), 0, 1, 0, "align_structure must be 0 or 1, got %d"},
@@ -767,7 +776,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->bwd_ws) (void)hipFree(c->bwd_ws);
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
-  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->ss_ws, &c->exposure_ws})
+  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->ss_ws, &c->exposure_ws, &c->domains_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1303,6 +1312,8 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   DMP_ARG(!c->opt.smap || c->opt.emit, "score_map scores the map of option emit_distmap, which is 0: set emit_distmap to 1");
   DMP_ARG(!c->opt.smap || c->opt.score, "score_map reads the native trace of option score_native, which is 0: set score_native to 1");
   DMP_ARG(!c->opt.passes || c->opt.score, "score_passes scores every pass against the native trace of option score_native, which is 0: set score_native to 1");
+  DMP_ARG(!c->opt.domains || c->opt.dom_min_segment <= c->opt.dom_min_size,
+          "domains_min_segment is %d, above domains_min_size = %d: a segment is part of a domain", c->opt.dom_min_segment, c->opt.dom_min_size);
   DMP_ARG(c->vg_waiters == 0, "members of the vertical-GRU group this context led have not taken their results yet");
   DMP_ARG(c->vg_leader == nullptr || c->vg_leader == c, "this context still waits for the vertical GRU of its group");
   c->vg_leader = nullptr;
@@ -1532,6 +1543,8 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.ss && (rc = assign_ss(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.ss.off, s))) return rc;
   // option "exposure": the exposure block behind that, from the same two inputs (exposure.hip)
   if (c->run.exposure && (rc = exposure(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.exposure.off, s))) return rc;
+  // option "domains": the domain block behind that, from the same two inputs (domains.hip)
+  if (c->run.domains && (rc = domains(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.domains.off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

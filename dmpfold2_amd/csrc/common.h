@@ -10,8 +10,10 @@
 #include "../../include/dmpfold_hip.h"
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
-// "search_refine", "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk"
-struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, search_refine = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0; };
+// "search_refine", "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk",
+// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment"
+struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, search_refine = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0,
+                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10; };
 
 namespace dmp {
 
@@ -88,11 +90,16 @@ __host__ __device__ inline int ss_floats(int L) { return SS_HEADER + 8 * L; }
 //   of the native), all of it out, between the SS block and the align block.
 constexpr int EXPOSURE_HEADER = 32;
 __host__ __device__ inline int exposure_floats(int L) { return EXPOSURE_HEADER + 16 * L; }
+//   | with "domains": the domain block = DOMAINS_HEADER floats (sixteen of the model, sixteen of the native) | label_model [L] |
+//   label_native [L] | two tables of DOMAINS_MAX rows of DOMAINS_ROW floats (model, native), all of it out, between the
+//   exposure block and the align block.
+constexpr int DOMAINS_HEADER = 32, DOMAINS_MAX = 16, DOMAINS_ROW = 8;
+__host__ __device__ inline int domains_floats(int L) { return DOMAINS_HEADER + 2 * L + 2 * DOMAINS_MAX * DOMAINS_ROW; }
 // The blocks in buffer order.  A block states where it begins, how many floats in front are the caller's input and where what
 // the library writes ends; a block whose option is off is empty (off = end).  `passes`: the rows R of the pass block, 0 =
 // none.  The align block's trailing input, whose length only the caller knows, lies behind `total`.
 struct ConfBlock { int64_t off, in, end; };                              // [off, off + in) in, [off + in, end) out
-struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, align; int64_t total; };
+struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, align; int64_t total; };
 __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int passes) {
   ConfLayout lay;
   int64_t at = 0;
@@ -109,6 +116,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
   lay.pass = block(behind > at ? behind - at : 0, passes ? pass_floats(passes) : 0);
   lay.ss = block(0, o.ss ? ss_floats(L) : 0);
   lay.exposure = block(0, o.exposure ? exposure_floats(L) : 0);
+  lay.domains = block(0, o.domains ? domains_floats(L) : 0);
   lay.align = block(1, o.align ? align_layout(L).in : 0);
   lay.total = at;
   return lay;
@@ -116,7 +124,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
 // true for the floats a prediction writes: what becomes NaN when it latched a fault (api.hip)
 __host__ __device__ inline bool conf_is_out(const ConfLayout& lay, int64_t i) {
   auto out = [i](const ConfBlock& b) { return i >= b.off + b.in && i < b.end; };
-  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.align);
+  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.align);
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -384,6 +392,8 @@ struct dmp_ctx {
                                    // flags and the two bit matrices, the native's backbone (ss.hip: ss_scratch)
   dmp::Scratch exposure_ws;        // "exposure": the counters, the ticket and has_native | the glycine flags, the native's backbone
                                    // (exposure.hip: exposure_scratch)
+  dmp::Scratch domains_ws;         // "domains": has_native and the counters | per entity the nodes, the lists, the slots, the cuts, the
+                                   // contact table, the summed-area tables of one level (domains.hip: domains_scratch)
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
@@ -664,7 +674,7 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 // what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
 ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
-    assign_ss_need(int max_L), exposure_need(int max_L);
+    assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
@@ -688,6 +698,9 @@ int exposure_capture_gly(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s)
 int exposure(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 int64_t exposure_points_fetch(float* d_dst, int64_t capacity, hipStream_t s);   // the sphere points as the device holds them -> floats written
 const float* exposure_native_backbone(const dmp_ctx* c);             // the native's rebuilt backbone in the scratch
+// option "domains" (domains.hip): the domain block from the C-alpha trace of d_coords and, with d_native (the score block's
+// trace) not null, from the native's
+int domains(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
 int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);
 // restrain: the final refinement with option "restrain_milli" on - the steps also pull towards c->best_dm (coords.hip)

@@ -35,12 +35,14 @@ from __future__ import annotations
 import argparse
 import contextlib
 import ctypes as C
+import inspect
 import json
 import os
 import sys
 import threading
 import time
 from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -370,6 +372,23 @@ def agree(values, option, setter):
     return values[0]
 
 
+def domains_options(tau=0.25, min_size=40, min_segment=10):
+    """The three parameters of option "domains" as the library takes them -> (tau_milli, min_size, min_segment): `tau` (the
+    largest ext / (min(int_A, int_B) + ext) that still splits, 0.001 .. 1) in thousandths, `min_size` 8 .. 1024 residues,
+    `min_segment` 1 .. 64 residues and no more than `min_size` - ValueError otherwise."""
+    milli = int(round(float(tau) * 1000.0))
+    if not (tau == tau) or not 1 <= milli <= 1000:
+        raise ValueError(f"domains: tau must be in [0.001, 1], got {tau}")
+    if not 8 <= int(min_size) <= 1024:
+        raise ValueError(f"domains: min_size must be 8 .. 1024, got {min_size}")
+    if not 1 <= int(min_segment) <= 64 or int(min_segment) > int(min_size):
+        raise ValueError(f"domains: min_segment must be 1 .. 64 and at most min_size = {min_size}, got {min_segment}")
+    return milli, int(min_size), int(min_segment)
+
+
+DOMAINS_OPTIONS = ("domains_tau_milli", "domains_min_size", "domains_min_segment")
+
+
 def agree_ss(values, option="assign_ss", setter="set_ss"):
     """`agree` for option "assign_ss" (the name and signature callers know)."""
     return agree(values, option, setter)
@@ -408,12 +427,13 @@ def agree_options(rows):
     return Flags(all(emits), any(emits), *rows[0][1:])
 
 
-def _stage(device, L, template_ca, flags, extras):
+def _stage(device, L, template_ca, flags, extras, domains=False):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is laid out (score.Layout) for the options as the context holds them (`flags`) -
     the library cannot check it - and its input blocks are filled from `extras`: with "score_native" on the native trace (no
     `native` = no row present: n_pairs 0, NaN scores); with "align_structure" on m and the rows of `structure` (none: m = 0,
-    which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU."""
+    which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU.
+    `domains`: option "domains" on (it travels beside `flags`, whose fields callers know by position)."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -427,7 +447,7 @@ def _stage(device, L, template_ca, flags, extras):
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, flags.passes, **{key: getattr(flags, key) for key in OWN_BLOCK})
+                 flags.max_L, flags.passes, domains=domains, **{key: getattr(flags, key) for key in OWN_BLOCK})
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
     if library is not None:
@@ -442,7 +462,8 @@ def _stage(device, L, template_ca, flags, extras):
 
 
 # The last prediction of an engine: its Outputs (without the coordinates), its length and the library it searched.
-_Last = namedtuple("_Last", "out L library")
+# `coords`: the coordinates, kept only where an unpacker reads them (the domains' radii of gyration).
+_Last = namedtuple("_Last", "out L library coords", defaults=(None,))
 
 
 class Engine:
@@ -581,7 +602,37 @@ class Engine:
         if block is None:
             return None
         torch.cuda.synchronize(self.device)
-        return row.unpack(block, self._last.L, library=self._last.library)
+        return row.unpack(block, self._last.L, library=self._last.library, coords=self._last.coords, confs=self._last.out.confs)
+
+    def set_domains(self, on, tau=0.25, min_size=40, min_segment=10):
+        """Option "domains" on this engine, as it stands from now on: every prediction's final C-alpha trace is split into
+        structural domains on the GPU (and, with a whole `native`, the native's); what a call returns does not change, the
+        result is in `domains` (score.unpack_domains) and `domains_block`.  `tau`, `min_size`, `min_segment`: domains_options."""
+        values = domains_options(tau, min_size, min_segment) if on else None      # (raises before anything changes)
+        for name, value in zip(DOMAINS_OPTIONS, values or ()):
+            self.set_option(name, value)
+        self.set_option("domains", 1 if on else 0)
+
+    @contextlib.contextmanager
+    def with_domains(self, tau=0.25, min_size=40, min_segment=10):
+        """Option "domains" and its three parameters set for the duration of the block, then as they were: the predictions
+        made inside it get their domains (`set_domains`)."""
+        values = dict(zip(DOMAINS_OPTIONS, domains_options(tau, min_size, min_segment)), domains=1)
+        before = {}
+        try:
+            for name, value in values.items():
+                before[name] = self.get_option(name)
+                self.set_option(name, value)
+            yield self
+        finally:
+            for name, value in reversed(list(before.items())):
+                self.set_option(name, value)
+
+    def predict_domains(self, alnmat, *args, domains_tau=0.25, domains_min_size=40, domains_min_segment=10, **asked):
+        """`predict` with option "domains" set for this call only: the same arguments, the same return value; the parse is in
+        `domains` and `domains_block` afterwards."""
+        with self.with_domains(domains_tau, domains_min_size, domains_min_segment):
+            return self.predict(alnmat, *args, **asked)
 
     @property
     def passes_run(self):
@@ -666,8 +717,9 @@ class Engine:
                       agree_passes([self.get_option("score_passes")], score, iterations), **_own_blocks([self]))
         with torch.cuda.device(self.device):
             self._forget_last()
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
-            self._last = _Last(out._replace(coords=None), L, library if search else None)
+            domains = bool(self.get_option("domains"))
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains)
+            self._last = _Last(out._replace(coords=None), L, library if search else None, out.coords if domains else None)
             milli = self.get_option("restrain_milli")
             if milli > 0:
                 self._restrained = (milli, self.get_option("restrain_cut_mA"), int(max(minsteps, 0)), out.coords)
@@ -772,6 +824,7 @@ RESULT_DOCS = {"scores": "The scores of the last prediction as score.unpack_scor
                "pass_scores": "The pass table of the last prediction as score.unpack_pass_scores gives it",
                "ss": "The secondary structure of the last prediction as score.unpack_ss gives it",
                "exposure": "The solvent exposure of the last prediction as score.unpack_exposure gives it",
+               "domains": "The structural domains of the last prediction as score.unpack_domains gives them",
                "alignment": "The structural alignment of the last prediction as score.unpack_alignment gives it",
                "hits": "The search of the last prediction as score.unpack_search gives it, with the library's `names` beside `hits` "
                        "and `rank`"}
@@ -937,6 +990,16 @@ class Pipeline:
         (and, with `set_score` on and a whole native given to `submit`, of the native's); idle pipeline only."""
         self._set_flag("exposure", on)
 
+    def use_domains(self, on, tau=0.25, min_size=40, min_segment=10):
+        """Option "domains" on every engine: targets submitted from now on get their final C-alpha trace split into structural
+        domains (and, with `set_score` on and a whole native given to `submit`, the native's); the domain block (32 + 2L + 256
+        floats, score.unpack_domains) then comes last of all in what `result`, `peek` and `collect` give per target.  `tau`,
+        `min_size`, `min_segment`: domains_options.  Idle pipeline only."""
+        values = domains_options(tau, min_size, min_segment) if on else None      # (raises before anything changes)
+        for name, value in zip(DOMAINS_OPTIONS, values or ()):
+            self.set_option(name, value)
+        self.set_option("domains", 1 if on else 0)
+
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
@@ -1001,7 +1064,12 @@ class Pipeline:
             extras = Extras(native=native if flags.score else None, structure=structure if flags.align else None,
                             library=self._search if flags.search else None)
             # (the native, align and search blocks are written on the current stream: `ready` below is behind it)
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras)
+            domains = agree([e.get_option("domains") for e in self.engines], "domains", "use_domains")
+            if domains and any(tuple(e.get_option(n) for n in DOMAINS_OPTIONS) != tuple(self.engines[0].get_option(n) for n in DOMAINS_OPTIONS)
+                               for e in self.engines[1:]):
+                raise RuntimeError("the engines must agree on \"domains_tau_milli\", \"domains_min_size\" and \"domains_min_segment\" "
+                                   "(whichever of them runs a target must give the same parse); use use_domains")
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -1293,10 +1361,32 @@ def aln_to_coords(input_file, device=default_device, template=None, iterations=d
     `return_exposure` (addition): the solvent exposure of the final backbone is counted on the GPU (option "exposure"; with a
     whole `native` also that of the native's rebuilt backbone) and the dict of score.unpack_exposure, made with the query's
     sequence, is appended last of all."""
-    r = _predict_file(input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain, compare,
-                      compare_chain, search, distmap=return_distmap, scores=return_scores, alignment=return_alignment,
-                      hits=return_hits, map_scores=return_map_scores, pass_scores=return_pass_scores, ss=return_ss,
-                      restrain=restrain, restrain_cutoff=restrain_cutoff, exposure=return_exposure)
+    return _coords_tuple(locals())
+
+
+def aln_to_domains(input_file, *args, domains_tau=0.25, domains_min_size=40, domains_min_segment=10, **asked):
+    """`aln_to_coords` with the model split into structural domains on the GPU (option "domains"; with a whole `native` also
+    the native's trace): the same arguments, and the dict of score.unpack_domains - made with the model's coordinates and
+    confidences, so every domain has its radius of gyration and mean confidence - appended last of all.  `domains_tau`,
+    `domains_min_size`, `domains_min_segment`: domains_options."""
+    call = inspect.signature(aln_to_coords).bind(input_file, *args, **asked)
+    call.apply_defaults()
+    return _coords_tuple(call.arguments, domains_options(domains_tau, domains_min_size, domains_min_segment))
+
+
+def _coords_tuple(call, domains=None):
+    """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave) -> what it returns."""
+    v = SimpleNamespace(**call)
+    r, parse = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
+                                  v.native, v.native_chain, v.compare, v.compare_chain, v.search, distmap=v.return_distmap,
+                                  scores=v.return_scores, alignment=v.return_alignment, hits=v.return_hits,
+                                  map_scores=v.return_map_scores, pass_scores=v.return_pass_scores, ss=v.return_ss,
+                                  restrain=v.restrain, restrain_cutoff=v.restrain_cutoff, exposure=v.return_exposure)
+    return _as_tuple(r, **{k: call[k] for k in call if k.startswith("return_")}) + ((parse,) if domains is not None else ())
+
+
+def _as_tuple(r, return_alnmat=False, return_distmap=False, return_scores=False, return_alignment=False, return_hits=False,
+              return_map_scores=False, return_pass_scores=False, return_ss=False, return_restrain=False, return_exposure=False):
     return ((r.coords, r.confs) + ((r.alnmat,) if return_alnmat else ()) + ((r.distmap,) if return_distmap else ())
             + ((r.scores,) if return_scores else ()) + ((r.alignment,) if return_alignment else ())
             + ((r.hits,) if return_hits else ()) + ((r.map_scores,) if return_map_scores else ())
@@ -1316,6 +1406,16 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
                   pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
     """`aln_to_coords` -> Prediction; the eight flags are its return_distmap, return_scores, return_alignment, return_hits,
     return_map_scores, return_pass_scores, return_ss and return_exposure; `restrain`, `restrain_cutoff` are its own."""
+    return _predict_file_with(None, input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain,
+                              compare, compare_chain, search, distmap, scores, alignment, hits, map_scores, pass_scores, ss,
+                              restrain, restrain_cutoff, exposure)[0]
+
+
+def _predict_file_with(domains, input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain,
+                       compare, compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
+                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
+    """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None).  `domains`: None, or what domains_options
+    gave - the prediction then runs with option "domains" (Engine.with_domains)."""
     restrain_options(restrain, restrain_cutoff)                              # (a bad value raises before any work)
     for option, wanted in (("score_map", map_scores), ("score_passes", pass_scores)):
         if wanted and native is None:
@@ -1345,10 +1445,12 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
         # (the engine holds both traces: its capacity covers the structure to align with, too)
         cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
-        out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
-                                  native=native, structure=compare, library=search, score_map=bool(map_scores),
-                                  score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain, restrain_cutoff=restrain_cutoff,
-                                  exposure=bool(exposure))
+        with (eng.with_domains(domains[0] * 1e-3, *domains[1:]) if domains is not None else contextlib.nullcontext()):
+            out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
+                                      native=native, structure=compare, library=search, score_map=bool(map_scores),
+                                      score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain,
+                                      restrain_cutoff=restrain_cutoff, exposure=bool(exposure))
+        parse = eng.domains if domains is not None else None
         exposed = None
         if exposure:
             torch.cuda.synchronize(eng.device)
@@ -1359,7 +1461,7 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
                           pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
                           scores=eng.scores if native is not None and scores else None,
-                          alignment=eng.alignment if compare is not None and alignment else None)
+                          alignment=eng.alignment if compare is not None and alignment else None), parse
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1455,8 +1557,31 @@ def dmpfold_parser():
                              "output is unchanged")
     parser.add_argument("--exposure-file", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --exposure to FILE instead of standard error")
+    # --domains [--domains-tau Q --domains-min-size N --domains-min-segment N] [--domains-file FILE]: split the model into
+    # structural domains on the GPU (a contact-density bisection; with --native given whole also the native's trace and the
+    # overlap of the two parses); the result goes to standard error, or to FILE, as one JSON line under the key "domains", the
+    # model on standard output is unchanged.  Hidden like --search-refine, for the same reason; README.md describes it.
+    parser.add_argument("--domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    parser.add_argument("--domains-tau", type=float, default=argparse.SUPPRESS, metavar="Q", help=argparse.SUPPRESS)
+    parser.add_argument("--domains-min-size", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
+    parser.add_argument("--domains-min-segment", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
+    parser.add_argument("--domains-file", type=str, default=argparse.SUPPRESS, metavar="FILE", help=argparse.SUPPRESS)
     add_restrain_arguments(parser, "-r")
     return parser
+
+
+def domains_arguments(parser, args):
+    """What --domains and its companions ask for: None without --domains, else what domains_options makes of them (a bad
+    value, or a companion without --domains, is an error of the command line)."""
+    given = {k: getattr(args, "domains_" + k) for k in ("tau", "min_size", "min_segment") if hasattr(args, "domains_" + k)}
+    if not hasattr(args, "domains"):
+        if given or hasattr(args, "domains_file"):
+            parser.error("--domains-tau, --domains-min-size, --domains-min-segment and --domains-file need --domains")
+        return None
+    try:
+        return domains_options(**given)
+    except ValueError as exc:
+        parser.error(str(exc))
 
 
 def run_dmpfold(argv=None):
@@ -1473,11 +1598,13 @@ def run_dmpfold(argv=None):
         if not 0 <= args.search_refine <= _score.SEARCH_MAX:
             parser.error(f"--search-refine must be 0 or 1 .. {_score.SEARCH_MAX}, got {args.search_refine}")
         search = _score.Library.open(args.search, refine=args.search_refine)
-    r = _predict_file(args.input_file, args.device, args.template, args.iterations, args.minsteps, args.model_weights,
-                      args.converge, args.native, args.native_chain, args.compare, args.compare_chain, search,
-                      distmap=args.distmap is not None, scores=args.native is not None, alignment=args.compare is not None,
-                      hits=args.search is not None, map_scores=args.score_map, pass_scores=args.score_passes, ss=args.ss,
-                      restrain=args.restrain, restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
+    domains = domains_arguments(parser, args)
+    r, parse = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
+                                  args.model_weights, args.converge, args.native, args.native_chain, args.compare,
+                                  args.compare_chain, search, distmap=args.distmap is not None, scores=args.native is not None,
+                                  alignment=args.compare is not None, hits=args.search is not None, map_scores=args.score_map,
+                                  pass_scores=args.score_passes, ss=args.ss, restrain=args.restrain,
+                                  restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1500,6 +1627,8 @@ def run_dmpfold(argv=None):
         json_line(_score.ss_json(r.ss), args.ss_file)
     if args.exposure:
         json_line({"exposure": _score.exposure_json(r.exposure)}, args.exposure_file)
+    if parse is not None:
+        json_line({"domains": _score.domains_json(parse)}, getattr(args, "domains_file", None))
     if r.restrain is not None:
         json_line({"restrain": r.restrain}, None)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

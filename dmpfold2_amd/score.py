@@ -106,11 +106,24 @@ def exposure_floats(L):
     return EXPOSURE_HEADER + EXPOSURE_ARRAYS * int(L)
 
 
+DOMAINS_HEADER = 32                  # floats in front of the labels of the domain block: sixteen of the model, sixteen of the native
+DOMAINS_MAX = 16                     # rows of a leg's table: four levels of bisection
+DOMAINS_ROW = 8                      # floats of a row
+DOMAINS_FIELDS = ("domains", "contacts", "tau_milli", "min_size", "min_segment", "discontinuous", "depth", "unexamined")
+DOMAINS_COLUMNS = ("size", "segments", "first", "contacts", "contacts_out", "cut_ext", "cut_den", "level")
+
+
+def domains_floats(L):
+    """Floats of the domain block (option "domains") of a prediction of length L."""
+    return DOMAINS_HEADER + 2 * int(L) + 2 * DOMAINS_MAX * DOMAINS_ROW
+
+
 class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_L passes ss exposure",
                         defaults=(False, False, False, None, None, None, None, False, False))):
     """Where everything lies in the `d_conf` buffer of a prediction of length L: the Python twin of ConfLayout / conf_layout()
     / search_base() of csrc/common.h, in the order of include/dmpfold_hip.h.  Made from what decides it - `distmap`, `score`,
-    `score_map`, `ss`, `exposure`: options "emit_distmap", "score_native", "score_map", "assign_ss", "exposure" on; `align_m`:
+    `score_map`, `ss`, `exposure`, `domains`: options "emit_distmap", "score_native", "score_map", "assign_ss", "exposure",
+    "domains" on (`domains` is an attribute beside the ten fields, which callers unpack by position); `align_m`:
     the m the align block holds (None = "align_structure" off); `search`: (K, M) of option "search_structures" (None = off);
     `max_L`: the context's, for the rule of B0 (None: whatever the align block's writer allocated, i.e. any whole m >= 0
     counts); `passes`: the rows R of the pass block of option "score_passes" (None = off).  The confidences, the map and its
@@ -118,15 +131,25 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
       (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | exposure_off (X0): exposure block (32 + 16L) |
-      align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
+      domains_off (D0): domain block (32 + 2L + 256) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
 
     and `total` is the floats the buffer must hold."""
 
     def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None,
-                ss=False, exposure=False):
-        return super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
+                ss=False, exposure=False, domains=False):
+        self = super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
                                None if passes is None else int(passes), bool(ss), bool(exposure))
+        self.domains = bool(domains)
+        return self
+
+    domains = False                  # (of a Layout made by `_make`)
+
+    def _replace(self, **changes):
+        domains = changes.pop("domains", self.domains)
+        new = super()._replace(**changes)
+        new.domains = bool(domains)
+        return new
 
     def floats(self, row):
         """The floats a row of BLOCKS takes in this buffer: 0 where its block is off."""
@@ -151,6 +174,7 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     pass_off = property(lambda s: s._begin("passes"))                                                       # T0
     ss_off = property(lambda s: s._begin("ss"))                                                             # U0
     exposure_off = property(lambda s: s._begin("exposure"))                                                 # X0
+    domains_off = property(lambda s: s._begin("domains"))                                                   # D0
     align_off = property(lambda s: s._begin("align"))                                                       # A0
     # the end of the align block as its writer allocated it ...
     align_end = property(lambda s: s._begin(None))
@@ -186,6 +210,10 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     def exposure_block(self, buf):
         """The exposure block of a `d_conf` buffer as a view (32 + 16L floats), None with `exposure` off."""
         return self._view("exposure", buf)
+
+    def domains_block(self, buf):
+        """The domain block of a `d_conf` buffer as a view (32 + 2L + 256 floats), None with `domains` off."""
+        return self._view("domains", buf)
 
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
@@ -223,8 +251,22 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
     score_block (5L + 24,), with "align_structure" align_block (25 + 2L + 3m,), with "search_structures" search_block
     (26K + 2LK + 3M,), with "score_map" map_block (64 + L,), with "score_passes" pass_block (16 + 8R,), with "assign_ss"
     ss_block (32 + 8L,), with "exposure" exposure_block (32 + 16L,) - None for what is absent.  The blocks stand in the
-    order they are handed out in (HANDOUT), not the buffer's (BLOCKS, at the end of this module)."""
+    order they are handed out in (HANDOUT), not the buffer's (BLOCKS, at the end of this module).  With "domains"
+    `domains_block` (32 + 2L + 256,) is an attribute beside the eleven fields, which callers unpack by position; it is handed
+    out behind them all."""
     __hash__ = tuple.__hash__
+    domains_block = None
+
+    def __new__(cls, *parts, domains_block=None, **named):
+        self = super().__new__(cls, *parts, **named)
+        self.domains_block = domains_block
+        return self
+
+    def _replace(self, **changes):
+        domains_block = changes.pop("domains_block", self.domains_block)
+        new = super()._replace(**changes)
+        new.domains_block = domains_block
+        return new
 
     def __eq__(self, other):        # (a part is an array or a tensor, whose == is elementwise: parts are the same by identity)
         return isinstance(other, tuple) and len(self) == len(other) and all(
@@ -234,24 +276,28 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
         return not self == other
 
     @classmethod
-    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False, ss=False, exposure=False):
+    def of(cls, public, distmap, score, align=False, search=False, score_map=False, passes=False, ss=False, exposure=False,
+           domains=False):
         """The inverse of `public` for a caller that knows which options were on (the keywords stand in HANDOUT's order)."""
         rest = iter(public)
-        return cls(*(next(rest) if on else None
-                     for on in (True, True, distmap, distmap, score, align, search, score_map, passes, ss, exposure)))
+        parts = [next(rest) if on else None
+                 for on in (True, True, distmap, distmap, score, align, search, score_map, passes, ss, exposure)]
+        return cls(*parts, domains_block=next(rest) if domains else None)
 
     def public(self, distmap=True, score=True, align=True, search=True, score_map=True, blocks=True, passes=True, ss=True,
-               exposure=True):
+               exposure=True, domains=True):
         """The tuple the public calls return: (coords, confs), then (distmap, info) if present and wanted, then the score
         block, the align block, the search block and - though they lie behind the score block in the buffer - the map-score
-        block, the pass block, the SS block and, last of all, the exposure block, each if present and wanted.  `blocks=False`:
-        none of the seven blocks, whatever else is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
+        block, the pass block, the SS block, the exposure block and, last of all, the domain block, each if present and wanted.
+        `blocks=False`: none of the blocks, whatever else is said - what a call of an `Engine` returns, `public(distmap, blocks=False)`."""
         wanted = (score, align, search, score_map, passes, ss, exposure)
         return (self[:2] + (self[2:4] if distmap and self.distmap is not None else ())
-                + tuple(block for block, want in zip(self[4:], wanted) if blocks and want and block is not None))
+                + tuple(block for block, want in zip(self[4:] + (self.domains_block,), wanted + (domains,))
+                        if blocks and want and block is not None))
 
 
-HANDOUT = Outputs._fields[4:]        # the blocks, by field, in the order `public` hands them out and `of` takes them
+# the blocks, by field, in the order `public` hands them out and `of` takes them
+HANDOUT = Outputs._fields[4:] + ("domains_block",)
 
 
 def split_conf_buffer(buf, L, emit=False, score=False, coords=None, align_m=None, search=None, score_map=False):
@@ -712,6 +758,110 @@ def exposure_json(ex, arrays=False):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# option "domains" (include/dmpfold_hip.h): the final C-alpha trace split into structural domains on the GPU by recursive
+# contact-density bisection.  The block holds integers only; radii of gyration, mean confidences and the overlap with the
+# native's parse are formed here in float64.
+# ---------------------------------------------------------------------------------------------------------------------
+def _segments(labels, d):
+    """[[first, last]] (inclusive) of the runs of residues with label d."""
+    idx = np.flatnonzero(labels == d)
+    if idx.size == 0:
+        return []
+    breaks = np.flatnonzero(np.diff(idx) > 1)
+    return [[int(a), int(b)] for a, b in zip(idx[np.r_[0, breaks + 1]], idx[np.r_[breaks, idx.size - 1]])]
+
+
+def _domains_leg(header, labels, table, ca=None, confs=None):
+    """One leg's sixteen header floats, L labels and 16 x 8 table -> its part of `unpack_domains`."""
+    out = {name: _whole(v) for name, v in zip(DOMAINS_FIELDS, header)}
+    out["unexamined"] = bool(out["unexamined"])
+    n = min(max(out["domains"], 0), DOMAINS_MAX)
+    labels = _index(labels)
+    out["labels"] = labels
+    rows, splits = [], {}
+    for d in range(n):
+        row = {name: _whole(v) for name, v in zip(DOMAINS_COLUMNS, table[d])}
+        row["segment_list"] = _segments(labels, d)
+        row["q"] = row["cut_ext"] / row["cut_den"] if row["cut_den"] else None
+        mine = labels == d
+        if ca is not None:
+            x = np.asarray(ca, dtype=np.float64).reshape(-1, 3)[mine]
+            row["rg"] = float(np.sqrt(((x - x.mean(0)) ** 2).sum(1).mean())) if x.size else float("nan")
+        if confs is not None:
+            c = np.asarray(confs, dtype=np.float64).reshape(-1)[mine]
+            row["mean_conf"] = float(c.mean()) if c.size else float("nan")
+        rows.append(row)
+        if row["cut_den"]:
+            splits.setdefault((row["level"], row["cut_ext"], row["cut_den"]), row["q"])
+    out["table"] = rows
+    # q of every split that left a domain in the table: one per (level, ext, denominator), shallowest first
+    out["splits"] = [{"level": level - 1, "ext": ext, "den": den, "q": q} for (level, ext, den), q in sorted(splits.items())]
+    return out
+
+
+def domains_overlap(a, b):
+    """The share of residues whose labels agree when the domains of `a` are matched with those of `b` greedily by largest
+    overlap (each domain matched at most once; ties to the lower labels)."""
+    a, b = np.asarray(a, dtype=np.int64).reshape(-1), np.asarray(b, dtype=np.int64).reshape(-1)
+    ok = (a >= 0) & (b >= 0)
+    if a.shape != b.shape or not ok.any():
+        return float("nan")
+    table = np.zeros((int(a[ok].max()) + 1, int(b[ok].max()) + 1), dtype=np.int64)
+    np.add.at(table, (a[ok], b[ok]), 1)
+    agree = 0
+    while table.size and table.max() > 0:
+        i, j = np.unravel_index(int(table.argmax()), table.shape)
+        agree += int(table[i, j])
+        table[i, :] = 0
+        table[:, j] = 0
+    return agree / float(a.shape[0])
+
+
+def unpack_domains(block, L, coords=None, confs=None):
+    """A domain block (32 + 2L + 256 floats, array or tensor) -> dict: domains, contacts, tau_milli, min_size, min_segment,
+    discontinuous (domains of more than one segment), depth (the deepest level a domain lies at), unexamined (a final domain
+    of level 4 was large enough to examine), labels (L,) int, table (per domain: size, segments, first, contacts,
+    contacts_out, cut_ext, cut_den, level, segment_list [[first, last]], q of the cut that made it or None) and splits (level,
+    ext, den, q of every split).  `coords` ((L, 5, 3) or the (L, 3) C-alpha trace) adds every domain's radius of gyration
+    `rg`, `confs` its `mean_conf`, both in float64.  has_native, and with a native leg the same under "native" plus `overlap`
+    (domains_overlap of the two labellings).  A block the library answered with NaN (a latched fault) gives zero counts."""
+    L = int(L)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != domains_floats(L):
+        raise ValueError(f"a domain block of length {L} has {domains_floats(L)} floats, got shape {tuple(b.shape)}")
+    ca = None
+    if coords is not None:
+        ca = _host(coords)
+        ca = ca.reshape(L, 5, 3)[:, 1] if ca.size == 15 * L else ca.reshape(L, 3)
+    tables = b[DOMAINS_HEADER + 2 * L:].reshape(2, DOMAINS_MAX, DOMAINS_ROW)
+    out = _domains_leg(b[:16], b[DOMAINS_HEADER:DOMAINS_HEADER + L], tables[0], ca, None if confs is None else _host(confs))
+    out["has_native"] = _whole(b[16]) > 0
+    if out["has_native"]:
+        out["native"] = _domains_leg(b[16:32], b[DOMAINS_HEADER + L:DOMAINS_HEADER + 2 * L], tables[1])
+        out["overlap"] = domains_overlap(out["labels"], out["native"]["labels"])
+    return out
+
+
+def domains_json(dom, arrays=False):
+    """`unpack_domains` as a JSON-ready dict (what `dmpfold --domains` prints): the header, every domain's row with its
+    segments and, where given, rg and mean_conf, the splits and, with a native, the same under "native" and the overlap; with
+    `arrays` also the labels as a list.  NaN becomes None."""
+    def leg(d):
+        js = {k: (bool(d[k]) if k == "unexamined" else int(d[k])) for k in DOMAINS_FIELDS}
+        js["table"] = [{k: (_num(v) if isinstance(v, float) else v) for k, v in row.items()} for row in d["table"]]
+        js["splits"] = [dict(sp, q=_num(sp["q"])) for sp in d["splits"]]
+        if arrays:
+            js["labels"] = [int(v) for v in d["labels"]]
+        return js
+    out = leg(dom)
+    out["has_native"] = bool(dom["has_native"])
+    if dom["has_native"]:
+        out["native"] = leg(dom["native"])
+        out["overlap"] = _num(dom["overlap"])
+    return out
+
+
 def simulate_converge(conf_mean, delta, tol_angstrom):
     """What a run with the convergence stop at `tol_angstrom` (the `converge` of the front ends, option "recycle_tol_mA" =
     converge_to_mA of it) would have done, decided from a full-depth pass table alone -> (passes_run, best_pass).  The stop
@@ -1045,6 +1195,9 @@ BLOCKS = (
           lambda L, on: ss_floats(L), _of_length(unpack_ss), _form(ss_json)),
     Block("exposure", "exposure", "exposure_block", "exposure", "exposure", "32 + 16L",
           lambda L, on: exposure_floats(L), lambda block, L, seq=None, **_: unpack_exposure(block, L, seq=seq), _form(exposure_json)),
+    Block("domains", "domains", "domains_block", "domains", "domains", "32 + 2L + 256",
+          lambda L, on: domains_floats(L),
+          lambda block, L, coords=None, confs=None, **_: unpack_domains(block, L, coords=coords, confs=confs), _form(domains_json)),
     Block("align", "align_structure", "align_block", "alignment", "align_m", "25 + 2L + 3m",
           align_floats, _of_length(unpack_alignment), _form(alignment_json)),
     Block("search", "search_structures", "search_block", "hits", "search", "26K + 2LK + 3M",

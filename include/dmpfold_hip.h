@@ -478,6 +478,66 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * about twice "assign_ss" on the same model (0.11, 0.29, 1.29, 2.78 ms, profiles/ss.txt) and 2.4 times "score_native" in
  * the same run at L = 2048; a folded-like native's leg adds under 0.03 ms, a collapsed native's 0.3 to 2.0 ms.
  * "exposure_chunk" (TESTS ONLY; n >= 0, default 0): at most n list entries per chunk when 0 < n < 1024.
+ * "domains" (0 or 1, default 0; any other value: DMP_ERR_ARG) with "domains_tau_milli" (1 .. 1000, default 250),
+ * "domains_min_size" (8 .. 1024, default 40) and "domains_min_segment" (1 .. 64, default 10; dmp_predict_begin_units answers
+ * DMP_ERR_ARG if it exceeds "domains_min_size" with "domains" on): split the final C-alpha trace into structural domains on
+ * the device - how many domains the model has, where their boundaries are, which of them are discontinuous - without a
+ * native or a second program.  All four are read when a prediction begins and held for it.  With "domains" 0 nothing is
+ * launched, read, written or allocated, and every offset and output is bit for bit what it is without the option.  With it 1
+ * THE d_conf ARGUMENT MUST HOLD D0 + 32 + 2L + 256 FLOATS, D0 = THE END OF THE EXPOSURE BLOCK (X0 + 32 + 16L with
+ * "exposure", X0 without): there sits the DOMAIN BLOCK, all of it outputs, and A0 and B0 below move behind it.  Everything
+ * else in the buffer does not change by a bit.  If "score_native" is on too and every one of the L native rows is present (no
+ * NaN coordinate), the native's trace is parsed the same way as a second leg.  Every value is an integer below 2^24, stored as
+ * a float.  Offsets relative to D0:
+ *   0                    number of domains of the model (1 .. 16)
+ *   1                    contact pairs of the chain
+ *   2, 3, 4              tau_milli, min_size, min_segment as the prediction held them
+ *   5                    domains of more than one segment
+ *   6                    the deepest level a domain lies at: 0 = the chain is whole, v = a domain of level v - 1 was split
+ *   7                    1 if a domain of level 4, which is never examined, has n >= 2 min_size residues
+ *   8 .. 15              zero
+ *   16 .. 31             the same fields of the native's leg; all zero without it
+ *   [32, 32 + L)         label_model: the domain of residue i, domains numbered from 0 by their lowest residue
+ *   [32 + L, 32 + 2L)    label_native; NaN without the native's leg
+ *   32 + 2L + 8d + c     table of the model, row d = 0 .. 15 of 8 floats; rows d >= the number of domains are zero
+ *     c = 0 size  1 segments  2 lowest residue  3 contact pairs inside  4 contact pairs to the rest of the chain
+ *     c = 5, 6 ext and denominator of the cut that made the domain (0, 0 for an unsplit chain)  7 its level
+ *   32 + 2L + 128 + 8d + c   the same table of the native; zero without its leg
+ * A prediction that latched a device-side fault returns NaN in the whole block.
+ * The definition, the only one (tests/domains_ref.py restates it in NumPy; the library agrees with it in every label and
+ * count).  Contacts: residues i and j are in contact iff |i - j| >= 3 and (dx dx + dy dy) + dz dz < 100.0, d = c_i - c_j in
+ * float64 formed from the float32 coordinates, contraction off, every operation in the order written; a NaN fails the
+ * comparison.  Everything behind that is integer arithmetic.  A domain is the ascending list of its n residues; list
+ * positions are virtual indices 0 .. n.  A cut (I, J), 0 <= I < J <= n, (I, J) != (0, n), puts list positions [I, J) into A
+ * and the rest into B (I = 0 or J = n: a plain boundary; otherwise B is discontinuous in the list).  int_A, int_B = contact
+ * pairs inside A, inside B; ext = pairs between them; each pair once, the domain's own residues only.  A cut is admissible iff
+ * J - I >= min_size, n - (J - I) >= min_size, (I = 0 or I >= min_segment), (J = n or n - J >= min_segment) and
+ * min(int_A, int_B) > 0.  Its quality is the rational q = ext / (min(int_A, int_B) + ext); the best cut has the smallest q,
+ * compared exactly by cross-multiplication in int64 (at L = 2048 every product is below 2^44), ties to the lexicographically
+ * smallest (I, J): a strict weak order with a total tie-break, so the order of the reduction cannot change the answer.  A
+ * domain with n >= 2 min_size is split at its best admissible cut iff ext * 1000 < tau_milli * (min(int_A, int_B) + ext).
+ * Levels: level 0 is the whole chain; every domain of a level is examined independently; the children of split domains form
+ * the next level; levels 0 .. 3 are examined, so there are at most 16 domains; children at level 4 are final.
+ * THIS IS A CONTACT-DENSITY BISECTION IN THE MANNER OF DOMAK (Siddiqui & Barton 1995) AND HOLM & SANDER (1994), NOT THEIR
+ * BITS: no smoothing of short stray segments, no sheet rule, and NO VALIDATION ON REAL DOMAINS - tau = 0.25 comes from
+ * synthetic compact traces only (two globules placed side by side have a best q of 0.008 .. 0.165; of 90 single globules of
+ * 80 .. 250 residues 85 have one of 0.26 .. 0.54 and stay whole, 5 one of 0.22 .. 0.25 and are split); nobody has compared
+ * the parse with a domain benchmark or with another program.  The reference has no such quantity.
+ * Cost with the option on: in dmp_predict_end behind "exposure" and in front of "align_structure", on the prediction's stream
+ * and without synchronising - the host reads nothing back between the levels - 24 launches (csrc/domains.hip): has_native
+ * and the reset; the L x L contact table as bytes; per level, the slot (at most 2^level domains) as a grid dimension and
+ * empty or final slots returning at once, the compaction of each domain's residue list by ballot prefix sums, the rows of its
+ * summed-area table in int32 by wave scans, the columns by one thread per column, every admissible (I, J) from five table
+ * reads reduced per I and then per domain with the int64 comparison, the children's labels; the contacts inside and outside
+ * every domain; the numbering by lowest residue, the labels, the table and the header.  Integer atomics only: the same bits
+ * on every run.  Scratch, both legs: 2560 + 48 max_L + 2 max_L^2 + 8 (max_L + 16)^2 bytes - the contact tables and
+ * the summed-area tables of one level, (n_s + 1)^2 int32 per domain, together at most (max_L + 16)^2 - 0.9 MiB at max_L =
+ * 300, 40.6 MiB at max_L = 2048; allocated when the option first becomes 1 on a context and counted in "device_mib"; an
+ * allocation failure is an error of dmp_ctx_set_option and leaves the option as it was.  Measured cost of dmp_predict_end
+ * with the option on (profiles/domains.txt; the collapsed model of profiles/exposure.txt, which stays whole at the defaults):
+ * 0.07 ms at L = 96, 0.07 ms at 300, 0.17 ms at 1000, 0.41 ms at 2048; forced through all four levels (tau_milli 1000,
+ * min_size 8, min_segment 2) 0.08, 0.12, 0.39 and 0.83 ms - against 5.15 ms for "exposure" and 17.0 ms for "align_structure"
+ * at L = 2048 in the same run; a native's leg adds 0.01 to 0.32 ms.
  * "restrain_milli" (0 .. 100000, default 0 = off; any other value: DMP_ERR_ARG) and "restrain_cut_mA" (0 .. 100000, default
  * 15000): restrain the prediction's FINAL refinement to the predicted distance map.  THE REFERENCE HAS NO SUCH TERM: its
  * minimiser (network.py:106-137) knows steric repulsion and the bond and never sees the map.  Both are read when a prediction
@@ -504,7 +564,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
