@@ -458,20 +458,30 @@ static int search_reserve(dmp_ctx* c) {
     need = std::max<int64_t>(need, (int64_t)search_chunk_entries(L, mm, 0) * search_slot(L, mm).total);
   return scratch_reserve(c, c->search_ws, SEARCH_HEAD_BYTES + need, SEARCH_HEAD_BYTES, "search scratch");
 }
-// Options "score_passes", "assign_ss" and "exposure": reserved when the option first becomes 1 on a context (score.hip, ss.hip, exposure.hip have the layouts).
+// Option "score_passes": reserved when the option first becomes 1 on a context (score.hip has the layout).
 static int passes_reserve(dmp_ctx* c) {
   return c->opt.passes ? scratch_reserve(c, c->pass_ws, score_passes_need(c->max_L), "pass-score scratch") : DMP_OK;
 }
+// Options "assign_ss", "exposure" and "domains": likewise (ss.hip, exposure.hip, domains.hip have the layouts), each behind the
+// scratch of the native entity that the three share (entity.hip).  A failure leaves both scratches and the count as they were.
+static int with_entity_reserve(dmp_ctx* c, Scratch& w, ScratchNeed n, const char* what) {
+  const bool had = c->entity_ws.p != nullptr;
+  int rc = scratch_reserve(c, c->entity_ws, entity_need(c->max_L), "native-entity scratch");
+  if (!rc && (rc = scratch_reserve(c, w, n, what)) && !had) {
+    (void)hipFree(c->entity_ws.p);
+    c->bytes -= c->entity_ws.bytes;
+    c->entity_ws = {};
+  }
+  return rc;
+}
 static int ss_reserve(dmp_ctx* c) {
-  return c->opt.ss ? scratch_reserve(c, c->ss_ws, assign_ss_need(c->max_L), "secondary-structure scratch") : DMP_OK;
+  return c->opt.ss ? with_entity_reserve(c, c->ss_ws, assign_ss_need(c->max_L), "secondary-structure scratch") : DMP_OK;
 }
 static int exposure_reserve(dmp_ctx* c) {
-  return c->opt.exposure ? scratch_reserve(c, c->exposure_ws, exposure_need(c->max_L), "exposure scratch") : DMP_OK;
+  return c->opt.exposure ? with_entity_reserve(c, c->exposure_ws, exposure_need(c->max_L), "exposure scratch") : DMP_OK;
 }
-
-// Option "domains": likewise (domains.hip has the layout and the byte count).
 static int domains_reserve(dmp_ctx* c) {
-  return c->opt.domains ? scratch_reserve(c, c->domains_ws, domains_need(c->max_L), "domain scratch") : DMP_OK;
+  return c->opt.domains ? with_entity_reserve(c, c->domains_ws, domains_need(c->max_L), "domain scratch") : DMP_OK;
 }
 
 // ---- the options --------------------------------------------------------------------------------------------------------
@@ -776,7 +786,8 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->bwd_ws) (void)hipFree(c->bwd_ws);
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
-  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->ss_ws, &c->exposure_ws, &c->domains_ws})
+  for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->entity_ws, &c->ss_ws, &c->exposure_ws,
+                     &c->domains_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1244,8 +1255,7 @@ static int issue_front_end_unit(dmp_ctx* c, hipStream_t s) {
     }
     used = side;
     rc = msa_weights(c, d_msa, N, L, c->w, side);
-    if (!rc && c->run.ss) rc = ss_capture_pro(c, d_msa, L, side);       // option "assign_ss": the first row's proline flags
-    if (!rc && c->run.exposure) rc = exposure_capture_gly(c, d_msa, L, side);   // option "exposure": the first row's glycine flags
+    if (!rc && (c->run.ss || c->run.exposure)) rc = entity_capture_row(c, d_msa, L, side);   // options "assign_ss", "exposure": the first row's codes
     if (!rc && N > 1) rc = cov_build(c, d_msa, c->w, N, L, c->cov, side, true);
   } else if (u <= c->fe_inv + c->fe_vgru) {
     // alternate GRU chunk / inverse chunk while both kinds remain
@@ -1539,12 +1549,17 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.smap && (rc = score_map(c, L, d_conf + lay.score.off, d_conf + lay.smap.off, s))) return rc;
   // option "score_passes": the pass block behind that, from ca_pass, conf_means and what score_native packed (score.hip)
   if (pass_R && (rc = score_passes(c, L, pass_R, std::min(c->passes_done, c->max_passes), d_conf + lay.pass.off, s))) return rc;
-  // option "assign_ss": the SS block behind that, from d_coords and - with "score_native" - the score block's native trace (ss.hip)
-  if (c->run.ss && (rc = assign_ss(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.ss.off, s))) return rc;
+  // the native entity of the next three, with "score_native": is the score block's native trace whole, and - for the first two -
+  // its rebuilt backbone (entity.hip)
+  const float* d_native = c->run.score ? d_conf + lay.score.off : nullptr;
+  const bool backbone = c->run.ss || c->run.exposure;
+  if (d_native && (backbone || c->run.domains) && (rc = entity_prepare(c, d_native, L, backbone, s))) return rc;
+  // option "assign_ss": the SS block behind that, from d_coords and - with "score_native" - the native entity (ss.hip)
+  if (c->run.ss && (rc = assign_ss(c, d_coords, L, d_native, d_conf + lay.ss.off, s))) return rc;
   // option "exposure": the exposure block behind that, from the same two inputs (exposure.hip)
-  if (c->run.exposure && (rc = exposure(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.exposure.off, s))) return rc;
+  if (c->run.exposure && (rc = exposure(c, d_coords, L, d_native, d_conf + lay.exposure.off, s))) return rc;
   // option "domains": the domain block behind that, from the same two inputs (domains.hip)
-  if (c->run.domains && (rc = domains(c, d_coords, L, c->run.score ? d_conf + lay.score.off : nullptr, d_conf + lay.domains.off, s))) return rc;
+  if (c->run.domains && (rc = domains(c, d_coords, L, d_native, d_conf + lay.domains.off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

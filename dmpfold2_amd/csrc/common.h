@@ -388,12 +388,13 @@ struct dmp_ctx {
   dmp::Scratch align_ws;           // "align_structure": the two tickets | one slot (align.hip: ALIGN_HEAD_BYTES, search_slot above)
   dmp::Scratch search_ws;          // "search_structures": the table, the tickets and the two tables of "search_refine" | the slots of a chunk (SEARCH_HEAD_BYTES, search_slot)
   dmp::Scratch pass_ws;            // "score_passes": the tickets | the delta's partial sums, the slots of a chunk of passes (score.hip: pass_slot)
-  dmp::Scratch ss_ws;              // "assign_ss": the counters and the ticket | the proline flags, per entity the hydrogens, the donor
-                                   // flags and the two bit matrices, the native's backbone (ss.hip: ss_scratch)
-  dmp::Scratch exposure_ws;        // "exposure": the counters, the ticket and has_native | the glycine flags, the native's backbone
-                                   // (exposure.hip: exposure_scratch)
-  dmp::Scratch domains_ws;         // "domains": has_native and the counters | per entity the nodes, the lists, the slots, the cuts, the
-                                   // contact table, the summed-area tables of one level (domains.hip: domains_scratch)
+  dmp::Scratch entity_ws;          // the native entity of the next three (reserved with the first of them): whole_x, whole_xyz | the
+                                   // alignment's first row, the native's rebuilt backbone (entity.hip: entity_scratch)
+  dmp::Scratch ss_ws;              // "assign_ss": the counters and the ticket | per entity the hydrogens, the donor flags and the two
+                                   // bit matrices (ss.hip: ss_scratch)
+  dmp::Scratch exposure_ws;        // "exposure": the counters and the ticket, nothing behind them (exposure.hip: exposure_scratch)
+  dmp::Scratch domains_ws;         // "domains": the counters | per entity the nodes, the lists, the slots, the cuts, the contact table,
+                                   // the summed-area tables of one level (domains.hip: domains_scratch)
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
@@ -608,6 +609,13 @@ __device__ __forceinline__ bool ticket_take_last(unsigned* ticket, unsigned n) {
   return __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == n - 1u;
 }
 __device__ __forceinline__ void ticket_reset(unsigned* ticket) { __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The last arriver drains a counter that the workgroups added to before they took their tickets: its value, zero left behind for
+// the next launch.
+__device__ __forceinline__ unsigned counter_drain(unsigned* counter) {
+  const unsigned v = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return v;
+}
 // The whole protocol (1-D grid, every thread calls it): the tree, thread 0 publishes its workgroup's sum in partial[block] and
 // takes the ticket, the last arriver adds the partial sums in index order.  True in that one thread of the launch, *total set.
 template <int THREADS>
@@ -674,7 +682,7 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 // what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
 ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
-    assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L);
+    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
@@ -688,18 +696,24 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
 // option "search_structures" (align.hip): the model aligned with each of the K entries of the search block, then ranked
 int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
 int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the batch launch
-// option "assign_ss" (ss.hip): the proline flags of the alignment's first row (front end), then at the prediction's end the SS
-// block from d_coords and, with d_native (the score block's trace) not null, from the native's rebuilt backbone
-int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
+// The native entity of options "assign_ss", "exposure" and "domains" (entity.hip), where it lies in dmp_ctx::entity_ws:
+struct NativeEntity {
+  int* whole_x;           // every row of the native trace has an x that is no NaN: the native leg of "assign_ss" and "exposure" runs
+  int* whole_xyz;         // no coordinate of the native trace is NaN: the native leg of "domains" runs
+  unsigned char* row;     // [L] the residue codes of the alignment's first row
+  float* bb;              // [L][5][3] the native's backbone rebuilt from its trace
+};
+NativeEntity native_entity(const dmp_ctx* c);
+// front end, with "assign_ss" or "exposure" on: `row`.  dmp_predict_end, with "score_native" and any of the three on: the two
+// words from d_native (the score block's trace) and - `backbone`: "assign_ss" or "exposure" is on - `bb`
+int entity_capture_row(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
+int entity_prepare(dmp_ctx* c, const float* d_native, int L, bool backbone, hipStream_t s);
+// options "assign_ss" (ss.hip), "exposure" (exposure.hip), "domains" (domains.hip): the option's block from d_coords and, with
+// d_native (the score block's trace) not null, from the native entity prepared before
 int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
-// option "exposure" (exposure.hip): the glycine flags of the alignment's first row (front end), then at the prediction's end the
-// exposure block from d_coords and, with d_native (the score block's trace) not null, from the native's rebuilt backbone
-int exposure_capture_gly(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s);
 int exposure(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 int64_t exposure_points_fetch(float* d_dst, int64_t capacity, hipStream_t s);   // the sphere points as the device holds them -> floats written
-const float* exposure_native_backbone(const dmp_ctx* c);             // the native's rebuilt backbone in the scratch
-// option "domains" (domains.hip): the domain block from the C-alpha trace of d_coords and, with d_native (the score block's
-// trace) not null, from the native's
+const float* exposure_native_backbone(const dmp_ctx* c);             // the native's rebuilt backbone (dmp_debug_fetch)
 int domains(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
 int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);

@@ -3,11 +3,13 @@
 // and the only definition of every count and of the choice of a cut).  Everything behind the contact test is integer
 // arithmetic; nothing waits between workgroups and nothing is read back by the host between the levels: the launches of one
 // prediction are stream-ordered and the same whatever the trace holds.  The entity (0 model, 1 native) is the last grid
-// dimension of every launch; a native leg that is absent returns at once.
+// dimension of every launch; a native leg that is absent returns at once.  Whether the native is whole (whole_xyz: no NaN
+// coordinate) comes from the native entity (entity.hip), prepared in front of these launches; its C-alpha are read from the
+// score block itself.
 //
 // A residue carries the node of a binary tree: 1 the chain, 2k and 2k + 1 the parts A and B of node k.  Level v examines the
 // nodes 2^v .. 2^(v+1) - 1, one per slot; a domain that was not split keeps a node below 2^(v+1) and is met by no later slot.
-//   domains_prep     one workgroup per entity: has_native, every node = 1, the counters zero
+//   domains_prep     one workgroup per entity: every node = 1, the counters zero
 //   domains_contacts the L x L contact table as bytes, and the chain's contact pairs (one integer atomic per workgroup)
 // per level v = 0 .. 3, the slot as blockIdx.y:
 //   domains_compact  one workgroup per slot: the sizes of the level's domains (LDS histogram), the slot's place in the lists
@@ -27,7 +29,7 @@ namespace dmp {
 
 constexpr int DOM_THREADS = 256, DOM_WAVES = DOM_THREADS / 64;
 constexpr int DOM_LEVELS = 4, DOM_MAX = 1 << DOM_LEVELS, DOM_NODES = 2 * DOM_MAX;
-constexpr int DOM_HEAD_INTS = 256;        // [0] has_native, [2 + e] contact pairs, [16 + 2 (32 e + node) + k] inside / outside
+constexpr int DOM_HEAD_INTS = 256;        // [2 + e] contact pairs, [16 + 2 (32 e + node) + k] inside / outside
 constexpr int64_t DOM_HEAD_BYTES = 4 * DOM_HEAD_INTS;
 static_assert(DOMAINS_HEADER == 32 && DOMAINS_ROW == 8 && DOMAINS_MAX == DOM_MAX, "the block of include/dmpfold_hip.h");
 
@@ -58,6 +60,7 @@ static_assert(sizeof(DomSlot) == 32 && sizeof(DomCut) == 16, "the scratch is car
 struct DomArgs {
   const float* xyz[2];        // the first C-alpha of the model / of the native ...
   int pitch[2];               // ... and the floats from one residue's to the next's
+  const int* whole;           // the native entity's whole_xyz; read only where entities == 2
   float* out;                 // the domain block, 32 + 2L + 256 floats
   int L, entities, tau_milli, min_size, min_segment;
   int* head;                  // [DOM_HEAD_INTS]
@@ -70,7 +73,7 @@ struct DomArgs {
   int* sat;                   // [2][(L + 16)^2]
 };
 
-__device__ inline bool dom_active(const DomArgs& a, int e) { return e == 0 || (a.entities == 2 && a.head[0] != 0); }
+__device__ inline bool dom_active(const DomArgs& a, int e) { return e == 0 || (a.entities == 2 && *a.whole != 0); }
 __device__ inline int64_t dom_sat_pitch(int L) { return (int64_t)(L + 16) * (L + 16); }
 
 // a is the better cut: the smaller ext / den, exactly; of equal ones the smaller (I, J).  Every product is below 2^44.
@@ -112,22 +115,7 @@ __device__ inline void dom_block_sum2(int& u, int& v, int* wsum) {
 }
 
 __global__ __launch_bounds__(DOM_THREADS) void domains_prep_kernel(DomArgs a) {
-  __shared__ int missing;
   const int e = blockIdx.x, tid = threadIdx.x, L = a.L;
-  if (tid == 0) missing = 0;
-  __syncthreads();
-  if (e == 1) {
-    // has_native: every row of the native trace is present
-    int mine = a.entities == 2 ? 0 : 1;
-    if (a.entities == 2)
-      for (int k = tid; k < L; k += DOM_THREADS) {
-        const float* p = a.xyz[1] + (int64_t)a.pitch[1] * k;
-        mine |= (p[0] == p[0] && p[1] == p[1] && p[2] == p[2]) ? 0 : 1;
-      }
-    if (mine) atomicOr(&missing, 1);
-    __syncthreads();
-    if (tid == 0) a.head[0] = missing ? 0 : 1;
-  }
   for (int k = tid; k < L; k += DOM_THREADS) a.node[(int64_t)e * L + k] = 1;
   if (tid == 0) a.head[2 + e] = 0;
   if (tid < 2 * DOM_NODES) {
@@ -398,6 +386,7 @@ int domains(dmp_ctx* c, const float* d_coords, int L, const float* d_native, flo
   a.pitch[0] = 15;
   a.xyz[1] = d_native;                // the score block's native trace [L][3], or null
   a.pitch[1] = 3;
+  a.whole = native_entity(c).whole_xyz;
   a.out = d_block;
   a.L = L;
   a.entities = d_native ? 2 : 1;

@@ -1,9 +1,8 @@
 // option "exposure": solvent exposure of the final backbone, and of the native's where option "score_native" holds a whole
 // native trace (include/dmpfold_hip.h has the layout of the exposure block and the only definition of every count).
-// One small launch in the front end and three in dmp_predict_end behind assign_ss, the entity (0 model, 1 native) as
-// blockIdx.y of the last two:
-//   exposure_capture_gly  front end, beside ss_capture_pro: the glycine flags of the alignment's first row
-//   exposure_prep         one workgroup: has_native
+// Two launches in dmp_predict_end behind assign_ss, the entity (0 model, 1 native) as blockIdx.y of both.  The alignment's first
+// row (a glycine has no side-chain atom), whether the native is whole (whole_x: no NaN x) and its rebuilt backbone come from the
+// native entity (entity.hip), prepared in front of these launches:
 //   exposure_surface      one workgroup per (residue, entity), thread k owns sphere point k of the residue's five atoms.
 //                         Stage A: the threads scan all 5L atoms, 256 at a time, and compact those that can reach one of the
 //                         five (centre distance below R_a + R_j + 0.01) into an LDS list of (x, y, z, R^2) doubles - wave
@@ -34,55 +33,25 @@ __device__ const float exposure_points_dev[3 * EXP_POINTS] = {
 #include "exposure_points.h"
 };
 
-// The scratch of a context of capacity `cap` (bytes from its start, every part 16-aligned).  head: the counters, the ticket
-// (zero between launches) and has_native; then the glycine flags and the native's backbone.
-struct ExpScratch { int64_t gly, nat, total; };
+// The scratch of a context, whatever its capacity: the head alone - the counters and the ticket (zero between launches).
+struct ExpScratch { int64_t total; };
 constexpr int64_t EXP_HEAD_BYTES = 256;
-inline ExpScratch exposure_scratch(int cap) {
-  auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
-  ExpScratch s;
-  s.gly = EXP_HEAD_BYTES;
-  s.nat = s.gly + up(cap);
-  s.total = s.nat + up(60 * (int64_t)cap);
-  return s;
-}
+inline ExpScratch exposure_scratch(int) { return {EXP_HEAD_BYTES}; }
 ScratchNeed exposure_need(int max_L) { return {exposure_scratch(max_L).total, EXP_HEAD_BYTES}; }
 
 struct ExpArgs {
-  const float* bb[2];         // [L][5][3] N, CA, C, O, CB of the model / of the native
-  const unsigned char* gly;   // [L]
-  const float* native;        // the score block's native trace [3L], or null
+  const float* bb[2];         // [L][5][3] N, CA, C, O, CB of the model / of the native (the native entity's)
+  const unsigned char* row;   // [L] the residue codes of the alignment's first row (the native entity's)
+  const int* whole;           // the native entity's whole_x; read only where entities == 2
   float* out;                 // the exposure block, 32 + 16L floats
   int L, entities, chunk;     // chunk: entries of the list walked at a time (1 .. EXP_LIST)
   unsigned* cnt;              // [EXP_COUNTERS]
   unsigned* ticket;           // zero between launches
-  int* has_native;            // written by exposure_prep, read by the launches behind it
 };
 
 // atom radius + the 1.4 A probe (Kabsch & Sander 1983): N, CA, C, O, a side-chain atom
 __device__ inline double exp_radius(int atom) {
   return atom == 0 ? 3.05 : (atom == 1 ? 3.27 : (atom == 2 ? 3.16 : (atom == 3 ? 2.80 : 3.20)));
-}
-
-__global__ void exposure_capture_gly_kernel(const uint8_t* __restrict__ msa, int L, unsigned char* __restrict__ gly) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L) gly[i] = msa[i] == EXP_GLYCINE ? 1 : 0;
-}
-
-// has_native = every row of the native trace is present (the condition of ss_prep)
-__global__ __launch_bounds__(EXP_THREADS) void exposure_prep_kernel(const float* __restrict__ native, int L, int* has_native) {
-  __shared__ int missing;
-  const int tid = threadIdx.x;
-  if (tid == 0) missing = 0;
-  __syncthreads();
-  int mine = 0;
-  for (int k = tid; k < L; k += EXP_THREADS) {
-    const float x = native[3 * k];
-    mine |= x == x ? 0 : 1;
-  }
-  if (mine) atomicOr(&missing, 1);
-  __syncthreads();
-  if (tid == 0) *has_native = missing ? 0 : 1;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -99,7 +68,7 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_surface_kernel(ExpArgs a
   const float nan = __builtin_nanf("");
   float* o = a.out + EXPOSURE_HEADER + (e ? 8 * (int64_t)L : 0);
   if (e == 0 && a.entities == 1 && tid < 5) a.out[EXPOSURE_HEADER + (8 + tid) * (int64_t)L + own_res] = nan;
-  const bool skip = e == 1 && !*a.has_native;              // uniform
+  const bool skip = e == 1 && !*a.whole;                   // uniform
   if (skip) {
     if (tid < 5) o[tid * (int64_t)L + own_res] = nan;
   } else {
@@ -108,7 +77,7 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_surface_kernel(ExpArgs a
       const float* p = bb + 15 * (int64_t)own_res + 3 * tid;
       own[tid][0] = (double)p[0]; own[tid][1] = (double)p[1]; own[tid][2] = (double)p[2];
       own[tid][3] = exp_radius(tid);
-      own_ok[tid] = !(tid == 4 && a.gly[own_res]);
+      own_ok[tid] = !(tid == 4 && a.row[own_res] == EXP_GLYCINE);
     }
     __syncthreads();
     const double ux = (double)exposure_points_dev[3 * tid], uy = (double)exposure_points_dev[3 * tid + 1],
@@ -151,7 +120,7 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_surface_kernel(ExpArgs a
       const int g = b0 + tid, r = g / 5, at = g - 5 * r;
       bool cand = false;
       double cx = 0.0, cy = 0.0, cz = 0.0, Rj = 0.0;
-      if (g < 5 * L && r != own_res && !(at == 4 && a.gly[r])) {
+      if (g < 5 * L && r != own_res && !(at == 4 && a.row[r] == EXP_GLYCINE)) {
         const float* p = bb + 3 * (int64_t)g;
         cx = (double)p[0]; cy = (double)p[1]; cz = (double)p[2];
         Rj = exp_radius(at);
@@ -218,12 +187,8 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_surface_kernel(ExpArgs a
   if (!ticket_take_last(a.ticket, gridDim.x * gridDim.y)) return;
   // the last arriver: the header (the native's counters are zero where its leg did not run)
   a.out[0] = (float)EXP_POINTS;
-  for (int k = 0; k < EXP_COUNTERS; ++k) {
-    const unsigned v = __hip_atomic_load(&a.cnt[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&a.cnt[k], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a.out[k < EXP_PER ? 1 + k : 2 + k] = (float)v;          // offsets 1 .. 7 and 9 .. 15
-  }
-  a.out[8] = a.entities == 2 && *a.has_native ? 1.f : 0.f;
+  for (int k = 0; k < EXP_COUNTERS; ++k) a.out[k < EXP_PER ? 1 + k : 2 + k] = (float)counter_drain(&a.cnt[k]);   // offsets 1 .. 7 and 9 .. 15
+  a.out[8] = a.entities == 2 && *a.whole ? 1.f : 0.f;
   for (int k = 16; k < EXPOSURE_HEADER; ++k) a.out[k] = 0.f;
   ticket_reset(a.ticket);
 }
@@ -238,7 +203,7 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_pairs_kernel(ExpArgs a) 
   float* o = a.out + EXPOSURE_HEADER + (e ? 8 * (int64_t)L : 0) + 5 * (int64_t)L;
   if (e == 0 && a.entities == 1 && i < L)
     for (int k = 0; k < 3; ++k) a.out[EXPOSURE_HEADER + (13 + k) * (int64_t)L + i] = nan;
-  if (e == 1 && !*a.has_native) {                          // uniform
+  if (e == 1 && !*a.whole) {                               // uniform
     if (i < L)
       for (int k = 0; k < 3; ++k) o[k * (int64_t)L + i] = nan;
     return;
@@ -279,36 +244,20 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_pairs_kernel(ExpArgs a) 
   o[2 * (int64_t)L + i] = (float)cn;
 }
 
-int exposure_capture_gly(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s) {
-  hipLaunchKernelGGL(exposure_capture_gly_kernel, dim3(cdiv(L, 256)), dim3(256), 0, s, d_msa, L,
-                     c->exposure_ws.p + exposure_scratch(c->max_L).gly);
-  DMP_LAUNCH_CHECK();
-  return DMP_OK;
-}
-
 int exposure(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s) {
-  const ExpScratch sc = exposure_scratch(c->max_L);
+  const NativeEntity nat = native_entity(c);
   unsigned char* ws = c->exposure_ws.p;
   ExpArgs a{};
-  float* nat_bb = (float*)(ws + sc.nat);
   a.bb[0] = d_coords;
-  a.bb[1] = nat_bb;
-  a.gly = ws + sc.gly;
-  a.native = d_native;
+  a.bb[1] = nat.bb;
+  a.row = nat.row;
+  a.whole = nat.whole_x;
   a.out = d_block;
   a.L = L;
   a.entities = d_native ? 2 : 1;
   a.chunk = c->run.exposure_chunk > 0 && c->run.exposure_chunk < EXP_LIST ? c->run.exposure_chunk : EXP_LIST;
   a.cnt = (unsigned*)ws;
   a.ticket = (unsigned*)ws + EXP_COUNTERS;
-  a.has_native = (int*)ws + EXP_COUNTERS + 1;
-  int rc;
-  if (d_native) {
-    // the native's backbone from its trace by the model's own device function (coords.hip)
-    if ((rc = trace_to_backbone(d_native, L, nat_bb, s))) return rc;
-    hipLaunchKernelGGL(exposure_prep_kernel, dim3(1), dim3(EXP_THREADS), 0, s, d_native, L, a.has_native);
-    DMP_LAUNCH_CHECK();
-  }
   hipLaunchKernelGGL(exposure_surface_kernel, dim3(L, a.entities), dim3(EXP_THREADS), 0, s, a);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(exposure_pairs_kernel, dim3(cdiv(L, EXP_THREADS), a.entities), dim3(EXP_THREADS), 0, s, a);
@@ -316,8 +265,8 @@ int exposure(dmp_ctx* c, const float* d_coords, int L, const float* d_native, fl
   return DMP_OK;
 }
 
-// where the native's rebuilt backbone lies in the scratch (dmp_debug_fetch "exposure_native_backbone")
-const float* exposure_native_backbone(const dmp_ctx* c) { return (const float*)(c->exposure_ws.p + exposure_scratch(c->max_L).nat); }
+// the native's rebuilt backbone, the native entity's (dmp_debug_fetch "exposure_native_backbone")
+const float* exposure_native_backbone(const dmp_ctx* c) { return native_entity(c).bb; }
 
 // the table as the device holds it (dmp_debug_fetch "exposure_points"): read by a kernel, as the surface kernel reads it
 __global__ void exposure_points_copy_kernel(float* __restrict__ dst) {

@@ -136,10 +136,7 @@ __global__ __launch_bounds__(SC_THREADS) void mapscore_count_kernel(MapScoreArgs
   // the last arriver (one thread): the header
   const double sum_abs = agent_load_f64(&a.sums[0]), sum_sq = agent_load_f64(&a.sums[1]), sum_e = total;
   unsigned cn[MS_COUNTERS];
-  for (int k = 0; k < MS_COUNTERS; ++k) {
-    cn[k] = __hip_atomic_load(&a.cnt[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&a.cnt[k], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  for (int k = 0; k < MS_COUNTERS; ++k) cn[k] = counter_drain(&a.cnt[k]);
   int n = 0;
   for (int i = 0; i < L; ++i) n += q[3 * i] == q[3 * i] ? 1 : 0;
   const float lnorm = a.nat[3 * L];

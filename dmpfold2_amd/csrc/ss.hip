@@ -1,9 +1,9 @@
 // option "assign_ss": secondary structure of the final backbone, and of the native's where option "score_native" holds a
 // whole native trace (include/dmpfold_hip.h has the layout of the SS block and the only definition of every predicate).
-// One small launch in the front end and three in dmp_predict_end behind score_passes, the entity (0 model, 1 native) as
-// blockIdx.y of the first two:
-//   ss_capture_pro  front end, beside msa_weights: the proline flags of the alignment's first row, kept for the prediction's end
-//   ss_prep         the amide hydrogens and the donor flags in float64; workgroup (0, 1) decides has_native
+// Three launches in dmp_predict_end behind score_passes, the entity (0 model, 1 native) as blockIdx.y of the first two.  The
+// alignment's first row, whether the native is whole (whole_x: no NaN x) and its rebuilt backbone come from the native entity
+// (entity.hip), prepared in front of these launches:
+//   ss_prep         the amide hydrogens and the donor flags (no donor where the first row has a proline) in float64
 //   ss_hbond        one workgroup per (residue, entity, side).  Side 0: residue i accepts - the energies E(i, j) over j, their
 //                   minimum with its partner, row i of the bit matrix R (bit j = hb(i, j)).  Side 1: residue j donates - the
 //                   same function over i, the column's minimum, row j of the transposed matrix T (bit i = hb(i, j)).  Every
@@ -28,24 +28,22 @@ constexpr int SS_CNT_HB = 0, SS_CNT_CODE = 1, SS_CNT_PAR = 9, SS_CNT_ANTI = 10, 
               SS_COUNTERS = 21;
 constexpr int SS_PROLINE = 14;         // the residue code of P (dmp_msa_encode)
 
-// The scratch of a context of capacity `cap` (bytes from its start, every part 16-aligned).  head: the counters, the ticket
-// (zero between launches) and has_native; then the proline flags, per entity the hydrogens, the donor flags and the two bit
-// matrices (rows of 2 ceil(cap / 64) words), and the native's backbone.
-struct SsScratch { int64_t pro, h[2], donor[2], R[2], T[2], nat, total; };
+// The scratch of a context of capacity `cap` (bytes from its start, every part 16-aligned).  head: the counters and the ticket
+// (zero between launches); then per entity the hydrogens, the donor flags and the two bit matrices (rows of 2 ceil(cap / 64)
+// words).
+struct SsScratch { int64_t h[2], donor[2], R[2], T[2], total; };
 __host__ __device__ inline int ss_row_words(int L) { return 2 * ((L + 63) / 64); }
 constexpr int64_t SS_HEAD_BYTES = 256;
 inline SsScratch ss_scratch(int cap) {
   auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
   SsScratch s;
   int64_t at = SS_HEAD_BYTES;
-  s.pro = at; at += up(cap);
   for (int e = 0; e < 2; ++e) {
     s.h[e] = at; at += up(24 * (int64_t)cap);
     s.donor[e] = at; at += up(cap);
     s.R[e] = at; at += up(4 * (int64_t)cap * ss_row_words(cap));
     s.T[e] = at; at += up(4 * (int64_t)cap * ss_row_words(cap));
   }
-  s.nat = at; at += up(60 * (int64_t)cap);
   s.total = at;
   return s;
 }
@@ -60,19 +58,13 @@ struct SsEntity {
 };
 struct SsArgs {
   SsEntity ent[2];
-  const unsigned char* pro;   // [L]
-  const float* native;        // the score block's native trace [3L], or null
+  const unsigned char* row;   // [L] the residue codes of the alignment's first row (the native entity's)
+  const int* whole;           // the native entity's whole_x; read only where entities == 2
   float* out;                 // the SS block, 32 + 8L floats
   int L, words, entities;
   unsigned* cnt;              // [SS_COUNTERS]
   unsigned* ticket;           // zero between launches
-  int* has_native;            // written by ss_prep, read by the launches behind it
 };
-
-__global__ void ss_capture_pro_kernel(const uint8_t* __restrict__ msa, int L, unsigned char* __restrict__ pro) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L) pro[i] = msa[i] == SS_PROLINE ? 1 : 0;
-}
 
 __device__ inline void ss_atom(const float* bb, int i, int atom, double* p) {
   const float* a = bb + 15 * (int64_t)i + 3 * atom;
@@ -94,21 +86,8 @@ __device__ inline double ss_energy(const double* c, const double* o, const doubl
 // ss_prep
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SS_THREADS) void ss_prep_kernel(SsArgs a) {
-  __shared__ int missing;
-  const int L = a.L, e = blockIdx.y, tid = threadIdx.x, i = blockIdx.x * SS_THREADS + tid;
+  const int L = a.L, e = blockIdx.y, i = blockIdx.x * SS_THREADS + threadIdx.x;
   const SsEntity& en = a.ent[e];
-  if (e == 1 && blockIdx.x == 0) {       // uniform: has_native = every row of the native trace is present
-    if (tid == 0) missing = 0;
-    __syncthreads();
-    int mine = 0;
-    for (int k = tid; k < L; k += SS_THREADS) {
-      const float x = a.native[3 * k];
-      mine |= x == x ? 0 : 1;
-    }
-    if (mine) atomicOr(&missing, 1);
-    __syncthreads();
-    if (tid == 0) *a.has_native = missing ? 0 : 1;
-  }
   if (i >= L) return;
   bool donor = false;
   double h[3] = {0.0, 0.0, 0.0};
@@ -119,7 +98,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_prep_kernel(SsArgs a) {
     ss_atom(en.bb, i, 0, n);
     const double vx = c[0] - o[0], vy = c[1] - o[1], vz = c[2] - o[2];
     const double vv = (vx * vx + vy * vy) + vz * vz;
-    donor = !a.pro[i] && vv > 0.0;
+    donor = a.row[i] != SS_PROLINE && vv > 0.0;
     if (donor) {
       const double s = sqrt(vv);
       h[0] = n[0] + vx / s; h[1] = n[1] + vy / s; h[2] = n[2] + vz / s;
@@ -137,7 +116,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_hbond_kernel(SsArgs a) {
   __shared__ int red_p[SS_THREADS / 64];
   const int L = a.L, own = blockIdx.x, e = blockIdx.y, side = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (e == 1 && !*a.has_native) return;            // uniform
+  if (e == 1 && !*a.whole) return;            // uniform
   const SsEntity& en = a.ent[e];
   // side 0: `own` accepts (its C, O); side 1: `own` donates (its N, H)
   double p0[3], p1[3];
@@ -228,7 +207,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_assign_kernel(SsArgs a) {
   __shared__ unsigned char t3[SS_WIN], t4[SS_WIN], t5[SS_WIN], hf[SS_WIN], gf[SS_WIN];
   __shared__ unsigned icnt[SS_COUNTERS];
   const int L = a.L, tid = threadIdx.x, r0 = blockIdx.x * SS_THREADS, i = r0 + tid, w0 = r0 - SS_HALO;
-  const bool native = a.entities == 2 && *a.has_native != 0;
+  const bool native = a.entities == 2 && *a.whole != 0;
   if (tid < SS_COUNTERS) icnt[tid] = 0u;
   // a flag of residue x from the window, 0 outside it
   auto at = [&](const unsigned char* f, int x) -> bool { return x >= w0 && x < w0 + SS_WIN && f[x - w0] != 0; };
@@ -319,25 +298,16 @@ __global__ __launch_bounds__(SS_THREADS) void ss_assign_kernel(SsArgs a) {
     if (icnt[k]) __hip_atomic_fetch_add(&a.cnt[k], icnt[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!ticket_take_last(a.ticket, gridDim.x)) return;
   // the last arriver: the header
-  for (int k = 0; k < SS_COUNTERS; ++k) {
-    const unsigned v = __hip_atomic_load(&a.cnt[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&a.cnt[k], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // counters 0 .. 10 are offsets 0 .. 10; q3, q8 offsets 12, 13; the native's codes offsets 14 .. 21
-    a.out[k < SS_CNT_Q3 ? k : k + 1] = (float)v;
-  }
+  // counters 0 .. 10 are offsets 0 .. 10; q3, q8 offsets 12, 13; the native's codes offsets 14 .. 21
+  for (int k = 0; k < SS_COUNTERS; ++k) a.out[k < SS_CNT_Q3 ? k : k + 1] = (float)counter_drain(&a.cnt[k]);
   a.out[11] = native ? 1.f : 0.f;
   for (int k = 22; k < 32; ++k) a.out[k] = 0.f;
   ticket_reset(a.ticket);
 }
 
-int ss_capture_pro(dmp_ctx* c, const uint8_t* d_msa, int L, hipStream_t s) {
-  hipLaunchKernelGGL(ss_capture_pro_kernel, dim3(cdiv(L, 256)), dim3(256), 0, s, d_msa, L, c->ss_ws.p + ss_scratch(c->max_L).pro);
-  DMP_LAUNCH_CHECK();
-  return DMP_OK;
-}
-
 int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s) {
   const SsScratch sc = ss_scratch(c->max_L);
+  const NativeEntity nat = native_entity(c);
   unsigned char* ws = c->ss_ws.p;
   SsArgs a{};
   for (int e = 0; e < 2; ++e) {
@@ -346,21 +316,16 @@ int assign_ss(dmp_ctx* c, const float* d_coords, int L, const float* d_native, f
     a.ent[e].R = (unsigned*)(ws + sc.R[e]);
     a.ent[e].T = (unsigned*)(ws + sc.T[e]);
   }
-  float* nat_bb = (float*)(ws + sc.nat);
   a.ent[0].bb = d_coords;
-  a.ent[1].bb = nat_bb;
-  a.pro = ws + sc.pro;
-  a.native = d_native;
+  a.ent[1].bb = nat.bb;
+  a.row = nat.row;
+  a.whole = nat.whole_x;
   a.out = d_block;
   a.L = L;
   a.words = ss_row_words(L);
   a.entities = d_native ? 2 : 1;
   a.cnt = (unsigned*)ws;
   a.ticket = (unsigned*)ws + SS_COUNTERS;
-  a.has_native = (int*)ws + SS_COUNTERS + 1;
-  int rc;
-  // the native's backbone from its trace by the model's own device function (coords.hip)
-  if (d_native && (rc = trace_to_backbone(d_native, L, nat_bb, s))) return rc;
   hipLaunchKernelGGL(ss_prep_kernel, dim3(cdiv(L, SS_THREADS), a.entities), dim3(SS_THREADS), 0, s, a);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(ss_hbond_kernel, dim3(L, a.entities, 2), dim3(SS_THREADS), 0, s, a);

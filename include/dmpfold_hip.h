@@ -343,6 +343,18 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * allocated when the option first becomes 1 on a context and counted in "device_mib"; an allocation failure is an error of
  * dmp_ctx_set_option and leaves the option as it was.  Measured cost: profiles/passes.txt.
  * "score_passes_chunk" (TESTS ONLY; n >= 0, default 0): at most n passes per chunk when n > 0.
+ * THE NATIVE ENTITY of "assign_ss", "exposure" and "domains" below, stated once (csrc/entity.hip).  Each of the three has a
+ * leg for the native of "score_native" and each states its own predicate for "the native is whole"; the inputs of those legs
+ * are prepared once per prediction, whichever of the three are on.  Front end, with "assign_ss" or "exposure" on: one launch
+ * (entity_row, beside the alignment's weights) keeps the L residue codes of the alignment's first row for the end - a proline
+ * donates no hydrogen bond ("assign_ss"), a glycine has no CB atom ("exposure").  dmp_predict_end, with "score_native" and any
+ * of the three on, in front of "assign_ss": one launch of one workgroup (entity_whole) reads the 3L floats of the native trace
+ * and writes two words - whole_x: every row has an x that is no NaN (the predicate of "assign_ss" and "exposure"); whole_xyz:
+ * no coordinate is NaN (the predicate of "domains") - and, with "assign_ss" or "exposure" on, one more launch rebuilds the
+ * native's backbone from its trace by the very device function that builds the model's (csrc/coords.hip, float32).  A native
+ * with a NaN only in some y or z is therefore whole to the first two options and not to "domains".  Scratch: the two words,
+ * the first row and the backbone - 61 max_L + 16 bytes, 122 KiB at max_L = 2048 - allocated when the first of the three options
+ * becomes 1 on a context, counted in "device_mib", and kept until the context is destroyed.
  * "assign_ss" (0 or 1, default 0; any other value: DMP_ERR_ARG): assign secondary structure to the final backbone that
  * dmp_predict_end has just written into d_coords, from its hydrogen bonds, on the device - helix, strand and coil content
  * and the strand pairing without a native, a partner structure or a second program.  Read when a prediction begins and held
@@ -352,7 +364,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * sits the SS BLOCK, all of it outputs, and A0 and B0 below move behind it (search_prep's rule for B0 starts from the moved
  * A0).  Everything else in the buffer does not change by a bit.  If "score_native" is on too and every one of the L native
  * rows is present (no NaN x), the native is assigned as well: its trace is rebuilt into a backbone by the very device
- * function that builds the model's from its trace (csrc/coords.hip, float32), into scratch, the same P_i apply, and the
+ * function that builds the model's from its trace (csrc/coords.hip, float32; the native entity above), the same P_i apply, and the
  * block gains the native's codes and the Q3 / Q8 agreement counts; otherwise has_native = 0.  So a native that is exactly
  * the model's returned C-alpha trace gives ss_native equal to ss, bit for bit.  Counts are integers below 2^24, stored as
  * floats.  Offsets relative to U0:
@@ -399,18 +411,17 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * THIS IS DSSP'S KIND OF ASSIGNMENT, NOT ITS BITS: there is no two-best-partner rule, no bulges, no sheet labels and no
  * chain breaks, and NOBODY HAS COMPARED THE STRINGS WITH THAT PROGRAM'S.  The backbone is the one the reference's
  * Levitt-style reconstruction places from the C-alpha trace (network.py:141-177), not an experimental one.
- * Cost with the option on: one launch in the front end (ss_capture_pro, beside the alignment's weights: the proline flags
- * of the first row, kept for the end) and, in dmp_predict_end behind "score_passes" and in front of "align_structure", on
- * the prediction's stream, three launches (csrc/ss.hip) - ss_prep (hydrogens and donor flags; has_native), ss_hbond (one
+ * Cost with the option on: the native entity's launches above (one in the front end; two in dmp_predict_end with the
+ * native, shared with "exposure" and "domains") and, in dmp_predict_end behind "score_passes" and in front of
+ * "align_structure", on the prediction's stream, three launches (csrc/ss.hip) - ss_prep (hydrogens and donor flags), ss_hbond (one
  * workgroup per residue, entity and side: the energies of a row of acceptor i or a column of donor j by the same device
  * function, the minimum of (E, index) pairs, the row of the bit matrix hb or of its transpose from the waves' ballots),
  * ss_assign (one thread per residue: the helix flags through LDS, the bridges from the set bits of two rows, integer
- * counts thread -> LDS -> one integer atomic per workgroup and counter, the last arriver writes the header) - and a fourth
- * with the native (its backbone).  No float atomics: the same bits on every run.  Scratch: both bit matrices of both
- * entities (4 x max_L x 2 ceil(max_L / 64) words, 2 MiB at max_L = 2048), the hydrogens, the donor and proline flags, the
- * native's backbone, 21 counters and a ticket - 2.3 MiB at max_L = 2048 - allocated when the option first becomes 1 on a
- * context and counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the option as it
- * was.  Measured cost of dmp_predict_end with the option on (profiles/ss.txt; a collapsed model with 2.6 million hydrogen
+ * counts thread -> LDS -> one integer atomic per workgroup and counter, the last arriver writes the header).  No float
+ * atomics: the same bits on every run.  Scratch, beside the native entity's: both bit matrices of both entities (4 x max_L x
+ * 2 ceil(max_L / 64) words, 2 MiB at max_L = 2048), the hydrogens, the donor flags, 21 counters and a ticket - 2.1 MiB at
+ * max_L = 2048 - allocated when the option first becomes 1 on a context and counted in "device_mib"; an allocation failure is
+ * an error of dmp_ctx_set_option and leaves the option and the count as they were.  Measured cost of dmp_predict_end with the option on (profiles/ss.txt; a collapsed model with 2.6 million hydrogen
  * bonds at L = 2048): 0.11 ms at L = 96, 0.29 ms at 300, 1.29 ms at 1000, 2.78 ms at 2048; with the native's leg 0.14,
  * 0.31, 1.35 and 2.86 ms - above "score_native" alone (1.10 ms at L = 2048) from L = 300 on.
  * "exposure" (0 or 1, default 0; any other value: DMP_ERR_ARG): count the solvent exposure of the final backbone that
@@ -424,7 +435,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * of it outputs, and A0 and B0 below move behind it (search_prep's rule for B0 starts from the moved A0).  Everything else
  * in the buffer does not change by a bit.  If "score_native" is on too and every one of the L native rows is present (no NaN
  * x - the condition of "assign_ss"), the native gets the same three measures: its trace is rebuilt into a backbone by the
- * very device function that builds the model's (csrc/coords.hip, float32), into scratch, and the same glycine flags apply;
+ * very device function that builds the model's (csrc/coords.hip, float32; the native entity above), and the same glycines apply;
  * otherwise has_native = 0.  So a native that is exactly the model's returned C-alpha trace gives native arrays equal to the
  * model's, bit for bit.  Counts are integers below 2^24, stored as floats.  Offsets relative to X0:
  *   0                    P = 256, the sphere points per atom
@@ -461,19 +472,18 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * THIS IS SHRAKE & RUPLEY'S KIND OF SURFACE ON A MODEL WITH NO SIDE CHAINS: IT IS NOT DSSP'S ACC, no relative accessibility
  * is offered, and NOBODY HAS COMPARED THE FIGURES WITH ANOTHER PROGRAM'S.  The backbone is the one the reference's
  * Levitt-style reconstruction places from the C-alpha trace, not an experimental one.
- * Cost with the option on: one launch in the front end (exposure_capture_gly, beside ss_capture_pro: the glycine flags of the
- * first row, kept for the end) and, in dmp_predict_end behind "assign_ss" and in front of "align_structure", on the
+ * Cost with the option on: the native entity's launches above (one in the front end; two in dmp_predict_end with the native,
+ * shared with "assign_ss" and "domains") and, in dmp_predict_end behind "assign_ss" and in front of "align_structure", on the
  * prediction's stream and without synchronising, two launches (csrc/exposure.hip) - exposure_surface (one workgroup of 256
  * threads per residue and entity, thread k owning point k of the residue's five atoms: the threads scan all 5L atoms and
  * compact the candidates into an LDS list of (x, y, z, R^2) doubles with wave ballots and a prefix; the list is walked by
  * every wave in step with early exit, in chunks of at most 1024 entries (32 KiB) with the buried bits carried in registers,
  * so that chunk boundaries do not change a bit; the counts are popcounts of the waves' ballots, the sums go through one
  * integer atomic per workgroup and counter, the last arriver writes the header) and exposure_pairs (one thread per residue:
- * the two half-sphere counts and cn10 over LDS tiles) - and two more with the native (its backbone; has_native).  No float
- * atomics, no waiting between workgroups: the same bits on every run.  Scratch: 14 counters, a ticket and has_native, the
- * glycine flags and the native's backbone - 61 max_L + 256 bytes, 122 KiB at max_L = 2048 - allocated when the option first
+ * the two half-sphere counts and cn10 over LDS tiles).  No float atomics, no waiting between workgroups: the same bits on
+ * every run.  Scratch, beside the native entity's: 14 counters and a ticket - 256 bytes - allocated when the option first
  * becomes 1 on a context and counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the
- * option as it was.  Measured cost of dmp_predict_end with the option on (profiles/exposure.txt; a collapsed model, 98 % of
+ * option and the count as they were.  Measured cost of dmp_predict_end with the option on (profiles/exposure.txt; a collapsed model, 98 % of
  * its atoms without an exposed point at L = 2048): 0.27 ms at L = 96, 0.69 ms at 300, 2.13 ms at 1000, 5.18 ms at 2048 -
  * about twice "assign_ss" on the same model (0.11, 0.29, 1.29, 2.78 ms, profiles/ss.txt) and 2.4 times "score_native" in
  * the same run at L = 2048; a folded-like native's leg adds under 0.03 ms, a collapsed native's 0.3 to 2.0 ms.
@@ -487,7 +497,8 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * THE d_conf ARGUMENT MUST HOLD D0 + 32 + 2L + 256 FLOATS, D0 = THE END OF THE EXPOSURE BLOCK (X0 + 32 + 16L with
  * "exposure", X0 without): there sits the DOMAIN BLOCK, all of it outputs, and A0 and B0 below move behind it.  Everything
  * else in the buffer does not change by a bit.  If "score_native" is on too and every one of the L native rows is present (no
- * NaN coordinate), the native's trace is parsed the same way as a second leg.  Every value is an integer below 2^24, stored as
+ * NaN coordinate: whole_xyz of the native entity above - NOT the condition of "assign_ss" and "exposure", which look at x
+ * alone), the native's trace is parsed the same way as a second leg.  Every value is an integer below 2^24, stored as
  * a float.  Offsets relative to D0:
  *   0                    number of domains of the model (1 .. 16)
  *   1                    contact pairs of the chain
@@ -524,17 +535,17 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * 80 .. 250 residues 85 have one of 0.26 .. 0.54 and stay whole, 5 one of 0.22 .. 0.25 and are split); nobody has compared
  * the parse with a domain benchmark or with another program.  The reference has no such quantity.
  * Cost with the option on: in dmp_predict_end behind "exposure" and in front of "align_structure", on the prediction's stream
- * and without synchronising - the host reads nothing back between the levels - 24 launches (csrc/domains.hip): has_native
- * and the reset; the L x L contact table as bytes; per level, the slot (at most 2^level domains) as a grid dimension and
+ * and without synchronising - the host reads nothing back between the levels - behind the native entity's launch for
+ * whole_xyz (with the native; no backbone is rebuilt for this option) 24 launches (csrc/domains.hip): the reset; the L x L contact table as bytes; per level, the slot (at most 2^level domains) as a grid dimension and
  * empty or final slots returning at once, the compaction of each domain's residue list by ballot prefix sums, the rows of its
  * summed-area table in int32 by wave scans, the columns by one thread per column, every admissible (I, J) from five table
  * reads reduced per I and then per domain with the int64 comparison, the children's labels; the contacts inside and outside
  * every domain; the numbering by lowest residue, the labels, the table and the header.  Integer atomics only: the same bits
- * on every run.  Scratch, both legs: 2560 + 48 max_L + 2 max_L^2 + 8 (max_L + 16)^2 bytes - the contact tables and
+ * on every run.  Scratch, both legs, beside the native entity's: 2560 + 48 max_L + 2 max_L^2 + 8 (max_L + 16)^2 bytes - the contact tables and
  * the summed-area tables of one level, (n_s + 1)^2 int32 per domain, together at most (max_L + 16)^2 - 0.9 MiB at max_L =
  * 300, 40.6 MiB at max_L = 2048; allocated when the option first becomes 1 on a context and counted in "device_mib"; an
- * allocation failure is an error of dmp_ctx_set_option and leaves the option as it was.  Measured cost of dmp_predict_end
- * with the option on (profiles/domains.txt; the collapsed model of profiles/exposure.txt, which stays whole at the defaults):
+ * allocation failure is an error of dmp_ctx_set_option and leaves the option and the count as they were.  Measured cost of
+ * dmp_predict_end with the option on (profiles/domains.txt; the collapsed model of profiles/exposure.txt, which stays whole at the defaults):
  * 0.07 ms at L = 96, 0.07 ms at 300, 0.17 ms at 1000, 0.41 ms at 2048; forced through all four levels (tau_milli 1000,
  * min_size 8, min_segment 2) 0.08, 0.12, 0.39 and 0.83 ms - against 5.15 ms for "exposure" and 17.0 ms for "align_structure"
  * at L = 2048 in the same run; a native's leg adds 0.01 to 0.32 ms.

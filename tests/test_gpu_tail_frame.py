@@ -1,8 +1,8 @@
 """Every option at a prediction's end on at once: the scratch of each lies beside the others', and its head is zero again.
 
-The options at the end of a prediction ("emit_distmap", "score_native", "score_map", "score_passes", "assign_ss",
-"align_structure", "search_structures") each own one device scratch carved by a layout function, a head in front of it zero
-between launches.  Two properties of that frame, through the public Python API only (the yardstick is the library itself: the
+The options at the end of a prediction ("emit_distmap", "score_native", "score_map", "score_passes", "assign_ss", "exposure",
+"domains", "align_structure", "search_structures") each own one device scratch carved by a layout function, a head in front of
+it zero between launches.  Two properties of that frame, through the public Python API only (the yardstick is the library itself: the
 test passes unchanged on the commit before the frame):
 
   * each block of a call with every extra on equals, bit for bit, the block of a call with that extra alone (plus the extras
@@ -12,6 +12,8 @@ test passes unchanged on the commit before the frame):
 One engine of max_L = 33 (synthetic weights, precision 2), one-row alignments of L = 8, 9 and 33, two iterations (three
 passes), "search_chunk" 2 for the library of three and "score_passes_chunk" 2 for the three passes: two chunks each.
 """
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -25,7 +27,8 @@ import dmpfold_oracle as O          # noqa: E402  (test infrastructure: encode_a
 from dmpfold2_amd import score as S  # noqa: E402
 
 MAX_L = 33
-BLOCKS = ("score_block", "map_score_block", "pass_block", "ss_block", "align_block", "search_block")
+BLOCKS = ("score_block", "map_score_block", "pass_block", "ss_block", "exposure_block", "domains_block", "align_block", "search_block")
+DOMAINS = (1.0, 8, 2)               # tau, min_size, min_segment: every admissible cut is accepted, L = 33 has some
 
 
 @pytest.fixture(scope="module")
@@ -44,9 +47,10 @@ def _bits(x):
     return x.detach().cpu().numpy().reshape(-1).view(np.uint32).copy()
 
 
-def _call(eng, aln, **extras):
-    """One prediction -> {name: bits} of what it returned and of every block it left."""
-    ret = eng.predict(aln, None, 2, 0, **extras)
+def _call(eng, aln, domains=False, **extras):
+    """One prediction -> {name: bits} of what it returned and of every block it left (`domains`: inside with_domains)."""
+    with eng.with_domains(*DOMAINS) if domains else contextlib.nullcontext():
+        ret = eng.predict(aln, None, 2, 0, **extras)
     eng.sync_check()
     got = {name: _bits(t) for name, t in zip(("coords", "confs", "distmap", "info"), ret)}
     for name in BLOCKS:
@@ -75,8 +79,9 @@ def _inputs(eng, L):
 @pytest.mark.parametrize("L", [8, 9, 33])
 def test_every_extra_at_once_equals_each_alone_and_repeats(eng, L):
     aln, native, structure, library = _inputs(eng, L)
-    every = dict(distmap=True, native=native, structure=structure, library=library, score_map=True, score_passes=True, ss=True)
-    first = _call(eng, aln, **every)
+    every = dict(distmap=True, native=native, structure=structure, library=library, score_map=True, score_passes=True, ss=True,
+                 exposure=True)
+    first = _call(eng, aln, domains=True, **every)
     assert set(first) == {"coords", "confs", "distmap", "info"} | set(BLOCKS)
     assert first["pass_block"].size == S.pass_floats(3) and first["search_block"].size == S.search_floats(L, 3, library.rows)
 
@@ -87,6 +92,8 @@ def test_every_extra_at_once_equals_each_alone_and_repeats(eng, L):
              "map_score_block": dict(native=native, score_map=True),
              "pass_block": dict(native=native, score_passes=True),
              "ss_block": dict(native=native, ss=True),          # (with a native the block holds the native's assignment too)
+             "exposure_block": dict(native=native, exposure=True),
+             "domains_block": dict(native=native, domains=True),
              "align_block": dict(structure=structure),
              "search_block": dict(library=library)}
     calls = {}
@@ -99,6 +106,6 @@ def test_every_extra_at_once_equals_each_alone_and_repeats(eng, L):
         assert np.array_equal(solo["coords"], first["coords"]) and np.array_equal(solo["confs"], first["confs"])
 
     # the same call again
-    second = _call(eng, aln, **every)
+    second = _call(eng, aln, domains=True, **every)
     for name in first:
         assert np.array_equal(second[name], first[name]), "L = %d: %s differs in the second call" % (L, name)

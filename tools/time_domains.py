@@ -74,7 +74,7 @@ def measure(L, args, weights):
         return "%.3f ms (min %.3f, max %.3f)" % (med[name], min(ts[name]), max(ts[name]))
     line = ("L=%d precision %d, %d runs: dmp_predict_end medians off %.3f ms, exposure %.3f ms, align_structure %.3f ms, domains at the "
             "defaults %s, forced %s, score_native %.3f ms, forced with a native's leg %s; the option costs %+.3f ms at the defaults, "
-            "%+.3f ms forced, a native's leg %+.3f ms more (24 launches each way); scratch %.1f MiB; domains: defaults %d, forced %d "
+            "%+.3f ms forced, a native's leg %+.3f ms more (24 launches each way, and the native entity's one in front with the native); scratch %.1f MiB; domains: defaults %d, forced %d "
             "(depth %d, %d discontinuous), the forced native %d; contact pairs %d"
             % (L, args.precision, args.repeats, med["off"], med["exposure"], med["align"], spread("domains"), spread("forced"),
                med["score"], spread("forced+native"), med["domains"] - med["off"], med["forced"] - med["off"],

@@ -70,7 +70,7 @@ def measure(L, args, weights):
         return e["buried_atoms"] / float(max(e["atoms"], 1))
     line = ("L=%d precision %d, %d runs: dmp_predict_end medians off %.3f ms, score_native %.3f ms, exposure %.3f ms (min %.3f, max "
             "%.3f), exposure + folded native %.3f ms (min %.3f, max %.3f), exposure + collapsed native %.3f ms (min %.3f, max %.3f); "
-            "the model's leg costs %+.3f ms (2 launches), a folded-like native's %+.3f ms, a collapsed native's %+.3f ms (4 launches "
+            "the model's leg costs %+.3f ms (2 launches), a folded-like native's %+.3f ms, a collapsed native's %+.3f ms (2 + the native entity's 2 launches "
             "each); scratch %d MiB; atoms without an exposed point: model %.2f, folded %.2f, collapsed %.2f; area model %.0f, folded "
             "%.0f, collapsed %.0f A^2"
             % (L, args.precision, args.repeats, med["off"], med["score"], med["exposure"], min(ts["exposure"]), max(ts["exposure"]),

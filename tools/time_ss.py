@@ -65,7 +65,7 @@ def measure(L, args, weights):
     assert one["ss8"] == two["ss8"] and two["has_native"]
     print("L=%d precision %d, %d runs: dmp_predict_end medians off %.3f ms, score_native %.3f ms, assign_ss %.3f ms (min %.3f, "
           "max %.3f), both %.3f ms (min %.3f, max %.3f); the model's leg costs %+.3f ms (3 launches), with the native's %+.3f ms "
-          "(4 launches); score_native alone costs %+.3f ms; scratch %d MiB; n_hb %d, helix %.2f strand %.2f, native helix %.2f"
+          "(5 launches, two of them the native entity's); score_native alone costs %+.3f ms; scratch %d MiB; n_hb %d, helix %.2f strand %.2f, native helix %.2f"
           % (L, args.precision, args.repeats, med["off"], med["score"], med["ss"], min(ts["ss"]), max(ts["ss"]), med["ss+native"],
              min(ts["ss+native"]), max(ts["ss+native"]), med["ss"] - med["off"], med["ss+native"] - med["score"],
              med["score"] - med["off"], mib["ss"], one["n_hb"], one["helix"], one["strand"],
