@@ -59,7 +59,7 @@ def _stale(target, deps):
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "conv_split.h", "conv_bf16.h", "conv_f16.h", "vgru.h", "score_common.h", "exposure_points.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "cluster.h", "conv_split.h", "conv_bf16.h", "conv_f16.h", "vgru.h", "score_common.h", "exposure_points.h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "dmpfold_hip.h"))
     extra = os.environ.get("DMP_EXTRA_HIPCC_FLAGS", "").split()      # tuning experiments (-DVG_CH=1 ...)
     lib = os.environ.get("DMP_LIB_OUT", LIB)

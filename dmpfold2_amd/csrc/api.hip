@@ -1,6 +1,6 @@
 // extern "C" surface of libdmpfold_hip.so (see include/dmpfold_hip.h): context and weight
 // management, host-side residue encoding, stage-level entry points and the fused dmp_predict.
-#include "common.h"
+#include "cluster.h"
 #include <atomic>
 #include "conv_bf16.h"
 #include "conv_f16.h"
@@ -670,10 +670,10 @@ int dmp_ctx_create(int device, int max_L, int max_N, dmp_ctx** out) {
   A_(seq_b, L * WIDTH);
   A_(emb, L * (WIDTH + 8));
   A_(mat1d, L * WIDTH);
-  A_(seq_hx, 2 * 2 * HID2 + 4);
+  A_(seq_hx, seq_gru_cluster_need());
   A_(seq_abort, 2);      // [0] fault word of the prediction in flight, [1] faults latched by finished ones
-  A_(refine_gx, 2 * 3 * L + 2);
-  A_(tri_gx, 8 * std::min<int64_t>(L, 640) + 2);
+  A_(refine_gx, refine_cluster_need((int)L));
+  A_(tri_gx, tridiag_cluster_need((int)L));
   A_(z0, (int64_t)STEM_OUT * LL);
   A_(planes, (int64_t)(NS * NS + 1) * LL);
   A_(dmap, LL);

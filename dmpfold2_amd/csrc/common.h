@@ -630,39 +630,6 @@ __device__ __forceinline__ bool grid_sum_f64(double v, double* red, double* part
   return true;
 }
 
-// ---- hand-off between the workgroups of a cluster kernel (seq_gru_kernel, refine_cluster_kernel) -------------------
-// Granules {epoch, value} are published with a store and gathered with sc1 loads (agent scope: past the L1, served by
-// the L2).  An agent-scope STORE is written through to the memory side so that every XCD can see it: measured
-// (tools/ubench_handoff.hip) 450 ns one way, and 2.78 us per step of the sequence GRU with 256 granules per step.  A
-// PLAIN store stops in the L2 of the XCD its workgroup runs on, where the sc1 loads of workgroups on THAT XCD find it:
-// 284 ns one way, 1.29 us per step, the same bits - and never seen from another XCD.  The block id -> XCD round robin
-// puts a cluster on one XCD, but nothing guarantees it, so the cluster checks where it actually runs: every workgroup
-// ORs the bit of its XCC id (hardware register) into a mask word and counts itself in (agent-scope atomics, zeroed
-// by the host before the launch); when all `members` have arrived, a mask with one bit set means plain stores are safe.
-// Returns true for "one XCD" (call from one thread per workgroup; bounded wait: false on a timeout, the slow path
-// then still works wherever the members run).
-// `allow` = false (option "cluster_local" = 0) answers false at once: the agent-scope protocol, for tests of that path.
-__device__ __forceinline__ bool cluster_on_one_xcd(unsigned long long* hdr, int members, bool allow = true) {
-  if (!allow) return false;
-  unsigned xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  __hip_atomic_fetch_or(&hdr[0], 1ull << (xcc & 15u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_fetch_add(&hdr[1], 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  for (unsigned spins = 0; spins < 2000000u; ++spins) {
-    if (__hip_atomic_load(&hdr[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned long long)members) {
-      const unsigned long long mask = __hip_atomic_load(&hdr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return (mask & (mask - 1)) == 0;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
-}
-// publication of a granule: `local` = cluster_on_one_xcd
-__device__ __forceinline__ void cluster_publish(unsigned long long* p, unsigned long long v, bool local) {
-  if (local) asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(v) : "memory");
-  else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 int mds_kernel_attrs(dmp_ctx* c);     // once per device, at context creation
 int gj_kernel_attrs(dmp_ctx* c);      // ditto (dca.hip)
 int eigh_top8(dmp_ctx* c, const float* d_M, int L, float* d_mds, hipStream_t s);

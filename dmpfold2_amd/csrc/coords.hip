@@ -2,7 +2,7 @@
 // minimiser (reference network.py:106-137) and the backbone builder (network.py:141-177).
 // The reference evaluates these as chains of separately rounded float32 tensor ops, so
 // floating-point contraction is switched off for this file.
-#include "common.h"
+#include "cluster.h"
 
 #pragma clang fp contract(off)
 
@@ -496,19 +496,16 @@ __global__ __launch_bounds__(1024) void refine_kernel(float* __restrict__ ca, in
 // The same iteration on a cluster of RF_G workgroups (one XCD): workgroup g owns the residues
 // [g Lg, (g+1) Lg), keeps a copy of all coordinates in LDS, and per step computes the accelerations of
 // its residues (T threads per residue, each over a contiguous slice of the partners, slices added in
-// order), publishes the new coordinates as 8-byte {epoch, value} granules (agent-scope stores, the
-// data is the flag - the protocol of seq_gru_kernel) and gathers the others' by sweeping the granule
-// array until every tag carries the step's epoch.  Two granule arrays alternate, so a workgroup that
-// is one step ahead never overwrites what a slower one still has to read.
+// order), publishes the new coordinates as granules and gathers the others' (the hand-off of cluster.h,
+// DESIGN section 4).
 constexpr int RF_G = 16;          // workgroups of the cluster
 constexpr int RF_THREADS = 512;    // 8 waves of 54 VGPRs: fits beside two convolution workgroups on a CU
-typedef unsigned long long u64;
-struct RefineArgs {
+constexpr ClusterLayout refine_layout(int L) { return {(int64_t)2 * 3 * L, 1}; }   // [2 parity][3L] granules, the placement header
+static_assert(refine_layout(513).words() == 6 * 513 + 2 && refine_layout(513).header() == 6 * 513, "granule buffer of the minimiser");
+int64_t refine_cluster_need(int max_L) { return refine_layout(max_L).words(); }
+struct RefineArgs : ClusterArgs {
   float* ca;
   int L, steps, xcd;
-  u64* gx;             // [2][3L] granules + [2] placement header, zeroed before the launch
-  int* abort_flag;     // bit 2 is set if a hand-off ever times out
-  int allow_local;     // 0: never the XCD-local publication
   Restraint r;         // option "restrain_milli" (the RESTRAIN = true instantiation reads it)
 };
 
@@ -522,7 +519,7 @@ __host__ __device__ inline int refine_slices(int L) {
 template <bool RESTRAIN>
 __global__ __launch_bounds__(RF_THREADS) void refine_cluster_kernel(RefineArgs a) {
   extern __shared__ float sm[];          // 3L coordinates + T x 3 Lg partial sums
-  __shared__ int sh_abort;
+  __shared__ int sh_abort, sh_local;
   if ((int)(blockIdx.x & 7) != a.xcd) return;
   const int g = blockIdx.x >> 3, L = a.L, tid = threadIdx.x;
   const int Lg = (L + RF_G - 1) / RF_G;
@@ -534,17 +531,10 @@ __global__ __launch_bounds__(RF_THREADS) void refine_cluster_kernel(RefineArgs a
   float* cur = sm;
   float* part = sm + 3 * L;
   for (int i = tid; i < 3 * L; i += RF_THREADS) cur[i] = a.ca[i];
-  __shared__ int sh_local;
-  if (tid == 0) {
-    sh_abort = 0;
-    // the workgroups that own residues: all on one XCD (common.h)?  Then plain stores publish the granules
-    sh_local = cluster_on_one_xcd(a.gx + (int64_t)2 * 3 * L, (L + Lg - 1) / Lg, a.allow_local != 0) ? 1 : 0;
-  }
-  __syncthreads();
-  const bool local = sh_local != 0;
+  const bool local = cluster_begin(&sh_local, &sh_abort, a.gx + refine_layout(L).header(), (L + Lg - 1) / Lg /* the owners of residues */, a.allow_local);
   for (int step = 0; step < a.steps; ++step) {
     const unsigned epoch = (unsigned)step + 1u;
-    u64* gx = a.gx + (int64_t)(step & 1) * 3 * L;
+    granule* gx = a.gx + (int64_t)(step & 1) * 3 * L;
     for (int idx = tid; idx < T * nj; idx += RF_THREADS) {
       const int jl = idx % nj, sub = idx / nj, j = j_lo + jl;
       const int i0 = sub * chunk, i1 = (i0 + chunk < L) ? i0 + chunk : L;
@@ -583,26 +573,20 @@ __global__ __launch_bounds__(RF_THREADS) void refine_cluster_kernel(RefineArgs a
       const float nx = xj + fminf(fmaxf(ax, -100.0f), 100.0f) * 0.001f;
       const float ny = yj + fminf(fmaxf(ay, -100.0f), 100.0f) * 0.001f;
       const float nz = zj + fminf(fmaxf(az, -100.0f), 100.0f) * 0.001f;
-      const u64 tag = (u64)epoch << 32;
-      cluster_publish(&gx[3 * j], tag | (u64)__float_as_uint(nx), local);
-      cluster_publish(&gx[3 * j + 1], tag | (u64)__float_as_uint(ny), local);
-      cluster_publish(&gx[3 * j + 2], tag | (u64)__float_as_uint(nz), local);
+      cluster_publish_f32(&gx[3 * j], nx, epoch, local);
+      cluster_publish_f32(&gx[3 * j + 1], ny, epoch, local);
+      cluster_publish_f32(&gx[3 * j + 2], nz, epoch, local);
     }
     __syncthreads();                     // every thread has read the old coordinates
-    for (int i = tid; i < 3 * L; i += RF_THREADS) {
-      u64 x = 0;
-      unsigned spins = 0;
-      for (;; ++spins) {
-        x = __hip_atomic_load(&gx[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(x >> 32) == epoch) break;
-        if (spins > 4000000u || sh_abort) { sh_abort = 1; atomicOr(a.abort_flag, 4); break; }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      cur[i] = __uint_as_float((unsigned)x);
+    for (int i = tid; i < 3 * L; i += RF_THREADS) {          // one granule at a time; a time-out shows in sh_abort
+      granule x[1][1];
+      cluster_gather(x, 1, epoch, REFINE_GATHER_BOUND, &sh_abort, [&](int, int) { return &gx[i]; });
+      cur[i] = granule_f32(x[0][0]);
     }
     __syncthreads();                     // cur holds the new coordinates
-    if (sh_abort) break;
+    if (sh_abort) break;                 // the same word in every thread: nothing writes it between this barrier and the next gather
   }
+  if (sh_abort && tid == 0) atomicOr(a.abort_flag, DMP_FAULT_REFINE_HANDOFF);
   for (int i = tid; i < 3 * nj; i += RF_THREADS) a.ca[3 * j_lo + i] = cur[3 * j_lo + i];
 }
 
@@ -625,18 +609,10 @@ int refine_coords(dmp_ctx* c, float* d_ca, int L, int steps, hipStream_t s, bool
   }
   RefineArgs a{};
   a.ca = d_ca; a.L = L; a.steps = steps; a.xcd = c->refine_xcd;
-  a.gx = (u64*)c->refine_gx;
-  a.abort_flag = c->seq_abort;
-  a.allow_local = c->cluster_local;
   a.r = r;
   const int Lg = (L + RF_G - 1) / RF_G;
-  CoResident guard(c, s, false);                       // not beside a persistent vertical-GRU launch (common.h)
-  if (guard.status()) return guard.status();
-  DMP_HIP(hipMemsetAsync(c->refine_gx, 0, sizeof(u64) * (2 * 3 * L + 2), s));
-  const auto kernel = restrain ? refine_cluster_kernel<true> : refine_cluster_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(8 * RF_G), dim3(RF_THREADS), sizeof(float) * (3 * L + 3 * refine_slices(L) * Lg), s, a);
-  DMP_LAUNCH_CHECK();
-  return guard.done();
+  return cluster_launch(c, s, restrain ? refine_cluster_kernel<true> : refine_cluster_kernel<false>, RF_G, RF_THREADS,
+                        sizeof(float) * (3 * L + 3 * refine_slices(L) * Lg), c->refine_gx, refine_layout(L), a);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 // network.py:190/225; coord_gru, network.py:211/253).  The vertical GRU is in vgru.hip.
 // Gate maths follow ATen's gru_cell: r,z = sigmoid(gi+gh), n = tanh(gi_n + r*gh_n),
 // h' = (h - n)*z + n.
-#include "common.h"
+#include "cluster.h"
 
 namespace dmp {
 
@@ -30,29 +30,24 @@ __device__ __forceinline__ float tanhf_(float x) { return gate_tanh(x); }
 
 // Weight-stationary cluster: each direction is run by SEQ_G workgroups; workgroup g keeps the
 // 96 rows of W_hh that produce hidden units [32g, 32g+32) in registers (96 floats per lane)
-// for the whole sequence.  Per time step a workgroup computes its 32 new state values,
-// publishes them as 8-byte {epoch, value} granules (one agent-scope store each, the data is
-// the flag) and gathers the other 224 by sweeping the granule array until every tag equals
-// the step's epoch.  The protocol does not depend on where the workgroups run; the 8 workgroups of a
-// direction are put on one XCD (block id % 8), and when they find themselves there (cluster_on_one_xcd,
-// common.h) they publish with plain stores that stop in that XCD's L2: 1.29 instead of 2.78 us per step.
-// Every wave gathers the state for itself into its own LDS copy (LDS operations of one wave execute in
-// order): no workgroup barrier anywhere in the step loop.
+// for the whole sequence.  Per time step a workgroup computes its 32 new state values, publishes them
+// as granules and gathers the other 224 (the hand-off of cluster.h; the XCD-local
+// publication makes a step 1.29 instead of 2.78 us).  Every wave gathers the state for itself into its
+// own LDS copy (LDS operations of one wave execute in order): no workgroup barrier anywhere in the step loop.
 constexpr int SEQ_G = 8;
-typedef unsigned long long u64;
+constexpr ClusterLayout seq_gru_layout() { return {2 * 2 * HID2, 2}; }   // [2 dir][2 parity][HID2] granules, a placement header per direction
+static_assert(seq_gru_layout().words() == 4 * HID2 + 4 && seq_gru_layout().header(1) == 4 * HID2 + 2, "granule buffer of the sequence GRU");
+int64_t seq_gru_cluster_need() { return seq_gru_layout().words(); }
 #ifndef SEQ_SHFL
 #define SEQ_SHFL 0
 #endif
 
-struct SeqArgs {
+struct SeqArgs : ClusterArgs {
   const float* G;        // [T][1536] input projections incl. b_ih (fwd | rev)
   const float* whh[2];   // [768][256]
   const float* bhh[2];   // [768]
   float* out;            // [T][512]
-  u64* hx;               // [2 dir][2 parity][256] granules + [2 dir][2] placement header, zeroed before every launch
-  int* abort_flag;       // set if a hand-off ever times out
   int T;
-  int allow_local;       // 0: never the XCD-local publication
   int xcd0;              // the two directions run on XCDs xcd0, xcd0 + 1 (block id % 8)
 };
 
@@ -91,11 +86,8 @@ __global__ __launch_bounds__(256) void seq_gru_kernel(SeqArgs a) {
   float* h = hs[wave];
 #pragma unroll
   for (int q = 0; q < 4; ++q) h[lane + 64 * q] = 0.f;
-  // do the SEQ_G workgroups of this direction share an XCD (common.h)?  Then granules are published with plain stores
-  if (tid == 0) sh_local = cluster_on_one_xcd(a.hx + 4 * HID2 + 2 * dir, SEQ_G, a.allow_local != 0) ? 1 : 0;
-  __syncthreads();
-  const bool local = sh_local != 0;
-  u64* hx_dir = a.hx + (int64_t)dir * 2 * HID2;
+  const bool local = cluster_begin(&sh_local, nullptr, a.gx + seq_gru_layout().header(dir), SEQ_G, a.allow_local);
+  granule* hx_dir = a.gx + (int64_t)dir * 2 * HID2;
   // Gates, one evaluation per lane: after the row reduction all 16 lanes of a row hold the six sums of its two hidden
   // units, so lane kg < 6 evaluates gate kg >> 1 (r, z, n) of unit kg & 1 - the four sigmoids in ONE pass of the
   // (long) library function, then the two tanh, with the r / z / n values moved between the lanes by DPP row shifts -
@@ -115,7 +107,7 @@ __global__ __launch_bounds__(256) void seq_gru_kernel(SeqArgs a) {
   for (int step = 0; step < a.T; ++step) {
     const int t = dir ? (a.T - 1 - step) : step;
     const unsigned epoch = (unsigned)step + 1u;
-    u64* hx = hx_dir + (step & 1) * HID2;
+    granule* hx = hx_dir + (step & 1) * HID2;
     // input projection of this step for this lane's gate and unit (lanes kg < 6): loaded one step ahead - behind the
     // previous step's publication, while that step's granules were being awaited - so that its L2 latency is off the
     // step's critical path (round 3)
@@ -170,34 +162,34 @@ __global__ __launch_bounds__(256) void seq_gru_kernel(SeqArgs a) {
         const float hp = my_uu ? hp1 : hp0;
         const float hn = (hp - nn) * zg + nn;
         a.out[(int64_t)t * 512 + dir * HID2 + u0 + my_uu] = hn;
-        cluster_publish(&hx[u0 + my_uu], ((u64)epoch << 32) | (u64)__float_as_uint(hn), local);
+        cluster_publish_f32(&hx[u0 + my_uu], hn, epoch, local);
       }
     }
     load_gi(step + 1);               // next step's input projections fly while this step's granules are gathered
     SEQ_T(2)
     {
-      // sweep the 256 granules of this step (4 per lane) until all carry this epoch
-      unsigned vals[4];
-      bool dead = false;
-      for (unsigned spins = 0;; ++spins) {
+      // The 256 granules of this step, 4 per lane, gathered by the wave for itself: cluster_gather's sweep in this kernel's own text, with a
+      // wave-uniform exit and no abort word.  Through the shared function: 324.2 / 324.6 us per launch; so: 320.4 / 320.4 (profiles/cluster_handoff.txt).
+      float vals[4]; bool dead = false;
+      for (unsigned sweeps = 0;; ++sweeps) {
         bool ok = true;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const u64 x = __hip_atomic_load(&hx[lane + 64 * q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          vals[q] = (unsigned)x;
-          ok = ok && ((unsigned)(x >> 32) == epoch);
+          const granule x = __hip_atomic_load(&hx[lane + 64 * q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          vals[q] = granule_f32(x);
+          ok = ok && granule_has(x, epoch);
         }
         if (__all(ok)) break;
-        if (spins > 2000000u) { dead = true; break; }
+        if (sweeps > SEQ_GATHER_BOUND) { dead = true; break; }    // the sweep count is wave-uniform: the whole wave leaves
         __builtin_amdgcn_s_sleep(1);
       }
       if (dead) {                    // every wave of the cluster waits for the same granules: all of them leave
-        if (lane == 0) atomicOr(a.abort_flag, 1);
+        if (lane == 0) atomicOr(a.abort_flag, DMP_FAULT_SEQ_HANDOFF);
         break;
       }
       __builtin_amdgcn_wave_barrier();   // every lane has read this step's h before it is overwritten
 #pragma unroll
-      for (int q = 0; q < 4; ++q) h[lane + 64 * q] = __uint_as_float(vals[q]);
+      for (int q = 0; q < 4; ++q) h[lane + 64 * q] = vals[q];
       __builtin_amdgcn_wave_barrier();
       SEQ_T(3)
     }
@@ -226,19 +218,8 @@ int gru_bidir(dmp_ctx* c, int which, const float* d_in, int T, float* d_out, hip
     a.whh[0] = w[0].whh; a.whh[1] = w[1].whh;
     a.bhh[0] = w[0].bhh; a.bhh[1] = w[1].bhh;
     a.out = out; a.T = T;
-    a.hx = (u64*)c->seq_hx;
-    a.abort_flag = c->seq_abort;
-    a.allow_local = c->cluster_local;
     a.xcd0 = c->seq_xcd0;
-    {
-      CoResident guard(c, s, false);                   // not beside a persistent vertical-GRU launch (common.h)
-      if (guard.status()) return guard.status();
-      DMP_HIP(hipMemsetAsync(c->seq_hx, 0, sizeof(u64) * (2 * 2 * HID2 + 4), s));
-      hipLaunchKernelGGL(seq_gru_kernel, dim3(8 * SEQ_G), dim3(256), 0, s, a);
-      DMP_LAUNCH_CHECK();
-      int rc = guard.done();
-      if (rc) return rc;
-    }
+    if (int rc = cluster_launch(c, s, seq_gru_kernel, SEQ_G, 256, 0, c->seq_hx, seq_gru_layout(), a)) return rc;
     in = out;
   }
   return DMP_OK;

@@ -8,7 +8,7 @@
 //   4. back-transformation with the stored reflectors, sign rule, scaling by sqrt(max(lambda,1e-8))
 // Sign rule (eigenvector signs are implementation-defined in the reference): the component of
 // largest magnitude (first index on ties) is made positive.
-#include "common.h"
+#include "cluster.h"
 
 namespace dmp {
 
@@ -324,9 +324,8 @@ __global__ __launch_bounds__(256) void tridiag_step_kernel(double* __restrict__ 
 // tau) redundantly in every workgroup, then each wave updates its rows with (v_{k-1}, w_{k-1}) and forms their
 // products with v_k, the lanes along the row with the SAME lane -> column map - so d, e, tau and the reflectors are
 // the per-step launches' bit for bit.  What a launch boundary carried is handed over per step: the products
-// p_k[r] by their rows' owners and the next pivot row by its owner, as 8-byte {epoch, half of a double} granules
-// (parity-alternating arrays, epoch = step + 1), published with cluster_publish (plain stores that stop in the
-// XCD's L2 when the cluster finds itself on one XCD - common.h) and gathered with sc1 loads.
+// p_k[r] by their rows' owners and the next pivot row by its owner, each double as two granules (the hand-off of
+// cluster.h).
 // Round 2 measured this form at 5.8 us per step against 4.5 for the launches - with agent-scope (written-through)
 // stores; the XCD-local publication is what makes it pay.
 #ifndef TC_G_N
@@ -335,21 +334,14 @@ __global__ __launch_bounds__(256) void tridiag_step_kernel(double* __restrict__ 
 constexpr int TC_G = TC_G_N;
 constexpr int TC_MAX_N = 640;      // (n / 32 rows + 4 vectors) of n doubles: 123 KB of LDS at 640
 static size_t tri_cluster_lds_bytes(int n) { return sizeof(double) * ((size_t)cdiv(n, TC_G) + 4) * (size_t)n; }
-typedef unsigned long long tc_u64;
-struct TriClusterArgs {
+constexpr ClusterLayout tridiag_layout(int n) { return {(int64_t)8 * n, 1}; }   // [2 parity][2 vectors: p, pivot row][2 halves][n] granules, the placement header
+static_assert(tridiag_layout(TC_MAX_N).words() == 8 * 640 + 2 && tridiag_layout(TC_MAX_N).header() == 8 * 640, "granule buffer of the tridiagonalisation");
+int64_t tridiag_cluster_need(int max_L) { return tridiag_layout(std::min(max_L, TC_MAX_N)).words(); }
+struct TriClusterArgs : ClusterArgs {
   const double* A;     // [n][n] symmetric, read once
   double *d, *e, *tau, *V;
-  tc_u64* gx;          // [2 parity][2 vectors: p, pivot row][2 halves][n] granules + [2] placement header; zeroed before the launch
-  int* abort_flag;     // DMP_FAULT_EIG_HANDOFF is set if a hand-off times out
   int n, xcd;
-  int allow_local;     // 0: never the XCD-local publication
 };
-
-__device__ __forceinline__ void tc_publish(tc_u64* lo, tc_u64* hi, int idx, double v, unsigned epoch, bool local) {
-  const tc_u64 bits = (tc_u64)__double_as_longlong(v), tag = (tc_u64)epoch << 32;
-  cluster_publish(&lo[idx], tag | (bits & 0xffffffffull), local);
-  cluster_publish(&hi[idx], tag | (bits >> 32), local);
-}
 
 // A workgroup leaves when it owns no row below the pivot any more (nobody waits for a pure consumer, so it could
 // fall behind by more than the one step the two granule parities cover); d[k], e[k], tau[k] and reflector k are
@@ -374,13 +366,8 @@ __global__ __launch_bounds__(256) void tridiag_cluster_kernel(TriClusterArgs a) 
     const double* src = a.A + (int64_t)(g + TC_G * t) * n;
     for (int j = tid; j < n; j += 256) rows[(int64_t)t * n + j] = src[j];
   }
-  if (tid == 0) {
-    sh_abort = 0;
-    sh_local = cluster_on_one_xcd(a.gx + (int64_t)8 * n, TC_G < n ? TC_G : n, a.allow_local != 0) ? 1 : 0;
-  }
-  __syncthreads();
-  const bool local = sh_local != 0;
-  constexpr int NI = 3;                                   // 256 * 3 >= 640 = largest order of this kernel
+  const bool local = cluster_begin(&sh_local, &sh_abort, a.gx + tridiag_layout(n).header(), TC_G < n ? TC_G : n, a.allow_local);
+  constexpr int NI = 3;                                  // 256 * 3 >= 640 = largest order of this kernel
   double tkprev = 0.0;                                    // tau_{k-1}
 #define TC_T(i)
   for (int k = 0; k < n; ++k) {
@@ -391,43 +378,24 @@ __global__ __launch_bounds__(256) void tridiag_cluster_kernel(TriClusterArgs a) 
     // ---- p_{k-1} and the pivot row as step k-1 published them (row 0 of the matrix at the start)
     double vi[NI], pi[NI], xi[NI];
     {
-      tc_u64* gp = a.gx + (int64_t)((k + 1) & 1) * 4 * n;  // parity of step k-1: [p lo][p hi][row lo][row hi]
+      granule* gp = a.gx + (int64_t)((k + 1) & 1) * 4 * n;  // parity of step k-1: [p lo][p hi][row lo][row hi]
       const unsigned epoch = (unsigned)k;                 // step k-1 published with epoch (k-1) + 1
+      int mine = 0;                                       // this thread's indices below mp: the first so many of its NI
 #pragma unroll
       for (int u = 0; u < NI; ++u) {
         const int i = tid + 256 * u;
         const bool in = i < mp;
+        mine += in;
         vi[u] = (in && k > 0) ? vp[i] : 0.0;
         pi[u] = 0.0;
         xi[u] = (in && k == 0) ? a.A[i] : 0.0;
       }
       if (k > 0) {
-        // all of this thread's granules in one sweep (a sweep costs an L2 round trip whatever it loads)
-        tc_u64 q[NI][4];
-        for (unsigned spins = 0;; ++spins) {
-          bool ok = true;
+        granule q[NI][4];                                 // all of this thread's granules in one sweep; a time-out shows in sh_abort behind the barrier below
+        cluster_gather(q, mine, epoch, TRIDIAG_GATHER_BOUND, &sh_abort, [&](int u, int c) { return &gp[(int64_t)c * n + (tid + 256 * u)]; });
 #pragma unroll
-          for (int u = 0; u < NI; ++u) {
-            const int i = tid + 256 * u;
-            if (i < mp) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                q[u][c] = __hip_atomic_load(&gp[(int64_t)c * n + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = ok && (unsigned)(q[u][c] >> 32) == epoch;
-              }
-            }
-          }
-          if (ok) break;
-          if (spins > 2000000u || sh_abort) { sh_abort = 1; break; }
-          __builtin_amdgcn_s_sleep(1);
-        }
-#pragma unroll
-        for (int u = 0; u < NI; ++u) {
-          if (tid + 256 * u < mp) {
-            pi[u] = __longlong_as_double((long long)((q[u][0] & 0xffffffffull) | (q[u][1] << 32)));
-            xi[u] = __longlong_as_double((long long)((q[u][2] & 0xffffffffull) | (q[u][3] << 32)));
-          }
-        }
+        for (int u = 0; u < NI; ++u)
+          if (u < mine) { pi[u] = granule_f64(q[u][0], q[u][1]); xi[u] = granule_f64(q[u][2], q[u][3]); }
       }
     }
     TC_T(0)
@@ -486,7 +454,7 @@ __global__ __launch_bounds__(256) void tridiag_cluster_kernel(TriClusterArgs a) 
     tkprev = tk;
     TC_T(3)
     // ---- this workgroup's rows of the trailing block: update with (v_{k-1}, w_{k-1}), product with v_k, publish
-    tc_u64* gq = a.gx + (int64_t)(k & 1) * 4 * n;
+    granule* gq = a.gx + (int64_t)(k & 1) * 4 * n;
     const unsigned epoch = (unsigned)k + 1u;
     const int t_lo = k >= g ? (k - g) / TC_G + 1 : 0;     // first slot whose row lies below the pivot
     const int t_w = t_lo + ((wave - t_lo) & 3);           // this wave's first one (slot t belongs to wave t % 4)
@@ -511,13 +479,13 @@ __global__ __launch_bounds__(256) void tridiag_cluster_kernel(TriClusterArgs a) 
         }
         acc0 += a0 * vnj;
         acc1 += a1 * vnj;
-        if (r0 == 1) tc_publish(gq + 2 * n, gq + 3 * n, j - 1, a0, epoch, local);   // the next pivot row
+        if (r0 == 1) cluster_publish_f64(gq + 2 * n + (j - 1), gq + 3 * n + (j - 1), a0, epoch, local);   // the next pivot row
       }
       acc0 = wave_sum_f64(acc0);
       if (two) acc1 = wave_sum_f64(acc1);
       if (lane == 0) {
-        tc_publish(gq, gq + n, r0 - 1, tk * acc0, epoch, local);
-        if (two) tc_publish(gq, gq + n, r1 - 1, tk * acc1, epoch, local);
+        cluster_publish_f64(gq + (r0 - 1), gq + n + (r0 - 1), tk * acc0, epoch, local);
+        if (two) cluster_publish_f64(gq + (r1 - 1), gq + n + (r1 - 1), tk * acc1, epoch, local);
       }
     }
     TC_T(4)
@@ -951,14 +919,8 @@ int eigh_top8(dmp_ctx* c, const float* d_M, int L, float* d_mds, hipStream_t s) 
   } else if (c->tridiag_cluster && n <= TC_MAX_N) {
     TriClusterArgs ta{};
     ta.A = A; ta.d = d; ta.e = e; ta.tau = tau; ta.V = V;
-    ta.gx = (tc_u64*)c->tri_gx; ta.abort_flag = c->seq_abort; ta.n = n; ta.xcd = (c->refine_xcd + 4) & 7; ta.allow_local = c->cluster_local;
-    CoResident guard(c, s, false);                     // not beside a persistent vertical-GRU launch (common.h)
-    if (guard.status()) return guard.status();
-    DMP_HIP(hipMemsetAsync(c->tri_gx, 0, sizeof(tc_u64) * (8 * (size_t)n + 2), s));
-    hipLaunchKernelGGL(tridiag_cluster_kernel, dim3(8 * TC_G), dim3(256), tri_cluster_lds_bytes(n), s, ta);
-    DMP_LAUNCH_CHECK();
-    int grc = guard.done();
-    if (grc) return grc;
+    ta.n = n; ta.xcd = (c->refine_xcd + 4) & 7;
+    if (int rc = cluster_launch(c, s, tridiag_cluster_kernel, TC_G, 256, tri_cluster_lds_bytes(n), c->tri_gx, tridiag_layout(n), ta)) return rc;
   } else {
     hipGraphExec_t ge;
     int rc = tridiag_graph(c, n, A, run, d, e, tau, V, P, &ge);
