@@ -606,7 +606,11 @@ __global__ __launch_bounds__(512) void tri_eig_kernel(const double* __restrict__
   TE_T(1)
   // ---- inverse iteration: lanes 0..7 of wave 0, one eigenvalue each, in lockstep
   const double eps = 2.220446049250313e-16;
-  const double ortol = 1e-3 * tnorm;
+  // T = 0 (the zero matrix; a float32 input has no other norm below 1e-45): the scale of the two thresholds below is 1
+  // there, so that the eight (nudged) copies of the one eigenvalue are a cluster and the pivots have a floor (tiny).
+  // For any tnorm > 0 both are the former values.
+  const double tscale = tnorm > 0.0 ? tnorm : 1.0;
+  const double ortol = 1e-3 * tscale;
   double* fa = F;                      // U diagonal
   double* fb = F + (int64_t)n * NEV;   // U first super-diagonal
   double* fc = F + (int64_t)2 * n * NEV;  // multipliers
@@ -622,7 +626,9 @@ __global__ __launch_bounds__(512) void tri_eig_kernel(const double* __restrict__
   __syncthreads();
   if (tid < NEV) {
     const double l = lam[tid];
-    const double tiny = eps * fmax(tnorm, 1e-300);
+    // (T = 0: every pivot is minus the Gershgorin guard's lambda, 1e-300, and the square of its reciprocal is not a
+    // float64.  With the floor the solve scales the start vectors, which the Gram-Schmidt below orthonormalises.)
+    const double tiny = eps * fmax(tscale, 1e-300);
     // LU with partial pivoting of T - l*I (rows k, k+1 at a time)
     // (the stored U diagonal is its guarded reciprocal: the back substitution multiplies)
     auto guarded_rcp = [&](double a) {
