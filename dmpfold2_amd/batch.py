@@ -162,6 +162,11 @@ def results_json(results, top=10):
     return out
 
 
+def domain_hits_form(domain_hits, domains=None, top=10):
+    """The JSON form of a target's domain search (the dict of Engine.domain_hits; `domains`: the dict of score.unpack_domains)."""
+    return _score.domain_hits_json(domain_hits, domain_hits["names"], domains, top, domain_hits.get("refine", 0))
+
+
 def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=None, info=None, *, hits_top=10, restrain=None,
                  **results):
     """One target's output file; returns its path.  With `distmap` (L, L) and `info` = [best_pass, passes_run, map_rms]
@@ -190,7 +195,11 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     Angstrom); pdb / ca get <stem>.exposure.json (the line `dmpfold --exposure` prints).  With `domains` (the dict of
     score.unpack_domains, --domains): npz gains dom_label (int32 (L,): every residue's domain) and dom_table (int32 (domains, 8):
     size, segments, lowest residue, contact pairs inside and to the rest, ext and denominator of the cut, level); pdb / ca get
-    <stem>.domains.json (the line `dmpfold --domains` prints)."""
+    <stem>.domains.json (the line `dmpfold --domains` prints).  With `domain_hits` (the dict of Engine.domain_hits, --library
+    --search-domains; beside `domains`): npz gains dom_hit_rank (int32 (D, K): per domain the entries by falling TM-score) and
+    dom_hit_tm (float32 (D, K): pair (d, k)'s TM-score normalised by the domain's size, in the library's order); pdb / ca get
+    <stem>.domain_hits.json (score.domain_hits_json, the best `hits_top` per domain)."""
+    domain_hits = results.pop("domain_hits", None)
     unknown = set(results) - {row.name for row in _score.BLOCKS}
     if unknown:
         raise TypeError(f"write_result: no result is called {sorted(unknown)}")
@@ -251,12 +260,18 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
                           "hit_names": np.asarray(hits["names"], dtype=np.str_)})
             if "refined" in hits:                        # (--search-refine)
                 extra["hit_refined"] = np.asarray(hits["refined"], dtype=np.bool_)
+        if domain_hits is not None:
+            D, K = domain_hits["domains"], len(domain_hits["names"])
+            extra.update({"dom_hit_rank": np.asarray(domain_hits["rank"], dtype=np.int32).reshape(D, K),
+                          "dom_hit_tm": np.asarray(domain_hits["headers"][:D, :, 2], dtype=np.float32).reshape(D, K)})
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
     if distmap is not None:
         save_distmap_npy(stem + ".distmap.npy", distmap)
     forms = results_json(results, hits_top)
+    if domain_hits is not None:
+        forms["domain_hits"] = domain_hits_form(domain_hits, domains, hits_top)
     for name, value in (("exposure", forms.get("exposure")), ("domains", forms.get("domains")), ("restrain", restrain)):
         if value is not None:
             forms[name] = {name: value}                  # (these lines carry their name)
@@ -414,6 +429,10 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         library.check(MAX_L)
         max_L = max(max_L, library.max_m)               # the engines' capacity bounds every entry's length
     domains = _DOMAINS                                  # (batch_domains)
+    search_domains = library is not None and bool(getattr(library, "domains", False))      # (--search-domains)
+    if search_domains and domains is None:
+        domains = domains_options()                     # the library's flag turns "domains" on, with the defaults
+        domains = (domains[0] * 1e-3,) + domains[1:]
     t0 = time.perf_counter()
     pipe, dev, copy_stream = None, None, None
     failed, outputs, parsed, faulted = [], [], {}, []
@@ -426,6 +445,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             sd = state_dict if state_dict is not None else load_state_dict(weights_file)
             pipe = Pipeline(dev, max_L, max_N, sd, streams=streams, precision=drop_in_precision())
             # (score_map and the restraint turn the distance map on: it is written only with `distmap`)
+            if domains is not None:
+                pipe.use_domains(True, *domains)            # (in front of set_search: a library with `domains` keeps these parameters)
             for setter, wanted, *value in (("converge", converge is not None, converge), ("distmap", distmap, True),
                                            ("score", natives, True), ("score_map", score_map, True),
                                            ("score_passes", score_passes, True), ("ss", ss, True), ("exposure", exposure, True),
@@ -433,8 +454,6 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                                            ("search", library is not None, library)):
                 if wanted:
                     getattr(pipe, "set_" + setter)(*value)
-            if domains is not None:
-                pipe.use_domains(True, *domains)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -451,6 +470,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     # including the pipeline's set-up against 6.7 for the same targets resident in HBM, tools/batch_throughput.py.)
     def start_copy_back(t):
         outs = pipe.peek(t)                           # (coords, confs), with `distmap` also (map, info)
+        if search_domains:
+            outs = outs + (pipe.outputs_of(t).domain_search_block,)      # which `peek` never hands out: last of all
         if outs[0].is_cuda:
             host = tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in outs)
             with (torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext()):
@@ -468,13 +489,16 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     scored, aligned = set(), set()                      # the tickets that had a native / a structure
     asked = {"natives": bool(natives), "structures": bool(structures), "library": library is not None, "ss": ss,
-             "exposure": exposure, "restrain": restraining, "domains": domains is not None}
+             "exposure": exposure, "restrain": restraining, "domains": domains is not None, "search_domains": search_domains}
     blocks_on = {"score": asked["natives"], "align": asked["structures"], "search": asked["library"], "score_map": score_map,
                  "passes": score_passes, "ss": ss, "exposure": exposure, "domains": domains is not None}
     gathered = {}                                       # {key of `stats_out`: {stem: what the summary takes}}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
+        ds_block = None
+        if search_domains:
+            public, ds_block = public[:-1], public[-1]
         out = Outputs.of(public, distmap=distmap or score_map or restraining, **blocks_on)
         aln_path, alnmat, _ = parsed.pop(t)
         stem = os.path.splitext(os.path.basename(aln_path))[0]
@@ -483,6 +507,12 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                                         coords=out.coords, confs=out.confs)
                    for row in _score.BLOCKS if getattr(out, row.field) is not None and had.get(row.key, True)}
         forms = results_json(results, search_top)
+        if ds_block is not None:
+            ds = dict(_score.unpack_domain_search(ds_block, alnmat.shape[1], len(library), library.refine), names=list(library.names))
+            if "refined" in ds:
+                ds["refine"] = library.refine
+            results["domain_hits"] = ds
+            forms["domain_hits"] = domain_hits_form(ds, results.get("domains"), search_top)
         rep = None
         if restraining:
             rep = forms["restrain"] = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap,
@@ -596,7 +626,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             if isinstance(res[t], Exception):
                 failed.append((parsed.pop(t)[0], res[t]))
             else:
-                write(t, res[t])
+                write(t, res[t] + ((pipe.collected[t].domain_search_block,) if search_domains else ()))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:
@@ -661,6 +691,10 @@ def batch_parser():
     # the hits gain "refined", npz gains hit_refined.  The help text and the parsed namespace of the other flags are recorded
     # (tests/golden/host_plumbing.json.gz): the flag stays out of both unless given, and README.md describes it.
     ap.add_argument("--search-refine", type=int, default=argparse.SUPPRESS, metavar="R", help=argparse.SUPPRESS)
+    # --search-domains (with --library): search the library with every domain of every target's model as well (the parse by the
+    # parameters of --domains, or the defaults); npz gains dom_hit_rank and dom_hit_tm, pdb / ca write <stem>.domain_hits.json,
+    # the summary carries every target's best hit per domain.  Hidden like --search-refine, for the same reason.
+    ap.add_argument("--search-domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     # --domains [--domains-tau Q --domains-min-size N --domains-min-segment N]: split every target's model into structural domains
     # on the GPU; the summary gains every target's domain count with mean, median and the share of multi-domain targets, npz
     # gains dom_label and dom_table, pdb / ca write <stem>.domains.json.  Hidden like --search-refine, for the same reason.
@@ -803,9 +837,14 @@ GATHERED = (("scores", "natives", score_summary),
             ("alignments", "structures", lambda found: {"aligned_targets": len(found), "alignments": found}),
             ("hits", "library", lambda found: {"searched_targets": len(found), "hits": found}),
             ("ss", "ss", ss_summary), ("exposure", "exposure", exposure_summary), ("restrain", "restrain", restrain_summary),
-            ("domains", "domains", domains_summary))
+            ("domains", "domains", domains_summary),
+            ("domain_hits", "search_domains", lambda found: {"domain_searched_targets": len(found), "domain_hits": found}))
 GATHERED_AS = {"alignment": ("alignments", lambda form: {k: form[k] for k in ("m",) + _score.ALIGN_NAMES}),
-               "hits": ("hits", lambda form: [{k: v for k, v in hit.items() if k not in ("R", "t")} for hit in form["hits"]])}
+               "hits": ("hits", lambda form: [{k: v for k, v in hit.items() if k not in ("R", "t")} for hit in form["hits"]]),
+               # every domain's best hit
+               "domain_hits": ("domain_hits", lambda form: [dict({k: d[k] for k in ("domain", "size") if k in d},
+                                                                 **({k: v for k, v in d["hits"][0].items() if k not in ("R", "t")}
+                                                                    if d["hits"] else {})) for d in form["domains"]])}
 
 
 def gather(key, mine, world, job_store):
@@ -833,6 +872,11 @@ def main(argv=None):
         if not 0 <= args.search_refine <= _score.SEARCH_MAX:
             ap.error(f"--search-refine must be 0 or 1 .. {_score.SEARCH_MAX}, got {args.search_refine}")
         library = _score.Library.open(args.library, refine=args.search_refine)
+    if hasattr(args, "search_domains"):
+        if not args.library:
+            ap.error("--search-domains needs --library")
+        library = library if isinstance(library, _score.Library) else _score.Library.open(args.library)
+        library.domains = True
 
     dom_given = {k: getattr(args, "domains_" + k) for k in ("tau", "min_size", "min_segment") if hasattr(args, "domains_" + k)}
     if dom_given and not hasattr(args, "domains"):

@@ -12,7 +12,8 @@
 // Option "search_structures" runs the same three stages over the K entries of a library, the entry as blockIdx.y, in chunks of
 // as many entries as the scratch budget holds, between search_prep (lengths validated, trace offsets, NaN fill) and search_rank.
 // Option "search_refine" = R makes that two passes: stage 1 and align_screen over every entry, search_select, the three stages
-// over the R entries chosen.
+// over the R entries chosen.  Option "search_domains" runs the same passes once more with every domain of the model as the model: the
+// bodies take the model's row count n from the slot header (AH_N); a.L is only the bound that sizes strides, LDS and grids.
 // Float64 from the float32 coordinates, contraction off, every sum in the fixed order of score_block_sum; every candidate
 // of a DP cell is one float64 add of two defined values, so H does not depend on the order the cells are evaluated in.
 // Every loop is bounded whatever the input holds, and every branch with a barrier inside is uniform over the workgroup.
@@ -73,28 +74,42 @@ __host__ __device__ inline void align_slot_args(AlignArgs& a, unsigned char* sl,
 // The three kernels' bodies are device functions of one AlignArgs: the single-partner launches pass theirs as the kernel
 // argument, the batch launches of option "search_structures" form one per entry (blockIdx.y) from the search block and the
 // entry's slot - the same code either way, so an entry's floats are "align_structure"'s bit for bit.
-__device__ __forceinline__ void align_prep_body(const AlignArgs& a) {
-  __shared__ int bad[SC_THREADS];
-  const int L = a.L, tid = threadIdx.x;
+// The structure half: NaN into the header, m validated, the structure's trace packed.  This thread's share of "a coordinate is
+// NaN" comes back; m (0 if invalid) and m_ok go out.
+__device__ __forceinline__ int align_prep_structure(const AlignArgs& a, int& m, bool& m_ok) {
+  const int tid = threadIdx.x;
   const float nan = __builtin_nanf("");
   for (int i = tid; i < ALIGN_HEADER; i += SC_THREADS) a.out[i] = nan;
-  for (int i = tid; i < 2 * L; i += SC_THREADS) a.ali[i] = nan;
   const float mf = a.mf;
-  const bool m_ok = mf >= 3.f && mf <= (float)a.max_m && mf == floorf(mf);      // a NaN fails the comparisons
-  const int m = m_ok ? (int)mf : 0;                                              // 0: nothing beyond [0] is read
+  m_ok = mf >= 3.f && mf <= (float)a.max_m && mf == floorf(mf);                 // a NaN fails the comparisons
+  m = m_ok ? (int)mf : 0;                                                        // 0: nothing beyond [0] is read
   int mine = 0;
   for (int i = tid; i < 3 * m; i += SC_THREADS) {
     const float x = a.trace[i];
     mine |= x != x ? 1 : 0;
     a.qs[i] = x;
   }
-  for (int i = tid; i < 3 * L; i += SC_THREADS) a.pm[i] = a.coords[15 * (int64_t)(i / 3) + 3 + i % 3];
+  return mine;
+}
+// The model half: the n rows row(0) < row(1) < ... of the backbone are the model - all L of them, or the residues of one domain
+// (option "search_domains") - packed into pm; NaN into their ali and deviation (a.ali[i], a.ali[a.L + i], i < n: a.L is the
+// stride, n the rows).  Then the scratch header, n in it: every stage reads the model's row count from there.
+template <class Row>
+__device__ __forceinline__ void align_prep_body(const AlignArgs& a, int n, Row row) {
+  __shared__ int bad[SC_THREADS];
+  const int L = a.L, tid = threadIdx.x;
+  const float nan = __builtin_nanf("");
+  int m;
+  bool m_ok;
+  const int mine = align_prep_structure(a, m, m_ok);
+  for (int i = tid; i < n; i += SC_THREADS) a.ali[i] = a.ali[L + i] = nan;
+  for (int i = tid; i < 3 * n; i += SC_THREADS) a.pm[i] = a.coords[15 * (int64_t)row(i / 3) + 3 + i % 3];
   bad[tid] = mine;
   __syncthreads();
   if (tid == 0) {
     int any = 0;
     for (int k = 0; k < SC_THREADS; ++k) any |= bad[k];
-    const int n = L, lmin = n < m ? n : m;
+    const int lmin = n < m ? n : m;
     const int minov = lmin / 2 > (lmin < 5 ? lmin : 5) ? lmin / 2 : (lmin < 5 ? lmin : 5);
     const double d0s = score_d0((double)lmin);
     a.hdr[AH_VALID] = m_ok && !any ? 1.0 : 0.0;
@@ -107,6 +122,10 @@ __device__ __forceinline__ void align_prep_body(const AlignArgs& a) {
     a.hdr[AH_DCUT] = fmin(fmax(d0s, 4.5), 8.0);
     a.surv[0] = 0;
   }
+}
+// the whole chain as the model
+__device__ __forceinline__ void align_prep_body(const AlignArgs& a) {
+  align_prep_body(a, a.L, [](int i) { return i; });
 }
 
 // the pairs of seed s: (i0 + t, i0 + k + t), t < ov
@@ -215,7 +234,7 @@ template <class PairI, class PairJ>
 __device__ __forceinline__ void align_finish(const AlignArgs& a, PairI pi, PairJ pj, int wK, int seed, float screened, int n, int m,
                                              int minov, double d_cut, float* pm2, float* qn2, unsigned char* fl,
                                              double (*wred)[16], double* bc) {
-  const int tid = threadIdx.x, L = a.L;
+  const int tid = threadIdx.x, L = a.L;                      // L: the stride between ali and deviation; the model has n rows
   const double d0n = score_d0((double)n), d0m = score_d0((double)m);
   align_pack(a, pi, pj, wK, pm2, qn2, fl);
   SeedBest bn;
@@ -242,7 +261,7 @@ __device__ __forceinline__ void align_finish(const AlignArgs& a, PairI pi, PairJ
     out[21] = screened;
     for (int c = 22; c < ALIGN_HEADER + 1; ++c) out[c] = 0.f;
   }
-  for (int i = tid; i < L; i += SC_THREADS) a.ali[i] = -1.f;      // (the deviations of these rows stay NaN)
+  for (int i = tid; i < n; i += SC_THREADS) a.ali[i] = -1.f;      // (the deviations of these rows stay NaN)
   __syncthreads();
   double R[9], tr[3];
   for (int c = 0; c < 9; ++c) R[c] = bc[c];
@@ -595,6 +614,22 @@ __device__ __forceinline__ int search_place(const float* tm, int K, int k) {
   return pos;
 }
 
+// The two rules as every thread of a workgroup applies them (tm: K floats of LDS, filled and behind a barrier): the R entries
+// that rank first into sel, in rank order; every entry's index into rank, as a float.  Each a permutation: every place is
+// written once.
+__device__ __forceinline__ void search_select_into(const float* tm, int K, int R, int* sel) {
+  for (int k = threadIdx.x; k < K; k += SC_THREADS) {
+    const int pos = search_place(tm, K, k);
+    if (pos < R) sel[pos] = k;
+  }
+}
+__device__ __forceinline__ void search_rank_into(const float* tm, int K, float* rank) {
+  for (int k = threadIdx.x; k < K; k += SC_THREADS) {
+    const int pos = search_place(tm, K, k);
+    if (pos < K) rank[pos] = (float)k;
+  }
+}
+
 // search_select, one workgroup (option "search_refine"): sel[r] = the entry with the r-th largest screened tm_model, r < R, by
 // the rule of search_rank.  With an invalid m_k somewhere nothing was screened: the identity (those entries return early).
 __global__ __launch_bounds__(SC_THREADS) void search_select_kernel(SearchArgs sa) {
@@ -608,10 +643,7 @@ __global__ __launch_bounds__(SC_THREADS) void search_select_kernel(SearchArgs sa
   const float* screen = search_screen_tm(sa);
   for (int k = tid; k < K; k += SC_THREADS) tm[k] = screen[k];
   __syncthreads();
-  for (int k = tid; k < K; k += SC_THREADS) {
-    const int pos = search_place(tm, K, k);
-    if (pos < R) sel[pos] = k;                               // a permutation: every r < R is written once
-  }
+  search_select_into(tm, K, R, sel);
 }
 
 // search_rank, one workgroup: rank[r] = the entry with the r-th largest tm_model, by counting - entry k comes behind every
@@ -630,11 +662,11 @@ __global__ __launch_bounds__(SC_THREADS) void search_rank_kernel(SearchArgs sa) 
   }
   for (int k = tid; k < K; k += SC_THREADS) tm[k] = b[lay.hdr + (int64_t)ALIGN_HEADER * k + 2];
   __syncthreads();
-  for (int k = tid; k < K; k += SC_THREADS) {
-    const int pos = search_place(tm, K, k);
-    if (pos < K) b[lay.rank + pos] = (float)k;               // a permutation: always
-  }
+  search_rank_into(tm, K, b + lay.rank);
 }
+
+struct DomSearchArgs;                                        // option "search_domains", below
+__global__ void domsearch_align_refine_kernel(DomSearchArgs da, int first);
 
 int align_kernel_attrs(dmp_ctx* c) {
   static_assert(AL_SLICE * SC_THREADS >= DMP_MAX_L + 1, "a thread's slice of a diagonal");
@@ -644,6 +676,8 @@ int align_kernel_attrs(dmp_ctx* c) {
   DMP_HIP(hipFuncSetAttribute((const void*)align_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               align_lds(DMP_MAX_L, DMP_MAX_L).total));
   DMP_HIP(hipFuncSetAttribute((const void*)align_refine_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              align_lds(DMP_MAX_L, DMP_MAX_L).total));
+  DMP_HIP(hipFuncSetAttribute((const void*)domsearch_align_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               align_lds(DMP_MAX_L, DMP_MAX_L).total));
   if (c->device >= 0 && c->device < 64) done[c->device] = true;
   return DMP_OK;
@@ -681,7 +715,7 @@ int search_wg_per_cu(int L, int max_m, int* out) {
 // search_prep, then the three stages per chunk of C consecutive entries (one slot each), then search_rank.  With option
 // "search_refine" = R, 0 < R < K: stage 1 and align_screen per chunk over all K, search_select, then the three stages per
 // chunk over the R selected entries.  Everything is sized from (L, max_m, K, R) here; nothing comes back from the device.
-int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
+static SearchArgs search_args(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay) {
   SearchArgs sa{};
   sa.coords = d_coords;
   sa.conf = d_conf;
@@ -694,6 +728,11 @@ int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, c
   sa.ws = c->search_ws.p;
   sa.slot = search_slot(L, sa.max_m);
   sa.fault = c->seq_abort;
+  return sa;
+}
+
+int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
+  SearchArgs sa = search_args(c, d_coords, L, d_conf, lay);
   const int C = search_chunk_entries(L, sa.max_m, c->run.search_chunk);
   DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws.bytes,
           "search_structures: the scratch does not hold a chunk of %d entries at L = %d, search_max_m = %d", C, L, sa.max_m);
@@ -731,6 +770,263 @@ int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, c
     DMP_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(search_rank_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// option "search_domains": the same stages with every domain of the model as the model (include/dmpfold_hip.h has the definition)
+// ---------------------------------------------------------------------------------------
+// Behind search_structures, on its stream, in its slots and with its table of the entries (validity, B0, trace offsets): the
+// whole-model search has finished with the slots and the table stays as search_prep left it.  The virtual entry p = d per + r
+// - domain d, the r-th of the `per` entries of a domain: all K of them, or the R that search_select chose for d - takes slot
+// p - first of its chunk, domain-major, so a chunk may straddle domains.  The model of pair (d, k) is the domain's rows
+// gathered through the residue list; n_d goes into the slot header, and the shared bodies above read every row count from
+// there.  ali and deviation of pair (d, k) go COMPACTLY into entry k's place of the block, at the domain's offset in the
+// sorted list - the domains partition the chain, so the pairs of one entry never overlap, and a chunk's slot may be reused
+// while they wait there - and domsearch_finish permutes each entry's 2L floats through LDS into residue order.
+// The scratch of its own (dmp_ctx::domsearch_ws): per domain the screened tm_model of every entry and the entries selected
+// (option "search_refine"), then 32 ints - [0] D, or 0 if nothing can be searched (the block stays NaN), [1] the one-domain
+// shortcut is taken, [2 + d] the offset of domain d in the list, d <= 16 - then the residue list sorted by (label, index).
+constexpr int64_t DS_SCREEN_OFF = 0, DS_SEL_OFF = 4 * (int64_t)DOMAINS_MAX * SEARCH_MAX, DS_INFO_OFF = 2 * DS_SEL_OFF,
+                  DS_LIST_OFF = DS_INFO_OFF + 128;
+ScratchNeed search_domains_need(int max_L) { return {DS_LIST_OFF + 4 * (int64_t)max_L, 0}; }
+
+struct DomSearchArgs {
+  SearchArgs sa;
+  float* blk;            // the domain-search block
+  const float* dom;      // the domain block of the same call
+  unsigned char* dws;    // the scratch above
+  int dmax;              // the domains the grids are sized for: max(1, min(16, L / min_size))
+  int mode;              // the option's value: 2 never takes the shortcut
+  int per, use_sel;      // entries per domain in this pass; taken through the domain's row of the select table
+};
+__device__ __forceinline__ float* ds_screen(const DomSearchArgs& da) { return reinterpret_cast<float*>(da.dws + DS_SCREEN_OFF); }
+__device__ __forceinline__ int* ds_sel(const DomSearchArgs& da) { return reinterpret_cast<int*>(da.dws + DS_SEL_OFF); }
+__device__ __forceinline__ int* ds_info(const DomSearchArgs& da) { return reinterpret_cast<int*>(da.dws + DS_INFO_OFF); }
+__device__ __forceinline__ int* ds_list(const DomSearchArgs& da) { return reinterpret_cast<int*>(da.dws + DS_LIST_OFF); }
+
+// domsearch_prep, one workgroup: NaN into the whole block; D and the labels from the domain block, validated (D an integer
+// in [1, dmax], every label an integer in [0, D), every domain of at least 3 rows - always, after domains.hip; and every
+// m_k valid, by search_prep's table - else D = 0 and nothing more runs); the counting sort: thread d counts label d, thread 0
+// scans the 16 counts, thread d writes its residues in rising order.  Integers only.
+__global__ __launch_bounds__(SC_THREADS) void domsearch_prep_kernel(DomSearchArgs da) {
+  __shared__ unsigned char lab[DMP_MAX_L];
+  __shared__ int cnt[DOMAINS_MAX], bad[SC_THREADS], sh_D;
+  const int tid = threadIdx.x, L = da.sa.L < DMP_MAX_L ? da.sa.L : DMP_MAX_L;
+  const DomSearchLayout lay = domsearch_layout(da.sa.L, da.sa.K);
+  const float nan = __builtin_nanf("");
+  for (int64_t i = tid; i < lay.total; i += SC_THREADS) da.blk[i] = nan;
+  const float Df = da.dom[0];
+  int D = Df >= 1.f && Df <= (float)da.dmax && Df <= (float)DOMAINS_MAX && Df == floorf(Df) ? (int)Df : 0;      // a NaN fails the comparisons
+  if (search_tab(da.sa)[0] != 1) D = 0;
+  int mine = 0;
+  for (int i = tid; i < L; i += SC_THREADS) {
+    const float lf = da.dom[DOMAINS_HEADER + i];
+    const bool ok = lf >= 0.f && lf < (float)D && lf == floorf(lf);
+    mine |= ok ? 0 : 1;
+    lab[i] = ok ? (unsigned char)lf : (unsigned char)0xff;
+  }
+  bad[tid] = mine;
+  __syncthreads();
+  if (tid < DOMAINS_MAX) {
+    int n = 0;
+    for (int i = 0; i < L; ++i) n += lab[i] == tid ? 1 : 0;
+    cnt[tid] = n;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int* info = ds_info(da);
+    int any = 0, run = 0;
+    for (int k = 0; k < SC_THREADS; ++k) any |= bad[k];
+    for (int d = 0; d < DOMAINS_MAX; ++d) {
+      const int n = cnt[d];
+      any |= d < D && n < 3 ? 1 : 0;
+      info[2 + d] = run;
+      cnt[d] = run;
+      run += n;
+    }
+    info[2 + DOMAINS_MAX] = run;
+    if (any || run != L) D = 0;
+    info[0] = D;
+    info[1] = D == 1 && da.mode != 2 ? 1 : 0;
+    sh_D = D;
+  }
+  __syncthreads();
+  if (sh_D == 0) return;                                     // uniform
+  if (tid < DOMAINS_MAX) {
+    int* list = ds_list(da);
+    int at = cnt[tid];
+    for (int i = 0; i < L; ++i)
+      if (lab[i] == tid) list[at++] = i;                     // at most cnt's n of them: the same labels were counted
+  }
+}
+
+// Virtual entry first + blockIdx.y -> pair (d, k) in slot blockIdx.y, the domain's n rows at `rows`.  False (uniform over the
+// workgroup) before a slot is touched for an index that is no pair: d >= D, the shortcut, nothing to search.
+__device__ __forceinline__ bool domsearch_entry(const DomSearchArgs& da, int first, AlignArgs& a, int& d, int& k, int& n, const int*& rows) {
+  const SearchArgs& sa = da.sa;
+  const int y = (int)blockIdx.y;
+  const int64_t at = (int64_t)first + y;
+  if (y >= SEARCH_CHUNK_MAX || first < 0 || da.per < 1 || da.per > sa.K || sa.K > SEARCH_MAX || at >= (int64_t)da.dmax * da.per) return false;
+  d = (int)(at / da.per);
+  const int r = (int)(at % da.per);
+  const int* info = ds_info(da);
+  if (d >= DOMAINS_MAX || d >= info[0] || info[1]) return false;
+  k = da.use_sel ? ds_sel(da)[d * SEARCH_MAX + r] : r;
+  if (k < 0 || k >= sa.K) return false;                      // never: domsearch_select writes entries
+  const int off = info[2 + d];
+  n = info[3 + d] - off;
+  if (off < 0 || n < 3 || off + n > sa.L) return false;      // never: domsearch_prep checked
+  rows = ds_list(da) + off;
+  const int64_t* tab = search_tab(sa);
+  const bool ok = tab[0] == 1;                               // (always: D = 0 otherwise)
+  float* b = sa.conf + tab[1];
+  const SearchLayout lay = search_layout(sa.L, sa.K);
+  const DomSearchLayout dl = domsearch_layout(sa.L, sa.K);
+  unsigned char* sl = sa.ws + SEARCH_HEAD_BYTES + (size_t)y * (size_t)sa.slot.total;
+  a.coords = sa.coords;
+  a.mf = ok ? b[k] : 0.f;
+  a.out = da.blk + dl.hdr + (int64_t)ALIGN_HEADER * ((int64_t)d * sa.K + k);
+  a.ali = da.blk + dl.res + 2 * (int64_t)sa.L * k + off;     // compact: rows [off, off + n) of entry k's ali and, L further, deviation
+  a.trace = b + lay.in + (ok ? 3 * tab[2 + k] : 0);
+  align_slot_args(a, sl, sa.slot, sa.L, sa.max_m, reinterpret_cast<unsigned*>(sa.ws + SEARCH_TAB_BYTES) + 2 * y);
+  return true;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void domsearch_align_prep_kernel(DomSearchArgs da, int first) {
+  AlignArgs a;
+  int d, k, n;
+  const int* rows;
+  if (domsearch_entry(da, first, a, d, k, n, rows)) align_prep_body(a, n, [rows](int i) { return rows[i]; });
+}
+__global__ __launch_bounds__(SC_THREADS) void domsearch_align_thread_kernel(DomSearchArgs da, int first) {
+  AlignArgs a;
+  int d, k, n;
+  const int* rows;
+  if (domsearch_entry(da, first, a, d, k, n, rows)) align_thread_body(a);
+}
+__global__ __launch_bounds__(SC_THREADS) void domsearch_align_refine_kernel(DomSearchArgs da, int first) {
+  AlignArgs a;
+  int d, k, n;
+  const int* rows;
+  if (domsearch_entry(da, first, a, d, k, n, rows)) align_refine_body(a);
+}
+__global__ __launch_bounds__(SC_THREADS) void domsearch_align_screen_kernel(DomSearchArgs da, int first) {
+  AlignArgs a;
+  int d, k, n;
+  const int* rows;
+  if (!domsearch_entry(da, first, a, d, k, n, rows)) return;
+  align_screen_body(a);
+  if (threadIdx.x == 0) ds_screen(da)[d * SEARCH_MAX + k] = a.out[2];      // what this thread wrote, or align_prep's NaN
+}
+
+// domsearch_select, one workgroup per domain: search_select's rule on the domain's row of the screen table
+__global__ __launch_bounds__(SC_THREADS) void domsearch_select_kernel(DomSearchArgs da, int R) {
+  __shared__ float tm[SEARCH_MAX];
+  const int tid = threadIdx.x, K = da.sa.K < SEARCH_MAX ? da.sa.K : SEARCH_MAX, d = (int)blockIdx.x;
+  const int* info = ds_info(da);
+  if (d >= DOMAINS_MAX || d >= info[0] || info[1]) return;   // uniform
+  const float* screen = ds_screen(da) + d * SEARCH_MAX;
+  int* sel = ds_sel(da) + d * SEARCH_MAX;
+  for (int k = tid; k < K; k += SC_THREADS) tm[k] = screen[k];
+  __syncthreads();
+  search_select_into(tm, K, R, sel);
+}
+
+// domsearch_rank, one workgroup per domain: search_rank's rule on the domain's K headers
+__global__ __launch_bounds__(SC_THREADS) void domsearch_rank_kernel(DomSearchArgs da) {
+  __shared__ float tm[SEARCH_MAX];
+  const int tid = threadIdx.x, K = da.sa.K < SEARCH_MAX ? da.sa.K : SEARCH_MAX, d = (int)blockIdx.x;
+  const int* info = ds_info(da);
+  if (d >= DOMAINS_MAX || d >= info[0] || info[1]) return;   // uniform
+  const DomSearchLayout dl = domsearch_layout(da.sa.L, da.sa.K);
+  for (int k = tid; k < K; k += SC_THREADS) tm[k] = da.blk[dl.hdr + (int64_t)ALIGN_HEADER * ((int64_t)d * K + k) + 2];
+  __syncthreads();
+  search_rank_into(tm, K, da.blk + (int64_t)d * K);
+}
+
+// domsearch_finish, one workgroup per entry.  The shortcut (D = 1, the domain is the chain): the whole search's rank, header,
+// ali and deviation of this entry into row 0.  Else: the entry's 2L compact floats into residue order, through LDS - position
+// j of the sorted list is residue list[j], and the list is a permutation of 0 .. L - 1.
+__global__ __launch_bounds__(SC_THREADS) void domsearch_finish_kernel(DomSearchArgs da) {
+  __shared__ float buf[2 * DMP_MAX_L];
+  const int tid = threadIdx.x, K = da.sa.K, k = (int)blockIdx.x, L = da.sa.L < DMP_MAX_L ? da.sa.L : DMP_MAX_L;
+  const int* info = ds_info(da);
+  if (k >= K || info[0] == 0) return;                        // uniform
+  const DomSearchLayout dl = domsearch_layout(da.sa.L, K);
+  float* res = da.blk + dl.res + 2 * (int64_t)L * k;
+  if (info[1]) {                                             // uniform
+    const float* b = da.sa.conf + search_tab(da.sa)[1];
+    const SearchLayout lay = search_layout(da.sa.L, K);
+    for (int i = tid; i < 2 * L; i += SC_THREADS) res[i] = b[lay.res + 2 * (int64_t)L * k + i];
+    for (int i = tid; i < ALIGN_HEADER; i += SC_THREADS)
+      da.blk[dl.hdr + (int64_t)ALIGN_HEADER * k + i] = b[lay.hdr + (int64_t)ALIGN_HEADER * k + i];
+    if (tid == 0) da.blk[k] = b[lay.rank + k];
+    return;
+  }
+  for (int i = tid; i < 2 * L; i += SC_THREADS) buf[i] = res[i];
+  __syncthreads();
+  const int* list = ds_list(da);
+  for (int j = tid; j < L; j += SC_THREADS) {
+    int i = list[j];
+    i = i < 0 ? 0 : (i >= L ? L - 1 : i);                    // never
+    res[i] = buf[j];
+    res[L + i] = buf[L + j];
+  }
+}
+
+// domsearch_prep, then search_structures' passes over the Dmax K virtual entries (with "search_refine" = R: screen over Dmax K,
+// domsearch_select, refine over Dmax R), domsearch_rank, domsearch_finish.  Dmax = max(1, min(16, L / min_size)) bounds D: a
+// cut is admissible only if both parts hold min_size residues (domains.hip, domains_cuts_kernel: `if (size < a.min_size ||
+// n - size < a.min_size ...) continue;`), so D min_size <= L.  Nothing comes back from the device.
+int search_domains(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
+  DomSearchArgs da{};
+  da.sa = search_args(c, d_coords, L, d_conf, lay);
+  SearchArgs& sa = da.sa;
+  da.blk = d_conf + lay.domsearch.off;
+  da.dom = d_conf + lay.domains.off;
+  da.dws = c->domsearch_ws.p;
+  da.dmax = std::max(1, std::min(DOMAINS_MAX, L / c->run.dom_min_size));
+  da.mode = c->run.search_domains;
+  const int C = search_chunk_entries(L, sa.max_m, c->run.search_chunk);
+  DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws.bytes && da.dws &&
+              c->domsearch_ws.bytes >= search_domains_need(L).bytes,
+          "search_domains: the scratch does not hold a chunk of %d entries at L = %d, search_max_m = %d", C, L, sa.max_m);
+  hipLaunchKernelGGL(domsearch_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, da);
+  DMP_LAUNCH_CHECK();
+  const size_t thread_lds = sizeof(float) * 6 * L + round_up(L, 16);
+  const int R = c->run.search_refine > 0 && c->run.search_refine < sa.K ? c->run.search_refine : 0;
+  if (R) {
+    da.per = sa.K;
+    const int all = da.dmax * sa.K;
+    for (int first = 0; first < all; first += C) {
+      const int cn = std::min(C, all - first);
+      hipLaunchKernelGGL(domsearch_align_prep_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, da, first);
+      DMP_LAUNCH_CHECK();
+      hipLaunchKernelGGL(domsearch_align_thread_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, da, first);
+      DMP_LAUNCH_CHECK();
+      hipLaunchKernelGGL(domsearch_align_screen_kernel, dim3(1, cn), dim3(SC_THREADS), thread_lds, s, da, first);
+      DMP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(domsearch_select_kernel, dim3(da.dmax), dim3(SC_THREADS), 0, s, da, R);
+    DMP_LAUNCH_CHECK();
+    da.use_sel = 1;
+  }
+  da.per = R ? R : sa.K;
+  const int todo = da.dmax * da.per;
+  for (int first = 0; first < todo; first += C) {
+    const int cn = std::min(C, todo - first);
+    hipLaunchKernelGGL(domsearch_align_prep_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, da, first);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(domsearch_align_thread_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, da, first);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(domsearch_align_refine_kernel, dim3(AL_T, cn), dim3(SC_THREADS), align_lds(L, sa.max_m).total, s, da, first);
+    DMP_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(domsearch_rank_kernel, dim3(da.dmax), dim3(SC_THREADS), 0, s, da);
+  DMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(domsearch_finish_kernel, dim3(sa.K), dim3(SC_THREADS), 0, s, da);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

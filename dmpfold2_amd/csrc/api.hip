@@ -458,6 +458,11 @@ static int search_reserve(dmp_ctx* c) {
     need = std::max<int64_t>(need, (int64_t)search_chunk_entries(L, mm, 0) * search_slot(L, mm).total);
   return scratch_reserve(c, c->search_ws, SEARCH_HEAD_BYTES + need, SEARCH_HEAD_BYTES, "search scratch");
 }
+// Option "search_domains": its own scratch - the per-domain tables and the residue list (align.hip has the layout) - reserved when
+// the option first becomes positive on a context; the slots it works in are the search scratch's.
+static int search_domains_reserve(dmp_ctx* c) {
+  return c->opt.search_domains ? scratch_reserve(c, c->domsearch_ws, search_domains_need(c->max_L), "domain-search scratch") : DMP_OK;
+}
 // Option "score_passes": reserved when the option first becomes 1 on a context (score.hip has the layout).
 static int passes_reserve(dmp_ctx* c) {
   return c->opt.passes ? scratch_reserve(c, c->pass_ws, score_passes_need(c->max_L), "pass-score scratch") : DMP_OK;
@@ -591,6 +596,8 @@ static const Option OPTIONS[] = {
     {"search_max_m", TAIL(search_mm), ANY, OPT_RW, check_search_max_m, nullptr, search_reserve},
     {"search_chunk", TAIL(search_chunk), 0, INT32_MAX, 0, "search_chunk must be >= 0, got %d"},                // tests only: entries per chunk, 0 = what the budget gives
     {"search_refine", TAIL(search_refine), 0, DMP_SEARCH_MAX, 0, "search_refine must be 0 or 1 .. " DMP_STR(DMP_SEARCH_MAX) ", got %d"},   // refine the best R by the screen only
+    {"search_domains", TAIL(search_domains), 0, 2, 0, "search_domains must be 0, 1 or 2 (tests only: 1 without the one-domain shortcut), got %d", OPT_RW,
+     nullptr, nullptr, search_domains_reserve},                                                                  // needs "domains" = 1 and "search_structures" > 0
     {"passes_run", CTX(passes_done), ANY, OPT_READ_ONLY},                                   // trunk passes of the last prediction
     {"search_chunk_used", CTX(search_last_C), ANY, OPT_READ_ONLY},                          // of the last prediction that searched: entries per chunk
     {"search_wg_per_cu", nullptr, nullptr, ANY, OPT_READ_ONLY, nullptr, nullptr, nullptr, get_search_wg_per_cu},
@@ -787,7 +794,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
   for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->entity_ws, &c->ss_ws, &c->exposure_ws,
-                     &c->domains_ws})
+                     &c->domains_ws, &c->domsearch_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1324,6 +1331,9 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   DMP_ARG(!c->opt.passes || c->opt.score, "score_passes scores every pass against the native trace of option score_native, which is 0: set score_native to 1");
   DMP_ARG(!c->opt.domains || c->opt.dom_min_segment <= c->opt.dom_min_size,
           "domains_min_segment is %d, above domains_min_size = %d: a segment is part of a domain", c->opt.dom_min_segment, c->opt.dom_min_size);
+  DMP_ARG(!c->opt.search_domains || c->opt.domains, "search_domains searches with the domains of option domains, which is 0: set domains to 1");
+  DMP_ARG(!c->opt.search_domains || c->opt.search > 0,
+          "search_domains searches the library of option search_structures, which is 0: set search_structures to the number of entries");
   DMP_ARG(c->vg_waiters == 0, "members of the vertical-GRU group this context led have not taken their results yet");
   DMP_ARG(c->vg_leader == nullptr || c->vg_leader == c, "this context still waits for the vertical GRU of its group");
   c->vg_leader = nullptr;
@@ -1564,6 +1574,8 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)
   if (c->run.search > 0 && (rc = search_structures(c, d_coords, L, d_conf, lay, s))) return rc;
+  // option "search_domains": the domain-search block in front of the align block, from the domain block and the search block
+  if (c->run.search_domains && (rc = search_domains(c, d_coords, L, d_conf, lay, s))) return rc;
   hipLaunchKernelGGL(fault_latch_kernel, dim3((unsigned)cdiv64(std::max<int64_t>(15 * L, lay.total), 256)), dim3(256), 0, s,
                      c->seq_abort, d_coords, d_conf, L, lay, c->end_fault_out);
   DMP_LAUNCH_CHECK();

@@ -427,13 +427,14 @@ def agree_options(rows):
     return Flags(all(emits), any(emits), *rows[0][1:])
 
 
-def _stage(device, L, template_ca, flags, extras, domains=False):
+def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is laid out (score.Layout) for the options as the context holds them (`flags`) -
     the library cannot check it - and its input blocks are filled from `extras`: with "score_native" on the native trace (no
     `native` = no row present: n_pairs 0, NaN scores); with "align_structure" on m and the rows of `structure` (none: m = 0,
     which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU.
-    `domains`: option "domains" on (it travels beside `flags`, whose fields callers know by position)."""
+    `domains`: option "domains" on (it travels beside `flags`, whose fields callers know by position); `search_domains`: option
+    "search_domains" on - the buffer then holds the domain-search block in front of the align block."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -447,7 +448,8 @@ def _stage(device, L, template_ca, flags, extras, domains=False):
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, flags.passes, domains=domains, **{key: getattr(flags, key) for key in OWN_BLOCK})
+                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None,
+                 **{key: getattr(flags, key) for key in OWN_BLOCK})
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
     if library is not None:
@@ -604,6 +606,24 @@ class Engine:
         torch.cuda.synchronize(self.device)
         return row.unpack(block, self._last.L, library=self._last.library, coords=self._last.coords, confs=self._last.out.confs)
 
+    @property
+    def domain_search_block(self):
+        """"search_domains": (400 + 2L) K floats - the library searched with every domain of the last prediction's model - or None."""
+        return self._last.out.domain_search_block
+
+    @property
+    def domain_hits(self):
+        """The domain search of the last prediction as score.unpack_domain_search gives it, with the library's `names` and -
+        where it gave `refined` - `refine` beside it; None if it ran without option "search_domains".  Synchronises with the GPU."""
+        block, library = self.domain_search_block, self._last.library
+        if block is None or library is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        hits = dict(_score.unpack_domain_search(block, self._last.L, len(library), library.refine), names=list(library.names))
+        if "refined" in hits:
+            hits["refine"] = library.refine
+        return hits
+
     def set_domains(self, on, tau=0.25, min_size=40, min_segment=10):
         """Option "domains" on this engine, as it stands from now on: every prediction's final C-alpha trace is split into
         structural domains on the GPU (and, with a whole `native`, the native's); what a call returns does not change, the
@@ -687,6 +707,9 @@ class Engine:
             want["search_structures"] = len(extras.library)
             if extras.library.refine:
                 want["search_refine"] = extras.library.refine      # screen every entry, refine the best so many
+        if extras.library is not None and getattr(extras.library, "domains", False) and not self.get_option("search_domains"):
+            turn_on("domains")                                     # (with the parameters set_domains / with_domains hold, or the defaults)
+            want["search_domains"] = 1                             # the library searched with every domain of the model as well
         before = {}
         try:
             for name, value in want.items():
@@ -718,7 +741,7 @@ class Engine:
         with torch.cuda.device(self.device):
             self._forget_last()
             domains = bool(self.get_option("domains"))
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains)
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, bool(self.get_option("search_domains")))
             self._last = _Last(out._replace(coords=None), L, library if search else None, out.coords if domains else None)
             milli = self.get_option("restrain_milli")
             if milli > 0:
@@ -1008,7 +1031,14 @@ class Pipeline:
     def set_search(self, library):
         """Option "search_structures" on every engine: targets submitted from now on are aligned with every entry of `library`
         (a score.Library; None = off) - with a `refine` of R on the library, screened and only the best R refined (option
-        "search_refine"); idle pipeline only."""
+        "search_refine"); with `domains` on the library, also with every domain of the model (option "search_domains", which
+        turns "domains" on with the parameters `use_domains` set, or the defaults; the domain-search block is the attribute
+        `domain_search_block` of what `outputs_of` gives); idle pipeline only."""
+        with_domains = library is not None and bool(getattr(library, "domains", False))
+        if self.engines[0].get_option("search_domains") != int(with_domains):
+            if with_domains and not all(e.get_option("domains") for e in self.engines):
+                self.set_option("domains", 1)
+            self.set_option("search_domains", int(with_domains))
         if library is None:
             self.set_option("search_structures", 0)
             self.set_option("search_max_m", 0)
@@ -1021,6 +1051,8 @@ class Pipeline:
             if library.refine or self.engines[0].get_option("search_refine"):
                 self.set_option("search_refine", library.refine)
         self._search = library
+
+    collected = {}                   # of the last `collect`: {ticket: the score.Outputs its entry was made of}, for what `public` leaves out
 
     def close(self):
         if self._p:
@@ -1069,7 +1101,8 @@ class Pipeline:
                                for e in self.engines[1:]):
                 raise RuntimeError("the engines must agree on \"domains_tau_milli\", \"domains_min_size\" and \"domains_min_segment\" "
                                    "(whichever of them runs a target must give the same parse); use use_domains")
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains)
+            search_domains = agree([e.get_option("search_domains") for e in self.engines], "search_domains", "set_search")
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -1127,6 +1160,11 @@ class Pipeline:
 
     def result(self, ticket):
         return self._result(ticket).public()
+
+    def outputs_of(self, ticket):
+        """The score.Outputs of a queued target, which stays queued: every block as a view of its buffer, the domain-search
+        block of option "search_domains" - which `result` never hands out - among them (valid once the target is done)."""
+        return self._jobs[ticket].out
 
     def _result(self, ticket):
         job = self._jobs.pop(ticket)
@@ -1192,6 +1230,7 @@ class Pipeline:
         remaining repeats run in it directly (the weights, not the alignment, put a trunk outside the
         f16 range: the others would only fault again first), with one note on stderr for all of them."""
         _lib.check(self.lib.dmp_pipeline_wait(self._p, 2))
+        self.collected = {}
         cur = torch.cuda.current_stream(self.device)
         for e in self.engines:
             cur.wait_stream(e._stream)
@@ -1232,6 +1271,7 @@ class Pipeline:
                         out[t] = exc
                         continue
                 out[t] = res.public()
+                self.collected[t] = res
         finally:
             eng.set_option("conv_mode", mode0)
         return out
@@ -1377,7 +1417,7 @@ def aln_to_domains(input_file, *args, domains_tau=0.25, domains_min_size=40, dom
 def _coords_tuple(call, domains=None):
     """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave) -> what it returns."""
     v = SimpleNamespace(**call)
-    r, parse = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
+    r, parse, _ = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
                                   v.native, v.native_chain, v.compare, v.compare_chain, v.search, distmap=v.return_distmap,
                                   scores=v.return_scores, alignment=v.return_alignment, hits=v.return_hits,
                                   map_scores=v.return_map_scores, pass_scores=v.return_pass_scores, ss=v.return_ss,
@@ -1411,11 +1451,14 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
                               restrain, restrain_cutoff, exposure)[0]
 
 
+
 def _predict_file_with(domains, input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain,
                        compare, compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
                        pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
-    """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None).  `domains`: None, or what domains_options
-    gave - the prediction then runs with option "domains" (Engine.with_domains)."""
+    """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None, the domain search or None).  `domains`: None, or
+    what domains_options gave - the prediction then runs with option "domains" (Engine.with_domains).  A `search` library with
+    `domains` on is also searched with every domain of the model: the third part is then (the dict of Engine.domain_hits, the
+    dict of score.unpack_domains of the same prediction)."""
     restrain_options(restrain, restrain_cutoff)                              # (a bad value raises before any work)
     for option, wanted in (("score_map", map_scores), ("score_passes", pass_scores)):
         if wanted and native is None:
@@ -1451,6 +1494,7 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
                                       score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain,
                                       restrain_cutoff=restrain_cutoff, exposure=bool(exposure))
         parse = eng.domains if domains is not None else None
+        domain_hits = (eng.domain_hits, eng.domains) if eng.domain_search_block is not None else None
         exposed = None
         if exposure:
             torch.cuda.synchronize(eng.device)
@@ -1461,7 +1505,7 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
                           pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
                           scores=eng.scores if native is not None and scores else None,
-                          alignment=eng.alignment if compare is not None and alignment else None), parse
+                          alignment=eng.alignment if compare is not None and alignment else None), parse, domain_hits
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1540,6 +1584,10 @@ def dmpfold_parser():
     # the JSON line gains "refine" and every hit "refined".  The help text and the parsed namespace of the other flags are
     # recorded (tests/golden/host_plumbing.json.gz): the flag stays out of both unless given, and README.md describes it.
     parser.add_argument("--search-refine", type=int, default=argparse.SUPPRESS, required=False, metavar="R", help=argparse.SUPPRESS)
+    # --search-domains (with --search): search the library with every domain of the model as well (option "search_domains", which
+    # splits the model by the parameters of --domains, or the defaults); the JSON line of --search gains the key "domain_hits".
+    # Hidden like --search-refine, for the same reason; README.md describes it.
+    parser.add_argument("--search-domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     parser.add_argument("--hits", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --search to FILE instead of standard error")
     parser.add_argument("--ss", action="store_true", default=False,
@@ -1598,8 +1646,13 @@ def run_dmpfold(argv=None):
         if not 0 <= args.search_refine <= _score.SEARCH_MAX:
             parser.error(f"--search-refine must be 0 or 1 .. {_score.SEARCH_MAX}, got {args.search_refine}")
         search = _score.Library.open(args.search, refine=args.search_refine)
+    if hasattr(args, "search_domains"):
+        if args.search is None:
+            parser.error("--search-domains needs --search")
+        search = search if isinstance(search, _score.Library) else _score.Library.open(args.search)
+        search.domains = True
     domains = domains_arguments(parser, args)
-    r, parse = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
+    r, parse, domain_hits = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
                                   args.model_weights, args.converge, args.native, args.native_chain, args.compare,
                                   args.compare_chain, search, distmap=args.distmap is not None, scores=args.native is not None,
                                   alignment=args.compare is not None, hits=args.search is not None, map_scores=args.score_map,
@@ -1611,7 +1664,11 @@ def run_dmpfold(argv=None):
         with (open(path, "w") if path is not None else contextlib.nullcontext(sys.stderr)) as fh:
             fh.write(json.dumps(obj) + "\n")
     if args.search is not None:
-        json_line(_score.BLOCK["search"].json(r.hits, top=args.search_top), args.hits)
+        js = _score.BLOCK["search"].json(r.hits, top=args.search_top)
+        if domain_hits is not None:                        # (--search-domains)
+            ds, dom = domain_hits
+            js["domain_hits"] = _score.domain_hits_json(ds, ds["names"], dom, args.search_top, ds.get("refine", 0))["domains"]
+        json_line(js, args.hits)
     if args.distmap is not None:
         save_distmap_npy(args.distmap, r.distmap)
     if args.compare is not None:

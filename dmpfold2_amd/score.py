@@ -131,28 +131,36 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
       (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | exposure_off (X0): exposure block (32 + 16L) |
-      domains_off (D0): domain block (32 + 2L + 256) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
+      domains_off (D0): domain block (32 + 2L + 256) | domain_search_off: domain-search block ((400 + 2L) K, with `search_domains`) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
 
-    and `total` is the floats the buffer must hold."""
+    and `total` is the floats the buffer must hold.  `search_domains` (option "search_domains" on; an attribute beside the
+    fields, like `domains`) puts the domain-search block, sized from the K of `search`, between the domain block and the
+    align block."""
 
     def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None,
-                ss=False, exposure=False, domains=False):
+                ss=False, exposure=False, domains=False, search_domains=False):
         self = super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
                                None if passes is None else int(passes), bool(ss), bool(exposure))
         self.domains = bool(domains)
+        self.search_domains = bool(search_domains)
         return self
 
     domains = False                  # (of a Layout made by `_make`)
+    search_domains = False
 
     def _replace(self, **changes):
         domains = changes.pop("domains", self.domains)
+        search_domains = changes.pop("search_domains", self.search_domains)
         new = super()._replace(**changes)
         new.domains = bool(domains)
+        new.search_domains = bool(search_domains)
         return new
 
     def floats(self, row):
         """The floats a row of BLOCKS takes in this buffer: 0 where its block is off."""
+        if row is DOMAIN_SEARCH:
+            return domain_search_floats(self.L, self.search[0]) if self.search_domains and self.search is not None else 0
         value = getattr(self, row.arg)
         return 0 if value is None or value is False else row.floats(self.L, value)
 
@@ -163,6 +171,9 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
         for row in BLOCKS[:-1]:
             yield row, at
             at += self.floats(row)
+            if row.key == "domains" and self.floats(DOMAIN_SEARCH):      # (no row of BLOCKS: see DOMAIN_SEARCH)
+                yield DOMAIN_SEARCH, at
+                at += self.floats(DOMAIN_SEARCH)
         yield None, at
 
     def _begin(self, key):
@@ -175,6 +186,7 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     ss_off = property(lambda s: s._begin("ss"))                                                             # U0
     exposure_off = property(lambda s: s._begin("exposure"))                                                 # X0
     domains_off = property(lambda s: s._begin("domains"))                                                   # D0
+    domain_search_off = property(lambda s: s.domains_off + s.floats(BLOCK["domains"]))
     align_off = property(lambda s: s._begin("align"))                                                       # A0
     # the end of the align block as its writer allocated it ...
     align_end = property(lambda s: s._begin(None))
@@ -214,6 +226,11 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     def domains_block(self, buf):
         """The domain block of a `d_conf` buffer as a view (32 + 2L + 256 floats), None with `domains` off."""
         return self._view("domains", buf)
+
+    def domain_search_block(self, buf):
+        """The domain-search block of a `d_conf` buffer as a view ((400 + 2L) K floats), None with `search_domains` off."""
+        floats = self.floats(DOMAIN_SEARCH)
+        return buf[self.domain_search_off:self.domain_search_off + floats] if floats else None
 
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
@@ -256,16 +273,20 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
     out behind them all."""
     __hash__ = tuple.__hash__
     domains_block = None
+    domain_search_block = None       # with "search_domains": (400 + 2L) K floats; an attribute too, and never handed out by `public`
 
-    def __new__(cls, *parts, domains_block=None, **named):
+    def __new__(cls, *parts, domains_block=None, domain_search_block=None, **named):
         self = super().__new__(cls, *parts, **named)
         self.domains_block = domains_block
+        self.domain_search_block = domain_search_block
         return self
 
     def _replace(self, **changes):
         domains_block = changes.pop("domains_block", self.domains_block)
+        domain_search_block = changes.pop("domain_search_block", self.domain_search_block)
         new = super()._replace(**changes)
         new.domains_block = domains_block
+        new.domain_search_block = domain_search_block
         return new
 
     def __eq__(self, other):        # (a part is an array or a tensor, whose == is elementwise: parts are the same by identity)
@@ -995,7 +1016,10 @@ def search_offset(L, distmap=False, score=False, align_m=None, max_L=None, score
 class Library:
     """A fold library: names, lengths and one concatenated float32 C-alpha trace (M, 3), M = sum of the lengths.
     `refine` (option "search_refine"): 0 = every entry is refined; R = every entry is screened by its best gapless threading
-    and only the R best by that are refined."""
+    and only the R best by that are refined.  `domains` (option "search_domains"): the library is also searched with every
+    domain of the model (the host layers then turn option "domains" on themselves)."""
+
+    domains = False
 
     def __init__(self, names, lengths, ca, refine=0):
         self.names = [str(n) for n in names]
@@ -1064,11 +1088,12 @@ class Library:
             return cls([str(n) for n in z["names"]], z["lengths"], z["ca"])
 
     @classmethod
-    def open(cls, path, refine=0):
-        """A directory of PDB files or an .npz written by `save`; `refine`: the library's `refine`."""
+    def open(cls, path, refine=0, domains=False):
+        """A directory of PDB files or an .npz written by `save`; `refine`, `domains`: the library's `refine` and `domains`."""
         import os
         library = cls.from_dir(path) if os.path.isdir(path) else cls.load(path)
         library.refine = refine
+        library.domains = bool(domains)
         return library
 
     def save(self, path):
@@ -1153,6 +1178,103 @@ def hits_json(search, names, top=10, refine=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# option "search_domains" (include/dmpfold_hip.h): the library searched with every domain of the model.  Pair (d, k) is what
+# "align_structure" gives for the domain's gathered trace and entry k, ali and deviation scattered back to the domain's residues;
+# the same kind of search, the same lower bound per pair, not compared with TM-align.
+# ---------------------------------------------------------------------------------------------------------------------
+def domain_search_floats(L, K):
+    """Floats of the domain-search block of a prediction of length L searching K entries: rank [16][K], 16 K headers of 24
+    floats, K x (ali [L], deviation [L]) - all of it out."""
+    L, K = int(L), int(K)
+    return DOMAINS_MAX * K * (1 + ALIGN_HEADER) + 2 * L * K
+
+
+def domain_search_offset(L, distmap=False, score=False, score_map=False, passes=None, ss=False, exposure=False):
+    """Where the domain-search block begins in the `d_conf` buffer: the end of the domain block."""
+    return Layout(L, distmap, score, score_map, passes=passes, ss=ss, exposure=exposure, domains=True).domain_search_off
+
+
+def pack_domain_search(L, K, rank=None, headers=None, ali=None, deviation=None):
+    """A domain-search block (float32) from its parts, NaN where a part is None: rank (16, K), headers (16, K, 24), ali (K, L),
+    deviation (K, L) - the inverse of the raw views of `unpack_domain_search` (tests, restatements)."""
+    L, K = int(L), int(K)
+    block = np.full(domain_search_floats(L, K), np.nan, dtype=np.float32)
+    r = DOMAINS_MAX * K
+    if rank is not None:
+        block[:r] = np.asarray(rank, dtype=np.float32).reshape(r)
+    if headers is not None:
+        block[r:r * (1 + ALIGN_HEADER)] = np.asarray(headers, dtype=np.float32).reshape(r * ALIGN_HEADER)
+    res = block[r * (1 + ALIGN_HEADER):].reshape(K, 2, L)
+    if ali is not None:
+        res[:, 0] = np.asarray(ali, dtype=np.float32).reshape(K, L)
+    if deviation is not None:
+        res[:, 1] = np.asarray(deviation, dtype=np.float32).reshape(K, L)
+    return block
+
+
+def unpack_domain_search(block, L, K, refine=0):
+    """A domain-search block (array or tensor) of a search of K entries -> dict: domains (D: the rows of `rank` that are no
+    NaN; 0 for a block the library answered with NaN - a bad m_k, a latched fault), rank (D, K) int - per domain the entries by
+    falling tm_model, the pair's TM-score normalised by the domain's size, ties to the lower index, NaN last -, hits (per
+    domain a list of K dicts: n_ali, rmsd_ali, tm_model, tm_struct, R, t, d0_model, d0_struct, seed_offset, seeds), ali (K, L)
+    int - the row of entry k aligned with residue i under the alignment of i's own domain, or -1 - and deviation (K, L); the
+    raw views `headers` (16, K, 24) and `rank_raw` (16, K).  `refine`: the "search_refine" the prediction ran with; with 0 <
+    refine < K also refined (D, K) bool."""
+    L, K = int(L), int(K)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != domain_search_floats(L, K):
+        raise ValueError(f"a domain-search block of length {L}, {K} entries has {domain_search_floats(L, K)} floats, got shape {tuple(b.shape)}")
+    r = DOMAINS_MAX * K
+    rank_raw = b[:r].reshape(DOMAINS_MAX, K)
+    headers = b[r:r * (1 + ALIGN_HEADER)].reshape(DOMAINS_MAX, K, ALIGN_HEADER)
+    res = b[r * (1 + ALIGN_HEADER):].reshape(K, 2, L)
+    whole = np.all(rank_raw == rank_raw, axis=1)
+    D = int(whole.sum()) if np.all(whole[:int(whole.sum())]) else 0
+    hits = []
+    for d in range(D):
+        row = []
+        for k in range(K):
+            h = headers[d, k]
+            row.append({"n_ali": _whole(h[0]), "rmsd_ali": float(h[1]), "tm_model": float(h[2]), "tm_struct": float(h[3]),
+                        "R": h[4:13].reshape(3, 3).copy(), "t": h[13:16].copy(), "d0_model": float(h[16]), "d0_struct": float(h[17]),
+                        "seed_offset": _whole(h[18]), "seeds": _whole(h[19])})
+        hits.append(row)
+    ali = res[:, 0]
+    out = {"domains": D, "rank": rank_raw[:D].astype(np.int64), "hits": hits, "ali": np.where(ali == ali, ali, -1.0).astype(np.int64),
+           "deviation": res[:, 1].copy(), "headers": headers.copy(), "rank_raw": rank_raw.copy()}
+    if 0 < int(refine) < K:
+        out["refined"] = headers[:D, :, 20] == 0
+    return out
+
+
+def domain_hits_json(ds, names, domains=None, top=10, refine=0):
+    """`unpack_domain_search` as a JSON-ready dict (the key "domain_hits" of `dmpfold --search ... --search-domains` and of
+    `dmpfold-batch`): per domain its number and - with `domains`, the dict of `unpack_domains` of the same prediction - its size
+    and segment list, then its best `top` entries in rank order, each with name, index, tm_domain (normalised by the domain's
+    size), tm_struct, rmsd_ali, n_ali, R, t and, where `unpack_domain_search` gave `refined`, refined; NaN becomes None."""
+    refined = ds.get("refined") if 0 < int(refine) < len(names) else None
+    out = []
+    for d in range(ds["domains"]):
+        js = {"domain": d}
+        if domains is not None and d < len(domains["table"]):
+            js["size"] = int(domains["table"][d]["size"])
+            js["segments"] = [list(seg) for seg in domains["table"][d]["segment_list"]]
+        js["hits"] = []
+        for k in [int(k) for k in ds["rank"][d][:max(int(top), 0)]]:
+            h = ds["hits"][d][k]
+            js["hits"].append({"name": str(names[k]), "index": k, "tm_domain": _num(h["tm_model"]), "tm_struct": _num(h["tm_struct"]),
+                               "rmsd_ali": _num(h["rmsd_ali"]), "n_ali": int(h["n_ali"]),
+                               "R": [[_num(v) for v in row] for row in np.asarray(h["R"])], "t": [_num(v) for v in np.asarray(h["t"])]})
+            if refined is not None:
+                js["hits"][-1]["refined"] = bool(refined[d][k])
+        out.append(js)
+    js = {"entries": len(names), "domains": out}
+    if refined is not None:
+        js["refine"] = int(refine)
+    return js
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The blocks behind the confidences, each stated once.  A row of BLOCKS: `key` - what the host calls the block (a keyword of
 # Outputs.public and Outputs.of, of a Pipeline's set_<key>); `option` - the library option that turns it on; `field` - its view
 # in an `Outputs`; `name` - what its unpacked form is called wherever it is handed on (a property of predict.Engine, a field of
@@ -1206,3 +1328,10 @@ BLOCKS = (
           lambda hits, top=10, **_: hits_json(hits, hits["names"], top, hits.get("refine", 0))),
 )
 BLOCK = {row.key: row for row in BLOCKS}
+# The domain-search block of option "search_domains" has no row of BLOCKS - whose rows, and their order, callers and recorded
+# tables know by position: it lies in the buffer between the domain block and the align block (Layout._walk), its view is an
+# attribute of an `Outputs` that `public` never hands out, and predict.Engine has its two properties beside the rows'.
+DOMAIN_SEARCH = Block("search_domains", "search_domains", "domain_search_block", "domain_hits", "search_domains", "(400 + 2L)K",
+                      lambda L, K: domain_search_floats(L, K),
+                      lambda block, L, library=None, **_: unpack_domain_search(block, L, len(library), library.refine),
+                      lambda ds, names=(), domains=None, top=10, refine=0, **_: domain_hits_json(ds, names, domains, top, refine))

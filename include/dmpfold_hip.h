@@ -575,7 +575,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
@@ -696,7 +696,58 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * behind the tickets; the slots and the budget are the same.  Stage 1 runs twice for the R selected entries: R / K of the
  * screen pass, for one definition of a refined entry.
  * THIS IS TM-ALIGN'S KIND OF SEARCH, a lower bound of the best TM-score per entry, not compared with that program
- * (see "align_structure").  Measured cost: profiles/search.txt, profiles/search_refine.txt. */
+ * (see "align_structure").  Measured cost: profiles/search.txt, profiles/search_refine.txt.
+ * "search_domains" (0, the default, or 1; 2 is FOR TESTS ONLY; any other value: DMP_ERR_ARG): search the library of
+ * "search_structures" with EVERY DOMAIN of the model as well - the tm_model of a multi-domain model against a library of
+ * single-domain folds is nearly meaningless, and "domains" says when that is so.  Read when a prediction begins and held for
+ * it; dmp_predict_begin_units answers DMP_ERR_ARG if it is on without "domains" = 1 or without "search_structures" > 0.
+ * With it 0 nothing is launched, read, written or allocated and every offset is what it was.  With it on, THE d_conf ARGUMENT
+ * MUST HOLD (400 + 2L) K MORE FLOATS AT THE END OF THE DOMAIN BLOCK (D0 + 32 + 2L + 256): there sits the DOMAIN-SEARCH BLOCK,
+ * all of it outputs, its size a matter of (L, K) alone, and A0 and B0 move behind it.  Offsets relative to its start:
+ *   [0, 16K)                      rank[d][r] at K d + r: the entry with the r-th largest tm_model of domain d
+ *   [16K, 400K)                   pair (d, k)'s header at 16K + 24 (K d + k): the 24 floats of an align block's offsets 1 .. 24
+ *   [400K, 400K + 2LK)            entry k's ali[L] then deviation[L] at 400K + 2Lk
+ * THE DEFINITION, the only one.  Let D be the model's domain count and label_model its labels, as the domain block of the
+ * same call holds them.  The trace of domain d is the C-alpha rows i with label_model[i] == d, in rising i; it has n_d rows.
+ * The result of pair (d, k), d < D, is EXACTLY WHAT "align_structure" GIVES FOR A MODEL CONSISTING OF THAT TRACE AND THE
+ * STRUCTURE OF ENTRY k: the same 24 header floats with the same meaning - tm_model normalised by n_d, d0_model = d0(n_d),
+ * seeds counted from n_d - and its ali and deviation scattered back to the residues of the domain.  The domains partition the
+ * chain, so entry k needs one ali[L] and one deviation[L] for all of them: residue i carries the structure's row and the
+ * deviation under the alignment and the superposition OF ITS OWN DOMAIN's pair with entry k (-1 and NaN where that alignment
+ * leaves it out).  rank[d] follows the rule of search_rank: falling tm_model, ties to the lower index, NaN entries last in
+ * index order.  Rows d >= D - ranks and headers - are NaN.  "search_refine" = R, 0 < R < K, applies to every domain
+ * separately by the rule above: every entry is screened against domain d, the R entries that screen best for d are refined,
+ * the others keep the screen's numbers and 1 at header offset 21; R = 0 or R >= K is the full sweep, bit for bit.
+ * If any m_k is invalid, or the prediction latched a device-side fault, every float of the block is NaN (the block lies
+ * inside what the fault latch covers).  A NaN among entry k's coordinates makes the headers of its 16 pairs and its 2L
+ * floats NaN.  The structure, the domain block, the search block and every other block keep their bits.
+ * THE ONE-DOMAIN SHORTCUT: with D = 1 the domain is the chain and the answer is the whole search's by definition; the sweep's
+ * workgroups return at once and the last launch copies the search block's ranks, headers, ali and deviation into row 0.
+ * Value 2 never takes the shortcut, so that a test can hold the gather path to the whole search bit for bit.
+ * THIS IS TM-ALIGN'S KIND OF SEARCH, a lower bound of the best TM-score per pair, not that program's bits, and nobody has
+ * compared its recall with another program's (see "align_structure"); the parse it searches with is "domains"', with every
+ * caveat stated there.
+ * Launches (csrc/align.hip), behind "search_structures" on the same stream and IN ITS SLOTS - the whole-model search has
+ * finished with them, and its table of the entries stays: domsearch_prep (one workgroup: NaN into the block; D and the labels
+ * read from the domain block and validated; the residue list sorted by (label, index) and its 17 offsets by a counting sort -
+ * integers only); then the stages of "search_structures" over the virtual entries p = K d + k, domain-major, in the same
+ * chunks of C slots (a chunk may straddle domains): align_prep - its structure half unchanged, its model half gathering the
+ * domain's rows through the list, n_d and what follows from it in the slot header -, align_thread, align_refine (with R:
+ * align_screen over all, domsearch_select per domain, then the three stages over the R chosen); domsearch_rank (one workgroup
+ * per domain); domsearch_finish (one per entry).  The bodies that compute are the ones "align_structure" runs: they read the
+ * model's row count from the slot header, and L only sizes strides, LDS and grids.  A pair's ali and deviation are written
+ * compactly at the domain's offset in the sorted list, inside entry k's 2L floats of the block - the slots are reused chunk
+ * after chunk, the block is not - and domsearch_finish permutes them into residue order through LDS.  Nothing comes back from
+ * the device: the grids are sized for Dmax = max(1, min(16, L / "domains_min_size")) domains - a split never leaves a part
+ * below min_size, so D <= Dmax - and the workgroups of d >= D return before they touch a slot; dmp_predict_end stays
+ * asynchronous.  Scratch of its own beside the search's: the screen and select tables per domain (2 x 16 x 4 DMP_SEARCH_MAX
+ * bytes), 128 bytes of counts and offsets, the list (4 max_L bytes) - 0.5 MiB, allocated when the option first becomes
+ * positive on a context and counted in "device_mib".
+ * Measured cost (profiles/search_domains.txt; L = 300, made-up libraries): a model that stays whole pays 0.05 to 2.3 ms beside
+ * a search of 3 to 116 ms (1 to 5 %: the copy and the launches that return at once); a model split in 2 (150 + 150) pays 0.8
+ * to 2.7 times the whole search again, in 3 (78 + 144 + 78, grids for 4) 1.0 to 3.7 times, in 16 (18 .. 27 residues) 2.1 to
+ * 9.2 times - a pair of a small domain costs about half a whole-model pair, because align_refine's dynamic programme pays one
+ * barrier per anti-diagonal and an entry of m rows has at least m of them whatever n_d is. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
