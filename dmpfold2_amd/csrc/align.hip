@@ -14,6 +14,8 @@
 // Option "search_refine" = R makes that two passes: stage 1 and align_screen over every entry, search_select, the three stages
 // over the R entries chosen.  Option "search_domains" runs the same passes once more with every domain of the model as the model: the
 // bodies take the model's row count n from the slot header (AH_N); a.L is only the bound that sizes strides, LDS and grids.
+// Both searches go through one frame, templates over a query (WholeQuery, DomainQuery): search_pair, search_align_{prep,thread,
+// refine,screen}_kernel, search_select_kernel, search_rank_kernel, and search_passes on the host.
 // Float64 from the float32 coordinates, contraction off, every sum in the fixed order of score_block_sum; every candidate
 // of a DP cell is one float64 add of two defined values, so H does not depend on the order the cells are evaluated in.
 // Every loop is bounded whatever the input holds, and every branch with a barrier inside is uniform over the workgroup.
@@ -72,8 +74,8 @@ __host__ __device__ inline void align_slot_args(AlignArgs& a, unsigned char* sl,
 // align_prep
 // ---------------------------------------------------------------------------------------
 // The three kernels' bodies are device functions of one AlignArgs: the single-partner launches pass theirs as the kernel
-// argument, the batch launches of option "search_structures" form one per entry (blockIdx.y) from the search block and the
-// entry's slot - the same code either way, so an entry's floats are "align_structure"'s bit for bit.
+// argument, the search launches of options "search_structures" and "search_domains" form one per pair (blockIdx.y) from the
+// search block and the pair's slot - the same code either way, so an entry's floats are "align_structure"'s bit for bit.
 // The structure half: NaN into the header, m validated, the structure's trace packed.  This thread's share of "a coordinate is
 // NaN" comes back; m (0 if invalid) and m_ok go out.
 __device__ __forceinline__ int align_prep_structure(const AlignArgs& a, int& m, bool& m_ok) {
@@ -480,8 +482,14 @@ __global__ __launch_bounds__(SC_THREADS) void align_thread_kernel(AlignArgs a) {
 __global__ __launch_bounds__(SC_THREADS) void align_refine_kernel(AlignArgs a) { align_refine_body(a); }
 
 // ---------------------------------------------------------------------------------------
-// option "search_structures": the same three stages over a chunk of entries (blockIdx.y), between search_prep and search_rank
+// options "search_structures" and "search_domains": the same three stages over a chunk of pairs (blockIdx.y)
 // ---------------------------------------------------------------------------------------
+// A search is a QUERY - what the library is searched with - run through one frame: the resolver search_pair, the four stage
+// kernels, search_select and search_rank, each a template over the query, and the host's walk search_passes.  A query holds the
+// SearchArgs as `sa` and answers, on the device: which pair - unit d (the chain, or one domain of it) against entry k - is
+// virtual entry first + blockIdx.y (pair); which rows of the backbone form the pair's model (rows); where the pair's header
+// (out) and its ali and deviation (ali) go; where a unit's screened tm_model, its select table and its ranking lie (screen,
+// sel, rank); and the special cases of its select and rank launches (unit, unscreened, faulted).
 struct SearchArgs {
   const float* coords;   // [L][5][3]
   float* conf;           // the d_conf buffer; the search block begins at B0 (search_base), which search_prep leaves in the table
@@ -491,58 +499,147 @@ struct SearchArgs {
   unsigned char* ws;     // the scratch: table, tickets, slots (common.h)
   SearchSlot slot;
   const int* fault;      // the fault word of the prediction in flight
-  const int* sel;        // option "search_refine": slot y of a chunk holds entry sel[first + y] of the nsel selected; null: entry first + y
-  int nsel, refine;      // refine: R, the entries search_select chooses
+  int per, use_sel;      // this pass: the entries of a unit - all K, or the R chosen (option "search_refine"), which are taken
+                         // through the unit's row of the select table
+};
+__device__ __forceinline__ int64_t* search_tab(const SearchArgs& sa) { return reinterpret_cast<int64_t*>(sa.ws); }
+
+// unit d against entry k; the model is rows [off, off + n) of the query's row map
+struct SearchPair { int d, k, off, n; };
+// The r-th entry of a unit in this pass: through the unit's row `sel` of the select table, or r itself.
+__device__ __forceinline__ bool search_pick(const SearchArgs& sa, const int* sel, int r, int& k) {
+  k = sa.use_sel ? sel[r] : r;
+  return k >= 0 && k < sa.K;                                 // always: search_select writes entries
+}
+
+// Option "search_structures": the whole chain against every entry.  One unit; the identity over the L rows; header, ali and
+// deviation in the search block at b = conf + B0; the tables of option "search_refine" in the search scratch (common.h).
+struct WholeQuery {
+  SearchArgs sa;
+  __device__ bool pair(int first, SearchPair& p) const {
+    const int at = first + (int)blockIdx.y;
+    if (at < 0 || at >= sa.per) return false;
+    p.d = 0, p.off = 0, p.n = sa.L;
+    return search_pick(sa, sel(0), at, p.k);
+  }
+  __device__ auto rows(const SearchPair&) const { return [](int i) { return i; }; }
+  __device__ float* out(float* b, int, int k) const { return b + search_layout(sa.L, sa.K).hdr + (int64_t)ALIGN_HEADER * k; }
+  __device__ float* ali(float* b, const SearchPair& p) const { return b + search_layout(sa.L, sa.K).res + 2 * (int64_t)sa.L * p.k; }
+  __device__ float* screen(int) const { return reinterpret_cast<float*>(sa.ws + SEARCH_SCREEN_OFF); }
+  __device__ int* sel(int) const { return reinterpret_cast<int*>(sa.ws + SEARCH_SEL_OFF); }
+  __device__ float* rank(float* b, int) const { return b + search_layout(sa.L, sa.K).rank; }
+  __device__ bool unit(int) const { return true; }           // (the grids of search_select and search_rank are 1)
+  // with an invalid m_k somewhere nothing was screened (those entries return early)
+  __device__ bool unscreened() const { return search_tab(sa)[0] != 1; }
+  // a prediction that latched a fault gets NaN in every out slot instead of a ranking (the fault latch of api.hip does not know B0)
+  __device__ bool faulted(float* b) const {
+    if (*sa.fault == 0) return false;
+    const SearchLayout lay = search_layout(sa.L, sa.K);
+    const float nan = __builtin_nanf("");
+    for (int64_t i = lay.rank + threadIdx.x; i < lay.in; i += SC_THREADS) b[i] = nan;
+    return true;
+  }
 };
 
-__device__ __forceinline__ int64_t* search_tab(const SearchArgs& sa) { return reinterpret_cast<int64_t*>(sa.ws); }
-// option "search_refine": the screened tm_model of every entry, and the R entries chosen from it in rank order
-__device__ __forceinline__ float* search_screen_tm(const SearchArgs& sa) { return reinterpret_cast<float*>(sa.ws + SEARCH_SCREEN_OFF); }
-__device__ __forceinline__ int* search_sel(const SearchArgs& sa) { return reinterpret_cast<int*>(sa.ws + SEARCH_SEL_OFF); }
+// Option "search_domains": every domain of the model against every entry (include/dmpfold_hip.h has the definition).
+// Behind search_structures, on its stream, in its slots and with its table of the entries (validity, B0, trace offsets): the
+// whole-model search has finished with the slots and the table stays as search_prep left it.  The virtual entry p = d per + r
+// - domain d, the r-th of the `per` entries of a domain - takes slot p - first of its chunk, domain-major, so a chunk may
+// straddle domains.  The model of pair (d, k) is the domain's rows gathered through the residue list; n_d goes into the slot
+// header, and the shared bodies above read every row count from there.  ali and deviation of pair (d, k) go COMPACTLY into
+// entry k's place of the block, at the domain's offset in the sorted list - the domains partition the chain, so the pairs of
+// one entry never overlap, and a chunk's slot may be reused while they wait there - and domsearch_finish permutes each
+// entry's 2L floats through LDS into residue order.
+// The scratch of its own (dmp_ctx::domsearch_ws): per domain the screened tm_model of every entry and the entries selected
+// (option "search_refine"), then 32 ints - [0] D, or 0 if nothing can be searched (the block stays NaN), [1] the one-domain
+// shortcut is taken, [2 + d] the offset of domain d in the list, d <= 16 - then the residue list sorted by (label, index).
+constexpr int64_t DS_SCREEN_OFF = 0, DS_SEL_OFF = 4 * (int64_t)DOMAINS_MAX * SEARCH_MAX, DS_INFO_OFF = 2 * DS_SEL_OFF,
+                  DS_LIST_OFF = DS_INFO_OFF + 128;
+ScratchNeed search_domains_need(int max_L) { return {DS_LIST_OFF + 4 * (int64_t)max_L, 0}; }
 
-// Entry k = first + blockIdx.y - through `sel`, if there is one - in slot blockIdx.y.  False (uniform over the workgroup) for
-// an index that is no entry.  With an invalid m_k somewhere the table says so: the entry then reads as m = 0 and nothing of
-// its trace is touched.
-__device__ __forceinline__ bool search_entry(const SearchArgs& sa, int first, AlignArgs& a, int* entry = nullptr) {
-  const int y = (int)blockIdx.y, at = first + y;
-  if (y >= SEARCH_CHUNK_MAX || at < 0 || at >= (sa.sel ? sa.nsel : sa.K)) return false;
-  const int k = sa.sel ? sa.sel[at] : at;
-  if (k < 0 || k >= sa.K) return false;                      // never: search_select writes entries
-  if (entry) *entry = k;
+struct DomainQuery {
+  SearchArgs sa;
+  float* blk;            // the domain-search block
+  const float* dom;      // the domain block of the same call
+  unsigned char* dws;    // the scratch above
+  int dmax;              // the domains the grids are sized for: max(1, min(16, L / min_size))
+  int mode;              // the option's value: 2 never takes the shortcut
+  __device__ int* info() const { return reinterpret_cast<int*>(dws + DS_INFO_OFF); }
+  __device__ int* list() const { return reinterpret_cast<int*>(dws + DS_LIST_OFF); }
+  // false before a slot is touched for an index that is no pair: d >= D, the shortcut, nothing to search
+  __device__ bool pair(int first, SearchPair& p) const {
+    const int64_t at = (int64_t)first + (int)blockIdx.y;
+    if (first < 0 || sa.per < 1 || sa.per > sa.K || sa.K > SEARCH_MAX || at >= (int64_t)dmax * sa.per) return false;
+    p.d = (int)(at / sa.per);
+    if (!unit(p.d) || !search_pick(sa, sel(p.d), (int)(at % sa.per), p.k)) return false;
+    p.off = info()[2 + p.d];
+    p.n = info()[3 + p.d] - p.off;
+    return p.off >= 0 && p.n >= 3 && p.off + p.n <= sa.L;    // always: domsearch_prep checked
+  }
+  __device__ auto rows(const SearchPair& p) const {
+    const int* r = list() + p.off;
+    return [r](int i) { return r[i]; };
+  }
+  __device__ float* out(float*, int d, int k) const {
+    return blk + domsearch_layout(sa.L, sa.K).hdr + (int64_t)ALIGN_HEADER * ((int64_t)d * sa.K + k);
+  }
+  // compact: rows [off, off + n) of entry k's ali and, L further, deviation
+  __device__ float* ali(float*, const SearchPair& p) const { return blk + domsearch_layout(sa.L, sa.K).res + 2 * (int64_t)sa.L * p.k + p.off; }
+  __device__ float* screen(int d) const { return reinterpret_cast<float*>(dws + DS_SCREEN_OFF) + d * SEARCH_MAX; }
+  __device__ int* sel(int d) const { return reinterpret_cast<int*>(dws + DS_SEL_OFF) + d * SEARCH_MAX; }
+  __device__ float* rank(float*, int d) const { return blk + (int64_t)d * sa.K; }
+  __device__ bool unit(int d) const { return d < DOMAINS_MAX && d < info()[0] && !info()[1]; }
+  __device__ bool unscreened() const { return false; }       // (D = 0 then: no unit)
+  __device__ bool faulted(float*) const { return false; }
+};
+
+// Virtual entry first + blockIdx.y of query q -> its pair p, in slot blockIdx.y.  False (uniform over the workgroup) for an
+// index that is no pair.  With an invalid m_k somewhere the table says so: the entry then reads as m = 0 and nothing of its
+// trace is touched.
+template <class Q>
+__device__ __forceinline__ bool search_pair(const Q& q, int first, AlignArgs& a, SearchPair& p) {
+  const SearchArgs& sa = q.sa;
+  const int y = (int)blockIdx.y;
+  if (y >= SEARCH_CHUNK_MAX || !q.pair(first, p)) return false;
   const int64_t* tab = search_tab(sa);
   const bool ok = tab[0] == 1;
   float* b = sa.conf + tab[1];
-  const SearchLayout lay = search_layout(sa.L, sa.K);
   unsigned char* sl = sa.ws + SEARCH_HEAD_BYTES + (size_t)y * (size_t)sa.slot.total;
   a.coords = sa.coords;
-  a.mf = ok ? b[k] : 0.f;
-  a.out = b + lay.hdr + (int64_t)ALIGN_HEADER * k;
-  a.ali = b + lay.res + 2 * (int64_t)sa.L * k;
-  a.trace = b + lay.in + (ok ? 3 * tab[2 + k] : 0);
+  a.mf = ok ? b[p.k] : 0.f;
+  a.out = q.out(b, p.d, p.k);
+  a.ali = q.ali(b, p);
+  a.trace = b + search_layout(sa.L, sa.K).in + (ok ? 3 * tab[2 + p.k] : 0);
   align_slot_args(a, sl, sa.slot, sa.L, sa.max_m, reinterpret_cast<unsigned*>(sa.ws + SEARCH_TAB_BYTES) + 2 * y);
   return true;
 }
 
-__global__ __launch_bounds__(SC_THREADS) void align_prep_batch_kernel(SearchArgs sa, int first) {
+template <class Q>
+__global__ __launch_bounds__(SC_THREADS) void search_align_prep_kernel(Q q, int first) {
   AlignArgs a;
-  if (search_entry(sa, first, a)) align_prep_body(a);
+  SearchPair p;
+  if (search_pair(q, first, a, p)) align_prep_body(a, p.n, q.rows(p));
 }
-__global__ __launch_bounds__(SC_THREADS) void align_thread_batch_kernel(SearchArgs sa, int first) {
+template <class Q>
+__global__ __launch_bounds__(SC_THREADS) void search_align_thread_kernel(Q q, int first) {
   AlignArgs a;
-  if (search_entry(sa, first, a)) align_thread_body(a);
+  SearchPair p;
+  if (search_pair(q, first, a, p)) align_thread_body(a);
 }
-__global__ __launch_bounds__(SC_THREADS) void align_refine_batch_kernel(SearchArgs sa, int first) {
+template <class Q>
+__global__ __launch_bounds__(SC_THREADS) void search_align_refine_kernel(Q q, int first) {
   AlignArgs a;
-  if (search_entry(sa, first, a)) align_refine_body(a);
+  SearchPair p;
+  if (search_pair(q, first, a, p)) align_refine_body(a);
 }
-
-// the screen pass of option "search_refine": the entry's answer from its best seed, its tm_model (NaN: no result) in the table
-__global__ __launch_bounds__(SC_THREADS) void align_screen_batch_kernel(SearchArgs sa, int first) {
+// the screen pass of option "search_refine": the pair's answer from its best seed, its tm_model (NaN: no result) in the unit's table
+template <class Q>
+__global__ __launch_bounds__(SC_THREADS) void search_align_screen_kernel(Q q, int first) {
   AlignArgs a;
-  int k;
-  if (!search_entry(sa, first, a, &k)) return;
+  SearchPair p;
+  if (!search_pair(q, first, a, p)) return;
   align_screen_body(a);
-  if (threadIdx.x == 0) search_screen_tm(sa)[k] = a.out[2];      // what this thread wrote, or align_prep's NaN
+  if (threadIdx.x == 0) q.screen(p.d)[p.k] = a.out[2];       // what this thread wrote, or align_prep's NaN
 }
 
 // search_prep, one workgroup: B0 by the rule of common.h; every m_k an integer in [3, max_m]?; the rows in front of each
@@ -630,55 +727,48 @@ __device__ __forceinline__ void search_rank_into(const float* tm, int K, float* 
   }
 }
 
-// search_select, one workgroup (option "search_refine"): sel[r] = the entry with the r-th largest screened tm_model, r < R, by
-// the rule of search_rank.  With an invalid m_k somewhere nothing was screened: the identity (those entries return early).
-__global__ __launch_bounds__(SC_THREADS) void search_select_kernel(SearchArgs sa) {
+// search_select, one workgroup per unit (option "search_refine"): sel[r] = the entry with the r-th largest screened tm_model of
+// unit blockIdx.x, r < R, by the rule of search_rank.  Where nothing was screened: the identity.
+template <class Q>
+__global__ __launch_bounds__(SC_THREADS) void search_select_kernel(Q q, int R) {
   __shared__ float tm[SEARCH_MAX];
-  const int tid = threadIdx.x, K = sa.K, R = sa.refine < K ? sa.refine : K;
-  int* sel = search_sel(sa);
-  if (search_tab(sa)[0] != 1) {                              // uniform
+  const int tid = threadIdx.x, K = q.sa.K < SEARCH_MAX ? q.sa.K : SEARCH_MAX, d = (int)blockIdx.x;
+  if (!q.unit(d)) return;                                    // uniform
+  R = R < K ? R : K;
+  int* sel = q.sel(d);
+  if (q.unscreened()) {                                      // uniform
     for (int r = tid; r < R; r += SC_THREADS) sel[r] = r;
     return;
   }
-  const float* screen = search_screen_tm(sa);
+  const float* screen = q.screen(d);
   for (int k = tid; k < K; k += SC_THREADS) tm[k] = screen[k];
   __syncthreads();
   search_select_into(tm, K, R, sel);
 }
 
-// search_rank, one workgroup: rank[r] = the entry with the r-th largest tm_model, by counting - entry k comes behind every
-// entry with a larger value and every equal one of a lower index; the NaN entries last, in index order.  A prediction that
-// latched a fault gets NaN in every out slot instead (the fault latch of api.hip does not know B0).
-__global__ __launch_bounds__(SC_THREADS) void search_rank_kernel(SearchArgs sa) {
+// search_rank, one workgroup per unit: rank[r] = the entry with the r-th largest tm_model of unit blockIdx.x, by counting -
+// entry k comes behind every entry with a larger value and every equal one of a lower index; the NaN entries last, in index
+// order.
+template <class Q>
+__global__ __launch_bounds__(SC_THREADS) void search_rank_kernel(Q q) {
   __shared__ float tm[SEARCH_MAX];
-  const int tid = threadIdx.x, K = sa.K;
-  const int64_t* tab = search_tab(sa);
-  float* b = sa.conf + tab[1];
-  const SearchLayout lay = search_layout(sa.L, K);
-  if (*sa.fault != 0) {                                      // uniform
-    const float nan = __builtin_nanf("");
-    for (int64_t i = lay.rank + tid; i < lay.in; i += SC_THREADS) b[i] = nan;
-    return;
-  }
-  for (int k = tid; k < K; k += SC_THREADS) tm[k] = b[lay.hdr + (int64_t)ALIGN_HEADER * k + 2];
+  const int tid = threadIdx.x, K = q.sa.K < SEARCH_MAX ? q.sa.K : SEARCH_MAX, d = (int)blockIdx.x;
+  if (!q.unit(d)) return;                                    // uniform
+  float* b = q.sa.conf + search_tab(q.sa)[1];
+  if (q.faulted(b)) return;                                  // uniform
+  for (int k = tid; k < K; k += SC_THREADS) tm[k] = q.out(b, d, k)[2];
   __syncthreads();
-  search_rank_into(tm, K, b + lay.rank);
+  search_rank_into(tm, K, q.rank(b, d));
 }
-
-struct DomSearchArgs;                                        // option "search_domains", below
-__global__ void domsearch_align_refine_kernel(DomSearchArgs da, int first);
 
 int align_kernel_attrs(dmp_ctx* c) {
   static_assert(AL_SLICE * SC_THREADS >= DMP_MAX_L + 1, "a thread's slice of a diagonal");
   static_assert(SEARCH_MAX % SC_THREADS == 0, "search_prep: a whole number of entries per thread");
   static bool done[64] = {};
   if (c->device >= 0 && c->device < 64 && done[c->device]) return DMP_OK;
-  DMP_HIP(hipFuncSetAttribute((const void*)align_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              align_lds(DMP_MAX_L, DMP_MAX_L).total));
-  DMP_HIP(hipFuncSetAttribute((const void*)align_refine_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              align_lds(DMP_MAX_L, DMP_MAX_L).total));
-  DMP_HIP(hipFuncSetAttribute((const void*)domsearch_align_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              align_lds(DMP_MAX_L, DMP_MAX_L).total));
+  for (const void* refine : {(const void*)align_refine_kernel, (const void*)search_align_refine_kernel<WholeQuery>,
+                             (const void*)search_align_refine_kernel<DomainQuery>})
+    DMP_HIP(hipFuncSetAttribute(refine, hipFuncAttributeMaxDynamicSharedMemorySize, align_lds(DMP_MAX_L, DMP_MAX_L).total));
   if (c->device >= 0 && c->device < 64) done[c->device] = true;
   return DMP_OK;
 }
@@ -686,6 +776,9 @@ int align_kernel_attrs(dmp_ctx* c) {
 // The scratch of "align_structure" (dmp_ctx::align_ws): the head - the two tickets - then the one slot, the largest a length takes.
 constexpr int64_t ALIGN_HEAD_BYTES = 16;
 ScratchNeed align_structure_need(int max_L) { return {ALIGN_HEAD_BYTES + search_slot(max_L, max_L).total, ALIGN_HEAD_BYTES}; }
+
+// LDS of align_thread and align_screen in bytes: a seed's overlap has at most L rows, 6L floats + L flags, 50 KB at L = 2048
+static size_t align_thread_lds(int L) { return sizeof(float) * 6 * L + round_up(L, 16); }
 
 int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
   const AlignLayout lay = align_layout(L);
@@ -697,8 +790,7 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
   align_slot_args(a, c->align_ws.p + ALIGN_HEAD_BYTES, search_slot(L, c->max_L), L, c->max_L, reinterpret_cast<unsigned*>(c->align_ws.p));
   hipLaunchKernelGGL(align_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, a, (const float*)d_block);
   DMP_LAUNCH_CHECK();
-  // a seed's overlap has at most L rows: 6L floats + L flags of LDS, 50 KB at L = 2048
-  hipLaunchKernelGGL(align_thread_kernel, dim3(L + c->max_L + 1), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
+  hipLaunchKernelGGL(align_thread_kernel, dim3(L + c->max_L + 1), dim3(SC_THREADS), align_thread_lds(L), s, a);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(align_refine_kernel, dim3(AL_T), dim3(SC_THREADS), align_lds(L, c->max_L).total, s, a);
   DMP_LAUNCH_CHECK();
@@ -706,15 +798,47 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
 }
 
 int search_wg_per_cu(int L, int max_m, int* out) {
-  DMP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(out, (const void*)align_refine_batch_kernel, SC_THREADS,
+  DMP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(out, (const void*)search_align_refine_kernel<WholeQuery>, SC_THREADS,
                                                        (size_t)align_lds(L, max_m).total));
   if (*out > 8) *out = 8;      // 256-thread workgroups: the hardware admits at most 8 per CU whatever the query answers
   return DMP_OK;
 }
 
-// search_prep, then the three stages per chunk of C consecutive entries (one slot each), then search_rank.  With option
-// "search_refine" = R, 0 < R < K: stage 1 and align_screen per chunk over all K, search_select, then the three stages per
-// chunk over the R selected entries.  Everything is sized from (L, max_m, K, R) here; nothing comes back from the device.
+// One pass of query q over `total` virtual entries, in chunks of C consecutive ones (one slot each): align_prep, align_thread
+// and the pass's last stage, `wgs` workgroups per pair with `lds` bytes.
+template <class Q>
+static int search_pass(const Q& q, int total, int C, void (*last)(Q, int), int wgs, size_t lds, hipStream_t s) {
+  const int L = q.sa.L;
+  for (int first = 0; first < total; first += C) {
+    const int cn = std::min(C, total - first);
+    hipLaunchKernelGGL(search_align_prep_kernel<Q>, dim3(1, cn), dim3(SC_THREADS), 0, s, q, first);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(search_align_thread_kernel<Q>, dim3(L + q.sa.max_m + 1, cn), dim3(SC_THREADS), align_thread_lds(L), s, q, first);
+    DMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(last, dim3(wgs, cn), dim3(SC_THREADS), lds, s, q, first);
+    DMP_LAUNCH_CHECK();
+  }
+  return DMP_OK;
+}
+// The passes of query q with `units` units (1, or the domains the grids are sized for): the three stages over every entry of
+// every unit.  With option "search_refine" = R, 0 < R < K: stage 1 and align_screen over all units x K, search_select per
+// unit, then the three stages over the units x R selected.  Everything is sized from (L, max_m, K, R) here; nothing comes
+// back from the device.
+template <class Q>
+static int search_passes(Q& q, int units, int C, int refine, hipStream_t s) {
+  SearchArgs& sa = q.sa;
+  const int R = refine > 0 && refine < sa.K ? refine : 0;
+  if (R) {
+    sa.per = sa.K;
+    if (int rc = search_pass(q, units * sa.K, C, search_align_screen_kernel<Q>, 1, align_thread_lds(sa.L), s)) return rc;
+    hipLaunchKernelGGL(search_select_kernel<Q>, dim3(units), dim3(SC_THREADS), 0, s, q, R);
+    DMP_LAUNCH_CHECK();
+  }
+  sa.per = R ? R : sa.K;                                     // slot y of a chunk holds virtual entry first + y of units x per
+  sa.use_sel = R ? 1 : 0;
+  return search_pass(q, units * sa.per, C, search_align_refine_kernel<Q>, AL_T, align_lds(sa.L, sa.max_m).total, s);
+}
+
 static SearchArgs search_args(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay) {
   SearchArgs sa{};
   sa.coords = d_coords;
@@ -731,8 +855,10 @@ static SearchArgs search_args(dmp_ctx* c, const float* d_coords, int L, float* d
   return sa;
 }
 
+// search_prep, the passes of the whole query, search_rank
 int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
-  SearchArgs sa = search_args(c, d_coords, L, d_conf, lay);
+  WholeQuery q{search_args(c, d_coords, L, d_conf, lay)};
+  SearchArgs& sa = q.sa;
   const int C = search_chunk_entries(L, sa.max_m, c->run.search_chunk);
   DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws.bytes,
           "search_structures: the scratch does not hold a chunk of %d entries at L = %d, search_max_m = %d", C, L, sa.max_m);
@@ -741,76 +867,20 @@ int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, c
   c->search_last_C = C;
   hipLaunchKernelGGL(search_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
   DMP_LAUNCH_CHECK();
-  const size_t thread_lds = sizeof(float) * 6 * L + round_up(L, 16);
-  const int R = c->run.search_refine > 0 && c->run.search_refine < sa.K ? c->run.search_refine : 0;
-  if (R) {
-    sa.refine = R;
-    for (int first = 0; first < sa.K; first += C) {
-      const int cn = std::min(C, sa.K - first);
-      hipLaunchKernelGGL(align_prep_batch_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, sa, first);
-      DMP_LAUNCH_CHECK();
-      hipLaunchKernelGGL(align_thread_batch_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, sa, first);
-      DMP_LAUNCH_CHECK();
-      hipLaunchKernelGGL(align_screen_batch_kernel, dim3(1, cn), dim3(SC_THREADS), thread_lds, s, sa, first);
-      DMP_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(search_select_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
-    DMP_LAUNCH_CHECK();
-    sa.sel = reinterpret_cast<const int*>(sa.ws + SEARCH_SEL_OFF);
-    sa.nsel = R;
-  }
-  const int todo = R ? R : sa.K;                             // the entries refined: slot y of a chunk holds entry (sel[)first + y(])
-  for (int first = 0; first < todo; first += C) {
-    const int cn = std::min(C, todo - first);
-    hipLaunchKernelGGL(align_prep_batch_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, sa, first);
-    DMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(align_thread_batch_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, sa, first);
-    DMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(align_refine_batch_kernel, dim3(AL_T, cn), dim3(SC_THREADS), align_lds(L, sa.max_m).total, s, sa, first);
-    DMP_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(search_rank_kernel, dim3(1), dim3(SC_THREADS), 0, s, sa);
+  if (int rc = search_passes(q, 1, C, c->run.search_refine, s)) return rc;
+  hipLaunchKernelGGL(search_rank_kernel<WholeQuery>, dim3(1), dim3(SC_THREADS), 0, s, q);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }
 
 // ---------------------------------------------------------------------------------------
-// option "search_domains": the same stages with every domain of the model as the model (include/dmpfold_hip.h has the definition)
+// option "search_domains": the domain query's own two kernels, in front of and behind the frame's
 // ---------------------------------------------------------------------------------------
-// Behind search_structures, on its stream, in its slots and with its table of the entries (validity, B0, trace offsets): the
-// whole-model search has finished with the slots and the table stays as search_prep left it.  The virtual entry p = d per + r
-// - domain d, the r-th of the `per` entries of a domain: all K of them, or the R that search_select chose for d - takes slot
-// p - first of its chunk, domain-major, so a chunk may straddle domains.  The model of pair (d, k) is the domain's rows
-// gathered through the residue list; n_d goes into the slot header, and the shared bodies above read every row count from
-// there.  ali and deviation of pair (d, k) go COMPACTLY into entry k's place of the block, at the domain's offset in the
-// sorted list - the domains partition the chain, so the pairs of one entry never overlap, and a chunk's slot may be reused
-// while they wait there - and domsearch_finish permutes each entry's 2L floats through LDS into residue order.
-// The scratch of its own (dmp_ctx::domsearch_ws): per domain the screened tm_model of every entry and the entries selected
-// (option "search_refine"), then 32 ints - [0] D, or 0 if nothing can be searched (the block stays NaN), [1] the one-domain
-// shortcut is taken, [2 + d] the offset of domain d in the list, d <= 16 - then the residue list sorted by (label, index).
-constexpr int64_t DS_SCREEN_OFF = 0, DS_SEL_OFF = 4 * (int64_t)DOMAINS_MAX * SEARCH_MAX, DS_INFO_OFF = 2 * DS_SEL_OFF,
-                  DS_LIST_OFF = DS_INFO_OFF + 128;
-ScratchNeed search_domains_need(int max_L) { return {DS_LIST_OFF + 4 * (int64_t)max_L, 0}; }
-
-struct DomSearchArgs {
-  SearchArgs sa;
-  float* blk;            // the domain-search block
-  const float* dom;      // the domain block of the same call
-  unsigned char* dws;    // the scratch above
-  int dmax;              // the domains the grids are sized for: max(1, min(16, L / min_size))
-  int mode;              // the option's value: 2 never takes the shortcut
-  int per, use_sel;      // entries per domain in this pass; taken through the domain's row of the select table
-};
-__device__ __forceinline__ float* ds_screen(const DomSearchArgs& da) { return reinterpret_cast<float*>(da.dws + DS_SCREEN_OFF); }
-__device__ __forceinline__ int* ds_sel(const DomSearchArgs& da) { return reinterpret_cast<int*>(da.dws + DS_SEL_OFF); }
-__device__ __forceinline__ int* ds_info(const DomSearchArgs& da) { return reinterpret_cast<int*>(da.dws + DS_INFO_OFF); }
-__device__ __forceinline__ int* ds_list(const DomSearchArgs& da) { return reinterpret_cast<int*>(da.dws + DS_LIST_OFF); }
-
 // domsearch_prep, one workgroup: NaN into the whole block; D and the labels from the domain block, validated (D an integer
 // in [1, dmax], every label an integer in [0, D), every domain of at least 3 rows - always, after domains.hip; and every
 // m_k valid, by search_prep's table - else D = 0 and nothing more runs); the counting sort: thread d counts label d, thread 0
 // scans the 16 counts, thread d writes its residues in rising order.  Integers only.
-__global__ __launch_bounds__(SC_THREADS) void domsearch_prep_kernel(DomSearchArgs da) {
+__global__ __launch_bounds__(SC_THREADS) void domsearch_prep_kernel(DomainQuery da) {
   __shared__ unsigned char lab[DMP_MAX_L];
   __shared__ int cnt[DOMAINS_MAX], bad[SC_THREADS], sh_D;
   const int tid = threadIdx.x, L = da.sa.L < DMP_MAX_L ? da.sa.L : DMP_MAX_L;
@@ -836,7 +906,7 @@ __global__ __launch_bounds__(SC_THREADS) void domsearch_prep_kernel(DomSearchArg
   }
   __syncthreads();
   if (tid == 0) {
-    int* info = ds_info(da);
+    int* info = da.info();
     int any = 0, run = 0;
     for (int k = 0; k < SC_THREADS; ++k) any |= bad[k];
     for (int d = 0; d < DOMAINS_MAX; ++d) {
@@ -855,104 +925,20 @@ __global__ __launch_bounds__(SC_THREADS) void domsearch_prep_kernel(DomSearchArg
   __syncthreads();
   if (sh_D == 0) return;                                     // uniform
   if (tid < DOMAINS_MAX) {
-    int* list = ds_list(da);
+    int* list = da.list();
     int at = cnt[tid];
     for (int i = 0; i < L; ++i)
       if (lab[i] == tid) list[at++] = i;                     // at most cnt's n of them: the same labels were counted
   }
 }
 
-// Virtual entry first + blockIdx.y -> pair (d, k) in slot blockIdx.y, the domain's n rows at `rows`.  False (uniform over the
-// workgroup) before a slot is touched for an index that is no pair: d >= D, the shortcut, nothing to search.
-__device__ __forceinline__ bool domsearch_entry(const DomSearchArgs& da, int first, AlignArgs& a, int& d, int& k, int& n, const int*& rows) {
-  const SearchArgs& sa = da.sa;
-  const int y = (int)blockIdx.y;
-  const int64_t at = (int64_t)first + y;
-  if (y >= SEARCH_CHUNK_MAX || first < 0 || da.per < 1 || da.per > sa.K || sa.K > SEARCH_MAX || at >= (int64_t)da.dmax * da.per) return false;
-  d = (int)(at / da.per);
-  const int r = (int)(at % da.per);
-  const int* info = ds_info(da);
-  if (d >= DOMAINS_MAX || d >= info[0] || info[1]) return false;
-  k = da.use_sel ? ds_sel(da)[d * SEARCH_MAX + r] : r;
-  if (k < 0 || k >= sa.K) return false;                      // never: domsearch_select writes entries
-  const int off = info[2 + d];
-  n = info[3 + d] - off;
-  if (off < 0 || n < 3 || off + n > sa.L) return false;      // never: domsearch_prep checked
-  rows = ds_list(da) + off;
-  const int64_t* tab = search_tab(sa);
-  const bool ok = tab[0] == 1;                               // (always: D = 0 otherwise)
-  float* b = sa.conf + tab[1];
-  const SearchLayout lay = search_layout(sa.L, sa.K);
-  const DomSearchLayout dl = domsearch_layout(sa.L, sa.K);
-  unsigned char* sl = sa.ws + SEARCH_HEAD_BYTES + (size_t)y * (size_t)sa.slot.total;
-  a.coords = sa.coords;
-  a.mf = ok ? b[k] : 0.f;
-  a.out = da.blk + dl.hdr + (int64_t)ALIGN_HEADER * ((int64_t)d * sa.K + k);
-  a.ali = da.blk + dl.res + 2 * (int64_t)sa.L * k + off;     // compact: rows [off, off + n) of entry k's ali and, L further, deviation
-  a.trace = b + lay.in + (ok ? 3 * tab[2 + k] : 0);
-  align_slot_args(a, sl, sa.slot, sa.L, sa.max_m, reinterpret_cast<unsigned*>(sa.ws + SEARCH_TAB_BYTES) + 2 * y);
-  return true;
-}
-
-__global__ __launch_bounds__(SC_THREADS) void domsearch_align_prep_kernel(DomSearchArgs da, int first) {
-  AlignArgs a;
-  int d, k, n;
-  const int* rows;
-  if (domsearch_entry(da, first, a, d, k, n, rows)) align_prep_body(a, n, [rows](int i) { return rows[i]; });
-}
-__global__ __launch_bounds__(SC_THREADS) void domsearch_align_thread_kernel(DomSearchArgs da, int first) {
-  AlignArgs a;
-  int d, k, n;
-  const int* rows;
-  if (domsearch_entry(da, first, a, d, k, n, rows)) align_thread_body(a);
-}
-__global__ __launch_bounds__(SC_THREADS) void domsearch_align_refine_kernel(DomSearchArgs da, int first) {
-  AlignArgs a;
-  int d, k, n;
-  const int* rows;
-  if (domsearch_entry(da, first, a, d, k, n, rows)) align_refine_body(a);
-}
-__global__ __launch_bounds__(SC_THREADS) void domsearch_align_screen_kernel(DomSearchArgs da, int first) {
-  AlignArgs a;
-  int d, k, n;
-  const int* rows;
-  if (!domsearch_entry(da, first, a, d, k, n, rows)) return;
-  align_screen_body(a);
-  if (threadIdx.x == 0) ds_screen(da)[d * SEARCH_MAX + k] = a.out[2];      // what this thread wrote, or align_prep's NaN
-}
-
-// domsearch_select, one workgroup per domain: search_select's rule on the domain's row of the screen table
-__global__ __launch_bounds__(SC_THREADS) void domsearch_select_kernel(DomSearchArgs da, int R) {
-  __shared__ float tm[SEARCH_MAX];
-  const int tid = threadIdx.x, K = da.sa.K < SEARCH_MAX ? da.sa.K : SEARCH_MAX, d = (int)blockIdx.x;
-  const int* info = ds_info(da);
-  if (d >= DOMAINS_MAX || d >= info[0] || info[1]) return;   // uniform
-  const float* screen = ds_screen(da) + d * SEARCH_MAX;
-  int* sel = ds_sel(da) + d * SEARCH_MAX;
-  for (int k = tid; k < K; k += SC_THREADS) tm[k] = screen[k];
-  __syncthreads();
-  search_select_into(tm, K, R, sel);
-}
-
-// domsearch_rank, one workgroup per domain: search_rank's rule on the domain's K headers
-__global__ __launch_bounds__(SC_THREADS) void domsearch_rank_kernel(DomSearchArgs da) {
-  __shared__ float tm[SEARCH_MAX];
-  const int tid = threadIdx.x, K = da.sa.K < SEARCH_MAX ? da.sa.K : SEARCH_MAX, d = (int)blockIdx.x;
-  const int* info = ds_info(da);
-  if (d >= DOMAINS_MAX || d >= info[0] || info[1]) return;   // uniform
-  const DomSearchLayout dl = domsearch_layout(da.sa.L, da.sa.K);
-  for (int k = tid; k < K; k += SC_THREADS) tm[k] = da.blk[dl.hdr + (int64_t)ALIGN_HEADER * ((int64_t)d * K + k) + 2];
-  __syncthreads();
-  search_rank_into(tm, K, da.blk + (int64_t)d * K);
-}
-
 // domsearch_finish, one workgroup per entry.  The shortcut (D = 1, the domain is the chain): the whole search's rank, header,
 // ali and deviation of this entry into row 0.  Else: the entry's 2L compact floats into residue order, through LDS - position
 // j of the sorted list is residue list[j], and the list is a permutation of 0 .. L - 1.
-__global__ __launch_bounds__(SC_THREADS) void domsearch_finish_kernel(DomSearchArgs da) {
+__global__ __launch_bounds__(SC_THREADS) void domsearch_finish_kernel(DomainQuery da) {
   __shared__ float buf[2 * DMP_MAX_L];
   const int tid = threadIdx.x, K = da.sa.K, k = (int)blockIdx.x, L = da.sa.L < DMP_MAX_L ? da.sa.L : DMP_MAX_L;
-  const int* info = ds_info(da);
+  const int* info = da.info();
   if (k >= K || info[0] == 0) return;                        // uniform
   const DomSearchLayout dl = domsearch_layout(da.sa.L, K);
   float* res = da.blk + dl.res + 2 * (int64_t)L * k;
@@ -967,7 +953,7 @@ __global__ __launch_bounds__(SC_THREADS) void domsearch_finish_kernel(DomSearchA
   }
   for (int i = tid; i < 2 * L; i += SC_THREADS) buf[i] = res[i];
   __syncthreads();
-  const int* list = ds_list(da);
+  const int* list = da.list();
   for (int j = tid; j < L; j += SC_THREADS) {
     int i = list[j];
     i = i < 0 ? 0 : (i >= L ? L - 1 : i);                    // never
@@ -976,57 +962,28 @@ __global__ __launch_bounds__(SC_THREADS) void domsearch_finish_kernel(DomSearchA
   }
 }
 
-// domsearch_prep, then search_structures' passes over the Dmax K virtual entries (with "search_refine" = R: screen over Dmax K,
-// domsearch_select, refine over Dmax R), domsearch_rank, domsearch_finish.  Dmax = max(1, min(16, L / min_size)) bounds D: a
-// cut is admissible only if both parts hold min_size residues (domains.hip, domains_cuts_kernel: `if (size < a.min_size ||
-// n - size < a.min_size ...) continue;`), so D min_size <= L.  Nothing comes back from the device.
+// domsearch_prep, the passes of the domain query over its Dmax units (select and rank one workgroup per domain),
+// domsearch_finish.  Dmax = max(1, min(16, L / min_size)) bounds D: a cut is admissible only if both parts hold min_size
+// residues (domains.hip, domains_cuts_kernel: `if (size < a.min_size || n - size < a.min_size ...) continue;`), so
+// D min_size <= L.  Nothing comes back from the device.
 int search_domains(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s) {
-  DomSearchArgs da{};
-  da.sa = search_args(c, d_coords, L, d_conf, lay);
-  SearchArgs& sa = da.sa;
-  da.blk = d_conf + lay.domsearch.off;
-  da.dom = d_conf + lay.domains.off;
-  da.dws = c->domsearch_ws.p;
-  da.dmax = std::max(1, std::min(DOMAINS_MAX, L / c->run.dom_min_size));
-  da.mode = c->run.search_domains;
+  DomainQuery q{search_args(c, d_coords, L, d_conf, lay)};
+  SearchArgs& sa = q.sa;
+  q.blk = d_conf + lay.domsearch.off;
+  q.dom = d_conf + lay.domains.off;
+  q.dws = c->domsearch_ws.p;
+  q.dmax = std::max(1, std::min(DOMAINS_MAX, L / c->run.dom_min_size));
+  q.mode = c->run.search_domains;
   const int C = search_chunk_entries(L, sa.max_m, c->run.search_chunk);
-  DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws.bytes && da.dws &&
+  DMP_ARG(sa.ws && SEARCH_HEAD_BYTES + (int64_t)C * sa.slot.total <= c->search_ws.bytes && q.dws &&
               c->domsearch_ws.bytes >= search_domains_need(L).bytes,
           "search_domains: the scratch does not hold a chunk of %d entries at L = %d, search_max_m = %d", C, L, sa.max_m);
-  hipLaunchKernelGGL(domsearch_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, da);
+  hipLaunchKernelGGL(domsearch_prep_kernel, dim3(1), dim3(SC_THREADS), 0, s, q);
   DMP_LAUNCH_CHECK();
-  const size_t thread_lds = sizeof(float) * 6 * L + round_up(L, 16);
-  const int R = c->run.search_refine > 0 && c->run.search_refine < sa.K ? c->run.search_refine : 0;
-  if (R) {
-    da.per = sa.K;
-    const int all = da.dmax * sa.K;
-    for (int first = 0; first < all; first += C) {
-      const int cn = std::min(C, all - first);
-      hipLaunchKernelGGL(domsearch_align_prep_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, da, first);
-      DMP_LAUNCH_CHECK();
-      hipLaunchKernelGGL(domsearch_align_thread_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, da, first);
-      DMP_LAUNCH_CHECK();
-      hipLaunchKernelGGL(domsearch_align_screen_kernel, dim3(1, cn), dim3(SC_THREADS), thread_lds, s, da, first);
-      DMP_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(domsearch_select_kernel, dim3(da.dmax), dim3(SC_THREADS), 0, s, da, R);
-    DMP_LAUNCH_CHECK();
-    da.use_sel = 1;
-  }
-  da.per = R ? R : sa.K;
-  const int todo = da.dmax * da.per;
-  for (int first = 0; first < todo; first += C) {
-    const int cn = std::min(C, todo - first);
-    hipLaunchKernelGGL(domsearch_align_prep_kernel, dim3(1, cn), dim3(SC_THREADS), 0, s, da, first);
-    DMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(domsearch_align_thread_kernel, dim3(L + sa.max_m + 1, cn), dim3(SC_THREADS), thread_lds, s, da, first);
-    DMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(domsearch_align_refine_kernel, dim3(AL_T, cn), dim3(SC_THREADS), align_lds(L, sa.max_m).total, s, da, first);
-    DMP_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(domsearch_rank_kernel, dim3(da.dmax), dim3(SC_THREADS), 0, s, da);
+  if (int rc = search_passes(q, q.dmax, C, c->run.search_refine, s)) return rc;
+  hipLaunchKernelGGL(search_rank_kernel<DomainQuery>, dim3(q.dmax), dim3(SC_THREADS), 0, s, q);
   DMP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(domsearch_finish_kernel, dim3(sa.K), dim3(SC_THREADS), 0, s, da);
+  hipLaunchKernelGGL(domsearch_finish_kernel, dim3(sa.K), dim3(SC_THREADS), 0, s, q);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

@@ -405,7 +405,7 @@ struct dmp_ctx {
   dmp::Scratch domains_ws;         // "domains": the counters | per entity the nodes, the lists, the slots, the cuts, the contact table,
                                    // the summed-area tables of one level (domains.hip: domains_scratch)
   dmp::Scratch domsearch_ws;       // "search_domains": nothing zeroed | the per-domain tables of "search_refine", the counts, the residue list (align.hip:
-                                   // domsearch_scratch); the slots are search_ws's
+                                   // DomainQuery); the slots are search_ws's
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
   int* end_fault_out = nullptr;  // pipeline.hip: device-visible host word that the NEXT dmp_predict_end's latch kernel writes this
                                  // prediction's fault bits to (per-ticket status without a synchronising copy); not owned
@@ -675,7 +675,7 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
 int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
 // option "search_domains" (align.hip): behind search_structures, the same stages with every domain of the model as the model
 int search_domains(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
-int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the batch launch
+int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the whole-model search's launch
 // The native entity of options "assign_ss", "exposure" and "domains" (entity.hip), where it lies in dmp_ctx::entity_ws:
 struct NativeEntity {
   int* whole_x;           // every row of the native trace has an x that is no NaN: the native leg of "assign_ss" and "exposure" runs

@@ -733,8 +733,9 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * integers only); then the stages of "search_structures" over the virtual entries p = K d + k, domain-major, in the same
  * chunks of C slots (a chunk may straddle domains): align_prep - its structure half unchanged, its model half gathering the
  * domain's rows through the list, n_d and what follows from it in the slot header -, align_thread, align_refine (with R:
- * align_screen over all, domsearch_select per domain, then the three stages over the R chosen); domsearch_rank (one workgroup
- * per domain); domsearch_finish (one per entry).  The bodies that compute are the ones "align_structure" runs: they read the
+ * align_screen over all, search_select per domain, then the three stages over the R chosen); search_rank (one workgroup
+ * per domain); domsearch_finish (one per entry) - the kernels of "search_structures" themselves, instantiated for the
+ * domain query instead of the whole chain.  The bodies that compute are the ones "align_structure" runs: they read the
  * model's row count from the slot header, and L only sizes strides, LDS and grids.  A pair's ali and deviation are written
  * compactly at the domain's offset in the sorted list, inside entry k's 2L floats of the block - the slots are reused chunk
  * after chunk, the block is not - and domsearch_finish permutes them into residue order through LDS.  Nothing comes back from
