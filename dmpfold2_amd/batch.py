@@ -198,8 +198,12 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     <stem>.domains.json (the line `dmpfold --domains` prints).  With `domain_hits` (the dict of Engine.domain_hits, --library
     --search-domains; beside `domains`): npz gains dom_hit_rank (int32 (D, K): per domain the entries by falling TM-score) and
     dom_hit_tm (float32 (D, K): pair (d, k)'s TM-score normalised by the domain's size, in the library's order); pdb / ca get
-    <stem>.domain_hits.json (score.domain_hits_json, the best `hits_top` per domain)."""
+    <stem>.domain_hits.json (score.domain_hits_json, the best `hits_top` per domain).  With `domain_scores` (the dict of
+    score.unpack_domain_scores, --natives --score-domains; only beside `scores`): npz gains dom_score_table (float32 (2, 16, 32):
+    the two tables of the domain-score block) and dom_score_res (float32 (4, L): per leg the per-residue lDDT and deviation inside
+    the residue's own domain); <stem>.scores.json gains the key "domain_scores" (score.domain_scores_json)."""
     domain_hits = results.pop("domain_hits", None)
+    domain_scores = results.pop("domain_scores", None)
     unknown = set(results) - {row.name for row in _score.BLOCKS}
     if unknown:
         raise TypeError(f"write_result: no result is called {sorted(unknown)}")
@@ -264,6 +268,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
             D, K = domain_hits["domains"], len(domain_hits["names"])
             extra.update({"dom_hit_rank": np.asarray(domain_hits["rank"], dtype=np.int32).reshape(D, K),
                           "dom_hit_tm": np.asarray(domain_hits["headers"][:D, :, 2], dtype=np.float32).reshape(D, K)})
+        if domain_scores is not None and scores is not None:
+            extra.update({"dom_score_table": np.asarray(domain_scores["table"], dtype=np.float32),
+                          "dom_score_res": np.asarray(domain_scores["res"], dtype=np.float32)})
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
@@ -272,6 +279,8 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     forms = results_json(results, hits_top)
     if domain_hits is not None:
         forms["domain_hits"] = domain_hits_form(domain_hits, domains, hits_top)
+    if domain_scores is not None and "scores" in forms:
+        forms["scores"]["domain_scores"] = _score.domain_scores_json(domain_scores, domains)
     for name, value in (("exposure", forms.get("exposure")), ("domains", forms.get("domains")), ("restrain", restrain)):
         if value is not None:
             forms[name] = {name: value}                  # (these lines carry their name)
@@ -343,6 +352,22 @@ def batch_domains(tau=0.25, min_size=40, min_segment=10):
         _DOMAINS = before
 
 
+_SCORE_DOMAINS = False
+
+
+@contextlib.contextmanager
+def batch_score_domains():
+    """Every run_batch inside the block, which must be given `natives`, also scores every domain of a scored target against its
+    native on the domain's own superposition (Pipeline.use_score_domains; the parse by the parameters of `batch_domains`, or the
+    defaults): the target's scores gain the key "domain_scores" (score.domain_scores_json) wherever they are written."""
+    global _SCORE_DOMAINS
+    before, _SCORE_DOMAINS = _SCORE_DOMAINS, True
+    try:
+        yield
+    finally:
+        _SCORE_DOMAINS = before
+
+
 def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_minsteps,
               weights_file=None, state_dict=None, streams=4, device=None, rank=0, world=1, fmt="pdb", store=None,
               converge=None, stats_out=None, distmap=False, natives=None, structures=None, library=None, search_top=10,
@@ -387,6 +412,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     for option, wanted in (("score_map", score_map), ("score_passes", score_passes)):
         if wanted and not natives:
             raise ValueError(needs_native(option, option, "`natives`", many=True))
+    score_domains = _SCORE_DOMAINS                         # (batch_score_domains)
+    if score_domains and not natives:
+        raise ValueError("score_domains scores every domain against native structures: give `natives`")
     restraining = restrain_to_milli(restrain) > 0          # (a bad value raises before any work)
     restrain_cutoff_to_mA(restrain_cutoff)
     check_output_stems(targets)
@@ -430,8 +458,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         max_L = max(max_L, library.max_m)               # the engines' capacity bounds every entry's length
     domains = _DOMAINS                                  # (batch_domains)
     search_domains = library is not None and bool(getattr(library, "domains", False))      # (--search-domains)
-    if search_domains and domains is None:
-        domains = domains_options()                     # the library's flag turns "domains" on, with the defaults
+    if (search_domains or score_domains) and domains is None:
+        domains = domains_options()                     # the library's flag, or --score-domains, turns "domains" on, with the defaults
         domains = (domains[0] * 1e-3,) + domains[1:]
     t0 = time.perf_counter()
     pipe, dev, copy_stream = None, None, None
@@ -454,6 +482,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                                            ("search", library is not None, library)):
                 if wanted:
                     getattr(pipe, "set_" + setter)(*value)
+            if score_domains:
+                pipe.use_score_domains(True)                # (behind set_score, which it needs)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -472,6 +502,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         outs = pipe.peek(t)                           # (coords, confs), with `distmap` also (map, info)
         if search_domains:
             outs = outs + (pipe.outputs_of(t).domain_search_block,)      # which `peek` never hands out: last of all
+        if score_domains:
+            outs = outs + (pipe.outputs_of(t).domain_score_block,)       # likewise, behind that
         if outs[0].is_cuda:
             host = tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in outs)
             with (torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext()):
@@ -496,7 +528,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        ds_block = None
+        ds_block, score_block = None, None
+        if score_domains:
+            public, score_block = public[:-1], public[-1]
         if search_domains:
             public, ds_block = public[:-1], public[-1]
         out = Outputs.of(public, distmap=distmap or score_map or restraining, **blocks_on)
@@ -513,6 +547,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 ds["refine"] = library.refine
             results["domain_hits"] = ds
             forms["domain_hits"] = domain_hits_form(ds, results.get("domains"), search_top)
+        if score_block is not None and t in scored and "scores" in forms:
+            results["domain_scores"] = _score.unpack_domain_scores(score_block, alnmat.shape[1])
+            forms["scores"]["domain_scores"] = _score.domain_scores_json(results["domain_scores"], results.get("domains"))
         rep = None
         if restraining:
             rep = forms["restrain"] = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap,
@@ -626,7 +663,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             if isinstance(res[t], Exception):
                 failed.append((parsed.pop(t)[0], res[t]))
             else:
-                write(t, res[t] + ((pipe.collected[t].domain_search_block,) if search_domains else ()))
+                write(t, res[t] + ((pipe.collected[t].domain_search_block,) if search_domains else ())
+                      + ((pipe.collected[t].domain_score_block,) if score_domains else ()))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:
@@ -695,6 +733,11 @@ def batch_parser():
     # parameters of --domains, or the defaults); npz gains dom_hit_rank and dom_hit_tm, pdb / ca write <stem>.domain_hits.json,
     # the summary carries every target's best hit per domain.  Hidden like --search-refine, for the same reason.
     ap.add_argument("--search-domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    # --score-domains (with --natives): score every domain of a scored target's model - and of its native, where that is whole -
+    # against the native on the domain's own superposition (the parse by the parameters of --domains, or the defaults);
+    # <stem>.scores.json gains the key "domain_scores", npz gains dom_score_table and dom_score_res, the summary carries per target
+    # the domain count, tm_domains and lddt_inter with their means and medians.  Hidden like --search-refine, for the same reason.
+    ap.add_argument("--score-domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     # --domains [--domains-tau Q --domains-min-size N --domains-min-segment N]: split every target's model into structural domains
     # on the GPU; the summary gains every target's domain count with mean, median and the share of multi-domain targets, npz
     # gains dom_label and dom_table, pdb / ca write <stem>.domains.json.  Hidden like --search-refine, for the same reason.
@@ -809,6 +852,15 @@ def restrain_summary(reports):
     return out
 
 
+def domain_scores_brief(form):
+    """The summary's figures of one target from its "domain_scores" (score.domain_scores_json): the domain count, tm_domains and
+    lddt_inter of the native's leg - of the model's leg where the native has none - and which leg that is."""
+    leg = "native" if "native" in form else "model"
+    if leg not in form:
+        return {"leg": None, "domains": 0, "tm_domains": None, "lddt_inter": None}
+    return {"leg": leg, "domains": len(form[leg]["rows"]), "tm_domains": form[leg]["tm_domains"], "lddt_inter": form[leg]["lddt_inter"]}
+
+
 def score_summary(scores):
     """{stem: scores} -> the summary's part: the per-target scores, and mean and median of each score over the targets
     that have it."""
@@ -824,6 +876,13 @@ def score_summary(scores):
             vals = [f[name] for f in flat.values() if f.get(name) is not None]
             out["mean_" + name] = float(np.mean(vals)) if vals else None
             out["median_" + name] = float(np.median(vals)) if vals else None
+    per_domain = {stem: domain_scores_brief(s["domain_scores"]) for stem, s in scores.items() if s.get("domain_scores") is not None}
+    if per_domain:                                   # --score-domains: per target D, tm_domains and lddt_inter
+        out["domain_scored_targets"], out["domain_scores"] = len(per_domain), per_domain
+        for name in ("domains", "tm_domains", "lddt_inter"):
+            vals = [b[name] for b in per_domain.values() if b.get(name) is not None]
+            out["mean_domain_" + name] = float(np.mean(vals)) if vals else None
+            out["median_domain_" + name] = float(np.median(vals)) if vals else None
     tables = {stem: s["passes"] for stem, s in scores.items() if s.get("passes") is not None}
     if tables:                                       # --score-passes: the pass tables' aggregates
         out.update(pass_summary(tables))
@@ -877,6 +936,8 @@ def main(argv=None):
             ap.error("--search-domains needs --library")
         library = library if isinstance(library, _score.Library) else _score.Library.open(args.library)
         library.domains = True
+    if hasattr(args, "score_domains") and not args.natives:
+        ap.error("--score-domains needs --natives")
 
     dom_given = {k: getattr(args, "domains_" + k) for k in ("tau", "min_size", "min_segment") if hasattr(args, "domains_" + k)}
     if dom_given and not hasattr(args, "domains"):
@@ -904,7 +965,8 @@ def main(argv=None):
     store = job_store if (world > 1 and not args.static_shards) else None
     passes = {}
     try:
-        with (batch_domains(**dom_given) if hasattr(args, "domains") else contextlib.nullcontext()):
+        with (batch_domains(**dom_given) if hasattr(args, "domains") else contextlib.nullcontext()), \
+                (batch_score_domains() if hasattr(args, "score_domains") else contextlib.nullcontext()):
             n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                       weights_file=args.model_weights, streams=args.streams,
                                       device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,

@@ -463,6 +463,10 @@ static int search_reserve(dmp_ctx* c) {
 static int search_domains_reserve(dmp_ctx* c) {
   return c->opt.search_domains ? scratch_reserve(c, c->domsearch_ws, search_domains_need(c->max_L), "domain-search scratch") : DMP_OK;
 }
+// Option "score_domains": reserved when the option first becomes 1 on a context (score.hip has the layout).
+static int score_domains_reserve(dmp_ctx* c) {
+  return c->opt.score_domains ? scratch_reserve(c, c->domscore_ws, score_domains_need(c->max_L), "domain-score scratch") : DMP_OK;
+}
 // Option "score_passes": reserved when the option first becomes 1 on a context (score.hip has the layout).
 static int passes_reserve(dmp_ctx* c) {
   return c->opt.passes ? scratch_reserve(c, c->pass_ws, score_passes_need(c->max_L), "pass-score scratch") : DMP_OK;
@@ -598,6 +602,7 @@ static const Option OPTIONS[] = {
     {"search_refine", TAIL(search_refine), 0, DMP_SEARCH_MAX, 0, "search_refine must be 0 or 1 .. " DMP_STR(DMP_SEARCH_MAX) ", got %d"},   // refine the best R by the screen only
     {"search_domains", TAIL(search_domains), 0, 2, 0, "search_domains must be 0, 1 or 2 (tests only: 1 without the one-domain shortcut), got %d", OPT_RW,
      nullptr, nullptr, search_domains_reserve},                                                                  // needs "domains" = 1 and "search_structures" > 0
+    {"score_domains", TAIL(score_domains), 0, 1, 0, "score_domains must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, score_domains_reserve},   // needs "domains" = 1 and "score_native" = 1
     {"passes_run", CTX(passes_done), ANY, OPT_READ_ONLY},                                   // trunk passes of the last prediction
     {"search_chunk_used", CTX(search_last_C), ANY, OPT_READ_ONLY},                          // of the last prediction that searched: entries per chunk
     {"search_wg_per_cu", nullptr, nullptr, ANY, OPT_READ_ONLY, nullptr, nullptr, nullptr, get_search_wg_per_cu},
@@ -794,7 +799,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
   for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->entity_ws, &c->ss_ws, &c->exposure_ws,
-                     &c->domains_ws, &c->domsearch_ws})
+                     &c->domains_ws, &c->domsearch_ws, &c->domscore_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1334,6 +1339,8 @@ int dmp_predict_begin_units(dmp_ctx* ctx, const uint8_t* d_msa, int N, int L, co
   DMP_ARG(!c->opt.search_domains || c->opt.domains, "search_domains searches with the domains of option domains, which is 0: set domains to 1");
   DMP_ARG(!c->opt.search_domains || c->opt.search > 0,
           "search_domains searches the library of option search_structures, which is 0: set search_structures to the number of entries");
+  DMP_ARG(!c->opt.score_domains || c->opt.domains, "score_domains scores the domains of option domains, which is 0: set domains to 1");
+  DMP_ARG(!c->opt.score_domains || c->opt.score, "score_domains scores against the native trace of option score_native, which is 0: set score_native to 1");
   DMP_ARG(c->vg_waiters == 0, "members of the vertical-GRU group this context led have not taken their results yet");
   DMP_ARG(c->vg_leader == nullptr || c->vg_leader == c, "this context still waits for the vertical GRU of its group");
   c->vg_leader = nullptr;
@@ -1570,6 +1577,11 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.exposure && (rc = exposure(c, d_coords, L, d_native, d_conf + lay.exposure.off, s))) return rc;
   // option "domains": the domain block behind that, from the same two inputs (domains.hip)
   if (c->run.domains && (rc = domains(c, d_coords, L, d_native, d_conf + lay.domains.off, s))) return rc;
+  // option "score_domains": the domain-score block in front of the align block, from d_coords, the score block's native trace and the
+  // labels of the domain block (score.hip)
+  if (c->run.score_domains &&
+      (rc = score_domains(c, d_coords, L, d_conf + lay.score.off, d_conf + lay.domains.off, d_conf + lay.domscore.off, s)))
+    return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

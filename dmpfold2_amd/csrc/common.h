@@ -11,9 +11,9 @@
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
 // "search_refine", "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk",
-// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment", "search_domains"
+// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment", "search_domains", "score_domains"
 struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, search_refine = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0,
-                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10, search_domains = 0; };
+                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10, search_domains = 0, score_domains = 0; };
 
 namespace dmp {
 
@@ -103,11 +103,20 @@ __host__ __device__ inline DomSearchLayout domsearch_layout(int L, int K) {
   const int64_t r = (int64_t)DOMAINS_MAX * K;
   return {r, r + ALIGN_HEADER * r, r + ALIGN_HEADER * r + 2 * (int64_t)L * K};
 }
+//   | with "score_domains": the domain-score block = DOMSCORE_HEADER floats | two tables of DOMAINS_MAX rows of DOMSCORE_ROW floats
+//   (the model's labels, the native's) | per leg lddt_res [L], deviation [L], all of it out, between the domain-search block and
+//   the align block.
+constexpr int DOMSCORE_HEADER = 16, DOMSCORE_ROW = 32;
+struct DomScoreLayout { int rows, res, total; };                        // relative to the block's start
+__host__ __device__ inline DomScoreLayout domscore_layout(int L) {
+  const int res = DOMSCORE_HEADER + 2 * DOMAINS_MAX * DOMSCORE_ROW;
+  return {DOMSCORE_HEADER, res, res + 4 * L};
+}
 // The blocks in buffer order.  A block states where it begins, how many floats in front are the caller's input and where what
 // the library writes ends; a block whose option is off is empty (off = end).  `passes`: the rows R of the pass block, 0 =
 // none.  The align block's trailing input, whose length only the caller knows, lies behind `total`.
 struct ConfBlock { int64_t off, in, end; };                              // [off, off + in) in, [off + in, end) out
-struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, domsearch, align; int64_t total; };
+struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, domsearch, domscore, align; int64_t total; };
 __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int passes) {
   ConfLayout lay;
   int64_t at = 0;
@@ -126,6 +135,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
   lay.exposure = block(0, o.exposure ? exposure_floats(L) : 0);
   lay.domains = block(0, o.domains ? domains_floats(L) : 0);
   lay.domsearch = block(0, o.search_domains ? domsearch_layout(L, o.search).total : 0);
+  lay.domscore = block(0, o.score_domains ? domscore_layout(L).total : 0);
   lay.align = block(1, o.align ? align_layout(L).in : 0);
   lay.total = at;
   return lay;
@@ -133,7 +143,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
 // true for the floats a prediction writes: what becomes NaN when it latched a fault (api.hip)
 __host__ __device__ inline bool conf_is_out(const ConfLayout& lay, int64_t i) {
   auto out = [i](const ConfBlock& b) { return i >= b.off + b.in && i < b.end; };
-  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.domsearch) || out(lay.align);
+  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.domsearch) || out(lay.domscore) || out(lay.align);
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -404,6 +414,8 @@ struct dmp_ctx {
   dmp::Scratch exposure_ws;        // "exposure": the counters and the ticket, nothing behind them (exposure.hip: exposure_scratch)
   dmp::Scratch domains_ws;         // "domains": the counters | per entity the nodes, the lists, the slots, the cuts, the contact table,
                                    // the summed-area tables of one level (domains.hip: domains_scratch)
+  dmp::Scratch domscore_ws;        // "score_domains": the tickets | per leg the domains' first rows and seeds, headers and counters, the packed
+                                   // traces, the seed records (score.hip: domscore_scratch)
   dmp::Scratch domsearch_ws;       // "search_domains": nothing zeroed | the per-domain tables of "search_refine", the counts, the residue list (align.hip:
                                    // DomainQuery); the slots are search_ws's
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
@@ -660,7 +672,7 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 // what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
 ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
-    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L), search_domains_need(int max_L);
+    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L), search_domains_need(int max_L), score_domains_need(int max_L);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
@@ -675,6 +687,9 @@ int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hi
 int search_structures(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
 // option "search_domains" (align.hip): behind search_structures, the same stages with every domain of the model as the model
 int search_domains(dmp_ctx* c, const float* d_coords, int L, float* d_conf, const ConfLayout& lay, hipStream_t s);
+// option "score_domains" (score.hip): behind domains, every domain of both legs of the domain block scored against the native of the
+// score block on its own superposition, into the domain-score block
+int score_domains(dmp_ctx* c, const float* d_coords, int L, float* d_score_block, const float* d_domain_block, float* d_block, hipStream_t s);
 int search_wg_per_cu(int L, int max_m, int* out);   // resident align_refine workgroups per CU in the whole-model search's launch
 // The native entity of options "assign_ss", "exposure" and "domains" (entity.hip), where it lies in dmp_ctx::entity_ws:
 struct NativeEntity {

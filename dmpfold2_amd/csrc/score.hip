@@ -6,7 +6,8 @@
 //   score_search  one workgroup per seed of the superposition search; the last arriver (agent-scope ticket, common.h)
 //                 reduces the seeds' records in seed order and writes the header and the deviations.
 // Option "score_passes" (at the end of this file) runs score_lddt and score_search over the recorded passes' traces, the pass
-// as blockIdx.y, with the native that score_prep packed.
+// as blockIdx.y, with the native that score_prep packed.  Option "score_domains" (behind it) runs the same two bodies per domain
+// of the domain block's two labellings, on traces it packs itself.
 // Float64 from the float32 coordinates throughout; every sum has a fixed per-thread order, a fixed butterfly inside a
 // wave (both partners of an exchange form a + b, so all 64 lanes hold the same bits) and a fixed order over the four
 // waves' partial sums in LDS: the same bits on every run, and every thread of a workgroup takes the same branch.
@@ -51,27 +52,70 @@ __device__ inline double score_dist(const float* a, const float* b) {
 }
 
 
-// One description for both uses.  "score_native": one model trace (atom 1 of the backbone: `model` = d_coords + 3, 15 floats
+// One description for the three uses.  "score_native": one model trace (atom 1 of the backbone: `model` = d_coords + 3, 15 floats
 // between rows), a grid with gridDim.y = 1, `rows` null, the results into the score block.  "score_passes": the model traces
 // are ca_pass[pass0 + blockIdx.y] (3 floats between rows, 3L between traces); the packed native, the row index and the
-// header are the ones score_prep made for the score block of the same call; every pass has its own packed model, totals,
-// records and ticket (`*_stride` apart), and its five scores go to its row of the pass block.
+// header are the ones score_prep made for the score block of the same call (their strides are 0); every pass has its own packed
+// model, totals, records and ticket (`*_stride` apart), and its five scores go to its row of the pass block.  "score_domains"
+// (at the end of this file): a slot is a leg, everything in it one leg apart - its own packed native, columns and headers too -
+// and `info` says where each domain lies inside the leg.
 struct ScoreArgs {
   const float* model;    // the model trace's first row
   int model_row;         // floats between its rows
   int64_t model_stride;  // floats between the traces of consecutive passes
   float* blk;            // the score block: [0, 3L) native (in), 3L lnorm (in), the rest out
   int L;
-  float* pm;             // [n][3] packed model trace (pass y: + y * pm_stride)
-  float* qn;             // [n][3] packed native trace
-  int* idx;              // [n] alignment column of a packed row
-  double* hdr;           // [8]
-  double* rec;           // [seeds][SCORE_REC] (pass y: + y * rec_stride)
-  unsigned long long* tot;   // [2] lDDT: preserved, pairs (pass y: + y * tot_stride)
-  unsigned* ticket;      // zero between launches (pass y: + y)
+  float* pm;             // [n][3] packed model trace (slot y: + y * pm_stride)
+  float* qn;             // [n][3] packed native trace (slot y: + y * qn_stride)
+  int* idx;              // [n] alignment column of a packed row (slot y: + y * idx_stride)
+  double* hdr;           // [8] (slot y: + y * hdr_stride)
+  double* rec;           // [seeds][SCORE_REC] (slot y: + y * rec_stride)
+  unsigned long long* tot;   // [2] lDDT: preserved, pairs (slot y: + y * tot_stride)
+  unsigned* ticket;      // zero between launches (slot y: + y * ticket_stride)
   int64_t pm_stride, rec_stride, tot_stride;
   float* rows;           // null, or row 0 of this launch's passes in the pass block
+  int64_t qn_stride, idx_stride, hdr_stride;   // 0: one native, one index, one header for every slot
+  int ticket_stride;     // 1, or the tickets of a leg
+  int* info;             // "score_domains" only: DS_INFO ints per leg (below), idx_stride apart
+  float* dom;            // "score_domains" only: the domain-score block
 };
+
+// What one launch's workgroup works on, resolved from the arguments: the whole slot y ("score_native", "score_passes"), or
+// domain d of leg y ("score_domains").  The packed rows [r0, r0 + n) of the slot's `nall` are the trace that is scored; the
+// rest of the slot's rows are only partners of the two outer counters of the lDDT.
+struct ScoreView {
+  const float *pm, *qn;      // the slot's packed traces, row 0
+  const int* idx;            // the slot's columns
+  const double* hdr;         // n, lnorm, d0, d_cut of the trace that is scored
+  double* rec;               // its seed records
+  unsigned long long* tot;   // [2] preserved, pairs inside it (+ [2] the outer counters, with `outer`)
+  unsigned* ticket;
+  int r0, n, nall;
+  bool outer;                // count the pairs that leave the trace as well, and count whatever n is
+  float* head;               // where header float 0 (lnorm) would lie: floats 2 .. 23 are written; null for a pass
+  float* row;                // a pass's row, or null
+  float* lddt_res;           // [L] by column, or null
+  float* dev;                // [L] by column, or null
+};
+__device__ inline ScoreView score_view(const ScoreArgs& a, int y) {
+  ScoreView v;
+  v.pm = a.pm + y * a.pm_stride;
+  v.qn = a.qn + y * a.qn_stride;
+  v.idx = a.idx + y * a.idx_stride;
+  v.hdr = a.hdr + y * a.hdr_stride;
+  v.rec = a.rec + y * a.rec_stride;
+  v.tot = a.tot + y * a.tot_stride;
+  v.ticket = a.ticket + y * a.ticket_stride;
+  v.r0 = 0;
+  v.n = v.nall = (int)v.hdr[HDR_N];
+  v.outer = false;
+  const ScoreLayout lay = score_layout(a.L);
+  v.head = a.rows ? nullptr : a.blk + lay.lnorm;
+  v.row = a.rows ? a.rows + PASS_ROW * (int64_t)y : nullptr;
+  v.lddt_res = a.rows ? nullptr : a.blk + lay.lddt_res;       // the passes have no per-residue arrays
+  v.dev = a.rows ? nullptr : a.blk + lay.deviation;
+  return v;
+}
 
 // ---------------------------------------------------------------------------------------
 // score_prep: pack the present rows, the constants, NaN into the out slots
@@ -144,67 +188,80 @@ __host__ __device__ inline int score_lddt_groups(int L) {
   return g < 1 ? 1 : (g > SC_LDDT_MAX_WG ? SC_LDDT_MAX_WG : g);
 }
 
-__global__ __launch_bounds__(SC_THREADS) void score_lddt_kernel(ScoreArgs a) {
-  extern __shared__ float sm[];          // 2 x 3n coordinates
-  __shared__ int ired[SC_WAVES][2];
-  const int n = (int)a.hdr[HDR_N], L = a.L, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (n < 3) return;                     // every out slot but n_pairs stays NaN
-  float* pm = sm;
-  float* qn = sm + 3 * n;
-  const float* gpm = a.pm + blockIdx.y * a.pm_stride;
-  unsigned long long* tot = a.tot + blockIdx.y * a.tot_stride;
-  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = gpm[i]; qn[i] = a.qn[i]; }
+// The rows of the view's trace dealt to `groups` workgroups, this one being number `g`; the partners of a row are all the
+// slot's rows: those of the trace count for the lDDT, the others - with `outer` - into the two outer counters.
+__device__ inline void score_lddt_body(const ScoreView& v, int g, int groups, float* sm) {
+  __shared__ int ired[SC_WAVES][4];
+  const int n = v.n, nall = v.nall, r0 = v.r0, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (n < 3 && !v.outer) return;         // every out slot but n_pairs stays NaN
+  float* pm = sm;                        // 2 x 3 nall coordinates
+  float* qn = sm + 3 * nall;
+  for (int i = tid; i < 3 * nall; i += SC_THREADS) { pm[i] = v.pm[i]; qn[i] = v.qn[i]; }
   __syncthreads();
-  float* out = a.rows ? nullptr : a.blk + score_layout(L).lddt_res;     // the passes have no per-residue arrays
-  unsigned long long tot_pres = 0ull, tot_part = 0ull;
-  for (int i = blockIdx.x; i < n; i += gridDim.x) {
-    int pres = 0, part = 0;
-    for (int j = tid; j < n; j += SC_THREADS) {
+  float* out = n < 3 ? nullptr : v.lddt_res;
+  unsigned long long tot_pres = 0ull, tot_part = 0ull, tot_opres = 0ull, tot_opart = 0ull;
+  for (int i = r0 + g; i < r0 + n; i += groups) {
+    int pres = 0, part = 0, opres = 0, opart = 0;
+    for (int j = tid; j < nall; j += SC_THREADS) {
       if (j == i) continue;
       const double dn = score_dist(qn + 3 * i, qn + 3 * j);
       if (dn < 15.0) {
         const double e = fabs(score_dist(pm + 3 * i, pm + 3 * j) - dn);
-        part += 1;
-        pres += (e < 0.5 ? 1 : 0) + (e < 1.0 ? 1 : 0) + (e < 2.0 ? 1 : 0) + (e < 4.0 ? 1 : 0);
+        const int kept = (e < 0.5 ? 1 : 0) + (e < 1.0 ? 1 : 0) + (e < 2.0 ? 1 : 0) + (e < 4.0 ? 1 : 0);
+        if (j >= r0 && j < r0 + n) { part += 1; pres += kept; }
+        else { opart += 1; opres += kept; }
       }
     }
     for (int off = 32; off > 0; off >>= 1) {
       pres += __shfl_xor(pres, off, 64);
       part += __shfl_xor(part, off, 64);
+      opres += __shfl_xor(opres, off, 64);
+      opart += __shfl_xor(opart, off, 64);
     }
     __syncthreads();
-    if (lane == 0) { ired[wv][0] = pres; ired[wv][1] = part; }
+    if (lane == 0) { ired[wv][0] = pres; ired[wv][1] = part; ired[wv][2] = opres; ired[wv][3] = opart; }
     __syncthreads();
     if (tid == 0) {
-      pres = part = 0;
-      for (int k = 0; k < SC_WAVES; ++k) { pres += ired[k][0]; part += ired[k][1]; }
-      if (out) out[a.idx[i]] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
+      pres = part = opres = opart = 0;
+      for (int k = 0; k < SC_WAVES; ++k) { pres += ired[k][0]; part += ired[k][1]; opres += ired[k][2]; opart += ired[k][3]; }
+      if (out) out[v.idx[i]] = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
       tot_pres += (unsigned long long)pres;
       tot_part += (unsigned long long)part;
+      tot_opres += (unsigned long long)opres;
+      tot_opart += (unsigned long long)opart;
     }
   }
   if (tid == 0) {
-    __hip_atomic_fetch_add(&tot[0], tot_pres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(&tot[1], tot_part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&v.tot[0], tot_pres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&v.tot[1], tot_part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v.outer) {
+      __hip_atomic_fetch_add(&v.tot[2], tot_opres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&v.tot[3], tot_opart, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
+}
+
+__global__ __launch_bounds__(SC_THREADS) void score_lddt_kernel(ScoreArgs a) {
+  extern __shared__ float sm[];
+  score_lddt_body(score_view(a, blockIdx.y), blockIdx.x, gridDim.x, sm);
 }
 
 // ---------------------------------------------------------------------------------------
 // score_search: one workgroup per seed
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
-  extern __shared__ float sm[];          // 2 x 3n coordinates, then n flags: the set S
+// Seed `seed` of the view's trace; at most `cap` seeds run (the launch's grid).  sm: 2 x 3n coordinates, then n flags: the set S.
+__device__ inline void score_search_body(const ScoreView& v, int seed, int cap, float* sm) {
   __shared__ double wred[SC_WAVES][16];
   __shared__ double bc[12];              // R, t of this iteration (at the end: of the best seed)
   __shared__ int sh_last, sh_seed[SC_WAVES];
-  const int n = (int)a.hdr[HDR_N], L = a.L, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n = v.n, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (n < 3) return;
   int nseeds = score_seeds(n);
-  if (nseeds > (int)gridDim.x) nseeds = (int)gridDim.x;     // never: score_seeds does not decrease with n, the grid is score_seeds(L)
-  if ((int)blockIdx.x >= nseeds) return;
-  const double lnorm = a.hdr[HDR_LNORM], d0 = a.hdr[HDR_D0], d_cut = a.hdr[HDR_DCUT];
+  if (nseeds > cap) nseeds = cap;        // never: score_seeds does not decrease with n, the grid is score_seeds(L)
+  if (seed >= nseeds) return;
+  const double lnorm = v.hdr[HDR_LNORM], d0 = v.hdr[HDR_D0], d_cut = v.hdr[HDR_DCUT];
   // (level, start) of this seed
-  int frag, start = (int)blockIdx.x;
+  int frag, start = seed;
   {
     int f[6];
     const int m = score_levels(n, f);
@@ -215,10 +272,12 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   float* pm = sm;
   float* qn = sm + 3 * n;
   unsigned char* fl = reinterpret_cast<unsigned char*>(sm + 6 * n);
-  const float* gpm = a.pm + blockIdx.y * a.pm_stride;
-  double* grec = a.rec + blockIdx.y * a.rec_stride;
-  unsigned* ticket = a.ticket + blockIdx.y;
-  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = gpm[i]; qn[i] = a.qn[i]; }
+  const float* gpm = v.pm + 3 * v.r0;
+  const float* gqn = v.qn + 3 * v.r0;
+  const int* gidx = v.idx + v.r0;
+  double* grec = v.rec;
+  unsigned* ticket = v.ticket;
+  for (int i = tid; i < 3 * n; i += SC_THREADS) { pm[i] = gpm[i]; qn[i] = gqn[i]; }
   for (int k = tid; k < n; k += SC_THREADS) fl[k] = (k >= start && k < start + frag) ? 1 : 0;
   __syncthreads();
 
@@ -229,7 +288,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   const double *best_R = best.R, *best_t = best.t, *best_cnt = best.cnt;
 
   if (tid == 0) {
-    double* rec = grec + (int64_t)blockIdx.x * SCORE_REC;
+    double* rec = grec + (int64_t)seed * SCORE_REC;
     agent_store_f64(rec + REC_TM, best_tm);
     for (int c = 0; c < 5; ++c) agent_store_f64(rec + REC_CNT + c, best_cnt[c]);
     for (int c = 0; c < 9; ++c) agent_store_f64(rec + REC_R + c, best_R[c]);
@@ -277,21 +336,20 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
     const float f_tm = found ? (float)top : nan;
     const float f_ts = (float)((((cmax[1] + cmax[2]) + cmax[3]) + cmax[4]) / 4.0 / lnorm);
     const float f_ha = (float)((((cmax[0] + cmax[1]) + cmax[2]) + cmax[3]) / 4.0 / lnorm);
-    const unsigned long long* tot = a.tot + blockIdx.y * a.tot_stride;
-    const unsigned long long pres = tot[0], part = tot[1];         // score_lddt ran before this launch
+    const unsigned long long pres = v.tot[0], part = v.tot[1];         // score_lddt ran before this launch
     const float f_lddt = part > 0 ? (float)((double)pres / (4.0 * (double)part)) : 0.f;
-    if (a.rows) {                                      // a pass: its five scores into its row, nothing else
-      float* row = a.rows + PASS_ROW * (int64_t)blockIdx.y;
+    if (v.row) {                                       // a pass: its five scores into its row, nothing else
+      float* row = v.row;
       row[2] = f_tm; row[3] = f_ts; row[4] = f_ha; row[5] = f_rmsd; row[6] = f_lddt;
       sh_last = 0;
     } else {
-      float* out = a.blk + score_layout(L).lnorm;      // the header
+      float* out = v.head;                             // the header
       out[2] = f_rmsd; out[3] = f_tm; out[4] = f_ts; out[5] = f_ha; out[6] = f_lddt;
       for (int c = 0; c < 5; ++c) out[7 + c] = (float)cmax[c];
       for (int c = 0; c < 12; ++c) {
-        const double v = agent_load_f64(rec + REC_R + c);
-        bc[c] = v;
-        out[12 + c] = found ? (float)v : nan;
+        const double w = agent_load_f64(rec + REC_R + c);
+        bc[c] = w;
+        out[12 + c] = found ? (float)w : nan;
       }
       sh_last = found ? 1 : 0;
     }
@@ -302,8 +360,12 @@ __global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
   double R[9], t[3];
   for (int c = 0; c < 9; ++c) R[c] = bc[c];
   for (int c = 0; c < 3; ++c) t[c] = bc[9 + c];
-  float* dev = a.blk + score_layout(L).deviation;
-  for (int k = tid; k < n; k += SC_THREADS) dev[a.idx[k]] = (float)score_dev(R, t, pm + 3 * k, qn + 3 * k);
+  for (int k = tid; k < n; k += SC_THREADS) v.dev[gidx[k]] = (float)score_dev(R, t, pm + 3 * k, qn + 3 * k);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void score_search_kernel(ScoreArgs a) {
+  extern __shared__ float sm[];
+  score_search_body(score_view(a, blockIdx.y), blockIdx.x, gridDim.x, sm);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -365,6 +427,7 @@ static void score_scratch_args(const dmp_ctx* c, unsigned char* slots, const Pas
   a.rec_stride = sl.total / 8;
   a.pm_stride = sl.total / 4;
   a.tot_stride = sl.total / 8;
+  a.ticket_stride = 1;
 }
 
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s) {
@@ -449,6 +512,220 @@ int score_passes(dmp_ctx* c, int L, int R, int rows, float* d_block, hipStream_t
     DMP_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(pass_header_kernel, dim3(1), dim3(64), 0, s, d_block, rows, c->best_pass);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// option "score_domains": the domain-score block (include/dmpfold_hip.h)
+// ---------------------------------------------------------------------------------------
+// Four launches behind `domains`, a leg (0: the model's labels, 1: the native's) as the slot of a ScoreArgs:
+//   domscore_prep    one workgroup per leg: the labels of both legs validated as domsearch_prep does (align.hip); the leg's part
+//                    of the block filled; the present rows packed in (domain, column) order - model from d_coords, native from
+//                    the score block -, and per domain its header (n, lnorm = n, d0, d_cut), its first packed row and its
+//                    first seed: the prefix sums of the <= 16 row counts and seed counts.
+//   domscore_lddt    score_lddt_body, (row group, domain, leg): the pairs inside the domain and the pairs that leave it.
+//   domscore_search  score_search_body on a flat grid of Dmax + 5L workgroups per leg (score_seeds(n) <= 1 + 5n and the domains
+//                    partition the chain): a workgroup finds its (domain, seed) in the prefix sums; each domain has its ticket
+//                    and its stretch of the leg's records.
+//   domscore_counts  the four integer counts of every row.
+// Nothing here reads what score_native left in score_ws.
+constexpr int DS_D = 0, DS_ROW0 = 1, DS_SEED0 = 1 + DOMAINS_MAX + 1, DS_INFO = 64;     // ints of a leg's info: D (0: no such leg),
+                                                                                       // 17 first rows, 17 first seeds
+constexpr int64_t DOMSCORE_HEAD_BYTES = 4 * 2 * DOMAINS_MAX;                           // the tickets [leg][domain]
+struct DomScoreScratch { int64_t info, hdr, tot, qn, pm, idx, rec, leg, total; };      // bytes; a leg's parts from the leg's start
+inline DomScoreScratch domscore_scratch(int max_L) {
+  DomScoreScratch w;
+  w.info = 0;
+  w.hdr = w.info + up16(4 * DS_INFO);
+  w.tot = w.hdr + 64 * DOMAINS_MAX;
+  w.qn = w.tot + 32 * DOMAINS_MAX;
+  w.pm = w.qn + up16(12 * (int64_t)max_L);
+  w.idx = w.pm + up16(12 * (int64_t)max_L);
+  w.rec = w.idx + up16(4 * (int64_t)max_L);
+  w.leg = w.rec + up16(8 * (int64_t)SCORE_REC * (DOMAINS_MAX + 5 * (int64_t)max_L));
+  w.total = DOMSCORE_HEAD_BYTES + 2 * w.leg;
+  return w;
+}
+ScratchNeed score_domains_need(int max_L) { return {domscore_scratch(max_L).total, DOMSCORE_HEAD_BYTES}; }
+
+// domain d of leg `leg`
+__device__ inline ScoreView domscore_view(const ScoreArgs& a, int leg, int d) {
+  const int* info = a.info + leg * a.idx_stride;
+  const DomScoreLayout lay = domscore_layout(a.L);
+  ScoreView v;
+  v.pm = a.pm + leg * a.pm_stride;
+  v.qn = a.qn + leg * a.qn_stride;
+  v.idx = a.idx + leg * a.idx_stride;
+  v.hdr = a.hdr + leg * a.hdr_stride + 8 * d;
+  v.rec = a.rec + leg * a.rec_stride + (int64_t)SCORE_REC * info[DS_SEED0 + d];
+  v.tot = a.tot + leg * a.tot_stride + 4 * d;
+  v.ticket = a.ticket + leg * a.ticket_stride + d;
+  v.r0 = info[DS_ROW0 + d];
+  v.n = info[DS_ROW0 + d + 1] - v.r0;
+  v.nall = info[DS_ROW0 + info[DS_D]];
+  v.outer = true;
+  v.head = a.dom + lay.rows + DOMSCORE_ROW * (DOMAINS_MAX * leg + d);
+  v.row = nullptr;
+  v.lddt_res = a.dom + lay.res + 2 * (int64_t)a.L * leg;
+  v.dev = v.lddt_res + a.L;
+  return v;
+}
+
+// D and the labels of one leg of the domain block (labels at `lab`): D if they are valid, 0 if not.  Every thread calls it;
+// lab8 [L] gets the labels, 0xff for an invalid one.
+__device__ inline int domscore_labels(float Df, const float* lab, int L, int dmax, unsigned char* lab8, int* bad) {
+  const int tid = threadIdx.x;
+  const int D = Df >= 1.f && Df <= (float)dmax && Df <= (float)DOMAINS_MAX && Df == floorf(Df) ? (int)Df : 0;      // a NaN fails the comparisons
+  int mine = 0;
+  for (int i = tid; i < L; i += SC_THREADS) {
+    const float lf = lab[i];
+    const bool ok = lf >= 0.f && lf < (float)D && lf == floorf(lf);
+    mine |= ok ? 0 : 1;
+    lab8[i] = ok ? (unsigned char)lf : (unsigned char)0xff;
+  }
+  __syncthreads();                        // (bad[] of the call before has been read)
+  bad[tid] = mine;
+  __syncthreads();
+  int any = 0;
+  for (int k = 0; k < SC_THREADS; ++k) any |= bad[k];
+  return any ? 0 : D;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void domscore_prep_kernel(ScoreArgs a, const float* dblk, int dmax) {
+  __shared__ unsigned char lab[DMP_MAX_L], other[DMP_MAX_L];
+  __shared__ int bad[SC_THREADS], cnt[DOMAINS_MAX], size[DOMAINS_MAX], row0[DOMAINS_MAX + 1];
+  const int tid = threadIdx.x, leg = blockIdx.x, L = a.L < DMP_MAX_L ? a.L : DMP_MAX_L;
+  const DomScoreLayout lay = domscore_layout(a.L);
+  const float nan = __builtin_nanf("");
+  int* info = a.info + leg * a.idx_stride;
+  // both workgroups judge both legs: the model's must be valid; the native's valid, or absent (its D is 0)
+  const int D0 = domscore_labels(dblk[0], dblk + DOMAINS_HEADER, L, dmax, leg == 0 ? lab : other, bad);
+  const float D1f = dblk[DOMAINS_HEADER / 2];
+  const int D1 = D1f == 0.f ? 0 : domscore_labels(D1f, dblk + DOMAINS_HEADER + a.L, L, dmax, leg == 1 ? lab : other, bad);
+  const bool valid = D0 > 0 && (D1f == 0.f || D1 > 0);
+  const int D = valid ? (leg == 0 ? D0 : D1) : 0;
+  __syncthreads();
+  if (tid < DOMAINS_MAX) {                // rows present and residues of domain tid
+    int n = 0, sz = 0;
+    for (int i = 0; i < L; ++i)
+      if (tid < D && lab[i] == tid) {
+        const float x = a.blk[3 * i];
+        sz += 1;
+        n += x == x ? 1 : 0;
+      }
+    cnt[tid] = n;
+    size[tid] = sz;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int rows = 0, seeds = 0;
+    info[DS_D] = D;
+    for (int d = 0; d < DOMAINS_MAX; ++d) {
+      const int n = cnt[d];
+      row0[d] = rows;
+      info[DS_ROW0 + d] = rows;
+      info[DS_SEED0 + d] = seeds;
+      rows += n;
+      seeds += n < 3 ? 0 : score_seeds(n);           // at most D + 5 (rows of the leg) <= dmax + 5L: the grid, and the records
+      const double lnorm = (double)n, d0 = score_d0(lnorm);
+      double* hdr = a.hdr + leg * a.hdr_stride + 8 * d;
+      hdr[HDR_N] = lnorm;
+      hdr[HDR_LNORM] = lnorm;
+      hdr[HDR_D0] = d0;
+      hdr[HDR_DCUT] = fmin(fmax(d0, 4.5), 8.0);
+      unsigned long long* tot = a.tot + leg * a.tot_stride + 4 * d;
+      tot[0] = tot[1] = tot[2] = tot[3] = 0ull;
+    }
+    row0[DOMAINS_MAX] = rows;
+    info[DS_ROW0 + DOMAINS_MAX] = rows;
+    info[DS_SEED0 + DOMAINS_MAX] = seeds;
+  }
+  __syncthreads();
+  // the leg's part of the block: its header words, its table, its two arrays
+  if (leg == 0)
+    for (int i = tid; i < DOMSCORE_HEADER; i += SC_THREADS)
+      a.dom[i] = !valid ? nan : i == 0 ? (float)D0 : i == 1 ? (float)D1 : i == 2 ? (float)row0[DOMAINS_MAX] : 0.f;
+  float* rows = a.dom + lay.rows + DOMSCORE_ROW * DOMAINS_MAX * leg;
+  for (int i = tid; i < DOMSCORE_ROW * DOMAINS_MAX; i += SC_THREADS) {
+    const int d = i / DOMSCORE_ROW, q = i % DOMSCORE_ROW;
+    rows[i] = d >= D ? nan : q <= 1 ? (float)cnt[d] : q < 24 ? nan : q == 28 ? (float)size[d] : 0.f;      // 24 .. 27: domscore_counts
+  }
+  float* res = a.dom + lay.res + 2 * (int64_t)a.L * leg;
+  for (int i = tid; i < 2 * a.L; i += SC_THREADS) res[i] = nan;
+  if (tid < D) {                          // the present rows of domain tid, in rising column
+    int at = row0[tid];
+    float* pm = a.pm + leg * a.pm_stride;
+    float* qn = a.qn + leg * a.qn_stride;
+    int* idx = a.idx + leg * a.idx_stride;
+    for (int i = 0; i < L; ++i) {
+      if (lab[i] != tid) continue;
+      const float x = a.blk[3 * i];
+      if (x != x) continue;
+      for (int c = 0; c < 3; ++c) {      // at < row0[tid + 1] <= L: the same rows were counted
+        pm[3 * at + c] = a.model[a.model_row * (int64_t)i + c];
+        qn[3 * at + c] = a.blk[3 * i + c];
+      }
+      idx[at] = i;
+      ++at;
+    }
+  }
+}
+
+__global__ __launch_bounds__(SC_THREADS) void domscore_lddt_kernel(ScoreArgs a) {
+  extern __shared__ float sm[];
+  const int leg = blockIdx.z, d = blockIdx.y;
+  if (d >= a.info[leg * a.idx_stride + DS_D]) return;                  // uniform
+  score_lddt_body(domscore_view(a, leg, d), blockIdx.x, gridDim.x, sm);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void domscore_search_kernel(ScoreArgs a) {
+  extern __shared__ float sm[];
+  const int leg = blockIdx.y, b = blockIdx.x;
+  const int* info = a.info + leg * a.idx_stride;
+  const int D = info[DS_D];
+  if (D == 0 || b >= info[DS_SEED0 + D]) return;                       // uniform
+  int d = 0;
+  while (d < D - 1 && b >= info[DS_SEED0 + d + 1]) ++d;
+  score_search_body(domscore_view(a, leg, d), b - info[DS_SEED0 + d], info[DS_SEED0 + d + 1] - info[DS_SEED0 + d], sm);
+}
+
+__global__ void domscore_counts_kernel(ScoreArgs a) {
+  const int leg = threadIdx.x / DOMAINS_MAX, d = threadIdx.x % DOMAINS_MAX;
+  if (leg >= 2 || d >= a.info[leg * a.idx_stride + DS_D]) return;
+  const unsigned long long* tot = a.tot + leg * a.tot_stride + 4 * d;
+  float* row = a.dom + domscore_layout(a.L).rows + DOMSCORE_ROW * (DOMAINS_MAX * leg + d);
+  for (int c = 0; c < 4; ++c) row[24 + c] = (float)tot[c];
+}
+
+int score_domains(dmp_ctx* c, const float* d_coords, int L, float* d_score_block, const float* d_domain_block, float* d_block, hipStream_t s) {
+  const DomScoreScratch w = domscore_scratch(c->max_L);
+  unsigned char* leg0 = c->domscore_ws.p + DOMSCORE_HEAD_BYTES;
+  const int dmax = std::max(1, std::min(DOMAINS_MAX, L / c->run.dom_min_size));
+  ScoreArgs a{};
+  a.model = d_coords + 3;
+  a.model_row = 15;
+  a.blk = d_score_block;                 // only its native trace is read
+  a.L = L;
+  a.dom = d_block;
+  a.info = reinterpret_cast<int*>(leg0 + w.info);
+  a.hdr = reinterpret_cast<double*>(leg0 + w.hdr);
+  a.tot = reinterpret_cast<unsigned long long*>(leg0 + w.tot);
+  a.qn = reinterpret_cast<float*>(leg0 + w.qn);
+  a.pm = reinterpret_cast<float*>(leg0 + w.pm);
+  a.idx = reinterpret_cast<int*>(leg0 + w.idx);
+  a.rec = reinterpret_cast<double*>(leg0 + w.rec);
+  a.ticket = reinterpret_cast<unsigned*>(c->domscore_ws.p);
+  a.pm_stride = a.qn_stride = a.idx_stride = w.leg / 4;
+  a.hdr_stride = a.rec_stride = a.tot_stride = w.leg / 8;
+  a.ticket_stride = DOMAINS_MAX;
+  hipLaunchKernelGGL(domscore_prep_kernel, dim3(2), dim3(SC_THREADS), 0, s, a, d_domain_block, dmax);
+  DMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(domscore_lddt_kernel, dim3(score_lddt_groups(L), dmax, 2), dim3(SC_THREADS), sizeof(float) * 6 * L, s, a);
+  DMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(domscore_search_kernel, dim3(dmax + 5 * L, 2), dim3(SC_THREADS), sizeof(float) * 6 * L + round_up(L, 16), s, a);
+  DMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(domscore_counts_kernel, dim3(1), dim3(64), 0, s, a);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

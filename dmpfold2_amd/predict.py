@@ -341,6 +341,8 @@ CALL_CHECKS = {"structure": _score.as_structure}
 # with a native only: an option that needs it asks for one (`needs_native`) where none is given.
 NEEDS = {"score_map": ("emit_distmap", "score_native"), "score_passes": ("score_native",), "restrain_milli": ("emit_distmap",)}
 NATIVE_NEEDED = {"score_map": "scores the distance map{s}", "score_passes": "scores every pass"}
+# (option "score_domains" is no field of a call's `Extras` and no flag of the parsers' loops over NATIVE_NEEDED: its text stands alone)
+SCORE_DOMAINS_NEEDS_NATIVE = "score_domains scores every domain against a native structure: give `native`"
 _BLOCK_OF = {row.option: row for row in _score.BLOCKS}
 
 
@@ -427,14 +429,15 @@ def agree_options(rows):
     return Flags(all(emits), any(emits), *rows[0][1:])
 
 
-def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False):
+def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False, score_domains=False):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is laid out (score.Layout) for the options as the context holds them (`flags`) -
     the library cannot check it - and its input blocks are filled from `extras`: with "score_native" on the native trace (no
     `native` = no row present: n_pairs 0, NaN scores); with "align_structure" on m and the rows of `structure` (none: m = 0,
     which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU.
     `domains`: option "domains" on (it travels beside `flags`, whose fields callers know by position); `search_domains`: option
-    "search_domains" on - the buffer then holds the domain-search block in front of the align block."""
+    "search_domains" on - the buffer then holds the domain-search block in front of the align block; `score_domains`: option
+    "score_domains" on - the domain-score block behind that."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -448,7 +451,7 @@ def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None,
+                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None, score_domains=score_domains,
                  **{key: getattr(flags, key) for key in OWN_BLOCK})
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
@@ -624,6 +627,41 @@ class Engine:
             hits["refine"] = library.refine
         return hits
 
+    @property
+    def domain_score_block(self):
+        """"score_domains": 1040 + 4L floats - every domain of the last prediction scored against the native - or None."""
+        return self._last.out.domain_score_block
+
+    @property
+    def domain_scores(self):
+        """The domain scores of the last prediction as score.unpack_domain_scores gives them; None if it ran without option
+        "score_domains".  Synchronises with the GPU."""
+        block = self.domain_score_block
+        if block is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        return _score.unpack_domain_scores(block, self._last.L)
+
+    _score_domains = False           # set_score_domains / with_score_domains: the calls of this engine score every domain
+
+    def set_score_domains(self, on):
+        """Every domain scored against the native (option "score_domains") by this engine's calls from now on: a call given a
+        `native` sets the option for itself - and "domains", with the parameters of `set_domains` / `with_domains` or the
+        defaults - and puts both back; it scores each domain of the model's parse and of the native's against the native on the
+        domain's own superposition.  What a call returns does not change, the result is in `domain_scores`
+        (score.unpack_domain_scores) and `domain_score_block`.  A call without `native` raises ValueError."""
+        self._score_domains = bool(on)
+
+    @contextlib.contextmanager
+    def with_score_domains(self):
+        """`set_score_domains(True)` for the duration of the block, then as it was."""
+        before = self._score_domains
+        try:
+            self._score_domains = True
+            yield self
+        finally:
+            self._score_domains = before
+
     def set_domains(self, on, tau=0.25, min_size=40, min_segment=10):
         """Option "domains" on this engine, as it stands from now on: every prediction's final C-alpha trace is split into
         structural domains on the GPU (and, with a whole `native`, the native's); what a call returns does not change, the
@@ -710,6 +748,11 @@ class Engine:
         if extras.library is not None and getattr(extras.library, "domains", False) and not self.get_option("search_domains"):
             turn_on("domains")                                     # (with the parameters set_domains / with_domains hold, or the defaults)
             want["search_domains"] = 1                             # the library searched with every domain of the model as well
+        if getattr(self, "_score_domains", False) and not self.get_option("score_domains"):        # (set_score_domains / with_score_domains)
+            if extras.native is None and not self.get_option("score_native"):
+                raise ValueError(SCORE_DOMAINS_NEEDS_NATIVE)
+            turn_on("domains")                                     # (likewise: the parameters as they stand, or the defaults)
+            want["score_domains"] = 1                              # behind "score_native" and "domains", which it needs
         before = {}
         try:
             for name, value in want.items():
@@ -741,7 +784,8 @@ class Engine:
         with torch.cuda.device(self.device):
             self._forget_last()
             domains = bool(self.get_option("domains"))
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, bool(self.get_option("search_domains")))
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, bool(self.get_option("search_domains")),
+                                bool(self.get_option("score_domains")))
             self._last = _Last(out._replace(coords=None), L, library if search else None, out.coords if domains else None)
             milli = self.get_option("restrain_milli")
             if milli > 0:
@@ -1023,6 +1067,19 @@ class Pipeline:
             self.set_option(name, value)
         self.set_option("domains", 1 if on else 0)
 
+    def use_score_domains(self, on):
+        """Option "score_domains" on every engine: every domain of targets submitted from now on - of the model's parse and,
+        where the native is whole, of the native's - is scored against the `native` given to `submit` on its own
+        superposition; the domain-score block (1040 + 4L floats, score.unpack_domain_scores) is the attribute
+        `domain_score_block` of what `outputs_of` gives.  It needs `set_score` on - RuntimeError if not - and turns "domains" on
+        where it is off, with the parameters `use_domains` set, or the defaults; turning it off leaves both as they are.
+        Idle pipeline only."""
+        if on and not all(e.get_option("score_native") for e in self.engines):
+            raise RuntimeError("use_score_domains scores every domain against the native of \"score_native\", which is off: use set_score first")
+        if on and not all(e.get_option("domains") for e in self.engines):
+            self.set_option("domains", 1)
+        self.set_option("score_domains", 1 if on else 0)
+
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
@@ -1102,7 +1159,8 @@ class Pipeline:
                 raise RuntimeError("the engines must agree on \"domains_tau_milli\", \"domains_min_size\" and \"domains_min_segment\" "
                                    "(whichever of them runs a target must give the same parse); use use_domains")
             search_domains = agree([e.get_option("search_domains") for e in self.engines], "search_domains", "set_search")
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains)
+            score_domains = agree([e.get_option("score_domains") for e in self.engines], "score_domains", "use_score_domains")
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains, score_domains)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -1163,7 +1221,8 @@ class Pipeline:
 
     def outputs_of(self, ticket):
         """The score.Outputs of a queued target, which stays queued: every block as a view of its buffer, the domain-search
-        block of option "search_domains" - which `result` never hands out - among them (valid once the target is done)."""
+        block of option "search_domains" and the domain-score block of option "score_domains" - which `result` never hands out -
+        among them (valid once the target is done)."""
         return self._jobs[ticket].out
 
     def _result(self, ticket):
@@ -1417,7 +1476,7 @@ def aln_to_domains(input_file, *args, domains_tau=0.25, domains_min_size=40, dom
 def _coords_tuple(call, domains=None):
     """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave) -> what it returns."""
     v = SimpleNamespace(**call)
-    r, parse, _ = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
+    r, parse, _, _ = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
                                   v.native, v.native_chain, v.compare, v.compare_chain, v.search, distmap=v.return_distmap,
                                   scores=v.return_scores, alignment=v.return_alignment, hits=v.return_hits,
                                   map_scores=v.return_map_scores, pass_scores=v.return_pass_scores, ss=v.return_ss,
@@ -1454,8 +1513,11 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
 
 def _predict_file_with(domains, input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain,
                        compare, compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
-                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False):
-    """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None, the domain search or None).  `domains`: None, or
+                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False, score_domains=False):
+    """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None, the domain search or None, the domain scores or
+    None).  `score_domains` (needs `native`): every domain is scored against the native (Engine.with_score_domains); the fourth
+    part is then (the dict of Engine.domain_scores, the dict of score.unpack_domains of the same prediction, the raw block as an
+    array).  `domains`: None, or
     what domains_options gave - the prediction then runs with option "domains" (Engine.with_domains).  A `search` library with
     `domains` on is also searched with every domain of the model: the third part is then (the dict of Engine.domain_hits, the
     dict of score.unpack_domains of the same prediction)."""
@@ -1463,6 +1525,8 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
     for option, wanted in (("score_map", map_scores), ("score_passes", pass_scores)):
         if wanted and native is None:
             raise ValueError(needs_native(option, "return_" + _BLOCK_OF[option].name, "`native`"))
+    if score_domains and native is None:
+        raise ValueError(SCORE_DOMAINS_NEEDS_NATIVE)
     tol = None if converge is None else converge_to_mA(converge) * 1e-3     # (a bad tolerance raises before any work)
     dev = _resolve_device(device)
     aln = read_aln(input_file)
@@ -1488,13 +1552,16 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
         # (the engine holds both traces: its capacity covers the structure to align with, too)
         cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
-        with (eng.with_domains(domains[0] * 1e-3, *domains[1:]) if domains is not None else contextlib.nullcontext()):
+        with (eng.with_domains(domains[0] * 1e-3, *domains[1:]) if domains is not None else contextlib.nullcontext()), \
+                (eng.with_score_domains() if score_domains else contextlib.nullcontext()):
             out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
                                       native=native, structure=compare, library=search, score_map=bool(map_scores),
                                       score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain,
                                       restrain_cutoff=restrain_cutoff, exposure=bool(exposure))
         parse = eng.domains if domains is not None else None
         domain_hits = (eng.domain_hits, eng.domains) if eng.domain_search_block is not None else None
+        domain_scores = ((eng.domain_scores, eng.domains, eng.domain_score_block.cpu().numpy().copy())
+                         if eng.domain_score_block is not None else None)
         exposed = None
         if exposure:
             torch.cuda.synchronize(eng.device)
@@ -1505,7 +1572,7 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
                           pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
                           scores=eng.scores if native is not None and scores else None,
-                          alignment=eng.alignment if compare is not None and alignment else None), parse, domain_hits
+                          alignment=eng.alignment if compare is not None and alignment else None), parse, domain_hits, domain_scores
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1588,6 +1655,11 @@ def dmpfold_parser():
     # splits the model by the parameters of --domains, or the defaults); the JSON line of --search gains the key "domain_hits".
     # Hidden like --search-refine, for the same reason; README.md describes it.
     parser.add_argument("--search-domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    # --score-domains (with --native): score every domain of the model's parse - and of the native's, where it is whole - against the
+    # native on its own superposition (option "score_domains", which splits the model by the parameters of --domains, or the
+    # defaults); the JSON line of --native gains the key "domain_scores".  Hidden like --search-refine, for the same reason;
+    # README.md describes it.
+    parser.add_argument("--score-domains", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     parser.add_argument("--hits", type=str, default=None, required=False, metavar="FILE",
                         help="write the JSON line of --search to FILE instead of standard error")
     parser.add_argument("--ss", action="store_true", default=False,
@@ -1651,13 +1723,16 @@ def run_dmpfold(argv=None):
             parser.error("--search-domains needs --search")
         search = search if isinstance(search, _score.Library) else _score.Library.open(args.search)
         search.domains = True
+    if hasattr(args, "score_domains") and args.native is None:
+        parser.error("--score-domains needs --native")
     domains = domains_arguments(parser, args)
-    r, parse, domain_hits = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
+    r, parse, domain_hits, domain_scores = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
                                   args.model_weights, args.converge, args.native, args.native_chain, args.compare,
                                   args.compare_chain, search, distmap=args.distmap is not None, scores=args.native is not None,
                                   alignment=args.compare is not None, hits=args.search is not None, map_scores=args.score_map,
                                   pass_scores=args.score_passes, ss=args.ss, restrain=args.restrain,
-                                  restrain_cutoff=args.restrain_cutoff, exposure=args.exposure)
+                                  restrain_cutoff=args.restrain_cutoff, exposure=args.exposure,
+                                  score_domains=hasattr(args, "score_domains"))
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1679,6 +1754,8 @@ def run_dmpfold(argv=None):
             js["map"] = _score.map_scores_json(r.map_scores)
         if r.pass_scores is not None:
             js["passes"] = _score.pass_scores_json(r.pass_scores)
+        if domain_scores is not None:                      # (--score-domains)
+            js["domain_scores"] = _score.domain_scores_json(domain_scores[0], domain_scores[1])
         json_line(js, args.scores)
     if args.ss:
         json_line(_score.ss_json(r.ss), args.ss_file)

@@ -131,36 +131,43 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
 
       [0, L) confidences | L: map (L*L), info (3) | score_off (S0): score block (5L + 24) | mapscore_off (M0): map-score block
       (64 + L) | pass_off (T0): pass block (16 + 8R) | ss_off (U0): SS block (32 + 8L) | exposure_off (X0): exposure block (32 + 16L) |
-      domains_off (D0): domain block (32 + 2L + 256) | domain_search_off: domain-search block ((400 + 2L) K, with `search_domains`) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
+      domains_off (D0): domain block (32 + 2L + 256) | domain_search_off: domain-search block ((400 + 2L) K, with `search_domains`) | domain_score_off: domain-score block (1040 + 4L, with `score_domains`) | align_off (A0): align block (25 + 2L + 3m) | align_end | search_off (B0): search block (26K + 2LK + 3M)
 
     and `total` is the floats the buffer must hold.  `search_domains` (option "search_domains" on; an attribute beside the
     fields, like `domains`) puts the domain-search block, sized from the K of `search`, between the domain block and the
-    align block."""
+    align block; `score_domains` (option "score_domains" on; an attribute likewise) puts the domain-score block behind that, in
+    front of the align block."""
 
     def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None,
-                ss=False, exposure=False, domains=False, search_domains=False):
+                ss=False, exposure=False, domains=False, search_domains=False, score_domains=False):
         self = super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
                                None if passes is None else int(passes), bool(ss), bool(exposure))
         self.domains = bool(domains)
         self.search_domains = bool(search_domains)
+        self.score_domains = bool(score_domains)
         return self
 
     domains = False                  # (of a Layout made by `_make`)
     search_domains = False
+    score_domains = False
 
     def _replace(self, **changes):
         domains = changes.pop("domains", self.domains)
         search_domains = changes.pop("search_domains", self.search_domains)
+        score_domains = changes.pop("score_domains", self.score_domains)
         new = super()._replace(**changes)
         new.domains = bool(domains)
         new.search_domains = bool(search_domains)
+        new.score_domains = bool(score_domains)
         return new
 
     def floats(self, row):
         """The floats a row of BLOCKS takes in this buffer: 0 where its block is off."""
         if row is DOMAIN_SEARCH:
             return domain_search_floats(self.L, self.search[0]) if self.search_domains and self.search is not None else 0
+        if row is DOMAIN_SCORES:
+            return domain_score_floats(self.L) if self.score_domains else 0
         value = getattr(self, row.arg)
         return 0 if value is None or value is False else row.floats(self.L, value)
 
@@ -174,6 +181,9 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
             if row.key == "domains" and self.floats(DOMAIN_SEARCH):      # (no row of BLOCKS: see DOMAIN_SEARCH)
                 yield DOMAIN_SEARCH, at
                 at += self.floats(DOMAIN_SEARCH)
+            if row.key == "domains" and self.floats(DOMAIN_SCORES):      # (likewise: see DOMAIN_SCORES)
+                yield DOMAIN_SCORES, at
+                at += self.floats(DOMAIN_SCORES)
         yield None, at
 
     def _begin(self, key):
@@ -187,6 +197,7 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     exposure_off = property(lambda s: s._begin("exposure"))                                                 # X0
     domains_off = property(lambda s: s._begin("domains"))                                                   # D0
     domain_search_off = property(lambda s: s.domains_off + s.floats(BLOCK["domains"]))
+    domain_score_off = property(lambda s: s.domain_search_off + s.floats(DOMAIN_SEARCH))
     align_off = property(lambda s: s._begin("align"))                                                       # A0
     # the end of the align block as its writer allocated it ...
     align_end = property(lambda s: s._begin(None))
@@ -232,6 +243,11 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
         floats = self.floats(DOMAIN_SEARCH)
         return buf[self.domain_search_off:self.domain_search_off + floats] if floats else None
 
+    def domain_score_block(self, buf):
+        """The domain-score block of a `d_conf` buffer as a view (1040 + 4L floats), None with `score_domains` off."""
+        floats = self.floats(DOMAIN_SCORES)
+        return buf[self.domain_score_off:self.domain_score_off + floats] if floats else None
+
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
 def conf_floats(L, distmap=False, score=False, align_m=None, score_map=False):
@@ -274,19 +290,23 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
     __hash__ = tuple.__hash__
     domains_block = None
     domain_search_block = None       # with "search_domains": (400 + 2L) K floats; an attribute too, and never handed out by `public`
+    domain_score_block = None        # with "score_domains": 1040 + 4L floats; likewise
 
-    def __new__(cls, *parts, domains_block=None, domain_search_block=None, **named):
+    def __new__(cls, *parts, domains_block=None, domain_search_block=None, domain_score_block=None, **named):
         self = super().__new__(cls, *parts, **named)
         self.domains_block = domains_block
         self.domain_search_block = domain_search_block
+        self.domain_score_block = domain_score_block
         return self
 
     def _replace(self, **changes):
         domains_block = changes.pop("domains_block", self.domains_block)
         domain_search_block = changes.pop("domain_search_block", self.domain_search_block)
+        domain_score_block = changes.pop("domain_score_block", self.domain_score_block)
         new = super()._replace(**changes)
         new.domains_block = domains_block
         new.domain_search_block = domain_search_block
+        new.domain_score_block = domain_score_block
         return new
 
     def __eq__(self, other):        # (a part is an array or a tensor, whose == is elementwise: parts are the same by identity)
@@ -1275,6 +1295,106 @@ def domain_hits_json(ds, names, domains=None, top=10, refine=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# option "score_domains" (include/dmpfold_hip.h): every domain of the model's labels (leg 0) and of the native's (leg 1) scored
+# against the native on its own superposition.  Row (leg, d) is what "score_native" gives for a native masked to the domain, with
+# lnorm 0; the library adds the integer counts of the pairs that leave the domain, and the ratios are formed here.
+# THE TM-SCORE PROGRAM'S KIND OF SEARCH PER DOMAIN, A LOWER BOUND, NOT ITS BITS; the domains are "domains"' contact-density
+# bisection, with no validation on real domains; nobody has compared the figures with an assessor's.
+# ---------------------------------------------------------------------------------------------------------------------
+DOMSCORE_HEADER = 16                 # floats in front of the two tables of the domain-score block
+DOMSCORE_ROW = 32                    # floats of a row
+
+
+def domain_score_floats(L):
+    """Floats of the domain-score block (option "score_domains") of a prediction of length L: 16 + 2 x 16 x 32 + 4L."""
+    return DOMSCORE_HEADER + 2 * DOMAINS_MAX * DOMSCORE_ROW + 4 * int(L)
+
+
+def pack_domain_scores(L, header=None, table=None, res=None):
+    """A domain-score block (float32) from its parts, NaN where a part is None: header (16,), table (2, 16, 32), res (4, L) - the
+    inverse of the raw views of `unpack_domain_scores` (tests, restatements)."""
+    L = int(L)
+    block = np.full(domain_score_floats(L), np.nan, dtype=np.float32)
+    at = DOMSCORE_HEADER + 2 * DOMAINS_MAX * DOMSCORE_ROW
+    if header is not None:
+        block[:DOMSCORE_HEADER] = np.asarray(header, dtype=np.float32).reshape(DOMSCORE_HEADER)
+    if table is not None:
+        block[DOMSCORE_HEADER:at] = np.asarray(table, dtype=np.float32).reshape(at - DOMSCORE_HEADER)
+    if res is not None:
+        block[at:] = np.asarray(res, dtype=np.float32).reshape(4 * L)
+    return block
+
+
+def _preserved_ratio(preserved, pairs):
+    return preserved / (4.0 * pairs) if pairs else float("nan")
+
+
+def unpack_domain_scores(block, L):
+    """A domain-score block (1040 + 4L floats, array or tensor) -> dict: domains (of the model's leg), domains_native, present
+    (rows with a native residue), legs - a list of two (one without the native's leg; none for a block the library answered
+    with NaN) - and the raw views header (16,), table (2, 16, 32), res (4, L).  A leg: rows, per domain a dict with the names
+    of `unpack_scores` (n_pairs, rmsd, tm, gdt_ts, gdt_ha, lddt, counts, R, t) and n, size, preserved, pairs, outer_preserved,
+    outer_pairs; lddt_res (L,) and deviation (L,), each residue inside and under the superposition of its own domain;
+    tm_domains, the size-weighted mean of the domains' tm; lddt_intra and lddt_inter = preserved / (4 pairs) from the integer
+    counts summed over the domains, inside them and leaving them (NaN without a pair)."""
+    L = int(L)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != domain_score_floats(L):
+        raise ValueError(f"a domain-score block of length {L} has {domain_score_floats(L)} floats, got shape {tuple(b.shape)}")
+    at = DOMSCORE_HEADER + 2 * DOMAINS_MAX * DOMSCORE_ROW
+    header, table, res = b[:DOMSCORE_HEADER], b[DOMSCORE_HEADER:at].reshape(2, DOMAINS_MAX, DOMSCORE_ROW), b[at:].reshape(4, L)
+    out = {"domains": _whole(header[0]), "domains_native": _whole(header[1]), "present": _whole(header[2]), "legs": [],
+           "header": header.copy(), "table": table.copy(), "res": res.copy()}
+    for leg, D in enumerate((out["domains"], out["domains_native"])):
+        if not 0 < D <= DOMAINS_MAX:
+            break
+        rows = []
+        for d in range(D):
+            h = table[leg, d]
+            row = {"n": _whole(h[0]), "n_pairs": _whole(h[1])}
+            for k, name in enumerate(SCORE_NAMES[1:]):
+                row[name] = float(h[2 + k])
+            row["counts"] = [int(v) if v == v else 0 for v in h[7:12]]
+            row["R"] = h[12:21].reshape(3, 3).copy()
+            row["t"] = h[21:24].copy()
+            for k, name in enumerate(("preserved", "pairs", "outer_preserved", "outer_pairs", "size")):
+                row[name] = _whole(h[24 + k])
+            rows.append(row)
+        scored = [r for r in rows if r["tm"] == r["tm"]]
+        weight = sum(r["size"] for r in scored)
+        out["legs"].append({
+            "rows": rows, "lddt_res": res[2 * leg].copy(), "deviation": res[2 * leg + 1].copy(),
+            "tm_domains": sum(r["size"] * r["tm"] for r in scored) / weight if weight else float("nan"),
+            "lddt_intra": _preserved_ratio(sum(r["preserved"] for r in rows), sum(r["pairs"] for r in rows)),
+            "lddt_inter": _preserved_ratio(sum(r["outer_preserved"] for r in rows), sum(r["outer_pairs"] for r in rows))})
+    return out
+
+
+def domain_scores_json(ds, domains=None):
+    """`unpack_domain_scores` as a JSON-ready dict (the key "domain_scores" of `dmpfold --native ... --score-domains` and of
+    `dmpfold-batch`): per leg ("model", "native": whose labels) the three summary figures and every domain's row - with
+    `domains`, the dict of `unpack_domains` of the same prediction, its size and segment list joined from there; NaN becomes
+    None."""
+    out = {"domains": int(ds["domains"]), "domains_native": int(ds["domains_native"]), "present": int(ds["present"])}
+    for name, leg in zip(("model", "native"), ds["legs"]):
+        parse = None if domains is None else domains if name == "model" else domains.get("native")
+        rows = []
+        for d, r in enumerate(leg["rows"]):
+            js = {"domain": d, "size": int(r["size"]), "n": int(r["n"])}
+            if parse is not None and d < len(parse["table"]):
+                js["segments"] = [list(seg) for seg in parse["table"][d]["segment_list"]]
+            for key in SCORE_NAMES[1:]:
+                js[key] = _num(r[key])
+            js["counts"] = [int(c) for c in r["counts"]]
+            for key in ("preserved", "pairs", "outer_preserved", "outer_pairs"):
+                js[key] = int(r[key])
+            rows.append(js)
+        out[name] = {"tm_domains": _num(leg["tm_domains"]), "lddt_intra": _num(leg["lddt_intra"]), "lddt_inter": _num(leg["lddt_inter"]),
+                     "rows": rows}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The blocks behind the confidences, each stated once.  A row of BLOCKS: `key` - what the host calls the block (a keyword of
 # Outputs.public and Outputs.of, of a Pipeline's set_<key>); `option` - the library option that turns it on; `field` - its view
 # in an `Outputs`; `name` - what its unpacked form is called wherever it is handed on (a property of predict.Engine, a field of
@@ -1335,3 +1455,9 @@ DOMAIN_SEARCH = Block("search_domains", "search_domains", "domain_search_block",
                       lambda L, K: domain_search_floats(L, K),
                       lambda block, L, library=None, **_: unpack_domain_search(block, L, len(library), library.refine),
                       lambda ds, names=(), domains=None, top=10, refine=0, **_: domain_hits_json(ds, names, domains, top, refine))
+# The domain-score block of option "score_domains": likewise no row of BLOCKS; it lies behind the domain-search block, in front of
+# the align block.
+DOMAIN_SCORES = Block("score_domains", "score_domains", "domain_score_block", "domain_scores", "score_domains", "1040 + 4L",
+                      lambda L, on: domain_score_floats(L),
+                      lambda block, L, **_: unpack_domain_scores(block, L),
+                      lambda ds, domains=None, **_: domain_scores_json(ds, domains))

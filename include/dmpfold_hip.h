@@ -575,7 +575,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains", + 1040 + 4L with "score_domains"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
@@ -748,7 +748,60 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * a search of 3 to 116 ms (1 to 5 %: the copy and the launches that return at once); a model split in 2 (150 + 150) pays 0.8
  * to 2.7 times the whole search again, in 3 (78 + 144 + 78, grids for 4) 1.0 to 3.7 times, in 16 (18 .. 27 residues) 2.1 to
  * 9.2 times - a pair of a small domain costs about half a whole-model pair, because align_refine's dynamic programme pays one
- * barrier per anti-diagonal and an entry of m rows has at least m of them whatever n_d is. */
+ * barrier per anti-diagonal and an entry of m rows has at least m of them whatever n_d is.
+ * "score_domains" (0 or 1, default 0; any other value: DMP_ERR_ARG): score EVERY DOMAIN of the model against the native ON ITS
+ * OWN SUPERPOSITION - on a multi-domain target the whole-chain TM-score of "score_native" mostly measures how the domains sit
+ * relative to each other, and its lDDT hides a wrong arrangement because few inter-domain pairs lie inside 15 Angstrom.  Read
+ * when a prediction begins and held for it; dmp_predict_begin_units answers DMP_ERR_ARG if it is on without "domains" = 1 or
+ * without "score_native" = 1.  With it 0 nothing is launched, read, written or allocated and every offset is what it was.  With it
+ * 1 THE d_conf ARGUMENT MUST HOLD 1040 + 4L MORE FLOATS AT THE END OF THE DOMAIN-SEARCH BLOCK (of the domain block, D0 + 32 + 2L +
+ * 256, with "search_domains" off): there sits the DOMAIN-SCORE BLOCK, all of it outputs, and A0 and B0 move behind it; nothing in
+ * front of it moves.  Offsets relative to its start:
+ *   0                    D of the model's leg
+ *   1                    D of the native's leg, 0 without that leg
+ *   2                    rows present: residues with a native row
+ *   3 .. 15              zero
+ *   16 + 32 (16 e + d) + c   row (e, d), leg e = 0, 1, domain d = 0 .. 15, of 32 floats:
+ *     c = 0 n   1 .. 23 the 23 floats of the score block's header behind lnorm (n_pairs, rmsd, tm, gdt_ts, gdt_ha, lddt, the five
+ *     counts, R, t)   24, 25 preserved and pairs inside the domain   26, 27 outer_preserved, outer_pairs   28 the domain's size
+ *     29 .. 31 zero.  Rows d >= D are NaN; all of leg 1 is NaN without the native's leg.
+ *   [1040, 1040 + L)     leg 0: per-residue lDDT inside the residue's own domain
+ *   [1040 + L, 1040 + 2L)  leg 0: deviation under its own domain's superposition
+ *   [1040 + 2L, 1040 + 4L) the same two arrays of leg 1; NaN without that leg
+ * THE DEFINITION, the only one.  Leg 0 uses the model's labels (label_model of the domain block of the same call), leg 1 the
+ * native's (label_native): it exists only when the domain block has the native's leg, i.e. when every native row is present.
+ * For leg e and domain d let P(e, d) be the residues that carry label d in that leg and have a native row (x not NaN), in
+ * sequence order.  ROW (e, d) IS EXACTLY WHAT "score_native" RETURNS FOR THE SAME MODEL TRACE AND A NATIVE IN WHICH EVERY ROW
+ * OUTSIDE P(e, d) IS NaN, WITH lnorm = 0: n = |P|, TM and GDT normalised by n with d0 from n, the same seeds, the same 20
+ * iterations, the same tie rules, an lDDT that counts only pairs inside the domain - the same device functions compute it, so the
+ * agreement is in the bits - and the two arrays are that call's lddt_res and deviation on the residues of P, NaN where the native
+ * row is absent.  A domain with n < 3 has NaN in floats 2 .. 23 and in the arrays, as that call has; its counts are still given.
+ * Two further integer counts per row, which the masked call cannot give: over the ordered pairs (i, j) with i in P(e, d), j
+ * present but OUTSIDE the domain and native distance below 15 Angstrom, outer_pairs counts them and outer_preserved the
+ * thresholds 0.5, 1, 2 and 4 Angstrom they preserve, with the distance function and the comparisons of the lDDT above.  The
+ * host forms from them the inter-domain lDDT, sum of outer_preserved / (4 x sum of outer_pairs) over the domains of a leg - the
+ * figure that shows a wrong arrangement - and from floats 24, 25 the lDDT inside the domains.  Every count is below 2^24 at
+ * L = 2048 (4 x 2048 x 2047), so the integers are exact as floats.  If D or a label of either leg present is no integer in
+ * range (as "search_domains" validates them), or the prediction latched a device-side fault, every float of the block is NaN.
+ * THE TM-SCORE PROGRAM'S KIND OF SEARCH PER DOMAIN, A LOWER BOUND, NOT ITS BITS; THE DOMAINS ARE THE CONTACT-DENSITY BISECTION OF
+ * "domains", WITH NO VALIDATION ON REAL DOMAINS; NOBODY HAS COMPARED THE FIGURES WITH AN ASSESSOR'S.  There is no one-domain
+ * shortcut: a whole chain is scored once more with lnorm = n.
+ * Launches (csrc/score.hip), in dmp_predict_end behind "domains", reading the native from the score block, the model from
+ * d_coords and the labels from the domain block - nothing that "score_native" left in its scratch: domscore_prep (one workgroup
+ * per leg: validation, the leg's part of the block, the present rows packed in (domain, column) order, per domain its header and
+ * the prefix sums of the <= 16 row counts and seed counts); domscore_lddt (the body of score_lddt, (row group, domain, leg), the
+ * partner loop over every present row with the domain test an index compare; integer atomics only); domscore_search (the body of
+ * score_search on a FLAT grid of Dmax + 5L workgroups per leg, Dmax = max(1, min(16, L / "domains_min_size")): score_seeds(n) <= 1
+ * + 5n and the domains partition the chain, so a leg never has more seeds; a workgroup finds its (domain, seed) in the prefix
+ * sums, each domain has its own ticket and its stretch of the leg's Dmax + 5 max_L records; 6L floats + L flags of LDS);
+ * domscore_counts (floats 24 .. 27).  The same bits on every run; dmp_predict_end stays asynchronous.  Scratch of its own: per leg
+ * 16 + 5 max_L records of 20 doubles, the packed traces and columns (28 max_L bytes) and 2 KiB of headers, counters and offsets -
+ * 0.5 MiB at max_L = 300, 3.2 MiB at 2048 - allocated when the option first becomes 1 on a context and counted in "device_mib";
+ * an allocation failure is an error of dmp_ctx_set_option and leaves the option as it was.
+ * Measured cost of dmp_predict_end with the option on (profiles/score_domains.txt; the collapsed model of profiles/exposure.txt, a
+ * whole folded-like native, both legs): 0.24 ms at L = 96, 0.60 ms at 300, 2.55 ms at 1000, 5.63 ms at 2048 where the model stays
+ * one domain - 1.9 to 2.6 times "score_native" alone in the same run - and 0.20, 0.40, 1.71 and 4.46 ms forced through all four
+ * levels (1.3 to 2.1 times). */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
