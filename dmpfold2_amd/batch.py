@@ -201,9 +201,13 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     <stem>.domain_hits.json (score.domain_hits_json, the best `hits_top` per domain).  With `domain_scores` (the dict of
     score.unpack_domain_scores, --natives --score-domains; only beside `scores`): npz gains dom_score_table (float32 (2, 16, 32):
     the two tables of the domain-score block) and dom_score_res (float32 (4, L): per leg the per-residue lDDT and deviation inside
-    the residue's own domain); <stem>.scores.json gains the key "domain_scores" (score.domain_scores_json)."""
+    the residue's own domain); <stem>.scores.json gains the key "domain_scores" (score.domain_scores_json).  With `flex` (the dict
+    of score.unpack_flex, --flex): npz gains flex_eig (float32 (8,): the model's eight lowest eigenvalues), flex_modes (float32
+    (8, L)), flex_msf (float32 (L,)) and flex_degree (int32 (L,)); pdb / ca get <stem>.flex.json (the line `dmpfold --flex`
+    prints)."""
     domain_hits = results.pop("domain_hits", None)
     domain_scores = results.pop("domain_scores", None)
+    flex = results.pop("flex", None)
     unknown = set(results) - {row.name for row in _score.BLOCKS}
     if unknown:
         raise TypeError(f"write_result: no result is called {sorted(unknown)}")
@@ -271,6 +275,9 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
         if domain_scores is not None and scores is not None:
             extra.update({"dom_score_table": np.asarray(domain_scores["table"], dtype=np.float32),
                           "dom_score_res": np.asarray(domain_scores["res"], dtype=np.float32)})
+        if flex is not None:
+            extra.update({"flex_eig": np.asarray(flex["eigenvalues"], dtype=np.float32), "flex_modes": np.asarray(flex["modes"], dtype=np.float32),
+                          "flex_msf": np.asarray(flex["msf"], dtype=np.float32), "flex_degree": np.asarray(flex["degree"], dtype=np.int32)})
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
@@ -281,7 +288,8 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
         forms["domain_hits"] = domain_hits_form(domain_hits, domains, hits_top)
     if domain_scores is not None and "scores" in forms:
         forms["scores"]["domain_scores"] = _score.domain_scores_json(domain_scores, domains)
-    for name, value in (("exposure", forms.get("exposure")), ("domains", forms.get("domains")), ("restrain", restrain)):
+    for name, value in (("exposure", forms.get("exposure")), ("domains", forms.get("domains")), ("restrain", restrain),
+                        ("flex", None if flex is None else _score.flex_json(flex))):
         if value is not None:
             forms[name] = {name: value}                  # (these lines carry their name)
     for name, form in forms.items():
@@ -353,6 +361,21 @@ def batch_domains(tau=0.25, min_size=40, min_segment=10):
 
 
 _SCORE_DOMAINS = False
+_FLEX = None                                            # --flex: the contact cutoff in Angstrom, or None
+
+
+@contextlib.contextmanager
+def batch_flex(cutoff=7.3):
+    """Every run_batch inside the block also gives every target's model its Gaussian network model on the GPU (Pipeline.use_flex;
+    contacts within `cutoff` Angstrom): the result is written with the target (write_result) and `stats_out` receives "flex":
+    {stem: lambda_1, components, hinges, r_conf of the model's leg}."""
+    global _FLEX
+    _score.flex_cut_mA(cutoff)                          # (a bad value raises before any work)
+    before, _FLEX = _FLEX, float(cutoff)
+    try:
+        yield
+    finally:
+        _FLEX = before
 
 
 @contextlib.contextmanager
@@ -457,6 +480,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         library.check(MAX_L)
         max_L = max(max_L, library.max_m)               # the engines' capacity bounds every entry's length
     domains = _DOMAINS                                  # (batch_domains)
+    flex = _FLEX                                        # (batch_flex)
     search_domains = library is not None and bool(getattr(library, "domains", False))      # (--search-domains)
     if (search_domains or score_domains) and domains is None:
         domains = domains_options()                     # the library's flag, or --score-domains, turns "domains" on, with the defaults
@@ -484,6 +508,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                     getattr(pipe, "set_" + setter)(*value)
             if score_domains:
                 pipe.use_score_domains(True)                # (behind set_score, which it needs)
+            if flex is not None:
+                pipe.use_flex(True, flex)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -504,6 +530,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             outs = outs + (pipe.outputs_of(t).domain_search_block,)      # which `peek` never hands out: last of all
         if score_domains:
             outs = outs + (pipe.outputs_of(t).domain_score_block,)       # likewise, behind that
+        if flex is not None:
+            outs = outs + (pipe.outputs_of(t).flex_block,)               # likewise, behind that
         if outs[0].is_cuda:
             host = tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in outs)
             with (torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext()):
@@ -521,14 +549,17 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
 
     scored, aligned = set(), set()                      # the tickets that had a native / a structure
     asked = {"natives": bool(natives), "structures": bool(structures), "library": library is not None, "ss": ss,
-             "exposure": exposure, "restrain": restraining, "domains": domains is not None, "search_domains": search_domains}
+             "exposure": exposure, "restrain": restraining, "domains": domains is not None, "search_domains": search_domains,
+             "flex": flex is not None}
     blocks_on = {"score": asked["natives"], "align": asked["structures"], "search": asked["library"], "score_map": score_map,
                  "passes": score_passes, "ss": ss, "exposure": exposure, "domains": domains is not None}
     gathered = {}                                       # {key of `stats_out`: {stem: what the summary takes}}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        ds_block, score_block = None, None
+        ds_block, score_block, flex_block = None, None, None
+        if flex is not None:
+            public, flex_block = public[:-1], public[-1]
         if score_domains:
             public, score_block = public[:-1], public[-1]
         if search_domains:
@@ -550,6 +581,9 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         if score_block is not None and t in scored and "scores" in forms:
             results["domain_scores"] = _score.unpack_domain_scores(score_block, alnmat.shape[1])
             forms["scores"]["domain_scores"] = _score.domain_scores_json(results["domain_scores"], results.get("domains"))
+        if flex_block is not None:
+            results["flex"] = _score.unpack_flex(flex_block, alnmat.shape[1], confs=out.confs, domains=results.get("domains"))
+            forms["flex"] = _score.flex_json(results["flex"])
         rep = None
         if restraining:
             rep = forms["restrain"] = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap,
@@ -664,7 +698,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 failed.append((parsed.pop(t)[0], res[t]))
             else:
                 write(t, res[t] + ((pipe.collected[t].domain_search_block,) if search_domains else ())
-                      + ((pipe.collected[t].domain_score_block,) if score_domains else ()))
+                      + ((pipe.collected[t].domain_score_block,) if score_domains else ())
+                      + ((pipe.collected[t].flex_block,) if flex is not None else ()))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:
@@ -745,6 +780,12 @@ def batch_parser():
     ap.add_argument("--domains-tau", type=float, default=argparse.SUPPRESS, metavar="Q", help=argparse.SUPPRESS)
     ap.add_argument("--domains-min-size", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
     ap.add_argument("--domains-min-segment", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
+    # --flex [--flex-cutoff A]: the Gaussian network model of every target's C-alpha trace on the GPU (contacts within A Angstrom,
+    # 7.3 by default); the summary carries per target lambda_1, components, the hinge count and the correlation of msf with
+    # 1 - confidence, with means and medians; npz gains flex_eig, flex_modes, flex_msf and flex_degree, pdb / ca write
+    # <stem>.flex.json.  Hidden like --search-refine, for the same reason.
+    ap.add_argument("--flex", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    ap.add_argument("--flex-cutoff", type=float, default=argparse.SUPPRESS, metavar="A", help=argparse.SUPPRESS)
     ap.add_argument("--ss", action="store_true",
                     help="assign secondary structure to every target's backbone on the GPU from its hydrogen bonds; the summary "
                          "gains every target's eight-state string and helix / strand / coil fractions with their means and "
@@ -841,6 +882,25 @@ def domains_summary(domains):
             "multi_domain_share": float(np.mean([c > 1 for c in counts])) if counts else None}
 
 
+def flex_brief(form):
+    """The summary's figures of one target from its "flex" (score.flex_json): the first non-zero eigenvalue, the components, the
+    hinge count and the correlation of msf with 1 - confidence, of the model's leg."""
+    k = form["first_mode"]
+    return {"lambda_1": None if k is None else form["eigenvalues"][k], "components": form["components"], "hinges": len(form["hinges"]),
+            "r_conf": form.get("r_conf")}
+
+
+def flex_summary(flex):
+    """{stem: flex_brief} -> the summary's part for --flex: every target's figures, and mean and median of each over the targets
+    that have it."""
+    out = {"flex_targets": len(flex), "flex": flex}
+    for name in ("lambda_1", "components", "hinges", "r_conf"):
+        vals = [v[name] for v in flex.values() if v.get(name) is not None]
+        out["mean_flex_" + name] = float(np.mean(vals)) if vals else None
+        out["median_flex_" + name] = float(np.median(vals)) if vals else None
+    return out
+
+
 def restrain_summary(reports):
     """{stem: the dict of predict.restrain_report} -> the summary's part for --restrain: every target's report, and mean and
     median of map_rms, restrained_pairs, clashes and bond_dev_max."""
@@ -896,9 +956,10 @@ GATHERED = (("scores", "natives", score_summary),
             ("alignments", "structures", lambda found: {"aligned_targets": len(found), "alignments": found}),
             ("hits", "library", lambda found: {"searched_targets": len(found), "hits": found}),
             ("ss", "ss", ss_summary), ("exposure", "exposure", exposure_summary), ("restrain", "restrain", restrain_summary),
-            ("domains", "domains", domains_summary),
+            ("domains", "domains", domains_summary), ("flex", "flex", flex_summary),
             ("domain_hits", "search_domains", lambda found: {"domain_searched_targets": len(found), "domain_hits": found}))
-GATHERED_AS = {"alignment": ("alignments", lambda form: {k: form[k] for k in ("m",) + _score.ALIGN_NAMES}),
+GATHERED_AS = {"flex": ("flex", flex_brief),
+               "alignment": ("alignments", lambda form: {k: form[k] for k in ("m",) + _score.ALIGN_NAMES}),
                "hits": ("hits", lambda form: [{k: v for k, v in hit.items() if k not in ("R", "t")} for hit in form["hits"]]),
                # every domain's best hit
                "domain_hits": ("domain_hits", lambda form: [dict({k: d[k] for k in ("domain", "size") if k in d},
@@ -944,6 +1005,10 @@ def main(argv=None):
         ap.error("--domains-tau, --domains-min-size and --domains-min-segment need --domains")
     try:
         domains_options(**dom_given)                     # (a bad value is an error of the command line)
+        if hasattr(args, "flex_cutoff"):
+            if not hasattr(args, "flex"):
+                ap.error("--flex-cutoff needs --flex")
+            _score.flex_cut_mA(args.flex_cutoff)
     except ValueError as exc:
         ap.error(str(exc))
 
@@ -966,7 +1031,8 @@ def main(argv=None):
     passes = {}
     try:
         with (batch_domains(**dom_given) if hasattr(args, "domains") else contextlib.nullcontext()), \
-                (batch_score_domains() if hasattr(args, "score_domains") else contextlib.nullcontext()):
+                (batch_score_domains() if hasattr(args, "score_domains") else contextlib.nullcontext()), \
+                (batch_flex(getattr(args, "flex_cutoff", 7.3)) if hasattr(args, "flex") else contextlib.nullcontext()):
             n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                       weights_file=args.model_weights, streams=args.streams,
                                       device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,

@@ -492,6 +492,10 @@ static int exposure_reserve(dmp_ctx* c) {
 static int domains_reserve(dmp_ctx* c) {
   return c->opt.domains ? with_entity_reserve(c, c->domains_ws, domains_need(c->max_L), "domain scratch") : DMP_OK;
 }
+// Option "flex": likewise (flex.hip has the layout); its native leg asks the native entity whether the trace is whole.
+static int flex_reserve(dmp_ctx* c) {
+  return c->opt.flex ? with_entity_reserve(c, c->flex_ws, flex_need(c->max_L), "flex scratch") : DMP_OK;
+}
 
 // ---- the options --------------------------------------------------------------------------------------------------------
 // One table; dmp_ctx_set_option and dmp_ctx_get_option walk it.  A NEW OPTION IS ONE ROW: its name, where the value lives (a
@@ -603,6 +607,8 @@ static const Option OPTIONS[] = {
     {"search_domains", TAIL(search_domains), 0, 2, 0, "search_domains must be 0, 1 or 2 (tests only: 1 without the one-domain shortcut), got %d", OPT_RW,
      nullptr, nullptr, search_domains_reserve},                                                                  // needs "domains" = 1 and "search_structures" > 0
     {"score_domains", TAIL(score_domains), 0, 1, 0, "score_domains must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, score_domains_reserve},   // needs "domains" = 1 and "score_native" = 1
+    {"flex", TAIL(flex), 0, 1, 0, "flex must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, flex_reserve},
+    {"flex_cut_mA", TAIL(flex_cut), 4000, 20000, 0, "flex_cut_mA must be 4000 .. 20000, got %d"},                 // the contact cutoff of "flex", milli-Angstrom
     {"passes_run", CTX(passes_done), ANY, OPT_READ_ONLY},                                   // trunk passes of the last prediction
     {"search_chunk_used", CTX(search_last_C), ANY, OPT_READ_ONLY},                          // of the last prediction that searched: entries per chunk
     {"search_wg_per_cu", nullptr, nullptr, ANY, OPT_READ_ONLY, nullptr, nullptr, nullptr, get_search_wg_per_cu},
@@ -799,7 +805,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
   for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->entity_ws, &c->ss_ws, &c->exposure_ws,
-                     &c->domains_ws, &c->domsearch_ws, &c->domscore_ws})
+                     &c->domains_ws, &c->domsearch_ws, &c->domscore_ws, &c->flex_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1570,7 +1576,7 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // its rebuilt backbone (entity.hip)
   const float* d_native = c->run.score ? d_conf + lay.score.off : nullptr;
   const bool backbone = c->run.ss || c->run.exposure;
-  if (d_native && (backbone || c->run.domains) && (rc = entity_prepare(c, d_native, L, backbone, s))) return rc;
+  if (d_native && (backbone || c->run.domains || c->run.flex) && (rc = entity_prepare(c, d_native, L, backbone, s))) return rc;
   // option "assign_ss": the SS block behind that, from d_coords and - with "score_native" - the native entity (ss.hip)
   if (c->run.ss && (rc = assign_ss(c, d_coords, L, d_native, d_conf + lay.ss.off, s))) return rc;
   // option "exposure": the exposure block behind that, from the same two inputs (exposure.hip)
@@ -1582,6 +1588,9 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   if (c->run.score_domains &&
       (rc = score_domains(c, d_coords, L, d_conf + lay.score.off, d_conf + lay.domains.off, d_conf + lay.domscore.off, s)))
     return rc;
+  // option "flex": the flex block behind that, from d_coords and - with "score_native" - the native entity (flex.hip).  The
+  // solver's scratch and graphs are free: the last pass is behind us on this stream
+  if (c->run.flex && (rc = flex(c, d_coords, L, d_native, d_conf + lay.flex.off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

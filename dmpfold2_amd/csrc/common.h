@@ -11,9 +11,9 @@
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
 // "search_refine", "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk",
-// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment", "search_domains", "score_domains"
+// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment", "search_domains", "score_domains", "flex", "flex_cut_mA"
 struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, search_refine = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0,
-                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10, search_domains = 0, score_domains = 0; };
+                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10, search_domains = 0, score_domains = 0, flex = 0, flex_cut = 7300; };
 
 namespace dmp {
 
@@ -112,11 +112,19 @@ __host__ __device__ inline DomScoreLayout domscore_layout(int L) {
   const int res = DOMSCORE_HEADER + 2 * DOMAINS_MAX * DOMSCORE_ROW;
   return {DOMSCORE_HEADER, res, res + 4 * L};
 }
+//   | with "flex": the flex block = FLEX_HEADER floats | per leg (the model's, the native's) FLEX_LEG floats | per leg degree [L],
+//   msf [L], modes [FLEX_MODES][L], all of it out, between the domain-score block and the align block.
+constexpr int FLEX_HEADER = 16, FLEX_LEG = 16, FLEX_MODES = 8;
+struct FlexLayout { int leg, res, per_leg, total; };                    // relative to the block's start; leg e's arrays at res + per_leg e
+__host__ __device__ inline FlexLayout flex_layout(int L) {
+  const int res = FLEX_HEADER + 2 * FLEX_LEG, per = (2 + FLEX_MODES) * L;
+  return {FLEX_HEADER, res, per, res + 2 * per};
+}
 // The blocks in buffer order.  A block states where it begins, how many floats in front are the caller's input and where what
 // the library writes ends; a block whose option is off is empty (off = end).  `passes`: the rows R of the pass block, 0 =
 // none.  The align block's trailing input, whose length only the caller knows, lies behind `total`.
 struct ConfBlock { int64_t off, in, end; };                              // [off, off + in) in, [off + in, end) out
-struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, domsearch, domscore, align; int64_t total; };
+struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, domsearch, domscore, flex, align; int64_t total; };
 __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int passes) {
   ConfLayout lay;
   int64_t at = 0;
@@ -136,6 +144,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
   lay.domains = block(0, o.domains ? domains_floats(L) : 0);
   lay.domsearch = block(0, o.search_domains ? domsearch_layout(L, o.search).total : 0);
   lay.domscore = block(0, o.score_domains ? domscore_layout(L).total : 0);
+  lay.flex = block(0, o.flex ? flex_layout(L).total : 0);
   lay.align = block(1, o.align ? align_layout(L).in : 0);
   lay.total = at;
   return lay;
@@ -143,7 +152,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
 // true for the floats a prediction writes: what becomes NaN when it latched a fault (api.hip)
 __host__ __device__ inline bool conf_is_out(const ConfLayout& lay, int64_t i) {
   auto out = [i](const ConfBlock& b) { return i >= b.off + b.in && i < b.end; };
-  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.domsearch) || out(lay.domscore) || out(lay.align);
+  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.domsearch) || out(lay.domscore) || out(lay.flex) || out(lay.align);
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -416,6 +425,7 @@ struct dmp_ctx {
                                    // the summed-area tables of one level (domains.hip: domains_scratch)
   dmp::Scratch domscore_ws;        // "score_domains": the tickets | per leg the domains' first rows and seeds, headers and counters, the packed
                                    // traces, the seed records (score.hip: domscore_scratch)
+  dmp::Scratch flex_ws;              // "flex": nothing zeroed | the float32 matrix sigma I - Gamma of one leg, the degrees, the counts (flex.hip: flex_scratch)
   dmp::Scratch domsearch_ws;       // "search_domains": nothing zeroed | the per-domain tables of "search_refine", the counts, the residue list (align.hip:
                                    // DomainQuery); the slots are search_ws's
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
@@ -656,6 +666,11 @@ __device__ __forceinline__ bool grid_sum_f64(double v, double* red, double* part
 int mds_kernel_attrs(dmp_ctx* c);     // once per device, at context creation
 int gj_kernel_attrs(dmp_ctx* c);      // ditto (dca.hip)
 int eigh_top8(dmp_ctx* c, const float* d_M, int L, float* d_mds, hipStream_t s);
+// the same factorisation with the other epilogue of the back-transformation (option "flex"): the eight unit eigenvectors under the
+// sign rule, column c of the solver's ascending order as row 7 - c of d_modes [8][L] (float32, one rounding each) and as column
+// c of the float64 *d_zq [L][8]; the eight eigenvalues, ascending, at *d_mu.  Both pointers lie in eig_ws and hold until the
+// solver runs again.
+int eigh_top8_modes(dmp_ctx* c, const float* d_M, int L, float* d_modes, const double** d_mu, const double** d_zq, hipStream_t s);
 // coords.hip
 int coord_fc(dmp_ctx* c, const float* d_g, int L, float* d_ca, hipStream_t s);
 int build_embed(const float* d_mat1d, const float* d_mds, int L, float* d_emb, hipStream_t s);
@@ -672,7 +687,7 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 // what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
 ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
-    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L), search_domains_need(int max_L), score_domains_need(int max_L);
+    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L), search_domains_need(int max_L), score_domains_need(int max_L), flex_need(int max_L);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
@@ -710,6 +725,8 @@ int exposure(dmp_ctx* c, const float* d_coords, int L, const float* d_native, fl
 int64_t exposure_points_fetch(float* d_dst, int64_t capacity, hipStream_t s);   // the sphere points as the device holds them -> floats written
 const float* exposure_native_backbone(const dmp_ctx* c);             // the native's rebuilt backbone (dmp_debug_fetch)
 int domains(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
+// option "flex" (flex.hip): the Gaussian network model of both traces, into the flex block
+int flex(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
 int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);
 // restrain: the final refinement with option "restrain_milli" on - the steps also pull towards c->best_dm (coords.hip)

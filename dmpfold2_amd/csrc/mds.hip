@@ -771,12 +771,16 @@ __global__ __launch_bounds__(512) void tri_eig_kernel(const double* __restrict__
 // reflector is a dot product and an axpy inside the wave - shuffles, no workgroup barrier (the
 // previous version spent its 1.0 ms at L = 300 in 600 barriers).  The reflector rows are fetched G
 // steps ahead.  block: 512 (8 waves = 8 columns); T = ceil(n / 64) rows per lane.
-template <int T, int G>
+// EPI, the epilogue: EPI_MDS - mds[i][c] = (float)(sgn z_i) * sqrt(max(lambda_c, 1e-8)), `zq` unused; EPI_MODES (option "flex") -
+// the unit vector itself, out[(7 - c) n + i] = (float)(sgn z_i) (row k of [8][n] in descending order of the eigenvalue), and
+// its float64 source zq[i][c] = sgn z_i for the caller's sums; lam is the caller's to read.
+enum { EPI_MDS = 0, EPI_MODES = 1 };
+template <int T, int G, int EPI>
 __global__ __launch_bounds__(512) void backtransform_kernel(const double* __restrict__ V,
                                                             const double* __restrict__ tau,
                                                             const double* __restrict__ lam,
                                                             const double* __restrict__ Z, int n,
-                                                            float* __restrict__ mds) {
+                                                            float* __restrict__ mds, double* __restrict__ zq) {
   const int lane = threadIdx.x & 63;
   const int c = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double z[T];
@@ -830,6 +834,18 @@ __global__ __launch_bounds__(512) void backtransform_kernel(const double* __rest
     if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; bz = oz; }
   }
   const double sgn = bz < 0.0 ? -1.0 : 1.0;
+  if (EPI == EPI_MODES) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int i = lane + 64 * t;
+      if (i < n) {
+        const double v = sgn * z[t];
+        mds[(int64_t)(NEV - 1 - c) * n + i] = (float)v;
+        zq[(int64_t)i * NEV + c] = v;
+      }
+    }
+    return;
+  }
   const float lf = (float)lam[c];
   const float scale = sqrtf(fmaxf(fmaxf(lf, 0.0f), 1e-8f));
 #pragma unroll
@@ -903,21 +919,32 @@ int mds_kernel_attrs(dmp_ctx* c) {
   return DMP_OK;
 }
 
-int eigh_top8(dmp_ctx* c, const float* d_M, int L, float* d_mds, hipStream_t s) {
-  const int n = L;
-  double* A = c->eig_a;
+// The scratch of one solve in eig_ws, for matrices of order n.
+struct EighWs { double *d, *e, *tau, *lam, *Z, *F, *V, *P; TriRun* run; };
+static EighWs eigh_ws(dmp_ctx* c, int n) {
+  EighWs w;
   double* ws = c->eig_ws;
-  double* d = ws;
-  double* e = ws + n;
-  double* tau = ws + 2 * n;
-  double* lam = ws + 3 * n;                 // 8
-  double* Z = ws + 3 * n + 16;              // n*8
-  double* F = Z + (int64_t)n * NEV;         // 5*n*8
-  double* V = F + (int64_t)5 * n * NEV;     // n*n
+  w.d = ws;
+  w.e = ws + n;
+  w.tau = ws + 2 * n;
+  w.lam = ws + 3 * n;                       // 8
+  w.Z = ws + 3 * n + 16;                    // n*8
+  w.F = w.Z + (int64_t)n * NEV;             // 5*n*8
+  w.V = w.F + (int64_t)5 * n * NEV;         // n*n
+  w.P = w.V + (int64_t)n * n;               // 2*n
+  w.run = reinterpret_cast<TriRun*>(w.P + 2 * n);
+  return w;
+}
+
+// The factorisation: d_M -> the reflectors (V, tau) and, of the tridiagonal matrix, the eight largest eigenvalues (lam, ascending)
+// with their unit eigenvectors (Z).
+static int eigh_factor(dmp_ctx* c, const float* d_M, int n, const EighWs& w, hipStream_t s) {
+  double* A = c->eig_a;
+  double *d = w.d, *e = w.e, *tau = w.tau, *lam = w.lam, *Z = w.Z, *F = w.F, *V = w.V, *P = w.P;
+  TriRun* run = w.run;
+  if (n > DMP_MAX_L) { set_error("eigh_top8: order %d exceeds %d", n, DMP_MAX_L); return DMP_ERR_CAPACITY; }
   hipLaunchKernelGGL(eig_load_kernel, dim3(cdiv(n, 256), n), dim3(256), 0, s, d_M, n, A);
   DMP_LAUNCH_CHECK();
-  double* P = V + (int64_t)n * n;           // 2*n
-  TriRun* run = reinterpret_cast<TriRun*>(P + 2 * n);
   if (c->tridiag_single) {
     hipLaunchKernelGGL(tridiag_kernel, dim3(1), dim3(1024), sizeof(double) * (2 * n + 1024), s, A, n, d,
                        e, tau, V);
@@ -944,17 +971,37 @@ int eigh_top8(dmp_ctx* c, const float* d_M, int L, float* d_mds, hipStream_t s) 
     default: hipLaunchKernelGGL(tri_eig_kernel<2>, dim3(1), dim3(512), tri_eig_lds_bytes(n), s, d, e, n, F, lam, Z);
   }
   DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// The back-transformation with epilogue EPI into d_out; zq: see backtransform_kernel.
+template <int EPI>
+static int eigh_back(int n, const EighWs& w, float* d_out, double* zq, hipStream_t s) {
   if (n <= 320)
-    hipLaunchKernelGGL((backtransform_kernel<5, 4>), dim3(1), dim3(512), 0, s, V, tau, lam, Z, n, d_mds);
+    hipLaunchKernelGGL((backtransform_kernel<5, 4, EPI>), dim3(1), dim3(512), 0, s, w.V, w.tau, w.lam, w.Z, n, d_out, zq);
   else if (n <= 640)
-    hipLaunchKernelGGL((backtransform_kernel<10, 2>), dim3(1), dim3(512), 0, s, V, tau, lam, Z, n, d_mds);
+    hipLaunchKernelGGL((backtransform_kernel<10, 2, EPI>), dim3(1), dim3(512), 0, s, w.V, w.tau, w.lam, w.Z, n, d_out, zq);
   else if (n <= 1280)
-    hipLaunchKernelGGL((backtransform_kernel<20, 1>), dim3(1), dim3(512), 0, s, V, tau, lam, Z, n, d_mds);
-  else if (n <= 2048)
-    hipLaunchKernelGGL((backtransform_kernel<32, 1>), dim3(1), dim3(512), 0, s, V, tau, lam, Z, n, d_mds);
-  else { set_error("eigh_top8: order %d exceeds %d", n, DMP_MAX_L); return DMP_ERR_CAPACITY; }
+    hipLaunchKernelGGL((backtransform_kernel<20, 1, EPI>), dim3(1), dim3(512), 0, s, w.V, w.tau, w.lam, w.Z, n, d_out, zq);
+  else
+    hipLaunchKernelGGL((backtransform_kernel<32, 1, EPI>), dim3(1), dim3(512), 0, s, w.V, w.tau, w.lam, w.Z, n, d_out, zq);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
+}
+
+int eigh_top8(dmp_ctx* c, const float* d_M, int L, float* d_mds, hipStream_t s) {
+  const EighWs w = eigh_ws(c, L);
+  if (int rc = eigh_factor(c, d_M, L, w, s)) return rc;
+  return eigh_back<EPI_MDS>(L, w, d_mds, nullptr, s);
+}
+
+// F, the factor scratch of tri_eig_kernel, is free once that kernel has finished: the float64 vectors go there.
+int eigh_top8_modes(dmp_ctx* c, const float* d_M, int L, float* d_modes, const double** d_mu, const double** d_zq, hipStream_t s) {
+  const EighWs w = eigh_ws(c, L);
+  if (int rc = eigh_factor(c, d_M, L, w, s)) return rc;
+  *d_mu = w.lam;
+  *d_zq = w.F;
+  return eigh_back<EPI_MODES>(L, w, d_modes, w.F, s);
 }
 
 }  // namespace dmp

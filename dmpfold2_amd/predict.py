@@ -429,7 +429,7 @@ def agree_options(rows):
     return Flags(all(emits), any(emits), *rows[0][1:])
 
 
-def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False, score_domains=False):
+def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False, score_domains=False, flex=False):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is laid out (score.Layout) for the options as the context holds them (`flags`) -
     the library cannot check it - and its input blocks are filled from `extras`: with "score_native" on the native trace (no
@@ -437,7 +437,7 @@ def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=
     which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU.
     `domains`: option "domains" on (it travels beside `flags`, whose fields callers know by position); `search_domains`: option
     "search_domains" on - the buffer then holds the domain-search block in front of the align block; `score_domains`: option
-    "score_domains" on - the domain-score block behind that."""
+    "score_domains" on - the domain-score block behind that; `flex`: option "flex" on - the flex block behind that."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -451,7 +451,7 @@ def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None, score_domains=score_domains,
+                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None, score_domains=score_domains, flex=flex,
                  **{key: getattr(flags, key) for key in OWN_BLOCK})
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
@@ -642,6 +642,53 @@ class Engine:
         torch.cuda.synchronize(self.device)
         return _score.unpack_domain_scores(block, self._last.L)
 
+    @property
+    def flex_block(self):
+        """"flex": 48 + 20L floats - the Gaussian network model of the last prediction's trace and of the native's - or None."""
+        return self._last.out.flex_block
+
+    @property
+    def flex(self):
+        """The flexibility of the last prediction as score.unpack_flex gives it, with the prediction's confidences and - where
+        option "domains" was on - its parse; None if it ran without option "flex".  Synchronises with the GPU."""
+        block = self.flex_block
+        if block is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        dom = self._last.out.domains_block
+        parse = None if dom is None else _score.unpack_domains(dom, self._last.L)
+        return _score.unpack_flex(block, self._last.L, confs=self._last.out.confs[:self._last.L], domains=parse)
+
+    def set_flex(self, on, cutoff=7.3):
+        """Option "flex" on this engine, as it stands from now on: every prediction's final C-alpha trace (and, with a whole
+        `native`, the native's) gets its Gaussian network model on the GPU - contacts within `cutoff` Angstrom (4 .. 20), the
+        eight lowest eigenpairs of the Kirchhoff matrix, the slow-mode fluctuation; what a call returns does not change, the
+        result is in `flex` (score.unpack_flex) and `flex_block`."""
+        mA = _score.flex_cut_mA(cutoff) if on else None       # (raises before anything changes)
+        if on:
+            self.set_option("flex_cut_mA", mA)
+        self.set_option("flex", 1 if on else 0)
+
+    @contextlib.contextmanager
+    def with_flex(self, cutoff=7.3):
+        """Option "flex" and its cutoff set for the duration of the block, then as they were (`set_flex`)."""
+        values = {"flex_cut_mA": _score.flex_cut_mA(cutoff), "flex": 1}
+        before = {}
+        try:
+            for name, value in values.items():
+                before[name] = self.get_option(name)
+                self.set_option(name, value)
+            yield self
+        finally:
+            for name, value in reversed(list(before.items())):
+                self.set_option(name, value)
+
+    def predict_flex(self, alnmat, *args, flex_cutoff=7.3, **asked):
+        """`predict` with option "flex" set for this call only: the same arguments, the same return value; the result is in
+        `flex` and `flex_block` afterwards."""
+        with self.with_flex(flex_cutoff):
+            return self.predict(alnmat, *args, **asked)
+
     _score_domains = False           # set_score_domains / with_score_domains: the calls of this engine score every domain
 
     def set_score_domains(self, on):
@@ -785,7 +832,7 @@ class Engine:
             self._forget_last()
             domains = bool(self.get_option("domains"))
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, bool(self.get_option("search_domains")),
-                                bool(self.get_option("score_domains")))
+                                bool(self.get_option("score_domains")), bool(self.get_option("flex")))
             self._last = _Last(out._replace(coords=None), L, library if search else None, out.coords if domains else None)
             milli = self.get_option("restrain_milli")
             if milli > 0:
@@ -1080,6 +1127,16 @@ class Pipeline:
             self.set_option("domains", 1)
         self.set_option("score_domains", 1 if on else 0)
 
+    def use_flex(self, on, cutoff=7.3):
+        """Option "flex" on every engine: targets submitted from now on get the Gaussian network model of their final C-alpha
+        trace (and, with `set_score` on and a whole native given to `submit`, of the native's) with contacts within `cutoff`
+        Angstrom; the flex block (48 + 20L floats, score.unpack_flex) is the attribute `flex_block` of what `outputs_of` gives.
+        Idle pipeline only."""
+        mA = _score.flex_cut_mA(cutoff) if on else None       # (raises before anything changes)
+        if on:
+            self.set_option("flex_cut_mA", mA)
+        self.set_option("flex", 1 if on else 0)
+
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
@@ -1160,7 +1217,10 @@ class Pipeline:
                                    "(whichever of them runs a target must give the same parse); use use_domains")
             search_domains = agree([e.get_option("search_domains") for e in self.engines], "search_domains", "set_search")
             score_domains = agree([e.get_option("score_domains") for e in self.engines], "score_domains", "use_score_domains")
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains, score_domains)
+            flex = agree([e.get_option("flex") for e in self.engines], "flex", "use_flex")
+            if flex and len({e.get_option("flex_cut_mA") for e in self.engines}) > 1:
+                raise RuntimeError("the engines must agree on \"flex_cut_mA\" (whichever of them runs a target must give the same network); use use_flex")
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains, score_domains, flex)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -1473,15 +1533,28 @@ def aln_to_domains(input_file, *args, domains_tau=0.25, domains_min_size=40, dom
     return _coords_tuple(call.arguments, domains_options(domains_tau, domains_min_size, domains_min_segment))
 
 
-def _coords_tuple(call, domains=None):
-    """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave) -> what it returns."""
+def aln_to_flex(input_file, *args, flex_cutoff=7.3, **asked):
+    """`aln_to_coords` with the Gaussian network model of the model's C-alpha trace on the GPU (option "flex"; with a whole
+    `native` also of the native's): the same arguments, and the dict of score.unpack_flex - made with the model's confidences,
+    so it has the correlations of msf with 1 - confidence - appended last of all.  `flex_cutoff`: the contact cutoff, 4 .. 20
+    Angstrom."""
+    call = inspect.signature(aln_to_coords).bind(input_file, *args, **asked)
+    call.apply_defaults()
+    _score.flex_cut_mA(flex_cutoff)                                          # (a bad value raises before any work)
+    return _coords_tuple(call.arguments, flex=flex_cutoff)
+
+
+def _coords_tuple(call, domains=None, flex=None):
+    """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave; for `aln_to_flex`, its cutoff) ->
+    what it returns."""
     v = SimpleNamespace(**call)
-    r, parse, _, _ = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
+    r, parse, _, _, flexed = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
                                   v.native, v.native_chain, v.compare, v.compare_chain, v.search, distmap=v.return_distmap,
                                   scores=v.return_scores, alignment=v.return_alignment, hits=v.return_hits,
                                   map_scores=v.return_map_scores, pass_scores=v.return_pass_scores, ss=v.return_ss,
-                                  restrain=v.restrain, restrain_cutoff=v.restrain_cutoff, exposure=v.return_exposure)
-    return _as_tuple(r, **{k: call[k] for k in call if k.startswith("return_")}) + ((parse,) if domains is not None else ())
+                                  restrain=v.restrain, restrain_cutoff=v.restrain_cutoff, exposure=v.return_exposure, flex=flex)
+    return (_as_tuple(r, **{k: call[k] for k in call if k.startswith("return_")}) + ((parse,) if domains is not None else ())
+            + ((flexed,) if flex is not None else ()))
 
 
 def _as_tuple(r, return_alnmat=False, return_distmap=False, return_scores=False, return_alignment=False, return_hits=False,
@@ -1513,9 +1586,10 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
 
 def _predict_file_with(domains, input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain,
                        compare, compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
-                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False, score_domains=False):
+                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False, score_domains=False, flex=None):
     """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None, the domain search or None, the domain scores or
-    None).  `score_domains` (needs `native`): every domain is scored against the native (Engine.with_score_domains); the fourth
+    None, the dict of score.unpack_flex or None).  `flex`: None, or the contact cutoff in Angstrom - the prediction then runs
+    with option "flex" (Engine.with_flex).  `score_domains` (needs `native`): every domain is scored against the native (Engine.with_score_domains); the fourth
     part is then (the dict of Engine.domain_scores, the dict of score.unpack_domains of the same prediction, the raw block as an
     array).  `domains`: None, or
     what domains_options gave - the prediction then runs with option "domains" (Engine.with_domains).  A `search` library with
@@ -1553,7 +1627,8 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
         cap = max(length, 0 if compare is None else compare.shape[0], 0 if search is None else search.max_m)
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         with (eng.with_domains(domains[0] * 1e-3, *domains[1:]) if domains is not None else contextlib.nullcontext()), \
-                (eng.with_score_domains() if score_domains else contextlib.nullcontext()):
+                (eng.with_score_domains() if score_domains else contextlib.nullcontext()), \
+                (eng.with_flex(flex) if flex is not None else contextlib.nullcontext()):
             out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
                                       native=native, structure=compare, library=search, score_map=bool(map_scores),
                                       score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain,
@@ -1572,7 +1647,8 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
                           pass_scores=eng.pass_scores if pass_scores else None,
                           hits=eng.hits if search is not None and hits else None,
                           scores=eng.scores if native is not None and scores else None,
-                          alignment=eng.alignment if compare is not None and alignment else None), parse, domain_hits, domain_scores
+                          alignment=eng.alignment if compare is not None and alignment else None), parse, domain_hits, domain_scores, \
+            (eng.flex if flex is not None else None)
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1686,6 +1762,14 @@ def dmpfold_parser():
     parser.add_argument("--domains-min-size", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
     parser.add_argument("--domains-min-segment", type=int, default=argparse.SUPPRESS, metavar="N", help=argparse.SUPPRESS)
     parser.add_argument("--domains-file", type=str, default=argparse.SUPPRESS, metavar="FILE", help=argparse.SUPPRESS)
+    # --flex [--flex-cutoff A] [--flex-file FILE]: the Gaussian network model of the model's C-alpha trace on the GPU (contacts
+    # within A Angstrom, 7.3 by default; the eight lowest modes, the hinges of the slowest, the slow-mode fluctuation and its
+    # correlation with 1 - confidence; with --native given whole also the native's); the result goes to standard error, or to
+    # FILE, as one JSON line under the key "flex", the model on standard output is unchanged.  Hidden like --search-refine, for
+    # the same reason; README.md describes it.
+    parser.add_argument("--flex", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    parser.add_argument("--flex-cutoff", type=float, default=argparse.SUPPRESS, metavar="A", help=argparse.SUPPRESS)
+    parser.add_argument("--flex-file", type=str, default=argparse.SUPPRESS, metavar="FILE", help=argparse.SUPPRESS)
     add_restrain_arguments(parser, "-r")
     return parser
 
@@ -1702,6 +1786,21 @@ def domains_arguments(parser, args):
         return domains_options(**given)
     except ValueError as exc:
         parser.error(str(exc))
+
+
+def flex_arguments(parser, args):
+    """What --flex and its companions ask for: None without --flex, else the cutoff in Angstrom (a bad value, or a companion
+    without --flex, is an error of the command line)."""
+    if not hasattr(args, "flex"):
+        if hasattr(args, "flex_cutoff") or hasattr(args, "flex_file"):
+            parser.error("--flex-cutoff and --flex-file need --flex")
+        return None
+    cutoff = getattr(args, "flex_cutoff", 7.3)
+    try:
+        _score.flex_cut_mA(cutoff)
+    except ValueError as exc:
+        parser.error(str(exc))
+    return cutoff
 
 
 def run_dmpfold(argv=None):
@@ -1726,13 +1825,14 @@ def run_dmpfold(argv=None):
     if hasattr(args, "score_domains") and args.native is None:
         parser.error("--score-domains needs --native")
     domains = domains_arguments(parser, args)
-    r, parse, domain_hits, domain_scores = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
+    flex = flex_arguments(parser, args)
+    r, parse, domain_hits, domain_scores, flexed = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
                                   args.model_weights, args.converge, args.native, args.native_chain, args.compare,
                                   args.compare_chain, search, distmap=args.distmap is not None, scores=args.native is not None,
                                   alignment=args.compare is not None, hits=args.search is not None, map_scores=args.score_map,
                                   pass_scores=args.score_passes, ss=args.ss, restrain=args.restrain,
                                   restrain_cutoff=args.restrain_cutoff, exposure=args.exposure,
-                                  score_domains=hasattr(args, "score_domains"))
+                                  score_domains=hasattr(args, "score_domains"), flex=flex)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1763,6 +1863,8 @@ def run_dmpfold(argv=None):
         json_line({"exposure": _score.exposure_json(r.exposure)}, args.exposure_file)
     if parse is not None:
         json_line({"domains": _score.domains_json(parse)}, getattr(args, "domains_file", None))
+    if flexed is not None:
+        json_line({"flex": _score.flex_json(flexed)}, getattr(args, "flex_file", None))
     if r.restrain is not None:
         json_line({"restrain": r.restrain}, None)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

@@ -136,27 +136,32 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     and `total` is the floats the buffer must hold.  `search_domains` (option "search_domains" on; an attribute beside the
     fields, like `domains`) puts the domain-search block, sized from the K of `search`, between the domain block and the
     align block; `score_domains` (option "score_domains" on; an attribute likewise) puts the domain-score block behind that, in
-    front of the align block."""
+    front of the align block; `flex` (option "flex" on; an attribute likewise) puts the flex block (48 + 20L, at `flex_off`)
+    behind that, in front of the align block."""
 
     def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None,
-                ss=False, exposure=False, domains=False, search_domains=False, score_domains=False):
+                ss=False, exposure=False, domains=False, search_domains=False, score_domains=False, flex=False):
         self = super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
                                None if passes is None else int(passes), bool(ss), bool(exposure))
         self.domains = bool(domains)
         self.search_domains = bool(search_domains)
         self.score_domains = bool(score_domains)
+        self.flex = bool(flex)
         return self
 
     domains = False                  # (of a Layout made by `_make`)
     search_domains = False
     score_domains = False
+    flex = False
 
     def _replace(self, **changes):
         domains = changes.pop("domains", self.domains)
         search_domains = changes.pop("search_domains", self.search_domains)
         score_domains = changes.pop("score_domains", self.score_domains)
+        flex = changes.pop("flex", self.flex)
         new = super()._replace(**changes)
+        new.flex = bool(flex)
         new.domains = bool(domains)
         new.search_domains = bool(search_domains)
         new.score_domains = bool(score_domains)
@@ -168,6 +173,8 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
             return domain_search_floats(self.L, self.search[0]) if self.search_domains and self.search is not None else 0
         if row is DOMAIN_SCORES:
             return domain_score_floats(self.L) if self.score_domains else 0
+        if row is FLEX:
+            return flex_floats(self.L) if self.flex else 0
         value = getattr(self, row.arg)
         return 0 if value is None or value is False else row.floats(self.L, value)
 
@@ -184,6 +191,9 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
             if row.key == "domains" and self.floats(DOMAIN_SCORES):      # (likewise: see DOMAIN_SCORES)
                 yield DOMAIN_SCORES, at
                 at += self.floats(DOMAIN_SCORES)
+            if row.key == "domains" and self.floats(FLEX):               # (likewise: see FLEX)
+                yield FLEX, at
+                at += self.floats(FLEX)
         yield None, at
 
     def _begin(self, key):
@@ -198,6 +208,7 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     domains_off = property(lambda s: s._begin("domains"))                                                   # D0
     domain_search_off = property(lambda s: s.domains_off + s.floats(BLOCK["domains"]))
     domain_score_off = property(lambda s: s.domain_search_off + s.floats(DOMAIN_SEARCH))
+    flex_off = property(lambda s: s.domain_score_off + s.floats(DOMAIN_SCORES))
     align_off = property(lambda s: s._begin("align"))                                                       # A0
     # the end of the align block as its writer allocated it ...
     align_end = property(lambda s: s._begin(None))
@@ -248,6 +259,11 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
         floats = self.floats(DOMAIN_SCORES)
         return buf[self.domain_score_off:self.domain_score_off + floats] if floats else None
 
+    def flex_block(self, buf):
+        """The flex block of a `d_conf` buffer as a view (48 + 20L floats), None with `flex` off."""
+        floats = self.floats(FLEX)
+        return buf[self.flex_off:self.flex_off + floats] if floats else None
+
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
 def conf_floats(L, distmap=False, score=False, align_m=None, score_map=False):
@@ -291,9 +307,11 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
     domains_block = None
     domain_search_block = None       # with "search_domains": (400 + 2L) K floats; an attribute too, and never handed out by `public`
     domain_score_block = None        # with "score_domains": 1040 + 4L floats; likewise
+    flex_block = None                # with "flex": 48 + 20L floats; likewise
 
-    def __new__(cls, *parts, domains_block=None, domain_search_block=None, domain_score_block=None, **named):
+    def __new__(cls, *parts, domains_block=None, domain_search_block=None, domain_score_block=None, flex_block=None, **named):
         self = super().__new__(cls, *parts, **named)
+        self.flex_block = flex_block
         self.domains_block = domains_block
         self.domain_search_block = domain_search_block
         self.domain_score_block = domain_score_block
@@ -303,7 +321,9 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
         domains_block = changes.pop("domains_block", self.domains_block)
         domain_search_block = changes.pop("domain_search_block", self.domain_search_block)
         domain_score_block = changes.pop("domain_score_block", self.domain_score_block)
+        flex_block = changes.pop("flex_block", self.flex_block)
         new = super()._replace(**changes)
+        new.flex_block = flex_block
         new.domains_block = domains_block
         new.domain_search_block = domain_search_block
         new.domain_score_block = domain_score_block
@@ -1395,6 +1415,187 @@ def domain_scores_json(ds, domains=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# option "flex" (include/dmpfold_hip.h): the Gaussian network model of the final C-alpha trace and, with a whole native, of the
+# native's - contacts, degrees, the eight lowest eigenpairs of the Kirchhoff matrix and the slow-mode fluctuation.  Hinges,
+# collectivities, the correlations with the confidence and with the native and the agreement with the domain parse are
+# formed here in float64.
+# ---------------------------------------------------------------------------------------------------------------------
+FLEX_HEADER = 16                     # floats in front of the two legs' headers of the flex block
+FLEX_LEG = 16                        # floats of a leg's header
+FLEX_MODES = 8                       # eigenpairs per leg
+FLEX_FIELDS = ("contacts", "sigma", "components", "used")
+
+
+def flex_floats(L):
+    """Floats of the flex block (option "flex") of a prediction of length L: 16 + 2 x 16 + 2 x (2 + 8) L."""
+    return FLEX_HEADER + 2 * FLEX_LEG + 2 * (2 + FLEX_MODES) * int(L)
+
+
+def flex_cut_mA(cutoff):
+    """A contact cutoff in Angstrom as option "flex_cut_mA" (4 .. 20 A); ValueError for anything else."""
+    mA = int(round(float(cutoff) * 1000.0)) if cutoff == cutoff else -1
+    if not 4000 <= mA <= 20000:
+        raise ValueError(f"the flex cutoff must be 4 .. 20 Angstrom, got {cutoff!r}")
+    return mA
+
+
+def pack_flex(L, cut_mA=7300, legs=()):
+    """A flex block from its parts (one dict per leg: contacts, sigma, components, used, eigenvalues (8,), degree (L,), msf (L,),
+    modes (8, L); one leg = no native: zeros and NaN in its place, as the library writes them): the inverse of the raw views of
+    `unpack_flex` (tests, restatements)."""
+    L = int(L)
+    b = np.zeros(flex_floats(L), dtype=np.float32)
+    b[0], b[1], b[2] = L, cut_mA, 1.0 if len(legs) > 1 else 0.0
+    res = FLEX_HEADER + 2 * FLEX_LEG
+    b[res + (2 + FLEX_MODES) * L * len(legs):] = np.nan
+    for e, leg in enumerate(legs):
+        h = b[FLEX_HEADER + FLEX_LEG * e:FLEX_HEADER + FLEX_LEG * (e + 1)]
+        h[:4] = [leg[k] for k in FLEX_FIELDS]
+        h[8:] = np.asarray(leg["eigenvalues"], dtype=np.float64).astype(np.float32)
+        a = b[res + (2 + FLEX_MODES) * L * e:res + (2 + FLEX_MODES) * L * (e + 1)].reshape(2 + FLEX_MODES, L)
+        a[0], a[1], a[2:] = leg["degree"], leg["msf"], leg["modes"]
+    return b
+
+
+def _ranks(v):
+    """Ranks 0 .. n - 1 of a vector, ties sharing their mean rank."""
+    v = np.asarray(v, dtype=np.float64)
+    order = np.argsort(v, kind="stable")
+    r = np.empty(v.size, dtype=np.float64)
+    r[order] = np.arange(v.size, dtype=np.float64)
+    _, inverse, counts = np.unique(v, return_inverse=True, return_counts=True)
+    sums = np.zeros(counts.size, dtype=np.float64)
+    np.add.at(sums, inverse, r)
+    return (sums / counts)[inverse]
+
+
+def flex_hinges(mode):
+    """The residues i where a mode changes sign between i and i + 1; the sign is that of the float, zero counts as positive."""
+    neg = np.asarray(mode) < 0
+    return [int(i) for i in np.flatnonzero(neg[1:] != neg[:-1])]
+
+
+def flex_collectivity(mode):
+    """exp(-sum u^2 ln u^2) / L of a mode, u^2 normalised to sum 1 (Bruschweiler 1995); 1 / L .. 1."""
+    u2 = np.asarray(mode, dtype=np.float64) ** 2
+    total = u2.sum()
+    if not total > 0:
+        return float("nan")
+    u2 = u2[u2 > 0] / total
+    return float(np.exp(-(u2 * np.log(u2)).sum()) / np.asarray(mode).size)
+
+
+def flex_parse_sides(domains_leg):
+    """The two sides of the first cut of a domain parse (one leg of `unpack_domains`) as a boolean vector over the residues, or
+    None where the parse has one domain or the block does not tell: a domain of level 1 is one whole side of the first cut and
+    every other domain lies on the other; a parse whose both halves were split again has no such domain."""
+    if domains_leg is None or domains_leg.get("domains", 0) < 2:
+        return None
+    labels = np.asarray(domains_leg["labels"])
+    for d, row in enumerate(domains_leg["table"]):
+        if row["level"] == 1:
+            return labels == d
+    return None
+
+
+def flex_parse_agreement(mode, sides):
+    """The share of residues whose sign in `mode` (zero counts as positive) agrees with the side of the first cut they lie on, the
+    better of the two assignments of signs to sides: 0.5 .. 1."""
+    neg = np.asarray(mode) < 0
+    same = float((neg == np.asarray(sides, dtype=bool)).mean())
+    return max(same, 1.0 - same)
+
+
+def flex_rmsip(a, b):
+    """The root mean square inner product of two sets of modes (rows), the first n = min(rows) of each: sqrt(sum (a_i . b_j)^2 / n)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    n = min(a.shape[0], b.shape[0])
+    if n == 0:
+        return float("nan")
+    return float(np.sqrt(((a[:n] @ b[:n].T) ** 2).sum() / n))
+
+
+def _flex_leg(header, arr, confs=None, domains_leg=None):
+    """One leg's sixteen header floats and ten arrays -> its part of `unpack_flex`."""
+    out = {name: _whole(v) for name, v in zip(FLEX_FIELDS, header)}
+    out["eigenvalues"] = np.asarray(header[8:16], dtype=np.float64)
+    out["degree"], out["msf"], out["modes"] = _count(arr[0]), np.asarray(arr[1]), np.asarray(arr[2:])
+    first = min(max(out["components"], 0), FLEX_MODES)
+    live = out["modes"][first:] if out["used"] > 0 else out["modes"][:0]
+    out["first_mode"] = first if out["used"] > 0 else None
+    out["hinges"] = flex_hinges(live[0]) if len(live) else []
+    out["collectivity"] = [flex_collectivity(m) for m in live]
+    mean = _mean(out["msf"])
+    out["msf_norm"] = np.asarray(out["msf"], dtype=np.float64) / mean if mean > 0 else np.full(out["msf"].shape, np.nan)
+    if confs is not None:
+        floppy = 1.0 - np.asarray(confs, dtype=np.float64).reshape(-1)
+        out["r_conf"] = _pearson(out["msf"], floppy)
+        ok = (out["msf"] == out["msf"]) & (floppy == floppy)
+        out["rho_conf"] = _pearson(_ranks(np.asarray(out["msf"], dtype=np.float64)[ok]), _ranks(floppy[ok])) if ok.sum() >= 2 else float("nan")
+    sides = flex_parse_sides(domains_leg)
+    if sides is not None and len(live):
+        out["parse_agreement"] = flex_parse_agreement(live[0], sides)
+    return out
+
+
+def unpack_flex(block, L, confs=None, domains=None):
+    """A flex block (48 + 20L floats, array or tensor) -> dict: L, cutoff (Angstrom), has_native and, of the model's leg,
+    contacts, sigma, components, used, eigenvalues (8,) ascending, degree (L,) int, msf (L,), modes (8, L) and, formed here in
+    float64: first_mode (the index of the first non-zero mode, None where used = 0), hinges (flex_hinges of that mode),
+    collectivity (flex_collectivity of every non-zero mode), msf_norm (msf with mean 1).  `confs` (the prediction's per-residue
+    confidence) adds r_conf and rho_conf, Pearson's and Spearman's correlation of msf with 1 - confidence; `domains` (the dict
+    of `unpack_domains` of the same prediction) adds parse_agreement (flex_parse_agreement of the first non-zero mode with
+    flex_parse_sides of the leg's parse) where the parse has two domains or more.  With a native's leg the same under "native"
+    (no r_conf), plus r_msf (Pearson r of the two legs' msf) and rmsip (flex_rmsip of the two legs' non-zero modes).  A block the
+    library answered with NaN (a latched fault) gives zero counts."""
+    L = int(L)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] != flex_floats(L):
+        raise ValueError(f"a flex block of length {L} has {flex_floats(L)} floats, got shape {tuple(b.shape)}")
+    res = FLEX_HEADER + 2 * FLEX_LEG
+    arr = b[res:].reshape(2, 2 + FLEX_MODES, L)
+    out = {"L": _whole(b[0]), "cutoff": float(b[1]) / 1000.0}
+    out.update(_flex_leg(b[FLEX_HEADER:FLEX_HEADER + FLEX_LEG], arr[0], None if confs is None else _host(confs), domains))
+    out["has_native"] = _whole(b[2]) > 0
+    if out["has_native"]:
+        nat_domains = domains.get("native") if domains is not None and domains.get("has_native") else None
+        nat = _flex_leg(b[FLEX_HEADER + FLEX_LEG:res], arr[1], None, nat_domains)
+        out["native"] = nat
+        out["r_msf"] = _pearson(out["msf"], nat["msf"])
+        out["rmsip"] = flex_rmsip(out["modes"][out["components"]:] if out["used"] > 0 else out["modes"][:0],
+                                  nat["modes"][nat["components"]:] if nat["used"] > 0 else nat["modes"][:0])
+    return out
+
+
+FLEX_SCALARS = ("r_conf", "rho_conf", "parse_agreement")
+
+
+def flex_json(fx, arrays=False):
+    """`unpack_flex` as a JSON-ready dict (the key "flex" of `dmpfold --flex` and of `dmpfold-batch --flex`): the cutoff, per leg
+    the counts, the eigenvalues, the hinges, the collectivities and the correlations that are there, with a native the same under
+    "native" plus r_msf and rmsip; with `arrays` also degree, msf and the modes as lists.  NaN becomes None."""
+    def leg(d):
+        js = {k: int(d[k]) for k in FLEX_FIELDS}
+        js["eigenvalues"] = [_num(v) for v in d["eigenvalues"]]
+        js["first_mode"] = d["first_mode"]
+        js["hinges"] = [int(i) for i in d["hinges"]]
+        js["collectivity"] = [_num(v) for v in d["collectivity"]]
+        js.update({k: _num(d[k]) for k in FLEX_SCALARS if k in d})
+        if arrays:
+            js["degree"] = [int(v) for v in d["degree"]]
+            js["msf"] = [_num(v) for v in d["msf"]]
+            js["modes"] = [[_num(v) for v in row] for row in d["modes"]]
+        return js
+    out = {"L": int(fx["L"]), "cutoff": _num(fx["cutoff"])}
+    out.update(leg(fx))
+    out["has_native"] = bool(fx["has_native"])
+    if fx["has_native"]:
+        out["native"] = leg(fx["native"])
+        out["r_msf"], out["rmsip"] = _num(fx["r_msf"]), _num(fx["rmsip"])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The blocks behind the confidences, each stated once.  A row of BLOCKS: `key` - what the host calls the block (a keyword of
 # Outputs.public and Outputs.of, of a Pipeline's set_<key>); `option` - the library option that turns it on; `field` - its view
 # in an `Outputs`; `name` - what its unpacked form is called wherever it is handed on (a property of predict.Engine, a field of
@@ -1461,3 +1662,8 @@ DOMAIN_SCORES = Block("score_domains", "score_domains", "domain_score_block", "d
                       lambda L, on: domain_score_floats(L),
                       lambda block, L, **_: unpack_domain_scores(block, L),
                       lambda ds, domains=None, **_: domain_scores_json(ds, domains))
+# The flex block of option "flex": likewise no row of BLOCKS; it lies behind the domain-score block, in front of the align block.
+FLEX = Block("flex", "flex", "flex_block", "flex", "flex", "48 + 20L",
+             lambda L, on: flex_floats(L),
+             lambda block, L, confs=None, domains=None, **_: unpack_flex(block, L, confs=confs, domains=domains),
+             lambda fx, arrays=False, **_: flex_json(fx, arrays))

@@ -575,7 +575,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains", + 1040 + 4L with "score_domains"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains", + 1040 + 4L with "score_domains", + 48 + 20L with "flex"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
@@ -801,7 +801,68 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * Measured cost of dmp_predict_end with the option on (profiles/score_domains.txt; the collapsed model of profiles/exposure.txt, a
  * whole folded-like native, both legs): 0.24 ms at L = 96, 0.60 ms at 300, 2.55 ms at 1000, 5.63 ms at 2048 where the model stays
  * one domain - 1.9 to 2.6 times "score_native" alone in the same run - and 0.20, 0.40, 1.71 and 4.46 ms forced through all four
- * levels (1.3 to 2.1 times). */
+ * levels (1.3 to 2.1 times).
+ * "flex" (0 or 1, default 0; any other value: DMP_ERR_ARG) with "flex_cut_mA" (4000 .. 20000, default 7300; anything else:
+ * DMP_ERR_ARG): THE SLOW MODES AND THE RESIDUE FLEXIBILITY OF THE MODEL by the Gaussian network model (GNM: Bahar, Atilgan & Erman,
+ * Fold. Des. 2, 173, 1997; Haliloglu, Bahar & Erman, Phys. Rev. Lett. 79, 3090, 1997) of its final C-alpha trace - which parts
+ * move together, about which hinge, and how floppy each residue is - without a native or a second program.  Both are read when a
+ * prediction begins and held for it.  With "flex" 0 nothing is launched, read, written or allocated and every offset is what it
+ * was.  With it 1 THE d_conf ARGUMENT MUST HOLD 48 + 20L MORE FLOATS AT THE END OF THE DOMAIN-SCORE BLOCK (of whatever block lies
+ * last in front of the align block, with those behind it off): there sits the FLEX BLOCK, all of it outputs, and A0 and B0 move
+ * behind it; nothing in front of it moves.  Offsets relative to its start:
+ *   0                    L
+ *   1                    the cutoff, "flex_cut_mA"
+ *   2                    has_native: 1 where the native's leg was computed, else 0
+ *   3 .. 15              zero
+ *   16 + 16 e + c        the header of leg e (0 the model, 1 the native): c = 0 contacts   1 sigma   2 components   3 used
+ *                        4 .. 7 zero   8 + k lambda_k, k = 0 .. 7
+ *   48 + 10 L e          degree [L] of leg e
+ *   48 + 10 L e + L      msf [L]
+ *   48 + 10 L e + 2L + k L   mode k [L], k = 0 .. 7
+ * The integers are exact as floats (contacts <= 2.1 million at L = 2048, below 2^24).  Without the native's leg its header is zero
+ * and its 10 L floats are NaN.
+ * THE DEFINITION, the only one.  c = "flex_cut_mA" / 1000.0 in double.  For a leg's C-alpha trace x (float32, L rows):
+ *   contacts    residues i != j are in contact iff d2 < c c, d2 formed in float64 from the float32 coordinates as
+ *               (dx*dx + dy*dy) + dz*dz (the expression of "domains"; a NaN coordinate makes no contact).  NO MINIMUM SEQUENCE
+ *               SEPARATION: chain neighbours are springs.  `contacts` counts the pairs i < j, degree_i the contacts of i.
+ *   Gamma       the Kirchhoff matrix D - A of the contact matrix A and its degrees D; sigma = 2 x the largest degree, an integer
+ *               that bounds Gamma's spectrum (Gershgorin).
+ *   eigenpairs  the eight lowest (lambda_k, v_k) of Gamma, ascending in lambda, k = 0 .. 7, computed as the eight largest
+ *               (mu, v) of M = sigma I - Gamma - whose entries are integers below 4096, exact in float32 - by the float64 solver
+ *               of the MDS step (dmp_eigh_top8's factorisation); lambda_k = sigma - mu_k in double, rounded once to float32; v_k
+ *               the unit eigenvector under that solver's sign rule - the component of largest magnitude positive, first index on
+ *               ties - each component rounded once to float32.
+ *   zero modes  mode k is a zero mode iff lambda_k <= 1e-7, absolute.  Gamma has integer entries; the solver's eigenvalue error is
+ *               n 2^-53 sigma <= 9.3e-10 at n = 2048; the smallest non-zero eigenvalue of a connected graph is at least
+ *               4 / (n diameter) >= 9.5e-7: 1e-7 sits 100 times above the first and about 10 times below the second.
+ *               components = the zero modes among the eight (1 for a connected network), used = 8 - components.
+ *   msf         msf_i = sum over the non-zero modes k, ascending, of v_k[i]^2 / lambda_k - the slow-mode mean-square fluctuation
+ *               in units of kT / spring constant - accumulated in float64 FROM THE FLOAT64 v OF THE BACK-TRANSFORMATION, not
+ *               from the float32 modes of the block, and rounded once to float32; 0 where used = 0.
+ * The model's leg is always computed, from the CA rows of d_coords: it sees the minimised and, with "restrain_milli", restrained
+ * model, as "assign_ss" and "exposure" do.  The native's leg is computed with "score_native" on and a native trace without a
+ * NaN coordinate (whole_xyz of the native entity above, as "domains"); a native with a missing row has no leg.  A prediction that
+ * latched a device-side fault has NaN in every float of the block.
+ * THIS IS THE GNM OF A C-ALPHA TRACE WITH ONE UNIFORM SPRING CONSTANT, NOT ProDy's BITS; SEVEN MODES AT MOST, NOT THE WHOLE
+ * SPECTRUM, SO msf IS THE SLOW-MODE FLUCTUATION, NOT THE FULL PSEUDO-INVERSE DIAGONAL; NOBODY HAS COMPARED THE FIGURES WITH
+ * EXPERIMENTAL B-FACTORS OR ANOTHER PROGRAM'S; INSIDE A CLUSTER OF EQUAL EIGENVALUES ANY ORTHONORMAL BASIS IS A RIGHT ANSWER, AND
+ * msf DEPENDS ON THE BASIS WHERE A CLUSTER STRADDLES THE 8TH / 9TH EIGENVALUE.
+ * Launches (csrc/flex.hip), in dmp_predict_end behind "score_domains" and in front of "align_structure", per leg: a memset of the
+ * degrees; flex_kirchhoff_kernel (tiles of 16 rows x 256 columns, the rows' coordinates through LDS: the off-diagonal of M and
+ * the degrees, one integer atomic per row and tile); flex_sigma_kernel (one workgroup: largest degree, contact total, sigma, the
+ * diagonal of M); the solver exactly as a recycling pass runs it (eig_load_kernel, the tridiagonalisation in the context's current
+ * form, tri_eig_kernel) with the second epilogue of backtransform_kernel, which writes the modes into the block and their float64
+ * sources into the solver's scratch; flex_finish_kernel (eigenvalues, components, used, msf, degrees, the header).  The solver's
+ * scratch and graphs are the passes' own - the last pass is behind these launches on the same stream - but M lies in a scratch of
+ * the option's: what dmp_debug_fetch hands out as "gram" and "mds" after a prediction is untouched.  With a score block whose trace
+ * is not whole the native's launches still run (nothing is read back to decide) and flex_finish_kernel overwrites what they
+ * left.  Integer atomics only: the same bits on every run; dmp_predict_end stays asynchronous.  Scratch of its own: max_L^2 + max_L
+ * floats (0.34 MiB at max_L = 300, 16 MiB at 2048) beside the native entity's, allocated when the option first becomes 1 on a
+ * context and counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the option as it was.
+ * Measured cost of dmp_predict_end with the option on (profiles/flex.txt; the collapsed model of profiles/exposure.txt, a whole
+ * folded-like native): the model's leg adds 0.45 ms at L = 96, 1.56 ms at 300, 9.4 ms at 1000 and 41.2 ms at 2048, the native's leg
+ * 0.45, 1.50, 9.3 and 41.0 ms more; one dmp_eigh_top8 of the same order takes 0.45, 1.53, 9.2 and 41.1 ms in the same run: a leg is
+ * 0.98 to 1.01 of it. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
