@@ -204,7 +204,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
     the residue's own domain); <stem>.scores.json gains the key "domain_scores" (score.domain_scores_json).  With `flex` (the dict
     of score.unpack_flex, --flex): npz gains flex_eig (float32 (8,): the model's eight lowest eigenvalues), flex_modes (float32
     (8, L)), flex_msf (float32 (L,)) and flex_degree (int32 (L,)); pdb / ca get <stem>.flex.json (the line `dmpfold --flex`
-    prints)."""
+    prints).  With `msa_report` (the dict of score.unpack_msa_report, --msa-report): npz gains msa_header (float32 (128,)) and
+    msa_columns (float32 (8, L)) and, with --dca-map, dca_map (float32 (L, L)); pdb / ca get <stem>.msa.json (the line `dmpfold
+    --msa-report` prints) and <stem>.dca_map.npy."""
+    msa_report = results.pop("msa_report", None)
     domain_hits = results.pop("domain_hits", None)
     domain_scores = results.pop("domain_scores", None)
     flex = results.pop("flex", None)
@@ -278,6 +281,11 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
         if flex is not None:
             extra.update({"flex_eig": np.asarray(flex["eigenvalues"], dtype=np.float32), "flex_modes": np.asarray(flex["modes"], dtype=np.float32),
                           "flex_msf": np.asarray(flex["msf"], dtype=np.float32), "flex_degree": np.asarray(flex["degree"], dtype=np.int32)})
+        if msa_report is not None:
+            extra.update({"msa_header": np.asarray(msa_report["header"], dtype=np.float32),
+                          "msa_columns": np.asarray(msa_report["columns"], dtype=np.float32)})
+            if "dca_map" in msa_report:
+                extra["dca_map"] = np.asarray(msa_report["dca_map"], dtype=np.float32)
         np.savez_compressed(path, coords=coords.detach().cpu().numpy(), confs=confs.detach().cpu().numpy(),
                             alnmat=alnmat, **extra)
         return path
@@ -292,6 +300,10 @@ def write_result(out_dir, aln_path, coords, confs, alnmat, fmt="pdb", distmap=No
                         ("flex", None if flex is None else _score.flex_json(flex))):
         if value is not None:
             forms[name] = {name: value}                  # (these lines carry their name)
+    if msa_report is not None:
+        forms["msa"] = {"msa": _score.msa_report_json(msa_report)}
+        if "dca_map" in msa_report:
+            np.save(stem + ".dca_map.npy", np.asarray(msa_report["dca_map"], dtype=np.float32))
     for name, form in forms.items():
         with open(f"{stem}.{name}.json", "w") as fh:
             fh.write(json.dumps(form) + "\n")
@@ -362,6 +374,20 @@ def batch_domains(tau=0.25, min_size=40, min_segment=10):
 
 _SCORE_DOMAINS = False
 _FLEX = None                                            # --flex: the contact cutoff in Angstrom, or None
+_MSA_REPORT = None                                      # --msa-report: whether the DCA contact map is wanted too, or None
+
+
+@contextlib.contextmanager
+def batch_msa_report(dca_map=False):
+    """Every run_batch inside the block also reports on every target's alignment on the GPU (Pipeline.use_msa_report; `dca_map`:
+    with the raw DCA contact map): the result is written with the target (write_result) and `stats_out` receives "msa": {stem:
+    N, neff_80, median_coverage}."""
+    global _MSA_REPORT
+    before, _MSA_REPORT = _MSA_REPORT, bool(dca_map)
+    try:
+        yield
+    finally:
+        _MSA_REPORT = before
 
 
 @contextlib.contextmanager
@@ -481,6 +507,7 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         max_L = max(max_L, library.max_m)               # the engines' capacity bounds every entry's length
     domains = _DOMAINS                                  # (batch_domains)
     flex = _FLEX                                        # (batch_flex)
+    msa_report = _MSA_REPORT                            # (batch_msa_report)
     search_domains = library is not None and bool(getattr(library, "domains", False))      # (--search-domains)
     if (search_domains or score_domains) and domains is None:
         domains = domains_options()                     # the library's flag, or --score-domains, turns "domains" on, with the defaults
@@ -510,6 +537,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
                 pipe.use_score_domains(True)                # (behind set_score, which it needs)
             if flex is not None:
                 pipe.use_flex(True, flex)
+            if msa_report is not None:
+                pipe.use_msa_report(True, msa_report)
             if dev.type == "cuda":
                 # every copy of this front end goes through its own (non-blocking) stream: nothing is ever enqueued on
                 # the process's default stream while the engines run
@@ -532,6 +561,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             outs = outs + (pipe.outputs_of(t).domain_score_block,)       # likewise, behind that
         if flex is not None:
             outs = outs + (pipe.outputs_of(t).flex_block,)               # likewise, behind that
+        if msa_report is not None:
+            outs = outs + (pipe.outputs_of(t).msa_report_block,)         # likewise, behind that
         if outs[0].is_cuda:
             host = tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in outs)
             with (torch.cuda.stream(copy_stream) if copy_stream is not None else contextlib.nullcontext()):
@@ -550,14 +581,16 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
     scored, aligned = set(), set()                      # the tickets that had a native / a structure
     asked = {"natives": bool(natives), "structures": bool(structures), "library": library is not None, "ss": ss,
              "exposure": exposure, "restrain": restraining, "domains": domains is not None, "search_domains": search_domains,
-             "flex": flex is not None}
+             "flex": flex is not None, "msa_report": msa_report is not None}
     blocks_on = {"score": asked["natives"], "align": asked["structures"], "search": asked["library"], "score_map": score_map,
                  "passes": score_passes, "ss": ss, "exposure": exposure, "domains": domains is not None}
     gathered = {}                                       # {key of `stats_out`: {stem: what the summary takes}}
 
     def write(t, public):
         """a finished target's files from what the pipeline handed out; its scores only if it had a native"""
-        ds_block, score_block, flex_block = None, None, None
+        ds_block, score_block, flex_block, msa_block = None, None, None, None
+        if msa_report is not None:
+            public, msa_block = public[:-1], public[-1]
         if flex is not None:
             public, flex_block = public[:-1], public[-1]
         if score_domains:
@@ -584,6 +617,10 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
         if flex_block is not None:
             results["flex"] = _score.unpack_flex(flex_block, alnmat.shape[1], confs=out.confs, domains=results.get("domains"))
             forms["flex"] = _score.flex_json(results["flex"])
+        if msa_block is not None:
+            results["msa_report"] = _score.unpack_msa_report(msa_block, alnmat.shape[1], confs=out.confs,
+                                                             seq="".join(_score.AA1[c] if c < 20 else "-" for c in alnmat[0]))
+            forms["msa_report"] = _score.msa_report_json(results["msa_report"])
         rep = None
         if restraining:
             rep = forms["restrain"] = restrain_report(float(restrain), float(restrain_cutoff), max(minsteps, 0), out.distmap,
@@ -699,7 +736,8 @@ def run_batch(targets, out_dir, iterations=default_iterations, minsteps=default_
             else:
                 write(t, res[t] + ((pipe.collected[t].domain_search_block,) if search_domains else ())
                       + ((pipe.collected[t].domain_score_block,) if score_domains else ())
-                      + ((pipe.collected[t].flex_block,) if flex is not None else ()))
+                      + ((pipe.collected[t].flex_block,) if flex is not None else ())
+                      + ((pipe.collected[t].msa_report_block,) if msa_report is not None else ()))
     elapsed = time.perf_counter() - t0
     if pipe is not None:
         if stats_out is not None and converge is not None:
@@ -786,6 +824,13 @@ def batch_parser():
     # <stem>.flex.json.  Hidden like --search-refine, for the same reason.
     ap.add_argument("--flex", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     ap.add_argument("--flex-cutoff", type=float, default=argparse.SUPPRESS, metavar="A", help=argparse.SUPPRESS)
+    # --msa-report [--dca-map]: a report on every target's alignment made on the GPU (Neff at 62, 80 and 90 % identity, gaps, copies,
+    # histograms, per-column conservation, the strongest DCA coupling per column; with --natives the DCA contact precisions); the
+    # summary carries per target N, neff_80 and the median coverage, with means and medians, and with --natives Spearman's
+    # correlation of log10 neff_80 with the TM-score and the mean TM-score per Neff bin; npz gains msa_header, msa_columns and (--dca-map,
+    # which implies --msa-report) dca_map, pdb / ca write <stem>.msa.json and <stem>.dca_map.npy.  Hidden like --search-refine, for the same reason.
+    ap.add_argument("--msa-report", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    ap.add_argument("--dca-map", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     ap.add_argument("--ss", action="store_true",
                     help="assign secondary structure to every target's backbone on the GPU from its hydrogen bonds; the summary "
                          "gains every target's eight-state string and helix / strand / coil fractions with their means and "
@@ -901,6 +946,38 @@ def flex_summary(flex):
     return out
 
 
+def msa_brief(form):
+    """The summary's figures of one target from its "msa" (score.msa_report_json): the depth, Neff at 80 % and the median coverage."""
+    return {k: form[k] for k in ("N", "neff_80", "median_coverage")}
+
+
+def msa_summary(found):
+    """{stem: msa_brief} -> the summary's part for --msa-report: every target's figures, and mean and median of each."""
+    out = {"msa_targets": len(found), "msa": found}
+    for name in ("N", "neff_80", "median_coverage"):
+        vals = [v[name] for v in found.values() if v.get(name) is not None]
+        out["mean_msa_" + name] = float(np.mean(vals)) if vals else None
+        out["median_msa_" + name] = float(np.median(vals)) if vals else None
+    return out
+
+
+NEFF_BINS = (("<10", 0.0, 10.0), ("10-100", 10.0, 100.0), ("100-1000", 100.0, 1000.0), (">=1000", 1000.0, float("inf")))
+
+
+def neff_tm_summary(msa, scores):
+    """{stem: msa_brief} and {stem: scores} -> the summary's part for --msa-report with --natives, over the targets that have both
+    a Neff above 0 and a TM-score: Spearman's correlation of log10 neff_80 with tm (None below two targets or without any
+    spread), and per Neff bin the targets and their mean tm."""
+    both = [(msa[s]["neff_80"], scores[s]["tm"]) for s in sorted(msa) if s in scores and scores[s].get("tm") is not None
+            and msa[s].get("neff_80") is not None and msa[s]["neff_80"] > 0]
+    rho = _score._spearman(np.log10([n for n, _ in both]), [t for _, t in both]) if len(both) >= 2 else float("nan")
+    bins = {}
+    for name, lo, hi in NEFF_BINS:
+        tms = [t for n, t in both if lo <= n < hi]
+        bins[name] = {"targets": len(tms), "mean_tm": float(np.mean(tms)) if tms else None}
+    return {"neff_tm_targets": len(both), "neff_tm_spearman": rho if rho == rho else None, "neff_tm_bins": bins}
+
+
 def restrain_summary(reports):
     """{stem: the dict of predict.restrain_report} -> the summary's part for --restrain: every target's report, and mean and
     median of map_rms, restrained_pairs, clashes and bond_dev_max."""
@@ -957,8 +1034,9 @@ GATHERED = (("scores", "natives", score_summary),
             ("hits", "library", lambda found: {"searched_targets": len(found), "hits": found}),
             ("ss", "ss", ss_summary), ("exposure", "exposure", exposure_summary), ("restrain", "restrain", restrain_summary),
             ("domains", "domains", domains_summary), ("flex", "flex", flex_summary),
+            ("msa", "msa_report", msa_summary),
             ("domain_hits", "search_domains", lambda found: {"domain_searched_targets": len(found), "domain_hits": found}))
-GATHERED_AS = {"flex": ("flex", flex_brief),
+GATHERED_AS = {"flex": ("flex", flex_brief), "msa_report": ("msa", msa_brief),
                "alignment": ("alignments", lambda form: {k: form[k] for k in ("m",) + _score.ALIGN_NAMES}),
                "hits": ("hits", lambda form: [{k: v for k, v in hit.items() if k not in ("R", "t")} for hit in form["hits"]]),
                # every domain's best hit
@@ -1000,6 +1078,8 @@ def main(argv=None):
     if hasattr(args, "score_domains") and not args.natives:
         ap.error("--score-domains needs --natives")
 
+    if hasattr(args, "dca_map"):
+        args.msa_report = True                           # (--dca-map implies --msa-report)
     dom_given = {k: getattr(args, "domains_" + k) for k in ("tau", "min_size", "min_segment") if hasattr(args, "domains_" + k)}
     if dom_given and not hasattr(args, "domains"):
         ap.error("--domains-tau, --domains-min-size and --domains-min-segment need --domains")
@@ -1032,7 +1112,8 @@ def main(argv=None):
     try:
         with (batch_domains(**dom_given) if hasattr(args, "domains") else contextlib.nullcontext()), \
                 (batch_score_domains() if hasattr(args, "score_domains") else contextlib.nullcontext()), \
-                (batch_flex(getattr(args, "flex_cutoff", 7.3)) if hasattr(args, "flex") else contextlib.nullcontext()):
+                (batch_flex(getattr(args, "flex_cutoff", 7.3)) if hasattr(args, "flex") else contextlib.nullcontext()), \
+                (batch_msa_report(hasattr(args, "dca_map")) if hasattr(args, "msa_report") else contextlib.nullcontext()):
             n, elapsed, _ = run_batch(targets, args.out_dir, args.iterations, args.minsteps,
                                       weights_file=args.model_weights, streams=args.streams,
                                       device=f"cuda:{local_rank}", rank=rank, world=world, fmt=args.format, store=store,
@@ -1066,6 +1147,8 @@ def main(argv=None):
         for key, argument, part in GATHERED:
             if getattr(args, argument, None):
                 summary.update(part(gather(key, passes, world, job_store if world > 1 else None)))
+        if "msa" in summary and "scores" in summary:    # --msa-report with --natives: accuracy against depth
+            summary.update(neff_tm_summary(summary["msa"], summary["scores"]))
         print(json.dumps(summary), flush=True)
     if (failed_all or broke_all) and status == 0:
         status = 1                                   # every rank of a job that lost targets fails, rank 0 included

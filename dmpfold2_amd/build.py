@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libdmpfold_hip.so")
 SOURCES = ["api.hip", "pipeline.hip", "gemm.hip", "msa.hip", "dca.hip", "gru.hip", "vgru.hip", "vgru_f32.hip", "vgru_x3.hip", "trunk.hip", "train.hip", "mds.hip",
-           "coords.hip", "score.hip", "mapscore.hip", "align.hip", "entity.hip", "ss.hip", "exposure.hip", "domains.hip", "flex.hip"]
+           "coords.hip", "score.hip", "mapscore.hip", "align.hip", "entity.hip", "ss.hip", "exposure.hip", "domains.hip", "flex.hip", "msareport.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # coords.hip: no SLP vectoriser = no packed-f32 instructions.  The vectoriser turns the cross products of the
 # backbone kernel into v_pk_mul_f32 ... op_sel:[0,1] op_sel_hi:[1,0], which returns 0 in lanes 48..63 when
@@ -31,10 +31,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # exposure.hip: float64 point tests and integer counts; likewise.
 # domains.hip: one float64 distance test per pair, integer counts behind it; likewise.
 # flex.hip: the same float64 distance test, integer counts, float64 sums; likewise.
+# msareport.hip: integer counts, float64 sums and entropies, copied bits; likewise.
 # entity.hip: NaN tests of float32 coordinates and a byte copy; likewise.
 PER_FILE_FLAGS = {"coords.hip": ["-fno-slp-vectorize"], "gru.hip": ["-fno-slp-vectorize"], "score.hip": ["-fno-slp-vectorize"],
                   "align.hip": ["-fno-slp-vectorize"], "mapscore.hip": ["-fno-slp-vectorize"], "ss.hip": ["-fno-slp-vectorize"],
-                  "exposure.hip": ["-fno-slp-vectorize"], "domains.hip": ["-fno-slp-vectorize"], "flex.hip": ["-fno-slp-vectorize"], "entity.hip": ["-fno-slp-vectorize"]}
+                  "exposure.hip": ["-fno-slp-vectorize"], "domains.hip": ["-fno-slp-vectorize"], "flex.hip": ["-fno-slp-vectorize"], "msareport.hip": ["-fno-slp-vectorize"], "entity.hip": ["-fno-slp-vectorize"]}
 
 
 def per_file_flags(src: str) -> list:

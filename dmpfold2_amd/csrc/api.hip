@@ -496,6 +496,10 @@ static int domains_reserve(dmp_ctx* c) {
 static int flex_reserve(dmp_ctx* c) {
   return c->opt.flex ? with_entity_reserve(c, c->flex_ws, flex_need(c->max_L), "flex scratch") : DMP_OK;
 }
+// Option "msa_report": its counters and the rows' neighbour counts (msareport.hip has the layout), sized by max_N.
+static int msa_report_reserve(dmp_ctx* c) {
+  return c->opt.msa_report ? scratch_reserve(c, c->report_ws, msa_report_need(c->max_N), "alignment-report scratch") : DMP_OK;
+}
 
 // ---- the options --------------------------------------------------------------------------------------------------------
 // One table; dmp_ctx_set_option and dmp_ctx_get_option walk it.  A NEW OPTION IS ONE ROW: its name, where the value lives (a
@@ -609,6 +613,7 @@ static const Option OPTIONS[] = {
     {"score_domains", TAIL(score_domains), 0, 1, 0, "score_domains must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, score_domains_reserve},   // needs "domains" = 1 and "score_native" = 1
     {"flex", TAIL(flex), 0, 1, 0, "flex must be 0 or 1, got %d", OPT_RW, nullptr, nullptr, flex_reserve},
     {"flex_cut_mA", TAIL(flex_cut), 4000, 20000, 0, "flex_cut_mA must be 4000 .. 20000, got %d"},                 // the contact cutoff of "flex", milli-Angstrom
+    {"msa_report", TAIL(msa_report), 0, 2, 0, "msa_report must be 0, 1 or 2 (with the DCA contact map), got %d", OPT_RW, nullptr, nullptr, msa_report_reserve},
     {"passes_run", CTX(passes_done), ANY, OPT_READ_ONLY},                                   // trunk passes of the last prediction
     {"search_chunk_used", CTX(search_last_C), ANY, OPT_READ_ONLY},                          // of the last prediction that searched: entries per chunk
     {"search_wg_per_cu", nullptr, nullptr, ANY, OPT_READ_ONLY, nullptr, nullptr, nullptr, get_search_wg_per_cu},
@@ -805,7 +810,7 @@ void dmp_ctx_destroy(dmp_ctx* c) {
   if (c->delta_host) (void)hipHostFree(c->delta_host);
   for (void* p : c->allocs) (void)hipFree(p);
   for (Scratch* w : {&c->score_ws, &c->map_ws, &c->align_ws, &c->search_ws, &c->pass_ws, &c->entity_ws, &c->ss_ws, &c->exposure_ws,
-                     &c->domains_ws, &c->domsearch_ws, &c->domscore_ws, &c->flex_ws})
+                     &c->domains_ws, &c->domsearch_ws, &c->domscore_ws, &c->flex_ws, &c->report_ws})
     if (w->p) (void)hipFree(w->p);
   release_weights(c);
   for (void* e : c->prof_ev) (void)hipEventDestroy((hipEvent_t)e);
@@ -1591,6 +1596,10 @@ int dmp_predict_end(dmp_ctx* ctx, float* d_coords, float* d_conf, void* stream) 
   // option "flex": the flex block behind that, from d_coords and - with "score_native" - the native entity (flex.hip).  The
   // solver's scratch and graphs are free: the last pass is behind us on this stream
   if (c->run.flex && (rc = flex(c, d_coords, L, d_native, d_conf + lay.flex.off, s))) return rc;
+  // option "msa_report": the report block behind that, from what unit 0 and the inverse's last unit left in msa_words, w and
+  // contacts (msareport.hip) - buffers of this context alone that nothing writes between the front end and here: the passes
+  // read the features from z0, a group's chain and its riders work in the vertical GRU's buffers
+  if (c->run.msa_report && (rc = msa_report(c, c->last_N, L, d_native, d_conf + lay.report.off, s))) return rc;
   // option "align_structure": the align block behind that, m and the structure's trace in it (align.hip)
   if (c->run.align && (rc = align_structure(c, d_coords, L, d_conf + lay.align.off, s))) return rc;
   // option "search_structures": the search block behind everything else, the entries' lengths and traces in it (align.hip)

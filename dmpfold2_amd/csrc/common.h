@@ -11,9 +11,9 @@
 
 // options "recycle_tol_mA", "emit_distmap", "score_native", "align_structure", "search_structures", "search_max_m", "search_chunk",
 // "search_refine", "score_map", "score_passes", "score_passes_chunk", "assign_ss", "restrain_milli", "restrain_cut_mA", "exposure", "exposure_chunk",
-// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment", "search_domains", "score_domains", "flex", "flex_cut_mA"
+// "domains", "domains_tau_milli", "domains_min_size", "domains_min_segment", "search_domains", "score_domains", "flex", "flex_cut_mA", "msa_report"
 struct TailOpts { int tol_mA = 0, emit = 0, score = 0, align = 0, search = 0, search_mm = 0, search_chunk = 0, search_refine = 0, smap = 0, passes = 0, passes_chunk = 0, ss = 0, restrain = 0, restrain_cut = 15000, exposure = 0, exposure_chunk = 0,
-                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10, search_domains = 0, score_domains = 0, flex = 0, flex_cut = 7300; };
+                  domains = 0, dom_tau = 250, dom_min_size = 40, dom_min_segment = 10, search_domains = 0, score_domains = 0, flex = 0, flex_cut = 7300, msa_report = 0; };
 
 namespace dmp {
 
@@ -120,11 +120,25 @@ __host__ __device__ inline FlexLayout flex_layout(int L) {
   const int res = FLEX_HEADER + 2 * FLEX_LEG, per = (2 + FLEX_MODES) * L;
   return {FLEX_HEADER, res, per, res + 2 * per};
 }
+//   | with "msa_report" = 1 or 2: the report block = MSAREPORT_HEADER floats | eight per-column arrays [L] | with 2 the DCA contact
+//   map [L][L], all of it out, between the flex block and the align block.
+constexpr int MSAREPORT_HEADER = 128, MSAREPORT_COLS = 8, MSAREPORT_HIST = 20, MSAREPORT_CLASSES = 76, MSAREPORT_N = 124;
+__host__ __device__ inline int64_t msareport_floats(int L, int value) {
+  return MSAREPORT_HEADER + MSAREPORT_COLS * (int64_t)L + (value == 2 ? (int64_t)L * L : 0);
+}
+// What "msa_report" ranks the DCA contact map by, ascending = strongest coupling first: an order-preserving map of the float's
+// bit pattern (negative floats reversed below the positive ones, so -0 < +0), inverted; every NaN last.
+__host__ __device__ inline unsigned coupling_rank_bits(float v) {
+  unsigned u;
+  __builtin_memcpy(&u, &v, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+}
 // The blocks in buffer order.  A block states where it begins, how many floats in front are the caller's input and where what
 // the library writes ends; a block whose option is off is empty (off = end).  `passes`: the rows R of the pass block, 0 =
 // none.  The align block's trailing input, whose length only the caller knows, lies behind `total`.
 struct ConfBlock { int64_t off, in, end; };                              // [off, off + in) in, [off + in, end) out
-struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, domsearch, domscore, flex, align; int64_t total; };
+struct ConfLayout { ConfBlock conf, map, info, score, smap, pass, ss, exposure, domains, domsearch, domscore, flex, report, align; int64_t total; };
 __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int passes) {
   ConfLayout lay;
   int64_t at = 0;
@@ -145,6 +159,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
   lay.domsearch = block(0, o.search_domains ? domsearch_layout(L, o.search).total : 0);
   lay.domscore = block(0, o.score_domains ? domscore_layout(L).total : 0);
   lay.flex = block(0, o.flex ? flex_layout(L).total : 0);
+  lay.report = block(0, o.msa_report ? msareport_floats(L, o.msa_report) : 0);
   lay.align = block(1, o.align ? align_layout(L).in : 0);
   lay.total = at;
   return lay;
@@ -152,7 +167,7 @@ __host__ __device__ inline ConfLayout conf_layout(int L, const TailOpts& o, int 
 // true for the floats a prediction writes: what becomes NaN when it latched a fault (api.hip)
 __host__ __device__ inline bool conf_is_out(const ConfLayout& lay, int64_t i) {
   auto out = [i](const ConfBlock& b) { return i >= b.off + b.in && i < b.end; };
-  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.domsearch) || out(lay.domscore) || out(lay.flex) || out(lay.align);
+  return out(lay.conf) || out(lay.map) || out(lay.info) || out(lay.score) || out(lay.smap) || out(lay.pass) || out(lay.ss) || out(lay.exposure) || out(lay.domains) || out(lay.domsearch) || out(lay.domscore) || out(lay.flex) || out(lay.report) || out(lay.align);
 }
 
 //   | with "search_structures" = K: the search block at B0 = the end of all that, the align block's trace included
@@ -426,6 +441,8 @@ struct dmp_ctx {
   dmp::Scratch domscore_ws;        // "score_domains": the tickets | per leg the domains' first rows and seeds, headers and counters, the packed
                                    // traces, the seed records (score.hip: domscore_scratch)
   dmp::Scratch flex_ws;              // "flex": nothing zeroed | the float32 matrix sigma I - Gamma of one leg, the degrees, the counts (flex.hip: flex_scratch)
+  dmp::Scratch report_ws;          // "msa_report": nothing zeroed (the counters are cleared on the stream) | the counters and histograms, the rows'
+                                   // four neighbour counts (msareport.hip: report_scratch)
   dmp::Scratch domsearch_ws;       // "search_domains": nothing zeroed | the per-domain tables of "search_refine", the counts, the residue list (align.hip:
                                    // DomainQuery); the slots are search_ws's
   int search_last_L = 0, search_last_mm = 0, search_last_C = 0;      // the last search's shape ("search_chunk_used", "search_wg_per_cu")
@@ -468,6 +485,9 @@ int gemm_f32(const GemmArgs& g, hipStream_t s);
 
 // msa.hip
 int msa_weights(dmp_ctx* c, const uint8_t* d_msa, int N, int L, float* d_w, hipStream_t s);
+// option "msa_report": the pair tiles of msa_weights once more over c->msa_words with the report's epilogue - d_nbr [4][N], zero
+// before the launch: the neighbour counts at 0.62, 0.8 and 0.9, then max over m != n of cnt[n][m]
+int msa_report_pairs(dmp_ctx* c, int N, int L, int* d_nbr, hipStream_t s);
 // dca.hip
 // lower_only: leave the 128 x 128 tiles above the diagonal uncomputed (spd_inverse never reads them)
 int cov_build(dmp_ctx* c, const uint8_t* d_msa, const float* d_w, int N, int L, float* d_cov,
@@ -687,7 +707,7 @@ int emit_distmap(dmp_ctx* c, const float* d_ca, int L, int passes_run, float* d_
 constexpr int SCORE_REC = 20;       // doubles per seed record (score.hip)
 // what a context of capacity max_L needs of each scratch (ScratchNeed above), stated beside the kernels that use it
 ScratchNeed score_native_need(int max_L), score_map_need(), align_structure_need(int max_L), score_passes_need(int max_L),
-    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L), search_domains_need(int max_L), score_domains_need(int max_L), flex_need(int max_L);
+    entity_need(int max_L), assign_ss_need(int max_L), exposure_need(int max_L), domains_need(int max_L), search_domains_need(int max_L), score_domains_need(int max_L), flex_need(int max_L), msa_report_need(int max_N);
 int score_native(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
 // option "score_passes" (score.hip): every recorded pass's trace scored against the native that score_native packed just
 // before, and its delta, into the pass block (R rows allocated, `rows` of them hold a pass)
@@ -695,6 +715,8 @@ constexpr int64_t PASS_BUDGET = (int64_t)DMP_PASSES_BUDGET_MIB << 20;
 int score_passes(dmp_ctx* c, int L, int R, int rows, float* d_block, hipStream_t s);
 // option "score_map" (mapscore.hip): best_dm against the native trace of the score block, into the map-score block
 int score_map(dmp_ctx* c, int L, const float* d_score_block, float* d_block, hipStream_t s);
+// the radix select of "score_map" with the key of "msa_report" (mapscore.hip): d_classes = the report block + 74
+int mapscore_select_couplings(const float* d_contacts, const float* d_score_block, float* d_classes, int L, hipStream_t s);
 constexpr int ALIGN_SURVIVORS = 16; // seeds of the gapless threading that the dynamic programme refines (align.hip)
 int align_kernel_attrs(dmp_ctx* c);   // once per device, at context creation
 int align_structure(dmp_ctx* c, const float* d_coords, int L, float* d_block, hipStream_t s);
@@ -727,6 +749,9 @@ const float* exposure_native_backbone(const dmp_ctx* c);             // the nati
 int domains(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
 // option "flex" (flex.hip): the Gaussian network model of both traces, into the flex block
 int flex(dmp_ctx* c, const float* d_coords, int L, const float* d_native, float* d_block, hipStream_t s);
+// option "msa_report" (msareport.hip): depth, conservation and the DCA contacts of the alignment the prediction ran on, from what
+// the front end left in c->msa_words, c->w and c->contacts, into the report block
+int msa_report(dmp_ctx* c, int N, int L, const float* d_native, float* d_block, hipStream_t s);
 // the backbone of a C-alpha trace alone, by the device function ca_to_backbone runs (coords.hip)
 int trace_to_backbone(const float* d_ca, int L, float* d_coords, hipStream_t s);
 // restrain: the final refinement with option "restrain_milli" on - the steps also pull towards c->best_dm (coords.hip)

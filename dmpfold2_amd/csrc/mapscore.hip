@@ -10,6 +10,8 @@
 //                    select - digit histograms in LDS, the class's pairs re-read once per 8-bit digit, the three digits of
 //                    the pair index only where the list ends inside a run of equal values - then h = the native contacts
 //                    among the keys <= that one.  The keys are unique, so ties are no separate path.
+//                    A template over what it ranks by: MsByDistance is this option's, MsByCoupling option "msa_report"'s
+//                    (mapscore_select_couplings, the DCA contact map strongest first).
 // No float atomics; every float64 sum has a fixed order: the same bits on every run.  Contraction is off (score_common.h) so
 // that the float32 contact test rounds every operation, as the definition says.
 #include "score_common.h"
@@ -202,8 +204,22 @@ __device__ inline bool ms_pair(const MsClass& k, int L, int idx, int& i, int& j)
   return i != r;
 }
 
+// What a select ranks by, and where its block keeps ln: the 32 bits in front of the pair index, ascending.  MsByDistance is
+// "score_map"'s (dm is not negative: its bits are its order; the block's offsets 0, 1 are n, ln and the classes follow at 2).
+// MsByCoupling is "msa_report"'s (msareport.hip): the DCA contact map DESCENDING - an order-preserving map of the float's
+// bits, inverted, every NaN last; the classes at the report block's offset 76 have "score_map"'s slots, so `out` is handed
+// over as the block + 74 and n, ln (124, 125) lie at 50, 51 of it.
+struct MsByDistance {
+  static constexpr int LN = 1;
+  __device__ static inline unsigned bits(float v) { return __float_as_uint(v); }
+};
+struct MsByCoupling {
+  static constexpr int LN = 51;
+  __device__ static inline unsigned bits(float v) { return coupling_rank_bits(v); }
+};
+
 // f(key, i, j) for every candidate of the class, MS_SEL_BATCH loads in flight per thread.  Every thread of the workgroup.
-template <class F>
+template <class K, class F>
 __device__ inline void ms_for_each(const MsClass& k, int L, const float* q, const float* dm, F f) {
   for (int base = threadIdx.x; base < k.total; base += MS_SEL_BATCH * MS_SEL_THREADS) {
     int ii[MS_SEL_BATCH], jj[MS_SEL_BATCH];
@@ -219,10 +235,11 @@ __device__ inline void ms_for_each(const MsClass& k, int L, const float* q, cons
     }
 #pragma unroll
     for (int u = 0; u < MS_SEL_BATCH; ++u)
-      if (ok[u]) f(((unsigned long long)__float_as_uint(v[u]) << 22) | (unsigned long long)(ii[u] * L + jj[u]), ii[u], jj[u]);
+      if (ok[u]) f(((unsigned long long)K::bits(v[u]) << 22) | (unsigned long long)(ii[u] * L + jj[u]), ii[u], jj[u]);
   }
 }
 
+template <class K>
 __global__ __launch_bounds__(MS_SEL_THREADS) void mapscore_select_kernel(MapScoreArgs a) {
   extern __shared__ float q[];           // 3L native coordinates
   __shared__ unsigned hist[256];
@@ -232,7 +249,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void mapscore_select_kernel(MapScor
   const int L = a.L, tid = threadIdx.x, c = blockIdx.x / 3, dq = blockIdx.x % 3;
   float* o = a.out + 2 + 12 * c;
   // N_c and ln as mapscore_count left them
-  const double Nc = (double)o[0], ln = (double)a.out[1];
+  const double Nc = (double)o[0], ln = (double)a.out[K::LN];
   const double kd = fmax(1.0, floor(ln / (dq == 0 ? 1.0 : (dq == 1 ? 2.0 : 5.0))));
   const unsigned t = (unsigned)fmin(kd, Nc);       // N_c < 2^24
   if (t == 0u) {                                   // uniform: an empty class
@@ -248,7 +265,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void mapscore_select_kernel(MapScor
     if (tid < 256) hist[tid] = 0u;
     __syncthreads();
     const unsigned long long prefix = sh_prefix;
-    ms_for_each(k, L, q, a.dm, [&](unsigned long long key, int, int) {
+    ms_for_each<K>(k, L, q, a.dm, [&](unsigned long long key, int, int) {
       if ((key >> (sh + nb)) == prefix) atomicAdd(&hist[(unsigned)(key >> sh) & ((1u << nb) - 1u)], 1u);
     });
     __syncthreads();
@@ -270,7 +287,7 @@ __global__ __launch_bounds__(MS_SEL_THREADS) void mapscore_select_kernel(MapScor
   }
   const unsigned long long thr = sh_prefix;
   unsigned mine = 0u;
-  ms_for_each(k, L, q, a.dm, [&](unsigned long long key, int i, int j) {
+  ms_for_each<K>(k, L, q, a.dm, [&](unsigned long long key, int i, int j) {
     mine += (key <= thr && ms_native_contact(q + 3 * i, q + 3 * j)) ? 1u : 0u;
   });
   for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
@@ -298,7 +315,20 @@ int score_map(dmp_ctx* c, int L, const float* d_score_block, float* d_block, hip
   a.sums = reinterpret_cast<double*>(c->map_ws.p + MS_WS_SUMS);
   hipLaunchKernelGGL(mapscore_count_kernel, dim3(mapscore_groups(L)), dim3(SC_THREADS), sizeof(float) * 3 * L, s, a);
   DMP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mapscore_select_kernel, dim3(12), dim3(MS_SEL_THREADS), sizeof(float) * 3 * L, s, a);
+  hipLaunchKernelGGL(mapscore_select_kernel<MsByDistance>, dim3(12), dim3(MS_SEL_THREADS), sizeof(float) * 3 * L, s, a);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// option "msa_report" (msareport.hip): the same select over the DCA contact map, strongest coupling first.  `d_classes`: the
+// report block + 74, N_c of every class and n, ln already in it (msareport_pairs_kernel and msareport_classes_kernel, in front of this on the stream).
+int mapscore_select_couplings(const float* d_contacts, const float* d_score_block, float* d_classes, int L, hipStream_t s) {
+  MapScoreArgs a{};
+  a.dm = d_contacts;
+  a.nat = d_score_block;
+  a.out = d_classes;
+  a.L = L;
+  hipLaunchKernelGGL(mapscore_select_kernel<MsByCoupling>, dim3(12), dim3(MS_SEL_THREADS), sizeof(float) * 3 * L, s, a);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

@@ -3,6 +3,7 @@
 //   w[n]     = 1 / #{m : float(cnt[n,m]) > float32(L*0.8)}
 // N^2*L byte compares; the alignment (<= 3000 x L bytes) lives in L2, tiles of 64x64 row
 // pairs are staged through LDS as packed words and compared four residues per instruction.
+// Option "msa_report" runs the same tiles once more at a prediction's end with a second, compile-time epilogue (msa_report_pairs).
 #include "common.h"
 
 namespace dmp {
@@ -38,9 +39,17 @@ __device__ __forceinline__ int eq_bytes(uint32_t a, uint32_t b) {
 constexpr int MT = 64;   // rows per tile side
 constexpr int KW = 16;   // words per K chunk
 
+// The tile loop and its two compile-time epilogues.  msa_count_kernel<false> is the weights': no argument behind `nbr`, the
+// arguments and the launch it always had.  msa_count_kernel<true, MsaReportCut> (option "msa_report", msareport.hip) takes the
+// report's thresholds as one more argument: per row the neighbour counts at the three of them into nbr[0 .. 3N) and the largest
+// count over m != n into nbr[3N .. 4N) (integer atomics).
+struct MsaReportCut { float t62, t80, t90; };
+__device__ __forceinline__ MsaReportCut msa_report_cut() { return {}; }
+__device__ __forceinline__ MsaReportCut msa_report_cut(const MsaReportCut& r) { return r; }
+template <bool REPORT, class... Cut>
 __global__ __launch_bounds__(256) void msa_count_kernel(const uint32_t* __restrict__ words, int N,
                                                         int Lw, int pad_matches, float id_min,
-                                                        int* __restrict__ nbr) {
+                                                        int* __restrict__ nbr, Cut... cut) {
   __shared__ uint32_t An[MT][KW + 1];
   __shared__ uint32_t Bm[MT][KW + 1];
   const int tid = threadIdx.x;
@@ -75,6 +84,38 @@ __global__ __launch_bounds__(256) void msa_count_kernel(const uint32_t* __restri
     }
     __syncthreads();
   }
+  if constexpr (REPORT) {
+    const MsaReportCut rep = msa_report_cut(cut...);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int n = n0 + tn * 4 + i;
+      int h62 = 0, h80 = 0, h90 = 0, top = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int m = m0 + tm + 16 * j;
+        if (m >= N) continue;
+        const int v = cnt[i][j] - pad_matches;
+        h62 += (float)v > rep.t62 ? 1 : 0;
+        h80 += (float)v > rep.t80 ? 1 : 0;
+        h90 += (float)v > rep.t90 ? 1 : 0;
+        if (m != n) top = v > top ? v : top;
+      }
+      for (int off = 8; off > 0; off >>= 1) {
+        h62 += __shfl_xor(h62, off, 16);
+        h80 += __shfl_xor(h80, off, 16);
+        h90 += __shfl_xor(h90, off, 16);
+        const int o = __shfl_xor(top, off, 16);
+        top = o > top ? o : top;
+      }
+      if (tm == 0 && n < N) {
+        if (h62) atomicAdd(&nbr[n], h62);
+        if (h80) atomicAdd(&nbr[N + n], h80);
+        if (h90) atomicAdd(&nbr[2 * N + n], h90);
+        if (top) atomicMax(&nbr[3 * N + n], top);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     int hits = 0;
@@ -104,10 +145,20 @@ int msa_weights(dmp_ctx* c, const uint8_t* d_msa, int N, int L, float* d_w, hipS
   DMP_LAUNCH_CHECK();
   DMP_HIP(hipMemsetAsync(c->nbr_count, 0, sizeof(int) * N, s));
   const float id_min = (float)((double)L * 0.8);
-  hipLaunchKernelGGL(msa_count_kernel, dim3(cdiv(N, MT), cdiv(N, MT)), dim3(256), 0, s,
+  hipLaunchKernelGGL(msa_count_kernel<false>, dim3(cdiv(N, MT), cdiv(N, MT)), dim3(256), 0, s,
                      c->msa_words, N, Lw, 4 * Lw - L, id_min, c->nbr_count);
   DMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(msa_recip_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, c->nbr_count, N, d_w);
+  DMP_LAUNCH_CHECK();
+  return DMP_OK;
+}
+
+// option "msa_report": the pair tiles once more over the words msa_weights packed, d_nbr [4][N] zero before the launch
+int msa_report_pairs(dmp_ctx* c, int N, int L, int* d_nbr, hipStream_t s) {
+  const int Lw = cdiv(L, 4);
+  const MsaReportCut rep{(float)((double)L * 0.62), (float)((double)L * 0.8), (float)((double)L * 0.9)};
+  hipLaunchKernelGGL((msa_count_kernel<true, MsaReportCut>), dim3(cdiv(N, MT), cdiv(N, MT)), dim3(256), 0, s,
+                     c->msa_words, N, Lw, 4 * Lw - L, 0.f, d_nbr, rep);
   DMP_LAUNCH_CHECK();
   return DMP_OK;
 }

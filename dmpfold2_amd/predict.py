@@ -429,7 +429,7 @@ def agree_options(rows):
     return Flags(all(emits), any(emits), *rows[0][1:])
 
 
-def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False, score_domains=False, flex=False):
+def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=False, score_domains=False, flex=False, msa_report=0):
     """What a prediction of length L needs on the GPU besides its alignment: (template CA trace (L, 3) or None, Outputs).
     The `d_conf` buffer behind the Outputs is laid out (score.Layout) for the options as the context holds them (`flags`) -
     the library cannot check it - and its input blocks are filled from `extras`: with "score_native" on the native trace (no
@@ -437,7 +437,8 @@ def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=
     which the library answers with NaN); with "search_structures" on the search block from the library's copy on the GPU.
     `domains`: option "domains" on (it travels beside `flags`, whose fields callers know by position); `search_domains`: option
     "search_domains" on - the buffer then holds the domain-search block in front of the align block; `score_domains`: option
-    "score_domains" on - the domain-score block behind that; `flex`: option "flex" on - the flex block behind that."""
+    "score_domains" on - the domain-score block behind that; `flex`: option "flex" on - the flex block behind that; `msa_report`: the value of option
+    "msa_report" - the report block behind that."""
     d_tpl = None
     if template_ca is not None:
         d_tpl = torch.as_tensor(template_ca, dtype=torch.float32).reshape(-1, 3).to(device).contiguous()
@@ -451,7 +452,7 @@ def _stage(device, L, template_ca, flags, extras, domains=False, search_domains=
     library = extras.library if flags.search else None
     align_m = None if ablock is None else (ablock.shape[0] - _score.align_floats(L, 0)) // 3
     lay = Layout(L, flags.emit, flags.score, flags.score_map, align_m, None if library is None else (len(library), library.rows),
-                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None, score_domains=score_domains, flex=flex,
+                 flags.max_L, flags.passes, domains=domains, search_domains=search_domains and library is not None, score_domains=score_domains, flex=flex, msa_report=msa_report,
                  **{key: getattr(flags, key) for key in OWN_BLOCK})
     floats = max(lay.total, lay._replace(distmap=flags.alloc).total)
     out = lay.split(torch.empty((floats,), dtype=torch.float32, device=device), coords)
@@ -689,6 +690,45 @@ class Engine:
         with self.with_flex(flex_cutoff):
             return self.predict(alnmat, *args, **asked)
 
+    @property
+    def msa_report_block(self):
+        """"msa_report": 128 + 8L floats (+ L*L with the map) - depth, conservation and DCA contacts of the last prediction's
+        alignment - or None."""
+        return self._last.out.msa_report_block
+
+    @property
+    def msa_report(self):
+        """The alignment report of the last prediction as score.unpack_msa_report gives it, with the prediction's confidences;
+        None if it ran without option "msa_report".  Synchronises with the GPU."""
+        block = self.msa_report_block
+        if block is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        return _score.unpack_msa_report(block, self._last.L, confs=self._last.out.confs[:self._last.L])
+
+    def set_msa_report(self, on, dca_map=False):
+        """Option "msa_report" on this engine, as it stands from now on: every prediction also reports on its alignment on the
+        GPU - Neff at three thresholds, gaps, copies, the histograms, per-column conservation, the strongest DCA coupling of
+        every column and, with a `native`, the DCA contact precisions; `dca_map` adds the raw L x L DCA contact map.  What a
+        call returns does not change, the result is in `msa_report` (score.unpack_msa_report) and `msa_report_block`."""
+        self.set_option("msa_report", (2 if dca_map else 1) if on else 0)
+
+    @contextlib.contextmanager
+    def with_msa_report(self, dca_map=False):
+        """Option "msa_report" set for the duration of the block, then as it was (`set_msa_report`)."""
+        before = self.get_option("msa_report")
+        try:
+            self.set_option("msa_report", 2 if dca_map else 1)
+            yield self
+        finally:
+            self.set_option("msa_report", before)
+
+    def predict_msa_report(self, alnmat, *args, dca_map=False, **asked):
+        """`predict` with option "msa_report" set for this call only: the same arguments, the same return value; the result is
+        in `msa_report` and `msa_report_block` afterwards."""
+        with self.with_msa_report(dca_map):
+            return self.predict(alnmat, *args, **asked)
+
     _score_domains = False           # set_score_domains / with_score_domains: the calls of this engine score every domain
 
     def set_score_domains(self, on):
@@ -832,7 +872,7 @@ class Engine:
             self._forget_last()
             domains = bool(self.get_option("domains"))
             d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, bool(self.get_option("search_domains")),
-                                bool(self.get_option("score_domains")), bool(self.get_option("flex")))
+                                bool(self.get_option("score_domains")), bool(self.get_option("flex")), self.get_option("msa_report"))
             self._last = _Last(out._replace(coords=None), L, library if search else None, out.coords if domains else None)
             milli = self.get_option("restrain_milli")
             if milli > 0:
@@ -1137,6 +1177,13 @@ class Pipeline:
             self.set_option("flex_cut_mA", mA)
         self.set_option("flex", 1 if on else 0)
 
+    def use_msa_report(self, on, dca_map=False):
+        """Option "msa_report" on every engine: targets submitted from now on get the report on their alignment (depth,
+        conservation, DCA contacts; with `set_score` on and a native given to `submit`, the DCA precisions; `dca_map`: the raw
+        map too); the report block (128 + 8L floats, + L*L; score.unpack_msa_report) is the attribute `msa_report_block` of what
+        `outputs_of` gives.  Idle pipeline only."""
+        self.set_option("msa_report", (2 if dca_map else 1) if on else 0)
+
     def set_align(self, on):
         """Option "align_structure" on every engine: targets submitted from now on are aligned with the `structure` given to
         `submit` (none given: m = 0, NaN in every out slot); idle pipeline only."""
@@ -1220,7 +1267,9 @@ class Pipeline:
             flex = agree([e.get_option("flex") for e in self.engines], "flex", "use_flex")
             if flex and len({e.get_option("flex_cut_mA") for e in self.engines}) > 1:
                 raise RuntimeError("the engines must agree on \"flex_cut_mA\" (whichever of them runs a target must give the same network); use use_flex")
-            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains, score_domains, flex)
+            msa_report = self.engines[0].get_option("msa_report")            # 0, 1 or 2: 2 is a larger block
+            agree([e.get_option("msa_report") == msa_report for e in self.engines], "msa_report", "use_msa_report")
+            d_tpl, out = _stage(self.device, L, template_ca, flags, extras, domains, search_domains, score_domains, flex, msa_report)
             # the stream that is current NOW produced d_msa (the caller's copy stream, say); the engine that takes the
             # target orders itself behind this point
             ready = torch.cuda.Event()
@@ -1544,17 +1593,29 @@ def aln_to_flex(input_file, *args, flex_cutoff=7.3, **asked):
     return _coords_tuple(call.arguments, flex=flex_cutoff)
 
 
-def _coords_tuple(call, domains=None, flex=None):
-    """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave; for `aln_to_flex`, its cutoff) ->
-    what it returns."""
+def aln_to_msa_report(input_file, *args, dca_map=False, **asked):
+    """`aln_to_coords` with the report on the alignment made on the GPU (option "msa_report": Neff at three thresholds, gaps,
+    copies, the histograms, per-column conservation and the strongest DCA coupling; with a `native` the DCA contact
+    precisions): the same arguments, and the dict of score.unpack_msa_report - made with the model's confidences and the
+    query, so it has the correlations and the consensus string - appended last of all.  `dca_map`: the raw L x L DCA contact
+    map too, as the dict's "dca_map"."""
+    call = inspect.signature(aln_to_coords).bind(input_file, *args, **asked)
+    call.apply_defaults()
+    return _coords_tuple(call.arguments, msa_report=bool(dca_map))
+
+
+def _coords_tuple(call, domains=None, flex=None, msa_report=None):
+    """The arguments of `aln_to_coords` (and, for `aln_to_domains`, what domains_options gave; for `aln_to_flex`, its cutoff; for
+    `aln_to_msa_report`, whether the map is wanted) -> what it returns."""
     v = SimpleNamespace(**call)
-    r, parse, _, _, flexed = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
+    r, parse, _, _, flexed, reported = _predict_file_with(domains, v.input_file, v.device, v.template, v.iterations, v.minsteps, v.weights_file, v.converge,
                                   v.native, v.native_chain, v.compare, v.compare_chain, v.search, distmap=v.return_distmap,
                                   scores=v.return_scores, alignment=v.return_alignment, hits=v.return_hits,
                                   map_scores=v.return_map_scores, pass_scores=v.return_pass_scores, ss=v.return_ss,
-                                  restrain=v.restrain, restrain_cutoff=v.restrain_cutoff, exposure=v.return_exposure, flex=flex)
+                                  restrain=v.restrain, restrain_cutoff=v.restrain_cutoff, exposure=v.return_exposure, flex=flex,
+                                  msa_report=msa_report)
     return (_as_tuple(r, **{k: call[k] for k in call if k.startswith("return_")}) + ((parse,) if domains is not None else ())
-            + ((flexed,) if flex is not None else ()))
+            + ((flexed,) if flex is not None else ()) + ((reported,) if msa_report is not None else ()))
 
 
 def _as_tuple(r, return_alnmat=False, return_distmap=False, return_scores=False, return_alignment=False, return_hits=False,
@@ -1586,9 +1647,10 @@ def _predict_file(input_file, device, template, iterations, minsteps, weights_fi
 
 def _predict_file_with(domains, input_file, device, template, iterations, minsteps, weights_file, converge, native, native_chain,
                        compare, compare_chain, search, distmap=False, scores=False, alignment=False, hits=False, map_scores=False,
-                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False, score_domains=False, flex=None):
+                       pass_scores=False, ss=False, restrain=None, restrain_cutoff=15.0, exposure=False, score_domains=False, flex=None, msa_report=None):
     """`_predict_file` -> (Prediction, the dict of score.unpack_domains or None, the domain search or None, the domain scores or
-    None, the dict of score.unpack_flex or None).  `flex`: None, or the contact cutoff in Angstrom - the prediction then runs
+    None, the dict of score.unpack_flex or None, the dict of score.unpack_msa_report or None).  `msa_report`: None, or whether
+    the DCA contact map is wanted too - the prediction then runs with option "msa_report" (Engine.with_msa_report).  `flex`: None, or the contact cutoff in Angstrom - the prediction then runs
     with option "flex" (Engine.with_flex).  `score_domains` (needs `native`): every domain is scored against the native (Engine.with_score_domains); the fourth
     part is then (the dict of Engine.domain_scores, the dict of score.unpack_domains of the same prediction, the raw block as an
     array).  `domains`: None, or
@@ -1628,7 +1690,8 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
         eng = get_engine(dev, cap, nseqs, weights_file=weights_file)
         with (eng.with_domains(domains[0] * 1e-3, *domains[1:]) if domains is not None else contextlib.nullcontext()), \
                 (eng.with_score_domains() if score_domains else contextlib.nullcontext()), \
-                (eng.with_flex(flex) if flex is not None else contextlib.nullcontext()):
+                (eng.with_flex(flex) if flex is not None else contextlib.nullcontext()), \
+                (eng.with_msa_report(msa_report) if msa_report is not None else contextlib.nullcontext()):
             out = eng.predict_checked(alnmat, template_ca, iterations, minsteps, converge=tol, distmap=bool(distmap),
                                       native=native, structure=compare, library=search, score_map=bool(map_scores),
                                       score_passes=bool(pass_scores), ss=bool(ss), restrain=restrain,
@@ -1641,6 +1704,10 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
         if exposure:
             torch.cuda.synchronize(eng.device)
             exposed = _score.unpack_exposure(eng.exposure_block, length, seq=alnmat[0])
+        reported = None
+        if msa_report is not None:
+            torch.cuda.synchronize(eng.device)
+            reported = _score.unpack_msa_report(eng.msa_report_block, length, confs=out[1][:length], seq=aln[0])
         return Prediction(out[0], out[1], alnmat, out[2] if distmap else None, ss=eng.ss if ss else None, exposure=exposed,
                           restrain=eng.restrain if restrain is not None else None,
                           map_scores=eng.map_scores if map_scores else None,
@@ -1648,7 +1715,7 @@ def _predict_file_with(domains, input_file, device, template, iterations, minste
                           hits=eng.hits if search is not None and hits else None,
                           scores=eng.scores if native is not None and scores else None,
                           alignment=eng.alignment if compare is not None and alignment else None), parse, domain_hits, domain_scores, \
-            (eng.flex if flex is not None else None)
+            (eng.flex if flex is not None else None), reported
 
 
 def pdb_text(coords, confs, alnmat):
@@ -1770,6 +1837,14 @@ def dmpfold_parser():
     parser.add_argument("--flex", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
     parser.add_argument("--flex-cutoff", type=float, default=argparse.SUPPRESS, metavar="A", help=argparse.SUPPRESS)
     parser.add_argument("--flex-file", type=str, default=argparse.SUPPRESS, metavar="FILE", help=argparse.SUPPRESS)
+    # --msa-report [--msa-report-file FILE] [--dca-map FILE.npy]: a report on the alignment made on the GPU (Neff at 62, 80 and
+    # 90 % identity, gaps, copies, histograms of identity, coverage and nearest neighbour, per-column conservation, the strongest
+    # DCA coupling per column; with --native the DCA contact precisions); the result goes to standard error, or to FILE, as one
+    # JSON line under the key "msa"; --dca-map (which implies --msa-report) saves the raw L x L DCA contact map.  The model on
+    # standard output is unchanged.  Hidden like --search-refine, for the same reason; README.md describes it.
+    parser.add_argument("--msa-report", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)
+    parser.add_argument("--msa-report-file", type=str, default=argparse.SUPPRESS, metavar="FILE", help=argparse.SUPPRESS)
+    parser.add_argument("--dca-map", type=str, default=argparse.SUPPRESS, metavar="FILE.npy", help=argparse.SUPPRESS)
     add_restrain_arguments(parser, "-r")
     return parser
 
@@ -1826,13 +1901,16 @@ def run_dmpfold(argv=None):
         parser.error("--score-domains needs --native")
     domains = domains_arguments(parser, args)
     flex = flex_arguments(parser, args)
-    r, parse, domain_hits, domain_scores, flexed = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
+    if hasattr(args, "msa_report_file") and not (hasattr(args, "msa_report") or hasattr(args, "dca_map")):
+        parser.error("--msa-report-file needs --msa-report")
+    msa_report = hasattr(args, "dca_map") if hasattr(args, "msa_report") or hasattr(args, "dca_map") else None
+    r, parse, domain_hits, domain_scores, flexed, reported = _predict_file_with(domains, args.input_file, args.device, args.template, args.iterations, args.minsteps,
                                   args.model_weights, args.converge, args.native, args.native_chain, args.compare,
                                   args.compare_chain, search, distmap=args.distmap is not None, scores=args.native is not None,
                                   alignment=args.compare is not None, hits=args.search is not None, map_scores=args.score_map,
                                   pass_scores=args.score_passes, ss=args.ss, restrain=args.restrain,
                                   restrain_cutoff=args.restrain_cutoff, exposure=args.exposure,
-                                  score_domains=hasattr(args, "score_domains"), flex=flex)
+                                  score_domains=hasattr(args, "score_domains"), flex=flex, msa_report=msa_report)
 
     def json_line(obj, path):
         """one JSON line to the file `path`, or to standard error without one"""
@@ -1865,6 +1943,10 @@ def run_dmpfold(argv=None):
         json_line({"domains": _score.domains_json(parse)}, getattr(args, "domains_file", None))
     if flexed is not None:
         json_line({"flex": _score.flex_json(flexed)}, getattr(args, "flex_file", None))
+    if reported is not None:
+        json_line({"msa": _score.msa_report_json(reported)}, getattr(args, "msa_report_file", None))
+        if hasattr(args, "dca_map"):
+            np.save(args.dca_map, np.asarray(reported["dca_map"], dtype=np.float32))
     if r.restrain is not None:
         json_line({"restrain": r.restrain}, None)
     sys.stdout.write(pdb_text(r.coords, r.confs, r.alnmat))

@@ -137,10 +137,11 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     fields, like `domains`) puts the domain-search block, sized from the K of `search`, between the domain block and the
     align block; `score_domains` (option "score_domains" on; an attribute likewise) puts the domain-score block behind that, in
     front of the align block; `flex` (option "flex" on; an attribute likewise) puts the flex block (48 + 20L, at `flex_off`)
-    behind that, in front of the align block."""
+    behind that, in front of the align block; `msa_report` (option "msa_report": 0, 1 or 2; an attribute likewise) puts the
+    report block (128 + 8L, with 2 + L*L, at `msa_report_off`) behind that, in front of the align block."""
 
     def __new__(cls, L, distmap=False, score=False, score_map=False, align_m=None, search=None, max_L=None, passes=None,
-                ss=False, exposure=False, domains=False, search_domains=False, score_domains=False, flex=False):
+                ss=False, exposure=False, domains=False, search_domains=False, score_domains=False, flex=False, msa_report=0):
         self = super().__new__(cls, int(L), bool(distmap), bool(score), bool(score_map), align_m,
                                None if search is None else (int(search[0]), int(search[1])), max_L,
                                None if passes is None else int(passes), bool(ss), bool(exposure))
@@ -148,20 +149,24 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
         self.search_domains = bool(search_domains)
         self.score_domains = bool(score_domains)
         self.flex = bool(flex)
+        self.msa_report = int(msa_report)
         return self
 
     domains = False                  # (of a Layout made by `_make`)
     search_domains = False
     score_domains = False
     flex = False
+    msa_report = 0
 
     def _replace(self, **changes):
         domains = changes.pop("domains", self.domains)
         search_domains = changes.pop("search_domains", self.search_domains)
         score_domains = changes.pop("score_domains", self.score_domains)
         flex = changes.pop("flex", self.flex)
+        msa_report = changes.pop("msa_report", self.msa_report)
         new = super()._replace(**changes)
         new.flex = bool(flex)
+        new.msa_report = int(msa_report)
         new.domains = bool(domains)
         new.search_domains = bool(search_domains)
         new.score_domains = bool(score_domains)
@@ -175,6 +180,8 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
             return domain_score_floats(self.L) if self.score_domains else 0
         if row is FLEX:
             return flex_floats(self.L) if self.flex else 0
+        if row is MSA_REPORT:
+            return msa_report_floats(self.L, self.msa_report == 2) if self.msa_report else 0
         value = getattr(self, row.arg)
         return 0 if value is None or value is False else row.floats(self.L, value)
 
@@ -194,6 +201,9 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
             if row.key == "domains" and self.floats(FLEX):               # (likewise: see FLEX)
                 yield FLEX, at
                 at += self.floats(FLEX)
+            if row.key == "domains" and self.floats(MSA_REPORT):         # (likewise: see MSA_REPORT)
+                yield MSA_REPORT, at
+                at += self.floats(MSA_REPORT)
         yield None, at
 
     def _begin(self, key):
@@ -209,6 +219,7 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
     domain_search_off = property(lambda s: s.domains_off + s.floats(BLOCK["domains"]))
     domain_score_off = property(lambda s: s.domain_search_off + s.floats(DOMAIN_SEARCH))
     flex_off = property(lambda s: s.domain_score_off + s.floats(DOMAIN_SCORES))
+    msa_report_off = property(lambda s: s.flex_off + s.floats(FLEX))                                        # Q0
     align_off = property(lambda s: s._begin("align"))                                                       # A0
     # the end of the align block as its writer allocated it ...
     align_end = property(lambda s: s._begin(None))
@@ -264,6 +275,11 @@ class Layout(namedtuple("Layout", "L distmap score score_map align_m search max_
         floats = self.floats(FLEX)
         return buf[self.flex_off:self.flex_off + floats] if floats else None
 
+    def msa_report_block(self, buf):
+        """The report block of a `d_conf` buffer as a view (128 + 8L floats, + L*L with `msa_report` 2), None with it off."""
+        floats = self.floats(MSA_REPORT)
+        return buf[self.msa_report_off:self.msa_report_off + floats] if floats else None
+
 
 # The positional functions that tests, tools and outside callers use: each one view of a `Layout`.
 def conf_floats(L, distmap=False, score=False, align_m=None, score_map=False):
@@ -308,10 +324,13 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
     domain_search_block = None       # with "search_domains": (400 + 2L) K floats; an attribute too, and never handed out by `public`
     domain_score_block = None        # with "score_domains": 1040 + 4L floats; likewise
     flex_block = None                # with "flex": 48 + 20L floats; likewise
+    msa_report_block = None          # with "msa_report": 128 + 8L (+ L*L) floats; likewise
 
-    def __new__(cls, *parts, domains_block=None, domain_search_block=None, domain_score_block=None, flex_block=None, **named):
+    def __new__(cls, *parts, domains_block=None, domain_search_block=None, domain_score_block=None, flex_block=None,
+                msa_report_block=None, **named):
         self = super().__new__(cls, *parts, **named)
         self.flex_block = flex_block
+        self.msa_report_block = msa_report_block
         self.domains_block = domains_block
         self.domain_search_block = domain_search_block
         self.domain_score_block = domain_score_block
@@ -322,8 +341,10 @@ class Outputs(namedtuple("Outputs", "coords confs distmap info score_block align
         domain_search_block = changes.pop("domain_search_block", self.domain_search_block)
         domain_score_block = changes.pop("domain_score_block", self.domain_score_block)
         flex_block = changes.pop("flex_block", self.flex_block)
+        msa_report_block = changes.pop("msa_report_block", self.msa_report_block)
         new = super()._replace(**changes)
         new.flex_block = flex_block
+        new.msa_report_block = msa_report_block
         new.domains_block = domains_block
         new.domain_search_block = domain_search_block
         new.domain_score_block = domain_score_block
@@ -1667,3 +1688,149 @@ FLEX = Block("flex", "flex", "flex_block", "flex", "flex", "48 + 20L",
              lambda L, on: flex_floats(L),
              lambda block, L, confs=None, domains=None, **_: unpack_flex(block, L, confs=confs, domains=domains),
              lambda fx, arrays=False, **_: flex_json(fx, arrays))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# option "msa_report" (include/dmpfold_hip.h): how deep the alignment was (Neff at three thresholds, gaps, copies, histograms
+# of identity, coverage and nearest neighbour), how conserved each column is, and the raw DCA contact map ranked against the
+# native by "score_map"'s definition.  Neff / L, the medians, the precisions and the correlations with the confidence are
+# formed here in float64.  A "gap" is a clamped code of 20: unknown residues and gaps merge, as the network sees them.
+# ---------------------------------------------------------------------------------------------------------------------
+MSA_HEADER = 128                     # floats in front of the per-column arrays of the report block
+MSA_COLS = 8                         # per-column arrays
+MSA_HIST = 20                        # bins of a histogram
+MSA_COLUMNS = ("gaps", "neff_col", "entropy", "cons", "cons_freq", "query_freq", "dca_max", "dca_partner")
+MSA_HISTS = ("hist_idq", "hist_cov", "hist_nn")
+MSA_NEFF = ("neff_62", "neff_80", "neff_90")
+MSA_CLASSES = MAP_CLASSES          # "score_map"'s classes
+
+
+def msa_report_floats(L, dca_map=False):
+    """Floats of the report block (option "msa_report") of a prediction of length L: 128 + 8L, with the map (value 2) + L*L."""
+    L = int(L)
+    return MSA_HEADER + MSA_COLS * L + (L * L if dca_map else 0)
+
+
+def pack_msa_report(L, header, columns, dca_map=None):
+    """A report block from its parts: `header` a dict with N, the three neff, gap_cells, copies, query_gaps, the three histograms
+    (20 each), classes (four dicts of candidates, native_contacts, h (3,), t (3,); or None), n, ln, has_dca, has_native;
+    `columns` (8, L); `dca_map` (L, L) or None - the inverse of the raw views of `unpack_msa_report` (tests, restatements)."""
+    L = int(L)
+    b = np.zeros(msa_report_floats(L, dca_map is not None), dtype=np.float32)
+    b[0], b[1] = header["N"], L
+    b[2:5] = [header[k] for k in MSA_NEFF]
+    b[5], b[6], b[7] = header["gap_cells"], header["copies"], header["query_gaps"]
+    for k, name in enumerate(MSA_HISTS):
+        b[16 + MSA_HIST * k:16 + MSA_HIST * (k + 1)] = header[name]
+    for c, cls in enumerate(header.get("classes") or ()):
+        o = b[76 + 12 * c:88 + 12 * c]
+        o[0], o[1], o[2:5], o[5:8] = cls["candidates"], cls["native_contacts"], cls["h"], cls["t"]
+    b[124], b[125] = header.get("n", 0), header.get("ln", 0)
+    b[126], b[127] = header["has_dca"], header["has_native"]
+    b[MSA_HEADER:MSA_HEADER + MSA_COLS * L] = np.asarray(columns, dtype=np.float32).reshape(-1)
+    if dca_map is not None:
+        b[MSA_HEADER + MSA_COLS * L:] = np.asarray(dca_map, dtype=np.float32).reshape(-1)
+    return b
+
+
+def hist_median(hist):
+    """The median of a 20-bin histogram of shares as the middle of the bin that holds the (count + 1) // 2-th row; NaN if empty."""
+    h = np.asarray(hist, dtype=np.int64)
+    total = int(h.sum())
+    if total <= 0:
+        return float("nan")
+    b = int(np.searchsorted(np.cumsum(h), (total + 1) // 2))
+    return (b + 0.5) / float(MSA_HIST)
+
+
+def _spearman(x, y):
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    ok = (x == x) & (y == y)
+    return _pearson(_ranks(x[ok]), _ranks(y[ok])) if ok.sum() >= 2 else float("nan")
+
+
+def unpack_msa_report(block, L, confs=None, seq=None):
+    """A report block (128 + 8L floats, or + L*L; array or tensor) -> dict: N, L, neff_62 / neff_80 / neff_90, gap_cells, copies,
+    query_gaps, hist_idq / hist_cov / hist_nn (20 ints each), has_dca, has_native, the eight per-column arrays of MSA_COLUMNS
+    (gaps, cons and dca_partner as ints, -1 for NaN), the raw `header` (128,) and `columns` (8, L) and, formed here in float64: neff_per_L and neff_per_sqrtL (of neff_80),
+    gap_share, median_identity, median_coverage, median_nearest.  With has_native and has_dca: n, ln and `classes` - per class of
+    MSA_CLASSES candidates, native_contacts, h, t, precision (h / t) and enrichment (precision over native_contacts /
+    candidates) for L/1, L/2, L/5 (NaN where a denominator is 0).  `confs` (the per-residue confidence) adds Pearson's and
+    Spearman's correlation of it with neff_col, entropy and dca_max as r_conf / rho_conf dicts; `seq` (the query as a string)
+    adds cons_seq, the consensus as letters ('-' in an all-gap column).  With the map (value 2) `dca_map` (L, L).  A block the
+    library answered with NaN (a latched fault) gives zero counts."""
+    L = int(L)
+    b = _host(block)
+    if b.ndim != 1 or b.shape[0] not in (msa_report_floats(L), msa_report_floats(L, True)):
+        raise ValueError(f"a report block of length {L} has {msa_report_floats(L)} or {msa_report_floats(L, True)} floats, got shape {tuple(b.shape)}")
+    out = {"N": _whole(b[0]), "L": _whole(b[1])}
+    out.update({name: float(b[2 + k]) for k, name in enumerate(MSA_NEFF)})
+    out.update(gap_cells=_whole(b[5]), copies=_whole(b[6]), query_gaps=_whole(b[7]))
+    for k, name in enumerate(MSA_HISTS):
+        out[name] = _count(b[16 + MSA_HIST * k:16 + MSA_HIST * (k + 1)])
+    out["has_dca"], out["has_native"] = _whole(b[126]) > 0, _whole(b[127]) > 0
+    cols = b[MSA_HEADER:MSA_HEADER + MSA_COLS * L].reshape(MSA_COLS, L)
+    out["header"], out["columns"] = b[:MSA_HEADER], cols                   # (the raw floats: the batch's npz arrays)
+    for k, name in enumerate(MSA_COLUMNS):
+        v = np.asarray(cols[k])
+        out[name] = np.where(v == v, v, -1.0).astype(np.int64) if name in ("gaps", "cons", "dca_partner") else v
+    out["neff_per_L"] = out["neff_80"] / L if L else float("nan")
+    out["neff_per_sqrtL"] = out["neff_80"] / float(np.sqrt(L)) if L else float("nan")
+    cells = out["N"] * L
+    out["gap_share"] = out["gap_cells"] / cells if cells else float("nan")
+    out["median_identity"], out["median_coverage"] = hist_median(out["hist_idq"]), hist_median(out["hist_cov"])
+    out["median_nearest"] = hist_median(out["hist_nn"])
+    if out["has_native"] and out["has_dca"]:
+        out["n"], out["ln"] = _whole(b[124]), float(b[125])
+        out["classes"] = {}
+        for c, name in enumerate(MSA_CLASSES):
+            o = b[76 + 12 * c:88 + 12 * c]
+            cand, nat = _whole(o[0]), _whole(o[1])
+            h, t = [_whole(v) for v in o[2:5]], [_whole(v) for v in o[5:8]]
+            prec = [hh / tt if tt else float("nan") for hh, tt in zip(h, t)]
+            base = nat / cand if cand else float("nan")
+            out["classes"][name] = {"candidates": cand, "native_contacts": nat, "h": h, "t": t, "precision": prec,
+                                    "enrichment": [p / base if base == base and base > 0 else float("nan") for p in prec]}
+    if confs is not None:
+        cf = _host(confs).reshape(-1)[:L]
+        out["r_conf"] = {k: _pearson(cf, out[k]) for k in ("neff_col", "entropy", "dca_max")}
+        out["rho_conf"] = {k: _spearman(cf, out[k]) for k in ("neff_col", "entropy", "dca_max")}
+    if seq is not None:
+        out["seq"] = str(seq)
+        out["cons_seq"] = "".join(AA1[c] if 0 <= c < 20 else "-" for c in out["cons"])
+    if b.shape[0] == msa_report_floats(L, True):
+        out["dca_map"] = b[MSA_HEADER + MSA_COLS * L:].reshape(L, L)
+    return out
+
+
+def msa_report_json(rep, arrays=False):
+    """`unpack_msa_report` as a JSON-ready dict (the key "msa" of `dmpfold --msa-report` and of `dmpfold-batch --msa-report`):
+    the depth figures, the histograms, the flags, the classes and correlations that are there; with `arrays` also the eight
+    per-column arrays as lists.  The map is never part of it (it goes to a .npy file).  NaN becomes None."""
+    js = {"N": int(rep["N"]), "L": int(rep["L"])}
+    js.update({k: _num(rep[k]) for k in MSA_NEFF + ("neff_per_L", "neff_per_sqrtL", "gap_share", "median_identity", "median_coverage",
+                                                     "median_nearest")})
+    js.update({k: int(rep[k]) for k in ("gap_cells", "copies", "query_gaps")})
+    js.update({k: [int(v) for v in rep[k]] for k in MSA_HISTS})
+    js["has_dca"], js["has_native"] = bool(rep["has_dca"]), bool(rep["has_native"])
+    js["mean_entropy"], js["mean_neff_col"] = _num(_mean(rep["entropy"])), _num(_mean(rep["neff_col"]))
+    if "classes" in rep:
+        js["n"], js["ln"] = int(rep["n"]), _num(rep["ln"])
+        js["classes"] = {name: {k: ([_num(x) for x in v] if isinstance(v, list) else int(v)) for k, v in cls.items()}
+                         for name, cls in rep["classes"].items()}
+    for k in ("r_conf", "rho_conf"):
+        if k in rep:
+            js[k] = {name: _num(v) for name, v in rep[k].items()}
+    if "cons_seq" in rep:
+        js["cons_seq"] = rep["cons_seq"]
+    if arrays:
+        for name in MSA_COLUMNS:
+            js[name] = [(int(v) if v >= 0 else None) if name in ("gaps", "cons", "dca_partner") else _num(v) for v in rep[name]]
+    return js
+
+
+# The report block of option "msa_report": likewise no row of BLOCKS; it lies behind the flex block, in front of the align block.
+MSA_REPORT = Block("msa_report", "msa_report", "msa_report_block", "msa_report", "msa_report", "128 + 8L (+ L*L)",
+                   lambda L, value: msa_report_floats(L, value == 2),
+                   lambda block, L, confs=None, seq=None, **_: unpack_msa_report(block, L, confs=confs, seq=seq),
+                   lambda rep, arrays=False, **_: msa_report_json(rep, arrays))

@@ -575,7 +575,7 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * the final, refined C-alpha trace (d_coords[:, 1], n = L rows); the coordinates, the confidences, the map extension and
  * the score block do not change by a bit.  THE d_conf ARGUMENT MUST THEN HOLD A0 + 25 + 2L + 3m FLOATS, A0 = THE END OF
  * WHAT THE OTHER OPTIONS GIVE (L, + L*L + 3 with "emit_distmap", + 5L + 24 with "score_native", + 64 + L with "score_map",
- * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains", + 1040 + 4L with "score_domains", + 48 + 20L with "flex"; the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
+ * + 16 + 8R with "score_passes", + 32 + 8L with "assign_ss", + 32 + 16L with "exposure", + 32 + 2L + 256 with "domains", + (400 + 2L) K with "search_domains", + 1040 + 4L with "score_domains", + 48 + 20L with "flex", + 128 + 8L (+ L*L) with "msa_report" = 1 (2); the library cannot check the size): there sits the ALIGN BLOCK.  THE CALLER WRITES ITS TWO INPUTS BEFORE THE CALL, as with the score block.
  * Every output lies at an offset that does not depend on m; the variable-length input comes last.  Offsets relative to A0:
  *   0                    in   m, the number of rows of the structure, as a float
  *   1                    out  n_ali: aligned pairs
@@ -862,7 +862,74 @@ void dmp_ctx_destroy(dmp_ctx* ctx);
  * Measured cost of dmp_predict_end with the option on (profiles/flex.txt; the collapsed model of profiles/exposure.txt, a whole
  * folded-like native): the model's leg adds 0.45 ms at L = 96, 1.56 ms at 300, 9.4 ms at 1000 and 41.2 ms at 2048, the native's leg
  * 0.45, 1.50, 9.3 and 41.0 ms more; one dmp_eigh_top8 of the same order takes 0.45, 1.53, 9.2 and 41.1 ms in the same run: a leg is
- * 0.98 to 1.01 of it. */
+ * 0.98 to 1.01 of it.
+ * "msa_report" (0, 1 or 2, default 0; any other value: DMP_ERR_ARG): A REPORT ON THE ALIGNMENT THE PREDICTION RAN ON - how deep it
+ * was, how conserved each column is, and what the raw DCA contact map says - the third leg beside "score_native" (the model) and
+ * "score_map" (the network's map): did the alignment carry the signal at all?  Read when a prediction begins and held for it.  With
+ * it 0 nothing is launched, read, written or allocated and every offset is what it was.  With it 1 THE d_conf ARGUMENT MUST HOLD
+ * 128 + 8L MORE FLOATS AT THE END OF THE FLEX BLOCK (of whatever block lies last in front of the align block, with those behind it
+ * off), WITH IT 2 128 + 8L + L*L: there sits the REPORT BLOCK at Q0, all of it outputs, and A0 and B0 move behind it; nothing in
+ * front of it moves.  It needs no other option; the DCA precisions need "score_native".
+ * A "gap" below is a clamped code of 20: UNKNOWN RESIDUES (20, 21) AND GAPS MERGE, exactly as the network and the reweighting see
+ * them.  a_nl is the clamped code of row n, column l; cnt[n,m] = #{l : a_nl == a_ml}, the reference's count (predict.py:32-37),
+ * GAPS MATCHING GAPS.  Every integer is stored as a float; all are below 2^24 (N L <= 3000 x 2048).  Offsets relative to Q0:
+ *   0, 1        N, L
+ *   2, 3, 4     neff_62, neff_80, neff_90: neff_t = sum_n 1 / #{m : float(cnt[n,m]) > float32((double)L * t)}, a float64 sum in
+ *               a fixed order, rounded once.  neff_80 uses the very expression of the sequence weights, so its neighbour counts
+ *               are the weights' own and neff_80 is the sum of the weights.
+ *   5           gap cells in the whole alignment
+ *   6           rows that are an exact copy of another row (max over m != n of cnt[n,m] == L)
+ *   7           gap columns of row 0 (the query)
+ *   8 .. 15     zero
+ *   16 .. 35    hist_idq[20]: rows by identity to the query, idq_n = #{l : a_nl == a_0l < 20} over #{l : a_0l < 20} - HERE GAPS DO
+ *               NOT MATCH - bin = min(19, 20 num / den) in integer division; row 0 included; den == 0: bin 0
+ *   36 .. 55    hist_cov[20]: rows by coverage #{l : a_nl < 20} / L, the same binning
+ *   56 .. 75    hist_nn[20]: rows by nearest neighbour, max over m != n of cnt[n,m] / L, the same binning; N == 1: all zero
+ *   76 + 12c    c = 0 .. 3, the classes of "score_map": N_c | native contacts | h_{c,1}, h_{c,2}, h_{c,5} | t_{c,1}, t_{c,2}, t_{c,5}
+ *               | four zeros
+ *   124, 125    n (present native rows), ln
+ *   126         has_dca: 1 where N > 1 (a single sequence has no covariance features and no contact map)
+ *   127         has_native: 1 where "score_native" is on
+ *   128 + kL    k = 0 .. 7, per column l:
+ *     0  gaps[l]         #{n : a_nl == 20}
+ *     1  neff_col[l]     sum_n w_n [a_nl < 20], w the float32 sequence weights, a float64 sum in a fixed order, rounded once
+ *     2  entropy[l]      -sum_a p_a ln p_a over the 20 letters, p_a = the weighted frequency among the non-gap rows, float64,
+ *                        rounded once; 0 where neff_col is 0
+ *     3  cons[l]         the letter with the largest RAW count, ties to the lowest code; NaN in an all-gap column
+ *     4  cons_freq[l]    p of that letter (NaN likewise)
+ *     5  query_freq[l]   p of the query's letter; NaN where the query has a gap
+ *     6  dca_max[l]      the strongest coupling of the column: the entry contacts[l][j], |j - l| >= 6, that comes first in the
+ *                        order of the ranked lists below - its bits
+ *     7  dca_partner[l]  the lowest j that attains it
+ *                        6 and 7 are NaN where has_dca is 0 or no such j exists
+ *   128 + 8L    with value 2: contacts[L][L], the DCA contact map the stem was given (channel 441 of fast_dca, network.py:10), bit
+ *               for bit; all zeros when N == 1.
+ * DCA against the native.  Rows and pairs, the candidates, the classes, the native-contact test, k_d, t_{c,d} and ln are those of
+ * "score_map" above, word for word ("Rows and pairs", "Contacts", "Ranked lists"), with the predicted map replaced by the DCA
+ * contact map and the order inverted: the candidates of a class are ordered by the key (r(contacts[i][j]), i, j) ascending, r an
+ * order-preserving map of the float's bit pattern to an unsigned integer, INVERTED - the strongest coupling first, +0 in front of
+ * -0, every NaN last, ties to the lower (i, j) - and h_{c,d} = the native contacts among the first t_{c,d}.  Only contacts[i][j]
+ * with i < j is read.  "score_map" and "emit_distmap" are not needed.  Without "score_native", or with N == 1, offsets 76 .. 125
+ * are zero and the two flags say why.  The precisions h / t and their enrichment over native contacts / N_c are formed on the host.
+ * A prediction that latched a device-side fault has NaN in every float of the block.
+ * THE REFERENCE HAS NO SUCH REPORT.  THE IDENTITY COUNTS ARE THE REFERENCE'S, GAPS MATCHING GAPS, EXCEPT idq.  NOBODY HAS COMPARED
+ * Neff WITH ANOTHER PROGRAM'S (hhblits, CCMpred and plmDCA count identity over aligned letters and weight differently) OR THE
+ * DCA PRECISIONS WITH ANOTHER EVALUATOR'S; the definition above is the only one (tests/msa_report_ref.py restates it in NumPy).
+ * Launches (csrc/msareport.hip), all in dmp_predict_end behind "flex" and in front of "align_structure", from what the front end
+ * left on the device - the packed clamped alignment, the weights and the contact map are buffers of the context alone that nothing
+ * writes between the front end and the end (the passes read the features from the stem's output; a group's vertical-GRU chain and
+ * its riders work in buffers of their own): a memset of the counters; the weights' pair kernel once more with a second, compile-
+ * time epilogue (msa_count_kernel<true, MsaReportCut>: 64 x 64 row pairs, packed words through LDS; per row the three neighbour counts and the
+ * largest count over the other rows, integer atomics) - with the option off the weights' own instantiation and launch are what they
+ * were; msareport_row_kernel (one wave per row, histograms in LDS, one integer atomic per bin and workgroup); msareport_col_kernel
+ * (one workgroup per column: raw and weighted 21-bin counts, every thread its own float64 LDS column, then a fixed tree);
+ * msareport_dca_kernel (one workgroup per row of the map); with a native msareport_pairs_kernel and msareport_classes_kernel (N_c,
+ * native contacts, n, ln) and "score_map"'s radix select instantiated with the coupling key (mapscore_select_kernel<MsByCoupling>;
+ * "score_map"'s own instantiation is instruction for instruction what it was); msareport_finish_kernel (one workgroup: the Neff
+ * sums through the fixed tree, the header); with value 2 one device-to-device copy of the map.  No float atomics: the same bits on
+ * every run; dmp_predict_end stays asynchronous.  Scratch of its own: 320 + 16 max_N bytes, allocated when the option first becomes
+ * non-zero on a context and counted in "device_mib"; an allocation failure is an error of dmp_ctx_set_option and leaves the option
+ * as it was.  Measured cost: profiles/msa_report.txt. */
 int dmp_ctx_set_option(dmp_ctx* ctx, const char* name, int value);
 /* Current value of an option of dmp_ctx_set_option ("conv_f32_exact" reads as conv_mode == 1). */
 int dmp_ctx_get_option(const dmp_ctx* ctx, const char* name, int* h_value);
